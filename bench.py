@@ -2,12 +2,20 @@
 """bench.py -- WDBX vector_search hot path on MI355X: queries/sec, latency, HBM roofline.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload t|c2|c3|c1] [--scaling strong|weak]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one single-vector query = one full scan of the (rank's) corpus + top-k
 (+ the cross-rank exchange for N > 1).  Inputs (corpus, queries) are resident in HBM
 before the timed region.  The timed region enqueues exactly K steps on the shard's
 stream and is bracketed by barrier + device synchronisation; the maximum over ranks
 is reported by rank 0 as ONE JSON line.
+
+A plain run only sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, and the roofline of
+the dominant kernel from the HIP events of the timed region).  `--full` adds every other leg: the single-client latency
+leg, the oracle parity check of timed queries, the CPU baseline, the other BASELINE configs, the WDBX.vector_search
+wall-clock leg, the live rocprofv3 traffic passes and, for N > 1, the per-query-exchange leg, the sharded check and the
+weak-scaling extra.  `--dump-outputs DIR` writes the last timed step's results after the timed region, as a caller
+receives them: DIR/ids.npy (float64 row ids) and DIR/scores.npy (float32 scores), one row per query of the step.
 
 Workloads (BASELINE.json configs / BASELINE.md section 3):
   t   10M x 384 fp32, cosine, top-10   north-star target row (default)
@@ -133,7 +141,24 @@ def parse():
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not measure roofline.traffic with rocprofv3 --pmc child passes (falls back to profiles/hbm_traffic.json)")
     ap.add_argument("--traffic-steps", type=int, default=24, help="queries (batches) per rocprofv3 child pass")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg besides the timed steps (latency, parity, CPU baseline, other configs, facade, "
+                         "live traffic; N > 1: per-query exchange, sharded check, weak scaling); the --no-* options apply to these")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's ids (float64) and scores (float32) as DIR/ids.npy and DIR/scores.npy")
+    a = ap.parse_args()
+    if a.dump_outputs and a.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
+    return a
+
+
+def dump_outputs(out_dir, ids, scores):
+    """The last timed step's results as a caller receives them: row ids (exact in float64) and fp32 scores, one row per
+    query of the step."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "ids.npy", np.asarray(ids, np.int64).astype(np.float64))
+    np.save(d / "scores.npy", np.asarray(scores, np.float32))
 
 
 def host_rows(ix, want_rows):
@@ -769,10 +794,12 @@ def main_group(args):
     res_idx, res_score = grp.results(args.steps, k) if args.steps > 0 else (np.zeros((1, k), np.int64), np.zeros((1, k), np.float32))
     for ix in shards:
         ix.profile(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res_idx[-1:], res_score[-1:])
     # second timed leg: the same K queries as K calls of ONE query, back to back, no host synchronisation between them --
     # one exchange (all-gather / device copies) + merge PER QUERY
     per_query = None
-    if args.steps > 0:
+    if args.full and args.steps > 0:
         grp.synchronize()
         x1 = grp.stat("exchanges")
         t1 = time.perf_counter()
@@ -805,14 +832,14 @@ def main_group(args):
 
     # latency: one query per call, results on the host (single client)
     lat = []
-    for i in range(args.latency_queries):
+    for i in range(args.latency_queries if args.full else 0):
         t1 = time.perf_counter()
         grp.search_resident(i, 1, k)
         grp.results(1, k)
         lat.append(time.perf_counter() - t1)
     # host-side cost of one group call: how long the enqueue alone takes (all shards' threads, exchange, merge launch)
     enq = []
-    for i in range(min(50, args.latency_queries)):
+    for i in range(min(50, args.latency_queries) if args.full else 0):
         grp.synchronize()
         t1 = time.perf_counter()
         grp.search_resident(i, 1, k)
@@ -821,7 +848,7 @@ def main_group(args):
 
     # the merged answer must equal a shard-by-shard host merge of the shards' own blocking searches
     sharded_check = None
-    if args.steps > 0:
+    if args.full and args.steps > 0:
         try:
             ncheck = min(4, args.steps)
             dq = _native.DeviceBuffer(shards[0], (args.warmup + ncheck) * shards[0].pitch * 4)
@@ -842,7 +869,7 @@ def main_group(args):
     # strong scaling: also BASELINE configs[4]-style WEAK scaling (every GPU keeps the workload's full row count:
     # 8 x 10M = 80M rows at N=8) as an extra on the same group, outside the timed region
     weak_extra = None
-    if n_gpus > 1 and args.scaling == "strong":
+    if args.full and n_gpus > 1 and args.scaling == "strong":
         try:
             wspans = ranges("weak")
             for ix, (b, e) in zip(shards, wspans):
@@ -872,7 +899,7 @@ def main_group(args):
         ix.close()
 
     facade = None
-    if not args.no_facade and not args.rows:
+    if args.full and not args.no_facade and not args.rows:
         facade = facade_latency(wl, k, n_queries=100, num_shards=n_gpus, devices=devices)
 
     out = {
@@ -922,6 +949,7 @@ def main_group(args):
         "rccl": {"rccl_nranks": info["rccl_nranks"], "shards": info["shards"], "communicator": "ncclCommInitAll (one process)"},
         "weak_scaling_extra": weak_extra,
         "timed_region_profiled": not args.no_profile,
+        "full": args.full,
         "facade_latency_ms": facade,
         "cpu_baseline": None,  # (timed at N = 1 only)
     }
@@ -1040,11 +1068,13 @@ def main():
     else:
         assert np.all(np.diff(res_score, axis=1) >= 0), "distances not ascending"
     assert res_idx.max() < total_rows
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res_idx[-batch:], res_score[-batch:])
 
     # N > 1, second timed leg: the same K queries as K calls of ONE query each, back to back, no host synchronisation
     # between them: one all-gather + merge PER QUERY (every rank issues the same sequence of collectives)
     per_query = None
-    if grouped and batch == 1 and args.steps > 0:
+    if args.full and grouped and batch == 1 and args.steps > 0:
         barrier()
         x1 = ix.get_option("exchanges")
         t1 = time.perf_counter()
@@ -1059,7 +1089,7 @@ def main():
 
     # latency: one query at a time, host-synchronised (single client)
     lat = []
-    for i in range(args.latency_queries if batch == 1 else 0):
+    for i in range(args.latency_queries if args.full and batch == 1 else 0):
         t1 = time.perf_counter()
         run(i, 1)
         ix.synchronize()
@@ -1068,7 +1098,7 @@ def main():
 
     # N > 1: every rank must hold the same merged answer, and it must equal the host-side exchange
     sharded_check = None
-    if grouped and args.steps > 0:
+    if args.full and grouped and args.steps > 0:
         try:
             ncheck = min(4, args.steps)
             qh = dq.download(np.float32, (nq_total, ix.pitch))[args.warmup:args.warmup + ncheck, : wl["dim"]]
@@ -1089,7 +1119,7 @@ def main():
     # row count: 8 x 10M = 80M rows at N=8) as an extra, outside the timed region.  Same communicator: the shard is
     # refilled with this rank's range of the larger corpus and re-based (wdbx_index_comm_set_row_base).
     weak_extra = None
-    if grouped and args.scaling == "strong" and batch == 1:
+    if args.full and grouped and args.scaling == "strong" and batch == 1:
         try:
             ix.clear()
             wbegin = rank * wl["rows"]
@@ -1177,9 +1207,10 @@ def main():
         "rccl": comm_info,  # {"rccl_nranks", "rccl_rank", "row_base"} from ncclCommCount / ncclCommUserRank; null at N = 1
         "weak_scaling_extra": weak_extra,
         "timed_region_profiled": not args.no_profile,
+        "full": args.full,
     }
     out["config"]["rccl_nranks"] = comm_info["rccl_nranks"] if comm_info else None
-    if rank == 0 and world == 1 and not grouped and args.workload == "t" and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and not grouped and args.workload == "t" and not args.no_other_configs:
         # the other BASELINE configs, measured briefly in the same run (they are parity-test cases, not the
         # bench line; exact parity for each lives in tests/test_gpu_parity.py)
         out["other_configs"] = {
@@ -1196,9 +1227,9 @@ def main():
                                                    "achieved": fp["achieved_GBps"], "algorithmic_bytes_per_launch": local_rows * wl["dim"] * 4,
                                                    "queries_per_s": fp["queries_per_s"]}
     c4_verify = (out.get("other_configs", {}).get("c4") or {}).pop("_verify", None)
-    if rank == 0 and world == 1 and not grouped and batch == 1 and not args.no_facade and not args.rows:
+    if args.full and rank == 0 and world == 1 and not grouped and batch == 1 and not args.no_facade and not args.rows:
         out["facade_latency_ms"] = facade_latency(wl, k)
-    if rank == 0 and world == 1 and not grouped and (args.verify > 0 or not args.no_cpu_baseline):
+    if args.full and rank == 0 and world == 1 and not grouped and (args.verify > 0 or not args.no_cpu_baseline):
         rows_h, whole = host_rows(ix, wl["rows"])
         if args.verify > 0 and args.steps > 0:
             nver = min(args.verify, args.steps * batch)
@@ -1211,7 +1242,7 @@ def main():
         del rows_h
     elif rank == 0:
         out["cpu_baseline"] = None
-    if rank == 0 and not grouped and not args.no_live_traffic:
+    if args.full and rank == 0 and not grouped and not args.no_live_traffic:
         # roofline.traffic of this very command line: two PMC child passes (children, never an exec), after every timed leg so
         # that nothing they do to clocks or temperatures touches a timed region
         live, live_err = live_traffic(args, batch)

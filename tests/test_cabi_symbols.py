@@ -63,7 +63,7 @@ def test_code_object_targets_gfx950(lib_path):
     assert "gfx950" in out
 
 
-def test_no_gpu_means_loud_failure_not_fallback(lib_path):
+def test_no_gpu_means_loud_failure_not_fallback(lib_path, tmp_path):
     import os
 
     from wdbx_amd import _native
@@ -76,7 +76,7 @@ def test_no_gpu_means_loud_failure_not_fallback(lib_path):
     from wdbx_amd import WDBX
 
     with pytest.raises(_native.HipBackendError):
-        WDBX(vector_dimension=4, data_dir=str(ROOT / "gpurun_out" / "_nogpu"), enable_plugins=False)
+        WDBX(vector_dimension=4, data_dir=str(tmp_path / "_nogpu"), enable_plugins=False)
 
 
 def test_product_never_imports_the_oracle():

@@ -6,12 +6,13 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 COMMON = ["--rows", "400000", "--steps", "24", "--warmup", "6", "--latency-queries", "8", "--no-facade", "--no-other-configs",
-          "--no-cpu-baseline"]
+          "--no-cpu-baseline", "--full"]
 
 
 def _run(cmd, env=None, timeout=300):
@@ -47,6 +48,35 @@ def test_plain_index_line():
     # algorithmic bytes, never much more)
     assert 0 < r["traffic"] < 1.1 * r["algorithmic_bytes_per_launch"]
     assert r["traffic_detail"]["launches"] >= 2 and r["traffic_detail"]["units"] == 12   # (a round of queries is ONE grid on a small shard)
+
+
+def test_plain_line_times_only_the_steps_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline figures and nothing that takes a leg of its own; --dump-outputs writes
+    the last timed query's top-k as a caller receives it, the same on every run of the same command line."""
+    import wdbx_oracle as O
+
+    rows, steps, warmup, k = 100_000, 24, 6, 10
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--rows", str(rows), "--steps", str(steps), "--warmup", str(warmup)]
+    d = _run(cmd + ["--dump-outputs", str(tmp_path / "a")])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == steps and d["warmup"] == warmup and d["full"] is False and d["value"] > 0
+    assert abs(d["ms_per_step"] * d["value"] / 1e3 - 1.0) < 1e-6 and d["roofline"]["launches_timed"] > 0
+    assert d["latency_ms"]["p50"] is None and d["cpu_baseline"] is None and "traffic_detail" not in d["roofline"]
+    assert not any(key in d for key in ("parity", "other_configs", "facade_latency_ms"))
+    ids, scores = np.load(tmp_path / "a" / "ids.npy"), np.load(tmp_path / "a" / "scores.npy")
+    assert ids.dtype == np.float64 and scores.dtype == np.float32 and ids.shape == scores.shape == (1, k)
+    # the last timed step is query warmup + steps - 1 of the synthetic query stream
+    q = O.normalize_rows_fast(O.synth_rows(O.SEED_QUERY, warmup + steps - 1, 1, 384))[0].astype(np.float64)
+    s = np.concatenate([O.normalize_rows_fast(O.synth_rows(O.SEED_CORPUS, r0, min(20_000, rows - r0), 384)) @ q
+                        for r0 in range(0, rows, 20_000)])
+    got = ids[0].astype(np.int64)
+    assert len(set(got.tolist())) == k and got.min() >= 0 and got.max() < rows
+    np.testing.assert_allclose(scores[0], np.sort(s)[::-1][:k], atol=1e-5, rtol=0)   # the best k scores ...
+    np.testing.assert_allclose(s[got], scores[0], atol=1e-5, rtol=0)                 # ... of the rows it names
+    _run(cmd + ["--dump-outputs", str(tmp_path / "b")])
+    for name in ("ids.npy", "scores.npy"):
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name))
 
 
 def test_live_traffic_can_be_switched_off_and_never_costs_the_line():

@@ -1,10 +1,10 @@
 #!/bin/bash
-# The driver's default command line with its wall clock: `python bench.py` -> <out>/bench_default.json (+ .err, wall_seconds.txt)
+# The full bench run with its wall clock: `python bench.py --full` -> <out>/bench_default.json (+ .err, wall_seconds.txt)
 # and a short digest on stdout.     usage (on the GPU box): tools/gpu/bench_default.sh <outdir> [bench.py arguments...]
 O=$1; shift
 mkdir -p $O
 SECONDS=0
-python bench.py "$@" > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full "$@" > $O/bench_default.json 2> $O/bench_default.err
 rc=$?
 echo "rc=$rc wall_seconds=$SECONDS" | tee $O/wall_seconds.txt
 python - $O/bench_default.json <<'PY'

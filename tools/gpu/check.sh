@@ -10,7 +10,7 @@ echo "gpu suite rc=$?"; tail -4 "$OUT/gputests.log"
 python __graft_entry__.py smoke > "$OUT/smoke.log" 2>&1; echo "smoke rc=$?"; tail -1 "$OUT/smoke.log"
 python tools/preflight_multigpu.py --devices 0,0 --out "$OUT/preflight_one_gpu.json" > "$OUT/preflight_one_gpu.log" 2>&1
 echo "preflight rc=$?"; tail -7 "$OUT/preflight_one_gpu.log"
-python bench.py --gpus 2 --devices 0,0 --steps 40 --warmup 5 --rows 2500000 --no-facade > "$OUT/bench_group2_one_gpu.json" 2> "$OUT/bench_group2_one_gpu.err"
+python bench.py --gpus 2 --devices 0,0 --steps 40 --warmup 5 --rows 2500000 --no-facade --full > "$OUT/bench_group2_one_gpu.json" 2> "$OUT/bench_group2_one_gpu.err"
 echo "group bench rc=$?"; tail -2 "$OUT/bench_group2_one_gpu.err"
 python - "$OUT/bench_group2_one_gpu.json" <<'PY'
 import json, sys

@@ -7,9 +7,9 @@ set -o pipefail
 O=${1:-gpurun_out/group_rehearsal}; STEPS=${2:-400}; mkdir -p $O
 for rows in 10000000 5000000 2500000 1250000; do
   timeout -k 10 200 python bench.py --rows $rows --steps $STEPS --warmup 40 --no-other-configs --no-cpu-baseline --no-facade --no-live-traffic > $O/index_$rows.json 2> $O/index_$rows.err || exit 1
-  timeout -k 10 200 python bench.py --mode group --rows $rows --steps $STEPS --warmup 40 --no-facade > $O/group_$rows.json 2> $O/group_$rows.err || exit 1
+  timeout -k 10 200 python bench.py --mode group --rows $rows --steps $STEPS --warmup 40 --no-facade --full > $O/group_$rows.json 2> $O/group_$rows.err || exit 1
   WDBX_BENCH_FORCE_GROUP=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 timeout -k 10 300 \
-      python bench.py --gpus 1 --rows $rows --steps $STEPS --warmup 40 --no-cpu-baseline --no-facade --no-other-configs --no-live-traffic > $O/launcher_$rows.json 2> $O/launcher_$rows.err || exit 1
+      python bench.py --gpus 1 --rows $rows --steps $STEPS --warmup 40 --no-cpu-baseline --no-facade --no-other-configs --no-live-traffic --full > $O/launcher_$rows.json 2> $O/launcher_$rows.err || exit 1
 done
 python3 - $O <<'PY'
 import json, sys

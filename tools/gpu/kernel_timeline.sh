@@ -2,8 +2,8 @@
 # Kernel timeline of a Python program: start / gap-to-previous / duration of the LAST <n> kernels of the run, from a rocprofv3
 # kernel trace.  Shows where a lone query's time goes: kernels vs launch gaps vs the host's share (wall clock minus the span).
 #   usage (on the GPU box): tools/gpu/kernel_timeline.sh <outdir> <n> <script.py> [arguments...]
-#   e.g.  tools/gpu/kernel_timeline.sh gpurun_out/r04/c2_timeline 24 bench.py --workload c2 --steps 8 --warmup 8 --latency-queries 30 \
-#             --no-cpu-baseline --no-facade --no-other-configs --no-live-traffic --verify 0
+#   e.g.  tools/gpu/kernel_timeline.sh out/c2_timeline 24 bench.py --workload c2 --steps 8 --warmup 8 --latency-queries 30 \
+#             --full --no-cpu-baseline --no-facade --no-other-configs --no-live-traffic --verify 0
 #         tools/gpu/kernel_timeline.sh gpurun_out/r04/lone_blocking_1m 12 tools/probes/lone_blocking.py 1000000
 set -o pipefail
 export TMPDIR=/tmp

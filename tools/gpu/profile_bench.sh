@@ -9,7 +9,7 @@ O=$1; shift
 mkdir -p $O
 O=$(cd $O && pwd)   # (absolute: the passes run from /tmp)
 cd /tmp
-ARGS="--no-other-configs --no-cpu-baseline --no-facade --no-live-traffic $*"
+ARGS="--full --no-other-configs --no-cpu-baseline --no-facade --no-live-traffic $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o t -- python3 $R/bench.py $ARGS > $O/bench_under_rocprof.json 2> $O/stats.err
 cp $(find $O/stats -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -o t -- python3 $R/bench.py $ARGS > $O/fetch.json 2> $O/fetch.err

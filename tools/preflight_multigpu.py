@@ -229,7 +229,7 @@ def stage_per_process(devs, limit):
             env["WDBX_BENCH_FORCE_GROUP"] = "1"
         cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(world), "--steps", "16", "--warmup", "4",
                "--rows", str(ROWS_PER_SHARD * world), "--latency-queries", "8", "--no-cpu-baseline", "--no-facade",
-               "--no-other-configs", "--no-live-traffic", "--verify", "0"]
+               "--no-other-configs", "--no-live-traffic", "--verify", "0", "--full"]
         procs.append(subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     rec = {"world": world, "ranks": []}
     status = "ok"
