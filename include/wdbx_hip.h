@@ -13,6 +13,8 @@
  *   _normalize_vector at add          indexing.py:851-856,886,939 wdbx_index_add(normalize=1)
  *   hnswlib replace_vector            indexing.py:374, :431, :552 wdbx_index_set_rows
  *   index.search(q[1,d], k)           indexing.py:1013 (and :490) wdbx_index_search
+ *   faiss IndexFlat range_search      (never reached: the reference  wdbx_index_range_search
+ *                                      post-filters a top-k, vector_store.py:337-342)
  *   self.next_index / index.ntotal    indexing.py:998, :1005      wdbx_index_size
  *   _create_index() on clear          indexing.py:1098            wdbx_index_clear
  *   per-shard loop + list.sort merge  vector_store.py:323-345     wdbx_index_search_sharded_device
@@ -125,6 +127,29 @@ int wdbx_index_search_masked(wdbx_index* idx, const float* queries, int nq, int 
  * refused with WDBX_E_INVALID instead of over-read.  What the Python binding calls. */
 int wdbx_index_search_masked_n(wdbx_index* idx, const float* queries, int nq, int k, int normalize_queries,
                                const uint32_t* mask_words, uint64_t mask_word_count, int64_t* out_idx, float* out_score);
+
+/* ---- range search: every row within a similarity, no k ----------------------- */
+/* every row whose score reaches thresholds[q] (cosine/IP: score >= t; L2: squared distance <= t), exact fp32,
+ * per query sorted like wdbx_index_search; replaces faiss' IndexFlat range_search, which the reference never reaches
+ * (it only post-filters a top-k, vector_store.py:337-342).  out_offsets[nq + 1] always receives the true counts
+ * (CSR: query i's results are [out_offsets[i], out_offsets[i+1])).  out_rows / out_scores hold the results only when
+ * out_offsets[nq] <= capacity (otherwise the call still returns WDBX_OK, their first `capacity` slots may have been used as
+ * scratch, and the caller retries with capacity = out_offsets[nq]; capacity 0 = count only).  mask_words may be NULL (then
+ * mask_word_count is ignored); a mask is checked against the row count under the handle's lock, as in
+ * wdbx_index_search_masked_n.
+ *   Result set: the live rows (passing the mask) whose fp32 score reaches the threshold; a NaN score never does (removed
+ *   rows, rows with a NaN element).  A NaN threshold is WDBX_E_INVALID; +-inf are allowed (-inf on cosine: every non-NaN row).
+ *   Scores: computed with exactly the arithmetic of the candidates' re-scoring on the top-k paths, whichever path selects
+ *   the rows -- bit-identical to what wdbx_index_search returns for the same rows where that takes the u8 selection scan.
+ *   L2 scores are the positive squared distances.
+ *   Order: (score descending, row ascending) for cosine, (distance ascending, row ascending) for L2.
+ *   Paths: from option "range_min_rows" (131 072) rows, with scan_shadow = 2 and a row shape the u8 selection scan serves,
+ *   a selection scan over the u8 shadow keeps every row whose quantisation upper bound reaches the threshold and the kept
+ *   rows are scored exactly; otherwise every row is scored exactly in fp32 (get_option "last_range_path": 2 / 0).
+ *   The call holds the handle's mutex to its end.  Nothing of a call's results stays in the handle. */
+int wdbx_index_range_search(wdbx_index* idx, const float* queries, int nq, const float* thresholds,
+                            int normalize_queries, const uint32_t* mask_words, uint64_t mask_word_count,
+                            uint64_t capacity, uint64_t* out_offsets, int64_t* out_rows, float* out_scores);
 
 /* ---- device-resident path (inputs already in HBM; asynchronous) -------------- */
 int wdbx_device_alloc(wdbx_index* idx, uint64_t bytes, void** out_dev_ptr);
@@ -275,10 +300,11 @@ int wdbx_index_profile_read(wdbx_index* idx, uint64_t* scan_launches, double* sc
 int wdbx_index_probe_read(wdbx_index* idx, int nontemporal, int blocks, int reps, double* out_ms_per_pass);
 /* tuning knobs (name/value); unknown names return WDBX_E_INVALID.  Settable: scan_lanes, scan_blocks, scan_nt,
  * scan_blocked, scan_generic, scan_force_ragged, exchange_batch, lds_lists, merge_fast (1: merges whose keys fit the registers are ranked there, default; 0: always the list walk), scan_one_grid (1: a round of several queries on the fp32 scan over a corpus of at most 1 GiB is one grid with a row per query, default; 0: a launch per query), poll_done (1: a blocking call of up to 32 queries whose chain ends in a final merge polls a word that kernel writes into the mapped staging slot, default; 0: always waits on its event), zero_copy, wg_merge, select_min_k,
- * scan_shadow (2 u8 selection scan / 1 bf16 tiles / 0 fp32 scan), scan8_wgs, single_min_rows, gemm_bf16 (tile family
+ * scan_shadow (2 u8 selection scan / 1 bf16 tiles / 0 fp32 scan; range search: 2 u8 selection, below 2 the fp32 range scan), scan8_wgs, single_min_rows,
+ * range_min_rows (rows from which a range search takes the u8 selection scan, default 131 072), gemm_bf16 (tile family
  * 3/2/1/0 as above), gemm_ct, gemm_l2, gemm_l2_i8, gemm8_variant, gemm8_refine (1: second selection stage of the i8 tiles, default), batch_repair, scan8_per_query, scan8_sample4 (1: a round's sample pass serves 3-4 queries per workgroup when the sample is too large for the L2s; 2: always; 0: never), gemm_min_queries, gemm_min_rows, gemm_min_work (below gemm_min_rows: the tiles from queries x rows >= this, default 800000; 0: never), gemm_sample_div, group_bounds.
  * get_option also answers the read-only names: last_gemm_family (0/1/2/3: what the last batch ran on),
- * last_single_path (0 fp32 scan / 1 bf16 tiles / 2 u8 selection scan), last_sample_qn (queries per workgroup of the last u8 sample launch: 1, 3 or 4), last_batch_repaired, shadow_rows + shadow_bytes (bf16 copy),
+ * last_single_path (0 fp32 scan / 1 bf16 tiles / 2 u8 selection scan), last_range_path (0 fp32 range scan / 2 u8 selection + exact filter), last_sample_qn (queries per workgroup of the last u8 sample launch: 1, 3 or 4), last_batch_repaired, shadow_rows + shadow_bytes (bf16 copy),
  * shadow8_rows + shadow8_bytes (u8 copy), shadowg_rows + shadowg_bytes (group-scaled i8 copy), group_bounds_active,
  * exchanges (all-gather + merge steps this handle's per-rank communicator has enqueued), device_bytes_resident (every device
  * allocation of the handle: fp32 rows, shadow copies and their tables, scratch). */

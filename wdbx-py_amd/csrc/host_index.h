@@ -126,6 +126,16 @@ struct wdbx_index {
   u64* d_pairs = nullptr;        // the tile waves' candidate (query, row) pairs and how many each wave produced
   uint32_t* d_pair_count = nullptr;
   size_t pairs_bytes = 0, pair_count_bytes = 0;
+  // range search (wdbx_index_range_search): per-query key buffers of the selection candidates and of the results, their
+  // counters ([0, 64) candidates, [64, 128) results) and thresholds ([0, 64) exact, [64, 128) selection scale); the per-query
+  // capacities grow to the exact count after an overflow and stay there
+  u64* d_rcand = nullptr;
+  u64* d_rkeys = nullptr;
+  uint32_t* d_rcnt = nullptr;
+  float* d_rthr = nullptr;
+  size_t rcand_bytes = 0, rkeys_bytes = 0, rcnt_bytes = 0, rthr_bytes = 0;
+  uint32_t range_cand_cap = 16384, range_out_cap = 16384;
+  int last_range_path = 0;     // 0 fp32 range scan, 2 u8 selection scan + exact filter (what the last range search ran on)
   // profiling
   bool profile = false;
   EventPool scan_ev, merge_ev, gemm_ev, sample_ev;
@@ -136,7 +146,7 @@ struct wdbx_index {
           opt_gemm8_refine = 1, opt_scan8_sample4 = 1, opt_gemm_l2 = 1, opt_gemm_l2_i8 = 1, opt_force_ragged = 0,
           opt_gemm_ct = 0, opt_wg_merge = 1, opt_zero_copy = 1, opt_lone_host_select = 1, opt_lds_lists = 0,
           opt_merge_fast = 1, opt_poll_done = 1, opt_scan_one_grid = 1, opt_select_min_k = 200, opt_gemm_min_nq = 4, opt_gemm_min_rows = 65536, opt_gemm_min_work = 800000,
-          opt_gemm_sample_div = 0;
+          opt_gemm_sample_div = 0, opt_range_min_rows = 131072;
 };
 
 struct DeviceGuard {
@@ -877,6 +887,32 @@ static scan8_fn pick_scan8_sample4(int L, int QPL) {
     case 643: return scan8_sample4_kernel<64, 3, METRIC>;
   }
   return nullptr;
+}
+
+// ---- range search (wdbx_index_range_search) -------------------------------------------------------
+// the u8 selection applies as for a lone top-k query (u8_single_eligible's shape and size rules; k plays no part)
+static bool range_u8_eligible(const wdbx_index* ix) {
+  if (ix->opt_scan_shadow < 2) return false;
+  const Scan8Shape* sh = scan8_shape((uint32_t)ix->dim);
+  if (!sh || (uint64_t)sh->pieces * 16 * 10 > (uint64_t)ix->pitch * 4 * 6) return false;
+  return (int64_t)ix->n >= ix->opt_range_min_rows;
+}
+
+typedef void (*range_fn)(RangeArgs);
+// lanes per row = the row's quads rounded up to a power of two (up to 64), and the unrolled loads per lane (0: the loop)
+template <int METRIC>
+static range_fn pick_range_scan(uint32_t pitch4) {
+  if (pitch4 <= 1) return range_scan_kernel<METRIC, 1, 1>;
+  if (pitch4 <= 2) return range_scan_kernel<METRIC, 2, 1>;
+  if (pitch4 <= 4) return range_scan_kernel<METRIC, 4, 1>;
+  if (pitch4 <= 8) return range_scan_kernel<METRIC, 8, 1>;
+  if (pitch4 <= 16) return range_scan_kernel<METRIC, 16, 1>;
+  if (pitch4 <= 32) return range_scan_kernel<METRIC, 32, 1>;
+  if (pitch4 <= 64) return range_scan_kernel<METRIC, 64, 1>;
+  if (pitch4 <= 128) return range_scan_kernel<METRIC, 64, 2>;
+  if (pitch4 <= 192) return range_scan_kernel<METRIC, 64, 3>;
+  if (pitch4 <= 256) return range_scan_kernel<METRIC, 64, 4>;
+  return range_scan_kernel<METRIC, 64, 0>;
 }
 
 // squared fp32 norms of the rows added since they were last computed (the L2 selection paths' |c|^2 term), and their

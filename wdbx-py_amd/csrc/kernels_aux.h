@@ -121,8 +121,42 @@ __global__ void tau_margin_kernel(float* tau, const float* queries, uint32_t pit
   }
 }
 
-// every kept candidate of every query is re-scored exactly in fp32, one wave per candidate: cosine by the
-// inner product, L2 by the direct form sum (c - q)^2 (no cancellation); its key becomes (score, row)
+// THE exact fp32 score of one row (rescore_kernel, the range kernels of kernels_range.h): lane j of a group of P lanes
+// accumulates quads j, j + P, j + 2P, ... with accum<METRIC> (f4 lanes, in that order), folds them as (x + y) + (z + w) and the
+// group's sums meet in the __shfl_xor tree P/2 .. 1.  Cosine: inner product; L2: the direct form sum (c - q)^2 (no
+// cancellation), returned negated ("higher is better").  Every lane of the group gets a sum; lane j = 0's is THE score.
+//   P = 64 is rescore_kernel's form.  P < 64 (rows of pitch4 <= P quads, 64 / P rows per wave) is bit-identical to it: lane j
+//   holds at most the one quad j, the lanes a 64-lane group would add on top hold none, so the offsets 32 .. P of the full tree
+//   would only add exact zeros to lane 0 (at most turning a -0 into +0, which every key normalises with + 0.0f anyway).
+//   NI > 0 (pitch4 <= NI * P): the same accumulation unrolled -- all NI loads issued before the first fma, no loop, so a caller
+//   that scores several rows at once gets every row's loads in flight together.  NI = 0: the loop, for any pitch4.
+template <int METRIC, int P = 64, int NI = 0, bool NT = false>
+__device__ __forceinline__ float exact_score(const f4* cp, const f4* qp, uint32_t pitch4, uint32_t j) {
+  f4 acc = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (NI == 0) {
+    for (uint32_t i = j; i < pitch4; i += P) acc = accum<METRIC>(acc, ld16<NT>(cp + i), qp[i]);
+  } else {
+    f4 c[NI], qv[NI];
+#pragma unroll
+    for (int t = 0; t < NI; ++t) {
+      const uint32_t i = j + (uint32_t)t * P;
+      if (i < pitch4) {
+        c[t] = ld16<NT>(cp + i);
+        qv[t] = qp[i];
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < NI; ++t)
+      if (j + (uint32_t)t * P < pitch4) acc = accum<METRIC>(acc, c[t], qv[t]);
+  }
+  float s = (acc.x + acc.y) + (acc.z + acc.w);
+  for (int o = P / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (METRIC == WDBX_METRIC_L2) s = -s;
+  return s;
+}
+
+// every kept candidate of every query is re-scored exactly in fp32, one wave per candidate (exact_score); its key becomes
+// (score, row)
 // host_keys / host_count (a lone blocking query): the exact keys and the candidate count also go to mapped host memory,
 // where the caller ranks them after its synchronisation (no merge launch)
 template <int METRIC>
@@ -137,12 +171,7 @@ __global__ __launch_bounds__(256) void rescore_kernel(const f4* rows, uint32_t p
   for (uint32_t j = blockIdx.x * 4 + (threadIdx.x >> 6); j < have; j += gridDim.x * 4) {
     u64* slot = cand + (size_t)q * cap + j;
     const uint32_t row = key_row(*slot);
-    const f4* cp = rows + (size_t)row * pitch4;
-    f4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (uint32_t i = lane; i < pitch4; i += 64) acc = accum<METRIC>(acc, cp[i], qp[i]);
-    float s = (acc.x + acc.y) + (acc.z + acc.w);
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (METRIC == WDBX_METRIC_L2) s = -s;
+    const float s = exact_score<METRIC>(rows + (size_t)row * pitch4, qp, pitch4, (uint32_t)lane);
     if (lane == 0) {
       const u64 key = (s == s) ? make_key(s + 0.0f, row) : 0ull;
       *slot = key;

@@ -164,6 +164,60 @@ __device__ __forceinline__ f4 accum(f4 acc, f4 c, f4 q) {
   return acc;
 }
 
+// wave-aggregated append (range search): every lane with keep set writes its key to out[pos], pos = *count + its rank among
+// the keeping lanes (__ballot + mbcnt); ONE atomicAdd per wave for all of them.  The counter keeps counting past cap (only
+// the stores stop), so it ends at the exact total.  Call with the whole wave (the ballot must see every lane).
+__device__ __forceinline__ void wave_append(bool keep, u64 key, u64* out, uint32_t* count, uint32_t cap, int lane) {
+  const u64 bal = __ballot(keep);
+  if (!bal) return;
+  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+  const int leader = __ffsll((long long)bal) - 1;
+  uint32_t base = 0;
+  if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(bal));
+  base = (uint32_t)__shfl((int)base, leader);
+  if (keep && base + rank < cap) out[base + rank] = key;
+}
+
+// the same append staged per wave in LDS: keys collect in a 128-key stage (ballot + mbcnt positions) and go out 64 at a time,
+// ONE atomicAdd and one 512-byte store per 64 keys; finish() writes the rest.  For a scan in which only a few lanes of a pass
+// keep a row (one lane per row group), wave_append alone would still cost an atomic per few rows -- on ONE counter per query,
+// which all CUs contend for.  The stage is the wave's own: only a barrier of the wave orders its LDS traffic.
+struct WaveStage {
+  u64* stage;     // 128 keys of LDS, this wave's
+  uint32_t fill;  // keys staged (wave-uniform, < 64 between pushes)
+  __device__ __forceinline__ void push(bool keep, u64 key, u64* out, uint32_t* count, uint32_t cap, int lane) {
+    const u64 bal = __ballot(keep);
+    if (!bal) return;
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+    if (keep) stage[fill + rank] = key;
+    fill += (uint32_t)__popcll(bal);
+    if (fill >= 64) flush(64, out, count, cap, lane);
+  }
+  __device__ __forceinline__ void finish(u64* out, uint32_t* count, uint32_t cap, int lane) {
+    if (fill) flush(fill, out, count, cap, lane);
+  }
+  __device__ __forceinline__ void flush(uint32_t n, u64* out, uint32_t* count, uint32_t cap, int lane) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(count, n);
+    base = (uint32_t)__shfl((int)base, 0);
+    const uint32_t l = (uint32_t)lane;
+    if (l < n && base + l < cap) out[base + l] = stage[l];
+    const uint32_t rest = fill - n;  // (< 64) moved to the front
+    const u64 v = l < rest ? stage[n + l] : 0ull;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (l < rest) stage[l] = v;
+    fill = rest;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+};
+
 // "higher is better" ranking value from the accumulated lane-group sum
 template <int METRIC>
 __device__ __forceinline__ float rank_value(float s) {

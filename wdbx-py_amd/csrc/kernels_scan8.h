@@ -15,6 +15,9 @@
 //            One launch serves all queries of a round (grid.y): they sample the same rows, which then come
 //            from L2 / Infinity Cache instead of HBM.
 //   PHASE 1 (all rows): every row whose UPPER bound w + m reaches tau is appended to the candidate buffer.
+//   PHASE 2 (range search, all rows): as PHASE 1 with the caller's threshold per query (tau[blockIdx.y], no PHASE 0), and the
+//            appends staged per wave in LDS (WaveStage: one atomic per 64 kept rows, not one per kept row), so a loose
+//            threshold that keeps millions of rows does not queue them on one counter.
 // No true top-k row can be missed; rescore_kernel then computes the candidates' exact fp32 scores from the
 // fp32 rows and merge_kernel ranks those.  L2 selects by 2 w - |c|^2 (cached fp32 norms; bound
 // 2 m + 3e-5 |c|^2).  Rows with an infinite element carry a NaN scale: never sampled, always candidates.  Rows with
@@ -153,6 +156,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     a.cand += (size_t)blockIdx.y * a.cap;
     a.count += blockIdx.y;
     float thr;
+    if constexpr (PHASE == 2) {  // range search: the caller's fixed threshold, mapped to the selection scale
+      thr = a.tau[0];
+    } else
     if (a.tau_keys) {  // (tau_n <= 1024 keys: 16 ordered score values per lane, searched bit by bit by every wave itself)
       uint32_t tv[16];
 #pragma unroll
@@ -167,6 +173,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     const uint32_t groups = (a.n_rows + R - 1) / R;
     const uint32_t W = gridDim.x * 4;
+    [[maybe_unused]] WaveStage st = {nullptr, 0u};  // (PHASE 2: the wave's LDS stage of appended keys)
+    if constexpr (PHASE == 2) {
+      __shared__ u64 stage8[4][128];
+      st.stage = stage8[wave];
+    }
     for (uint32_t cur = blockIdx.x * 4 + wave; cur < groups; cur += U * W) {
       u4v v[U][QPL];
       uint32_t row[U];
@@ -198,6 +209,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           }
         }
         s = group_sum<L>(s);
+        if constexpr (PHASE == 2) {
+          // the same rigorous test; cosine adds the rounding of the exact pass that decides (range_filter_kernel's fp32 sum
+          // of at most pitch / 256 + 8 terms deep, |c_i| <= 127 s: 127 * gamma < 2e-4 of s |q|_1 up to 4096 dimensions), as
+          // a row must be kept whose fp32 score reaches t even when its real c.q lies a rounding below it.  (L2: the caller
+          // lowers the threshold by that rounding instead, range_selection_tau_l2.)  Appends go through the wave's LDS stage.
+          bool keep = false;
+          u64 key = 0;
+          if (j == 0 && row[u] <= last_row) {
+            float m;
+            const float w = finish(s, sc[u], cn[u], m);
+            if constexpr (METRIC == WDBX_METRIC_COSINE) m = fmaf(1e-3f, sc[u] * q1, m);
+            keep = !(sc[u] < 0.f) && !(w + m < thr) && (!a.mask || ((a.mask[row[u] >> 5] >> (row[u] & 31)) & 1u));
+            key = make_key((w == w) ? w + 0.0f : INFINITY, row[u]);
+          }
+          st.push(keep, key, a.cand, a.count, a.cap, lane);
+        } else
         if (j == 0 && row[u] <= last_row) {
           float m;
           const float w = finish(s, sc[u], cn[u], m);
@@ -214,6 +241,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
       }
     }
+    if constexpr (PHASE == 2) st.finish(a.cand, a.count, a.cap, lane);
   }
 }
 

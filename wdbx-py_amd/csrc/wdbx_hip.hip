@@ -22,6 +22,8 @@
 //                           single queries), rows -> u8 + scales, query norms
 //   kernels_aux.h           row norms, threshold margins, rescore_kernel (exact fp32 scores of the candidates),
 //                           synthetic fill / normalise, read probes
+//   kernels_range.h         range search: range_scan_kernel (fp32, every row scored exactly), range_filter_kernel (exact
+//                           scores of the u8 selection's candidates); wave-aggregated appends, no k
 //   host_index.h            the handle, kernel choice, and the enqueue functions of every search path
 //   host_group.h            the in-process shard group: per-shard host threads, exchange (RCCL all-gather / device copies), merge
 // The selection paths never decide a result: they keep every row whose score could reach the true k-th best
@@ -58,6 +60,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 // the option table lookup live in host_dispatch.h: the device-free slice of the host side, which the CPU suite also builds
 // with plain g++ under -fsanitize=thread / address,undefined (tests/test_host_dispatch_sanitizers.py)
 #include "host_dispatch.h"
+#include "host_range.h"  // (device-free as well: CSR offsets, per-query sort and decoding of a range search's keys)
 
 #define HIP_TRY(expr)                                                                        \
   do {                                                                                       \
@@ -85,6 +88,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "kernels_scan8.h"
 #include "kernels_tiles8.h"
 #include "kernels_aux.h"
+#include "kernels_range.h"
 #include "host_index.h"
 #include "host_group.h"
 
@@ -101,6 +105,7 @@ static uint64_t device_bytes_resident(const wdbx_index* ix) {
   b += (uint64_t)ix->out_elems * 12 + ix->dump_bytes + ix->sel_bytes + ix->state_bytes + ix->mask_bytes + ix->qblock_bytes;
   b += ix->halfmax_bytes + ix->tau_bytes + ix->cand_bytes + ix->count_bytes + ix->qb16_bytes + ix->qn_bytes + ix->selsrc_bytes;
   b += ix->qb8_bytes + ix->qpar_bytes + ix->pairs_bytes + ix->pair_count_bytes + ix->cnmax_bytes;
+  b += ix->rcand_bytes + ix->rkeys_bytes + ix->rcnt_bytes + ix->rthr_bytes;
   return b;
 }
 
@@ -177,7 +182,7 @@ void wdbx_index_destroy(wdbx_index* ix) try {
                     ix->d_qblock, ix->d_halfmax, ix->d_tau, ix->d_cand, ix->d_count, ix->d_ticket, ix->d_mask, ix->d_dump, ix->d_sel,
                     ix->d_state, ix->d_cn, ix->d_cnmax, ix->d_qb16, ix->d_rows16, ix->d_rows8, ix->d_scale8, ix->d_selsrc,
                     ix->d_gmax, ix->d_qn, ix->d_rows8g, ix->d_groups8, ix->d_gbad8, ix->d_gref8, ix->d_over_list, ix->d_qb8,
-                    ix->d_qpar, ix->d_pairs, ix->d_pair_count};
+                    ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr};
     for (void* p : bufs)
       if (p) (void)hipFree(p);
     if (ix->h_stage) (void)hipHostFree(ix->h_stage);
@@ -656,6 +661,189 @@ int wdbx_index_search_masked_n(wdbx_index* ix, const float* queries, int nq, int
                                const uint32_t* mask_words, uint64_t mask_word_count, int64_t* out_idx, float* out_score) try {
   if (!mask_words) return fail(WDBX_E_INVALID, "mask_words is null");
   return search_host(ix, queries, nq, k, normalize_queries, mask_words, mask_word_count, out_idx, out_score);
+} WDBX_CATCH
+
+// ---- range search (range_u8_eligible, pick_range_scan: host_index.h) -------------------------------
+// The whole call holds the handle's mutex (like a masked search: the key buffers are the handle's).  Per round of up to 64
+// queries: [u8 path: memset counters, scan8_kernel<PHASE 2> -> candidates] -> memset, range_filter_kernel / range_scan_kernel
+// -> result keys; one synchronisation reads both counters.  A counter past its buffer (the counters count on) grows that
+// buffer to the exact count and the overflowed stage runs again -- once: the same inputs give the same count (a candidate
+// overflow reruns the filter too, whose input was cut).  Then the keys go to the caller's row array at their CSR offsets and
+// range_sort_decode (host_range.h) sorts and decodes them there.
+static int range_search_host(wdbx_index* ix, const float* queries, int nq, const float* thresholds, int normalize_queries,
+                             const uint32_t* mask_words, uint64_t mask_word_count, uint64_t capacity, uint64_t* out_offsets,
+                             int64_t* out_rows, float* out_scores) {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  if (nq < 1) return fail(WDBX_E_INVALID, "nq=%d", nq);
+  if (!queries || !thresholds || !out_offsets) return fail(WDBX_E_INVALID, "null buffer");
+  if (capacity && (!out_rows || !out_scores)) return fail(WDBX_E_INVALID, "capacity %llu without result buffers", (u64)capacity);
+  for (int q = 0; q < nq; ++q)
+    if (thresholds[q] != thresholds[q]) return fail(WDBX_E_INVALID, "threshold of query %d is NaN", q);
+  std::lock_guard<std::mutex> lk(ix->mu);
+  DeviceGuard g(ix->device);
+  struct MaskScope {
+    wdbx_index* ix;
+    bool set = false;
+    ~MaskScope() {
+      if (set) ix->active_mask = nullptr;
+    }
+  } scope{ix};
+  int rc;
+  out_offsets[0] = 0;
+  if (ix->n == 0) {
+    for (int q = 0; q < nq; ++q) out_offsets[q + 1] = 0;
+    return WDBX_OK;
+  }
+  if (mask_words) {
+    const size_t words = (size_t)((ix->n + 31) / 32);
+    if (mask_word_count < words)
+      return fail(WDBX_E_INVALID, "row mask of %llu words for %llu rows (%zu words needed)", (u64)mask_word_count, (u64)ix->n, words);
+    if ((rc = grow((void**)&ix->d_mask, &ix->mask_bytes, words * sizeof(uint32_t)))) return rc;
+    HIP_TRY(hipMemcpyAsync(ix->d_mask, mask_words, words * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+    ix->active_mask = ix->d_mask;
+    scope.set = true;
+  }
+  const size_t q_bytes = (size_t)nq * ix->pitch * sizeof(float);
+  if ((rc = grow((void**)&ix->d_q, &ix->q_bytes, q_bytes))) return rc;
+  if (ix->pitch == ix->dim) {
+    HIP_TRY(hipMemcpyAsync(ix->d_q, queries, q_bytes, hipMemcpyHostToDevice, ix->stream));
+  } else {
+    HIP_TRY(hipMemsetAsync(ix->d_q, 0, q_bytes, ix->stream));
+    HIP_TRY(hipMemcpy2DAsync(ix->d_q, (size_t)ix->pitch * sizeof(float), queries, (size_t)ix->dim * sizeof(float),
+                             (size_t)ix->dim * sizeof(float), nq, hipMemcpyHostToDevice, ix->stream));
+  }
+  const bool l2 = ix->metric == WDBX_METRIC_L2;
+  if (normalize_queries && !l2 && (rc = launch_normalize(ix, ix->d_q, (uint64_t)nq))) return rc;
+  const bool u8 = range_u8_eligible(ix) && prepare_u8_shadow(ix);
+  if (u8 && l2 && (rc = ensure_row_norms(ix))) return rc;
+  ix->last_range_path = u8 ? 2 : 0;
+  constexpr int ROUND = 64;
+  if ((rc = grow((void**)&ix->d_rcnt, &ix->rcnt_bytes, 2 * ROUND * sizeof(uint32_t)))) return rc;
+  if ((rc = grow((void**)&ix->d_rthr, &ix->rthr_bytes, 2 * ROUND * sizeof(float)))) return rc;
+  const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
+  const Scan8Shape* sh = u8 ? scan8_shape((uint32_t)ix->dim) : nullptr;
+  const scan8_fn f2 = !u8 ? nullptr : l2 ? pick_scan8<2, WDBX_METRIC_L2>(sh->L, sh->QPL) : pick_scan8<2, WDBX_METRIC_COSINE>(sh->L, sh->QPL);
+  if (u8 && !f2) return fail(WDBX_E_STATE, "no u8 range instance for %d lanes x %d loads", sh->L, sh->QPL);
+  const range_fn fscan = l2 ? pick_range_scan<WDBX_METRIC_L2>(pitch4) : pick_range_scan<WDBX_METRIC_COSINE>(pitch4);
+  const range_fn ffilter = l2 ? range_filter_kernel<WDBX_METRIC_L2> : range_filter_kernel<WDBX_METRIC_COSINE>;
+  std::vector<float> hthr(2 * ROUND);
+  std::vector<uint32_t> hcnt(2 * ROUND);
+  std::vector<uint64_t> cnt(ROUND);
+
+  for (int q0 = 0; q0 < nq; q0 += ROUND) {
+    const int nv = std::min(ROUND, nq - q0);
+    const float* dq = ix->d_q + (size_t)q0 * ix->pitch;
+    for (int i = 0; i < nv; ++i) {
+      const float t = thresholds[q0 + i];
+      hthr[i] = t;
+      if (l2) {
+        double qq = 0.0;
+        for (int c = 0; c < ix->dim; ++c) qq += (double)queries[(size_t)(q0 + i) * ix->dim + c] * queries[(size_t)(q0 + i) * ix->dim + c];
+        hthr[ROUND + i] = range_selection_tau_l2(qq, t);
+      } else {
+        hthr[ROUND + i] = t;  // (the rounding of the exact pass is added to the bound inside the scan)
+      }
+    }
+    HIP_TRY(hipMemcpyAsync(ix->d_rthr, hthr.data(), 2 * ROUND * sizeof(float), hipMemcpyHostToDevice, ix->stream));
+    auto enqueue_select = [&]() -> int {  // u8 path: the candidates
+      const uint32_t cap = ix->range_cand_cap;
+      int rc2 = grow((void**)&ix->d_rcand, &ix->rcand_bytes, (size_t)nv * cap * sizeof(u64));
+      if (rc2) return rc2;
+      HIP_TRY(hipMemsetAsync(ix->d_rcnt, 0, (size_t)nv * sizeof(uint32_t), ix->stream));
+      Scan8Args a = {};
+      a.rows8 = (const u4v*)ix->d_rows8;
+      a.scale = ix->d_scale8;
+      a.cn = ix->d_cn;
+      a.query = (const f4*)dq;
+      a.mask = ix->active_mask;
+      a.n_rows = (uint32_t)ix->n;
+      a.pieces = sh->pieces;
+      a.qquads = pitch4;
+      a.tau = ix->d_rthr + ROUND;
+      a.cand = ix->d_rcand;
+      a.count = ix->d_rcnt;
+      a.cap = cap;
+      const uint32_t groups1 = (uint32_t)((ix->n + (64 / sh->L) - 1) / (64 / sh->L));
+      const uint32_t grid1 = std::min<uint32_t>((groups1 + 3) / 4, (uint32_t)ix->cu_count * 2);
+      if ((rc2 = record(ix->scan_ev, ix->profile, ix->stream, true))) return rc2;
+      hipLaunchKernelGGL(f2, dim3(grid1, nv), dim3(256), 0, ix->stream, a);
+      HIP_TRY(hipGetLastError());
+      return record(ix->scan_ev, ix->profile, ix->stream, false, (uint32_t)nv);
+    };
+    auto enqueue_out = [&]() -> int {  // the exact pass: result keys
+      const uint32_t cap = u8 ? ix->range_cand_cap : ix->range_out_cap;  // (u8: results <= candidates, never past the buffer)
+      int rc2 = grow((void**)&ix->d_rkeys, &ix->rkeys_bytes, (size_t)nv * cap * sizeof(u64));
+      if (rc2) return rc2;
+      HIP_TRY(hipMemsetAsync(ix->d_rcnt + ROUND, 0, (size_t)nv * sizeof(uint32_t), ix->stream));
+      RangeArgs r = {};
+      r.rows = (const f4*)ix->d_rows;
+      r.queries = (const f4*)dq;
+      r.thr = ix->d_rthr;
+      r.mask = ix->active_mask;
+      r.n_rows = (uint32_t)ix->n;
+      r.pitch4 = pitch4;
+      r.out = ix->d_rkeys;
+      r.count = ix->d_rcnt + ROUND;
+      r.cap = cap;
+      r.cand = ix->d_rcand;
+      r.cand_count = ix->d_rcnt;
+      r.cand_cap = ix->range_cand_cap;
+      EventPool& ev = u8 ? ix->merge_ev : ix->scan_ev;
+      if ((rc2 = record(ev, ix->profile, ix->stream, true))) return rc2;
+      if (u8) {
+        hipLaunchKernelGGL(ffilter, dim3((uint32_t)ix->cu_count * 8, nv), dim3(256), 0, ix->stream, r);
+      } else {
+        uint32_t P = 1;  // (lanes per row, as pick_range_scan chose them)
+        while (P < pitch4 && P < 64) P <<= 1;
+        const uint64_t groups = (ix->n + (64 / P) - 1) / (64 / P);
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((groups + 3) / 4, (uint64_t)ix->cu_count * 8);
+        hipLaunchKernelGGL(fscan, dim3(grid, nv), dim3(256), 0, ix->stream, r);
+      }
+      HIP_TRY(hipGetLastError());
+      return record(ev, ix->profile, ix->stream, false, (uint32_t)nv);
+    };
+    auto read_counts = [&]() -> int {
+      HIP_TRY(hipMemcpyAsync(hcnt.data(), ix->d_rcnt, 2 * ROUND * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
+      HIP_TRY(hipStreamSynchronize(ix->stream));
+      return WDBX_OK;
+    };
+    auto max_of = [&](int base) {
+      uint32_t m = 0;
+      for (int i = 0; i < nv; ++i) m = std::max(m, hcnt[base + i]);
+      return m;
+    };
+    if (u8 && (rc = enqueue_select())) return rc;
+    if ((rc = enqueue_out()) || (rc = read_counts())) return rc;
+    if (u8 && max_of(0) > ix->range_cand_cap) {  // candidates past their buffer: grow to the exact count, select + filter again
+      ix->range_cand_cap = max_of(0);
+      if ((rc = enqueue_select()) || (rc = enqueue_out()) || (rc = read_counts())) return rc;
+      if (max_of(0) > ix->range_cand_cap) return fail(WDBX_E_STATE, "range search: candidate count changed between two passes");
+    }
+    if (!u8 && max_of(ROUND) > ix->range_out_cap) {  // results past their buffer: grow, the scan again
+      ix->range_out_cap = max_of(ROUND);
+      if ((rc = enqueue_out()) || (rc = read_counts())) return rc;
+      if (max_of(ROUND) > ix->range_out_cap) return fail(WDBX_E_STATE, "range search: result count changed between two passes");
+    }
+    for (int i = 0; i < nv; ++i) cnt[i] = hcnt[ROUND + i];
+    const uint64_t total = range_csr_offsets(cnt.data(), nv, out_offsets + q0);
+    if (total <= capacity) {  // the keys, straight into the caller's row array at their offsets (u64 slots)
+      const uint32_t cap = u8 ? ix->range_cand_cap : ix->range_out_cap;
+      for (int i = 0; i < nv; ++i)
+        if (cnt[i])
+          HIP_TRY(hipMemcpyAsync(out_rows + out_offsets[q0 + i], ix->d_rkeys + (size_t)i * cap, cnt[i] * sizeof(u64),
+                                 hipMemcpyDeviceToHost, ix->stream));
+      HIP_TRY(hipStreamSynchronize(ix->stream));
+    }
+  }
+  if (out_offsets[nq] <= capacity) range_sort_decode(l2 ? 1 : 0, nq, out_offsets, out_rows, out_scores);
+  return WDBX_OK;
+}
+
+int wdbx_index_range_search(wdbx_index* ix, const float* queries, int nq, const float* thresholds, int normalize_queries,
+                            const uint32_t* mask_words, uint64_t mask_word_count, uint64_t capacity, uint64_t* out_offsets,
+                            int64_t* out_rows, float* out_scores) try {
+  return range_search_host(ix, queries, nq, thresholds, normalize_queries, mask_words, mask_word_count, capacity, out_offsets,
+                           out_rows, out_scores);
 } WDBX_CATCH
 
 int wdbx_device_alloc(wdbx_index* ix, uint64_t bytes, void** out_dev_ptr) try {
@@ -1304,6 +1492,7 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"scan8_ablate", &wdbx_index::opt_scan8_ablate},
     {"batch_repair", &wdbx_index::opt_batch_repair},
     {"single_min_rows", &wdbx_index::opt_single_min_rows},
+    {"range_min_rows", &wdbx_index::opt_range_min_rows},
     {"group_bounds", &wdbx_index::opt_group_bounds},
     {"scan_force_ragged", &wdbx_index::opt_force_ragged},
     {"select_min_k", &wdbx_index::opt_select_min_k},
@@ -1337,6 +1526,7 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "shadowg_rows")) return *value = (int64_t)ix->shadowg_rows, WDBX_OK;
   if (name && !strcmp(name, "shadowg_bytes")) return *value = (int64_t)(ix->rows8g_bytes + ix->groups8_bytes), WDBX_OK;
   if (name && !strcmp(name, "last_single_path")) return *value = ix->last_single_path, WDBX_OK;
+  if (name && !strcmp(name, "last_range_path")) return *value = ix->last_range_path, WDBX_OK;
   if (name && !strcmp(name, "last_sample_qn")) return *value = ix->last_sample_qn, WDBX_OK;
   if (name && !strcmp(name, "last_batch_repaired")) return *value = ix->last_batch_repaired ? 1 : 0, WDBX_OK;
   if (name && !strcmp(name, "group_bounds_active")) return *value = ix->group_bounds ? 1 : 0, WDBX_OK;

@@ -61,6 +61,8 @@ SIGNATURES = {
                                            _f32p]),
     "wdbx_index_search_masked_n": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
                                              _i64p, _f32p]),
+    "wdbx_index_range_search": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
+                                          C.c_uint64, _u64p, _i64p, _f32p]),
     "wdbx_device_alloc": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "wdbx_device_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "wdbx_device_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
@@ -304,6 +306,39 @@ class NativeIndex:
                                                         int(normalize_queries), m.ctypes.data_as(C.POINTER(C.c_uint32)), m.size,
                                                         idx.ctypes.data_as(_i64p), score.ctypes.data_as(_f32p)))
         return idx, score
+
+    def range_search(self, queries, thresholds, normalize_queries: bool = False,
+                     mask_words: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Every row whose score reaches its query's threshold (cosine / inner product: score >= t; L2: squared distance
+        <= t), exact fp32, per query sorted like :meth:`search`.  ``thresholds``: one per query (a scalar serves all).
+        Returns CSR ``(offsets int64[nq + 1], rows int64[total], scores f32[total])``: query i's results are
+        ``[offsets[i], offsets[i + 1])``.  A first call guesses the capacity (the previous answer's size, at least 4096 per
+        query); if the answer is larger, one more call with the exact total (a third only if rows were added in between;
+        after three the call raises)."""
+        q = _as_f32(queries, self.dim)
+        nq = q.shape[0]
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, dtype=np.float32), (nq,)))
+        m = None
+        if mask_words is not None:
+            m = np.ascontiguousarray(mask_words, dtype=np.uint32)
+            if m.size < (self.size() + 31) // 32:
+                raise ValueError("mask has fewer bits than the index has rows")
+        offsets = np.zeros(nq + 1, np.uint64)
+        # the guess: the previous answer's size (repeated queries of one kind then take one call), at least 4096 per query
+        capacity = max(4096 * nq, getattr(self, "_range_hint", 0))
+        for _ in range(3):
+            rows = np.empty(capacity, np.int64)
+            scores = np.empty(capacity, np.float32)
+            _check(self._lib.wdbx_index_range_search(
+                self._h, q.ctypes.data_as(_f32p), nq, t.ctypes.data_as(_f32p), int(normalize_queries),
+                m.ctypes.data_as(C.POINTER(C.c_uint32)) if m is not None else None, m.size if m is not None else 0,
+                capacity, offsets.ctypes.data_as(_u64p), rows.ctypes.data_as(_i64p), scores.ctypes.data_as(_f32p)))
+            total = int(offsets[nq])
+            self._range_hint = total
+            if total <= capacity:
+                return offsets.astype(np.int64), rows[:total], scores[:total]
+            capacity = total
+        raise HipBackendError(-6, "range search: the result kept growing between calls (concurrent adds)")
 
     # -- device-resident path --
     def alloc(self, nbytes: int) -> DeviceBuffer:

@@ -10,6 +10,7 @@ same validation outcome (a malformed body is a 422 there; here a ``ValueError`` 
     async def search_vectors(body: dict):
         return await search_endpoint(wdbx, body)
 
+``range_search_endpoint`` answers "every vector within this similarity" (no limit; the extension the reference lacks).
 ``search_batch_endpoint`` is the batch form the reference lacks: many queries in one request, answered by
 one batched pass per shard (``vector_search_batch``).  Concurrent single requests need no batch route: they are
 coalesced at ``VectorStore.search_async`` (what the reference's server produces, api/server.py:143).
@@ -73,3 +74,27 @@ async def search_batch_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]
     loop = asyncio.get_running_loop()
     per_query = await loop.run_in_executor(None, lambda: wdbx.vector_search_batch(queries, limit, threshold, flt))
     return {"results": [_render(r)["results"] for r in per_query]}
+
+
+async def range_search_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
+    """Range form (extension): body ``{"query_vector": [...], "threshold": 0.8, "filter_metadata": null,
+    "max_results": null}`` -> the ``search_endpoint`` response shape with EVERY vector whose similarity reaches
+    ``threshold`` (``wdbx.vector_search_range_async``), best first; ``max_results`` (null = all) cuts after sorting."""
+    if not isinstance(payload, dict):
+        raise ValueError("request body must be an object")
+    if "query_vector" not in payload:
+        raise ValueError("query_vector is required")
+    if "threshold" not in payload:
+        raise ValueError("threshold is required")
+    threshold = payload["threshold"]
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or threshold != threshold:
+        raise ValueError("threshold must be a number")
+    flt = payload.get("filter_metadata")
+    if flt is not None and not isinstance(flt, dict):
+        raise ValueError("filter_metadata must be an object")
+    max_results = payload.get("max_results")
+    if max_results is not None and (isinstance(max_results, bool) or not isinstance(max_results, int) or max_results < 0):
+        raise ValueError("max_results must be a non-negative integer or null")
+    query = _vector(payload["query_vector"], "query_vector")
+    return _render(await wdbx.vector_search_range_async(query, float(threshold), filter_metadata=flt,
+                                                        max_results=max_results))

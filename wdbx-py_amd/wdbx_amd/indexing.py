@@ -593,6 +593,32 @@ class HipFlatIndex(VectorIndex):
                 return []  # reference convention (indexing.py:1028-1030)
             raise
 
+    def range_search(self, query_vector: np.ndarray, threshold: float,
+                     row_mask: Optional[np.ndarray] = None) -> List[Tuple[str, float]]:
+        """Every stored vector whose score reaches ``threshold``, best first (extension: faiss' ``range_search``, which the
+        reference never calls).  ``threshold`` is in the convention ``search`` returns scores in -- cosine similarity, for
+        L2 the negated squared distance -- so the rule is always ``score >= threshold``.  No limit: the answer is exact
+        and complete.  ``row_mask`` as in ``search``; errors are swallowed or raised as there."""
+        try:
+            if self.next_index == 0:
+                return []
+            threshold = float(threshold)
+            if threshold != threshold:
+                raise ValueError("threshold is NaN")
+            q = self._prepare(query_vector)
+            words = None
+            if row_mask is not None:
+                words = row_mask if row_mask.dtype == np.uint32 else _native.pack_row_mask(row_mask)
+            # the library's rule for L2 is distance <= t: score = -distance >= threshold  <=>  distance <= -threshold
+            t = threshold if self.metric == _native.METRIC_COSINE else -threshold
+            _, rows, scores = self._native.range_search(q, t, mask_words=words)
+            return self._map(rows, scores)
+        except Exception as e:
+            logger.error("Error in HIP range search: %s", e)
+            if self.swallow_errors:
+                return []
+            raise
+
     def row_mask_for(self, predicate) -> np.ndarray:
         """uint32 mask words of the rows whose id satisfies ``predicate(id)``; unmapped (removed)
         rows are excluded."""

@@ -94,6 +94,22 @@ def _as_query(query_vector) -> np.ndarray:
     return np.array(query_vector, dtype=np.float32)
 
 
+def merge_range(shard_results, metadata: Dict[str, Any], filter_metadata: Optional[Dict[str, Any]] = None,
+                max_results: Optional[int] = None) -> List[Result]:
+    """The merge of a range search (``VectorStore.search_range``): the shards' [(id, score)] lists concatenated in shard
+    order, stable-sorted by score descending (as ``_merge``: ties keep shard order, then each shard's own order), the
+    metadata post-filter, then the cut to ``max_results`` (None = all); metadata attached."""
+    merged: List[Tuple[str, float]] = []
+    for results in shard_results:
+        merged.extend(results)
+    merged.sort(key=lambda r: r[1], reverse=True)
+    if filter_metadata:
+        merged = [r for r in merged if matches_filter(metadata.get(r[0], {}), filter_metadata)]
+    if max_results is not None:
+        merged = merged[: max(0, int(max_results))]
+    return [(vid, score, metadata.get(vid, {})) for vid, score in merged]
+
+
 class _SyncRequest:
     """One synchronous caller waiting in ``VectorStore._search_coalesced``.  ``gate`` is a plain lock used as a one-shot
     signal (created held; the server releases it): a tenth of the cost of ``threading.Event`` under the GIL."""
@@ -773,6 +789,34 @@ class VectorStore:
             per_shard = [ix.search_batch(queries, limit=limit) for ix in self.indices]
         return [self._merge([res[q] for res in per_shard], limit, threshold, filter_metadata)
                 for q in range(queries.shape[0])]
+
+    # ---- range search (extension: every vector within a similarity, no limit) ----
+    def search_range(self, query_vector: List[float], threshold: float,
+                     filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,
+                     max_results: Optional[int] = None) -> List[Result]:
+        """Every stored vector whose score reaches ``threshold`` (``score >= threshold`` in the scores ``search`` returns:
+        cosine similarity, for L2 the negated squared distance), best first, cut to ``max_results`` only after sorting and
+        filtering (None = all).  Unlike ``search(limit, threshold)``, which ranks a top-``limit`` and then drops what is
+        below the threshold, nothing is lost to a limit.  Each shard answers with the library's range search (on the shard
+        pool, gathered in shard order); no shard group and no coalescing.  ``prefilter`` / FILTER_PUSHDOWN as in
+        ``search``: without ``max_results`` the pushed-down filter and the post-filter give the same list."""
+        query = _as_query(query_vector)
+        if query.shape != (self.vector_dim,):
+            raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {query.shape}")
+        masks = self._masks_for(filter_metadata, prefilter)
+        if len(self.indices) > 1:
+            shard_results = list(self._shard_pool.map(lambda a: a[0].range_search(query, threshold, row_mask=a[1]),
+                                                      zip(self.indices, masks)))
+        else:
+            shard_results = [ix.range_search(query, threshold, row_mask=m) for ix, m in zip(self.indices, masks)]
+        return merge_range(shard_results, self.metadata, filter_metadata, max_results)
+
+    async def search_range_async(self, query_vector: List[float], threshold: float,
+                                 filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,
+                                 max_results: Optional[int] = None) -> List[Result]:
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(self.thread_pool, lambda: self.search_range(
+            query_vector, threshold, filter_metadata=filter_metadata, prefilter=prefilter, max_results=max_results))
 
     # ---- row management ----
     def _known(self, vector_id: str) -> bool:

@@ -122,6 +122,23 @@ class WDBX:
         return self.vector_store.search_batch(query_vectors, limit=limit, threshold=threshold,
                                               filter_metadata=filter_metadata)
 
+    def vector_search_range(self, query_vector: List[float], threshold: float,
+                            filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,
+                            max_results: Optional[int] = None) -> List[Result]:
+        """Extension: EVERY stored vector whose score reaches ``threshold`` (cosine similarity; for L2 the negated squared
+        distance), best first, with no top-k limit in between (``vector_search(limit, threshold)`` thresholds a top-``limit``
+        and silently drops the rest).  ``max_results`` cuts the sorted, filtered list (None = all)."""
+        self._check_dim(query_vector)
+        return self.vector_store.search_range(query_vector, threshold, filter_metadata=filter_metadata,
+                                              prefilter=prefilter, max_results=max_results)
+
+    async def vector_search_range_async(self, query_vector: List[float], threshold: float,
+                                        filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,
+                                        max_results: Optional[int] = None) -> List[Result]:
+        self._check_dim(query_vector)
+        return await self.vector_store.search_range_async(query_vector, threshold, filter_metadata=filter_metadata,
+                                                          prefilter=prefilter, max_results=max_results)
+
     # ---- row management ----
     def delete_vector(self, vector_id: str) -> bool:
         return self.vector_store.delete(vector_id)
