@@ -1,3 +1,5 @@
+"""Candidates per query on the bench corpus (10 M x 384, fill_synthetic's rows, top-10, one round of 32 queries):
+the u8 selection scan, the bf16 tiles, and the six-bit u6 scan with its stored-residual bound."""
 import sys, numpy as np
 sys.path.insert(0, "wdbx-py_amd")
 from wdbx_amd import _native
@@ -5,9 +7,18 @@ ix = _native.NativeIndex(384, capacity_rows=10_000_000)
 ix.fill_synthetic(0xC0FFEE, 0, 10_000_000, True)
 dq = ix.device_queries_synthetic(0xBEEF, 0, 32, True)
 d_idx, d_score = ix.alloc(32 * 10 * 8), ix.alloc(32 * 10 * 4)
+ix.set_option("scan_u6", 0)
 for path in (2, 1):
     ix.set_option("scan_shadow", path)
     ix.search_device(dq, 32, 10, d_idx, d_score); ix.synchronize()
     st = ix.batch_status(32)
     print("path", path, "candidates mean/min/max", st["counts"].mean(), st["counts"].min(), st["counts"].max(), "cap", st["capacity"])
-print("shadow8_bytes", ix.get_option("shadow8_bytes"), "shadow_bytes", ix.get_option("shadow_bytes"))
+ix.set_option("scan_shadow", 2)
+ix.set_option("scan_u6", -1)
+ix.search_device(dq, 32, 10, d_idx, d_score); ix.synchronize()
+assert ix.get_option("last_single_u6") == 1
+st = ix.batch_status(32)
+print("u6 scan: candidates mean/max", ix.get_option("u6_candidates_sum") / 32, ix.get_option("u6_candidates_max"),
+      "; keys behind the cut mean/max", st["counts"].mean(), st["counts"].max(), "of", st["capacity"], "overflowed", st["overflowed"])
+print("shadow8_bytes", ix.get_option("shadow8_bytes"), "shadow6_bytes", ix.get_option("shadow6_bytes"),
+      "shadow_bytes", ix.get_option("shadow_bytes"), "device_bytes_resident", ix.get_option("device_bytes_resident"))

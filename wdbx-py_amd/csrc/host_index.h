@@ -90,6 +90,16 @@ struct wdbx_index {
   uint64_t shadow8_rows = 0;
   uint32_t pitch8 = 0;
   uint64_t u8_no_room_cap = ~0ull;  // capacity at which the u8 shadow last failed to allocate
+  // u6 shadow copy of rows [0, shadow6_rows) for rounds of single queries (kernels_scan6.h): ONE allocation, the six-bit codes
+  // in 64-row tiles of units6 units followed by the per-row {s, a} pairs
+  uint32_t* d_rows6 = nullptr;
+  size_t rows6_bytes = 0;
+  uint64_t shadow6_rows = 0, rows6_tiles = 0;
+  uint32_t units6 = 0;
+  uint64_t u6_no_room_cap = ~0ull;
+  uint32_t* d_count6 = nullptr;  // its candidate counters (d_count holds the cut's: what the repair launches look at)
+  size_t count6_bytes = 0;
+  int last_single_u6 = 0;      // 1: the last single-query search selected on the u6 shadow (last_single_path stays 2)
   uint32_t* defer_flag_dev = nullptr;  // non-null during a blocking call that repairs overflow itself (mapped host word)
   // a lone blocking call through a staging slot: the LAST kernel of its chain writes done_seq into done_flag_dev (a mapped
   // host word of the slot) and the caller polls that word instead of waiting on the runtime; done_signals counts the launches
@@ -146,7 +156,7 @@ struct wdbx_index {
           opt_gemm8_refine = 1, opt_scan8_sample4 = 1, opt_gemm_l2 = 1, opt_gemm_l2_i8 = 1, opt_force_ragged = 0,
           opt_gemm_ct = 0, opt_wg_merge = 1, opt_zero_copy = 1, opt_lone_host_select = 1, opt_lds_lists = 0,
           opt_merge_fast = 1, opt_poll_done = 1, opt_scan_one_grid = 1, opt_select_min_k = 200, opt_gemm_min_nq = 4, opt_gemm_min_rows = 65536, opt_gemm_min_work = 800000,
-          opt_gemm_sample_div = 0, opt_range_min_rows = 131072;
+          opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0;
 };
 
 struct DeviceGuard {
@@ -488,6 +498,10 @@ static bool u8_single_eligible(const wdbx_index* ix, int k, int nq_call);
 static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, int k, int64_t* d_out_idx, float* d_out_score,
                               u64* keys_out, bool candidates_only = false);
 static bool prepare_u8_shadow(wdbx_index* ix);
+static bool u6_single_eligible(const wdbx_index* ix, int k, int nq_call);
+static bool prepare_u6_shadow(wdbx_index* ix);
+static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, int k, int64_t* d_out_idx, float* d_out_score,
+                              u64* keys_out);
 
 static int enqueue_search(wdbx_index* ix, const float* d_queries, int nq, int k, int64_t* d_out_idx,
                           float* d_out_score, int mode, u64* keys_dst = nullptr) {
@@ -549,6 +563,7 @@ static int enqueue_search(wdbx_index* ix, const float* d_queries, int nq, int k,
       // which of the two the chain reads.
       const bool u8 = u8_single_eligible(ix, k, nq) && prepare_u8_shadow(ix);  // (also for the in-process group's local stage)
       ix->last_single_path = u8 ? 2 : 0;
+      ix->last_single_u6 = 0;
       SelectSrc* src = nullptr;
       if (u8) {
         if ((rc = grow((void**)&ix->d_count, &ix->count_bytes, ((size_t)batch + 2 * GB_N) * sizeof(uint32_t)))) return rc;
@@ -615,9 +630,15 @@ static int enqueue_search(wdbx_index* ix, const float* d_queries, int nq, int k,
       const bool u8 = u8_single_eligible(ix, k, nq) && prepare_u8_shadow(ix);  // (also for the in-process group's local stage)
       const bool shadow = u8 || (!keys_only && shadow_single_eligible(ix, k, nq));
       ix->last_single_path = u8 ? 2 : shadow ? 1 : 0;
+      // rounds on a large shard select on the six-bit shadow instead (0.76 of the u8 bytes per pass; kernels_scan6.h)
+      const bool u6 = u8 && u6_single_eligible(ix, k, nq) && prepare_u6_shadow(ix);
+      ix->last_single_u6 = u6 ? 1 : 0;
       if (shadow) {
         if ((rc = grow((void**)&ix->d_count, &ix->count_bytes, ((size_t)batch + 2 * GB_N) * sizeof(uint32_t)))) return rc;
-        if (u8)  // the u8 selection scan: a quarter of the fp32 bytes per query
+        if (u6)
+          rc = enqueue_singles_u6(ix, d_queries + (size_t)q0 * ix->pitch, b, k, d_out_idx ? d_out_idx + (size_t)q0 * k : nullptr,
+                                  d_out_score ? d_out_score + (size_t)q0 * k : nullptr, sharded ? lkeys : nullptr);
+        else if (u8)  // the u8 selection scan: a quarter of the fp32 bytes per query
           rc = enqueue_singles_u8(ix, d_queries + (size_t)q0 * ix->pitch, b, k, d_out_idx ? d_out_idx + (size_t)q0 * k : nullptr,
                                   d_out_score ? d_out_score + (size_t)q0 * k : nullptr, sharded ? lkeys : nullptr);
         else     // the bf16 tile kernel with one live column: half the fp32 bytes
@@ -1110,6 +1131,209 @@ static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, in
     f.i_stride = 0;
     f.p_stride = 1;
     f.P = cap;
+    f.P_dev = ix->d_count + q0;
+    f.list_len = 1;
+    f.k = k;
+    f.metric = ix->metric;
+    f.over_out = ix->defer_flag_dev ? ix->defer_flag_dev + q0 : nullptr;
+    if (keys_out) {
+      f.row_base = (uint32_t)ix->row_base;
+      f.out_keys = keys_out + (size_t)q0 * k;
+    } else {
+      f.out_idx = d_out_idx + (size_t)q0 * k;
+      f.out_score = d_out_score + (size_t)q0 * k;
+    }
+    if ((rc = launch_merge(ix, f, nv))) return rc;
+  }
+  return WDBX_OK;
+}
+
+// ---- rounds of single queries on the u6 selection scan (kernels_scan6.h) ---------------------------------------
+// units in flight per wave = the largest of 8 .. 4 that divides the row's units (24 -> 8, 25 -> 5, 6 -> 6); 0 = none
+static int u6_unit_chunk(uint32_t units) {
+  for (int uc = 8; uc >= 4; --uc)
+    if (units % (uint32_t)uc == 0) return uc;
+  return 0;
+}
+
+// Where the u8 scan is eligible AND: inner product / cosine, k <= 32, no row mask, a call of several queries (a lone query
+// keeps the u8 scan's short chain), rows of whole 16-element units.  Option scan_u6: -1 = shards whose u8 shadow exceeds
+// 1 GiB (where a pass per launch is the rule and the bytes of a pass are the step), 0 = never, 1 = wherever eligible.
+static bool u6_single_eligible(const wdbx_index* ix, int k, int nq_call) {
+  if (ix->opt_scan_u6 == 0 || ix->metric == WDBX_METRIC_L2 || ix->active_mask || k > 32 || nq_call < 2) return false;
+  if (ix->pitch % 16 != 0 || ix->pitch > 4096 || !u6_unit_chunk((uint32_t)ix->pitch / 16)) return false;
+  const Scan8Shape* sh = scan8_shape((uint32_t)ix->dim);
+  if (ix->opt_scan_u6 < 0 && (!sh || (uint64_t)ix->n * sh->pieces * 16 <= (1ull << 30))) return false;
+  return true;
+}
+
+// Allocates / refreshes the u6 shadow for the rows added since the last search that took this path (the life cycle of
+// prepare_u8_shadow).  false = no room on the device (remembered per capacity): the caller stays on the u8 scan.
+static bool prepare_u6_shadow(wdbx_index* ix) {
+  const uint32_t units = (uint32_t)ix->pitch / 16;
+  const uint64_t tiles = ((uint64_t)ix->cap + 63) / 64;
+  const size_t need = (size_t)tiles * units * 768 + (size_t)tiles * 64 * sizeof(f2v);
+  if (ix->rows6_bytes < need || ix->units6 != units || ix->rows6_tiles != tiles) {
+    if (ix->u6_no_room_cap == ix->cap) return false;
+    if (ix->d_rows6) (void)hipFree(ix->d_rows6);
+    ix->d_rows6 = nullptr;
+    ix->rows6_bytes = 0;
+    ix->shadow6_rows = 0;
+    if (hipMalloc((void**)&ix->d_rows6, need) != hipSuccess) {
+      (void)hipGetLastError();
+      ix->d_rows6 = nullptr;
+      ix->u6_no_room_cap = ix->cap;
+      return false;
+    }
+    ix->rows6_bytes = need;
+    ix->units6 = units;
+    ix->rows6_tiles = tiles;
+  }
+  if (ix->shadow6_rows < ix->n) {
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((ix->n - ix->shadow6_rows + 3) / 4, 65536);
+    hipLaunchKernelGGL(rows_to_u6_kernel, dim3(blocks), dim3(256), 0, ix->stream, (const float*)ix->d_rows, (u64)ix->shadow6_rows,
+                       (u64)ix->n, (uint32_t)ix->dim, (uint32_t)ix->pitch, units, ix->d_rows6,
+                       (f2v*)(ix->d_rows6 + (size_t)ix->rows6_tiles * units * 192));
+    if (hipGetLastError() != hipSuccess) return false;
+    ix->shadow6_rows = ix->n;
+  }
+  return true;
+}
+
+typedef void (*scan6_fn)(Scan6Args);
+static scan6_fn pick_scan6(int uc, bool sample) {
+  switch (uc) {
+    case 4: return sample ? scan8_u6_sample_kernel<4> : scan8_u6_kernel<4>;
+    case 5: return sample ? scan8_u6_sample_kernel<5> : scan8_u6_kernel<5>;
+    case 6: return sample ? scan8_u6_sample_kernel<6> : scan8_u6_kernel<6>;
+    case 7: return sample ? scan8_u6_sample_kernel<7> : scan8_u6_kernel<7>;
+    case 8: return sample ? scan8_u6_sample_kernel<8> : scan8_u6_kernel<8>;
+  }
+  return nullptr;
+}
+
+// nq single queries of a round, each with its own full pass over the u6 shadow: sample (4 queries per workgroup) ->
+// thresholds -> a pass per query -> exact re-scoring (rescore_kernel, as behind the u8 scan) -> cut -> final top-k.
+// The candidate counters live in d_count6; d_count[0 .. nq) are the CUT's counters against last_batch_cap = its capacity, and
+// end above it for a query whose candidate buffer or short list overflowed: what the callers' repair launches test.
+static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, int k, int64_t* d_out_idx, float* d_out_score,
+                              u64* keys_out) {
+  const uint32_t units = (uint32_t)ix->pitch / 16;
+  const int uc = u6_unit_chunk(units);
+  scan6_fn f0 = pick_scan6(uc, true), f1 = pick_scan6(uc, false);
+  if (!f0 || !f1) return fail(WDBX_E_STATE, "no u6 scan instance for %u units", units);
+  if (!ix->d_rows6 || ix->units6 != units || ix->shadow6_rows < ix->n) return fail(WDBX_E_STATE, "u6 shadow not prepared");
+  int rc;
+  // sampled 256-row tiles (4 groups of 64 rows each), as on the u8 scan
+  const uint32_t tiles = (uint32_t)((ix->n + 255) / 256);
+  const uint32_t div = ix->opt_gemm_sample_div > 0 ? (uint32_t)ix->opt_gemm_sample_div : std::min(32u, std::max(4u, 1024u / (uint32_t)k));
+  uint32_t sample_tiles = std::max<uint32_t>(tiles / div, (8u * k + 3) / 4);
+  sample_tiles = std::max<uint32_t>(1, std::min(sample_tiles, tiles));
+  const uint32_t stride = tiles / sample_tiles, ngroups = 4 * sample_tiles;
+  if (ngroups < (uint32_t)k) return fail(WDBX_E_STATE, "corpus too small for the selection scan at k=%d", k);
+  // candidates: 256 x the k * (stride + 1) rows expected above the threshold (10 M x 384 top-10: 84 480; measured 3.8 k per
+  // query on the bench corpus, an estimated 25 k on Gaussian rows)
+  const uint64_t expect = (uint64_t)k * (tiles / sample_tiles + 1);
+  const uint32_t cap = ix->opt_scan_u6_cap > 0 ? (uint32_t)std::min<int64_t>(ix->opt_scan_u6_cap, 1 << 22)
+                                               : (uint32_t)std::min<uint64_t>(std::max<uint64_t>(4096, expect * 256), 1u << 22);
+  constexpr uint32_t cap2 = 4096;  // the cut's short list: a few keys beyond k per segment
+  constexpr int ROUND = 64;
+  if ((rc = grow((void**)&ix->d_halfmax, &ix->halfmax_bytes, (size_t)ROUND * ngroups * sizeof(u64)))) return rc;
+  if ((rc = grow((void**)&ix->d_tau, &ix->tau_bytes, (size_t)GB_N * sizeof(float)))) return rc;
+  if ((rc = grow((void**)&ix->d_cand, &ix->cand_bytes, (size_t)ROUND * ((size_t)cap + cap2) * sizeof(u64)))) return rc;
+  if ((rc = grow((void**)&ix->d_count6, &ix->count6_bytes, (size_t)ROUND * sizeof(uint32_t)))) return rc;
+  if (ix->count_bytes < ((size_t)nq + GB_N) * sizeof(uint32_t)) return fail(WDBX_E_STATE, "candidate counters not sized by the caller");
+  ix->last_batch_nq = (uint32_t)nq;
+  ix->last_batch_cap = cap2;
+  u64* const cand2 = ix->d_cand + (size_t)ROUND * cap;
+  const uint32_t tiles64 = (uint32_t)((ix->n + 63) / 64);
+  // workgroups per CU of the full pass (option scan8_wgs).  Measured at 10 M x 384, whole steps: 2 -> 2222 q/s, 4 -> 2125,
+  // 6 -> 2008, 8 -> 1990 (profiles/u6/README.md): eight waves per CU with 6 KiB in flight each keep HBM busy, more of them
+  // only spread the stream over more pages at once
+  const uint32_t wgs = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(ix->opt_scan8_wgs > 0 ? ix->opt_scan8_wgs : 2, 8));
+  const uint32_t grid1 = std::min<uint32_t>((tiles64 + 3) / 4, (uint32_t)ix->cu_count * wgs);
+  const uint32_t grid0 = std::min<uint32_t>((ngroups + 3) / 4, (uint32_t)ix->cu_count * 4);
+  const size_t pitch4 = ix->pitch / 4;
+  const Scan8Shape* sh = scan8_shape((uint32_t)ix->dim);
+  const bool one_grid = ix->opt_scan8_per_query == 0 ||
+                        (ix->opt_scan8_per_query < 0 && sh && (uint64_t)ix->n * sh->pieces * 16 <= (1ull << 30));
+
+  for (int q0 = 0; q0 < nq; q0 += ROUND) {
+    const int nv = std::min(ROUND, nq - q0);
+    const float* qsrc = d_queries + (size_t)q0 * ix->pitch;
+    Scan6Args a = {};
+    a.codes = ix->d_rows6;
+    a.sa = (const f2v*)(ix->d_rows6 + (size_t)ix->rows6_tiles * units * 192);
+    a.query = qsrc;
+    a.n_rows = (uint32_t)ix->n;
+    a.units = units;
+    a.qpitch = (uint32_t)ix->pitch;
+    a.halfmax = ix->d_halfmax;
+    a.num_tiles = sample_tiles;
+    a.tile_stride = stride;
+    a.nq = (uint32_t)nv;
+    a.tau = ix->d_tau;
+    a.cand = ix->d_cand;
+    a.count = ix->d_count6;
+    a.count2 = ix->d_count + q0;
+    a.cap = cap;
+    // the sample, all queries of the round in one launch: maxima of the lower bounds over the sampled groups
+    if ((rc = record(ix->sample_ev, ix->profile, ix->stream, true))) return rc;
+    ix->last_sample_qn = 4;
+    hipLaunchKernelGGL(f0, dim3(grid0, (nv + 3) / 4), dim3(256), 0, ix->stream, a);
+    HIP_TRY(hipGetLastError());
+    if ((rc = record(ix->sample_ev, ix->profile, ix->stream, false))) return rc;
+    if (ngroups <= (uint32_t)KTH_R * 1024 && !ix->opt_lds_lists) {
+      // a threshold from the k-th largest sampled lower bound (at most 2^-15 relative below it: kth_score_kernel)
+      KthArgs ka = {ix->d_halfmax, (u64)ngroups, ngroups, k, ix->d_tau};
+      if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
+      hipLaunchKernelGGL(kth_score_kernel, dim3(nv), dim3(1024), 0, ix->stream, ka);
+      HIP_TRY(hipGetLastError());
+      if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
+    } else {
+      MergeArgs m = {};
+      m.in = ix->d_halfmax;
+      m.q_stride = ngroups;
+      m.i_stride = 0;
+      m.p_stride = 1;
+      m.P = ngroups;
+      m.list_len = 1;
+      m.k = k;
+      m.metric = ix->metric;
+      m.out_kth = ix->d_tau;  // = a rigorous lower bound of each query's true k-th best score
+      if ((rc = launch_merge(ix, m, nv))) return rc;
+    }
+    // the full passes: every query makes its own pass over all rows (one grid on small shards, as the u8 scan); one event
+    // pair around them, the profile reports elapsed / passes
+    if ((rc = record(ix->gemm_ev, ix->profile, ix->stream, true))) return rc;
+    if (one_grid && nv > 1) {
+      hipLaunchKernelGGL(f1, dim3(grid1, nv), dim3(256), 0, ix->stream, a);
+      HIP_TRY(hipGetLastError());
+    } else {
+      for (int i = 0; i < nv; ++i) {
+        a.query = qsrc + (size_t)i * ix->pitch;
+        a.tau = ix->d_tau + i;
+        a.cand = ix->d_cand + (size_t)i * cap;
+        a.count = ix->d_count6 + i;
+        hipLaunchKernelGGL(f1, dim3(grid1), dim3(256), 0, ix->stream, a);
+        HIP_TRY(hipGetLastError());
+      }
+    }
+    if ((rc = record(ix->gemm_ev, ix->profile, ix->stream, false, (uint32_t)nv))) return rc;
+    // exact fp32 scores for the candidates, from the fp32 rows
+    hipLaunchKernelGGL(rescore_kernel<WDBX_METRIC_COSINE>, dim3(256, nv), dim3(256), 0, ix->stream, (const f4*)ix->d_rows,
+                       (uint32_t)pitch4, (const f4*)qsrc, ix->d_cand, (const uint32_t*)ix->d_count6, cap, (u64*)nullptr,
+                       (uint32_t*)nullptr);
+    // the cut: per segment of the re-scored keys those that can be among the best k
+    hipLaunchKernelGGL(u6_cut_kernel, dim3((cap + U6_CUT_SEG - 1) / U6_CUT_SEG, nv), dim3(1024), 0, ix->stream, (const u64*)ix->d_cand,
+                       (const uint32_t*)ix->d_count6, cap, k, cand2, ix->d_count + q0, cap2);
+    HIP_TRY(hipGetLastError());
+    MergeArgs f = {};
+    f.in = cand2;
+    f.q_stride = cap2;
+    f.i_stride = 0;
+    f.p_stride = 1;
+    f.P = cap2;
     f.P_dev = ix->d_count + q0;
     f.list_len = 1;
     f.k = k;
@@ -1865,6 +2089,13 @@ static int upload_rows(wdbx_index* ix, uint64_t first, const float* rows, uint64
     hipLaunchKernelGGL(rows_to_u8_kernel, dim3((uint32_t)std::min<uint64_t>((e - first + 3) / 4, 65536)), dim3(256), 0, ix->stream,
                        (const float*)ix->d_rows, (u64)first, (u64)e, (uint32_t)ix->dim, (uint32_t)ix->pitch, ix->d_rows8, ix->pitch8,
                        ix->d_scale8);
+    HIP_TRY(hipGetLastError());
+  }
+  if (first < ix->shadow6_rows && ix->d_rows6) {
+    const uint64_t e = std::min(end, ix->shadow6_rows);
+    hipLaunchKernelGGL(rows_to_u6_kernel, dim3((uint32_t)std::min<uint64_t>((e - first + 3) / 4, 65536)), dim3(256), 0, ix->stream,
+                       (const float*)ix->d_rows, (u64)first, (u64)e, (uint32_t)ix->dim, (uint32_t)ix->pitch, ix->units6, ix->d_rows6,
+                       (f2v*)(ix->d_rows6 + (size_t)ix->rows6_tiles * ix->units6 * 192));
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipStreamSynchronize(ix->stream));

@@ -22,6 +22,8 @@
 //                           single queries), rows -> u8 + scales, query norms
 //   kernels_aux.h           row norms, threshold margins, rescore_kernel (exact fp32 scores of the candidates),
 //                           synthetic fill / normalise, read probes
+//   kernels_scan6.h         scan8_u6_kernel: the same selection over the six-bit u6 shadow copy with a stored residual norm per
+//                           row (rounds of single queries on large shards), its quantiser and the cut behind the re-scoring
 //   kernels_range.h         range search: range_scan_kernel (fp32, every row scored exactly), range_filter_kernel (exact
 //                           scores of the u8 selection's candidates); wave-aggregated appends, no k
 //   host_index.h            the handle, kernel choice, and the enqueue functions of every search path
@@ -86,6 +88,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "kernels_merge_select.h"
 #include "kernels_tiles.h"
 #include "kernels_scan8.h"
+#include "kernels_scan6.h"
 #include "kernels_tiles8.h"
 #include "kernels_aux.h"
 #include "kernels_range.h"
@@ -106,6 +109,7 @@ static uint64_t device_bytes_resident(const wdbx_index* ix) {
   b += ix->halfmax_bytes + ix->tau_bytes + ix->cand_bytes + ix->count_bytes + ix->qb16_bytes + ix->qn_bytes + ix->selsrc_bytes;
   b += ix->qb8_bytes + ix->qpar_bytes + ix->pairs_bytes + ix->pair_count_bytes + ix->cnmax_bytes;
   b += ix->rcand_bytes + ix->rkeys_bytes + ix->rcnt_bytes + ix->rthr_bytes;
+  b += ix->rows6_bytes + ix->count6_bytes;
   return b;
 }
 
@@ -182,7 +186,7 @@ void wdbx_index_destroy(wdbx_index* ix) try {
                     ix->d_qblock, ix->d_halfmax, ix->d_tau, ix->d_cand, ix->d_count, ix->d_ticket, ix->d_mask, ix->d_dump, ix->d_sel,
                     ix->d_state, ix->d_cn, ix->d_cnmax, ix->d_qb16, ix->d_rows16, ix->d_rows8, ix->d_scale8, ix->d_selsrc,
                     ix->d_gmax, ix->d_qn, ix->d_rows8g, ix->d_groups8, ix->d_gbad8, ix->d_gref8, ix->d_over_list, ix->d_qb8,
-                    ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr};
+                    ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr, ix->d_rows6, ix->d_count6};
     for (void* p : bufs)
       if (p) (void)hipFree(p);
     if (ix->h_stage) (void)hipHostFree(ix->h_stage);
@@ -227,6 +231,7 @@ int wdbx_index_clear(wdbx_index* ix) try {
   ix->cn_stats_dirty = false;
   ix->shadow_rows = 0;
   ix->shadow8_rows = 0;
+  ix->shadow6_rows = 0;
   ix->shadowg_rows = 0;
   ix->shadowg_tail_n = ~0ull;
   return WDBX_OK;
@@ -343,6 +348,7 @@ int wdbx_index_compact(wdbx_index* ix, const uint64_t* src_rows, uint64_t n_keep
   ix->cn_rows = std::min(ix->cn_rows, first_moved);
   ix->shadow_rows = std::min(ix->shadow_rows, first_moved);
   ix->shadow8_rows = std::min(ix->shadow8_rows, first_moved);
+  ix->shadow6_rows = std::min(ix->shadow6_rows, first_moved);
   ix->shadowg_rows = std::min(ix->shadowg_rows, first_moved / 64 * 64);  // (whole 64-row groups: a group's scale depends on all its rows)
   ix->shadowg_tail_n = ~0ull;  // the groups behind the new last row still describe dropped rows: rewritten by the next batch
   ix->cn_stats_dirty = true;  // the running maximum / sum still hold the dropped rows' norms
@@ -1490,6 +1496,8 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"scan8_wgs", &wdbx_index::opt_scan8_wgs},
     {"scan8_per_query", &wdbx_index::opt_scan8_per_query},
     {"scan8_ablate", &wdbx_index::opt_scan8_ablate},
+    {"scan_u6", &wdbx_index::opt_scan_u6},
+    {"scan_u6_cap", &wdbx_index::opt_scan_u6_cap},
     {"batch_repair", &wdbx_index::opt_batch_repair},
     {"single_min_rows", &wdbx_index::opt_single_min_rows},
     {"range_min_rows", &wdbx_index::opt_range_min_rows},
@@ -1526,6 +1534,20 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "shadowg_rows")) return *value = (int64_t)ix->shadowg_rows, WDBX_OK;
   if (name && !strcmp(name, "shadowg_bytes")) return *value = (int64_t)(ix->rows8g_bytes + ix->groups8_bytes), WDBX_OK;
   if (name && !strcmp(name, "last_single_path")) return *value = ix->last_single_path, WDBX_OK;
+  if (name && !strcmp(name, "last_single_u6")) return *value = ix->last_single_u6, WDBX_OK;
+  if (name && (!strcmp(name, "u6_candidates_sum") || !strcmp(name, "u6_candidates_max"))) {
+    // the u6 scan's candidate counts of the last round (batch_status reports the cut's short lists); waits for the stream
+    const uint32_t nq = ix->last_single_u6 ? std::min<uint32_t>(ix->last_batch_nq, 64) : 0;
+    std::vector<uint32_t> c(std::max<uint32_t>(nq, 1), 0u);
+    DeviceGuard g(ix->device);
+    if (nq) HIP_TRY(hipMemcpyAsync(c.data(), ix->d_count6, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    int64_t sum = 0, mx = 0;
+    for (uint32_t v : c) sum += v, mx = std::max<int64_t>(mx, v);
+    return *value = name[14] == 's' ? sum : mx, WDBX_OK;
+  }
+  if (name && !strcmp(name, "shadow6_rows")) return *value = (int64_t)ix->shadow6_rows, WDBX_OK;
+  if (name && !strcmp(name, "shadow6_bytes")) return *value = (int64_t)ix->rows6_bytes, WDBX_OK;
   if (name && !strcmp(name, "last_range_path")) return *value = ix->last_range_path, WDBX_OK;
   if (name && !strcmp(name, "last_sample_qn")) return *value = ix->last_sample_qn, WDBX_OK;
   if (name && !strcmp(name, "last_batch_repaired")) return *value = ix->last_batch_repaired ? 1 : 0, WDBX_OK;
