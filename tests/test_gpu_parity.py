@@ -849,7 +849,8 @@ def test_batched_path_query_block_widths_agree(native, n, d, nq, k):
         assert np.array_equal(outs[0][0], o[0]) and np.array_equal(outs[0][1], o[1])
 
 
-@pytest.mark.parametrize("k,opts", [(25, {}), (25, {"scan_generic": 1}), (300, {}), (25, {"lds_lists": 1})])
+@pytest.mark.parametrize("k,opts", [(25, {}), (25, {"scan_generic": 1}), (300, {}), (25, {"lds_lists": 1}),
+                                    (150, {}), (150, {"select_min_k": 0}), (300, {"select_min_k": 0}), (512, {"select_min_k": 0})])
 def test_massive_exact_ties_match_the_c_oracle(native, k, opts):
     """Every vector stored 10 times: the answer is decided by the tie rule (row ascending) at every
     rank.  The C oracle sums each row in one fixed order, so its ties are exact like the kernel's."""
@@ -870,6 +871,127 @@ def test_massive_exact_ties_match_the_c_oracle(native, k, opts):
     assert idx[0, :10].tolist() == list(range(123, 50_000, 5000)) and len(set(score[0, :10].tolist())) == 1
     m_idx, _ = CO.flat_search(rows, q, k, allowed=(np.arange(50_000) % 3 != 0))
     assert midx[0].tolist() == m_idx.tolist()
+
+
+# ---- more keys tied at the k-th score than the medium-k merge sorts in LDS (1 024): its way out is the list walk ---------
+_TIE_N, _TIE_D, _TIE_COPIES = 540_000, 96, 1500
+
+
+@pytest.fixture(scope="module")
+def tie_corpus():
+    """540 k rows (every k below reaches the u8 selection scan, whose re-scored candidates the merge ranks) holding 1 500
+    identical copies of one vector and 1 500 near-duplicates of another: base + noise small enough that all 1 500 cosine
+    scores against the base lie within 2^-15 relative (in fact within 64 units of the ordered score: checked here with the
+    C oracle)."""
+    import c_oracle as CO
+
+    rows = _rows(O.SEED_CORPUS, _TIE_N, _TIE_D)
+    rng = np.random.default_rng(20240611)
+    a, b = O.normalize_rows_fast(rng.standard_normal((2, _TIE_D)).astype(np.float32))
+    where = rng.permutation(_TIE_N)[: 2 * _TIE_COPIES]
+    rows[where[:_TIE_COPIES]] = a
+    near = b[None, :] + rng.standard_normal((_TIE_COPIES, _TIE_D)).astype(np.float32) * np.float32(2e-5)
+    rows[where[_TIE_COPIES:]] = O.normalize_rows_fast(near.astype(np.float32))
+    for q, copies in ((a, where[:_TIE_COPIES]), (b, where[_TIE_COPIES:])):
+        idx, score = CO.flat_search(rows, q, _TIE_COPIES)
+        assert sorted(idx.tolist()) == sorted(copies.tolist())
+        bits = score.view(np.uint32).astype(np.int64)  # (positive floats: their bit patterns order like the ordered score)
+        assert score.min() > 0.99 and bits.max() - bits.min() < 64, (bits.max() - bits.min())
+    return rows, a, b
+
+
+def _assert_tied_answer(idx, score, o_idx, o_score, exact):
+    assert len(set(idx.tolist())) == len(idx) and np.all(idx >= 0), "a row returned twice / missing"
+    assert np.all(score[1:] <= score[:-1]), "scores not in descending order"
+    np.testing.assert_allclose(score, o_score, atol=ATOL, rtol=0)
+    if exact:  # identical rows: identical scores, the order is the tie rule (row ascending)
+        assert idx.tolist() == o_idx.tolist()
+
+
+@pytest.mark.parametrize("k,opts", [(150, {}), (300, {"select_min_k": 0}), (512, {"select_min_k": 0}), (25, {"lds_lists": 1}), (25, {})])
+def test_more_than_1024_keys_tied_at_the_kth_score(native, tie_corpus, k, opts):
+    import c_oracle as CO
+
+    rows, a, b = tie_corpus
+    queries = np.stack([a, b, rows[7]])
+    oracle = [CO.flat_search(rows, q, k) for q in queries]
+    with native.NativeIndex(_TIE_D, capacity_rows=_TIE_N) as ix:
+        ix.add(rows)
+        for name, v in opts.items():
+            ix.set_option(name, v)
+        ix.set_option("lone_host_select", 0)  # (a lone blocking query's candidates are ranked by merge_kernel, not by the host)
+        got = {}
+        for fast in (1, 0):
+            ix.set_option("merge_fast", fast)
+            lone = [ix.search(q, k) for q in queries]
+            assert ix.get_option("last_single_path") == 2  # the u8 selection scan: merge_kernel ranks its re-scored candidates
+            batch = ix.search(queries, k)  # one round of single-query passes, one merge launch for the three
+            got[fast] = lone, batch
+        for fast in (1, 0):
+            lone, batch = got[fast]
+            for qi, (o_idx, o_score) in enumerate(oracle):
+                _assert_tied_answer(lone[qi][0][0], lone[qi][1][0], o_idx, o_score, exact=qi == 0)
+                _assert_tied_answer(batch[0][qi], batch[1][qi], o_idx, o_score, exact=qi == 0)
+        for qi in range(len(queries)):  # the two merges rank the same exact scores: identical, near-duplicates included
+            assert np.array_equal(got[1][0][qi][0], got[0][0][qi][0]) and np.array_equal(got[1][0][qi][1], got[0][0][qi][1]), qi
+        assert np.array_equal(got[1][1][0], got[0][1][0]) and np.array_equal(got[1][1][1], got[0][1][1])
+
+
+def test_zero_query_ties_every_row(native):
+    """Dot products with a zero query are all +0.0: the answer is rows 0 .. k - 1 by the tie rule alone."""
+    rows = _rows(O.SEED_CORPUS, 200_000, 96)
+    q = np.zeros(96, np.float32)
+    with native.NativeIndex(96, capacity_rows=len(rows)) as ix:
+        ix.add(rows)
+        for opts in ({}, {"lone_host_select": 0}, {"merge_fast": 0}, {"scan_shadow": 0, "merge_fast": 1}, {"select_min_k": 0}):
+            for name, v in opts.items():
+                ix.set_option(name, v)
+            for k in (25, 150, 300):
+                idx, score = ix.search(q, k)
+                assert idx[0].tolist() == list(range(k)), (opts, k)
+                assert np.array_equal(score[0].view(np.uint32), np.zeros(k, np.uint32)), (opts, k)
+
+
+@pytest.mark.parametrize("k_out", [200, 512])
+def test_group_merge_of_shards_full_of_duplicates(native, k_out):
+    """8 shards sharing the device, 190 copies of one vector in each: the 8 x 140 gathered keys of the final merge are all
+    tied, more than its LDS sort holds."""
+    import c_oracle as CO
+
+    S, per, d, k = 8, 6000, 96, 140
+    rows = _rows(O.SEED_CORPUS, S * per, d)
+    rng = np.random.default_rng(77)
+    a = O.normalize_rows_fast(rng.standard_normal((1, d)).astype(np.float32))[0]
+    for s in range(S):
+        rows[s * per + rng.permutation(per)[:190]] = a
+    bounds = [s * per for s in range(S + 1)]
+    queries = np.stack([a, rows[11]])
+    expect = []
+    for q in queries:  # the union of the shards' own best 140, best first
+        cand = []
+        for s in range(S):
+            i, sc = CO.flat_search(rows[bounds[s]: bounds[s + 1]], q, k)
+            cand += [(-float(x), int(r) + bounds[s]) for r, x in zip(i, sc)]
+        cand.sort()
+        expect.append(cand[:k_out])
+    outs = []
+    for fast in (1, 0):
+        shards, grp = _attached_group(native, rows, bounds, d, merge_fast=fast)
+        try:
+            idx, score = grp.search_merged(queries, k, k_out)
+            lone = grp.search_merged(queries[0], k, k_out)
+        finally:
+            grp.close()
+            for sh in shards:
+                sh.close()
+        assert np.array_equal(lone[0][0], idx[0]) and np.array_equal(lone[1][0], score[0])
+        assert idx[0].tolist() == [r for _, r in expect[0]], f"merge_fast={fast}: tied rows out of order or repeated"
+        for qi in range(2):
+            assert len(set(idx[qi].tolist())) == k_out
+            np.testing.assert_allclose(score[qi], [-x for x, _ in expect[qi]], atol=ATOL, rtol=0)
+        assert _ids_match(idx[1], score[1], [r for _, r in expect[1]], [-x for x, _ in expect[1]]) <= 4
+        outs.append((idx, score))
+    assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1])
 
 
 def test_batched_path_exact_ties_match_the_c_oracle(native):

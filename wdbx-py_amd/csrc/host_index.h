@@ -412,12 +412,6 @@ static int plan_scan(wdbx_index* ix, int k, LaunchPlan* out, bool listed = false
   return WDBX_OK;
 }
 
-static int merge_waves_for(int k) {
-  const size_t budget = 128 * 1024;
-  int nw = (int)(budget / ((size_t)k * sizeof(u64))) - 1;
-  return std::max(1, std::min(16, nw));
-}
-
 static int record(EventPool& pool, bool enabled, hipStream_t s, bool start, uint32_t launches = 1) {
   if (!enabled) return WDBX_OK;
   if (start) {
@@ -448,17 +442,11 @@ static int launch_merge(wdbx_index* ix, const MergeArgs& m_in, int nq) {
     m.done_ticket = ix->d_ticket;
     ++ix->done_signals;
   }
-  const int nw = merge_waves_for(m.k);
-  size_t lds = (size_t)(nw + 1) * m.k * sizeof(u64);
-  if (m.k > MERGE_FAST_K && m.k <= MERGE_MID_K) lds = std::max(lds, (size_t)MERGE_MID_CAP * sizeof(u64));  // (its LDS sort)
-  const bool reg = m.k <= 128 && !ix->opt_lds_lists;
-  void (*fn)(MergeArgs) = reg ? merge_kernel<true> : merge_kernel<false>;
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  MergeLaunch ml;  // (waves, LDS, instance: kernels_merge_select.h)
+  HIP_TRY(merge_launch_for(m.k, ix->opt_lds_lists != 0, &ml));
   int rc = record(ix->merge_ev, ix->profile, ix->stream, true);
   if (rc) return rc;
-  hipLaunchKernelGGL(fn, dim3(nq), dim3(nw * 64), lds, ix->stream, m);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(enqueue_merge(ix->stream, ml, m, nq));
   return record(ix->merge_ev, ix->profile, ix->stream, false);
 }
 
@@ -555,9 +543,7 @@ static int enqueue_search(wdbx_index* ix, const float* d_queries, int nq, int k,
     u64* const lkeys = lbase ? lbase + (size_t)(q0 % xch) * k : nullptr;  // this round's lists inside the exchange chunk
     if (select) {
       // large k: per query  scan (key per row) -> radix select -> compact -> sort
-      const uint32_t sgrid_rows = (uint32_t)std::min<uint64_t>((ix->n + 255) / 256, (uint64_t)ix->cu_count * 16);
-      uint32_t npow2 = 2;
-      while (npow2 < (uint32_t)k) npow2 <<= 1;
+      const uint32_t sgrid_rows = radix_select_grid(ix->n, ix->cu_count);
       // On the u8 selection scan the chain below ranks the query's re-scored CANDIDATES; the key-per-row fp32 scan
       // is then only the conditional repair of an overflowed candidate buffer, and a device-side descriptor picks
       // which of the two the chain reads.
@@ -599,14 +585,8 @@ static int enqueue_search(wdbx_index* ix, const float* d_queries, int nq, int k,
         if (u8)
           hipLaunchKernelGGL(select_source_kernel, dim3(1), dim3(64), 0, ix->stream, src, (const uint32_t*)ix->d_count,
                              ix->last_batch_cap, (const u64*)ix->d_cand, (const u64*)ix->d_dump, (u64)ix->n);
-        hipLaunchKernelGGL(select_init_kernel, dim3(1), dim3(256), 0, ix->stream, ix->d_state, (uint32_t)k);
-        for (int shift = 56; shift >= 0; shift -= 8) {
-          hipLaunchKernelGGL(radix_hist_kernel, dim3(sgrid), dim3(256), 0, ix->stream, (const u64*)ix->d_dump, (u64)ix->n,
-                             ix->d_state, shift, (const SelectSrc*)src);
-          hipLaunchKernelGGL(radix_pick_kernel, dim3(1), dim3(256), 0, ix->stream, ix->d_state, shift);
-        }
-        hipLaunchKernelGGL(radix_compact_kernel, dim3(sgrid), dim3(256), 0, ix->stream, (const u64*)ix->d_dump, (u64)ix->n,
-                           ix->d_state, ix->d_sel, (uint32_t)k, (const SelectSrc*)src);
+        HIP_TRY(enqueue_radix_select(ix->stream, (const u64*)ix->d_dump, (u64)ix->n, (const SelectSrc*)src, (SelectState*)ix->d_state,
+                                     (u64*)ix->d_sel, (uint32_t)k, sgrid));
         MergeArgs m = {};
         m.k = k;
         m.metric = ix->metric;
@@ -614,9 +594,7 @@ static int enqueue_search(wdbx_index* ix, const float* d_queries, int nq, int k,
         m.out_keys = sharded ? lkeys + (size_t)q * k : nullptr;
         m.out_idx = sharded ? nullptr : d_out_idx + (size_t)(q0 + q) * k;
         m.out_score = sharded ? nullptr : d_out_score + (size_t)(q0 + q) * k;
-        hipLaunchKernelGGL(sort_out_kernel, dim3(1), dim3(1024), (size_t)npow2 * sizeof(u64), ix->stream,
-                           (const u64*)ix->d_sel, (const SelectState*)ix->d_state, m, npow2);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(enqueue_sort_out(ix->stream, (const u64*)ix->d_sel, (const SelectState*)ix->d_state, m));
         if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
       }
     } else if (ix->n) {
@@ -1054,12 +1032,8 @@ static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, in
       if (nv != 1) return fail(WDBX_E_STATE, "large-k selection runs one query per call");
       if ((rc = grow((void**)&ix->d_state, &ix->state_bytes, sizeof(SelectState)))) return rc;
       const uint32_t hgrid = std::min<uint32_t>((ngroups + 255) / 256, (uint32_t)ix->cu_count * 4);
-      hipLaunchKernelGGL(select_init_kernel, dim3(1), dim3(256), 0, ix->stream, ix->d_state, (uint32_t)k);
-      for (int shift = 56; shift >= 0; shift -= 8) {
-        hipLaunchKernelGGL(radix_hist_kernel, dim3(hgrid), dim3(256), 0, ix->stream, (const u64*)ix->d_halfmax, (u64)ngroups,
-                           ix->d_state, shift, (const SelectSrc*)nullptr);
-        hipLaunchKernelGGL(radix_pick_kernel, dim3(1), dim3(256), 0, ix->stream, ix->d_state, shift);
-      }
+      HIP_TRY(enqueue_radix_select(ix->stream, (const u64*)ix->d_halfmax, (u64)ngroups, nullptr, (SelectState*)ix->d_state, nullptr,
+                                   (uint32_t)k, hgrid));
       hipLaunchKernelGGL(select_kth_value_kernel, dim3(1), dim3(64), 0, ix->stream, (const SelectState*)ix->d_state, (uint32_t)k,
                          ix->d_tau);
       HIP_TRY(hipGetLastError());
@@ -1067,8 +1041,7 @@ static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, in
       // a threshold from the k-th largest sampled lower bound (at most 2^-15 relative below it: kth_score_kernel)
       KthArgs ka = {ix->d_halfmax, (u64)ngroups, ngroups, k, ix->d_tau};
       if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
-      hipLaunchKernelGGL(kth_score_kernel, dim3(nv), dim3(1024), 0, ix->stream, ka);
-      HIP_TRY(hipGetLastError());
+      HIP_TRY(enqueue_kth(ix->stream, ka, nv));
       if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
     } else {
       MergeArgs m = {};
@@ -1287,8 +1260,7 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
       // a threshold from the k-th largest sampled lower bound (at most 2^-15 relative below it: kth_score_kernel)
       KthArgs ka = {ix->d_halfmax, (u64)ngroups, ngroups, k, ix->d_tau};
       if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
-      hipLaunchKernelGGL(kth_score_kernel, dim3(nv), dim3(1024), 0, ix->stream, ka);
-      HIP_TRY(hipGetLastError());
+      HIP_TRY(enqueue_kth(ix->stream, ka, nv));
       if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
     } else {
       MergeArgs m = {};
@@ -1917,8 +1889,7 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
     if (rw * sample_tiles <= KTH_R * 1024 && !ix->opt_lds_lists) {
       KthArgs ka = {ix->d_halfmax, (u64)rw * sample_tiles, rw * sample_tiles, k, ix->d_tau};
       if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
-      hipLaunchKernelGGL(kth_score_kernel, dim3(nv), dim3(1024), 0, ix->stream, ka);
-      HIP_TRY(hipGetLastError());
+      HIP_TRY(enqueue_kth(ix->stream, ka, nv));
       if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
     } else {
       MergeArgs m = {};

@@ -1,5 +1,7 @@
 // kernels_merge_select.h -- merge of partial top-k lists; exact radix select for large k.
-// Part of the single translation unit wdbx_hip.hip (included there, in order); not a standalone header.
+// Part of the single translation unit wdbx_hip.hip (included there, in order); not a standalone header.  The tests' kernel
+// harness (tests/kernel_harness/rank_harness.hip) includes it as well, behind kernels_common.h: the kernels and the host
+// helpers below them need nothing else of the library.
 
 // ------------------------------------------------------------------------------------------------
 // A threshold from up to R * blockDim.x ordered 32-bit values, R per thread in REGISTERS (0 = absent), by the whole
@@ -294,6 +296,9 @@ __global__ __launch_bounds__(1024) void merge_kernel(MergeArgs a) {
       return;
     }
     __syncthreads();  // (the list walk reuses the LDS)
+    // ... in which the LDS lists (REG == false) lie where the keys were just compacted: empty them again.  Each wave its own
+    // list, which only that wave touches until the barrier behind the walk, so no further barrier here.
+    if constexpr (!REG) top.init(lds_lists + (size_t)wave * k, k, lane);
   }
   u64 thr = 0;
   for (uint32_t p0 = wave * 64; p0 < P; p0 += nwaves * 64) {
@@ -326,7 +331,38 @@ __global__ __launch_bounds__(1024) void merge_kernel(MergeArgs a) {
   merge_signal_done(a, wave == 0);
 }
 
+// Host side of a merge launch, free of any index state (the library's launch_merge and the tests' kernel harness both go
+// through it): the workgroup's waves (one TopList of k keys each plus the final one within 128 KiB of LDS; 16 waves up to
+// k = 963, which is also where the register paths end: they need blockDim.x == 1024), the dynamic LDS and the instance.
+static int merge_waves_for(int k) {
+  const size_t budget = 128 * 1024;
+  int nw = (int)(budget / ((size_t)k * sizeof(u64))) - 1;
+  return std::max(1, std::min(16, nw));
+}
 
+struct MergeLaunch {
+  void (*fn)(MergeArgs);
+  int waves;
+  size_t lds;
+};
+
+// lds_lists: the per-wave lists in LDS whatever k is (option lds_lists); else in registers up to k = 128
+static hipError_t merge_launch_for(int k, bool lds_lists, MergeLaunch* out) {
+  MergeLaunch ml;
+  ml.waves = merge_waves_for(k);
+  ml.lds = (size_t)(ml.waves + 1) * k * sizeof(u64);
+  if (k > MERGE_FAST_K && k <= MERGE_MID_K) ml.lds = std::max(ml.lds, (size_t)MERGE_MID_CAP * sizeof(u64));  // (its LDS sort)
+  const bool reg = k <= 128 && !lds_lists;
+  ml.fn = reg ? merge_kernel<true> : merge_kernel<false>;
+  *out = ml;
+  if (ml.lds > 64 * 1024) return hipFuncSetAttribute((const void*)ml.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ml.lds);
+  return hipSuccess;
+}
+
+static hipError_t enqueue_merge(hipStream_t stream, const MergeLaunch& ml, const MergeArgs& m, int nq) {
+  hipLaunchKernelGGL(ml.fn, dim3(nq), dim3(ml.waves * 64), ml.lds, stream, m);
+  return hipGetLastError();
+}
 
 // A threshold from the k-th largest SCORE among n keys per query (0 = no key): out_kth[q] <= that score, short of it by less
 // than 2^-15 relative (block_kth_threshold); -inf when fewer than k keys.  For n up to KTH_R per thread.
@@ -351,6 +387,12 @@ __global__ __launch_bounds__(1024) void kth_score_kernel(KthArgs a) {
   __syncthreads();
   const uint32_t ord = block_kth_threshold<KTH_R>(v, (uint32_t)a.k, s_k);
   if (threadIdx.x == 0) a.out_kth[blockIdx.x] = ord ? ord2f(ord) : -INFINITY;
+}
+
+// (host; the library and the tests' kernel harness) one workgroup of 1024 threads per query, a.n <= KTH_R * 1024
+static hipError_t enqueue_kth(hipStream_t stream, const KthArgs& a, int nq) {
+  hipLaunchKernelGGL(kth_score_kernel, dim3(nq), dim3(1024), 0, stream, a);
+  return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -511,4 +553,32 @@ __global__ __launch_bounds__(1024) void sort_out_kernel(const u64* sel, const Se
       a.out_score[i] = key ? s : 0.0f;
     }
   }
+}
+
+// Host side of the chain, free of any index state (the library and the tests' kernel harness both go through it).
+// grid of the passes over one key per row
+static uint32_t radix_select_grid(uint64_t n, int cu_count) {
+  return (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)cu_count * 16);
+}
+
+// init, the eight histogram + pick passes and -- with sel != null -- the compaction of the keys at or above the cut into
+// sel[0 .. k).  Afterwards state->prefix is the k-th largest key (the smallest valid key when fewer than k are valid) and
+// state->total the number of valid keys.  src != null: the kernels read keys / n from *src on the device instead.
+static hipError_t enqueue_radix_select(hipStream_t stream, const u64* keys, u64 n, const SelectSrc* src, SelectState* state,
+                                       u64* sel, uint32_t k, uint32_t grid) {
+  hipLaunchKernelGGL(select_init_kernel, dim3(1), dim3(256), 0, stream, state, k);
+  for (int shift = 56; shift >= 0; shift -= 8) {
+    hipLaunchKernelGGL(radix_hist_kernel, dim3(grid), dim3(256), 0, stream, keys, n, state, shift, src);
+    hipLaunchKernelGGL(radix_pick_kernel, dim3(1), dim3(256), 0, stream, state, shift);
+  }
+  if (sel) hipLaunchKernelGGL(radix_compact_kernel, dim3(grid), dim3(256), 0, stream, keys, n, state, sel, k, src);
+  return hipGetLastError();
+}
+
+// the selected keys sorted into the outputs named by m (one query: m's output pointers are that query's)
+static hipError_t enqueue_sort_out(hipStream_t stream, const u64* sel, const SelectState* state, const MergeArgs& m) {
+  uint32_t npow2 = 2;
+  while (npow2 < (uint32_t)m.k) npow2 <<= 1;
+  hipLaunchKernelGGL(sort_out_kernel, dim3(1), dim3(1024), (size_t)npow2 * sizeof(u64), stream, sel, state, m, npow2);
+  return hipGetLastError();
 }
