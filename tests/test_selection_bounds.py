@@ -13,14 +13,19 @@ import pytest
 
 
 def quantise_u8(rows):
-    """kernels_scan8.h::rows_to_u8_kernel: s = max|c| / 127, u = rint(c * (127 / max|c|)) + 128 (float32)."""
+    """kernels_scan8.h::rows_to_u8_kernel: s = max|c| / 127, u = rint(c * (127 / max|c|)) + 128 (float32).  A row with a NaN
+    element: scale -1, a row with an infinite element (and no NaN): scale NaN; both all bytes 128."""
     rows = rows.astype(np.float32)
+    has_nan = np.isnan(rows).any(axis=1)
+    finite = np.isfinite(rows).all(axis=1)
+    rows = np.where(finite[:, None], rows, np.float32(0))
     mx = np.max(np.abs(rows), axis=1).astype(np.float32)
     vanishing = mx < np.float32(1.2e-30)                      # 127 / max would overflow: quantise to 0, widen the scale
     sc = np.where(vanishing, np.float32(2.0) * mx, mx / np.float32(127.0)).astype(np.float32)
     with np.errstate(over="ignore", divide="ignore"):
         inv = np.where(vanishing, 0, np.float32(127.0) / np.where(vanishing, 1, mx)).astype(np.float32)
     n = np.clip(np.rint(rows * inv[:, None]).astype(np.float32), -127, 127)
+    sc = np.where(has_nan, np.float32(-1.0), np.where(finite, sc, np.float32(np.nan))).astype(np.float32)
     return (n + 128).astype(np.uint8), sc
 
 
@@ -128,15 +133,21 @@ def test_two_phase_selection_never_loses_a_top_k_row(seed):
 # ACTUAL residual norms:  |c.q - s_g s_q D| <= a_g E_q + b_g M_q
 # ------------------------------------------------------------------------------------------------
 def quantise_i8_groups(rows, group=64):
-    """kernels_tiles8.h::rows_to_i8g_kernel (float32 arithmetic): per group s_g = max|c| / 127 over its finite rows,
-    n = rint(c * (127 / max)), residual delta = c * inv - n; a_g = s_g max|n|_2 * 1.0002, b_g = s_g (max|delta|_2 * 1.0002
-    + 2e-5 sqrt(d)).  Returns n (int8), and per ROW the group's (s_g, a_g, b_g)."""
+    """kernels_tiles8.h::rows_to_i8g_kernel (float32 arithmetic): per group s_g = max|c| / 127 over its FINITE rows (a row with
+    a NaN or infinite element is left out of the maximum and quantises to zeros with a zero residual),
+    n = rint(c * (127 / max)), residual delta = c * inv - n; a_g = s_g max|n|_2 * 1.0002 (+inf when the group holds a row with
+    an infinite element and no NaN), b_g = s_g (max|delta|_2 * 1.0002 + 2e-5 sqrt(d)).  Returns n (int8), and per ROW the
+    group's (s_g, a_g, b_g)."""
     rows = rows.astype(np.float32)
     nrow, d = rows.shape
     n_out = np.zeros((nrow, d), np.int8)
     s_r, a_r, b_r = (np.zeros(nrow, np.float32) for _ in range(3))
     for g0 in range(0, nrow, group):
         blk = rows[g0:g0 + group]
+        has_nan = np.isnan(blk).any(axis=1)
+        ok = np.isfinite(blk).all(axis=1)
+        g_inf = bool((~ok & ~has_nan).any())
+        blk = np.where(ok[:, None], blk, np.float32(0))
         mx = np.float32(np.max(np.abs(blk))) if blk.size else np.float32(0)
         vanishing = mx < np.float32(1.2e-30)
         s_g = np.float32(2.0) * mx if vanishing else mx / np.float32(127.0)
@@ -144,20 +155,24 @@ def quantise_i8_groups(rows, group=64):
             inv = np.float32(0) if vanishing else np.float32(127.0) / mx
             x = np.clip(np.rint(blk * inv), -127, 127).astype(np.float32)
             res = (np.full_like(blk, 0.5 if mx > 0 else 0.0) if vanishing else blk * inv - x).astype(np.float32)
+        res = np.where(ok[:, None], res, np.float32(0))
         n2 = np.sqrt((x * x).sum(axis=1, dtype=np.float32).max(initial=0)).astype(np.float32)
         d2 = np.sqrt((res * res).sum(axis=1, dtype=np.float32).max(initial=0)).astype(np.float32)
         n_out[g0:g0 + group] = x.astype(np.int8)
         s_r[g0:g0 + group] = s_g
-        a_r[g0:g0 + group] = s_g * n2 * np.float32(1.0002)
+        a_r[g0:g0 + group] = np.float32(np.inf) if g_inf else s_g * n2 * np.float32(1.0002)
         b_r[g0:g0 + group] = s_g * (d2 * np.float32(1.0002) + np.float32(2e-5) * np.float32(np.sqrt(d)))
     return n_out, s_r, a_r, b_r
 
 
 def quantise_i8_query(q):
     """kernels_tiles8.h::queries_to_i8_kernel: m = rint(q * (127 / max|q|)), E = s_q (|eps|_2 * 1.0002 + 2e-5 sqrt(d) + 1e-6
-    |m|_2 * 1.0002), M = s_q (|m|_2 * 1.0002 + |eps|_2 * 1.0002 + 2e-5 sqrt(d))."""
+    |m|_2 * 1.0002), M = s_q (|m|_2 * 1.0002 + |eps|_2 * 1.0002 + 2e-5 sqrt(d)).  A query with a non-finite element: zeros,
+    s_q = 0, E = +inf."""
     q = q.astype(np.float32)
     d = q.shape[0]
+    if not np.isfinite(q).all():
+        return np.zeros(d, np.int8), np.float32(0), np.float32(np.inf), np.float32(0)
     mx = np.float32(np.max(np.abs(q)))
     vanishing = mx < np.float32(1.2e-30)
     s_q = np.float32(2.0) * mx if vanishing else mx / np.float32(127.0)

@@ -13,9 +13,13 @@ from test_selection_bounds import _datasets
 
 
 def quantise_u6(rows):
-    """kernels_scan6.h::rows_to_u6_kernel: codes, s and a per row (float32; fmaf(-s, k, x) has ONE rounding)."""
+    """kernels_scan6.h::rows_to_u6_kernel: codes, s and a per row (float32; fmaf(-s, k, x) has ONE rounding).  A row with a
+    NaN element: {-1, 0}, a row with an infinite element (and no NaN): {NaN, 0}; both all codes 32."""
     rows = rows.astype(np.float32)
     d = rows.shape[1]
+    has_nan = np.isnan(rows).any(axis=1)
+    finite = np.isfinite(rows).all(axis=1)
+    rows = np.where(finite[:, None], rows, np.float32(0))
     mx = np.max(np.abs(rows), axis=1).astype(np.float32)
     vanishing = mx < np.float32(1.2e-30)                      # 31 / max would overflow: every code 32, s = 0, a = max (sqrt(d) + 1)
     safe = np.where(vanishing, np.float32(1), mx)
@@ -28,6 +32,8 @@ def quantise_u6(rows):
     rr = (rho * rho).astype(np.float32).sum(axis=1, dtype=np.float32)
     a = (s * (np.sqrt(rr, dtype=np.float32) * np.float32(1.0005) + np.float32(1e-4))).astype(np.float32)
     a = np.where(vanishing, mx * (np.sqrt(np.float32(d)) + np.float32(1.0)), a).astype(np.float32)
+    s = np.where(has_nan, np.float32(-1.0), np.where(finite, s, np.float32(np.nan))).astype(np.float32)
+    a = np.where(finite, a, np.float32(0)).astype(np.float32)
     return (k + 32).astype(np.uint8), s, a
 
 

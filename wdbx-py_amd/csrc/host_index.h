@@ -798,17 +798,6 @@ static bool shadow_single_eligible(const wdbx_index* ix, int k, int nq_call) {
 }
 
 // ---- single queries on the u8 selection scan ---------------------------------------------------
-// row shapes the scan8 kernel is instantiated for: pieces (16 bytes each) per row = L lanes x QPL loads
-struct Scan8Shape { uint32_t pieces; int L, QPL; };
-static const Scan8Shape kScan8Shapes[] = {{8, 8, 1},   {16, 8, 2},  {24, 8, 3},   {32, 16, 2},  {48, 16, 3},
-                                           {64, 32, 2}, {96, 32, 3}, {128, 64, 2}, {192, 64, 3}, {256, 64, 4}};
-// the smallest instantiated shape that holds a row of `dim` elements (its padded byte pitch = pieces * 16)
-static const Scan8Shape* scan8_shape(uint32_t dim) {
-  for (const Scan8Shape& sh : kScan8Shapes)
-    if (sh.pieces * 16 >= dim) return &sh;
-  return nullptr;
-}
-
 static bool u8_single_eligible(const wdbx_index* ix, int k, int nq_call) {
   if (ix->opt_scan_shadow < 2) return false;  // (row masks and k >= 200 are served by the u8 scan too)
   const Scan8Shape* sh = scan8_shape((uint32_t)ix->dim);
@@ -844,48 +833,13 @@ static bool prepare_u8_shadow(wdbx_index* ix) {
     ix->pitch8 = pitch8;
   }
   if (ix->shadow8_rows < ix->n) {
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((ix->n - ix->shadow8_rows + 3) / 4, 65536);
+    const uint32_t blocks = rows_to_u8_grid(ix->n - ix->shadow8_rows);
     hipLaunchKernelGGL(rows_to_u8_kernel, dim3(blocks), dim3(256), 0, ix->stream, (const float*)ix->d_rows, (u64)ix->shadow8_rows,
                        (u64)ix->n, (uint32_t)ix->dim, (uint32_t)ix->pitch, ix->d_rows8, pitch8, ix->d_scale8);
     if (hipGetLastError() != hipSuccess) return false;
     ix->shadow8_rows = ix->n;
   }
   return true;
-}
-
-typedef void (*scan8_fn)(Scan8Args);
-template <int PHASE, int METRIC>
-static scan8_fn pick_scan8(int L, int QPL) {
-  switch (L * 10 + QPL) {
-    case 81: return scan8_kernel<8, 1, METRIC, PHASE>;
-    case 82: return scan8_kernel<8, 2, METRIC, PHASE>;
-    case 83: return scan8_kernel<8, 3, METRIC, PHASE>;
-    case 162: return scan8_kernel<16, 2, METRIC, PHASE>;
-    case 163: return scan8_kernel<16, 3, METRIC, PHASE>;
-    case 322: return scan8_kernel<32, 2, METRIC, PHASE>;
-    case 323: return scan8_kernel<32, 3, METRIC, PHASE>;
-    case 642: return scan8_kernel<64, 2, METRIC, PHASE>;
-    case 643: return scan8_kernel<64, 3, METRIC, PHASE>;
-    case 644: return scan8_kernel<64, 4, METRIC, PHASE>;
-  }
-  return nullptr;
-}
-
-// the several-queries-per-workgroup sample pass (scan8_sample4_kernel: 4 queries, 3 at QPL = 3)
-template <int METRIC>
-static scan8_fn pick_scan8_sample4(int L, int QPL) {
-  switch (L * 10 + QPL) {
-    case 81: return scan8_sample4_kernel<8, 1, METRIC>;
-    case 82: return scan8_sample4_kernel<8, 2, METRIC>;
-    case 83: return scan8_sample4_kernel<8, 3, METRIC>;
-    case 162: return scan8_sample4_kernel<16, 2, METRIC>;
-    case 163: return scan8_sample4_kernel<16, 3, METRIC>;
-    case 322: return scan8_sample4_kernel<32, 2, METRIC>;
-    case 323: return scan8_sample4_kernel<32, 3, METRIC>;
-    case 642: return scan8_sample4_kernel<64, 2, METRIC>;
-    case 643: return scan8_sample4_kernel<64, 3, METRIC>;
-  }
-  return nullptr;
 }
 
 // ---- range search (wdbx_index_range_search) -------------------------------------------------------
@@ -925,7 +879,7 @@ static int ensure_row_norms(wdbx_index* ix) {
   }
   if (ix->cn_rows == 0) HIP_TRY(hipMemsetAsync(ix->d_cnmax, 0, 4 * sizeof(uint32_t), ix->stream));
   if (ix->cn_rows < ix->n) {
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((ix->n - ix->cn_rows + 3) / 4, 65536);
+    const uint32_t blocks = row_sqnorm_grid(ix->n - ix->cn_rows);
     hipLaunchKernelGGL(row_sqnorm_kernel, dim3(blocks), dim3(256), 0, ix->stream, (const float*)ix->d_rows, (u64)ix->cn_rows,
                        (u64)ix->n, (uint32_t)ix->pitch, ix->d_cn, ix->d_cnmax);
     HIP_TRY(hipGetLastError());
@@ -980,8 +934,8 @@ static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, in
   const uint64_t shadow_bytes = (uint64_t)ix->n * pitch8;
   const int64_t wgs_auto = (nq > 1 && shadow_bytes >= (400ull << 20) && shadow_bytes <= (1ull << 30)) ? 6 : 2;  // (measured on rounds)
   const uint32_t wgs = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(ix->opt_scan8_wgs > 0 ? ix->opt_scan8_wgs : wgs_auto, 8));
-  const uint32_t grid1 = std::min<uint32_t>((groups1 + 3) / 4, (uint32_t)ix->cu_count * wgs);
-  const uint32_t grid0 = std::min<uint32_t>((ngroups + 3) / 4, (uint32_t)ix->cu_count * 4);
+  const uint32_t grid1 = scan_full_grid(groups1, (uint32_t)ix->cu_count, wgs);
+  const uint32_t grid0 = scan_sample_grid(ngroups, (uint32_t)ix->cu_count);
   const size_t pitch4 = ix->pitch / 4;
 
   for (int q0 = 0; q0 < nq; q0 += ROUND) {
@@ -1122,13 +1076,6 @@ static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, in
 }
 
 // ---- rounds of single queries on the u6 selection scan (kernels_scan6.h) ---------------------------------------
-// units in flight per wave = the largest of 8 .. 4 that divides the row's units (24 -> 8, 25 -> 5, 6 -> 6); 0 = none
-static int u6_unit_chunk(uint32_t units) {
-  for (int uc = 8; uc >= 4; --uc)
-    if (units % (uint32_t)uc == 0) return uc;
-  return 0;
-}
-
 // Where the u8 scan is eligible AND: inner product / cosine, k <= 32, no row mask, a call of several queries (a lone query
 // keeps the u8 scan's short chain), rows of whole 16-element units.  Option scan_u6: -1 = shards whose u8 shadow exceeds
 // 1 GiB (where a pass per launch is the rule and the bytes of a pass are the step), 0 = never, 1 = wherever eligible.
@@ -1163,7 +1110,7 @@ static bool prepare_u6_shadow(wdbx_index* ix) {
     ix->rows6_tiles = tiles;
   }
   if (ix->shadow6_rows < ix->n) {
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((ix->n - ix->shadow6_rows + 3) / 4, 65536);
+    const uint32_t blocks = rows_to_u6_grid(ix->n - ix->shadow6_rows);
     hipLaunchKernelGGL(rows_to_u6_kernel, dim3(blocks), dim3(256), 0, ix->stream, (const float*)ix->d_rows, (u64)ix->shadow6_rows,
                        (u64)ix->n, (uint32_t)ix->dim, (uint32_t)ix->pitch, units, ix->d_rows6,
                        (f2v*)(ix->d_rows6 + (size_t)ix->rows6_tiles * units * 192));
@@ -1171,18 +1118,6 @@ static bool prepare_u6_shadow(wdbx_index* ix) {
     ix->shadow6_rows = ix->n;
   }
   return true;
-}
-
-typedef void (*scan6_fn)(Scan6Args);
-static scan6_fn pick_scan6(int uc, bool sample) {
-  switch (uc) {
-    case 4: return sample ? scan8_u6_sample_kernel<4> : scan8_u6_kernel<4>;
-    case 5: return sample ? scan8_u6_sample_kernel<5> : scan8_u6_kernel<5>;
-    case 6: return sample ? scan8_u6_sample_kernel<6> : scan8_u6_kernel<6>;
-    case 7: return sample ? scan8_u6_sample_kernel<7> : scan8_u6_kernel<7>;
-    case 8: return sample ? scan8_u6_sample_kernel<8> : scan8_u6_kernel<8>;
-  }
-  return nullptr;
 }
 
 // nq single queries of a round, each with its own full pass over the u6 shadow: sample (4 queries per workgroup) ->
@@ -1224,8 +1159,8 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
   // 6 -> 2008, 8 -> 1990 (profiles/u6/README.md): eight waves per CU with 6 KiB in flight each keep HBM busy, more of them
   // only spread the stream over more pages at once
   const uint32_t wgs = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(ix->opt_scan8_wgs > 0 ? ix->opt_scan8_wgs : 2, 8));
-  const uint32_t grid1 = std::min<uint32_t>((tiles64 + 3) / 4, (uint32_t)ix->cu_count * wgs);
-  const uint32_t grid0 = std::min<uint32_t>((ngroups + 3) / 4, (uint32_t)ix->cu_count * 4);
+  const uint32_t grid1 = scan_full_grid(tiles64, (uint32_t)ix->cu_count, wgs);
+  const uint32_t grid0 = scan_sample_grid(ngroups, (uint32_t)ix->cu_count);
   const size_t pitch4 = ix->pitch / 4;
   const Scan8Shape* sh = scan8_shape((uint32_t)ix->dim);
   const bool one_grid = ix->opt_scan8_per_query == 0 ||
@@ -1391,7 +1326,7 @@ static bool prepare_i8g_shadow(wdbx_index* ix) {
     const u64 g0 = std::min<u64>(ix->shadowg_rows, ix->n) / 64;
     const u64 g1 = (ix->n + G8_ROWS - 1) / G8_ROWS * (G8_ROWS / 64);
     if (g1 > g0) {
-      hipLaunchKernelGGL(rows_to_i8g_kernel, dim3((uint32_t)std::min<u64>(g1 - g0, 1u << 20)), dim3(256), 0, ix->stream,
+      hipLaunchKernelGGL(rows_to_i8g_kernel, dim3(rows_to_i8g_grid(g1 - g0)), dim3(256), 0, ix->stream,
                          (const float*)ix->d_rows, g0, g1, (u64)ix->n, (uint32_t)ix->dim, (uint32_t)ix->pitch, ix->d_rows8g, pitch8,
                          ix->d_groups8, ix->d_gbad8);
       if (hipGetLastError() != hipSuccess) return false;
@@ -1868,7 +1803,7 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
     ct = std::min(ct, max_ct);
     const int gbn = 64 * ct, nv = std::min(gbn, rem);
     const float* qsrc = d_queries + (size_t)q0 * ix->pitch;
-    hipLaunchKernelGGL(queries_to_i8_kernel, dim3((uint32_t)(gbn + 3) / 4), dim3(256), 0, ix->stream, qsrc, (uint32_t)ix->dim,
+    hipLaunchKernelGGL(queries_to_i8_kernel, dim3(queries_to_i8_grid((uint32_t)gbn)), dim3(256), 0, ix->stream, qsrc, (uint32_t)ix->dim,
                        (uint32_t)ix->pitch, (uint32_t)nv, ix->d_qb8, pitch8, (uint32_t)gbn, ix->d_qpar, ix->d_tau, ix->d_count + q0, d_lost);
     HIP_TRY(hipGetLastError());
     Gemm8Args g = {};
@@ -2033,7 +1968,7 @@ static int upload_rows(wdbx_index* ix, uint64_t first, const float* rows, uint64
   const uint64_t end = first + n;
   if (first < ix->cn_rows && ix->d_cn) {
     const uint64_t e = std::min(end, ix->cn_rows);
-    hipLaunchKernelGGL(row_sqnorm_kernel, dim3((uint32_t)std::min<uint64_t>((e - first + 3) / 4, 65536)), dim3(256), 0, ix->stream,
+    hipLaunchKernelGGL(row_sqnorm_kernel, dim3(row_sqnorm_grid(e - first)), dim3(256), 0, ix->stream,
                        (const float*)ix->d_rows, (u64)first, (u64)e, (uint32_t)ix->pitch, ix->d_cn, (uint32_t*)nullptr);
     HIP_TRY(hipGetLastError());
     ix->gmax_valid = false;
@@ -2049,7 +1984,7 @@ static int upload_rows(wdbx_index* ix, uint64_t first, const float* rows, uint64
   if (first < ix->shadowg_rows && ix->d_rows8g) {  // whole groups: a group's scale depends on all of its rows
     const uint64_t e = std::min(end, ix->shadowg_rows);
     const u64 g0 = first / 64, g1 = (e + 63) / 64;
-    hipLaunchKernelGGL(rows_to_i8g_kernel, dim3((uint32_t)std::min<u64>(g1 - g0, 1u << 20)), dim3(256), 0, ix->stream,
+    hipLaunchKernelGGL(rows_to_i8g_kernel, dim3(rows_to_i8g_grid(g1 - g0)), dim3(256), 0, ix->stream,
                        (const float*)ix->d_rows, g0, g1, (u64)std::max<uint64_t>(ix->n, end), (uint32_t)ix->dim, (uint32_t)ix->pitch,
                        ix->d_rows8g, ix->pitch8g, ix->d_groups8, ix->d_gbad8);
     HIP_TRY(hipGetLastError());
@@ -2057,14 +1992,14 @@ static int upload_rows(wdbx_index* ix, uint64_t first, const float* rows, uint64
   }
   if (first < ix->shadow8_rows && ix->d_rows8) {
     const uint64_t e = std::min(end, ix->shadow8_rows);
-    hipLaunchKernelGGL(rows_to_u8_kernel, dim3((uint32_t)std::min<uint64_t>((e - first + 3) / 4, 65536)), dim3(256), 0, ix->stream,
+    hipLaunchKernelGGL(rows_to_u8_kernel, dim3(rows_to_u8_grid(e - first)), dim3(256), 0, ix->stream,
                        (const float*)ix->d_rows, (u64)first, (u64)e, (uint32_t)ix->dim, (uint32_t)ix->pitch, ix->d_rows8, ix->pitch8,
                        ix->d_scale8);
     HIP_TRY(hipGetLastError());
   }
   if (first < ix->shadow6_rows && ix->d_rows6) {
     const uint64_t e = std::min(end, ix->shadow6_rows);
-    hipLaunchKernelGGL(rows_to_u6_kernel, dim3((uint32_t)std::min<uint64_t>((e - first + 3) / 4, 65536)), dim3(256), 0, ix->stream,
+    hipLaunchKernelGGL(rows_to_u6_kernel, dim3(rows_to_u6_grid(e - first)), dim3(256), 0, ix->stream,
                        (const float*)ix->d_rows, (u64)first, (u64)e, (uint32_t)ix->dim, (uint32_t)ix->pitch, ix->units6, ix->d_rows6,
                        (f2v*)(ix->d_rows6 + (size_t)ix->rows6_tiles * ix->units6 * 192));
     HIP_TRY(hipGetLastError());

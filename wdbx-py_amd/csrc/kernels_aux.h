@@ -41,6 +41,9 @@ __global__ __launch_bounds__(256) void row_sqnorm_kernel(const float* rows, u64 
   if (lane == 0 && wcnt) atomicAdd(cn_max_bits + 2, wcnt);
 }
 
+// workgroups of a row_sqnorm_kernel launch over `rows` rows: four waves = four rows per workgroup at a time
+static inline uint32_t row_sqnorm_grid(uint64_t rows) { return (uint32_t)std::min<uint64_t>((rows + 3) / 4, 65536); }
+
 // the same statistics from the cached norms alone (after rows were overwritten in place: the running maximum and sum
 // of row_sqnorm_kernel only ever grow, so they are rebuilt): stats[0] = largest non-NaN norm (float bits), [1] = sum of
 // the finite norms, [2] = their count.  The caller zeroes the three words first.

@@ -298,3 +298,26 @@ __global__ __launch_bounds__(1024) void u6_cut_kernel(const u64* cand, const uin
 #pragma unroll
   for (int r = 0; r < KTH_R; ++r) wave_append(v[r] >= thr, key[r], out + (size_t)q * cap2, count2 + q, cap2, lane);
 }
+
+// workgroups of a rows_to_u6_kernel launch over `rows` rows: four waves = four rows per workgroup at a time
+static inline uint32_t rows_to_u6_grid(uint64_t rows) { return (uint32_t)std::min<uint64_t>((rows + 3) / 4, 65536); }
+
+// ---- host side: the instances of the scans above and which one serves a row ----------------------
+// units in flight per wave = the largest of 8 .. 4 that divides the row's units (24 -> 8, 25 -> 5, 6 -> 6); 0 = none
+static int u6_unit_chunk(uint32_t units) {
+  for (int uc = 8; uc >= 4; --uc)
+    if (units % (uint32_t)uc == 0) return uc;
+  return 0;
+}
+
+typedef void (*scan6_fn)(Scan6Args);
+static scan6_fn pick_scan6(int uc, bool sample) {
+  switch (uc) {
+    case 4: return sample ? scan8_u6_sample_kernel<4> : scan8_u6_kernel<4>;
+    case 5: return sample ? scan8_u6_sample_kernel<5> : scan8_u6_kernel<5>;
+    case 6: return sample ? scan8_u6_sample_kernel<6> : scan8_u6_kernel<6>;
+    case 7: return sample ? scan8_u6_sample_kernel<7> : scan8_u6_kernel<7>;
+    case 8: return sample ? scan8_u6_sample_kernel<8> : scan8_u6_kernel<8>;
+  }
+  return nullptr;
+}

@@ -62,6 +62,21 @@ __device__ __forceinline__ float u8_dot16(u4v v, const f4 (&q)[4], float acc) {
   return (a0 + a1) + (a2 + a3);
 }
 
+// The lower bound w - m of one row in the sample passes, with every fused operation written out: scan8_kernel<PHASE 0> and
+// scan8_sample4_kernel promise identical lower bounds, and `w - m` left to the compiler's contraction became
+// fma(s, x, -m) in the former and fma(-0.51 s, |q|_1, w) in the latter on the cosine metric -- a last-place difference.
+// (This is the form the former always had; L2 was pinned by its explicit fmas already.)
+template <int METRIC>
+__device__ __forceinline__ float scan8_lower_bound(float s, float sc, float cn, float q1, float qsum128) {
+  const float m = 0.51f * sc * q1;
+  if constexpr (METRIC == WDBX_METRIC_L2) {
+    const float w = fmaf(2.0f, sc * (s - qsum128), -cn);
+    return w - fmaf(2.0f, m, 3e-5f * cn);
+  } else {
+    return fmaf(sc, s - qsum128, -m);
+  }
+}
+
 // ABLATE (timing only, wrong answers; option scan8_ablate): 1 = a quarter of the convert + fma work per 16 bytes
 template <int L, int QPL, int METRIC, int PHASE, int ABLATE = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan8_kernel(Scan8Args a) {
@@ -100,7 +115,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
   const uint32_t last_row = a.n_rows - 1;
   // w and the bound m of one row from the lane-group sum (scale and norm were loaded with the row)
-  auto finish = [&](float s, float sc, float cn, float& m) -> float {
+  // (PHASE 0 goes through scan8_lower_bound instead)
+  [[maybe_unused]] auto finish = [&](float s, float sc, float cn, float& m) -> float {
     float w = sc * (s - qsum128);
     m = 0.51f * sc * q1;
     if constexpr (METRIC == WDBX_METRIC_L2) {
@@ -138,9 +154,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           for (int i = 0; i < QPL; ++i) s = u8_dot16(v[u][i], q[i], s);
           s = group_sum<L>(s);
           if (row[u] <= last_row) {
-            float m;
-            const float w = finish(s, sc[u], cn[u], m);
-            const float lo = w - m;
+            const float lo = scan8_lower_bound<METRIC>(s, sc[u], cn[u], q1, qsum128);
             // (NaN or negative scale: not sampled; masked-out rows cannot vouch for the threshold either)
             if (sc[u] >= 0.f && lo == lo && (!a.mask || ((a.mask[row[u] >> 5] >> (row[u] & 31)) & 1u))) best = fmaxf(best, lo);
           }
@@ -315,13 +329,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
           for (int i = 0; i < QPL; ++i) s = u8_dot16(v[u][i], q[t][i], s);
           s = group_sum<L>(s);
-          float w = sc[u] * (s - qsum128[t]);
-          float m = 0.51f * sc[u] * q1[t];
-          if constexpr (METRIC == WDBX_METRIC_L2) {
-            w = fmaf(2.0f, w, -cn[u]);
-            m = fmaf(2.0f, m, 3e-5f * cn[u]);
-          }
-          const float lo = w - m;
+          const float lo = scan8_lower_bound<METRIC>(s, sc[u], cn[u], q1[t], qsum128[t]);
           if (ok && lo == lo) best[t] = fmaxf(best[t], lo);
         }
       }
@@ -366,4 +374,62 @@ __global__ __launch_bounds__(256) void rows_to_u8_kernel(const float* rows, u64 
     }
     if (lane == 0) scale[r] = sc;
   }
+}
+
+// workgroups of a rows_to_u8_kernel launch over `rows` rows: four waves = four rows per workgroup at a time
+static inline uint32_t rows_to_u8_grid(uint64_t rows) { return (uint32_t)std::min<uint64_t>((rows + 3) / 4, 65536); }
+
+// ---- host side: the instances of the scans above and which one serves a row ----------------------
+// row shapes the scan8 kernel is instantiated for: pieces (16 bytes each) per row = L lanes x QPL loads
+struct Scan8Shape { uint32_t pieces; int L, QPL; };
+static const Scan8Shape kScan8Shapes[] = {{8, 8, 1},   {16, 8, 2},  {24, 8, 3},   {32, 16, 2},  {48, 16, 3},
+                                           {64, 32, 2}, {96, 32, 3}, {128, 64, 2}, {192, 64, 3}, {256, 64, 4}};
+// the smallest instantiated shape that holds a row of `dim` elements (its padded byte pitch = pieces * 16)
+static const Scan8Shape* scan8_shape(uint32_t dim) {
+  for (const Scan8Shape& sh : kScan8Shapes)
+    if (sh.pieces * 16 >= dim) return &sh;
+  return nullptr;
+}
+
+// grid.x of a selection pass (u8 and u6 alike), four waves per workgroup: the sample pass takes one sampled 64-row group per
+// wave at a time and at most 4 workgroups per CU; the full pass one wave-pass of rows (u8: 64 / L rows, u6: a 64-row tile)
+// per wave at a time and `wgs` workgroups per CU
+static inline uint32_t scan_sample_grid(uint32_t ngroups, uint32_t cus) { return std::min<uint32_t>((ngroups + 3) / 4, cus * 4); }
+static inline uint32_t scan_full_grid(uint32_t wave_passes, uint32_t cus, uint32_t wgs) {
+  return std::min<uint32_t>((wave_passes + 3) / 4, cus * wgs);
+}
+
+typedef void (*scan8_fn)(Scan8Args);
+template <int PHASE, int METRIC>
+static scan8_fn pick_scan8(int L, int QPL) {
+  switch (L * 10 + QPL) {
+    case 81: return scan8_kernel<8, 1, METRIC, PHASE>;
+    case 82: return scan8_kernel<8, 2, METRIC, PHASE>;
+    case 83: return scan8_kernel<8, 3, METRIC, PHASE>;
+    case 162: return scan8_kernel<16, 2, METRIC, PHASE>;
+    case 163: return scan8_kernel<16, 3, METRIC, PHASE>;
+    case 322: return scan8_kernel<32, 2, METRIC, PHASE>;
+    case 323: return scan8_kernel<32, 3, METRIC, PHASE>;
+    case 642: return scan8_kernel<64, 2, METRIC, PHASE>;
+    case 643: return scan8_kernel<64, 3, METRIC, PHASE>;
+    case 644: return scan8_kernel<64, 4, METRIC, PHASE>;
+  }
+  return nullptr;
+}
+
+// the several-queries-per-workgroup sample pass (scan8_sample4_kernel: 4 queries, 3 at QPL = 3)
+template <int METRIC>
+static scan8_fn pick_scan8_sample4(int L, int QPL) {
+  switch (L * 10 + QPL) {
+    case 81: return scan8_sample4_kernel<8, 1, METRIC>;
+    case 82: return scan8_sample4_kernel<8, 2, METRIC>;
+    case 83: return scan8_sample4_kernel<8, 3, METRIC>;
+    case 162: return scan8_sample4_kernel<16, 2, METRIC>;
+    case 163: return scan8_sample4_kernel<16, 3, METRIC>;
+    case 322: return scan8_sample4_kernel<32, 2, METRIC>;
+    case 323: return scan8_sample4_kernel<32, 3, METRIC>;
+    case 642: return scan8_sample4_kernel<64, 2, METRIC>;
+    case 643: return scan8_sample4_kernel<64, 3, METRIC>;
+  }
+  return nullptr;
 }

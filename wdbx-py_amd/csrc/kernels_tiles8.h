@@ -677,6 +677,9 @@ __global__ __launch_bounds__(256) void rows_to_i8g_kernel(const float* rows, u64
   }
 }
 
+// workgroups of a rows_to_i8g_kernel launch over `groups` 64-row groups: one each
+static inline uint32_t rows_to_i8g_grid(uint64_t groups) { return (uint32_t)std::min<uint64_t>(groups, 1u << 20); }
+
 // queries [nv, pitch] fp32 -> the i8 query block [gbn][pitch8] (signed bytes, zero padded) and its parameters
 // {s_q, E_q, M_q, 1 / s_q} (E, M rounded up; a non-finite query gets E = +inf: every row becomes a candidate and the exact
 // pass decides); one wave per query
@@ -733,6 +736,9 @@ __global__ __launch_bounds__(256) void queries_to_i8_kernel(const float* q, uint
     qpar[r] = f4{s_q, E, M, s_q > 0.f ? 1.0f / s_q : 0.f};
   }
 }
+
+// workgroups of a queries_to_i8_kernel launch for a block of `gbn` queries (padded ones included): one wave per query
+static inline uint32_t queries_to_i8_grid(uint32_t gbn) { return (gbn + 3) / 4; }
 
 // the waves' candidate pairs -> the per-query candidate buffers the exact pass reads: cand[q][count[q]++] = key(row).
 // One workgroup per 16 producing waves.  A wave that ran out of room (a tile whose every row is a candidate for every
