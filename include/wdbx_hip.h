@@ -184,6 +184,19 @@ int wdbx_index_synchronize(wdbx_index* idx);
  * wdbx_index_search_device. */
 int wdbx_index_search_batch_device(wdbx_index* idx, const float* d_queries, int nq, int k,
                                    int64_t* d_out_idx, float* d_out_score);
+/* The same with a row mask from the HOST (uint32 words, bit r % 32 of word r / 32 = row r may be returned;
+ * mask_word_count >= ceil(rows / 32) or WDBX_E_INVALID): the filter push-down of wdbx_index_search_masked for a whole
+ * batch.  When the int8 tiles are what would run (gemm_bf16 = 3, gemm8_variant = 0, k below the select range; option
+ * gemm_masked, default 1) the batch is ONE masked pass: the mask becomes the call's bad-row table, masked-out rows neither
+ * vouch for the sampled threshold nor enter the candidate lists, and the sample grows with 1 / (allowed fraction)
+ * (get_option "last_batch_masked" == 1, "last_batch_allowed_rows").  Otherwise the queries take the masked per-query
+ * paths.  Exact either way.  The mask is copied before the call returns and applies to this call only.
+ * wdbx_index_batch_status describes this call when it ran the masked pass (last_batch_masked == 1); after the per-query
+ * fall-back it describes that path's last round of queries, as after wdbx_index_search_device.
+ * wdbx_index_search_masked / _masked_n and the group's masked calls take the same pass from gemm_min_queries queries on. */
+int wdbx_index_search_batch_masked_device(wdbx_index* idx, const float* d_queries, int nq, int k,
+                                          const uint32_t* mask_words, uint64_t mask_word_count,
+                                          int64_t* d_out_idx, float* d_out_score);
 /* synchronises; per query the number of candidates the filter kept (out_counts[nq], may be null),
  * the buffer capacity, and how many queries exceeded it.  Since round 3 such queries are re-run exactly ON THE DEVICE by
  * conditional launches queued behind their block (get_option "last_batch_repaired" == 1; option "batch_repair"): the
@@ -302,9 +315,9 @@ int wdbx_index_probe_read(wdbx_index* idx, int nontemporal, int blocks, int reps
  * scan_blocked, scan_generic, scan_force_ragged, exchange_batch, lds_lists, merge_fast (1: merges whose keys fit the registers are ranked there, default; 0: always the list walk), scan_one_grid (1: a round of several queries on the fp32 scan over a corpus of at most 1 GiB is one grid with a row per query, default; 0: a launch per query), poll_done (1: a blocking call of up to 32 queries whose chain ends in a final merge polls a word that kernel writes into the mapped staging slot, default; 0: always waits on its event), zero_copy, wg_merge, select_min_k,
  * scan_shadow (2 u8 selection scan / 1 bf16 tiles / 0 fp32 scan; range search: 2 u8 selection, below 2 the fp32 range scan), scan8_wgs, single_min_rows,
  * range_min_rows (rows from which a range search takes the u8 selection scan, default 131 072), gemm_bf16 (tile family
- * 3/2/1/0 as above), gemm_ct, gemm_l2, gemm_l2_i8, gemm8_variant, gemm8_refine (1: second selection stage of the i8 tiles, default), batch_repair, scan8_per_query, scan8_sample4 (1: a round's sample pass serves 3-4 queries per workgroup when the sample is too large for the L2s; 2: always; 0: never), gemm_min_queries, gemm_min_rows, gemm_min_work (below gemm_min_rows: the tiles from queries x rows >= this, default 800000; 0: never), gemm_sample_div, group_bounds.
+ * 3/2/1/0 as above), gemm_ct, gemm_l2, gemm_l2_i8, gemm8_variant, gemm8_refine (1: second selection stage of the i8 tiles, default), batch_repair, scan8_per_query, scan8_sample4 (1: a round's sample pass serves 3-4 queries per workgroup when the sample is too large for the L2s; 2: always; 0: never), gemm_min_queries, gemm_min_rows, gemm_min_work (below gemm_min_rows: the tiles from queries x rows >= this, default 800000; 0: never), gemm_sample_div, gemm_masked (1: a masked call with enough queries is one masked pass over the int8 tiles, default; 0: masked per-query scans), group_bounds.
  * get_option also answers the read-only names: last_gemm_family (0/1/2/3: what the last batch ran on),
- * last_single_path (0 fp32 scan / 1 bf16 tiles / 2 u8 selection scan), last_range_path (0 fp32 range scan / 2 u8 selection + exact filter), last_sample_qn (queries per workgroup of the last u8 sample launch: 1, 3 or 4), last_batch_repaired, shadow_rows + shadow_bytes (bf16 copy),
+ * last_single_path (0 fp32 scan / 1 bf16 tiles / 2 u8 selection scan), last_range_path (0 fp32 range scan / 2 u8 selection + exact filter), last_sample_qn (queries per workgroup of the last u8 sample launch: 1, 3 or 4), last_batch_repaired, last_batch_masked (1: the last batch ran the masked tile pass), last_batch_allowed_rows (the rows its mask allowed), shadow_rows + shadow_bytes (bf16 copy),
  * shadow8_rows + shadow8_bytes (u8 copy), shadowg_rows + shadowg_bytes (group-scaled i8 copy), group_bounds_active,
  * exchanges (all-gather + merge steps this handle's per-rank communicator has enqueued), device_bytes_resident (every device
  * allocation of the handle: fp32 rows, shadow copies and their tables, scratch). */

@@ -341,12 +341,11 @@ static int group_enqueue_search(wdbx_group* g, int first, int nq, int k, int k_o
       const auto stage = [&]() -> int {  // this shard's local stage
         int r2;
         if (masks && masks[s] && ix->n) {
-          const size_t words = (size_t)((ix->n + 31) / 32);
-          if ((r2 = grow((void**)&ix->d_mask, &ix->mask_bytes, words * sizeof(uint32_t)))) return r2;
-          HIP_TRY(hipMemcpyAsync(ix->d_mask, masks[s], words * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
-          ix->active_mask = ix->d_mask;
+          if ((r2 = set_active_mask(ix, masks[s]))) return r2;
         }
-        if (allow_batch && ix->n && !ix->active_mask && !use_select(ix, k) && ix->opt_batch_repair && gemm_eligible(ix, c, k)) {
+        // (a shard with a row mask: one MASKED pass when the int8 tiles are what would run there; a null mask entry: unmasked)
+        if (allow_batch && ix->n && !use_select(ix, k) && ix->opt_batch_repair && gemm_eligible(ix, c, k) &&
+            (!ix->active_mask || masked_tiles_ready(ix, k))) {
           // enough queries for ONE matrix-core pass over this shard (i8 / bf16 selection tiles + exact re-scoring, overflowed
           // queries repaired by conditional launches): the shard's lists come out as keys all the same
           return enqueue_search_gemm(ix, q, c, k, nullptr, nullptr, SEARCH_FINAL, -1, keys);

@@ -53,6 +53,12 @@ struct wdbx_index {
   uint32_t* d_mask = nullptr;
   size_t mask_bytes = 0;
   const uint32_t* active_mask = nullptr;  // set only for the duration of a masked search (under the mutex)
+  uint64_t mask_allowed = 0;              // ... and how many of the rows it allows (popcount of the host mask: set_active_mask)
+  // the int8 tiles' bad-row table of ONE masked batch: d_gbad8 | ~mask (gbad_with_mask_kernel); d_gbad8 itself never changes
+  u64* d_call_bad = nullptr;
+  size_t call_bad_bytes = 0;
+  bool last_batch_masked = false;         // the last batch ran the masked tile pass
+  uint64_t last_batch_allowed = 0;        // ... over this many allowed rows
   // batched (GEMM) path scratch
   float* d_qblock = nullptr;
   size_t qblock_bytes = 0;
@@ -156,7 +162,7 @@ struct wdbx_index {
           opt_gemm8_refine = 1, opt_scan8_sample4 = 1, opt_gemm_l2 = 1, opt_gemm_l2_i8 = 1, opt_force_ragged = 0,
           opt_gemm_ct = 0, opt_wg_merge = 1, opt_zero_copy = 1, opt_lone_host_select = 1, opt_lds_lists = 0,
           opt_merge_fast = 1, opt_poll_done = 1, opt_scan_one_grid = 1, opt_select_min_k = 200, opt_gemm_min_nq = 4, opt_gemm_min_rows = 65536, opt_gemm_min_work = 800000,
-          opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0;
+          opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0, opt_gemm_masked = 1;
 };
 
 struct DeviceGuard {
@@ -182,6 +188,26 @@ static int grow(void** p, size_t* have, size_t need) {
         HIP_TRY(hipFree(old));
         return WDBX_OK;
       });
+}
+
+// A call's row mask (uint32 words, bit r % 32 of word r / 32 = row r may be returned; the caller has checked that it holds
+// ceil(rows / 32) words): to the handle's one mask buffer, behind the stream's earlier work.  The caller keeps the handle's
+// mutex and resets active_mask at the end of the call.  The allowed rows are counted here, on the host copy (bits past the
+// last row do not count): the batched dispatch sizes its sample by them without asking the device.
+static int set_active_mask(wdbx_index* ix, const uint32_t* mask_words) {
+  const size_t words = (size_t)((ix->n + 31) / 32);
+  int rc = grow((void**)&ix->d_mask, &ix->mask_bytes, words * sizeof(uint32_t));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(ix->d_mask, mask_words, words * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+  uint64_t allowed = 0;
+  for (size_t w = 0; w + 1 < words; ++w) allowed += (uint64_t)__builtin_popcount(mask_words[w]);
+  if (words) {
+    const uint32_t tail = (uint32_t)(ix->n & 31);
+    allowed += (uint64_t)__builtin_popcount(mask_words[words - 1] & (tail ? (1u << tail) - 1u : ~0u));
+  }
+  ix->mask_allowed = allowed;
+  ix->active_mask = ix->d_mask;
+  return WDBX_OK;
 }
 
 // ---- scan dispatch ------------------------------------------------------------------------------
@@ -728,7 +754,7 @@ static int enqueue_batch_repair(wdbx_index* ix, const float* qsrc, int nv, int k
   sa.rows = (const f4*)ix->d_rows;
   sa.query = (const f4*)qsrc;
   sa.partials = ix->d_partials;
-  sa.mask = nullptr;
+  sa.mask = ix->active_mask;  // (a masked batch: its overflowed queries are repaired by the masked scan)
   sa.n_rows = (uint32_t)ix->n;
   sa.pitch4 = (uint32_t)(ix->pitch / 4);
   sa.groups = lp.groups;
@@ -1273,12 +1299,17 @@ static inline int i8g_max_ct(const wdbx_index* ix) {
   const uint32_t p = i8g_pitch(ix);
   return p * 256u <= (uint32_t)G8_LDS_B_MAX ? 4 : p * 128u <= (uint32_t)G8_LDS_B_MAX ? 2 : p * 64u <= (uint32_t)G8_LDS_B_MAX ? 1 : 0;
 }
-static bool i8_tiles_eligible(const wdbx_index* ix) {
-  if (ix->opt_gemm_bf16 < 3 || ix->active_mask) return false;
+static bool i8_tiles_shape_ok(const wdbx_index* ix) {  // (everything but the row mask)
+  if (ix->opt_gemm_bf16 < 3) return false;
   if (ix->metric == WDBX_METRIC_L2 && (!ix->opt_gemm_l2 || !ix->opt_gemm_l2_i8)) return false;
   if (i8g_max_ct(ix) == 0) return false;
   // short rows: the padded i8 image (128-byte multiples) must be clearly smaller than the fp32 row
   return (uint64_t)i8g_pitch(ix) * 10 <= (uint64_t)ix->pitch * 4 * 8;
+}
+// (a row mask: the masked full pass exists for the product forms only -- option gemm_masked = 0 keeps masked calls off the tiles)
+static bool i8_tiles_eligible(const wdbx_index* ix) {
+  if (ix->active_mask && !(ix->opt_gemm_masked > 0 && ix->opt_gemm8_variant == 0)) return false;
+  return i8_tiles_shape_ok(ix);
 }
 
 // Allocates / refreshes shadow copy G for the rows added since the last batch (whole 64-row groups: the group that was
@@ -1336,6 +1367,13 @@ static bool prepare_i8g_shadow(wdbx_index* ix) {
     ix->gref_valid = false;
   }
   return true;
+}
+// A call WITH a row mask may take the batched path only when the int8 tiles are what would run (no other tile family reads
+// masks), in their product form, with k below the select range; their shadow copy must be in place (no room: not eligible).
+// Everything else keeps the per-query paths.  (Looked at before or after active_mask is set: the answer is the same.)
+static bool masked_tiles_ready(wdbx_index* ix, int k) {
+  if (ix->opt_gemm_masked <= 0 || ix->opt_gemm8_variant != 0 || use_select(ix, k) || !ix->n) return false;
+  return i8_tiles_shape_ok(ix) && prepare_i8g_shadow(ix);
 }
 static inline uint32_t gemm_tile_rows(int family) { return family == GEMM_FP32 ? GB_M : GW_M; }
 
@@ -1413,8 +1451,11 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
   if (ix->n >= 0xFFFFFF00ull) return fail(WDBX_E_INVALID, "shard holds too many rows for 32-bit row keys");
   int rc;
   ix->last_batch_repaired = false;
+  ix->last_batch_masked = false;
   if (count_slot < 0 && i8_tiles_eligible(ix) && prepare_i8g_shadow(ix))
     return enqueue_search_gemm8(ix, d_queries, nq, k, d_out_idx, d_out_score, mode, keys_out);
+  // (the other tile families read no row mask: their callers ask masked_tiles_ready first)
+  if (ix->active_mask) return fail(WDBX_E_STATE, "a row mask on the batched path needs the int8 tiles");
   int family = gemm_family(ix);
   // short rows: the padded shadow would be no smaller than the fp32 rows, so the tiles read those
   if (family == GEMM_BF16_SHADOW && ((uint64_t)ix->pitch + 127) / 128 * 128 >= 2 * (uint64_t)ix->pitch) family = GEMM_BF16;
@@ -1723,14 +1764,46 @@ static void (*pick_gemm8(uint32_t pitch8, int ring, int variant))(Gemm8Args) {
   return r2 ? gemm_i8_kernel<PHASE, CT8, 2> : gemm_i8_kernel<PHASE, CT8, 2, 0, PV>;
 }
 
+// the full pass of a call with a row mask (MASKED: the bad rows of g.gbad leave the hit set before pairs are appended): the
+// product forms of pick_gemm8 / pick_gemm8_l2 and nothing else
+template <int CT8>
+static void (*pick_gemm8_masked(uint32_t pitch8, int ring, bool l2))(Gemm8Args) {
+  constexpr int C = WDBX_METRIC_COSINE, L = WDBX_METRIC_L2, PV = 256 + 64;
+  if (l2) {
+    if constexpr (CT8 <= 4) {
+      if (pitch8 == 384) return gemm_i8_kernel<1, CT8, 6, 384, 0, L, true>;
+      if (pitch8 == 768) return gemm_i8_kernel<1, CT8, 6, 768, 0, L, true>;
+      if (ring == 6) return gemm_i8_kernel<1, CT8, 6, 0, 0, L, true>;
+      if (ring == 4) return gemm_i8_kernel<1, CT8, 4, 0, 0, L, true>;
+      return gemm_i8_kernel<1, CT8, 2, 0, 0, L, true>;
+    }
+    return nullptr;
+  }
+  if (pitch8 == 384) {
+    if constexpr (CT8 == 8) return gemm_i8_kernel<1, 8, 3, 384, PV, C, true>;
+    else return gemm_i8_kernel<1, CT8, 6, 384, PV, C, true>;
+  }
+  if constexpr (CT8 <= 4) {
+    if (pitch8 == 768) return gemm_i8_kernel<1, CT8, 6, 768, PV, C, true>;
+    if (ring == 6) return gemm_i8_kernel<1, CT8, 6, 0, PV, C, true>;
+    if (ring == 4) return gemm_i8_kernel<1, CT8, 4, 0, PV, C, true>;
+  }
+  return gemm_i8_kernel<1, CT8, 2, 0, PV, C, true>;
+}
+
 template <int PHASE>
-static int launch_gemm8(wdbx_index* ix, const Gemm8Args& g, int ct) {
+static int launch_gemm8(wdbx_index* ix, const Gemm8Args& g, int ct, bool masked = false) {
   // k-steps (64 bytes of a row: two A fragments) in flight per wave: a divisor of the row's k-steps (pitch8 is a multiple of
   // 128).  256-query blocks leave room for 2 or 3 (128 accumulator + 32 query-fragment registers), narrower blocks for 6.
   const uint32_t steps = g.pitch8 / 64;
   const int ring = ct == 4 ? 2 : (steps % 6 == 0 ? 6 : steps % 4 == 0 ? 4 : 2);
   const int var = (int)ix->opt_gemm8_variant;
-  void (*fn)(Gemm8Args) = ix->metric == WDBX_METRIC_L2
+  const bool l2 = ix->metric == WDBX_METRIC_L2;
+  void (*fn)(Gemm8Args) = (PHASE == 1 && masked)
+                              ? (ct == 4 ? pick_gemm8_masked<8>(g.pitch8, ring, l2)
+                                 : ct == 2 ? pick_gemm8_masked<4>(g.pitch8, ring, l2)
+                                           : pick_gemm8_masked<2>(g.pitch8, ring, l2))
+                          : l2
                               ? (ct == 2 ? pick_gemm8_l2<PHASE, 4>(g.pitch8, ring) : ct == 1 ? pick_gemm8_l2<PHASE, 2>(g.pitch8, ring) : nullptr)
                           : ct == 4 ? pick_gemm8<PHASE, 8>(g.pitch8, ring, var)
                           : ct == 2 ? pick_gemm8<PHASE, 4>(g.pitch8, ring, var)
@@ -1754,15 +1827,36 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
   const bool sharded = mode == SEARCH_SHARDED;
   int rc;
   ix->last_gemm_mode = GEMM_I8;
+  const bool masked = ix->active_mask != nullptr;
   const uint32_t pitch8 = ix->pitch8g;
   const uint32_t tiles = (uint32_t)((ix->n + G8_ROWS - 1) / G8_ROWS), rw = G8_ROWS / 32;  // a lower bound per 32-row block
   const uint32_t div = ix->opt_gemm_sample_div > 0 ? (uint32_t)ix->opt_gemm_sample_div : std::min(32u, std::max(4u, 1024u / (uint32_t)k));
   uint32_t sample_tiles = std::max<uint32_t>(tiles / div, (8u * k + rw - 1) / rw);
+  // (a mask of at most 16 384 rows: the candidate buffers hold ALL of them, see below, so tau = -inf is answered from the
+  // candidates and a larger sample would buy nothing: the sample stays what an unmasked call takes)
+  if (masked && ix->mask_allowed > 16384) {
+    // A row mask that allows a fraction f of the rows: only blocks holding an allowed row vouch, and each for the best of its
+    // ~32 f allowed rows.  tau is then the k-th best of ~(sampled rows) x f rows and the full pass keeps ~k x rows / (sampled
+    // rows) of the allowed ones: the candidates per query do not grow with 1 / f, but the VOUCHING blocks shrink -- a fraction
+    // 1 - (1 - f)^32 of the sampled ones.  So the sample grows by 1 / f, up to 8 x (a quarter of the corpus at the default
+    // 1 / 32: beyond that the sample pass would cost what the full pass does), and further only while fewer than 8 k sampled
+    // blocks are expected to vouch; clamped to all tiles.  Fewer than k vouching blocks leave tau = -inf: every allowed row is a
+    // candidate, what does not fit is repaired by the masked fp32 scan.  
+    const double f = ix->n ? (double)ix->mask_allowed / (double)ix->n : 0.0;
+    if (f > 0.0) {
+      const double pv = 1.0 - std::pow(1.0 - std::min(f, 1.0), 32.0);
+      const double scaled = (double)sample_tiles * std::min(1.0 / f, 8.0), vouch = (8.0 * k) / (rw * std::max(pv, 1e-9));
+      sample_tiles = (uint32_t)std::min<double>(std::ceil(std::max(scaled, vouch)), (double)tiles);
+    }
+  }
   sample_tiles = std::max<uint32_t>(1, std::min(sample_tiles, tiles));
   const uint32_t stride = tiles / sample_tiles;
   if (rw * sample_tiles < (uint32_t)k) return fail(WDBX_E_STATE, "corpus too small for the batched path at k=%d", k);
   const uint64_t expect = (uint64_t)k * (tiles / sample_tiles + 1);
-  const uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(4096, expect * 32), 1u << 22);
+  uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(4096, expect * 32), 1u << 22);
+  // (a mask that allows few rows: room for ALL of them, so that tau = -inf -- no sampled block held an allowed row -- is
+  // answered from the candidates, not by a repair scan per query; 16 384 rows = 32 MiB of candidate buffers)
+  if (masked && ix->mask_allowed <= 16384) cap = std::max<uint32_t>(cap, (uint32_t)ix->mask_allowed);
   const size_t pitch4 = ix->pitch / 4;
   if ((rc = grow((void**)&ix->d_halfmax, &ix->halfmax_bytes, (size_t)GB_N * rw * sample_tiles * sizeof(u64)))) return rc;
   if ((rc = grow((void**)&ix->d_tau, &ix->tau_bytes, (size_t)GB_N * sizeof(float)))) return rc;
@@ -1783,6 +1877,17 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
   // (the counters of every block, tau and the lost flag are initialised by the block's queries_to_i8_kernel: no memsets)
   ix->last_batch_nq = (uint32_t)nq;
   ix->last_batch_cap = cap;
+  ix->last_batch_masked = masked;
+  ix->last_batch_allowed = masked ? ix->mask_allowed : ix->n;
+  const u64* gbad = ix->d_gbad8;
+  if (masked) {  // this call's bad-row table: one launch over the whole group table (8 bytes per 64 rows), no synchronisation
+    const u64 ngroups = ix->groups8_bytes / sizeof(f4);  // (d_gbad8's entries: to the end of the last tile + the pad groups)
+    if ((rc = grow((void**)&ix->d_call_bad, &ix->call_bad_bytes, (size_t)ngroups * sizeof(u64)))) return rc;
+    hipLaunchKernelGGL(gbad_with_mask_kernel, dim3(gbad_with_mask_grid(ngroups)), dim3(256), 0, ix->stream, (const u64*)ix->d_gbad8,
+                       ix->active_mask, (u64)((ix->n + 31) / 32), ngroups, ix->d_call_bad);
+    HIP_TRY(hipGetLastError());
+    gbad = ix->d_call_bad;
+  }
   const bool l2 = ix->metric == WDBX_METRIC_L2;
   if (l2 && (rc = ensure_row_norms(ix))) return rc;
   if (!ix->gref_valid) {  // the ordinary-group bounds of the prefilter epilogue (two passes over the group table, ~10 us)
@@ -1810,7 +1915,7 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
     g.rows8 = ix->d_rows8g;
     g.groups = ix->d_groups8;
     g.cn = ix->d_cn;
-    g.gbad = ix->d_gbad8;
+    g.gbad = gbad;
     g.gref = ix->d_gref8;
     g.qb8 = ix->d_qb8;
     g.qpar = ix->d_qpar;
@@ -1846,7 +1951,7 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
     g.pairs = ix->d_pairs;
     g.pair_count = ix->d_pair_count;
     g.pair_cap = pair_cap;
-    if ((rc = launch_gemm8<1>(ix, g, ct))) return rc;
+    if ((rc = launch_gemm8<1>(ix, g, ct, masked))) return rc;
     hipLaunchKernelGGL(scatter_pairs_kernel, dim3((nwaves + SCATTER_LISTS - 1) / SCATTER_LISTS), dim3(1024), 0, ix->stream,
                        (const u64*)ix->d_pairs, (const uint32_t*)ix->d_pair_count, nwaves, pair_cap, ix->d_cand, ix->d_count + q0, cap,
                        d_lost);
@@ -1859,7 +1964,7 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
       r.count = ix->d_count + q0;
       r.cap = cap;
       r.groups = ix->d_groups8;
-      r.gbad = ix->d_gbad8;
+      r.gbad = gbad;
       r.cn = ix->d_cn;
       r.qpar = ix->d_qpar;
       r.k = k;

@@ -108,8 +108,15 @@ __device__ __forceinline__ uint32_t g8_bswz(uint32_t c, uint32_t r, bool odd) {
 //          compare) in a row with the hit masks kept in scalar registers, then -- in about two tiles of three -- the rows
 //          of the column groups that had a hit.  (The product form branches per column group: each of its 16 blocks
 //          waits out its own LDS read of the query parameters.)
-template <int PHASE, int CT8, int RING, int PITCH8 = 0, int VAR = 0, int METRIC = WDBX_METRIC_COSINE>
+// MASKED (PHASE 1, the product forms only): a.gbad is the CALL's bad-row table (gbad_with_mask_kernel: removed rows, rows past
+// the end and the rows the caller's row mask leaves out); the wave's 32 bits are read on the scalar path as in PHASE 0 and its
+// bad rows are cleared from the hit set BEFORE pairs are appended -- with a selective mask tau is low, and masked-out rows
+// above it would otherwise flood the per-wave pair lists.  PHASE 0 needs no flag: fed the same table, a masked-out row cannot vouch.
+template <int PHASE, int CT8, int RING, int PITCH8 = 0, int VAR = 0, int METRIC = WDBX_METRIC_COSINE, bool MASKED = false>
 __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
+  // (exactly the forms whose append sites clear the bad rows: the prefilter epilogue for inner product, the plain one for L2)
+  static_assert(!MASKED || (PHASE == 1 && VAR == (METRIC == WDBX_METRIC_L2 ? 0 : 256 + 64)),
+                "row masks: the full pass of the product forms only");
   constexpr bool L2 = METRIC == WDBX_METRIC_L2;
   constexpr int GBN = 32 * CT8, NJ = 2 * CT8;  // NJ column groups of 16 queries
   constexpr bool PRE = PHASE == 1 && (VAR & 256) != 0 && METRIC == WDBX_METRIC_COSINE;
@@ -273,7 +280,9 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
   // L2: per tile, this lane's 8 rows' norm terms.  PHASE 0: |c_r|^2 taken high.  PHASE 1: u_r = |c_r|^2 / (2 s_g) taken low;
   // a NaN norm (a removed row: never a result) becomes +inf = never kept, a norm that overflowed -inf = always kept.
   float e_u[L2 ? 8 : 1];
-  uint32_t e_bad = 0;  // PHASE 0: the bad-row bits of this wave's 32 rows (wave-uniform)
+  uint32_t e_bad = 0;  // PHASE 0, MASKED: the bad-row bits of this wave's 32 rows (wave-uniform)
+  // MASKED: this lane's 8 rows' bad bits, in the order of the hit sets below (row r = 16 (r >> 2) + (r & 3) behind 4 kb)
+  auto lane_bad = [&]() -> uint32_t { return ((e_bad >> (4 * kb)) & 0xFu) | (((e_bad >> (4 * kb + 16)) & 0xFu) << 4); };
   // PHASE 1: the lanes' kept rows (bits: which of the lane's 8 rows of column group j) go to the wave's pair list, one
   // ballot per trip (a lane rarely holds more than one).  A pair carries its integer dot product D in 24 bits
   // (|D| < 2^23 holds up to d = 520 at full-scale bytes; anything outside is stored as "unknown"): refine_pairs_kernel
@@ -358,6 +367,7 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
           for (int r = 0; r < 8; ++r)
             if (!(f[r] < T) && lrow0 + 16 * (r >> 2) + (r & 3) < a.n_rows) bits |= 1u << r;
         }
+        if constexpr (MASKED) bits &= ~lane_bad();
         append_pairs(bits, q, j, lrow0);
       }
     } else {
@@ -375,6 +385,7 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
           for (int r = 0; r < 8; ++r)
             if (!((float)acc[j][r >> 2][r & 3] < T) && lrow0 + 16 * (r >> 2) + (r & 3) < a.n_rows) bits |= 1u << r;
         }
+        if constexpr (MASKED) bits &= ~lane_bad();
         append_pairs(bits, q, j, lrow0);
       }
     }
@@ -497,10 +508,13 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
     {  // the group's {s_g, a_g, b_g, vouch}: a wave-uniform address, read on the scalar path
       const uint32_t gidx = __builtin_amdgcn_readfirstlane(e_wrow0 >> 6);
       e_gt = *(const __attribute__((address_space(4))) f4*)(a.groups + gidx);
-      if constexpr (PHASE == 0) {
+      if constexpr (PHASE == 0 || MASKED) {
         const u64 bad = *(const __attribute__((address_space(4))) u64*)(a.gbad + gidx);
         e_bad = (uint32_t)(bad >> (e_wrow0 & 32u));
       }
+    }
+    if constexpr (MASKED) {
+      if (e_bad == 0xFFFFFFFFu) continue;  // (wave-uniform) none of this wave's 32 rows may be returned: no epilogue at all
     }
     if constexpr (PHASE == 1) {
       // keep row r for query q iff s_g s_q D + a_g E + b_g M >= tau  <=>  D >= (tau / s_q - (a_g E + b_g M) / s_q) / s_g.
@@ -679,6 +693,20 @@ __global__ __launch_bounds__(256) void rows_to_i8g_kernel(const float* rows, u64
 
 // workgroups of a rows_to_i8g_kernel launch over `groups` 64-row groups: one each
 static inline uint32_t rows_to_i8g_grid(uint64_t groups) { return (uint32_t)std::min<uint64_t>(groups, 1u << 20); }
+
+// The bad-row table of ONE masked call: call_bad[g] = gbad[g] | ~mask64[g] for all n_groups groups of the table (to the end
+// of the last tile and the pad groups behind it).  The caller's row mask is mask_words uint32 words (bit r % 32 of word
+// r / 32 = row r may be returned): two of them, little end first, are the complement of a group's bad-row word.  Words past
+// the mask's end read as zero (ceil(rows / 32) may be odd, and the groups behind the last row have no word at all), and the
+// bits a caller left set past the last row meet the table's own past-the-end bits: such rows stay bad whatever the mask says.
+__global__ __launch_bounds__(256) void gbad_with_mask_kernel(const u64* gbad, const uint32_t* mask, u64 mask_words, u64 n_groups,
+                                                             u64* call_bad) {
+  for (u64 g = (u64)blockIdx.x * 256 + threadIdx.x; g < n_groups; g += (u64)gridDim.x * 256) {
+    const u64 lo = 2 * g < mask_words ? mask[2 * g] : 0u, hi = 2 * g + 1 < mask_words ? mask[2 * g + 1] : 0u;
+    call_bad[g] = gbad[g] | ~(lo | (hi << 32));
+  }
+}
+static inline uint32_t gbad_with_mask_grid(uint64_t groups) { return (uint32_t)std::min<uint64_t>((groups + 255) / 256, 4096); }
 
 // queries [nv, pitch] fp32 -> the i8 query block [gbn][pitch8] (signed bytes, zero padded) and its parameters
 // {s_q, E_q, M_q, 1 / s_q} (E, M rounded up; a non-finite query gets E = +inf: every row becomes a candidate and the exact

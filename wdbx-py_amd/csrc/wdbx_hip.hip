@@ -186,7 +186,8 @@ void wdbx_index_destroy(wdbx_index* ix) try {
                     ix->d_qblock, ix->d_halfmax, ix->d_tau, ix->d_cand, ix->d_count, ix->d_ticket, ix->d_mask, ix->d_dump, ix->d_sel,
                     ix->d_state, ix->d_cn, ix->d_cnmax, ix->d_qb16, ix->d_rows16, ix->d_rows8, ix->d_scale8, ix->d_selsrc,
                     ix->d_gmax, ix->d_qn, ix->d_rows8g, ix->d_groups8, ix->d_gbad8, ix->d_gref8, ix->d_over_list, ix->d_qb8,
-                    ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr, ix->d_rows6, ix->d_count6};
+                    ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr, ix->d_rows6, ix->d_count6,
+                    ix->d_call_bad};
     for (void* p : bufs)
       if (p) (void)hipFree(p);
     if (ix->h_stage) (void)hipHostFree(ix->h_stage);
@@ -399,7 +400,8 @@ static int search_host(wdbx_index* ix, const float* queries, int nq, int k, int 
   } hold{ix, &lk};
   bool gemm, zero_copy;
   for (;;) {
-    gemm = !(mask_words && ix->n) && gemm_eligible(ix, nq, k);
+    // (a row mask: one masked pass over the int8 tiles when they are what would run; per-query masked scans otherwise)
+    gemm = gemm_eligible(ix, nq, k) && (!(mask_words && ix->n) || masked_tiles_ready(ix, k));
     zero_copy = ix->opt_zero_copy && !gemm && q_bytes <= STAGE_Q && elems * sizeof(int64_t) <= STAGE_IDX;
     if (zero_copy && !ix->h_stage) {
       void* hp = nullptr;
@@ -431,11 +433,9 @@ static int search_host(wdbx_index* ix, const float* queries, int nq, int k, int 
     const size_t words = (size_t)((ix->n + 31) / 32);
     if (mask_word_count < words)
       return fail(WDBX_E_INVALID, "row mask of %llu words for %llu rows (%zu words needed)", (u64)mask_word_count, (u64)ix->n, words);
-    rc = grow((void**)&ix->d_mask, &ix->mask_bytes, words * sizeof(uint32_t));
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(ix->d_mask, mask_words, words * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
-    ix->active_mask = ix->d_mask;
     scope.set = true;
+    if ((rc = set_active_mask(ix, mask_words))) return rc;
+    if (!gemm) ix->last_batch_masked = false;
   }
   char* const hs = zero_copy ? ix->h_stage + (size_t)hold.slot * SLOT_BYTES : nullptr;      // this call's slot, host view
   char* const ds = zero_copy ? ix->h_stage_dev + (size_t)hold.slot * SLOT_BYTES : nullptr;  // ... and device view
@@ -934,6 +934,36 @@ int wdbx_index_search_batch_device(wdbx_index* ix, const float* d_queries, int n
   if (!gemm_eligible(ix, std::max(nq, (int)ix->opt_gemm_min_nq), k))
     return fail(WDBX_E_STATE, "batched MFMA path needs >= %lld rows and k*1024 <= rows", (long long)ix->opt_gemm_min_rows);
   return enqueue_search_gemm(ix, d_queries, nq, k, d_out_idx, d_out_score);
+} WDBX_CATCH
+
+// wdbx_index_search_batch_device with a row mask from the host (uint32 words, bit r % 32 of word r / 32 = row r may be
+// returned; mask_word_count >= ceil(rows / 32) or the call is refused): one masked pass over the int8 tiles when they are what
+// would run (option last_batch_masked = 1), the masked per-query paths otherwise.  The mask is copied before the call
+// returns and applies to this call only; the results are device-resident and ordered on the handle's stream as for the
+// unmasked call; wdbx_index_batch_status describes the call when it ran the masked pass (after the per-query fall-back: that
+// path's last round, as after wdbx_index_search_device).
+int wdbx_index_search_batch_masked_device(wdbx_index* ix, const float* d_queries, int nq, int k, const uint32_t* mask_words,
+                                          uint64_t mask_word_count, int64_t* d_out_idx, float* d_out_score) try {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  if (!mask_words) return fail(WDBX_E_INVALID, "mask_words is null");
+  if (k < 1 || k > WDBX_MAX_K) return fail(WDBX_E_INVALID, "k=%d outside [1, %d]", k, WDBX_MAX_K);
+  std::lock_guard<std::mutex> lk(ix->mu);
+  DeviceGuard g(ix->device);
+  if (!gemm_eligible(ix, std::max(nq, (int)ix->opt_gemm_min_nq), k))
+    return fail(WDBX_E_STATE, "batched MFMA path needs >= %lld rows and k*1024 <= rows", (long long)ix->opt_gemm_min_rows);
+  const uint64_t words = (ix->n + 31) / 32;
+  if (mask_word_count < words)
+    return fail(WDBX_E_INVALID, "row mask of %llu words for %llu rows (%llu words needed)", (u64)mask_word_count, (u64)ix->n, (u64)words);
+  struct MaskScope {
+    wdbx_index* ix;
+    ~MaskScope() { ix->active_mask = nullptr; }
+  } scope{ix};
+  int rc;
+  const bool tiles = masked_tiles_ready(ix, k);
+  if ((rc = set_active_mask(ix, mask_words))) return rc;
+  if (tiles) return enqueue_search_gemm(ix, d_queries, nq, k, d_out_idx, d_out_score);
+  ix->last_batch_masked = false;
+  return enqueue_search(ix, d_queries, nq, k, d_out_idx, d_out_score, SEARCH_FINAL);
 } WDBX_CATCH
 
 int wdbx_index_batch_status(wdbx_index* ix, uint32_t* out_counts, int nq, uint32_t* out_capacity, int* out_overflowed) try {
@@ -1508,6 +1538,7 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"gemm_min_rows", &wdbx_index::opt_gemm_min_rows},
     {"gemm_min_work", &wdbx_index::opt_gemm_min_work},
     {"gemm_sample_div", &wdbx_index::opt_gemm_sample_div},
+    {"gemm_masked", &wdbx_index::opt_gemm_masked},
 };
 
 static int64_t* option_slot(wdbx_index* ix, const char* name) { return find_option(ix, kOptions, name); }
@@ -1551,6 +1582,8 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "last_range_path")) return *value = ix->last_range_path, WDBX_OK;
   if (name && !strcmp(name, "last_sample_qn")) return *value = ix->last_sample_qn, WDBX_OK;
   if (name && !strcmp(name, "last_batch_repaired")) return *value = ix->last_batch_repaired ? 1 : 0, WDBX_OK;
+  if (name && !strcmp(name, "last_batch_masked")) return *value = ix->last_batch_masked ? 1 : 0, WDBX_OK;
+  if (name && !strcmp(name, "last_batch_allowed_rows")) return *value = (int64_t)ix->last_batch_allowed, WDBX_OK;
   if (name && !strcmp(name, "group_bounds_active")) return *value = ix->group_bounds ? 1 : 0, WDBX_OK;
   if (name && !strcmp(name, "exchanges")) return *value = (int64_t)ix->exchanges, WDBX_OK;
   if (name && !strcmp(name, "device_bytes_resident")) return *value = (int64_t)device_bytes_resident(ix), WDBX_OK;

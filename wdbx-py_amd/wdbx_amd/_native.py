@@ -71,6 +71,8 @@ SIGNATURES = {
     "wdbx_index_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "wdbx_index_synchronize": (C.c_int, [C.c_void_p]),
     "wdbx_index_search_batch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "wdbx_index_search_batch_masked_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint32),
+                                                        C.c_uint64, C.c_void_p, C.c_void_p]),
     "wdbx_index_batch_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_uint32),
                                           C.POINTER(C.c_int)]),
     "wdbx_index_profile_read_gemm": (C.c_int, [C.c_void_p, _u64p, _dblp]),
@@ -374,6 +376,15 @@ class NativeIndex:
         qptr = d_queries.ptr + int(query_offset) * self.pitch * 4
         fn = self._lib.wdbx_index_search_sharded_batch_device if sharded else self._lib.wdbx_index_search_batch_device
         _check(fn(self._h, qptr, int(nq), int(k), d_idx.ptr, d_score.ptr))
+
+    def search_batch_masked_device(self, d_queries: DeviceBuffer, nq: int, k: int, mask_words, d_idx: DeviceBuffer,
+                                   d_score: DeviceBuffer, query_offset: int = 0) -> None:
+        """:meth:`search_batch_device` with a row mask from the host (see :func:`pack_row_mask`): one masked pass over the
+        int8 tiles where they run (``get_option("last_batch_masked") == 1``).  The library checks the mask's length."""
+        m = np.ascontiguousarray(mask_words, dtype=np.uint32)
+        qptr = d_queries.ptr + int(query_offset) * self.pitch * 4
+        _check(self._lib.wdbx_index_search_batch_masked_device(self._h, qptr, int(nq), int(k), m.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                               m.size, d_idx.ptr, d_score.ptr))
 
     def batch_status(self, nq: int):
         counts = np.zeros(max(int(nq), 1), np.uint32)

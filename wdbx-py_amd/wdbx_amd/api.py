@@ -61,8 +61,10 @@ async def search_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
 
 
 async def search_batch_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
-    """Batch form (extension): body ``{"query_vectors": [[...], ...], "limit", "threshold", "filter_metadata"}`` ->
-    ``{"results": [<one search_endpoint result list per query>]}``.  One batched matrix-core pass per shard."""
+    """Batch form (extension): body ``{"query_vectors": [[...], ...], "limit", "threshold", "filter_metadata",
+    "prefilter"}`` -> ``{"results": [<one search_endpoint result list per query>]}``.  One batched matrix-core pass per
+    shard.  ``prefilter`` (true / false; absent or null = the store's ``FILTER_PUSHDOWN``): push the metadata filter down
+    into that pass, so every query returns a full ``limit`` whenever enough rows match."""
     import asyncio
 
     limit, threshold, flt = _parse_common(payload)
@@ -72,7 +74,11 @@ async def search_batch_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]
     if not queries:
         return {"results": []}
     loop = asyncio.get_running_loop()
-    per_query = await loop.run_in_executor(None, lambda: wdbx.vector_search_batch(queries, limit, threshold, flt))
+    prefilter = payload.get("prefilter")
+    if prefilter is not None and not isinstance(prefilter, bool):
+        raise ValueError("prefilter must be true, false or null")
+    extra = {} if prefilter is None else {"prefilter": prefilter}  # (absent / null: the facade's own default)
+    per_query = await loop.run_in_executor(None, lambda: wdbx.vector_search_batch(queries, limit, threshold, flt, **extra))
     return {"results": [_render(r)["results"] for r in per_query]}
 
 

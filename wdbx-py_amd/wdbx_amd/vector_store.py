@@ -466,7 +466,7 @@ class VectorStore:
     def _row_masks(self, filter_metadata: Dict[str, Any]):
         """Per-shard row masks of the metadata filter (push-down), cached until the
         store changes."""
-        key = json.dumps(filter_metadata, sort_keys=False, default=str)
+        key = self._mask_key(filter_metadata)
         version = (sum(ix.next_index for ix in self.indices), len(self.metadata), self._meta_version)
         cache = self._mask_cache
         if cache.get("version") != version:
@@ -596,6 +596,11 @@ class VectorStore:
             prefilter = bool(self.config.get("FILTER_PUSHDOWN", False))
         return self._row_masks(filter_metadata) if (prefilter and filter_metadata) else [None] * len(self.indices)
 
+    @staticmethod
+    def _mask_key(filter_metadata) -> str:
+        """The ``_mask_cache`` key of a pushed-down filter: callers with the same key share one set of row masks."""
+        return json.dumps(filter_metadata, sort_keys=False, default=str)
+
     def search(self, query_vector: List[float], limit: int = 10, threshold: float = 0.0,
                filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None) -> List[Result]:
         """``prefilter=True`` (or config ``FILTER_PUSHDOWN``) evaluates the metadata filter BEFORE the
@@ -717,18 +722,21 @@ class VectorStore:
         per caller.  No waiting window: a lone caller is served at once, exactly as before.  Every
         shard is still asked for each query's own top-``limit``; results are the exact ones
         (config ``ASYNC_COALESCE=False`` restores one call per query).  ``prefilter`` / FILTER_PUSHDOWN as in
-        ``search`` (such callers are served one by one: the batched pass takes no row masks)."""
+        ``search``: waiting callers that push down the SAME filter (the same ``_mask_cache`` key) share one masked batched
+        call -- one masked matrix-core pass per shard; callers with different filters are served in separate calls."""
         query = np.array(query_vector, dtype=np.float32)
         if query.shape != (self.vector_dim,):
             raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {query.shape}")
         loop = asyncio.get_running_loop()
         masks = self._masks_for(filter_metadata, prefilter)
-        if not self.config.get("ASYNC_COALESCE", True) or any(m is not None for m in masks):
+        pushed = any(m is not None for m in masks)
+        if not self.config.get("ASYNC_COALESCE", True):
             shard_results = await loop.run_in_executor(self.thread_pool, self._fan_out, query, limit, masks,
                                                        bool(filter_metadata))
             return self._merge(shard_results, limit, threshold, filter_metadata)
         fut = loop.create_future()
-        self._pending.append((query, int(limit), threshold, filter_metadata, fut))
+        self._pending.append((query, int(limit), threshold, filter_metadata, fut,
+                              self._mask_key(filter_metadata) if pushed else None))
         if self._drain_task is None or self._drain_task.done():
             self._drain_task = loop.create_task(self._drain_pending())
         return await fut
@@ -737,53 +745,80 @@ class VectorStore:
         loop = asyncio.get_running_loop()
         nomask = [None] * len(self.indices)
         while self._pending:
-            batch, self._pending = self._pending, []
-            try:
-                if len(batch) == 1:
-                    query, limit, threshold, flt, fut = batch[0]
-                    res = await loop.run_in_executor(self.thread_pool, self._fan_out, query, limit, nomask, bool(flt))
-                    if not fut.done():
-                        fut.set_result(self._merge(res, limit, threshold, flt))
-                    continue
-                kmax = max(b[1] for b in batch)
-                queries = np.stack([b[0] for b in batch])
-                if all(b[1] == kmax for b in batch) and self._shard_group() is not None:
-                    # same limit everywhere: ONE group call answers the whole batch (a caller with a filter needs the
-                    # union of the shards' lists, as in ``search``)
-                    keep_all = any(bool(b[3]) for b in batch)
-                    merged = await loop.run_in_executor(self.thread_pool, self._group_search, queries, kmax, keep_all)
-                    if merged is not None:
-                        self.last_search_path = self._group_path
-                        for m, (_, limit, threshold, flt, fut) in zip(merged, batch):
-                            if not fut.done():
-                                fut.set_result(self._merge([m], limit, threshold, flt))
-                        continue
+            taken, self._pending = self._pending, []
+            # callers that push down the same filter share one masked call; the others (no mask) share the unmasked one
+            by_mask: Dict[Any, List[Any]] = {}
+            for b in taken:
+                by_mask.setdefault(b[5], []).append(b)
+            # (the groups run side by side, as such callers did when each went to the pool alone; a group's masks are taken
+            # NOW, once, not when its first caller queued: the store may have changed since)
+            await asyncio.gather(*[
+                self._drain_batch(loop, [b[:5] for b in batch], None if key is None else batch[0][3], nomask)
+                for key, batch in by_mask.items()])
+
+    async def _drain_batch(self, loop, batch, pushed_filter, nomask) -> None:
+        """One coalesced batch of ``search_async`` callers; ``pushed_filter``: the filter they all push down, or None."""
+        try:
+            masks = None if pushed_filter is None else self._row_masks(pushed_filter)
+            if len(batch) == 1:
+                query, limit, threshold, flt, fut = batch[0]
+                res = await loop.run_in_executor(self.thread_pool, self._fan_out, query, limit, masks or nomask, bool(flt))
+                if not fut.done():
+                    fut.set_result(self._merge(res, limit, threshold, flt))
+                return
+            kmax = max(b[1] for b in batch)
+            queries = np.stack([b[0] for b in batch])
+            if all(b[1] == kmax for b in batch) and self._shard_group() is not None:
+                # same limit everywhere: ONE group call answers the whole batch (a caller with a filter needs the
+                # union of the shards' lists, as in ``search``)
+                keep_all = any(bool(b[3]) for b in batch)
+                merged = await loop.run_in_executor(self.thread_pool, self._group_search, queries, kmax, keep_all, masks)
+                if merged is not None:
+                    self.last_search_path = self._group_path
+                    for m, (_, limit, threshold, flt, fut) in zip(merged, batch):
+                        if not fut.done():
+                            fut.set_result(self._merge([m], limit, threshold, flt))
+                    return
+            if masks is None:
                 per_shard = await asyncio.gather(*[
                     loop.run_in_executor(ix.thread_pool, ix.search_batch, queries, kmax) for ix in self.indices])
-                for i, (_, limit, threshold, flt, fut) in enumerate(batch):
-                    if not fut.done():
-                        # a shard's top-kmax list cut to `limit` IS its top-`limit` list
-                        fut.set_result(self._merge([res[i][:limit] for res in per_shard], limit, threshold, flt))
-            except Exception as e:  # deliver the failure to every waiter of this batch
-                for b in batch:
-                    if not b[4].done():
-                        b[4].set_exception(e)
+            else:  # every shard's own row mask travels with its batched call
+                per_shard = await asyncio.gather(*[
+                    loop.run_in_executor(ix.thread_pool, ix.search_batch, queries, kmax, m)
+                    for ix, m in zip(self.indices, masks)])
+            for i, (_, limit, threshold, flt, fut) in enumerate(batch):
+                if not fut.done():
+                    # a shard's top-kmax list cut to `limit` IS its top-`limit` list
+                    fut.set_result(self._merge([res[i][:limit] for res in per_shard], limit, threshold, flt))
+        except Exception as e:  # deliver the failure to every waiter of this batch
+            for b in batch:
+                if not b[4].done():
+                    b[4].set_exception(e)
 
     def search_batch(self, queries, limit: int = 10, threshold: float = 0.0,
-                     filter_metadata: Optional[Dict[str, Any]] = None) -> List[List[Result]]:
+                     filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None) -> List[List[Result]]:
         """Extension: one corpus pass per shard for a whole query batch -- through the shard group when there is
         one (every shard runs its matrix-core pass, or per-query scans for a few queries, inside ONE library call, the
-        lists are exchanged and merged on the device), else shard by shard on the shard pool."""
+        lists are exchanged and merged on the device), else shard by shard on the shard pool.  ``prefilter`` / FILTER_PUSHDOWN
+        as in ``search``: the filter's row masks travel with the call (one MASKED matrix-core pass per shard), so every query
+        returns a full ``limit`` whenever enough rows match; the default post-filters the top-``limit`` as before."""
         queries = np.asarray(queries, dtype=np.float32)
         if queries.ndim != 2 or queries.shape[1] != self.vector_dim:
             raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {queries.shape}")
+        masks = self._masks_for(filter_metadata, prefilter)
+        pushed = any(m is not None for m in masks)
         if queries.shape[0]:
-            merged = self._group_search(queries, limit, keep_all=bool(filter_metadata))
+            merged = self._group_search(queries, limit, keep_all=bool(filter_metadata), masks=masks if pushed else None)
             if merged is not None:
                 self.last_search_path = self._group_path
                 return [self._merge([m], limit, threshold, filter_metadata) for m in merged]
         self.last_search_path = "threads"
-        if len(self.indices) > 1:  # shards run concurrently (GIL-releasing calls), gathered in shard order
+        if pushed:
+            def one(a):
+                return a[0].search_batch(queries, limit=limit, row_mask=a[1])
+            pairs = list(zip(self.indices, masks))
+            per_shard = list(self._shard_pool.map(one, pairs)) if len(pairs) > 1 else [one(pairs[0])]
+        elif len(self.indices) > 1:  # shards run concurrently (GIL-releasing calls), gathered in shard order
             per_shard = list(self._shard_pool.map(lambda ix: ix.search_batch(queries, limit=limit), self.indices))
         else:
             per_shard = [ix.search_batch(queries, limit=limit) for ix in self.indices]

@@ -115,12 +115,14 @@ class WDBX:
                                                     filter_metadata=filter_metadata)
 
     def vector_search_batch(self, query_vectors, limit: int = 10, threshold: float = 0.0,
-                            filter_metadata: Optional[Dict[str, Any]] = None) -> List[List[Result]]:
-        """Extension: several queries at once (the reference is single-query)."""
+                            filter_metadata: Optional[Dict[str, Any]] = None,
+                            prefilter: Optional[bool] = None) -> List[List[Result]]:
+        """Extension: several queries at once (the reference is single-query).  ``prefilter`` as in
+        ``vector_search``: the metadata filter is pushed down into the batched pass."""
         for q in query_vectors:
             self._check_dim(q)
         return self.vector_store.search_batch(query_vectors, limit=limit, threshold=threshold,
-                                              filter_metadata=filter_metadata)
+                                              filter_metadata=filter_metadata, prefilter=prefilter)
 
     def vector_search_range(self, query_vector: List[float], threshold: float,
                             filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,
