@@ -1571,6 +1571,28 @@ def test_i8_prefilter_epilogue_keeps_exactly_the_same_candidates(native):
     assert i0[7, 0] == 70_010
 
 
+def test_removed_experiment_options_are_refused(native):
+    """The library keeps three int8 tile epilogue forms (`gemm8_variant` 0 = 14, 12, 13) and no timing-only instance of the
+    u8 scan: a probe script that asks for a removed form fails loudly instead of silently timing the product form."""
+    n, d = 256, 128
+    rows = O.normalize_rows_fast(np.random.default_rng(5).standard_normal((n, d)).astype(np.float32))
+    with native.NativeIndex(d, capacity_rows=n) as ix:
+        ix.add(rows)
+        with pytest.raises(native.HipBackendError) as err:
+            ix.set_option("scan8_ablate", 1)
+        assert err.value.code == -1 and "unknown option" in err.value.message
+        for kept in (12, 13, 14, 0):
+            ix.set_option("gemm8_variant", kept)
+            assert ix.get_option("gemm8_variant") == kept
+        for previous in (0, 13):
+            ix.set_option("gemm8_variant", previous)
+            for removed in (1, 6, 8, 29, 31):
+                with pytest.raises(native.HipBackendError) as err:
+                    ix.set_option("gemm8_variant", removed)
+                assert err.value.code == -1 and "gemm8_variant" in err.value.message, removed
+                assert ix.get_option("gemm8_variant") == previous
+
+
 @pytest.mark.parametrize("metric,k", [("cosine", 10), ("cosine", 150), ("l2", 10), ("l2", 100)])
 def test_i8_second_stage_drops_rows_but_never_an_answer(native, metric, k):
     """refine_pairs_kernel (round 3): between the tile pass and the exact pass every candidate's own bounds (from the

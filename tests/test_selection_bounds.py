@@ -308,7 +308,7 @@ def test_i8_l2_selection_never_loses_a_top_k_row(seed):
 
 @pytest.mark.parametrize("seed", range(3))
 def test_i8_prefilter_threshold_is_never_above_the_exact_one(seed):
-    """The prefilter epilogue (VAR bit 8): U = A1 - a_ref E' - b_ref M' - 4e-6 (|A1| + a_ref E' + b_ref M') per query, test
+    """The prefilter epilogue (EPI8_PRE_GROUP, EPI8_PRE_BLOCK): U = A1 - a_ref E' - b_ref M' - 4e-6 (|A1| + a_ref E' + b_ref M') per query, test
     D >= e_inv U - 1 on ORDINARY groups (a_g <= a_ref, b_g <= b_ref).  It must pass every (row, query) the exact chain keeps."""
     f32 = np.float32
     rng = np.random.default_rng(77 + seed)

@@ -1,6 +1,6 @@
 // One-kernel translation unit for iterating on an int8 tile kernel's code generation without the 4-minute device pass of the
 // whole library:  hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Iwdbx-py_amd/csrc -S --cuda-device-only \
-//   -Rpass-analysis=kernel-resource-usage -DINST8='1, 8, 6, 384, 640' tools/probes/tile8_tu.hip -o /tmp/tile8.s
+//   -Rpass-analysis=kernel-resource-usage -DINST8='1, 8, 3, 384, EPI8_PRE_BLOCK' tools/probes/tile8_tu.hip -o /tmp/tile8.s
 #include <hip/hip_runtime.h>
 #include <climits>
 #include <cmath>

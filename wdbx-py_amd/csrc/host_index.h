@@ -158,7 +158,7 @@ struct wdbx_index {
   // options
   int64_t opt_lanes = 0, opt_blocks = 0, opt_nt = 1, opt_blocked = 0, opt_batch = 32, opt_generic = 0;
   int64_t opt_group_bounds = -1, opt_single_min_rows = 131072, opt_scan8_wgs = -1, opt_scan8_per_query = -1,
-          opt_scan8_ablate = 0, opt_batch_repair = 1, opt_scan_shadow = 2, opt_gemm_bf16 = 3, opt_gemm8_variant = 0,
+          opt_batch_repair = 1, opt_scan_shadow = 2, opt_gemm_bf16 = 3, opt_gemm8_variant = 0,
           opt_gemm8_refine = 1, opt_scan8_sample4 = 1, opt_gemm_l2 = 1, opt_gemm_l2_i8 = 1, opt_force_ragged = 0,
           opt_gemm_ct = 0, opt_wg_merge = 1, opt_zero_copy = 1, opt_lone_host_select = 1, opt_lds_lists = 0,
           opt_merge_fast = 1, opt_poll_done = 1, opt_scan_one_grid = 1, opt_select_min_k = 200, opt_gemm_min_nq = 4, opt_gemm_min_rows = 65536, opt_gemm_min_work = 800000,
@@ -948,8 +948,6 @@ static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, in
   scan8_fn f0 = l2 ? pick_scan8<0, WDBX_METRIC_L2>(sh->L, sh->QPL) : pick_scan8<0, WDBX_METRIC_COSINE>(sh->L, sh->QPL);
   scan8_fn f1 = l2 ? pick_scan8<1, WDBX_METRIC_L2>(sh->L, sh->QPL) : pick_scan8<1, WDBX_METRIC_COSINE>(sh->L, sh->QPL);
   if (!f0 || !f1) return fail(WDBX_E_STATE, "no u8 scan instance for %d lanes x %d loads", sh->L, sh->QPL);
-  if (ix->opt_scan8_ablate == 1 && !l2 && sh->L == 8 && sh->QPL == 3) f1 = scan8_kernel<8, 3, WDBX_METRIC_COSINE, 1, 1>;  // timing only
-  if (ix->opt_scan8_ablate == 2 && !l2 && sh->L == 8 && sh->QPL == 3) f1 = scan8_kernel<8, 3, WDBX_METRIC_COSINE, 1, 2>;  // all the arithmetic, no appends
   const uint32_t R = 64u / (uint32_t)sh->L;
   const uint32_t groups1 = (uint32_t)((ix->n + R - 1) / R);
   // workgroups per CU in the full pass's grid (2 fit at once: 8 waves per CU).  Shards of about 1 - 2.7 M rows at d = 384 -- the
@@ -1692,103 +1690,44 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
 }
 
 // ---- batched queries on the int8 tiles (kernels_tiles8.h) ----------------------------------------
-// The instance for a block of 32 * CT8 queries: rows of 384 and 768 bytes (d <= 768 in steps that cover the reference's
-// embedding sizes 384 and 768) get the compile-time pitch, everything else the run-time form.  Option gemm8_variant
-// (experiments, tools/probes/c4_i8_ab.py): 1 = run-time pitch everywhere, 2 = row stream with the default cache policy, 3 = SIMD
-// partners half a tile apart, 4 = two k-steps in flight instead of three, 5 = the tile epilogue inside the next tile's first
-// k-step, 6 = the epilogue as one block + one branch, 7 = a query-fragment window of 4, 12 / 13 / 14 = prefilter epilogue with a branch per
-// column group / the round-2 forms / prefilter in one block = the default (correct answers all: profiles/r03/c4_i8/); 8, 10, 11 = timing-only ablations (no epilogue; and no row
-// stream / no query-fragment reads): wrong answers, never set outside the probe.
-// L2 instances: the compile-time pitch for rows of 768 bytes (BASELINE config 3) and 384, the run-time form for the rest
-template <int PHASE, int CT8>
-static void (*pick_gemm8_l2(uint32_t pitch8, int ring))(Gemm8Args) {
-  constexpr int M = WDBX_METRIC_L2;
-  if constexpr (CT8 <= 4) {
-    if (pitch8 == 384) return gemm_i8_kernel<PHASE, CT8, 6, 384, 0, M>;
-    if (pitch8 == 768) return gemm_i8_kernel<PHASE, CT8, 6, 768, 0, M>;
-    if (ring == 6) return gemm_i8_kernel<PHASE, CT8, 6, 0, 0, M>;
-    if (ring == 4) return gemm_i8_kernel<PHASE, CT8, 4, 0, 0, M>;
-    return gemm_i8_kernel<PHASE, CT8, 2, 0, 0, M>;
+// The instance of one epilogue form for a block of 32 * CT8 queries: rows of 384 and 768 bytes (d <= 768 in steps that cover
+// the reference's embedding sizes 384 and 768; L2: 768 = BASELINE config 3) get the compile-time pitch, everything else the
+// run-time form with `ring` k-steps in flight.
+template <int PHASE, int CT8, Epi8 EPI, int METRIC, bool MASKED>
+static void (*gemm8_instance(uint32_t pitch8, int ring))(Gemm8Args) {
+  if constexpr (CT8 == 8) {
+    // (256-query blocks: 128 accumulator registers leave room for 3 k-steps in flight with compile-time addressing, 2 without;
+    // L2 runs on query blocks of at most 128: its epilogue keeps 16 more values per lane)
+    if constexpr (METRIC == WDBX_METRIC_L2) return nullptr;
+    else if (pitch8 == 384) return gemm_i8_kernel<PHASE, 8, 3, 384, EPI, METRIC, MASKED>;
+    else return gemm_i8_kernel<PHASE, 8, 2, 0, EPI, METRIC, MASKED>;
+  } else {
+    if (pitch8 == 384) return gemm_i8_kernel<PHASE, CT8, 6, 384, EPI, METRIC, MASKED>;
+    if (pitch8 == 768) return gemm_i8_kernel<PHASE, CT8, 6, 768, EPI, METRIC, MASKED>;
+    if (ring == 6) return gemm_i8_kernel<PHASE, CT8, 6, 0, EPI, METRIC, MASKED>;
+    if (ring == 4) return gemm_i8_kernel<PHASE, CT8, 4, 0, EPI, METRIC, MASKED>;
+    return gemm_i8_kernel<PHASE, CT8, 2, 0, EPI, METRIC, MASKED>;
   }
-  return nullptr;  // (L2 runs on query blocks of at most 128: its epilogue keeps 16 more values per lane)
 }
 
+// The epilogue form.  The sample pass and L2 have the exact epilogue only.  The full pass of every inner-product instance
+// carries the prefilter, its tests in one block, since round 3 (-2 % against the round-2 form, identical candidates:
+// profiles/r03/c4_i8/); a call with a row mask (MASKED: the bad rows of g.gbad leave the hit set before pairs are appended)
+// runs that form and nothing else.  Option gemm8_variant (tools/probes/c4_i8_ab.py), for A/B: 13 = the round-2 form (exact
+// epilogue) everywhere, 12 = the prefilter with a branch per column group for 256-query blocks of 384-byte rows, 0 / 14 = the default.
 template <int PHASE, int CT8>
-static void (*pick_gemm8(uint32_t pitch8, int ring, int variant))(Gemm8Args) {
-  // the full pass (PHASE 1) of every inner-product instance carries the prefilter epilogue (VAR bits 8 + 6) since round 3;
-  // gemm8_variant = 13: the round-2 forms, for A/B
-  constexpr int PV = PHASE == 1 ? 256 + 64 : 0;
-  if (variant != 1) {
-    if (pitch8 == 384) {
-      if constexpr (CT8 == 8 && PHASE == 1) {  // the tile epilogue as one block + one branch (VAR bit 6)
-        // (15 .. 18 = round 4's 4 x 2 wave split, measured 18-47 % slower and removed: profiles/r04/c4_split/)
-        if (variant == 6) return gemm_i8_kernel<1, 8, 3, 384, 64>;
-        // (21 .. 25 = round 4's four waves of 64 rows x 256 queries, one per SIMD with 256 + 256 registers: never ran clean
-        // through the register allocator, and VALU ops cannot read the accumulator file -- profiles/r04/c4_wide/)
-        // 27 .. 29: the row stream through buffer loads (VAR bit 9), which frees the registers a ring of 6 k-steps needs
-        if (variant == 27) return gemm_i8_kernel<1, 8, 6, 384, 512 + 128>;       // ring 6, window 4, branch per column group
-        if (variant == 28) return gemm_i8_kernel<1, 8, 6, 384, 512 + 128 + 64>;  // ring 6, window 4, one-block epilogue
-        if (variant == 29) return gemm_i8_kernel<1, 8, 3, 384, 512 + 256 + 64>;  // the product form on buffer loads
-        // timing only (wrong answers): 30 = matrix ops alone; 31 / 32 = no epilogue / product form over an L2-resident row stream
-        if (variant == 30) return gemm_i8_kernel<1, 8, 3, 384, 4 + 8 + 16>;
-        if (variant == 31) return gemm_i8_kernel<1, 8, 3, 384, 4 + 1024>;
-        if (variant == 32) return gemm_i8_kernel<1, 8, 3, 384, 256 + 64 + 1024>;
-        // default since round 3: the prefilter epilogue (VAR bit 8; -2 % against the round-2 form, identical candidates);
-        // 13 = the round-2 product form, for A/B
-        if (variant == 0 || variant == 14) return gemm_i8_kernel<1, 8, 3, 384, 256 + 64>;  // ... its 16 tests in one block, one branch
-        if (variant == 12) return gemm_i8_kernel<1, 8, 3, 384, 256>;                       // ... with a branch per column group
-        if (variant == 13) return gemm_i8_kernel<1, 8, 3, 384>;
-        if (variant == 7) return gemm_i8_kernel<1, 8, 3, 384, 128>;   // query-fragment window of 4 instead of 8
-        // (9 = ... and the 16 freed registers as two more k-steps of row ring: 0.891 vs 0.844 ms, 16 B of scratch; measured in
-        // profiles/r03/c4_i8/ab_0_7_9.json and removed)
-      }
-      if constexpr (CT8 == 8)
-        return variant == 2   ? gemm_i8_kernel<PHASE, 8, 3, 384, 1>
-               : variant == 3 ? gemm_i8_kernel<PHASE, 8, 3, 384, 2>
-               : variant == 4 ? gemm_i8_kernel<PHASE, 8, 2, 384>
-               : variant == 5 ? gemm_i8_kernel<PHASE, 8, 3, 384, 32>
-               : variant == 8 ? gemm_i8_kernel<PHASE, 8, 3, 384, 4>
-               : variant == 10 ? gemm_i8_kernel<PHASE, 8, 3, 384, 12>
-               : variant == 11 ? gemm_i8_kernel<PHASE, 8, 3, 384, 20>
-                              : gemm_i8_kernel<PHASE, 8, 3, 384>;
-      else return variant == 13 ? gemm_i8_kernel<PHASE, CT8, 6, 384> : gemm_i8_kernel<PHASE, CT8, 6, 384, PV>;
-    }
-    if constexpr (CT8 <= 4)
-      if (pitch8 == 768) return variant == 13 ? gemm_i8_kernel<PHASE, CT8, 6, 768> : gemm_i8_kernel<PHASE, CT8, 6, 768, PV>;
+static void (*pick_gemm8(uint32_t pitch8, int ring, bool l2, bool masked, int variant))(Gemm8Args) {
+  constexpr int C = WDBX_METRIC_COSINE, L = WDBX_METRIC_L2;
+  if constexpr (PHASE == 0) {
+    return l2 ? gemm8_instance<0, CT8, EPI8_EXACT, L, false>(pitch8, ring) : gemm8_instance<0, CT8, EPI8_EXACT, C, false>(pitch8, ring);
+  } else {
+    if (l2) return masked ? gemm8_instance<1, CT8, EPI8_EXACT, L, true>(pitch8, ring) : gemm8_instance<1, CT8, EPI8_EXACT, L, false>(pitch8, ring);
+    if (masked) return gemm8_instance<1, CT8, EPI8_PRE_BLOCK, C, true>(pitch8, ring);
+    if (variant == 13) return gemm8_instance<1, CT8, EPI8_EXACT, C, false>(pitch8, ring);
+    if constexpr (CT8 == 8)
+      if (variant == 12 && pitch8 == 384) return gemm_i8_kernel<1, 8, 3, 384, EPI8_PRE_GROUP>;
+    return gemm8_instance<1, CT8, EPI8_PRE_BLOCK, C, false>(pitch8, ring);
   }
-  const bool r2 = variant == 13 || variant == 1;  // (1 = run-time pitch everywhere, in its round-2 form)
-  if constexpr (CT8 < 8) {  // (256-query blocks with run-time addressing have registers for 2 k-steps in flight, not more)
-    if (ring == 6) return r2 ? gemm_i8_kernel<PHASE, CT8, 6> : gemm_i8_kernel<PHASE, CT8, 6, 0, PV>;
-    if (ring == 4) return r2 ? gemm_i8_kernel<PHASE, CT8, 4> : gemm_i8_kernel<PHASE, CT8, 4, 0, PV>;
-  }
-  return r2 ? gemm_i8_kernel<PHASE, CT8, 2> : gemm_i8_kernel<PHASE, CT8, 2, 0, PV>;
-}
-
-// the full pass of a call with a row mask (MASKED: the bad rows of g.gbad leave the hit set before pairs are appended): the
-// product forms of pick_gemm8 / pick_gemm8_l2 and nothing else
-template <int CT8>
-static void (*pick_gemm8_masked(uint32_t pitch8, int ring, bool l2))(Gemm8Args) {
-  constexpr int C = WDBX_METRIC_COSINE, L = WDBX_METRIC_L2, PV = 256 + 64;
-  if (l2) {
-    if constexpr (CT8 <= 4) {
-      if (pitch8 == 384) return gemm_i8_kernel<1, CT8, 6, 384, 0, L, true>;
-      if (pitch8 == 768) return gemm_i8_kernel<1, CT8, 6, 768, 0, L, true>;
-      if (ring == 6) return gemm_i8_kernel<1, CT8, 6, 0, 0, L, true>;
-      if (ring == 4) return gemm_i8_kernel<1, CT8, 4, 0, 0, L, true>;
-      return gemm_i8_kernel<1, CT8, 2, 0, 0, L, true>;
-    }
-    return nullptr;
-  }
-  if (pitch8 == 384) {
-    if constexpr (CT8 == 8) return gemm_i8_kernel<1, 8, 3, 384, PV, C, true>;
-    else return gemm_i8_kernel<1, CT8, 6, 384, PV, C, true>;
-  }
-  if constexpr (CT8 <= 4) {
-    if (pitch8 == 768) return gemm_i8_kernel<1, CT8, 6, 768, PV, C, true>;
-    if (ring == 6) return gemm_i8_kernel<1, CT8, 6, 0, PV, C, true>;
-    if (ring == 4) return gemm_i8_kernel<1, CT8, 4, 0, PV, C, true>;
-  }
-  return gemm_i8_kernel<1, CT8, 2, 0, PV, C, true>;
 }
 
 template <int PHASE>
@@ -1799,15 +1738,9 @@ static int launch_gemm8(wdbx_index* ix, const Gemm8Args& g, int ct, bool masked 
   const int ring = ct == 4 ? 2 : (steps % 6 == 0 ? 6 : steps % 4 == 0 ? 4 : 2);
   const int var = (int)ix->opt_gemm8_variant;
   const bool l2 = ix->metric == WDBX_METRIC_L2;
-  void (*fn)(Gemm8Args) = (PHASE == 1 && masked)
-                              ? (ct == 4 ? pick_gemm8_masked<8>(g.pitch8, ring, l2)
-                                 : ct == 2 ? pick_gemm8_masked<4>(g.pitch8, ring, l2)
-                                           : pick_gemm8_masked<2>(g.pitch8, ring, l2))
-                          : l2
-                              ? (ct == 2 ? pick_gemm8_l2<PHASE, 4>(g.pitch8, ring) : ct == 1 ? pick_gemm8_l2<PHASE, 2>(g.pitch8, ring) : nullptr)
-                          : ct == 4 ? pick_gemm8<PHASE, 8>(g.pitch8, ring, var)
-                          : ct == 2 ? pick_gemm8<PHASE, 4>(g.pitch8, ring, var)
-                                    : pick_gemm8<PHASE, 2>(g.pitch8, ring, var);
+  void (*fn)(Gemm8Args) = ct == 4   ? pick_gemm8<PHASE, 8>(g.pitch8, ring, l2, masked, var)
+                          : ct == 2 ? pick_gemm8<PHASE, 4>(g.pitch8, ring, l2, masked, var)
+                                    : pick_gemm8<PHASE, 2>(g.pitch8, ring, l2, masked, var);
   if (!fn) return fail(WDBX_E_STATE, "no int8 tile instance for this query block");
   const size_t lds = (size_t)64 * ct * g.pitch8 + (size_t)64 * ct * sizeof(f4);  // the query block + its parameters
   HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -93,34 +93,34 @@ __device__ __forceinline__ uint32_t g8_bswz(uint32_t c, uint32_t r, bool odd) {
 // (64 bytes of every row: two A fragments) in flight per wave, a divisor of pitch8 / 64; PITCH8 = the rows' bytes as a
 // compile-time constant (384, 768: every LDS read address is then one of a few per-lane registers plus an immediate, no
 // address arithmetic in the loop) or 0 = run time.
-// VAR: experiment switches (option gemm8_variant; 0 = the product form):
-//   bit 0: row stream with the default cache policy instead of non-temporal
-//   bit 1: SIMD partners (waves w, w + 4) start half a tile apart (measured: no gain)
-//   bit 2: TIMING ONLY, wrong answers: no tile epilogue
-//   bit 5: the tile epilogue inside the next tile's first k-step instead of a block of its own (measured: slower)
-//   bit 8: (PHASE 1, inner product) PREFILTER epilogue: per lane and column group a launch-constant U = A1 - a_ref E' - b_ref M'
-//          (16 registers, paid for by a query-fragment window of 4); on a tile whose group is ordinary (a_g <= a_ref,
-//          b_g <= b_ref) the test "max of 8 accumulators >= e_inv U - 1" needs no LDS read and one fma, and is never stricter
-//          than the exact one, which runs -- unchanged -- only for the column groups that pass it
-//   bit 3: TIMING ONLY: the row stream is not read inside the loop;  bit 4: TIMING ONLY: no query-fragment reads inside the loop
-//   bit 10: TIMING ONLY: the row stream re-reads the workgroup's FIRST tile (an L2-resident stream: the vector-memory path without HBM)
-//   bit 6: (PHASE 1) the tile epilogue as ONE straight-line block + one branch: all NJ (threshold, max of 8 accumulators,
-//          compare) in a row with the hit masks kept in scalar registers, then -- in about two tiles of three -- the rows
-//          of the column groups that had a hit.  (The product form branches per column group: each of its 16 blocks
-//          waits out its own LDS read of the query parameters.)
+// Epi8 = the form of the PHASE 1 tile epilogue (PHASE 0 and L2 run EPI8_EXACT only):
+//   EPI8_EXACT      per column group the exact test "max of 8 accumulators >= T(group, query)" (one LDS read of the query's
+//                   parameters, three fmas) and a branch; the round-2 form, kept as the A/B partner of the two below
+//                   (option gemm8_variant = 13)
+//   EPI8_PRE_GROUP  (inner product) a PREFILTER in front of it: per lane and column group a launch-constant
+//                   U = A1 - a_ref E' - b_ref M' (16 registers, paid for by a query-fragment window of 4 instead of 8); on a
+//                   tile whose group is ordinary (a_g <= a_ref, b_g <= b_ref) the test "max of 8 accumulators >= e_inv U - 1"
+//                   needs no LDS read and one fma, and is never stricter than the exact one, which runs -- unchanged -- only
+//                   for the column groups that pass it.  A branch per column group (gemm8_variant = 12)
+//   EPI8_PRE_BLOCK  the same with all NJ prefilter tests in ONE straight-line block, the hit masks kept in scalar registers,
+//                   one branch, then the exact epilogue of the column groups that passed: the product form
+// The other forms measured on the way here (row stream through buffer loads or with the default cache policy, staggered SIMD
+// partners, the epilogue inside the next tile's first k-step, timing-only ablations) are on record in NOTEBOOK.md and profiles/.
 // MASKED (PHASE 1, the product forms only): a.gbad is the CALL's bad-row table (gbad_with_mask_kernel: removed rows, rows past
 // the end and the rows the caller's row mask leaves out); the wave's 32 bits are read on the scalar path as in PHASE 0 and its
 // bad rows are cleared from the hit set BEFORE pairs are appended -- with a selective mask tau is low, and masked-out rows
 // above it would otherwise flood the per-wave pair lists.  PHASE 0 needs no flag: fed the same table, a masked-out row cannot vouch.
-template <int PHASE, int CT8, int RING, int PITCH8 = 0, int VAR = 0, int METRIC = WDBX_METRIC_COSINE, bool MASKED = false>
+enum Epi8 { EPI8_EXACT, EPI8_PRE_GROUP, EPI8_PRE_BLOCK };
+template <int PHASE, int CT8, int RING, int PITCH8 = 0, Epi8 EPI = EPI8_EXACT, int METRIC = WDBX_METRIC_COSINE, bool MASKED = false>
 __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
   // (exactly the forms whose append sites clear the bad rows: the prefilter epilogue for inner product, the plain one for L2)
-  static_assert(!MASKED || (PHASE == 1 && VAR == (METRIC == WDBX_METRIC_L2 ? 0 : 256 + 64)),
+  static_assert(!MASKED || (PHASE == 1 && EPI == (METRIC == WDBX_METRIC_L2 ? EPI8_EXACT : EPI8_PRE_BLOCK)),
                 "row masks: the full pass of the product forms only");
+  static_assert(EPI == EPI8_EXACT || (PHASE == 1 && METRIC == WDBX_METRIC_COSINE), "the prefilter: the inner-product full pass only");
   constexpr bool L2 = METRIC == WDBX_METRIC_L2;
   constexpr int GBN = 32 * CT8, NJ = 2 * CT8;  // NJ column groups of 16 queries
-  constexpr bool PRE = PHASE == 1 && (VAR & 256) != 0 && METRIC == WDBX_METRIC_COSINE;
-  constexpr int WMAX = ((VAR & 128) || PRE) ? 4 : 8;  // (bit 7, experiment: a window of 4 register sets instead of 8)
+  constexpr bool PRE = EPI != EPI8_EXACT;
+  constexpr int WMAX = PRE ? 4 : 8;            // (the prefilter's U[NJ] is paid for by a window of 4 register sets instead of 8)
   constexpr int W = NJ < WMAX ? NJ : WMAX;     // query fragments in flight (a rolling window over the (k-step, group) sequence)
   extern __shared__ __attribute__((aligned(16))) char lds8[];
   const uint32_t pitch8 = PITCH8 ? (uint32_t)PITCH8 : a.pitch8;
@@ -206,40 +206,14 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
   const uint32_t gdim = gridDim.x;
   uint32_t ld_tile = blockIdx.x, ld_s = 0;   // loader cursor
   const int8_t* ld_p = a.rows8 + ((size_t)ld_tile * a.tile_stride * 8 + wave) * blk_bytes + lane * 16;
-  // bit 9: the stream through BUFFER loads -- a descriptor of this wave's block of the tile in 4 scalar registers (rebuilt per
-  // tile on the scalar unit), ONE vector register of lane offset, the k-step as scalar offset + immediate -- instead of a
-  // 64-bit per-lane pointer and its carries: the registers that buys are what a ring of 6 k-steps needs to fit without scratch
-  constexpr bool BUF = (VAR & 512) != 0;
-  auto block_rsrc = [&](uint32_t tile) {
-    const u64 blk = (u64)__builtin_amdgcn_readfirstlane(tile * a.tile_stride * 8 + wave);
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(a.rows8 + blk * blk_bytes), (short)0, (int)blk_bytes, 0x00020000);
-  };
-  __amdgpu_buffer_rsrc_t ld_rsrc = block_rsrc(ld_tile);
-  const uint32_t lane_off = (uint32_t)lane * 16;
   i32x4 ring[RING][2];
   auto load_next = [&](int j) {
-    if constexpr (BUF) {
-      ring[j][0] = (i32x4)__builtin_amdgcn_raw_buffer_load_b128(ld_rsrc, lane_off, ld_s * 2048, 2);          // (aux 2 = nt)
-      ring[j][1] = (i32x4)__builtin_amdgcn_raw_buffer_load_b128(ld_rsrc, lane_off, ld_s * 2048 + 1024, 2);
-      if (++ld_s == steps) {
-        ld_s = 0;
-        if (ld_tile + gdim < a.num_tiles) ld_tile += gdim;  // past the last tile: re-read it (valid memory, never used)
-        ld_rsrc = block_rsrc(ld_tile);
-      }
-      return;
-    }
-    if constexpr (VAR & 1) {
-      ring[j][0] = *(const i32x4*)ld_p;
-      ring[j][1] = *(const i32x4*)(ld_p + 1024);
-    } else {
-      ring[j][0] = __builtin_nontemporal_load((const i32x4*)ld_p);
-      ring[j][1] = __builtin_nontemporal_load((const i32x4*)(ld_p + 1024));
-    }
+    ring[j][0] = __builtin_nontemporal_load((const i32x4*)ld_p);
+    ring[j][1] = __builtin_nontemporal_load((const i32x4*)(ld_p + 1024));
     ld_p += 2048;
     if (++ld_s == steps) {
       ld_s = 0;
-      // past the last tile: re-read it (valid memory, never used)
-      if (!(VAR & 1024) && ld_tile + gdim < a.num_tiles) ld_tile += gdim;
+      if (ld_tile + gdim < a.num_tiles) ld_tile += gdim;  // past the last tile: re-read it (valid memory, never used)
       ld_p = a.rows8 + ((size_t)ld_tile * a.tile_stride * 8 + wave) * blk_bytes + lane * 16;
     }
   };
@@ -263,17 +237,9 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
 #pragma unroll
   for (int j = 0; j < W; ++j) bf[j] = b_read(0, j, tb);
 
-  if constexpr ((VAR & 2) != 0) {
-    if (wave >= 4)
-      for (uint32_t i = 0; i < steps * NJ / 4; ++i) __builtin_amdgcn_s_sleep(1);  // steps * NJ matrix ops of 16 cycles = half a tile alone on the pipe
-  }
-
   // ---- the tile epilogue, one column group at a time: this wave's 32 rows x 16 queries, one scale for all of them ----
-  // e_* = the state of the tile whose accumulators are in the registers (wave-uniform).  Product form: a block of its own
-  // behind the tile's last k-step.  (VAR bit 5 runs group j's epilogue inside the NEXT tile's first k-step, right before the
-  // two matrix ops that restart group j's accumulators, so that its vector instructions issue under matrix ops: the branches
-  // cut that k-step into 16 blocks and it came out slower, 0.82 vs 0.79 ms.)
-  bool e_have = false;
+  // e_* = the state of the tile whose accumulators are in the registers (wave-uniform); the epilogue is a block of its own
+  // behind the tile's last k-step.
   uint32_t e_wrow0 = 0, e_ht = 0;
   f4 e_gt = {0.f, 0.f, 0.f, 0.f};
   float e_inv = 0.f, e_ai = 0.f, e_bi = 0.f;
@@ -390,8 +356,6 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
       }
     }
   };
-  constexpr bool FUSED = (VAR & 32) != 0;   // (bit 5; measured slower than the epilogue as a block of its own: 0.82 vs 0.79 ms)
-  constexpr bool NO_EPI = (VAR & 4) != 0;
   // ---- PRE: the launch-constant part of the prefilter threshold, per lane and column group ----
   float U[PRE ? NJ : 1];
   float g_aref = 0.f, g_bref = 0.f;
@@ -405,7 +369,6 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
       U[j] = u - 4e-6f * (fabsf(p.x) + g_aref * p.y + g_bref * p.z);  // (low by more than the two chains' roundings can differ)
     }
   }
-  constexpr bool EPI1 = PHASE == 1 && (VAR & 64) != 0 && !L2 && !PRE;
   auto load_norm_terms = [&]() {  // L2: once per tile, before its epilogue
     if constexpr (L2) {
       const uint32_t lrow0 = e_wrow0 + 4 * kb;
@@ -415,36 +378,6 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
         const float cn = a.cn[row < a.n_rows ? row : a.n_rows - 1];
         if constexpr (PHASE == 0) e_u[r] = cn * 1.0001f;
         else e_u[r] = (cn != cn) ? INFINITY : (cn < INFINITY ? 0.5f * cn * 0.9999f * e_inv : -INFINITY);
-      }
-    }
-  };
-  auto epilogue_block = [&]() {  // (bit 6) every column group's test first, one branch, then the groups that had a hit
-    const uint32_t lrow0 = e_wrow0 + 4 * kb;
-    u64 hm[NJ], any = 0;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const f4 p = qpl[j * 16];  // {A1, E', M', padded}
-      const float T = fmaf(-e_bi, p.z, fmaf(-e_ai, p.y, fmaf(e_inv, p.x, -1.0f)));
-      int m = max(max(acc[j][0][0], acc[j][0][1]), max(acc[j][0][2], acc[j][0][3]));
-      m = max(m, max(max(acc[j][1][0], acc[j][1][1]), max(acc[j][1][2], acc[j][1][3])));
-      hm[j] = __ballot(!((float)m < T) && p.w == 0.f);
-      any |= hm[j];
-    }
-    if (any) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        if (!hm[j]) continue;
-        const f4 p = qpl[j * 16];
-        const float T = fmaf(-e_bi, p.z, fmaf(-e_ai, p.y, fmaf(e_inv, p.x, -1.0f)));  // (the same chain: the same value)
-        uint32_t bits = 0, q = (uint32_t)l15;
-        asm volatile("" : "+v"(q));
-        q += j * 16;
-        if ((hm[j] >> lane) & 1) {
-#pragma unroll
-          for (int r = 0; r < 8; ++r)
-            if (!((float)acc[j][r >> 2][r & 3] < T) && lrow0 + 16 * (r >> 2) + (r & 3) < a.n_rows) bits |= 1u << r;
-        }
-        append_pairs(bits, q, j, lrow0);
       }
     }
   };
@@ -460,8 +393,6 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
           if (decltype(first_tag)::value && jj == 0) {
-            if constexpr (FUSED && !NO_EPI)
-              if (e_have) epilogue(j);  // the previous tile's column group j, before its accumulators restart
             const i32x4 zero = {0, 0, 0, 0};
             acc[j][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af0, bf[j % W], zero, 0, 0, 0);
             acc[j][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af1, bf[j % W], zero, 0, 0, 0);
@@ -469,22 +400,17 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
             acc[j][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af0, bf[j % W], acc[j][0], 0, 0, 0);
             acc[j][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af1, bf[j % W], acc[j][1], 0, 0, 0);
           }
-          if constexpr ((VAR & 16) != 0) asm volatile("" : "+v"(bf[j % W]));
-          else if (j + W < NJ) bf[j % W] = b_read(s0 + jj, j + W, tb);
+          if (j + W < NJ) bf[j % W] = b_read(s0 + jj, j + W, tb);
           else bf[j % W] = b_read(sn, j + W - NJ, tbn);
         }
-        // (keep that order: one fragment read behind each pair of matrix ops, not all reads in a clump behind the last one;
-        // the k-step that carries the epilogue is cut into blocks by its branches and keeps program order anyway)
-        if (!(decltype(first_tag)::value && jj == 0 && FUSED && !NO_EPI)) {
+        // (keep that order: one fragment read behind each pair of matrix ops, not all reads in a clump behind the last one)
 #pragma unroll
-          for (int j = 0; j < NJ; ++j) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);  // MFMA
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
-          }
-          __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);    // VMEM read: the ring's loads stay HERE (not sunk to their use)
+        for (int j = 0; j < NJ; ++j) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);  // MFMA
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
         }
-        if constexpr ((VAR & 8) != 0) asm volatile("" : "+v"(ring[jj][0]), "+v"(ring[jj][1]));
-        else load_next(jj);  // the k-step RING further down the stream takes the slot just consumed
+        __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);    // VMEM read: the ring's loads stay HERE (not sunk to their use)
+        load_next(jj);  // the k-step RING further down the stream takes the slot just consumed
         tb = tbn;
       }
     };
@@ -497,11 +423,6 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
       for (uint32_t s0 = RING; s0 < steps; s0 += RING) trip(std::false_type{}, s0);
     }
 
-    if constexpr (NO_EPI) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) asm volatile("" ::"v"(acc[j][0]), "v"(acc[j][1]));
-      continue;
-    }
     // this tile's accumulators are complete: its epilogue state
     e_wrow0 = (t * a.tile_stride * 8 + wave) * 32;
     e_ht = t * 8 + wave;
@@ -529,22 +450,18 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
       e_ai = e_gt.y * e_inv;
       e_bi = e_gt.z * e_inv;
     }
-    e_have = true;
     load_norm_terms();
-    if constexpr (EPI1) {
-      epilogue_block();
-      e_have = false;
-    } else if constexpr (PRE) {
+    if constexpr (PRE) {
       // (wave-uniform; a NaN or infinite bound compares false: the exact epilogue for every column group)
       const bool ordinary = __builtin_amdgcn_readfirstlane((e_gt.y <= g_aref && e_gt.z <= g_bref) ? 1 : 0) != 0;
-      if constexpr ((VAR & 64) != 0) {  // (experiment: all NJ prefilter tests in a row, one branch, then the groups that passed)
+      if constexpr (EPI == EPI8_PRE_BLOCK) {  // all NJ prefilter tests in a row, one branch, then the groups that passed
         if (ordinary) {
           u64 hm[NJ], any = 0;
 #pragma unroll
           for (int j = 0; j < NJ; ++j) {
             int m = max(max(acc[j][0][0], acc[j][0][1]), max(acc[j][0][2], acc[j][0][3]));
             m = max(m, max(max(acc[j][1][0], acc[j][1][1]), max(acc[j][1][2], acc[j][1][3])));
-            hm[j] = __ballot(!((float)m < fmaf(e_inv, U[PRE ? j : 0], -1.0f)));
+            hm[j] = __ballot(!((float)m < fmaf(e_inv, U[j], -1.0f)));
             any |= hm[j];
           }
           if (any) {
@@ -556,26 +473,19 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
 #pragma unroll
           for (int j = 0; j < NJ; ++j) epilogue(j);
         }
-      } else
+      } else {
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        bool go = !ordinary;
-        if (ordinary) {
-          int m = max(max(acc[j][0][0], acc[j][0][1]), max(acc[j][0][2], acc[j][0][3]));
-          m = max(m, max(max(acc[j][1][0], acc[j][1][1]), max(acc[j][1][2], acc[j][1][3])));
-          go = __any(!((float)m < fmaf(e_inv, U[PRE ? j : 0], -1.0f)));
+        for (int j = 0; j < NJ; ++j) {
+          bool go = !ordinary;
+          if (ordinary) {
+            int m = max(max(acc[j][0][0], acc[j][0][1]), max(acc[j][0][2], acc[j][0][3]));
+            m = max(m, max(max(acc[j][1][0], acc[j][1][1]), max(acc[j][1][2], acc[j][1][3])));
+            go = __any(!((float)m < fmaf(e_inv, U[j], -1.0f)));
+          }
+          if (go) epilogue(j);
         }
-        if (go) epilogue(j);
       }
-      e_have = false;
-    } else if constexpr (!FUSED) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) epilogue(j);
-      e_have = false;
-    }
-  }
-  if constexpr (FUSED && !NO_EPI) {
-    if (e_have) {  // the last tile's epilogue
+    } else {
 #pragma unroll
       for (int j = 0; j < NJ; ++j) epilogue(j);
     }

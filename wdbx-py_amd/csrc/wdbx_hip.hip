@@ -1525,7 +1525,6 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"scan_shadow", &wdbx_index::opt_scan_shadow},
     {"scan8_wgs", &wdbx_index::opt_scan8_wgs},
     {"scan8_per_query", &wdbx_index::opt_scan8_per_query},
-    {"scan8_ablate", &wdbx_index::opt_scan8_ablate},
     {"scan_u6", &wdbx_index::opt_scan_u6},
     {"scan_u6_cap", &wdbx_index::opt_scan_u6_cap},
     {"batch_repair", &wdbx_index::opt_batch_repair},
@@ -1548,6 +1547,8 @@ int wdbx_index_set_option(wdbx_index* ix, const char* name, int64_t value) try {
   std::lock_guard<std::mutex> lk(ix->mu);
   int64_t* slot = option_slot(ix, name);
   if (!slot) return fail(WDBX_E_INVALID, "unknown option '%s'", name ? name : "(null)");
+  if (slot == &ix->opt_gemm8_variant && value != 0 && value != 12 && value != 13 && value != 14)
+    return fail(WDBX_E_INVALID, "gemm8_variant %lld: 0 (= 14), 12 and 13 are the forms the library has", (long long)value);
   *slot = value;
   if (!strcmp(name, "group_bounds")) ix->gmax_valid = false;  // re-decide (and rebuild the group maxima) at the next batch
   return WDBX_OK;
