@@ -128,6 +128,27 @@ int wdbx_index_search_masked(wdbx_index* idx, const float* queries, int nq, int 
 int wdbx_index_search_masked_n(wdbx_index* idx, const float* queries, int nq, int k, int normalize_queries,
                                const uint32_t* mask_words, uint64_t mask_word_count, int64_t* out_idx, float* out_score);
 
+/* ---- search among listed rows: the exact top-k of an explicit row list -------- */
+/* The exact fp32 top-k of the rows row_ids[0 .. n_ids) (host memory, the index's own row numbers) for each of nq host
+ * queries [nq, dim]: what a selective `filter=` (vector_store.py:337-342 post-filters a top-k instead) or "rank these
+ * candidates" costs when only the listed rows are read -- n_ids rows per block of queries, not the shard.  Blocking.
+ *   Results: the format and order of wdbx_index_search -- (score descending, row ascending), L2 (distance ascending, row
+ *   ascending) with positive squared distances; unused slots hold row -1 and score 0 (fewer than k listed rows, n_ids == 0).
+ *   A row whose score is NaN (removed rows, rows with a NaN element) is never returned.
+ *   Scores: exactly the arithmetic of the candidates' re-scoring on every other path (rescore_kernel), so a listed row's
+ *   score is bit-identical to what wdbx_index_search, the masked calls and wdbx_index_range_search return for it.
+ *   row_ids must be STRICTLY INCREASING and below the row count, checked under the handle's lock (a list built before a
+ *   concurrent add stays valid: row numbers do not move); anything else is WDBX_E_INVALID, as are k outside
+ *   [1, WDBX_MAX_K] and nq < 1.  n_ids may be 0 (every slot -1) and as large as the index.
+ *   Every fetched row is scored against a block of queries (8 up to k = 64, 4 up to k = 128, else 1; a lone query is the
+ *   block of one).  Routes (get_option "last_rows_path"): 1 = lists of at most option "rows_keys_max" rows (default 8192):
+ *   a key per listed row and query, ranked by the merge kernel; 2 = per-workgroup top-k lists merged like the fp32 scan's;
+ *   3 = k from option "select_min_k" on a longer list: a key per listed row, then the radix-select chain per query;
+ *   0 = nothing launched (empty list).  The scoring launches count as scan launches in wdbx_index_profile_read.
+ *   The call holds the handle's mutex to its end.  Nothing of a call's list stays valid in the handle. */
+int wdbx_index_search_rows(wdbx_index* idx, const float* queries, int nq, int k, int normalize_queries,
+                           const uint64_t* row_ids, uint64_t n_ids, int64_t* out_idx, float* out_score);
+
 /* ---- range search: every row within a similarity, no k ----------------------- */
 /* every row whose score reaches thresholds[q] (cosine/IP: score >= t; L2: squared distance <= t), exact fp32,
  * per query sorted like wdbx_index_search; replaces faiss' IndexFlat range_search, which the reference never reaches
@@ -315,9 +336,9 @@ int wdbx_index_probe_read(wdbx_index* idx, int nontemporal, int blocks, int reps
  * scan_blocked, scan_generic, scan_force_ragged, exchange_batch, lds_lists, merge_fast (1: merges whose keys fit the registers are ranked there, default; 0: always the list walk), scan_one_grid (1: a round of several queries on the fp32 scan over a corpus of at most 1 GiB is one grid with a row per query, default; 0: a launch per query), poll_done (1: a blocking call of up to 32 queries whose chain ends in a final merge polls a word that kernel writes into the mapped staging slot, default; 0: always waits on its event), zero_copy, wg_merge, select_min_k,
  * scan_shadow (2 u8 selection scan / 1 bf16 tiles / 0 fp32 scan; range search: 2 u8 selection, below 2 the fp32 range scan), scan8_wgs, single_min_rows,
  * range_min_rows (rows from which a range search takes the u8 selection scan, default 131 072), gemm_bf16 (tile family
- * 3/2/1/0 as above), gemm_ct, gemm_l2, gemm_l2_i8, gemm8_variant (the i8 tiles' full-pass epilogue, for A/B: 0 = 14 the product form, 12, 13; any other value returns WDBX_E_INVALID), gemm8_refine (1: second selection stage of the i8 tiles, default), batch_repair, scan8_per_query, scan8_sample4 (1: a round's sample pass serves 3-4 queries per workgroup when the sample is too large for the L2s; 2: always; 0: never), gemm_min_queries, gemm_min_rows, gemm_min_work (below gemm_min_rows: the tiles from queries x rows >= this, default 800000; 0: never), gemm_sample_div, gemm_masked (1: a masked call with enough queries is one masked pass over the int8 tiles, default; 0: masked per-query scans), group_bounds.
+ * 3/2/1/0 as above), gemm_ct, gemm_l2, gemm_l2_i8, gemm8_variant (the i8 tiles' full-pass epilogue, for A/B: 0 = 14 the product form, 12, 13; any other value returns WDBX_E_INVALID), gemm8_refine (1: second selection stage of the i8 tiles, default), batch_repair, scan8_per_query, scan8_sample4 (1: a round's sample pass serves 3-4 queries per workgroup when the sample is too large for the L2s; 2: always; 0: never), gemm_min_queries, gemm_min_rows, gemm_min_work (below gemm_min_rows: the tiles from queries x rows >= this, default 800000; 0: never), gemm_sample_div, gemm_masked (1: a masked call with enough queries is one masked pass over the int8 tiles, default; 0: masked per-query scans), group_bounds, rows_keys_max (wdbx_index_search_rows: lists of at most this many rows are ranked from one key per listed row, default 8192; 0: never).
  * get_option also answers the read-only names: last_gemm_family (0/1/2/3: what the last batch ran on),
- * last_single_path (0 fp32 scan / 1 bf16 tiles / 2 u8 selection scan), last_range_path (0 fp32 range scan / 2 u8 selection + exact filter), last_sample_qn (queries per workgroup of the last u8 sample launch: 1, 3 or 4), last_batch_repaired, last_batch_masked (1: the last batch ran the masked tile pass), last_batch_allowed_rows (the rows its mask allowed), shadow_rows + shadow_bytes (bf16 copy),
+ * last_single_path (0 fp32 scan / 1 bf16 tiles / 2 u8 selection scan), last_range_path (0 fp32 range scan / 2 u8 selection + exact filter), last_rows_path (the route of the last wdbx_index_search_rows: 0 nothing launched / 1 keys + merge / 2 lists + merge / 3 keys + radix select), last_sample_qn (queries per workgroup of the last u8 sample launch: 1, 3 or 4), last_batch_repaired, last_batch_masked (1: the last batch ran the masked tile pass), last_batch_allowed_rows (the rows its mask allowed), shadow_rows + shadow_bytes (bf16 copy),
  * shadow8_rows + shadow8_bytes (u8 copy), shadowg_rows + shadowg_bytes (group-scaled i8 copy), group_bounds_active,
  * exchanges (all-gather + merge steps this handle's per-rank communicator has enqueued), device_bytes_resident (every device
  * allocation of the handle: fp32 rows, shadow copies and their tables, scratch). */

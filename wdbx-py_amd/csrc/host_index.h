@@ -152,6 +152,12 @@ struct wdbx_index {
   size_t rcand_bytes = 0, rkeys_bytes = 0, rcnt_bytes = 0, rthr_bytes = 0;
   uint32_t range_cand_cap = 16384, range_out_cap = 16384;
   int last_range_path = 0;     // 0 fp32 range scan, 2 u8 selection scan + exact filter (what the last range search ran on)
+  // search among listed rows (wdbx_index_search_rows): the device copy of the call's row list and, on the key routes, one key
+  // per listed row and query of a round; the partial lists of the list route live in d_partials
+  uint32_t* d_sub_ids = nullptr;
+  u64* d_sub_keys = nullptr;
+  size_t sub_ids_bytes = 0, sub_keys_bytes = 0;
+  int last_rows_path = 0;      // 0 nothing launched (empty list), 1 keys + merge, 2 lists + merge, 3 keys + radix select
   // profiling
   bool profile = false;
   EventPool scan_ev, merge_ev, gemm_ev, sample_ev;
@@ -162,7 +168,7 @@ struct wdbx_index {
           opt_gemm8_refine = 1, opt_scan8_sample4 = 1, opt_gemm_l2 = 1, opt_gemm_l2_i8 = 1, opt_force_ragged = 0,
           opt_gemm_ct = 0, opt_wg_merge = 1, opt_zero_copy = 1, opt_lone_host_select = 1, opt_lds_lists = 0,
           opt_merge_fast = 1, opt_poll_done = 1, opt_scan_one_grid = 1, opt_select_min_k = 200, opt_gemm_min_nq = 4, opt_gemm_min_rows = 65536, opt_gemm_min_work = 800000,
-          opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0, opt_gemm_masked = 1;
+          opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0, opt_gemm_masked = 1, opt_rows_keys_max = 8192;
 };
 
 struct DeviceGuard {

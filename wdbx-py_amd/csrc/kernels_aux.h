@@ -133,6 +133,16 @@ __global__ void tau_margin_kernel(float* tau, const float* queries, uint32_t pit
 //   would only add exact zeros to lane 0 (at most turning a -0 into +0, which every key normalises with + 0.0f anyway).
 //   NI > 0 (pitch4 <= NI * P): the same accumulation unrolled -- all NI loads issued before the first fma, no loop, so a caller
 //   that scores several rows at once gets every row's loads in flight together.  NI = 0: the loop, for any pitch4.
+//   exact_finish is the tail on its own (fold, tree, sign): a caller that accumulates ONE loaded row against several queries
+//   (kernels_subset.h) finishes each query's lanes with it, so its scores are these scores bit for bit.
+template <int METRIC, int P = 64>
+__device__ __forceinline__ float exact_finish(f4 acc) {
+  float s = (acc.x + acc.y) + (acc.z + acc.w);
+  for (int o = P / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (METRIC == WDBX_METRIC_L2) s = -s;
+  return s;
+}
+
 template <int METRIC, int P = 64, int NI = 0, bool NT = false>
 __device__ __forceinline__ float exact_score(const f4* cp, const f4* qp, uint32_t pitch4, uint32_t j) {
   f4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -152,10 +162,7 @@ __device__ __forceinline__ float exact_score(const f4* cp, const f4* qp, uint32_
     for (int t = 0; t < NI; ++t)
       if (j + (uint32_t)t * P < pitch4) acc = accum<METRIC>(acc, c[t], qv[t]);
   }
-  float s = (acc.x + acc.y) + (acc.z + acc.w);
-  for (int o = P / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if (METRIC == WDBX_METRIC_L2) s = -s;
-  return s;
+  return exact_finish<METRIC, P>(acc);
 }
 
 // every kept candidate of every query is re-scored exactly in fp32, one wave per candidate (exact_score); its key becomes

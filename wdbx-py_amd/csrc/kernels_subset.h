@@ -1,0 +1,152 @@
+// kernels_subset.h -- exact top-k among LISTED rows (wdbx_index_search_rows): the kernel walks the device copy of the caller's
+// row list instead of the corpus, one wave per listed row, and scores every fetched row against a block of QB queries.
+// Part of the single translation unit wdbx_hip.hip (included there, in order); not a standalone header.
+
+struct SubsetArgs {
+  const f4* rows;       // [n_rows, pitch4] quads
+  const f4* queries;    // [nq, pitch4] the round's queries
+  const uint32_t* ids;  // [n_ids] strictly increasing row numbers (validated on the host)
+  u64* out;             // lists: [nq][k][P] as the fp32 scan's partial lists; keys: [nq][key_stride], entry i = listed row i
+  uint64_t key_stride;
+  uint32_t n_ids;
+  uint32_t pitch4;
+  uint32_t nq;          // queries of the round (the last query block may be short: its idle slots repeat the last query)
+  int k;
+};
+
+// One loaded row against QB queries, each with exact_score's arithmetic (kernels_aux.h): lane j accumulates quads j, j + 64,
+// ... in that order with accum<METRIC> and exact_finish folds and reduces, so a score here is rescore_kernel's score bit for
+// bit -- the row's quads are simply used QB times once they are in registers.
+//   NI > 0 (pitch4 <= 64 NI): the queries' quads live in registers for the whole launch (q), the row's NI loads are issued by
+//   the caller (c), nothing is loaded here.  NI = 0: any pitch4, the loop, the queries read through the caches (qp).
+template <int METRIC, int QB, int NI>
+__device__ __forceinline__ void exact_score_block(const f4 (&c)[NI > 0 ? NI : 1], const f4* cp, const f4 (&q)[QB][NI > 0 ? NI : 1],
+                                                  const f4* const (&qp)[QB], uint32_t pitch4, uint32_t j, float (&s)[QB]) {
+  f4 acc[QB];
+#pragma unroll
+  for (int b = 0; b < QB; ++b) acc[b] = f4{0.f, 0.f, 0.f, 0.f};
+  if constexpr (NI == 0) {
+    for (uint32_t i = j; i < pitch4; i += 64) {
+      const f4 v = ld16<true>(cp + i);
+#pragma unroll
+      for (int b = 0; b < QB; ++b) acc[b] = accum<METRIC>(acc[b], v, qp[b][i]);
+    }
+  } else {
+#pragma unroll
+    for (int t = 0; t < NI; ++t)
+      if (j + (uint32_t)t * 64 < pitch4) {
+#pragma unroll
+        for (int b = 0; b < QB; ++b) acc[b] = accum<METRIC>(acc[b], c[t], q[b][t]);
+      }
+  }
+#pragma unroll
+  for (int b = 0; b < QB; ++b) s[b] = exact_finish<METRIC, 64>(acc[b]);
+}
+
+// MODE 0: a sorted list of k keys per wave and query in LDS (QB = 1), 1: in registers (k <= 128), 2: no list, every listed
+// row's key goes to out[query][i] (ranked by merge_kernel as unsorted candidates, or by the radix-select chain).
+// Grid: x = workgroups along the list (wave w of the grid takes listed rows w, w + W, ...; U rows' loads in flight per
+// wave), y = query blocks.  Lists: the workgroup's four wave lists are merged here (wave 0 walks the other three, as in
+// scan_body), so out holds one partial list per workgroup and query, in the layout merge_kernel merges for the fp32 scan.
+// Every lane of a wave ends with the same sum (the xor tree is symmetric), so a row's key is wave-uniform: it is read from
+// lane 0 into scalar registers and the list insert is a uniform branch.
+template <int METRIC, int QB, int NI, int MODE>
+__global__ __launch_bounds__(256) void subset_kernel(SubsetArgs a) {
+  constexpr bool REG = MODE == 1;
+  constexpr int U = NI == 0 ? 1 : (NI <= 2 ? 4 : 2);
+  constexpr int NR = NI > 0 ? NI : 1;
+  extern __shared__ u64 lds_lists[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t j = (uint32_t)lane;
+  const uint32_t q0 = blockIdx.y * QB;
+  TopList<REG> top[QB];
+  u64 thr[QB];
+  const f4* qp[QB];
+  f4 q[QB][NR];
+#pragma unroll
+  for (int b = 0; b < QB; ++b) {
+    if constexpr (MODE != 2) top[b].init(lds_lists + (size_t)(wave * QB + b) * a.k, a.k, lane);
+    thr[b] = 0;
+    qp[b] = a.queries + (size_t)min(q0 + (uint32_t)b, a.nq - 1) * a.pitch4;
+#pragma unroll
+    for (int t = 0; t < NR; ++t) {
+      q[b][t] = f4{0.f, 0.f, 0.f, 0.f};
+      if (NI > 0 && j + (uint32_t)t * 64 < a.pitch4) q[b][t] = qp[b][j + (uint32_t)t * 64];
+    }
+  }
+  const uint32_t W = gridDim.x * 4, wg = blockIdx.x * 4 + wave;
+  for (uint32_t cur = wg; cur < a.n_ids; cur += U * W) {
+    f4 c[U][NR];
+    uint32_t row[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t idx = cur + (uint32_t)u * W;
+      row[u] = a.ids[min(idx, a.n_ids - 1)];  // (past the end: the last listed row again, dropped below)
+      const f4* cp = a.rows + (size_t)row[u] * a.pitch4;
+#pragma unroll
+      for (int t = 0; t < NR; ++t) {
+        c[u][t] = f4{0.f, 0.f, 0.f, 0.f};
+        if (NI > 0 && j + (uint32_t)t * 64 < a.pitch4) c[u][t] = ld16<true>(cp + j + (uint32_t)t * 64);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t idx = cur + (uint32_t)u * W;
+      const bool live = idx < a.n_ids;  // (wave-uniform)
+      float s[QB];
+      exact_score_block<METRIC, QB, NI>(c[u], a.rows + (size_t)row[u] * a.pitch4, q, qp, a.pitch4, j, s);
+#pragma unroll
+      for (int b = 0; b < QB; ++b) {
+        const u64 mine = (live && s[b] == s[b]) ? make_key(s[b] + 0.0f, row[u]) : 0ull;  // a NaN score is never a result
+        if constexpr (MODE == 2) {
+          if (lane == 0 && live && q0 + (uint32_t)b < a.nq) a.out[(size_t)(q0 + b) * a.key_stride + idx] = mine;
+        } else {
+          const u64 key = readlane64(mine, 0);
+          if (key > thr[b]) thr[b] = top[b].insert(key, lane);
+        }
+      }
+    }
+  }
+  if constexpr (MODE != 2) {
+    if constexpr (REG) {
+#pragma unroll
+      for (int b = 0; b < QB; ++b) top[b].store(lds_lists + (size_t)(wave * QB + b) * a.k, 1, lane);
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int b = 0; b < QB; ++b) {
+        const u64* other = lds_lists + (size_t)(lane * QB + b) * a.k;  // (lanes 1 .. 3: the other waves' lists of query b)
+        walk_lists<REG>([&](int ptr) { return other[ptr]; }, lane >= 1 && lane < 4, a.k, top[b], thr[b], lane);
+        if (q0 + (uint32_t)b < a.nq) top[b].store(a.out + (size_t)(q0 + b) * a.k * gridDim.x + blockIdx.x, gridDim.x, lane);
+      }
+    }
+  }
+}
+
+typedef void (*subset_fn)(SubsetArgs);
+
+template <int METRIC, int QB, int MODE>
+static subset_fn pick_subset_ni(uint32_t pitch4) {
+  if (pitch4 <= 128) return subset_kernel<METRIC, QB, 2, MODE>;
+  if (pitch4 <= 256) return subset_kernel<METRIC, QB, 4, MODE>;
+  return subset_kernel<METRIC, QB, 0, MODE>;
+}
+
+// mode / qb as subset_query_block (host_subset.h) pairs them: lists in LDS only with the block of one, register lists with
+// 1, 4 or 8, keys with 1 or 8; null for any other pair
+template <int METRIC>
+static subset_fn pick_subset_metric(int mode, int qb, uint32_t pitch4) {
+  if (mode == 0 && qb == 1) return pick_subset_ni<METRIC, 1, 0>(pitch4);
+  if (mode == 1 && qb == 1) return pick_subset_ni<METRIC, 1, 1>(pitch4);
+  if (mode == 1 && qb == 4) return pick_subset_ni<METRIC, 4, 1>(pitch4);
+  if (mode == 1 && qb == 8) return pick_subset_ni<METRIC, 8, 1>(pitch4);
+  if (mode == 2 && qb == 1) return pick_subset_ni<METRIC, 1, 2>(pitch4);
+  if (mode == 2 && qb == 8) return pick_subset_ni<METRIC, 8, 2>(pitch4);
+  return nullptr;
+}
+
+static subset_fn pick_subset(int metric, int mode, int qb, uint32_t pitch4) {
+  return metric == WDBX_METRIC_L2 ? pick_subset_metric<WDBX_METRIC_L2>(mode, qb, pitch4)
+                                  : pick_subset_metric<WDBX_METRIC_COSINE>(mode, qb, pitch4);
+}

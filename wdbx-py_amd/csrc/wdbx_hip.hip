@@ -26,6 +26,8 @@
 //                           row (rounds of single queries on large shards), its quantiser and the cut behind the re-scoring
 //   kernels_range.h         range search: range_scan_kernel (fp32, every row scored exactly), range_filter_kernel (exact
 //                           scores of the u8 selection's candidates); wave-aggregated appends, no k
+//   kernels_subset.h        subset_kernel: exact scores of LISTED rows (wdbx_index_search_rows), a block of queries per fetched
+//                           row, per-workgroup top-k lists or a key per listed row
 //   host_index.h            the handle, kernel choice, and the enqueue functions of every search path
 //   host_group.h            the in-process shard group: per-shard host threads, exchange (RCCL all-gather / device copies), merge
 // The selection paths never decide a result: they keep every row whose score could reach the true k-th best
@@ -63,6 +65,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 // with plain g++ under -fsanitize=thread / address,undefined (tests/test_host_dispatch_sanitizers.py)
 #include "host_dispatch.h"
 #include "host_range.h"  // (device-free as well: CSR offsets, per-query sort and decoding of a range search's keys)
+#include "host_subset.h"  // (device-free as well: row-list validation, route and grid sizing of a search among listed rows)
 
 #define HIP_TRY(expr)                                                                        \
   do {                                                                                       \
@@ -92,6 +95,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "kernels_tiles8.h"
 #include "kernels_aux.h"
 #include "kernels_range.h"
+#include "kernels_subset.h"
 #include "host_index.h"
 #include "host_group.h"
 
@@ -110,6 +114,7 @@ static uint64_t device_bytes_resident(const wdbx_index* ix) {
   b += ix->qb8_bytes + ix->qpar_bytes + ix->pairs_bytes + ix->pair_count_bytes + ix->cnmax_bytes;
   b += ix->rcand_bytes + ix->rkeys_bytes + ix->rcnt_bytes + ix->rthr_bytes;
   b += ix->rows6_bytes + ix->count6_bytes;
+  b += ix->sub_ids_bytes + ix->sub_keys_bytes;
   return b;
 }
 
@@ -187,7 +192,7 @@ void wdbx_index_destroy(wdbx_index* ix) try {
                     ix->d_state, ix->d_cn, ix->d_cnmax, ix->d_qb16, ix->d_rows16, ix->d_rows8, ix->d_scale8, ix->d_selsrc,
                     ix->d_gmax, ix->d_qn, ix->d_rows8g, ix->d_groups8, ix->d_gbad8, ix->d_gref8, ix->d_over_list, ix->d_qb8,
                     ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr, ix->d_rows6, ix->d_count6,
-                    ix->d_call_bad};
+                    ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys};
     for (void* p : bufs)
       if (p) (void)hipFree(p);
     if (ix->h_stage) (void)hipHostFree(ix->h_stage);
@@ -667,6 +672,140 @@ int wdbx_index_search_masked_n(wdbx_index* ix, const float* queries, int nq, int
                                const uint32_t* mask_words, uint64_t mask_word_count, int64_t* out_idx, float* out_score) try {
   if (!mask_words) return fail(WDBX_E_INVALID, "mask_words is null");
   return search_host(ix, queries, nq, k, normalize_queries, mask_words, mask_word_count, out_idx, out_score);
+} WDBX_CATCH
+
+// ---- search among listed rows (kernels_subset.h, host_subset.h) -------------------------------------
+// The whole call holds the handle's mutex (like a masked search: the list buffer is the handle's).  The list is validated
+// and narrowed under the lock (row numbers are checked against the row count a concurrent add cannot change meanwhile), goes
+// to the device once, and the queries are served in rounds (subset_plan): subset_kernel, then per round one merge launch
+// (lists or keys) or per query the radix-select chain.  The scoring launches are bracketed as scan launches.
+static int search_rows_host(wdbx_index* ix, const float* queries, int nq, int k, int normalize_queries, const uint64_t* row_ids,
+                            uint64_t n_ids, int64_t* out_idx, float* out_score) {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  if (nq < 1) return fail(WDBX_E_INVALID, "nq=%d", nq);
+  if (!queries || !out_idx || !out_score) return fail(WDBX_E_INVALID, "null buffer");
+  if (n_ids && !row_ids) return fail(WDBX_E_INVALID, "row_ids is null");
+  if (k < 1 || k > WDBX_MAX_K) return fail(WDBX_E_INVALID, "k=%d outside [1, %d]", k, WDBX_MAX_K);
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (ix->n >= 0xFFFFFF00ull) return fail(WDBX_E_INVALID, "shard holds too many rows for 32-bit row keys");
+  if (n_ids > ix->n) return fail(WDBX_E_INVALID, "%llu listed rows of %llu stored", (u64)n_ids, (u64)ix->n);
+  std::vector<uint32_t> ids32((size_t)n_ids);
+  const uint64_t bad = subset_validate(row_ids, n_ids, ix->n, ids32.data());
+  if (bad != n_ids)
+    return fail(WDBX_E_INVALID, "row_ids must be strictly increasing row numbers below %llu (entry %llu)", (u64)ix->n, (u64)bad);
+  const size_t elems = (size_t)nq * k;
+  const SubsetPlan sp = subset_plan(n_ids, nq, k, ix->cu_count, ix->opt_rows_keys_max, ix->opt_select_min_k, ix->opt_lds_lists != 0);
+  ix->last_rows_path = sp.route;
+  if (sp.route == SUBSET_NONE) {  // nothing listed: every slot empty, as wdbx_index_search leaves them
+    for (size_t i = 0; i < elems; ++i) {
+      out_idx[i] = -1;
+      out_score[i] = 0.0f;
+    }
+    return WDBX_OK;
+  }
+  DeviceGuard g(ix->device);
+  int rc;
+  const size_t q_bytes = (size_t)nq * ix->pitch * sizeof(float);
+  if ((rc = grow((void**)&ix->d_q, &ix->q_bytes, q_bytes))) return rc;
+  if (elems > ix->out_elems) {
+    if (ix->d_oidx) HIP_TRY(hipFree(ix->d_oidx));
+    if (ix->d_oscore) HIP_TRY(hipFree(ix->d_oscore));
+    ix->d_oidx = nullptr;
+    ix->d_oscore = nullptr;
+    ix->out_elems = 0;
+    HIP_TRY(hipMalloc((void**)&ix->d_oidx, elems * sizeof(int64_t)));
+    HIP_TRY(hipMalloc((void**)&ix->d_oscore, elems * sizeof(float)));
+    ix->out_elems = elems;
+  }
+  if ((rc = grow((void**)&ix->d_sub_ids, &ix->sub_ids_bytes, (size_t)n_ids * sizeof(uint32_t)))) return rc;
+  const bool lists = sp.route == SUBSET_LISTS;
+  if (lists) {
+    if ((rc = grow((void**)&ix->d_partials, &ix->partials_bytes, sp.scratch_u64 * sizeof(u64)))) return rc;
+  } else {
+    if ((rc = grow((void**)&ix->d_sub_keys, &ix->sub_keys_bytes, sp.scratch_u64 * sizeof(u64)))) return rc;
+  }
+  if (sp.route == SUBSET_SELECT) {
+    if ((rc = grow((void**)&ix->d_sel, &ix->sel_bytes, (size_t)WDBX_MAX_K * sizeof(u64)))) return rc;
+    if ((rc = grow((void**)&ix->d_state, &ix->state_bytes, sizeof(SelectState)))) return rc;
+  }
+  if (ix->pitch == ix->dim) {
+    HIP_TRY(hipMemcpyAsync(ix->d_q, queries, q_bytes, hipMemcpyHostToDevice, ix->stream));
+  } else {
+    HIP_TRY(hipMemsetAsync(ix->d_q, 0, q_bytes, ix->stream));
+    HIP_TRY(hipMemcpy2DAsync(ix->d_q, (size_t)ix->pitch * sizeof(float), queries, (size_t)ix->dim * sizeof(float),
+                             (size_t)ix->dim * sizeof(float), nq, hipMemcpyHostToDevice, ix->stream));
+  }
+  HIP_TRY(hipMemcpyAsync(ix->d_sub_ids, ids32.data(), (size_t)n_ids * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+  if (normalize_queries && ix->metric == WDBX_METRIC_COSINE && (rc = launch_normalize(ix, ix->d_q, (uint64_t)nq))) return rc;
+
+  const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
+  const bool reg = k <= 128 && !ix->opt_lds_lists;
+  const int mode = lists ? (reg ? 1 : 0) : 2;
+  const subset_fn fn = pick_subset(ix->metric, mode, sp.qb, pitch4);
+  if (!fn) return fail(WDBX_E_STATE, "no listed-rows instance for mode %d with %d queries per block", mode, sp.qb);
+  const size_t lds = lists ? sp.lds : 0;
+  if (lds >= 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  for (int q0 = 0; q0 < nq; q0 += sp.round) {
+    const int b = std::min(sp.round, nq - q0);
+    SubsetArgs a = {};
+    a.rows = (const f4*)ix->d_rows;
+    a.queries = (const f4*)(ix->d_q + (size_t)q0 * ix->pitch);
+    a.ids = ix->d_sub_ids;
+    a.out = lists ? ix->d_partials : ix->d_sub_keys;
+    a.key_stride = n_ids;
+    a.n_ids = (uint32_t)n_ids;
+    a.pitch4 = pitch4;
+    a.nq = (uint32_t)b;
+    a.k = k;
+    const uint32_t qblocks = (uint32_t)((b + sp.qb - 1) / sp.qb);
+    if ((rc = record(ix->scan_ev, ix->profile, ix->stream, true))) return rc;
+    hipLaunchKernelGGL(fn, dim3(sp.blocks, qblocks), dim3(256), lds, ix->stream, a);
+    HIP_TRY(hipGetLastError());
+    if ((rc = record(ix->scan_ev, ix->profile, ix->stream, false))) return rc;
+    MergeArgs m = {};
+    m.k = k;
+    m.metric = ix->metric;
+    if (sp.route == SUBSET_SELECT) {
+      const uint32_t sgrid = radix_select_grid(n_ids, ix->cu_count);
+      for (int q = 0; q < b; ++q) {
+        if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
+        HIP_TRY(enqueue_radix_select(ix->stream, (const u64*)ix->d_sub_keys + (size_t)q * n_ids, (u64)n_ids, nullptr,
+                                     (SelectState*)ix->d_state, (u64*)ix->d_sel, (uint32_t)k, sgrid));
+        m.out_idx = ix->d_oidx + (size_t)(q0 + q) * k;
+        m.out_score = ix->d_oscore + (size_t)(q0 + q) * k;
+        HIP_TRY(enqueue_sort_out(ix->stream, (const u64*)ix->d_sel, (const SelectState*)ix->d_state, m));
+        if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
+      }
+      continue;
+    }
+    if (lists) {
+      m.in = ix->d_partials;
+      m.q_stride = (uint64_t)k * sp.P;
+      m.i_stride = sp.P;
+      m.p_stride = 1;
+      m.P = sp.P;
+      m.list_len = k;
+    } else {
+      m.in = ix->d_sub_keys;
+      m.q_stride = n_ids;
+      m.i_stride = 0;
+      m.p_stride = 1;
+      m.P = (uint32_t)n_ids;
+      m.list_len = 1;
+    }
+    m.out_idx = ix->d_oidx + (size_t)q0 * k;
+    m.out_score = ix->d_oscore + (size_t)q0 * k;
+    if ((rc = launch_merge(ix, m, b))) return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(out_idx, ix->d_oidx, elems * sizeof(int64_t), hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipMemcpyAsync(out_score, ix->d_oscore, elems * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  return WDBX_OK;
+}
+
+int wdbx_index_search_rows(wdbx_index* ix, const float* queries, int nq, int k, int normalize_queries, const uint64_t* row_ids,
+                           uint64_t n_ids, int64_t* out_idx, float* out_score) try {
+  return search_rows_host(ix, queries, nq, k, normalize_queries, row_ids, n_ids, out_idx, out_score);
 } WDBX_CATCH
 
 // ---- range search (range_u8_eligible, pick_range_scan: host_index.h) -------------------------------
@@ -1538,6 +1677,7 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"gemm_min_work", &wdbx_index::opt_gemm_min_work},
     {"gemm_sample_div", &wdbx_index::opt_gemm_sample_div},
     {"gemm_masked", &wdbx_index::opt_gemm_masked},
+    {"rows_keys_max", &wdbx_index::opt_rows_keys_max},
 };
 
 static int64_t* option_slot(wdbx_index* ix, const char* name) { return find_option(ix, kOptions, name); }
@@ -1581,6 +1721,7 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "shadow6_rows")) return *value = (int64_t)ix->shadow6_rows, WDBX_OK;
   if (name && !strcmp(name, "shadow6_bytes")) return *value = (int64_t)ix->rows6_bytes, WDBX_OK;
   if (name && !strcmp(name, "last_range_path")) return *value = ix->last_range_path, WDBX_OK;
+  if (name && !strcmp(name, "last_rows_path")) return *value = ix->last_rows_path, WDBX_OK;
   if (name && !strcmp(name, "last_sample_qn")) return *value = ix->last_sample_qn, WDBX_OK;
   if (name && !strcmp(name, "last_batch_repaired")) return *value = ix->last_batch_repaired ? 1 : 0, WDBX_OK;
   if (name && !strcmp(name, "last_batch_masked")) return *value = ix->last_batch_masked ? 1 : 0, WDBX_OK;

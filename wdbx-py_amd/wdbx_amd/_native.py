@@ -61,6 +61,7 @@ SIGNATURES = {
                                            _f32p]),
     "wdbx_index_search_masked_n": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
                                              _i64p, _f32p]),
+    "wdbx_index_search_rows": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _u64p, C.c_uint64, _i64p, _f32p]),
     "wdbx_index_range_search": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
                                           C.c_uint64, _u64p, _i64p, _f32p]),
     "wdbx_device_alloc": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -307,6 +308,19 @@ class NativeIndex:
             _check(self._lib.wdbx_index_search_masked_n(self._h, q.ctypes.data_as(_f32p), nq, int(k),
                                                         int(normalize_queries), m.ctypes.data_as(C.POINTER(C.c_uint32)), m.size,
                                                         idx.ctypes.data_as(_i64p), score.ctypes.data_as(_f32p)))
+        return idx, score
+
+    def search_rows(self, queries, k: int, row_ids, normalize_queries: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """The exact top-``k`` of the listed rows only (``row_ids``: strictly increasing row numbers of this index), in the
+        format and order of :meth:`search`; the cost follows the list, not the index.  An empty list gives rows of -1."""
+        q = _as_f32(queries, self.dim)
+        nq = q.shape[0]
+        ids = np.ascontiguousarray(row_ids, dtype=np.uint64).reshape(-1)
+        idx = np.empty((nq, int(k)), np.int64)
+        score = np.empty((nq, int(k)), np.float32)
+        _check(self._lib.wdbx_index_search_rows(self._h, q.ctypes.data_as(_f32p), nq, int(k), int(normalize_queries),
+                                                ids.ctypes.data_as(_u64p), ids.size, idx.ctypes.data_as(_i64p),
+                                                score.ctypes.data_as(_f32p)))
         return idx, score
 
     def range_search(self, queries, thresholds, normalize_queries: bool = False,

@@ -76,6 +76,9 @@ class WDBXConfig:
         "HIP_PERSIST_INDEX": True,
         "HIP_COMPACT_MIN_FRACTION": 0.0,
         "FILTER_PUSHDOWN": False,
+        # a pushed-down filter that matches at most this many rows of a shard is answered from those rows alone (the search
+        # among listed rows) instead of a masked pass over the shard; 0 = off
+        "FILTER_GATHER_MAX_ROWS": 0,
         "ASYNC_COALESCE": True,
     }
 

@@ -118,6 +118,17 @@ def normalize_vector(vector: np.ndarray) -> np.ndarray:
 _METRICS = {"cosine": _native.METRIC_COSINE, "ip": _native.METRIC_COSINE, "l2": _native.METRIC_L2}
 
 
+class RowList:
+    """A pushed-down filter in the form of the rows it allows (strictly increasing uint64 row numbers of ONE shard) instead of
+    a row mask: where ``search`` / ``search_batch`` take a ``row_mask`` they take this too and answer through the library's
+    search among listed rows, whose cost follows the list."""
+
+    __slots__ = ("rows",)
+
+    def __init__(self, rows: np.ndarray):
+        self.rows = np.ascontiguousarray(rows, dtype=np.uint64)
+
+
 class HipFlatIndex(VectorIndex):
     """Exact flat index resident in one MI355X's HBM (one shard)."""
 
@@ -179,6 +190,7 @@ class HipFlatIndex(VectorIndex):
         self._unsaved_adds = 0
         self._rows_gen = 0        # generation of the committed row file (see _rows_path)
         self._rewrite = False     # the next save must write a whole new generation (rows moved or dropped under the mapping)
+        self.rows_searches = 0    # calls answered by a search among listed rows (search_rows_raw)
         self._load_index()
 
     # ---- persistence: flat [n, d] fp32 rows + id table ----
@@ -582,6 +594,9 @@ class HipFlatIndex(VectorIndex):
             if actual_limit <= 0:
                 return []
             q = self._prepare(query_vector)
+            if isinstance(row_mask, RowList):  # the filter's rows instead of its mask: only they are read
+                raw = self.search_rows_raw(q[None, :], actual_limit, row_mask.rows)
+                return [] if raw is None else self._map(raw[0][0], raw[1][0])
             words = None
             if row_mask is not None:
                 words = row_mask if row_mask.dtype == np.uint32 else _native.pack_row_mask(row_mask)
@@ -649,6 +664,8 @@ class HipFlatIndex(VectorIndex):
         actual_limit = min(int(limit), self.next_index, _native.MAX_K)
         if actual_limit <= 0:
             return None
+        if isinstance(row_mask, RowList):
+            return self.search_rows_raw(queries, actual_limit, row_mask.rows)
         try:
             q = np.stack([self._prepare(r) for r in queries])
             if row_mask is None:
@@ -660,6 +677,53 @@ class HipFlatIndex(VectorIndex):
             if self.swallow_errors:
                 return None
             raise
+
+    # ---- search among listed ids (extension: the exact top-k of an explicit list; the cost follows the list) ----
+    def rows_of(self, ids) -> np.ndarray:
+        """Row numbers of the given ids, sorted and de-duplicated (what ``search_rows`` takes); unknown and removed ids are
+        dropped silently."""
+        row_of = self._row_of
+        rows = {r for r in (row_of(i) for i in ids) if r is not None}
+        return np.fromiter(sorted(rows), dtype=np.uint64, count=len(rows))
+
+    def search_rows_raw(self, queries: np.ndarray, limit: int, rows: np.ndarray):
+        """``search_batch_raw`` over the listed rows only (``rows``: strictly increasing row numbers, as ``rows_of`` returns
+        them): (rows int64[nq, k], scores f32[nq, k]) or None for "no results"."""
+        queries = np.asarray(queries, dtype=np.float32)
+        if queries.ndim != 2 or queries.shape[1] != self.vector_dim:
+            raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {queries.shape}")
+        actual_limit = min(int(limit), _native.MAX_K)
+        if self.next_index == 0 or queries.shape[0] == 0 or len(rows) == 0 or actual_limit <= 0:
+            return None
+        try:
+            q = np.stack([self._prepare(r) for r in queries])
+            out = self._native.search_rows(q, actual_limit, rows)
+            self.rows_searches += 1
+            return out
+        except Exception as e:
+            logger.error("Error searching listed rows of HIP index: %s", e)
+            if self.swallow_errors:
+                return None
+            raise
+
+    def search_among(self, query_vector: np.ndarray, ids, limit: int = 10) -> List[Tuple[str, float]]:
+        """Exact top-``limit`` among the vectors named by ``ids`` (any order, duplicates allowed; unknown and removed ids are
+        ignored), best first, scores as ``search`` returns them.  Errors are swallowed or raised as in ``search``."""
+        return self.search_batch_among(np.asarray(query_vector, dtype=np.float32)[None, :], ids, limit)[0]
+
+    def search_batch_among(self, queries: np.ndarray, ids, limit: int = 10) -> List[List[Tuple[str, float]]]:
+        """``search_among`` for many queries over ONE list: every listed row is fetched once per block of queries."""
+        try:
+            rows = self.rows_of(ids)
+        except Exception as e:
+            logger.error("Error mapping ids of HIP index: %s", e)
+            if self.swallow_errors:
+                return [[] for _ in range(len(queries))]
+            raise
+        raw = self.search_rows_raw(queries, limit, rows)
+        if raw is None:
+            return [[] for _ in range(len(queries))]
+        return [self._map(i, s) for i, s in zip(*raw)]
 
     async def search_async(self, query_vector: np.ndarray, limit: int = 10) -> List[Tuple[str, float]]:
         loop = asyncio.get_event_loop()

@@ -35,7 +35,7 @@ import numpy as np
 
 from . import _native
 from .config import WDBXConfig
-from .indexing import HipFlatIndex
+from .indexing import HipFlatIndex, RowList
 
 logger = logging.getLogger(__name__)
 
@@ -551,8 +551,9 @@ class VectorStore:
         """Per-shard candidate lists of one query, in shard order (or ONE already merged list from the shard group:
         the stable sort of ``_merge`` leaves it as it is)."""
         # (a pushed-down filter travels with the call: every shard applies its own row mask inside its scan)
-        merged = self._group_search(query[None, :], limit, keep_all=post_filtered,
-                                    masks=None if all(m is None for m in masks) else masks)
+        # (a shard that answers from a row list is not a group call: the group knows masks only)
+        merged = None if self._has_lists(masks) else self._group_search(
+            query[None, :], limit, keep_all=post_filtered, masks=None if all(m is None for m in masks) else masks)
         if merged is not None and self._group_path == "rccl_group" and not self._group_verified:
             merged = self._verify_group_once(query, limit, masks, post_filtered, merged)
         if merged is not None:
@@ -591,10 +592,33 @@ class VectorStore:
                                              zip(self.indices, masks)))
         return [ix.search(query, limit=limit, row_mask=m) for ix, m in zip(self.indices, masks)]
 
-    def _masks_for(self, filter_metadata, prefilter: Optional[bool]):
+    def _masks_for(self, filter_metadata, prefilter: Optional[bool], gather: bool = False):
+        """Per shard what a pushed-down filter travels as: None (no push-down), the row mask, or -- ``gather`` (the top-k
+        searches) with config ``FILTER_GATHER_MAX_ROWS`` > 0 -- a ``RowList`` for a shard in which the filter matches at
+        most that many rows: that shard answers through the search among listed rows, at the cost of those rows."""
         if prefilter is None:
             prefilter = bool(self.config.get("FILTER_PUSHDOWN", False))
-        return self._row_masks(filter_metadata) if (prefilter and filter_metadata) else [None] * len(self.indices)
+        if not (prefilter and filter_metadata):
+            return [None] * len(self.indices)
+        masks = self._row_masks(filter_metadata)
+        gmax = int(self.config.get("FILTER_GATHER_MAX_ROWS", 0) or 0) if gather else 0
+        if gmax <= 0:
+            return masks
+        # (cached next to the masks, under the same version: _row_masks has just cleared the cache if the store changed)
+        key = ("rows", self._mask_key(filter_metadata), gmax)
+        cache = self._mask_cache
+        if key not in cache:
+            out = []
+            for ix, words in zip(self.indices, masks):
+                bits = np.unpackbits(np.ascontiguousarray(words, dtype="<u4").view(np.uint8), bitorder="little")
+                rows = np.flatnonzero(bits[: ix.next_index])
+                out.append(RowList(rows.astype(np.uint64)) if rows.size <= gmax else words)
+            cache[key] = out
+        return cache[key]
+
+    @staticmethod
+    def _has_lists(masks) -> bool:
+        return masks is not None and any(isinstance(m, RowList) for m in masks)
 
     @staticmethod
     def _mask_key(filter_metadata) -> str:
@@ -607,7 +631,7 @@ class VectorStore:
         scan, so a filtered query returns a full ``limit`` whenever enough rows match; the default keeps
         the reference's post-filter (vector_store.py:337-342), which can under-return."""
         query = _as_query(query_vector)
-        masks = self._masks_for(filter_metadata, prefilter)
+        masks = self._masks_for(filter_metadata, prefilter, gather=True)
         if self._sync_coalesce and all(m is None for m in masks) and query.shape == (self.vector_dim,):
             return self._search_coalesced(query, int(limit), threshold, filter_metadata)
         shard_results = self._fan_out(query, limit, masks, post_filtered=bool(filter_metadata))
@@ -728,7 +752,7 @@ class VectorStore:
         if query.shape != (self.vector_dim,):
             raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {query.shape}")
         loop = asyncio.get_running_loop()
-        masks = self._masks_for(filter_metadata, prefilter)
+        masks = self._masks_for(filter_metadata, prefilter, gather=True)
         pushed = any(m is not None for m in masks)
         if not self.config.get("ASYNC_COALESCE", True):
             shard_results = await loop.run_in_executor(self.thread_pool, self._fan_out, query, limit, masks,
@@ -759,7 +783,7 @@ class VectorStore:
     async def _drain_batch(self, loop, batch, pushed_filter, nomask) -> None:
         """One coalesced batch of ``search_async`` callers; ``pushed_filter``: the filter they all push down, or None."""
         try:
-            masks = None if pushed_filter is None else self._row_masks(pushed_filter)
+            masks = None if pushed_filter is None else self._masks_for(pushed_filter, True, gather=True)
             if len(batch) == 1:
                 query, limit, threshold, flt, fut = batch[0]
                 res = await loop.run_in_executor(self.thread_pool, self._fan_out, query, limit, masks or nomask, bool(flt))
@@ -768,7 +792,7 @@ class VectorStore:
                 return
             kmax = max(b[1] for b in batch)
             queries = np.stack([b[0] for b in batch])
-            if all(b[1] == kmax for b in batch) and self._shard_group() is not None:
+            if all(b[1] == kmax for b in batch) and not self._has_lists(masks) and self._shard_group() is not None:
                 # same limit everywhere: ONE group call answers the whole batch (a caller with a filter needs the
                 # union of the shards' lists, as in ``search``)
                 keep_all = any(bool(b[3]) for b in batch)
@@ -805,9 +829,9 @@ class VectorStore:
         queries = np.asarray(queries, dtype=np.float32)
         if queries.ndim != 2 or queries.shape[1] != self.vector_dim:
             raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {queries.shape}")
-        masks = self._masks_for(filter_metadata, prefilter)
+        masks = self._masks_for(filter_metadata, prefilter, gather=True)
         pushed = any(m is not None for m in masks)
-        if queries.shape[0]:
+        if queries.shape[0] and not self._has_lists(masks):
             merged = self._group_search(queries, limit, keep_all=bool(filter_metadata), masks=masks if pushed else None)
             if merged is not None:
                 self.last_search_path = self._group_path
@@ -824,6 +848,46 @@ class VectorStore:
             per_shard = [ix.search_batch(queries, limit=limit) for ix in self.indices]
         return [self._merge([res[q] for res in per_shard], limit, threshold, filter_metadata)
                 for q in range(queries.shape[0])]
+
+    # ---- search among listed ids (extension: the exact top-k of an explicit list of vectors) ----
+    def _ids_by_shard(self, vector_ids) -> List[List[str]]:
+        per: List[List[str]] = [[] for _ in self.indices]
+        for vid in vector_ids:
+            per[self._get_shard_for_id(vid)].append(vid)
+        return per
+
+    def search_batch_among(self, queries, vector_ids, limit: int = 10, threshold: float = 0.0) -> List[List[Result]]:
+        """Per query the best ``limit`` among the vectors named by ``vector_ids`` only -- "rank these candidates", or a filter
+        evaluated elsewhere -- with the merge semantics of ``search`` (threshold, cut, metadata attached).  Ids may come in
+        any order and repeat; unknown and deleted ids are ignored; an empty list gives empty results.  The ids are split by
+        shard and every shard holding some scores ITS listed rows exactly (the library's search among listed rows: the cost
+        follows the list, not the shard), on the shard pool; no shard group, no coalescing."""
+        queries = np.asarray(queries, dtype=np.float32)
+        if queries.ndim != 2 or queries.shape[1] != self.vector_dim:
+            raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {queries.shape}")
+        self.last_search_path = "threads"
+        if queries.shape[0] == 0:
+            return []
+        work = [(ix, ids) for ix, ids in zip(self.indices, self._ids_by_shard(vector_ids)) if ids]
+        if not work:
+            return [[] for _ in range(queries.shape[0])]
+
+        def one(a):
+            return a[0].search_batch_among(queries, a[1], limit=limit)
+        per_shard = list(self._shard_pool.map(one, work)) if len(work) > 1 else [one(work[0])]
+        return [self._merge([res[q] for res in per_shard], limit, threshold, None) for q in range(queries.shape[0])]
+
+    def search_among(self, query_vector: List[float], vector_ids, limit: int = 10, threshold: float = 0.0) -> List[Result]:
+        query = _as_query(query_vector)
+        if query.shape != (self.vector_dim,):
+            raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {query.shape}")
+        return self.search_batch_among(query[None, :], vector_ids, limit=limit, threshold=threshold)[0]
+
+    async def search_among_async(self, query_vector: List[float], vector_ids, limit: int = 10,
+                                 threshold: float = 0.0) -> List[Result]:
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(self.thread_pool, lambda: self.search_among(
+            query_vector, vector_ids, limit=limit, threshold=threshold))
 
     # ---- range search (extension: every vector within a similarity, no limit) ----
     def search_range(self, query_vector: List[float], threshold: float,

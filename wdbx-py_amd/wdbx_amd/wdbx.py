@@ -124,6 +124,24 @@ class WDBX:
         return self.vector_store.search_batch(query_vectors, limit=limit, threshold=threshold,
                                               filter_metadata=filter_metadata, prefilter=prefilter)
 
+    def vector_search_among(self, query_vector: List[float], vector_ids, limit: int = 10,
+                            threshold: float = 0.0) -> List[Result]:
+        """Extension: the best ``limit`` among the vectors named by ``vector_ids`` only (re-ranking a candidate list, a filter
+        evaluated elsewhere); unknown and deleted ids are ignored.  Costs what the listed vectors cost, not the store."""
+        self._check_dim(query_vector)
+        return self.vector_store.search_among(query_vector, vector_ids, limit=limit, threshold=threshold)
+
+    def vector_search_batch_among(self, query_vectors, vector_ids, limit: int = 10,
+                                  threshold: float = 0.0) -> List[List[Result]]:
+        for q in query_vectors:
+            self._check_dim(q)
+        return self.vector_store.search_batch_among(query_vectors, vector_ids, limit=limit, threshold=threshold)
+
+    async def vector_search_among_async(self, query_vector: List[float], vector_ids, limit: int = 10,
+                                        threshold: float = 0.0) -> List[Result]:
+        self._check_dim(query_vector)
+        return await self.vector_store.search_among_async(query_vector, vector_ids, limit=limit, threshold=threshold)
+
     def vector_search_range(self, query_vector: List[float], threshold: float,
                             filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,
                             max_results: Optional[int] = None) -> List[Result]:
