@@ -128,6 +128,34 @@ int wdbx_index_search_masked(wdbx_index* idx, const float* queries, int nq, int 
 int wdbx_index_search_masked_n(wdbx_index* idx, const float* queries, int nq, int k, int normalize_queries,
                                const uint32_t* mask_words, uint64_t mask_word_count, int64_t* out_idx, float* out_score);
 
+/* ---- one row mask PER QUERY in one batched call ------------------------------- */
+/* The workload row masks exist for is one filter per tenant, user or language: a batch whose queries do not share a mask.
+ * mask_words[0 .. n_masks) are masks in the format of wdbx_index_search_masked_n (mask_word_counts[m] words each, checked
+ * against the row count under the handle's lock), query_mask[i] says which of them query i reads, -1 = every row.  Blocking,
+ * host buffers.
+ *   Results: in the CALLER'S query order; format, order, -1 slots and NaN handling as wdbx_index_search_masked_n.  Query i's
+ *   answer is the exact fp32 top-k of the rows its mask allows, bit-identical to wdbx_index_search_masked_n called with that
+ *   query alone and its mask (wdbx_index_search for a -1 query) -- except for queries whose candidate buffer overflowed: they
+ *   are repaired by the fp32 scan with THEIR mask and carry its scores (same ids, scores up to 1 ulp apart), as repaired
+ *   queries of every batch do.
+ *   WDBX_E_INVALID: n_masks outside [0, WDBX_MAX_CALL_MASKS], a query_mask entry outside [-1, n_masks), a mask shorter than
+ *   ceil(rows / 32) words, a null mask pointer, k outside [1, WDBX_MAX_K], nq < 1.  n_masks == 0 with every entry -1 is the
+ *   unmasked batch.
+ *   Route: when the int8 tiles are what a masked batch would run (gemm_bf16 = 3, gemm8_variant = 0, k below the select range,
+ *   option gemm_masked, enough queries and rows for the batched path) the call is ONE tile pass per block of up to 256 placed
+ *   queries (128 for L2 and rows beyond 384 bytes of i8), whatever the number of masks: the queries are sorted by mask, each
+ *   mask's queries padded to whole column groups of 16, and the kernels read the mask word of the column group at hand
+ *   (get_option "last_batch_masked" == 2, "last_batch_mask_classes" = distinct masks the call used, the maskless class
+ *   included, "last_batch_blocks" = tile blocks it ran; wdbx_index_batch_status reports its counts in the caller's query
+ *   order).  Otherwise every distinct mask's queries go through wdbx_index_search_masked_n (wdbx_index_search for -1) and
+ *   the answers are scattered back.  Exact either way.
+ *   The call holds the handle's mutex to its end.  Nothing of a call's masks stays valid in the handle. */
+#define WDBX_MAX_CALL_MASKS 64
+int wdbx_index_search_multimask(wdbx_index* idx, const float* queries, int nq, int k, int normalize_queries,
+                                const uint32_t* const* mask_words, const uint64_t* mask_word_counts, int n_masks,
+                                const int32_t* query_mask, /* [nq]: index into mask_words, or -1 = every row */
+                                int64_t* out_idx, float* out_score);
+
 /* ---- search among listed rows: the exact top-k of an explicit row list -------- */
 /* The exact fp32 top-k of the rows row_ids[0 .. n_ids) (host memory, the index's own row numbers) for each of nq host
  * queries [nq, dim]: what a selective `filter=` (vector_store.py:337-342 post-filters a top-k instead) or "rank these

@@ -57,7 +57,13 @@ struct wdbx_index {
   // the int8 tiles' bad-row table of ONE masked batch: d_gbad8 | ~mask (gbad_with_mask_kernel); d_gbad8 itself never changes
   u64* d_call_bad = nullptr;
   size_t call_bad_bytes = 0;
-  bool last_batch_masked = false;         // the last batch ran the masked tile pass
+  int last_batch_masked = 0;              // the last batch ran the masked tile pass (1), or the pass with a mask per query (2)
+  // a call with one row mask per query (wdbx_index_search_multimask): its queries in slot order, the slots' queries, its masks
+  // and the classes' mask numbers in one scratch allocation; what the last such tile call looked like
+  char* d_mm = nullptr;
+  size_t mm_bytes = 0;
+  uint32_t last_batch_classes = 0, last_batch_blocks = 0;
+  std::vector<int32_t> last_batch_slot;   // ... and the slot of each of the caller's queries (wdbx_index_batch_status)
   uint64_t last_batch_allowed = 0;        // ... over this many allowed rows
   // batched (GEMM) path scratch
   float* d_qblock = nullptr;
@@ -511,8 +517,9 @@ enum { SEARCH_FINAL = 0, SEARCH_SHARDED = 1, SEARCH_LOCAL_KEYS = 2 };
 
 static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, int k, int64_t* d_out_idx, float* d_out_score,
                                int mode, int count_slot, u64* keys_out);
+struct MultiCall;
 static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, int k, int64_t* d_out_idx, float* d_out_score, int mode,
-                                u64* keys_out);
+                                u64* keys_out, const MultiCall* mc = nullptr);
 static bool shadow_single_eligible(const wdbx_index* ix, int k, int nq_call);
 static bool u8_single_eligible(const wdbx_index* ix, int k, int nq_call);
 static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, int k, int64_t* d_out_idx, float* d_out_score,
@@ -1722,11 +1729,14 @@ static void (*gemm8_instance(uint32_t pitch8, int ring))(Gemm8Args) {
 // runs that form and nothing else.  Option gemm8_variant (tools/probes/c4_i8_ab.py), for A/B: 13 = the round-2 form (exact
 // epilogue) everywhere, 12 = the prefilter with a branch per column group for 256-query blocks of 384-byte rows, 0 / 14 = the default.
 template <int PHASE, int CT8>
-static void (*pick_gemm8(uint32_t pitch8, int ring, bool l2, bool masked, int variant))(Gemm8Args) {
+static void (*pick_gemm8(uint32_t pitch8, int ring, bool l2, bool masked, int variant, bool multi))(Gemm8Args) {
   constexpr int C = WDBX_METRIC_COSINE, L = WDBX_METRIC_L2;
   if constexpr (PHASE == 0) {
+    if (multi) return l2 ? gemm8_instance<0, CT8, EPI8_MULTI_EXACT, L, false>(pitch8, ring) : gemm8_instance<0, CT8, EPI8_MULTI_EXACT, C, false>(pitch8, ring);
     return l2 ? gemm8_instance<0, CT8, EPI8_EXACT, L, false>(pitch8, ring) : gemm8_instance<0, CT8, EPI8_EXACT, C, false>(pitch8, ring);
   } else {
+    // (a mask per query: the same product forms, the mask word read per column group)
+    if (multi) return l2 ? gemm8_instance<1, CT8, EPI8_MULTI_EXACT, L, false>(pitch8, ring) : gemm8_instance<1, CT8, EPI8_MULTI_PRE_BLOCK, C, false>(pitch8, ring);
     if (l2) return masked ? gemm8_instance<1, CT8, EPI8_EXACT, L, true>(pitch8, ring) : gemm8_instance<1, CT8, EPI8_EXACT, L, false>(pitch8, ring);
     if (masked) return gemm8_instance<1, CT8, EPI8_PRE_BLOCK, C, true>(pitch8, ring);
     if (variant == 13) return gemm8_instance<1, CT8, EPI8_EXACT, C, false>(pitch8, ring);
@@ -1737,16 +1747,16 @@ static void (*pick_gemm8(uint32_t pitch8, int ring, bool l2, bool masked, int va
 }
 
 template <int PHASE>
-static int launch_gemm8(wdbx_index* ix, const Gemm8Args& g, int ct, bool masked = false) {
+static int launch_gemm8(wdbx_index* ix, const Gemm8Args& g, int ct, bool masked = false, bool multi = false) {
   // k-steps (64 bytes of a row: two A fragments) in flight per wave: a divisor of the row's k-steps (pitch8 is a multiple of
   // 128).  256-query blocks leave room for 2 or 3 (128 accumulator + 32 query-fragment registers), narrower blocks for 6.
   const uint32_t steps = g.pitch8 / 64;
   const int ring = ct == 4 ? 2 : (steps % 6 == 0 ? 6 : steps % 4 == 0 ? 4 : 2);
   const int var = (int)ix->opt_gemm8_variant;
   const bool l2 = ix->metric == WDBX_METRIC_L2;
-  void (*fn)(Gemm8Args) = ct == 4   ? pick_gemm8<PHASE, 8>(g.pitch8, ring, l2, masked, var)
-                          : ct == 2 ? pick_gemm8<PHASE, 4>(g.pitch8, ring, l2, masked, var)
-                                    : pick_gemm8<PHASE, 2>(g.pitch8, ring, l2, masked, var);
+  void (*fn)(Gemm8Args) = ct == 4   ? pick_gemm8<PHASE, 8>(g.pitch8, ring, l2, masked, var, multi)
+                          : ct == 2 ? pick_gemm8<PHASE, 4>(g.pitch8, ring, l2, masked, var, multi)
+                                    : pick_gemm8<PHASE, 2>(g.pitch8, ring, l2, masked, var, multi);
   if (!fn) return fail(WDBX_E_STATE, "no int8 tile instance for this query block");
   const size_t lds = (size_t)64 * ct * g.pitch8 + (size_t)64 * ct * sizeof(f4);  // the query block + its parameters
   HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1761,43 +1771,86 @@ static int launch_gemm8(wdbx_index* ix, const Gemm8Args& g, int ct, bool masked 
 // nq (any number) queries in blocks of up to 256 through the int8 tiles.  Same contract as enqueue_search_gemm: per-query
 // candidate counters in d_count[q] (a count above the capacity = that query must be re-run on the scan path), results are
 // the exact fp32 ranking of the kept rows (rescore_kernel + merge_kernel).
+// mc != null: a call with one row mask PER QUERY (wdbx_index_search_multimask).  d_queries are then the
+// call's SLOTS (host_multimask.h: every column group of 16 slots holds queries of one class; pad slots are zero rows), nq
+// their number, the blocks are the plan's, and results and candidate counters come back in slot order.
+struct MultiCall {
+  const MultimaskPlan* plan;
+  const int32_t* d_slot_query;  // the plan's slot_query on the device
+  const uint32_t* d_masks;      // the masks of the call's classes: class row r at d_masks + r * mask_stride (a row without a mask: unused)
+  size_t mask_stride;           // words
+  const int32_t* d_class_mask;  // per class row: r, or -1 for the class without a mask
+  const uint64_t* allowed;      // per class row: how many rows the class allows
+};
 static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, int k, int64_t* d_out_idx, float* d_out_score,
-                                int mode, u64* keys_out) {
+                                int mode, u64* keys_out, const MultiCall* mc) {
   const bool sharded = mode == SEARCH_SHARDED;
   int rc;
   ix->last_gemm_mode = GEMM_I8;
-  const bool masked = ix->active_mask != nullptr;
+  const bool masked = ix->active_mask != nullptr, multi = mc != nullptr;
+  if (multi && (masked || sharded || keys_out)) return fail(WDBX_E_STATE, "a mask per query: the plain blocking call only");
   const uint32_t pitch8 = ix->pitch8g;
   const uint32_t tiles = (uint32_t)((ix->n + G8_ROWS - 1) / G8_ROWS), rw = G8_ROWS / 32;  // a lower bound per 32-row block
   const uint32_t div = ix->opt_gemm_sample_div > 0 ? (uint32_t)ix->opt_gemm_sample_div : std::min(32u, std::max(4u, 1024u / (uint32_t)k));
-  uint32_t sample_tiles = std::max<uint32_t>(tiles / div, (8u * k + rw - 1) / rw);
-  // (a mask of at most 16 384 rows: the candidate buffers hold ALL of them, see below, so tau = -inf is answered from the
-  // candidates and a larger sample would buy nothing: the sample stays what an unmasked call takes)
-  if (masked && ix->mask_allowed > 16384) {
-    // A row mask that allows a fraction f of the rows: only blocks holding an allowed row vouch, and each for the best of its
-    // ~32 f allowed rows.  tau is then the k-th best of ~(sampled rows) x f rows and the full pass keeps ~k x rows / (sampled
-    // rows) of the allowed ones: the candidates per query do not grow with 1 / f, but the VOUCHING blocks shrink -- a fraction
-    // 1 - (1 - f)^32 of the sampled ones.  So the sample grows by 1 / f, up to 8 x (a quarter of the corpus at the default
-    // 1 / 32: beyond that the sample pass would cost what the full pass does), and further only while fewer than 8 k sampled
-    // blocks are expected to vouch; clamped to all tiles.  Fewer than k vouching blocks leave tau = -inf: every allowed row is a
-    // candidate, what does not fit is repaired by the masked fp32 scan.  
-    const double f = ix->n ? (double)ix->mask_allowed / (double)ix->n : 0.0;
-    if (f > 0.0) {
-      const double pv = 1.0 - std::pow(1.0 - std::min(f, 1.0), 32.0);
-      const double scaled = (double)sample_tiles * std::min(1.0 / f, 8.0), vouch = (8.0 * k) / (rw * std::max(pv, 1e-9));
-      sample_tiles = (uint32_t)std::min<double>(std::ceil(std::max(scaled, vouch)), (double)tiles);
+  // the sampled tiles of a call (or, with a mask per query, of one block) whose mask allows `allowed` rows
+  auto sample_for = [&](bool masked, uint64_t allowed) -> uint32_t {
+    uint32_t sample_tiles = std::max<uint32_t>(tiles / div, (8u * k + rw - 1) / rw);
+    // (a mask of at most 16 384 rows: the candidate buffers hold ALL of them, see below, so tau = -inf is answered from the
+    // candidates and a larger sample would buy nothing: the sample stays what an unmasked call takes)
+    if (masked && allowed > 16384) {
+      // A row mask that allows a fraction f of the rows: only blocks holding an allowed row vouch, and each for the best of its
+      // ~32 f allowed rows.  tau is then the k-th best of ~(sampled rows) x f rows and the full pass keeps ~k x rows / (sampled
+      // rows) of the allowed ones: the candidates per query do not grow with 1 / f, but the VOUCHING blocks shrink -- a fraction
+      // 1 - (1 - f)^32 of the sampled ones.  So the sample grows by 1 / f, up to 8 x (a quarter of the corpus at the default
+      // 1 / 32: beyond that the sample pass would cost what the full pass does), and further only while fewer than 8 k sampled
+      // blocks are expected to vouch; clamped to all tiles.  Fewer than k vouching blocks leave tau = -inf: every allowed row is a
+      // candidate, what does not fit is repaired by the masked fp32 scan.  
+      const double f = ix->n ? (double)allowed / (double)ix->n : 0.0;
+      if (f > 0.0) {
+        const double pv = 1.0 - std::pow(1.0 - std::min(f, 1.0), 32.0);
+        const double scaled = (double)sample_tiles * std::min(1.0 / f, 8.0), vouch = (8.0 * k) / (rw * std::max(pv, 1e-9));
+        sample_tiles = (uint32_t)std::min<double>(std::ceil(std::max(scaled, vouch)), (double)tiles);
+      }
     }
+    return std::max<uint32_t>(1, std::min(sample_tiles, tiles));
+  };
+  // A mask per query: the rule per BLOCK, for its most selective class above 16 384 rows (the class whose vouching blocks
+  // are fewest; the block's other classes get a larger sample than they need, never a smaller one).  Sizes below: the
+  // smallest sample of the call gives the most candidates per query, the largest the most sampled bounds.
+  std::vector<uint32_t> block_sample;
+  uint32_t sample_tiles, sample_max;
+  uint64_t small_class = 0;  // the largest mask of at most 16 384 rows: room for ALL its rows in the candidate buffers
+  if (multi) {
+    const MultimaskPlan& pl = *mc->plan;
+    std::vector<int> row_of_class((size_t)WDBX_MAX_CALL_MASKS + 1, 0);
+    for (size_t r = 0; r < pl.classes.size(); ++r) {
+      row_of_class[(size_t)(pl.classes[r] + 1)] = (int)r;
+      if (mc->allowed[r] <= 16384) small_class = std::max(small_class, mc->allowed[r]);
+    }
+    sample_tiles = tiles;
+    sample_max = 1;
+    for (uint32_t b = 0; b < pl.blocks(); ++b) {
+      uint64_t least = ~0ull;
+      for (uint32_t g = pl.block_group[b]; g < pl.block_group[b + 1]; ++g) {
+        const uint64_t al = mc->allowed[(size_t)row_of_class[(size_t)(pl.group_class[g] + 1)]];
+        if (al > 16384) least = std::min(least, al);
+      }
+      block_sample.push_back(least == ~0ull ? sample_for(false, 0) : sample_for(true, least));
+      sample_tiles = std::min(sample_tiles, block_sample.back());
+      sample_max = std::max(sample_max, block_sample.back());
+    }
+  } else {
+    sample_tiles = sample_max = sample_for(masked, ix->mask_allowed);
+    if (masked && ix->mask_allowed <= 16384) small_class = ix->mask_allowed;
   }
-  sample_tiles = std::max<uint32_t>(1, std::min(sample_tiles, tiles));
-  const uint32_t stride = tiles / sample_tiles;
   if (rw * sample_tiles < (uint32_t)k) return fail(WDBX_E_STATE, "corpus too small for the batched path at k=%d", k);
   const uint64_t expect = (uint64_t)k * (tiles / sample_tiles + 1);
   uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(4096, expect * 32), 1u << 22);
   // (a mask that allows few rows: room for ALL of them, so that tau = -inf -- no sampled block held an allowed row -- is
   // answered from the candidates, not by a repair scan per query; 16 384 rows = 32 MiB of candidate buffers)
-  if (masked && ix->mask_allowed <= 16384) cap = std::max<uint32_t>(cap, (uint32_t)ix->mask_allowed);
+  cap = std::max<uint32_t>(cap, (uint32_t)small_class);
   const size_t pitch4 = ix->pitch / 4;
-  if ((rc = grow((void**)&ix->d_halfmax, &ix->halfmax_bytes, (size_t)GB_N * rw * sample_tiles * sizeof(u64)))) return rc;
+  if ((rc = grow((void**)&ix->d_halfmax, &ix->halfmax_bytes, (size_t)GB_N * rw * sample_max * sizeof(u64)))) return rc;
   if ((rc = grow((void**)&ix->d_tau, &ix->tau_bytes, (size_t)GB_N * sizeof(float)))) return rc;
   if ((rc = grow((void**)&ix->d_cand, &ix->cand_bytes, (size_t)GB_N * cap * sizeof(u64)))) return rc;
   // (+ 1 word behind the counters: "a wave's pair list overflowed" -- see scatter_pairs_kernel)
@@ -1816,14 +1869,18 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
   // (the counters of every block, tau and the lost flag are initialised by the block's queries_to_i8_kernel: no memsets)
   ix->last_batch_nq = (uint32_t)nq;
   ix->last_batch_cap = cap;
-  ix->last_batch_masked = masked;
+  ix->last_batch_masked = multi ? 2 : masked ? 1 : 0;
   ix->last_batch_allowed = masked ? ix->mask_allowed : ix->n;
+  ix->last_batch_classes = multi ? (uint32_t)mc->plan->classes.size() : 0u;
+  ix->last_batch_blocks = multi ? mc->plan->blocks() : 0u;
   const u64* gbad = ix->d_gbad8;
-  if (masked) {  // this call's bad-row table: one launch over the whole group table (8 bytes per 64 rows), no synchronisation
-    const u64 ngroups = ix->groups8_bytes / sizeof(f4);  // (d_gbad8's entries: to the end of the last tile + the pad groups)
-    if ((rc = grow((void**)&ix->d_call_bad, &ix->call_bad_bytes, (size_t)ngroups * sizeof(u64)))) return rc;
-    hipLaunchKernelGGL(gbad_with_mask_kernel, dim3(gbad_with_mask_grid(ngroups)), dim3(256), 0, ix->stream, (const u64*)ix->d_gbad8,
-                       ix->active_mask, (u64)((ix->n + 31) / 32), ngroups, ix->d_call_bad);
+  const u64 ngroups = ix->groups8_bytes / sizeof(f4);  // (d_gbad8's entries: to the end of the last tile + the pad groups)
+  if (masked || multi) {  // this call's bad-row table(s): one launch over the whole group table (8 bytes per 64 rows), no synchronisation
+    const uint32_t rows = multi ? (uint32_t)mc->plan->classes.size() : 1u;
+    if ((rc = grow((void**)&ix->d_call_bad, &ix->call_bad_bytes, (size_t)rows * ngroups * sizeof(u64)))) return rc;
+    hipLaunchKernelGGL(gbad_with_mask_kernel, dim3(gbad_with_mask_grid(ngroups), rows), dim3(256), 0, ix->stream, (const u64*)ix->d_gbad8,
+                       multi ? mc->d_masks : ix->active_mask, (u64)((ix->n + 31) / 32), ngroups, ix->d_call_bad,
+                       (u64)(multi ? mc->mask_stride : 0), multi ? mc->d_class_mask : (const int32_t*)nullptr);
     HIP_TRY(hipGetLastError());
     gbad = ix->d_call_bad;
   }
@@ -1841,12 +1898,23 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
     ix->gref_valid = true;
   }
   const int max_ct = l2 ? std::min(2, i8g_max_ct(ix)) : i8g_max_ct(ix);  // (L2: query blocks of at most 128)
-  for (int q0 = 0; q0 < nq;) {
-    const int rem = nq - q0;
+  // the class runs of a block with a mask per query: {first slot in the block, slots, class row} -- what reads ONE mask per
+  // launch (the second selection stage, the repair scan) is launched per run
+  struct ClassRun {
+    int s0, n, row;
+  };
+  std::vector<ClassRun> runs;
+  uint32_t mblock = 0;
+  for (int q0 = 0; q0 < nq; ++mblock) {
+    // (a mask per query: the plan's block -- its slots are whole column groups and fit the widest query block)
+    const int rem = multi ? (int)(mc->plan->block_group[mblock + 1] - mc->plan->block_group[mblock]) * MULTIMASK_GROUP : nq - q0;
     int ct = (ix->opt_gemm_ct == 1 || ix->opt_gemm_ct == 2 || ix->opt_gemm_ct == 4) ? (int)ix->opt_gemm_ct : rem > 128 ? 4 : rem > 64 ? 2 : 1;
     ct = std::min(ct, max_ct);
     const int gbn = 64 * ct, nv = std::min(gbn, rem);
+    if (multi && nv != rem) return fail(WDBX_E_STATE, "a block of %d slots for query blocks of %d", rem, gbn);
     const float* qsrc = d_queries + (size_t)q0 * ix->pitch;
+    const uint32_t stride = tiles / (multi ? block_sample[mblock] : sample_tiles);
+    if (multi) sample_tiles = block_sample[mblock];
     hipLaunchKernelGGL(queries_to_i8_kernel, dim3(queries_to_i8_grid((uint32_t)gbn)), dim3(256), 0, ix->stream, qsrc, (uint32_t)ix->dim,
                        (uint32_t)ix->pitch, (uint32_t)nv, ix->d_qb8, pitch8, (uint32_t)gbn, ix->d_qpar, ix->d_tau, ix->d_count + q0, d_lost);
     HIP_TRY(hipGetLastError());
@@ -1863,7 +1931,19 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
     g.num_tiles = sample_tiles;
     g.tile_stride = stride;
     g.halfmax = ix->d_halfmax;
-    if ((rc = launch_gemm8<0>(ix, g, ct))) return rc;
+    if (multi) {
+      const MultimaskPlan& pl = *mc->plan;
+      g.n_class_groups = ngroups;
+      runs.clear();
+      for (uint32_t gi = pl.block_group[mblock]; gi < pl.block_group[mblock + 1]; ++gi) {
+        const int j = (int)(gi - pl.block_group[mblock]);
+        const int row = (int)(std::lower_bound(pl.classes.begin(), pl.classes.end(), pl.group_class[gi]) - pl.classes.begin());
+        g.class_row[j] = (uint8_t)row;  // (column groups behind the block's last: row 0, all their queries padded)
+        if (!runs.empty() && runs.back().row == row) runs.back().n += MULTIMASK_GROUP;
+        else runs.push_back({j * MULTIMASK_GROUP, MULTIMASK_GROUP, row});
+      }
+    }
+    if ((rc = launch_gemm8<0>(ix, g, ct, false, multi))) return rc;
     // the k-th largest of the groups' LOWER bounds: a valid threshold by itself (no margin)
     if (rw * sample_tiles <= KTH_R * 1024 && !ix->opt_lds_lists) {
       KthArgs ka = {ix->d_halfmax, (u64)rw * sample_tiles, rw * sample_tiles, k, ix->d_tau};
@@ -1883,6 +1963,10 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
       m.out_kth = ix->d_tau;
       if ((rc = launch_merge(ix, m, nv))) return rc;
     }
+    if (multi) {  // the pad slots inside the block are padded queries
+      hipLaunchKernelGGL(pad_tau_kernel, dim3((nv + 255) / 256), dim3(256), 0, ix->stream, ix->d_tau, mc->d_slot_query + q0, (uint32_t)nv);
+      HIP_TRY(hipGetLastError());
+    }
     g.num_tiles = tiles;
     g.tile_stride = 1;
     g.halfmax = nullptr;
@@ -1890,7 +1974,7 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
     g.pairs = ix->d_pairs;
     g.pair_count = ix->d_pair_count;
     g.pair_cap = pair_cap;
-    if ((rc = launch_gemm8<1>(ix, g, ct, masked))) return rc;
+    if ((rc = launch_gemm8<1>(ix, g, ct, masked, multi))) return rc;
     hipLaunchKernelGGL(scatter_pairs_kernel, dim3((nwaves + SCATTER_LISTS - 1) / SCATTER_LISTS), dim3(1024), 0, ix->stream,
                        (const u64*)ix->d_pairs, (const uint32_t*)ix->d_pair_count, nwaves, pair_cap, ix->d_cand, ix->d_count + q0, cap,
                        d_lost);
@@ -1911,7 +1995,19 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
       void (*fn)(RefineArgs) = l2 ? (reg ? refine_pairs_kernel<WDBX_METRIC_L2, true> : refine_pairs_kernel<WDBX_METRIC_L2, false>)
                                   : (reg ? refine_pairs_kernel<WDBX_METRIC_COSINE, true> : refine_pairs_kernel<WDBX_METRIC_COSINE, false>);
       r.n_lds = std::min<uint32_t>(cap, REFINE_R * 1024);
-      hipLaunchKernelGGL(fn, dim3(nv), dim3(1024), std::max((size_t)r.n_lds * 4, (size_t)17 * k * sizeof(u64)), ix->stream, r);
+      const size_t lds = std::max((size_t)r.n_lds * 4, (size_t)17 * k * sizeof(u64));
+      if (multi) {  // (one workgroup per query, one bad-row table per launch: a launch per class run, its class's table)
+        for (const ClassRun& cr : runs) {
+          RefineArgs rr = r;
+          rr.cand = r.cand + (size_t)cr.s0 * cap;
+          rr.count = r.count + cr.s0;
+          rr.qpar = r.qpar + cr.s0;
+          rr.gbad = gbad + (size_t)cr.row * ngroups;
+          hipLaunchKernelGGL(fn, dim3(cr.n), dim3(1024), lds, ix->stream, rr);
+        }
+      } else {
+        hipLaunchKernelGGL(fn, dim3(nv), dim3(1024), lds, ix->stream, r);
+      }
       HIP_TRY(hipGetLastError());
     }
     // exact fp32 scores of the kept rows (L2: the direct form sum (c - q)^2)
@@ -1940,7 +2036,21 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
       f.out_score = d_out_score + (size_t)q0 * k;
     }
     if ((rc = launch_merge(ix, f, nv))) return rc;
-    {  // (marks the block's queries overflowed if a wave lost pairs, then the conditional repair launches)
+    if (multi) {
+      // an overflowed query is repaired by the scan with ITS mask: the repair launches per class run, each with its class's
+      // mask as the scan's (a run of the class without a mask: none)
+      bool done = true;
+      for (const ClassRun& cr : runs) {
+        bool d1 = false;
+        ix->active_mask = mc->d_class_mask && mc->plan->classes[(size_t)cr.row] >= 0 ? mc->d_masks + (size_t)cr.row * mc->mask_stride : nullptr;
+        rc = enqueue_batch_repair(ix, qsrc + (size_t)cr.s0 * ix->pitch, cr.n, k, ix->d_count + q0 + cr.s0, cap, f.out_idx + (size_t)cr.s0 * k,
+                                  f.out_score + (size_t)cr.s0 * k, nullptr, &d1, d_lost);
+        ix->active_mask = nullptr;
+        if (rc) return rc;
+        done = done && d1;
+      }
+      ix->last_batch_repaired = q0 == 0 ? done : (ix->last_batch_repaired && done);
+    } else {  // (marks the block's queries overflowed if a wave lost pairs, then the conditional repair launches)
       bool done = false;
       if ((rc = enqueue_batch_repair(ix, qsrc, nv, k, ix->d_count + q0, cap, f.out_idx, f.out_score, f.out_keys, &done, d_lost))) return rc;
       if (q0 == 0) ix->last_batch_repaired = done;

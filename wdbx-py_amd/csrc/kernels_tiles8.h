@@ -81,6 +81,10 @@ struct Gemm8Args {
   u64* pairs;            // [gridDim.x * 8 waves][pair_cap]
   uint32_t* pair_count;  // [gridDim.x * 8]: pairs each wave produced (beyond pair_cap: dropped, the call is flagged)
   uint32_t pair_cap;
+  // EPI8_MULTI_*: one row mask per query (see there).  gbad is then a table of n_class_groups entries per class of the call
+  // and class_row[j] the table row of column group j's class.  (Behind everything else: no other field moves.)
+  u64 n_class_groups;
+  uint8_t class_row[16];
 };
 
 // position (in 16-byte pieces) of piece c of query row r inside its LDS row: an XOR swizzle that makes the MFMA
@@ -110,9 +114,20 @@ __device__ __forceinline__ uint32_t g8_bswz(uint32_t c, uint32_t r, bool odd) {
 // the end and the rows the caller's row mask leaves out); the wave's 32 bits are read on the scalar path as in PHASE 0 and its
 // bad rows are cleared from the hit set BEFORE pairs are appended -- with a selective mask tau is low, and masked-out rows
 // above it would otherwise flood the per-wave pair lists.  PHASE 0 needs no flag: fed the same table, a masked-out row cannot vouch.
-enum Epi8 { EPI8_EXACT, EPI8_PRE_GROUP, EPI8_PRE_BLOCK };
-template <int PHASE, int CT8, int RING, int PITCH8 = 0, Epi8 EPI = EPI8_EXACT, int METRIC = WDBX_METRIC_COSINE, bool MASKED = false>
+// EPI8_MULTI_EXACT / EPI8_MULTI_PRE_BLOCK (one row mask PER QUERY in one call; the product forms only:
+// the exact epilogue for PHASE 0 and L2, the prefilter block for the inner-product full pass): the epilogue named, and the
+// mask word a scalar PER COLUMN GROUP.  The host places the call's queries so that the 16 queries of a column group share one
+// mask (host_multimask.h); a.gbad is one bad-row table per class of the call (gbad_with_mask_kernel, grid.y = class) and
+// epilogue(j) reads its word from row a.class_row[j] of it, on the scalar path, then does what PHASE 0 and MASKED do with it.
+// No per-lane state: scalar registers and scalar loads.  (Epilogue values, not a template parameter of their own: the
+// existing instances keep their names and their code.)
+enum Epi8 { EPI8_EXACT, EPI8_PRE_GROUP, EPI8_PRE_BLOCK, EPI8_MULTI_EXACT, EPI8_MULTI_PRE_BLOCK };
+template <int PHASE, int CT8, int RING, int PITCH8 = 0, Epi8 EPI_ = EPI8_EXACT, int METRIC = WDBX_METRIC_COSINE, bool MASKED = false>
 __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
+  constexpr bool MULTI = EPI_ == EPI8_MULTI_EXACT || EPI_ == EPI8_MULTI_PRE_BLOCK;
+  constexpr Epi8 EPI = EPI_ == EPI8_MULTI_EXACT ? EPI8_EXACT : EPI_ == EPI8_MULTI_PRE_BLOCK ? EPI8_PRE_BLOCK : EPI_;
+  static_assert(!MULTI || (!MASKED && EPI == ((PHASE == 0 || METRIC == WDBX_METRIC_L2) ? EPI8_EXACT : EPI8_PRE_BLOCK)),
+                "per-query row masks: the product forms only");
   // (exactly the forms whose append sites clear the bad rows: the prefilter epilogue for inner product, the plain one for L2)
   static_assert(!MASKED || (PHASE == 1 && EPI == (METRIC == WDBX_METRIC_L2 ? EPI8_EXACT : EPI8_PRE_BLOCK)),
                 "row masks: the full pass of the product forms only");
@@ -246,7 +261,8 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
   // L2: per tile, this lane's 8 rows' norm terms.  PHASE 0: |c_r|^2 taken high.  PHASE 1: u_r = |c_r|^2 / (2 s_g) taken low;
   // a NaN norm (a removed row: never a result) becomes +inf = never kept, a norm that overflowed -inf = always kept.
   float e_u[L2 ? 8 : 1];
-  uint32_t e_bad = 0;  // PHASE 0, MASKED: the bad-row bits of this wave's 32 rows (wave-uniform)
+  uint32_t e_bad = 0;  // PHASE 0, MASKED: the bad-row bits of this wave's 32 rows (wave-uniform); MULTI: for the column group at hand
+  uint32_t e_gidx = 0; // MULTI: the tile's 64-row group, for the column groups' own loads of those bits
   // MASKED: this lane's 8 rows' bad bits, in the order of the hit sets below (row r = 16 (r >> 2) + (r & 3) behind 4 kb)
   auto lane_bad = [&]() -> uint32_t { return ((e_bad >> (4 * kb)) & 0xFu) | (((e_bad >> (4 * kb + 16)) & 0xFu) << 4); };
   // PHASE 1: the lanes' kept rows (bits: which of the lane's 8 rows of column group j) go to the wave's pair list, one
@@ -271,6 +287,15 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
   };
   auto epilogue = [&](int j) {
     const uint32_t lrow0 = e_wrow0 + 4 * kb;  // this lane's rows: lrow0 + 16 h + i
+    if constexpr (MULTI) {  // this column group's class: its word of the class's table (a wave-uniform address: the scalar path)
+      uint32_t row = a.class_row[j];
+      asm volatile("" : "+s"(row));  // (computed here: NJ table addresses hoisted out of the tile loop would cost 2 NJ scalar registers)
+      const u64 bad = *(const __attribute__((address_space(4))) u64*)(a.gbad + (u64)row * a.n_class_groups + e_gidx);
+      e_bad = (uint32_t)(bad >> (e_wrow0 & 32u));
+      if constexpr (PHASE == 1) {
+        if (e_bad == 0xFFFFFFFFu) return;  // (wave-uniform) none of the wave's 32 rows may be returned to this class
+      }
+    }
     if constexpr (PHASE == 0) {
       uint32_t q = (uint32_t)l15;
       asm volatile("" : "+v"(q));  // (computed here, not kept in NJ registers across the launch)
@@ -333,7 +358,7 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
           for (int r = 0; r < 8; ++r)
             if (!(f[r] < T) && lrow0 + 16 * (r >> 2) + (r & 3) < a.n_rows) bits |= 1u << r;
         }
-        if constexpr (MASKED) bits &= ~lane_bad();
+        if constexpr (MASKED || MULTI) bits &= ~lane_bad();
         append_pairs(bits, q, j, lrow0);
       }
     } else {
@@ -351,7 +376,7 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
           for (int r = 0; r < 8; ++r)
             if (!((float)acc[j][r >> 2][r & 3] < T) && lrow0 + 16 * (r >> 2) + (r & 3) < a.n_rows) bits |= 1u << r;
         }
-        if constexpr (MASKED) bits &= ~lane_bad();
+        if constexpr (MASKED || MULTI) bits &= ~lane_bad();
         append_pairs(bits, q, j, lrow0);
       }
     }
@@ -429,7 +454,9 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
     {  // the group's {s_g, a_g, b_g, vouch}: a wave-uniform address, read on the scalar path
       const uint32_t gidx = __builtin_amdgcn_readfirstlane(e_wrow0 >> 6);
       e_gt = *(const __attribute__((address_space(4))) f4*)(a.groups + gidx);
-      if constexpr (PHASE == 0 || MASKED) {
+      if constexpr (MULTI) {
+        e_gidx = gidx;
+      } else if constexpr (PHASE == 0 || MASKED) {
         const u64 bad = *(const __attribute__((address_space(4))) u64*)(a.gbad + gidx);
         e_bad = (uint32_t)(bad >> (e_wrow0 & 32u));
       }
@@ -605,18 +632,39 @@ __global__ __launch_bounds__(256) void rows_to_i8g_kernel(const float* rows, u64
 static inline uint32_t rows_to_i8g_grid(uint64_t groups) { return (uint32_t)std::min<uint64_t>(groups, 1u << 20); }
 
 // The bad-row table of ONE masked call: call_bad[g] = gbad[g] | ~mask64[g] for all n_groups groups of the table (to the end
-// of the last tile and the pad groups behind it).  The caller's row mask is mask_words uint32 words (bit r % 32 of word
-// r / 32 = row r may be returned): two of them, little end first, are the complement of a group's bad-row word.  Words past
+// of the last tile and the pad groups behind it).  The caller's row mask is mask_words uint32 words (bit r % 32 of word r / 32 =
+// row r may be returned): two of them, little end first, are the complement of a group's bad-row word.  Words past
 // the mask's end read as zero (ceil(rows / 32) may be odd, and the groups behind the last row have no word at all), and the
 // bits a caller left set past the last row meet the table's own past-the-end bits: such rows stay bad whatever the mask says.
+// A call with one mask PER QUERY builds the tables of all its classes in this one launch: grid.y = the class's row of the
+// table (call_bad + y * n_groups), class_mask[y] = which of the call's masks (mask + class_mask[y] * mask_stride words) that
+// class reads, or -1 for the class without a mask, whose row is gbad itself.  class_mask == null: the one mask, row 0.
 __global__ __launch_bounds__(256) void gbad_with_mask_kernel(const u64* gbad, const uint32_t* mask, u64 mask_words, u64 n_groups,
-                                                             u64* call_bad) {
+                                                             u64* call_bad, u64 mask_stride, const int32_t* class_mask) {
+  const int32_t m = class_mask ? class_mask[blockIdx.y] : 0;
+  if (m >= 0) mask += (u64)m * mask_stride;
+  call_bad += (u64)blockIdx.y * n_groups;
   for (u64 g = (u64)blockIdx.x * 256 + threadIdx.x; g < n_groups; g += (u64)gridDim.x * 256) {
-    const u64 lo = 2 * g < mask_words ? mask[2 * g] : 0u, hi = 2 * g + 1 < mask_words ? mask[2 * g + 1] : 0u;
-    call_bad[g] = gbad[g] | ~(lo | (hi << 32));
+    const u64 lo = (m >= 0 && 2 * g < mask_words) ? mask[2 * g] : 0u, hi = (m >= 0 && 2 * g + 1 < mask_words) ? mask[2 * g + 1] : 0u;
+    call_bad[g] = m < 0 ? gbad[g] : gbad[g] | ~(lo | (hi << 32));
   }
 }
 static inline uint32_t gbad_with_mask_grid(uint64_t groups) { return (uint32_t)std::min<uint64_t>((groups + 255) / 256, 4096); }
+
+// A call with one mask per query: its queries [nq, pitch] into the slots the host's placement gave them (host_multimask.h:
+// slot_query[s] = the caller's query in slot s, -1 = a pad slot: a zero row).  One thread per float4.
+__global__ __launch_bounds__(256) void place_queries_kernel(const f4* q, const int32_t* slot_query, uint32_t pitch4, uint32_t slots, f4* out) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= slots * pitch4) return;
+  const int32_t src = slot_query[i / pitch4];
+  out[i] = src < 0 ? f4{0.f, 0.f, 0.f, 0.f} : q[(size_t)src * pitch4 + i % pitch4];
+}
+// ... and behind the sampled thresholds of a block of them: a pad slot is a PADDED query (tau = +inf: never a candidate) --
+// as an all-zero query with a threshold of its own it would keep every row its class allows
+__global__ __launch_bounds__(256) void pad_tau_kernel(float* tau, const int32_t* slot_query, uint32_t slots) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i < slots && slot_query[i] < 0) tau[i] = INFINITY;
+}
 
 // queries [nv, pitch] fp32 -> the i8 query block [gbn][pitch8] (signed bytes, zero padded) and its parameters
 // {s_q, E_q, M_q, 1 / s_q} (E, M rounded up; a non-finite query gets E = +inf: every row becomes a candidate and the exact

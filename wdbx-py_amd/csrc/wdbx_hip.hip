@@ -28,6 +28,7 @@
 //                           scores of the u8 selection's candidates); wave-aggregated appends, no k
 //   kernels_subset.h        subset_kernel: exact scores of LISTED rows (wdbx_index_search_rows), a block of queries per fetched
 //                           row, per-workgroup top-k lists or a key per listed row
+//   host_multimask.h        a call with one row mask per query: the placement of its queries in the int8 tiles' query blocks
 //   host_index.h            the handle, kernel choice, and the enqueue functions of every search path
 //   host_group.h            the in-process shard group: per-shard host threads, exchange (RCCL all-gather / device copies), merge
 // The selection paths never decide a result: they keep every row whose score could reach the true k-th best
@@ -66,6 +67,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_dispatch.h"
 #include "host_range.h"  // (device-free as well: CSR offsets, per-query sort and decoding of a range search's keys)
 #include "host_subset.h"  // (device-free as well: row-list validation, route and grid sizing of a search among listed rows)
+#include "host_multimask.h"  // (device-free as well: where the queries of a call with a mask per query sit in the tile blocks)
 
 #define HIP_TRY(expr)                                                                        \
   do {                                                                                       \
@@ -114,7 +116,7 @@ static uint64_t device_bytes_resident(const wdbx_index* ix) {
   b += ix->qb8_bytes + ix->qpar_bytes + ix->pairs_bytes + ix->pair_count_bytes + ix->cnmax_bytes;
   b += ix->rcand_bytes + ix->rkeys_bytes + ix->rcnt_bytes + ix->rthr_bytes;
   b += ix->rows6_bytes + ix->count6_bytes;
-  b += ix->sub_ids_bytes + ix->sub_keys_bytes;
+  b += ix->sub_ids_bytes + ix->sub_keys_bytes + ix->mm_bytes;
   return b;
 }
 
@@ -192,7 +194,7 @@ void wdbx_index_destroy(wdbx_index* ix) try {
                     ix->d_state, ix->d_cn, ix->d_cnmax, ix->d_qb16, ix->d_rows16, ix->d_rows8, ix->d_scale8, ix->d_selsrc,
                     ix->d_gmax, ix->d_qn, ix->d_rows8g, ix->d_groups8, ix->d_gbad8, ix->d_gref8, ix->d_over_list, ix->d_qb8,
                     ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr, ix->d_rows6, ix->d_count6,
-                    ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys};
+                    ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys, ix->d_mm};
     for (void* p : bufs)
       if (p) (void)hipFree(p);
     if (ix->h_stage) (void)hipHostFree(ix->h_stage);
@@ -364,8 +366,11 @@ int wdbx_index_compact(wdbx_index* ix, const uint64_t* src_rows, uint64_t n_keep
 
 // mask_word_count: how many words the caller's mask holds (checked against the row count under the handle's lock: a mask built
 // before a concurrent add is refused instead of over-read); ~0 = the caller vouches for ceil(rows / 32) words
+// held: the caller already holds the handle's mutex through this lock and keeps it (a call that answers in several steps,
+// wdbx_index_search_multimask's class-by-class route): the call then never lets go of it -- no staging slot, no narrow wait.
 static int search_host(wdbx_index* ix, const float* queries, int nq, int k, int normalize_queries,
-                       const uint32_t* mask_words, uint64_t mask_word_count, int64_t* out_idx, float* out_score) {
+                       const uint32_t* mask_words, uint64_t mask_word_count, int64_t* out_idx, float* out_score,
+                       std::unique_lock<std::mutex>* held = nullptr) {
   if (!ix) return fail(WDBX_E_INVALID, "null handle");
   if (nq < 0) return fail(WDBX_E_INVALID, "nq=%d", nq);
   if (nq == 0) return WDBX_OK;
@@ -377,7 +382,9 @@ static int search_host(wdbx_index* ix, const float* queries, int nq, int k, int 
   // another thread enqueues behind this call on the stream while this one waits for its event, so N threads calling one
   // handle (the reference's 4-worker pools per index, indexing.py:692, :1045-1048) pipeline instead of taking turns at
   // wall-clock latency.  Scratch buffers are shared by consecutive calls: the stream runs them in order.
-  std::unique_lock<std::mutex> lk(ix->mu);
+  std::unique_lock<std::mutex> own;
+  if (!held) own = std::unique_lock<std::mutex>(ix->mu);
+  std::unique_lock<std::mutex>& lk = held ? *held : own;
   DeviceGuard g(ix->device);
   struct MaskScope {  // the mask applies to this call only (such a call keeps the mutex to its end: d_mask is one buffer)
     wdbx_index* ix;
@@ -407,7 +414,7 @@ static int search_host(wdbx_index* ix, const float* queries, int nq, int k, int 
   for (;;) {
     // (a row mask: one masked pass over the int8 tiles when they are what would run; per-query masked scans otherwise)
     gemm = gemm_eligible(ix, nq, k) && (!(mask_words && ix->n) || masked_tiles_ready(ix, k));
-    zero_copy = ix->opt_zero_copy && !gemm && q_bytes <= STAGE_Q && elems * sizeof(int64_t) <= STAGE_IDX;
+    zero_copy = ix->opt_zero_copy && !gemm && !held && q_bytes <= STAGE_Q && elems * sizeof(int64_t) <= STAGE_IDX;
     if (zero_copy && !ix->h_stage) {
       void* hp = nullptr;
       void* dp = nullptr;
@@ -440,8 +447,8 @@ static int search_host(wdbx_index* ix, const float* queries, int nq, int k, int 
       return fail(WDBX_E_INVALID, "row mask of %llu words for %llu rows (%zu words needed)", (u64)mask_word_count, (u64)ix->n, words);
     scope.set = true;
     if ((rc = set_active_mask(ix, mask_words))) return rc;
-    if (!gemm) ix->last_batch_masked = false;
   }
+  if (!gemm) ix->last_batch_masked = 0;  // (what the last_batch_* options describe is the last call, whatever it ran)
   char* const hs = zero_copy ? ix->h_stage + (size_t)hold.slot * SLOT_BYTES : nullptr;      // this call's slot, host view
   char* const ds = zero_copy ? ix->h_stage_dev + (size_t)hold.slot * SLOT_BYTES : nullptr;  // ... and device view
   // wait for this call's launches: with a slot and no row mask, by its own event with the mutex RELEASED
@@ -672,6 +679,166 @@ int wdbx_index_search_masked_n(wdbx_index* ix, const float* queries, int nq, int
                                const uint32_t* mask_words, uint64_t mask_word_count, int64_t* out_idx, float* out_score) try {
   if (!mask_words) return fail(WDBX_E_INVALID, "mask_words is null");
   return search_host(ix, queries, nq, k, normalize_queries, mask_words, mask_word_count, out_idx, out_score);
+} WDBX_CATCH
+
+// ---- one row mask PER QUERY in one batched call (host_multimask.h) ---------------------------
+// query_mask[i] = which of the call's masks query i reads, or -1 (every row).  When the int8 tiles are what a masked batch
+// would run (masked_tiles_ready) the whole call is one tile pass per block of up to 256 placed queries, whatever the number
+// of masks: the queries are placed so that a column group of 16 shares one mask, each class of the call gets its bad-row
+// table, and the kernels read the table row of the column group at hand.  Otherwise every class goes through the call that
+// existed before (wdbx_index_search_masked_n; wdbx_index_search for the class without a mask) and the answers are scattered
+// back.  Results in the caller's order either way.  The call holds the handle's mutex to its end on both routes (the masks,
+// the placed queries and the tables are the handle's; the class-by-class calls run under the lock this call took).
+int wdbx_index_search_multimask(wdbx_index* ix, const float* queries, int nq, int k, int normalize_queries,
+                                const uint32_t* const* mask_words, const uint64_t* mask_word_counts, int n_masks,
+                                const int32_t* query_mask, int64_t* out_idx, float* out_score) try {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  if (nq < 1) return fail(WDBX_E_INVALID, "nq=%d", nq);
+  if (!queries || !out_idx || !out_score || !query_mask) return fail(WDBX_E_INVALID, "null buffer");
+  if (k < 1 || k > WDBX_MAX_K) return fail(WDBX_E_INVALID, "k=%d outside [1, %d]", k, WDBX_MAX_K);
+  if (n_masks < 0 || n_masks > WDBX_MAX_CALL_MASKS) return fail(WDBX_E_INVALID, "n_masks=%d outside [0, %d]", n_masks, WDBX_MAX_CALL_MASKS);
+  if (n_masks && (!mask_words || !mask_word_counts)) return fail(WDBX_E_INVALID, "null mask list");
+  for (int m = 0; m < n_masks; ++m)
+    if (!mask_words[m]) return fail(WDBX_E_INVALID, "mask %d is null", m);
+  for (int q = 0; q < nq; ++q)
+    if (query_mask[q] < -1 || query_mask[q] >= n_masks)
+      return fail(WDBX_E_INVALID, "query_mask[%d]=%d outside [-1, %d)", q, (int)query_mask[q], n_masks);
+  std::unique_lock<std::mutex> lk(ix->mu);
+  DeviceGuard g(ix->device);
+  const size_t words = (size_t)((ix->n + 31) / 32);
+  for (int m = 0; m < n_masks && ix->n; ++m)
+    if (mask_word_counts[m] < words)
+      return fail(WDBX_E_INVALID, "row mask %d of %llu words for %llu rows (%zu words needed)", m, (u64)mask_word_counts[m], (u64)ix->n, words);
+  int rc;
+  const bool l2 = ix->metric == WDBX_METRIC_L2;
+  ix->last_batch_masked = 0;
+  const bool tiles = ix->n && ix->n < 0xFFFFFF00ull && gemm_eligible(ix, nq, k) && masked_tiles_ready(ix, k);
+  if (!tiles) {
+    // class by class through the calls that existed before, in the caller's order inside a class; the lock stays held
+    std::vector<float> cq;
+    std::vector<int64_t> ci;
+    std::vector<float> cs;
+    std::vector<int> members;
+    for (int c = -1; c < n_masks; ++c) {
+      members.clear();
+      for (int q = 0; q < nq; ++q)
+        if (query_mask[q] == c) members.push_back(q);
+      if (members.empty()) continue;
+      const size_t nm = members.size();
+      cq.resize(nm * (size_t)ix->dim);
+      ci.resize(nm * (size_t)k);
+      cs.resize(nm * (size_t)k);
+      for (size_t i = 0; i < nm; ++i) memcpy(&cq[i * ix->dim], queries + (size_t)members[i] * ix->dim, (size_t)ix->dim * sizeof(float));
+      rc = search_host(ix, cq.data(), (int)nm, k, normalize_queries, c < 0 ? nullptr : mask_words[c], c < 0 ? 0 : mask_word_counts[c], ci.data(),
+                       cs.data(), &lk);
+      if (rc) return rc;
+      for (size_t i = 0; i < nm; ++i) {
+        memcpy(out_idx + (size_t)members[i] * k, &ci[i * k], (size_t)k * sizeof(int64_t));
+        memcpy(out_score + (size_t)members[i] * k, &cs[i * k], (size_t)k * sizeof(float));
+      }
+    }
+    return WDBX_OK;
+  }
+  // ---- the tile route ----
+  const int forced = (ix->opt_gemm_ct == 1 || ix->opt_gemm_ct == 2 || ix->opt_gemm_ct == 4) ? (int)ix->opt_gemm_ct : 4;
+  const int max_ct = std::min(forced, l2 ? std::min(2, i8g_max_ct(ix)) : i8g_max_ct(ix));
+  MultimaskPlan plan;
+  if (!multimask_plan(query_mask, nq, n_masks, 64 * max_ct, &plan)) return fail(WDBX_E_INVALID, "query_mask cannot be placed");
+  const size_t slots = plan.slot_query.size(), rows = plan.classes.size();
+  // the classes' masks (class row r at r * stride words; the class without a mask has none), their allowed rows counted on
+  // the host copies as set_active_mask does, and the row -> mask table of the bad-row kernel
+  const size_t stride = (words + 63) / 64 * 64;
+  std::vector<uint64_t> allowed(rows, ix->n);
+  std::vector<int32_t> class_mask(rows, -1);
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t off_q = 0, off_slot = up(slots * ix->pitch * sizeof(float)), off_cm = off_slot + up(slots * sizeof(int32_t)),
+               off_masks = off_cm + up(rows * sizeof(int32_t)), total = off_masks + rows * stride * sizeof(uint32_t);
+  if ((rc = grow((void**)&ix->d_mm, &ix->mm_bytes, total))) return rc;
+  float* const d_slots_q = (float*)(ix->d_mm + off_q);
+  int32_t* const d_slot_query = (int32_t*)(ix->d_mm + off_slot);
+  int32_t* const d_class_mask = (int32_t*)(ix->d_mm + off_cm);
+  uint32_t* const d_masks = (uint32_t*)(ix->d_mm + off_masks);
+  for (size_t r = 0; r < rows; ++r) {
+    const int c = plan.classes[r];
+    if (c < 0) continue;
+    class_mask[r] = (int32_t)r;
+    const uint32_t* mw = mask_words[c];
+    HIP_TRY(hipMemcpyAsync(d_masks + r * stride, mw, words * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+    uint64_t al = 0;
+    for (size_t w = 0; w + 1 < words; ++w) al += (uint64_t)__builtin_popcount(mw[w]);
+    const uint32_t tail = (uint32_t)(ix->n & 31);
+    al += (uint64_t)__builtin_popcount(mw[words - 1] & (tail ? (1u << tail) - 1u : ~0u));
+    allowed[r] = al;
+  }
+  HIP_TRY(hipMemcpyAsync(d_slot_query, plan.slot_query.data(), slots * sizeof(int32_t), hipMemcpyHostToDevice, ix->stream));
+  HIP_TRY(hipMemcpyAsync(d_class_mask, class_mask.data(), rows * sizeof(int32_t), hipMemcpyHostToDevice, ix->stream));
+  // the queries as in search_host, then into their slots
+  const size_t q_bytes = (size_t)nq * ix->pitch * sizeof(float), elems = slots * (size_t)k;
+  if ((rc = grow((void**)&ix->d_q, &ix->q_bytes, q_bytes))) return rc;
+  if (elems > ix->out_elems) {
+    if (ix->d_oidx) HIP_TRY(hipFree(ix->d_oidx));
+    if (ix->d_oscore) HIP_TRY(hipFree(ix->d_oscore));
+    ix->d_oidx = nullptr;
+    ix->d_oscore = nullptr;
+    ix->out_elems = 0;
+    HIP_TRY(hipMalloc((void**)&ix->d_oidx, elems * sizeof(int64_t)));
+    HIP_TRY(hipMalloc((void**)&ix->d_oscore, elems * sizeof(float)));
+    ix->out_elems = elems;
+  }
+  if (ix->pitch == ix->dim) {
+    HIP_TRY(hipMemcpyAsync(ix->d_q, queries, q_bytes, hipMemcpyHostToDevice, ix->stream));
+  } else {
+    HIP_TRY(hipMemsetAsync(ix->d_q, 0, q_bytes, ix->stream));
+    HIP_TRY(hipMemcpy2DAsync(ix->d_q, (size_t)ix->pitch * sizeof(float), queries, (size_t)ix->dim * sizeof(float),
+                             (size_t)ix->dim * sizeof(float), nq, hipMemcpyHostToDevice, ix->stream));
+  }
+  if (normalize_queries && ix->metric == WDBX_METRIC_COSINE && (rc = launch_normalize(ix, ix->d_q, nq))) return rc;
+  const uint32_t pitch4 = (uint32_t)(ix->pitch / 4);
+  hipLaunchKernelGGL(place_queries_kernel, dim3((uint32_t)((slots * pitch4 + 255) / 256)), dim3(256), 0, ix->stream, (const f4*)ix->d_q,
+                     (const int32_t*)d_slot_query, pitch4, (uint32_t)slots, (f4*)d_slots_q);
+  HIP_TRY(hipGetLastError());
+  ix->last_batch_repaired = false;
+  MultiCall mc = {&plan, d_slot_query, d_masks, stride, d_class_mask, allowed.data()};
+  struct MaskScope {  // (the repair launches set the class's mask for their own duration; nothing outlives the call)
+    wdbx_index* ix;
+    ~MaskScope() { ix->active_mask = nullptr; }
+  } scope{ix};
+  if ((rc = enqueue_search_gemm8(ix, d_slots_q, (int)slots, k, ix->d_oidx, ix->d_oscore, SEARCH_FINAL, nullptr, &mc))) return rc;
+  // what wdbx_index_batch_status reports: the caller's queries
+  ix->last_batch_nq = (uint32_t)nq;
+  ix->last_batch_slot.assign((size_t)nq, 0);
+  for (size_t s2 = 0; s2 < slots; ++s2)
+    if (plan.slot_query[s2] >= 0) ix->last_batch_slot[(size_t)plan.slot_query[s2]] = (int32_t)s2;
+  std::vector<uint32_t> counts(slots);
+  HIP_TRY(hipMemcpyAsync(counts.data(), ix->d_count, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  // shapes without a device-side repair (option batch_repair = 0, partial lists beyond 256 MiB): the overflowed queries are
+  // re-run here on the fp32 scan, each with its class's mask
+  for (size_t s2 = 0; s2 < slots && !ix->last_batch_repaired; ++s2)
+    if (plan.slot_query[s2] >= 0 && counts[s2] > ix->last_batch_cap) {
+      const int c = plan.group_class[s2 / MULTIMASK_GROUP];
+      const size_t r = (size_t)(std::lower_bound(plan.classes.begin(), plan.classes.end(), c) - plan.classes.begin());
+      const int64_t keep = ix->opt_scan_shadow;
+      ix->opt_scan_shadow = 0;
+      ix->active_mask = c < 0 ? nullptr : d_masks + r * stride;
+      ix->mask_allowed = allowed[r];
+      rc = enqueue_search(ix, d_slots_q + s2 * ix->pitch, 1, k, ix->d_oidx + s2 * k, ix->d_oscore + s2 * k, SEARCH_FINAL);
+      ix->active_mask = nullptr;
+      ix->opt_scan_shadow = keep;
+      if (rc) return rc;
+    }
+  std::vector<int64_t> h_idx(elems);
+  std::vector<float> h_score(elems);
+  HIP_TRY(hipMemcpyAsync(h_idx.data(), ix->d_oidx, elems * sizeof(int64_t), hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipMemcpyAsync(h_score.data(), ix->d_oscore, elems * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  for (size_t s2 = 0; s2 < slots; ++s2) {
+    const int q = plan.slot_query[s2];
+    if (q < 0) continue;
+    memcpy(out_idx + (size_t)q * k, &h_idx[s2 * k], (size_t)k * sizeof(int64_t));
+    memcpy(out_score + (size_t)q * k, &h_score[s2 * k], (size_t)k * sizeof(float));
+  }
+  return WDBX_OK;
 } WDBX_CATCH
 
 // ---- search among listed rows (kernels_subset.h, host_subset.h) -------------------------------------
@@ -1111,7 +1278,14 @@ int wdbx_index_batch_status(wdbx_index* ix, uint32_t* out_counts, int nq, uint32
   DeviceGuard g(ix->device);
   if (nq < 0 || (uint32_t)nq > ix->last_batch_nq) return fail(WDBX_E_INVALID, "nq=%d but the last batch had %u queries", nq, ix->last_batch_nq);
   std::vector<uint32_t> counts((size_t)std::max(nq, 1));
-  if (nq) HIP_TRY(hipMemcpyAsync(counts.data(), ix->d_count, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
+  if (ix->last_batch_masked == 2) {  // a mask per query: the counters are per slot; reported in the caller's query order
+    std::vector<uint32_t> slots(ix->last_batch_slot.empty() ? 0 : (size_t)*std::max_element(ix->last_batch_slot.begin(), ix->last_batch_slot.end()) + 1);
+    if (!slots.empty()) HIP_TRY(hipMemcpyAsync(slots.data(), ix->d_count, slots.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    for (int q = 0; q < nq; ++q) counts[(size_t)q] = slots[(size_t)ix->last_batch_slot[(size_t)q]];
+  } else if (nq) {
+    HIP_TRY(hipMemcpyAsync(counts.data(), ix->d_count, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
+  }
   HIP_TRY(hipStreamSynchronize(ix->stream));
   int over = 0;
   for (int q = 0; q < nq; ++q) {
@@ -1724,7 +1898,10 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "last_rows_path")) return *value = ix->last_rows_path, WDBX_OK;
   if (name && !strcmp(name, "last_sample_qn")) return *value = ix->last_sample_qn, WDBX_OK;
   if (name && !strcmp(name, "last_batch_repaired")) return *value = ix->last_batch_repaired ? 1 : 0, WDBX_OK;
-  if (name && !strcmp(name, "last_batch_masked")) return *value = ix->last_batch_masked ? 1 : 0, WDBX_OK;
+  if (name && !strcmp(name, "last_batch_masked")) return *value = ix->last_batch_masked, WDBX_OK;
+  // (the last tile call with a mask per query: its classes and tile blocks; 0 after any other call)
+  if (name && !strcmp(name, "last_batch_mask_classes")) return *value = ix->last_batch_masked == 2 ? (int64_t)ix->last_batch_classes : 0, WDBX_OK;
+  if (name && !strcmp(name, "last_batch_blocks")) return *value = ix->last_batch_masked == 2 ? (int64_t)ix->last_batch_blocks : 0, WDBX_OK;
   if (name && !strcmp(name, "last_batch_allowed_rows")) return *value = (int64_t)ix->last_batch_allowed, WDBX_OK;
   if (name && !strcmp(name, "group_bounds_active")) return *value = ix->group_bounds ? 1 : 0, WDBX_OK;
   if (name && !strcmp(name, "exchanges")) return *value = (int64_t)ix->exchanges, WDBX_OK;

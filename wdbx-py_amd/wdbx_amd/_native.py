@@ -61,6 +61,8 @@ SIGNATURES = {
                                            _f32p]),
     "wdbx_index_search_masked_n": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
                                              _i64p, _f32p]),
+    "wdbx_index_search_multimask": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.POINTER(C.c_uint32)),
+                                              _u64p, C.c_int, C.POINTER(C.c_int32), _i64p, _f32p]),
     "wdbx_index_search_rows": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _u64p, C.c_uint64, _i64p, _f32p]),
     "wdbx_index_range_search": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
                                           C.c_uint64, _u64p, _i64p, _f32p]),
@@ -165,6 +167,9 @@ def _as_f32(a, shape_last: int) -> np.ndarray:
     if arr.ndim != 2 or arr.shape[1] != shape_last:
         raise ValueError(f"expected rows of length {shape_last}, got array of shape {arr.shape}")
     return arr
+
+
+MAX_CALL_MASKS = 64  # WDBX_MAX_CALL_MASKS: row masks one wdbx_index_search_multimask call takes
 
 
 def pack_row_mask(allowed: np.ndarray) -> np.ndarray:
@@ -308,6 +313,29 @@ class NativeIndex:
             _check(self._lib.wdbx_index_search_masked_n(self._h, q.ctypes.data_as(_f32p), nq, int(k),
                                                         int(normalize_queries), m.ctypes.data_as(C.POINTER(C.c_uint32)), m.size,
                                                         idx.ctypes.data_as(_i64p), score.ctypes.data_as(_f32p)))
+        return idx, score
+
+    def search_multimask(self, queries, k: int, masks, query_mask,
+                         normalize_queries: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """One row mask PER QUERY in one batched call: ``masks`` is a list of uint32 word arrays (:func:`pack_row_mask`),
+        ``query_mask[i]`` the index of query i's mask in it, or -1 for every row.  Results in the order of ``queries``,
+        each the exact top-``k`` of the rows its mask allows -- one pass over the int8 tiles for all masks together when
+        they are what a masked batch would run (``get_option("last_batch_masked") == 2``), the per-mask calls otherwise."""
+        q = _as_f32(queries, self.dim)
+        nq = q.shape[0]
+        words = [np.ascontiguousarray(m, dtype=np.uint32).reshape(-1) for m in masks]
+        which = np.ascontiguousarray(query_mask, dtype=np.int32).reshape(-1)
+        if which.size != nq:
+            raise ValueError(f"query_mask has {which.size} entries for {nq} queries")
+        u32p = C.POINTER(C.c_uint32)
+        ptrs = (u32p * max(len(words), 1))(*[m.ctypes.data_as(u32p) for m in words])
+        counts = np.array([m.size for m in words], dtype=np.uint64)
+        idx = np.empty((nq, int(k)), np.int64)
+        score = np.empty((nq, int(k)), np.float32)
+        # (lengths, mask numbers and k are checked by the library, the lengths under the handle's lock)
+        _check(self._lib.wdbx_index_search_multimask(self._h, q.ctypes.data_as(_f32p), nq, int(k), int(normalize_queries), ptrs,
+                                                     counts.ctypes.data_as(_u64p), len(words), which.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                     idx.ctypes.data_as(_i64p), score.ctypes.data_as(_f32p)))
         return idx, score
 
     def search_rows(self, queries, k: int, row_ids, normalize_queries: bool = False) -> Tuple[np.ndarray, np.ndarray]:

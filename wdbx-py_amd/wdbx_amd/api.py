@@ -23,7 +23,7 @@ from typing import Any, Dict, List, Optional
 _FIELDS = ("query_vector", "limit", "threshold", "filter_metadata")
 
 
-def _parse_common(payload: Dict[str, Any]):
+def _parse_common(payload: Dict[str, Any], filter_list: bool = False):
     if not isinstance(payload, dict):
         raise ValueError("request body must be an object")
     limit = payload.get("limit", 10)
@@ -35,7 +35,10 @@ def _parse_common(payload: Dict[str, Any]):
         raise ValueError("limit must be an integer")
     if isinstance(threshold, bool) or not isinstance(threshold, (int, float)):
         raise ValueError("threshold must be a number")
-    if flt is not None and not isinstance(flt, dict):
+    if filter_list and isinstance(flt, list):  # the batch form: one filter (an object or null) per query
+        if not all(f is None or isinstance(f, dict) for f in flt):
+            raise ValueError("filter_metadata must be an object, or a list of objects and nulls")
+    elif flt is not None and not isinstance(flt, dict):
         raise ValueError("filter_metadata must be an object")
     return limit, float(threshold), flt
 
@@ -64,13 +67,16 @@ async def search_batch_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]
     """Batch form (extension): body ``{"query_vectors": [[...], ...], "limit", "threshold", "filter_metadata",
     "prefilter"}`` -> ``{"results": [<one search_endpoint result list per query>]}``.  One batched matrix-core pass per
     shard.  ``prefilter`` (true / false; absent or null = the store's ``FILTER_PUSHDOWN``): push the metadata filter down
-    into that pass, so every query returns a full ``limit`` whenever enough rows match."""
+    into that pass, so every query returns a full ``limit`` whenever enough rows match.  ``filter_metadata`` may be a LIST
+    with one filter (an object or null) per query; any other length is refused."""
     import asyncio
 
-    limit, threshold, flt = _parse_common(payload)
+    limit, threshold, flt = _parse_common(payload, filter_list=True)
     if "query_vectors" not in payload or not isinstance(payload["query_vectors"], (list, tuple)):
         raise ValueError("query_vectors is required and must be a list of vectors")
     queries = [_vector(v, f"query_vectors[{i}]") for i, v in enumerate(payload["query_vectors"])]
+    if isinstance(flt, list) and len(flt) != len(queries):
+        raise ValueError(f"filter_metadata lists {len(flt)} filters for {len(queries)} queries")
     if not queries:
         return {"results": []}
     loop = asyncio.get_running_loop()

@@ -80,6 +80,9 @@ class WDBXConfig:
         # among listed rows) instead of a masked pass over the shard; 0 = off
         "FILTER_GATHER_MAX_ROWS": 0,
         "ASYNC_COALESCE": True,
+        # search_async callers that push down DIFFERENT filters with one limit share one call per shard with a row mask per
+        # query (wdbx_index_search_multimask) instead of one call per filter; off until a measurement recommends it
+        "ASYNC_COALESCE_FILTERS": False,
     }
 
     def __init__(self, config_dict: Optional[Dict[str, Any]] = None, config_path: Optional[str] = None):

@@ -133,6 +133,7 @@ class HipFlatIndex(VectorIndex):
     """Exact flat index resident in one MI355X's HBM (one shard)."""
 
     _warned_no_cpu_path = False
+    supports_row_masks = True  # search_batch(row_masks=, mask_of_query=): one row mask per query in one call
 
     def __init__(self, vector_dim: int, index_path: Path, use_gpu: bool = False, config: Any = None,
                  device_id: int = 0):
@@ -643,16 +644,20 @@ class HipFlatIndex(VectorIndex):
                 allowed[row] = True
         return _native.pack_row_mask(allowed)
 
-    def search_batch(self, queries: np.ndarray, limit: int = 10,
-                     row_mask: Optional[np.ndarray] = None) -> List[List[Tuple[str, float]]]:
+    def search_batch(self, queries: np.ndarray, limit: int = 10, row_mask: Optional[np.ndarray] = None,
+                     row_masks=None, mask_of_query=None) -> List[List[Tuple[str, float]]]:
         """Extension: many queries in one call.  ``row_mask`` as in ``search``, one for the whole batch: with
-        enough queries the library runs ONE masked pass over the int8 tiles instead of a masked scan per query."""
-        raw = self.search_batch_raw(queries, limit, row_mask=row_mask)
+        enough queries the library runs ONE masked pass over the int8 tiles instead of a masked scan per query.
+        ``row_masks=[...]`` with ``mask_of_query=[...]`` instead: one mask PER QUERY -- ``mask_of_query[i]`` is the index of
+        query i's mask in ``row_masks``, or -1 for every row -- still one pass for all of them
+        (``wdbx_index_search_multimask``)."""
+        raw = self.search_batch_raw(queries, limit, row_mask=row_mask, row_masks=row_masks, mask_of_query=mask_of_query)
         if raw is None:
             return [[] for _ in range(len(queries))]
         return [self._map(i, s) for i, s in zip(*raw)]
 
-    def search_batch_raw(self, queries: np.ndarray, limit: int = 10, row_mask: Optional[np.ndarray] = None):
+    def search_batch_raw(self, queries: np.ndarray, limit: int = 10, row_mask: Optional[np.ndarray] = None,
+                         row_masks=None, mask_of_query=None):
         """``search_batch`` without the id mapping: (rows int64[nq, k], scores f32[nq, k]) or None for "no results" (empty
         index, swallowed backend error).  The coalescing front of ``VectorStore`` hands each waiting caller ITS row of
         these, and the caller maps ids and merges on its own thread while the next batch is already on the GPU."""
@@ -664,10 +669,16 @@ class HipFlatIndex(VectorIndex):
         actual_limit = min(int(limit), self.next_index, _native.MAX_K)
         if actual_limit <= 0:
             return None
+        if row_masks is not None:
+            if row_mask is not None or mask_of_query is None or len(mask_of_query) != queries.shape[0]:
+                raise ValueError("row_masks needs mask_of_query with one entry per query, and no row_mask")
         if isinstance(row_mask, RowList):
             return self.search_rows_raw(queries, actual_limit, row_mask.rows)
         try:
             q = np.stack([self._prepare(r) for r in queries])
+            if row_masks is not None:
+                words = [m if m.dtype == np.uint32 else _native.pack_row_mask(m) for m in row_masks]
+                return self._native.search_multimask(q, actual_limit, words, mask_of_query)
             if row_mask is None:
                 return self._native.search(q, actual_limit)
             words = row_mask if row_mask.dtype == np.uint32 else _native.pack_row_mask(row_mask)

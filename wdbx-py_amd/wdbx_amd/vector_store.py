@@ -747,7 +747,9 @@ class VectorStore:
         shard is still asked for each query's own top-``limit``; results are the exact ones
         (config ``ASYNC_COALESCE=False`` restores one call per query).  ``prefilter`` / FILTER_PUSHDOWN as in
         ``search``: waiting callers that push down the SAME filter (the same ``_mask_cache`` key) share one masked batched
-        call -- one masked matrix-core pass per shard; callers with different filters are served in separate calls."""
+        call -- one masked matrix-core pass per shard; callers with different filters are served in separate calls, unless
+        config ``ASYNC_COALESCE_FILTERS`` (default False) is on: then all waiting push-down callers with equal ``limit`` go in
+        ONE call per shard with a row mask per query (``wdbx_index_search_multimask``)."""
         query = np.array(query_vector, dtype=np.float32)
         if query.shape != (self.vector_dim,):
             raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {query.shape}")
@@ -770,15 +772,43 @@ class VectorStore:
         nomask = [None] * len(self.indices)
         while self._pending:
             taken, self._pending = self._pending, []
+            jobs = []
+            if self.config.get("ASYNC_COALESCE_FILTERS", False) and all(
+                    getattr(ix, "supports_row_masks", False) for ix in self.indices):
+                # push-down callers with equal limit and DIFFERENT filters: one call per shard with a mask per query
+                by_limit: Dict[int, List[Any]] = {}
+                rest = []
+                for b in taken:
+                    (rest if b[5] is None else by_limit.setdefault(b[1], [])).append(b)
+                for group in by_limit.values():
+                    if len({b[5] for b in group}) > 1:
+                        jobs.append(self._drain_filters(loop, [b[:5] for b in group]))
+                    else:
+                        rest.extend(group)
+                taken = rest
             # callers that push down the same filter share one masked call; the others (no mask) share the unmasked one
             by_mask: Dict[Any, List[Any]] = {}
             for b in taken:
                 by_mask.setdefault(b[5], []).append(b)
             # (the groups run side by side, as such callers did when each went to the pool alone; a group's masks are taken
             # NOW, once, not when its first caller queued: the store may have changed since)
-            await asyncio.gather(*[
+            await asyncio.gather(*jobs, *[
                 self._drain_batch(loop, [b[:5] for b in batch], None if key is None else batch[0][3], nomask)
                 for key, batch in by_mask.items()])
+
+    async def _drain_filters(self, loop, batch) -> None:
+        """One coalesced batch of ``search_async`` callers that push down different filters with one ``limit``."""
+        try:
+            queries = np.stack([b[0] for b in batch])
+            per_shard = await loop.run_in_executor(self.thread_pool, self._per_shard_filters, queries, batch[0][1],
+                                                   [b[3] for b in batch])
+            for i, (_, limit, threshold, flt, fut) in enumerate(batch):
+                if not fut.done():
+                    fut.set_result(self._merge([res[i] for res in per_shard], limit, threshold, flt))
+        except Exception as e:  # deliver the failure to every waiter of this batch
+            for b in batch:
+                if not b[4].done():
+                    b[4].set_exception(e)
 
     async def _drain_batch(self, loop, batch, pushed_filter, nomask) -> None:
         """One coalesced batch of ``search_async`` callers; ``pushed_filter``: the filter they all push down, or None."""
@@ -819,16 +849,87 @@ class VectorStore:
                 if not b[4].done():
                     b[4].set_exception(e)
 
+    def _search_batch_filters(self, queries: np.ndarray, limit: int, threshold: float, filters,
+                              prefilter: Optional[bool]) -> List[List[Result]]:
+        """``search_batch`` with one filter (or None) PER QUERY.  With push-down every shard gets the distinct filters' row
+        masks and the per-query index in ONE call (one pass over the int8 tiles for all filters together); a shard for which
+        some filter travels as a ``RowList`` keeps one call per filter.  Without push-down every query's top-``limit`` is
+        post-filtered by its own filter.  Shard by shard: the shard group takes no per-query masks."""
+        if len(filters) != queries.shape[0]:
+            raise ValueError(f"filter_metadata lists {len(filters)} filters for {queries.shape[0]} queries")
+        if prefilter is None:
+            prefilter = bool(self.config.get("FILTER_PUSHDOWN", False))
+        self.last_search_path = "threads"
+        nq = queries.shape[0]
+        if not nq:
+            return []
+        if not (prefilter and any(filters)):
+            if len(self.indices) > 1:
+                per_shard = list(self._shard_pool.map(lambda ix: ix.search_batch(queries, limit=limit), self.indices))
+            else:
+                per_shard = [ix.search_batch(queries, limit=limit) for ix in self.indices]
+            return [self._merge([res[q] for res in per_shard], limit, threshold, filters[q] or None) for q in range(nq)]
+        per_shard = self._per_shard_filters(queries, limit, filters)
+        return [self._merge([res[q] for res in per_shard], limit, threshold, filters[q] or None) for q in range(nq)]
+
+    def _per_shard_filters(self, queries: np.ndarray, limit: int, filters) -> List[Any]:
+        """Every shard's top-``limit`` lists of a batch whose query i pushes down ``filters[i]`` (None: no filter)."""
+        nq = queries.shape[0]
+        # the distinct filters (by mask-cache key) and which of them every query pushes down (-1: none)
+        keys: Dict[str, int] = {}
+        distinct: List[Any] = []
+        which = []
+        for flt in filters:
+            if not flt:
+                which.append(-1)
+                continue
+            key = self._mask_key(flt)
+            if key not in keys:
+                keys[key] = len(distinct)
+                distinct.append(flt)
+            which.append(keys[key])
+        per_filter = [self._masks_for(flt, True, gather=True) for flt in distinct]  # [filter][shard]
+
+        cmax = _native.MAX_CALL_MASKS  # masks one library call takes: more distinct filters go in groups of that many
+
+        def one(s):
+            ix, masks = self.indices[s], [pf[s] for pf in per_filter]
+            if not any(isinstance(m, RowList) for m in masks) and len(masks) <= cmax:
+                return ix.search_batch(queries, limit=limit, row_masks=masks, mask_of_query=which)
+            out: List[Any] = [None] * nq
+            if not any(isinstance(m, RowList) for m in masks):
+                # (the queries without a filter travel with the first group)
+                for c0 in range(0, len(masks), cmax):
+                    members = [q for q in range(nq) if c0 <= which[q] < c0 + cmax or (c0 == 0 and which[q] < 0)]
+                    res = ix.search_batch(queries[members], limit=limit, row_masks=masks[c0:c0 + cmax],
+                                          mask_of_query=[which[q] - c0 if which[q] >= 0 else -1 for q in members])
+                    for q, r in zip(members, res):
+                        out[q] = r
+                return out
+            # (a filter that travels as its rows: one call per filter, as before)
+            for c in sorted(set(which)):
+                members = [q for q in range(nq) if which[q] == c]
+                res = ix.search_batch(queries[members], limit=limit, row_mask=None if c < 0 else masks[c])
+                for q, r in zip(members, res):
+                    out[q] = r
+            return out
+        shards = range(len(self.indices))
+        return list(self._shard_pool.map(one, shards)) if len(self.indices) > 1 else [one(0)]
+
     def search_batch(self, queries, limit: int = 10, threshold: float = 0.0,
-                     filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None) -> List[List[Result]]:
+                     filter_metadata=None, prefilter: Optional[bool] = None) -> List[List[Result]]:
         """Extension: one corpus pass per shard for a whole query batch -- through the shard group when there is
         one (every shard runs its matrix-core pass, or per-query scans for a few queries, inside ONE library call, the
         lists are exchanged and merged on the device), else shard by shard on the shard pool.  ``prefilter`` / FILTER_PUSHDOWN
         as in ``search``: the filter's row masks travel with the call (one MASKED matrix-core pass per shard), so every query
-        returns a full ``limit`` whenever enough rows match; the default post-filters the top-``limit`` as before."""
+        returns a full ``limit`` whenever enough rows match; the default post-filters the top-``limit`` as before.
+        ``filter_metadata`` may be a LIST holding one filter or ``None`` per query (any other length raises ``ValueError``):
+        with push-down every shard still makes one call, with the distinct filters' masks and the per-query index."""
         queries = np.asarray(queries, dtype=np.float32)
         if queries.ndim != 2 or queries.shape[1] != self.vector_dim:
             raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {queries.shape}")
+        if isinstance(filter_metadata, (list, tuple)):
+            return self._search_batch_filters(queries, int(limit), threshold, list(filter_metadata), prefilter)
         masks = self._masks_for(filter_metadata, prefilter, gather=True)
         pushed = any(m is not None for m in masks)
         if queries.shape[0] and not self._has_lists(masks):

@@ -115,10 +115,10 @@ class WDBX:
                                                     filter_metadata=filter_metadata)
 
     def vector_search_batch(self, query_vectors, limit: int = 10, threshold: float = 0.0,
-                            filter_metadata: Optional[Dict[str, Any]] = None,
-                            prefilter: Optional[bool] = None) -> List[List[Result]]:
+                            filter_metadata=None, prefilter: Optional[bool] = None) -> List[List[Result]]:
         """Extension: several queries at once (the reference is single-query).  ``prefilter`` as in
-        ``vector_search``: the metadata filter is pushed down into the batched pass."""
+        ``vector_search``: the metadata filter is pushed down into the batched pass.  ``filter_metadata``: one filter for
+        the batch, or a LIST with one filter or ``None`` per query (``VectorStore.search_batch``)."""
         for q in query_vectors:
             self._check_dim(q)
         return self.vector_store.search_batch(query_vectors, limit=limit, threshold=threshold,
