@@ -177,6 +177,32 @@ int wdbx_index_search_multimask(wdbx_index* idx, const float* queries, int nq, i
 int wdbx_index_search_rows(wdbx_index* idx, const float* queries, int nq, int k, int normalize_queries,
                            const uint64_t* row_ids, uint64_t n_ids, int64_t* out_idx, float* out_score);
 
+/* ---- search among listed rows, one row list PER QUERY in one batched call ------ */
+/* What wdbx_index_search_rows answers for one list, for a batch whose queries each name their own list (a rerank stage's
+ * candidates, a selective filter per tenant): query i is ranked among the rows of list query_list[i].  The lists come back to
+ * back in list_rows with list_offsets[l] .. list_offsets[l + 1] bounding list l.  Blocking, host buffers.
+ *   Results in the caller's query order; format, order, -1 / 0 unused slots and NaN handling as wdbx_index_search_rows.
+ *   Query i's ids and scores are bit-identical to wdbx_index_search_rows called with that query alone and its list.
+ *   Several queries may name one list (they share every fetch of its rows, 8 queries at a time); a list may be empty (every
+ *   slot of its queries -1); a list no query names is still checked.
+ *   WDBX_E_INVALID: a list that is not strictly increasing or reaches the row count (checked under the handle's lock; the
+ *   message names the list and the entry), list_offsets[0] != 0 or decreasing offsets, a query_list entry outside
+ *   [0, n_lists) (there is no "-1 = every row": a whole-shard query is not a list), n_lists < 1, nq < 1, k outside
+ *   [1, WDBX_MAX_K], a null buffer.  A refused call leaves the handle usable.
+ *   Routes: the queries of lists of at most option "rows_keys_max" rows run in rounds of up to 256 queries, each round one
+ *   scoring launch (one workgroup per chunk of 256 listed rows and block of queries; counted as a scan launch in
+ *   wdbx_index_profile_read) and one merge launch; the queries of a longer list -- all of them with rows_keys_max = 0 -- go
+ *   through wdbx_index_search_rows' own routes, list by list, under the lock the call already holds.  Exact either way.
+ *   get_option: "last_lists_path" 0 = nothing launched, 1 = the batched pass only, 2 = both, 3 = list by list only;
+ *   "last_lists_items" the work items of the call; "last_lists_rounds" its rounds.
+ *   The call holds the handle's mutex to its end.  Nothing of a call's lists stays valid in the handle. */
+int wdbx_index_search_row_lists(wdbx_index* idx, const float* queries, int nq, int k, int normalize_queries,
+                                const uint64_t* list_rows,     /* every list back to back */
+                                const uint64_t* list_offsets,  /* [n_lists + 1], list_offsets[0] == 0, non-decreasing */
+                                int n_lists,
+                                const int32_t* query_list,     /* [nq]: which list query i is ranked in */
+                                int64_t* out_idx, float* out_score);
+
 /* ---- range search: every row within a similarity, no k ----------------------- */
 /* every row whose score reaches thresholds[q] (cosine/IP: score >= t; L2: squared distance <= t), exact fp32,
  * per query sorted like wdbx_index_search; replaces faiss' IndexFlat range_search, which the reference never reaches

@@ -164,6 +164,12 @@ struct wdbx_index {
   u64* d_sub_keys = nullptr;
   size_t sub_ids_bytes = 0, sub_keys_bytes = 0;
   int last_rows_path = 0;      // 0 nothing launched (empty list), 1 keys + merge, 2 lists + merge, 3 keys + radix select
+  // one row list per query (wdbx_index_search_row_lists): the call's work items, then its slots' list lengths; the lists' rows
+  // and the round's keys live in d_sub_ids / d_sub_keys
+  char* d_rl = nullptr;
+  size_t rl_bytes = 0;
+  int last_lists_path = 0;     // 0 nothing launched, 1 the batched pass only, 2 both, 3 list by list only
+  int64_t last_lists_items = 0, last_lists_rounds = 0;
   // profiling
   bool profile = false;
   EventPool scan_ev, merge_ev, gemm_ev, sample_ev;

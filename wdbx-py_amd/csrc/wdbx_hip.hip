@@ -28,6 +28,8 @@
 //                           scores of the u8 selection's candidates); wave-aggregated appends, no k
 //   kernels_subset.h        subset_kernel: exact scores of LISTED rows (wdbx_index_search_rows), a block of queries per fetched
 //                           row, per-workgroup top-k lists or a key per listed row
+//   kernels_rowlists.h      rowlists_kernel: the same scores for a call with one row list PER QUERY (wdbx_index_search_row_lists),
+//                           one workgroup per (chunk of a list, block of its queries) work item of host_rowlists.h
 //   host_multimask.h        a call with one row mask per query: the placement of its queries in the int8 tiles' query blocks
 //   host_index.h            the handle, kernel choice, and the enqueue functions of every search path
 //   host_group.h            the in-process shard group: per-shard host threads, exchange (RCCL all-gather / device copies), merge
@@ -68,6 +70,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_range.h"  // (device-free as well: CSR offsets, per-query sort and decoding of a range search's keys)
 #include "host_subset.h"  // (device-free as well: row-list validation, route and grid sizing of a search among listed rows)
 #include "host_multimask.h"  // (device-free as well: where the queries of a call with a mask per query sit in the tile blocks)
+#include "host_rowlists.h"  // (device-free as well: slots, rounds, query blocks and work items of a call with a row list per query)
 
 #define HIP_TRY(expr)                                                                        \
   do {                                                                                       \
@@ -98,6 +101,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "kernels_aux.h"
 #include "kernels_range.h"
 #include "kernels_subset.h"
+#include "kernels_rowlists.h"
 #include "host_index.h"
 #include "host_group.h"
 
@@ -116,7 +120,7 @@ static uint64_t device_bytes_resident(const wdbx_index* ix) {
   b += ix->qb8_bytes + ix->qpar_bytes + ix->pairs_bytes + ix->pair_count_bytes + ix->cnmax_bytes;
   b += ix->rcand_bytes + ix->rkeys_bytes + ix->rcnt_bytes + ix->rthr_bytes;
   b += ix->rows6_bytes + ix->count6_bytes;
-  b += ix->sub_ids_bytes + ix->sub_keys_bytes + ix->mm_bytes;
+  b += ix->sub_ids_bytes + ix->sub_keys_bytes + ix->mm_bytes + ix->rl_bytes;
   return b;
 }
 
@@ -194,7 +198,7 @@ void wdbx_index_destroy(wdbx_index* ix) try {
                     ix->d_state, ix->d_cn, ix->d_cnmax, ix->d_qb16, ix->d_rows16, ix->d_rows8, ix->d_scale8, ix->d_selsrc,
                     ix->d_gmax, ix->d_qn, ix->d_rows8g, ix->d_groups8, ix->d_gbad8, ix->d_gref8, ix->d_over_list, ix->d_qb8,
                     ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr, ix->d_rows6, ix->d_count6,
-                    ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys, ix->d_mm};
+                    ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys, ix->d_mm, ix->d_rl};
     for (void* p : bufs)
       if (p) (void)hipFree(p);
     if (ix->h_stage) (void)hipHostFree(ix->h_stage);
@@ -846,14 +850,16 @@ int wdbx_index_search_multimask(wdbx_index* ix, const float* queries, int nq, in
 // and narrowed under the lock (row numbers are checked against the row count a concurrent add cannot change meanwhile), goes
 // to the device once, and the queries are served in rounds (subset_plan): subset_kernel, then per round one merge launch
 // (lists or keys) or per query the radix-select chain.  The scoring launches are bracketed as scan launches.
+// held: the caller already holds the handle's mutex and keeps it (wdbx_index_search_row_lists' list-by-list route), as in search_host.
 static int search_rows_host(wdbx_index* ix, const float* queries, int nq, int k, int normalize_queries, const uint64_t* row_ids,
-                            uint64_t n_ids, int64_t* out_idx, float* out_score) {
+                            uint64_t n_ids, int64_t* out_idx, float* out_score, bool held = false) {
   if (!ix) return fail(WDBX_E_INVALID, "null handle");
   if (nq < 1) return fail(WDBX_E_INVALID, "nq=%d", nq);
   if (!queries || !out_idx || !out_score) return fail(WDBX_E_INVALID, "null buffer");
   if (n_ids && !row_ids) return fail(WDBX_E_INVALID, "row_ids is null");
   if (k < 1 || k > WDBX_MAX_K) return fail(WDBX_E_INVALID, "k=%d outside [1, %d]", k, WDBX_MAX_K);
-  std::lock_guard<std::mutex> lk(ix->mu);
+  std::unique_lock<std::mutex> lk;
+  if (!held) lk = std::unique_lock<std::mutex>(ix->mu);
   if (ix->n >= 0xFFFFFF00ull) return fail(WDBX_E_INVALID, "shard holds too many rows for 32-bit row keys");
   if (n_ids > ix->n) return fail(WDBX_E_INVALID, "%llu listed rows of %llu stored", (u64)n_ids, (u64)ix->n);
   std::vector<uint32_t> ids32((size_t)n_ids);
@@ -973,6 +979,153 @@ static int search_rows_host(wdbx_index* ix, const float* queries, int nq, int k,
 int wdbx_index_search_rows(wdbx_index* ix, const float* queries, int nq, int k, int normalize_queries, const uint64_t* row_ids,
                            uint64_t n_ids, int64_t* out_idx, float* out_score) try {
   return search_rows_host(ix, queries, nq, k, normalize_queries, row_ids, n_ids, out_idx, out_score);
+} WDBX_CATCH
+
+// ---- one row list PER QUERY in one batched call (host_rowlists.h, kernels_rowlists.h) --------
+// The whole call holds the handle's mutex.  Under it: the CSR pair and every list are checked, the plan is made, the pass
+// lists' rows, the work items, the slots' list lengths and the queries (in slot order) go to the device once, and every round
+// is one rowlists_kernel launch (bracketed as a scan launch) and one merge_kernel launch over the slots' keys as unsorted
+// candidates with the slot's list length as its count.  One download, then the results go back to the caller's order.  The
+// queries of lists beyond rows_keys_max then run list by list through search_rows_host under the same lock.
+int wdbx_index_search_row_lists(wdbx_index* ix, const float* queries, int nq, int k, int normalize_queries, const uint64_t* list_rows,
+                                const uint64_t* list_offsets, int n_lists, const int32_t* query_list, int64_t* out_idx,
+                                float* out_score) try {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  if (nq < 1) return fail(WDBX_E_INVALID, "nq=%d", nq);
+  if (n_lists < 1) return fail(WDBX_E_INVALID, "n_lists=%d: every query needs a list", n_lists);
+  if (!queries || !out_idx || !out_score || !list_offsets || !query_list) return fail(WDBX_E_INVALID, "null buffer");
+  if (k < 1 || k > WDBX_MAX_K) return fail(WDBX_E_INVALID, "k=%d outside [1, %d]", k, WDBX_MAX_K);
+  int64_t where = -1;
+  switch (rowlists_check(list_offsets, n_lists, query_list, nq, &where)) {
+    case ROWLISTS_OK: break;
+    case ROWLISTS_BAD_OFFSET:
+      return where == 0 ? fail(WDBX_E_INVALID, "list_offsets[0]=%llu, not 0", (u64)list_offsets[0])
+                        : fail(WDBX_E_INVALID, "list_offsets[%lld]=%llu below list_offsets[%lld]=%llu", (long long)where,
+                               (u64)list_offsets[where], (long long)where - 1, (u64)list_offsets[where - 1]);
+    case ROWLISTS_BAD_QUERY:
+      return fail(WDBX_E_INVALID, "query_list[%lld]=%d outside [0, %d)", (long long)where, (int)query_list[where], n_lists);
+    default: return fail(WDBX_E_INVALID, "bad list arguments");
+  }
+  if (list_offsets[n_lists] && !list_rows) return fail(WDBX_E_INVALID, "list_rows is null");
+  std::unique_lock<std::mutex> lk(ix->mu);
+  if (ix->n >= 0xFFFFFF00ull) return fail(WDBX_E_INVALID, "shard holds too many rows for 32-bit row keys");
+  RowListsPlan plan;
+  if (!rowlists_plan(list_offsets, n_lists, query_list, nq, ix->opt_rows_keys_max, &plan))
+    return fail(WDBX_E_INVALID, "%llu listed rows in one call: at most 2^32 - 1", (u64)plan.pass_ids);
+  std::vector<uint32_t> ids32((size_t)plan.pass_ids);
+  int bad_list = -1;
+  uint64_t bad_entry = 0;
+  if (!rowlists_validate(list_rows, list_offsets, n_lists, ix->n, &plan, ids32.data(), &bad_list, &bad_entry))
+    return fail(WDBX_E_INVALID, "list %d must hold strictly increasing row numbers below %llu (entry %llu)", bad_list, (u64)ix->n,
+                (u64)bad_entry);
+  ix->last_lists_path = plan.path();
+  ix->last_lists_items = (int64_t)plan.items.size();
+  ix->last_lists_rounds = plan.items.empty() ? 0 : (int64_t)plan.rounds.size();
+  const size_t slots = plan.slot_query.size();
+  if (plan.items.empty()) {  // (only empty lists on the pass: every slot empty, as wdbx_index_search_rows leaves them)
+    for (size_t s = 0; s < slots; ++s)
+      for (int i = 0; i < k; ++i) {
+        out_idx[(size_t)plan.slot_query[s] * k + i] = -1;
+        out_score[(size_t)plan.slot_query[s] * k + i] = 0.0f;
+      }
+  } else {
+    DeviceGuard g(ix->device);
+    int rc;
+    const size_t elems = slots * (size_t)k, q_bytes = slots * ix->pitch * sizeof(float);
+    if ((rc = grow((void**)&ix->d_q, &ix->q_bytes, q_bytes))) return rc;
+    if (elems > ix->out_elems) {
+      if (ix->d_oidx) HIP_TRY(hipFree(ix->d_oidx));
+      if (ix->d_oscore) HIP_TRY(hipFree(ix->d_oscore));
+      ix->d_oidx = nullptr;
+      ix->d_oscore = nullptr;
+      ix->out_elems = 0;
+      HIP_TRY(hipMalloc((void**)&ix->d_oidx, elems * sizeof(int64_t)));
+      HIP_TRY(hipMalloc((void**)&ix->d_oscore, elems * sizeof(float)));
+      ix->out_elems = elems;
+    }
+    size_t key_u64 = 0;
+    for (const RowListsRound& r : plan.rounds) key_u64 = std::max(key_u64, (size_t)r.slots * (size_t)r.stride);
+    const size_t items_bytes = (plan.items.size() * sizeof(RowListsItem) + 255) / 256 * 256;
+    if ((rc = grow((void**)&ix->d_sub_ids, &ix->sub_ids_bytes, (size_t)plan.pass_ids * sizeof(uint32_t)))) return rc;
+    if ((rc = grow((void**)&ix->d_sub_keys, &ix->sub_keys_bytes, key_u64 * sizeof(u64)))) return rc;
+    if ((rc = grow((void**)&ix->d_rl, &ix->rl_bytes, items_bytes + slots * sizeof(uint32_t)))) return rc;
+    const RowListsItem* const d_items = (const RowListsItem*)ix->d_rl;
+    const uint32_t* const d_len = (const uint32_t*)(ix->d_rl + items_bytes);
+    // the queries in slot order, padded to the row pitch (host side: one upload whatever the order)
+    std::vector<float> hq(slots * (size_t)ix->pitch, 0.0f);
+    for (size_t s = 0; s < slots; ++s)
+      memcpy(&hq[s * ix->pitch], queries + (size_t)plan.slot_query[s] * ix->dim, (size_t)ix->dim * sizeof(float));
+    HIP_TRY(hipMemcpyAsync(ix->d_q, hq.data(), q_bytes, hipMemcpyHostToDevice, ix->stream));
+    HIP_TRY(hipMemcpyAsync(ix->d_sub_ids, ids32.data(), (size_t)plan.pass_ids * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+    HIP_TRY(hipMemcpyAsync(ix->d_rl, plan.items.data(), plan.items.size() * sizeof(RowListsItem), hipMemcpyHostToDevice, ix->stream));
+    HIP_TRY(hipMemcpyAsync(ix->d_rl + items_bytes, plan.slot_len.data(), slots * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+    if (normalize_queries && ix->metric == WDBX_METRIC_COSINE && (rc = launch_normalize(ix, ix->d_q, (uint64_t)slots))) return rc;
+    const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
+    const rowlists_fn fn = pick_rowlists(ix->metric, plan.qb, pitch4);
+    if (!fn) return fail(WDBX_E_STATE, "no row-lists instance with %d queries per block", plan.qb);
+    for (const RowListsRound& r : plan.rounds) {
+      if (r.items) {  // (a round of empty lists only scores nothing; the ranking below still empties its slots)
+        if (r.items > 0x7FFFFFFFull) return fail(WDBX_E_INVALID, "%zu work items in one round", r.items);
+        RowListsArgs a = {};
+        a.rows = (const f4*)ix->d_rows;
+        a.queries = (const f4*)(ix->d_q + (size_t)r.slot0 * ix->pitch);
+        a.ids = ix->d_sub_ids;
+        a.items = d_items + r.item0;
+        a.keys = ix->d_sub_keys;
+        a.stride = r.stride;
+        a.pitch4 = pitch4;
+        if ((rc = record(ix->scan_ev, ix->profile, ix->stream, true))) return rc;
+        hipLaunchKernelGGL(fn, dim3((uint32_t)r.items), dim3(256), 0, ix->stream, a);
+        HIP_TRY(hipGetLastError());
+        if ((rc = record(ix->scan_ev, ix->profile, ix->stream, false))) return rc;
+      }
+      MergeArgs m = {};
+      m.k = k;
+      m.metric = ix->metric;
+      m.in = ix->d_sub_keys;
+      m.q_stride = r.stride;
+      m.i_stride = 0;
+      m.p_stride = 1;
+      m.P = (uint32_t)r.stride;
+      m.P_dev = d_len + r.slot0;
+      m.list_len = 1;
+      m.out_idx = ix->d_oidx + (size_t)r.slot0 * k;
+      m.out_score = ix->d_oscore + (size_t)r.slot0 * k;
+      if ((rc = launch_merge(ix, m, (int)r.slots))) return rc;
+    }
+    std::vector<int64_t> h_idx(elems);
+    std::vector<float> h_score(elems);
+    HIP_TRY(hipMemcpyAsync(h_idx.data(), ix->d_oidx, elems * sizeof(int64_t), hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipMemcpyAsync(h_score.data(), ix->d_oscore, elems * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    for (size_t s = 0; s < slots; ++s) {
+      memcpy(out_idx + (size_t)plan.slot_query[s] * k, &h_idx[s * k], (size_t)k * sizeof(int64_t));
+      memcpy(out_score + (size_t)plan.slot_query[s] * k, &h_score[s * k], (size_t)k * sizeof(float));
+    }
+  }
+  // the longer lists, each with its queries in the caller's order, through the call that existed before; the lock stays held
+  std::vector<float> cq;
+  std::vector<int64_t> ci;
+  std::vector<float> cs;
+  std::vector<int> members;
+  for (const int32_t l : plan.fallback_lists) {
+    members.clear();
+    for (int q = 0; q < nq; ++q)
+      if (query_list[q] == l) members.push_back(q);
+    const size_t nm = members.size();
+    cq.resize(nm * (size_t)ix->dim);
+    ci.resize(nm * (size_t)k);
+    cs.resize(nm * (size_t)k);
+    for (size_t i = 0; i < nm; ++i) memcpy(&cq[i * ix->dim], queries + (size_t)members[i] * ix->dim, (size_t)ix->dim * sizeof(float));
+    const int rc = search_rows_host(ix, cq.data(), (int)nm, k, normalize_queries, list_rows + list_offsets[l],
+                                    list_offsets[l + 1] - list_offsets[l], ci.data(), cs.data(), true);
+    if (rc) return rc;
+    for (size_t i = 0; i < nm; ++i) {
+      memcpy(out_idx + (size_t)members[i] * k, &ci[i * k], (size_t)k * sizeof(int64_t));
+      memcpy(out_score + (size_t)members[i] * k, &cs[i * k], (size_t)k * sizeof(float));
+    }
+  }
+  return WDBX_OK;
 } WDBX_CATCH
 
 // ---- range search (range_u8_eligible, pick_range_scan: host_index.h) -------------------------------
@@ -1896,6 +2049,9 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "shadow6_bytes")) return *value = (int64_t)ix->rows6_bytes, WDBX_OK;
   if (name && !strcmp(name, "last_range_path")) return *value = ix->last_range_path, WDBX_OK;
   if (name && !strcmp(name, "last_rows_path")) return *value = ix->last_rows_path, WDBX_OK;
+  if (name && !strcmp(name, "last_lists_path")) return *value = ix->last_lists_path, WDBX_OK;
+  if (name && !strcmp(name, "last_lists_items")) return *value = ix->last_lists_items, WDBX_OK;
+  if (name && !strcmp(name, "last_lists_rounds")) return *value = ix->last_lists_rounds, WDBX_OK;
   if (name && !strcmp(name, "last_sample_qn")) return *value = ix->last_sample_qn, WDBX_OK;
   if (name && !strcmp(name, "last_batch_repaired")) return *value = ix->last_batch_repaired ? 1 : 0, WDBX_OK;
   if (name && !strcmp(name, "last_batch_masked")) return *value = ix->last_batch_masked, WDBX_OK;

@@ -64,6 +64,8 @@ SIGNATURES = {
     "wdbx_index_search_multimask": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.POINTER(C.c_uint32)),
                                               _u64p, C.c_int, C.POINTER(C.c_int32), _i64p, _f32p]),
     "wdbx_index_search_rows": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _u64p, C.c_uint64, _i64p, _f32p]),
+    "wdbx_index_search_row_lists": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _u64p, _u64p, C.c_int,
+                                              C.POINTER(C.c_int32), _i64p, _f32p]),
     "wdbx_index_range_search": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
                                           C.c_uint64, _u64p, _i64p, _f32p]),
     "wdbx_device_alloc": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -349,6 +351,31 @@ class NativeIndex:
         _check(self._lib.wdbx_index_search_rows(self._h, q.ctypes.data_as(_f32p), nq, int(k), int(normalize_queries),
                                                 ids.ctypes.data_as(_u64p), ids.size, idx.ctypes.data_as(_i64p),
                                                 score.ctypes.data_as(_f32p)))
+        return idx, score
+
+    def search_row_lists(self, queries, k: int, lists, query_list,
+                         normalize_queries: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """:meth:`search_rows` with one row list PER QUERY in one batched call: ``lists`` is a sequence of uint64 arrays
+        (each strictly increasing row numbers of this index, possibly empty), ``query_list[i]`` the index of query i's list
+        in it.  Results in the order of ``queries``, each bit-identical to ``search_rows(queries[i], k, lists[query_list[i]])``."""
+        q = _as_f32(queries, self.dim)
+        nq = q.shape[0]
+        arrays = [np.ascontiguousarray(r, dtype=np.uint64).reshape(-1) for r in lists]
+        which = np.ascontiguousarray(query_list, dtype=np.int32).reshape(-1)
+        if which.size != nq:
+            raise ValueError(f"query_list has {which.size} entries for {nq} queries")
+        offsets = np.zeros(len(arrays) + 1, dtype=np.uint64)
+        if arrays:
+            np.cumsum([a.size for a in arrays], out=offsets[1:])
+        rows = np.concatenate(arrays) if arrays else np.empty(0, np.uint64)
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        idx = np.empty((nq, int(k)), np.int64)
+        score = np.empty((nq, int(k)), np.float32)
+        # (the lists, the list numbers and k are checked by the library, the lists under the handle's lock)
+        _check(self._lib.wdbx_index_search_row_lists(self._h, q.ctypes.data_as(_f32p), nq, int(k), int(normalize_queries),
+                                                     rows.ctypes.data_as(_u64p), offsets.ctypes.data_as(_u64p), len(arrays),
+                                                     which.ctypes.data_as(C.POINTER(C.c_int32)), idx.ctypes.data_as(_i64p),
+                                                     score.ctypes.data_as(_f32p)))
         return idx, score
 
     def range_search(self, queries, thresholds, normalize_queries: bool = False,

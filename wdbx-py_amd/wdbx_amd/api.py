@@ -68,7 +68,9 @@ async def search_batch_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]
     "prefilter"}`` -> ``{"results": [<one search_endpoint result list per query>]}``.  One batched matrix-core pass per
     shard.  ``prefilter`` (true / false; absent or null = the store's ``FILTER_PUSHDOWN``): push the metadata filter down
     into that pass, so every query returns a full ``limit`` whenever enough rows match.  ``filter_metadata`` may be a LIST
-    with one filter (an object or null) per query; any other length is refused."""
+    with one filter (an object or null) per query; any other length is refused.  ``vector_id_lists`` (a list with one list
+    of vector ids per query; any other length is refused; not together with ``filter_metadata``): every query is ranked
+    among ITS listed vectors only (``vector_search_batch_among_each``), one call per shard for the whole batch."""
     import asyncio
 
     limit, threshold, flt = _parse_common(payload, filter_list=True)
@@ -77,9 +79,22 @@ async def search_batch_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]
     queries = [_vector(v, f"query_vectors[{i}]") for i, v in enumerate(payload["query_vectors"])]
     if isinstance(flt, list) and len(flt) != len(queries):
         raise ValueError(f"filter_metadata lists {len(flt)} filters for {len(queries)} queries")
+    id_lists = payload.get("vector_id_lists")
+    if id_lists is not None:
+        if not isinstance(id_lists, (list, tuple)) or not all(
+                isinstance(ids, (list, tuple)) and all(isinstance(i, str) for i in ids) for ids in id_lists):
+            raise ValueError("vector_id_lists must be a list of lists of vector ids")
+        if len(id_lists) != len(queries):
+            raise ValueError(f"vector_id_lists holds {len(id_lists)} lists for {len(queries)} queries")
+        if flt is not None:
+            raise ValueError("vector_id_lists and filter_metadata exclude each other")
     if not queries:
         return {"results": []}
     loop = asyncio.get_running_loop()
+    if id_lists is not None:
+        per_query = await loop.run_in_executor(None, lambda: wdbx.vector_search_batch_among_each(
+            queries, [list(ids) for ids in id_lists], limit, threshold))
+        return {"results": [_render(r)["results"] for r in per_query]}
     prefilter = payload.get("prefilter")
     if prefilter is not None and not isinstance(prefilter, bool):
         raise ValueError("prefilter must be true, false or null")

@@ -79,6 +79,10 @@ class WDBXConfig:
         # a pushed-down filter that matches at most this many rows of a shard is answered from those rows alone (the search
         # among listed rows) instead of a masked pass over the shard; 0 = off
         "FILTER_GATHER_MAX_ROWS": 0,
+        # a batch with a filter per query: the queries whose filter travels as its rows (FILTER_GATHER_MAX_ROWS) share ONE call
+        # per shard with a row list per query (wdbx_index_search_row_lists) instead of one call per filter; off until a
+        # measurement recommends it
+        "FILTER_GATHER_PER_QUERY": False,
         "ASYNC_COALESCE": True,
         # search_async callers that push down DIFFERENT filters with one limit share one call per shard with a row mask per
         # query (wdbx_index_search_multimask) instead of one call per filter; off until a measurement recommends it

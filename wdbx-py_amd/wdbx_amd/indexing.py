@@ -736,6 +736,57 @@ class HipFlatIndex(VectorIndex):
             return [[] for _ in range(len(queries))]
         return [self._map(i, s) for i, s in zip(*raw)]
 
+    # ---- the same with one list PER QUERY (wdbx_index_search_row_lists: one call for the whole batch) ----
+    supports_row_lists = True
+
+    def search_row_lists_raw(self, queries: np.ndarray, limit: int, lists, list_of_query):
+        """``search_rows_raw`` with one row list per query: ``lists`` is a sequence of strictly increasing row arrays (as
+        ``rows_of`` returns them; a list may be empty), ``list_of_query[i]`` the index of query i's list.  One library call:
+        (rows int64[nq, k], scores f32[nq, k]) in the order of ``queries`` -- a query with an empty list gets rows of -1 --
+        or None for "no results"."""
+        queries = np.asarray(queries, dtype=np.float32)
+        if queries.ndim != 2 or queries.shape[1] != self.vector_dim:
+            raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {queries.shape}")
+        if len(list_of_query) != queries.shape[0]:
+            raise ValueError("list_of_query needs one entry per query")
+        actual_limit = min(int(limit), _native.MAX_K)
+        if self.next_index == 0 or queries.shape[0] == 0 or actual_limit <= 0 or not any(len(r) for r in lists):
+            return None
+        try:
+            q = np.stack([self._prepare(r) for r in queries])
+            out = self._native.search_row_lists(q, actual_limit, lists, list_of_query)
+            self.rows_searches += 1
+            return out
+        except Exception as e:
+            logger.error("Error searching row lists of HIP index: %s", e)
+            if self.swallow_errors:
+                return None
+            raise
+
+    def search_batch_among_each(self, queries: np.ndarray, ids_per_query, limit: int = 10) -> List[List[Tuple[str, float]]]:
+        """``search_among`` for many queries, each over ITS OWN id list (``ids_per_query[i]``: any order, duplicates allowed,
+        unknown and removed ids ignored), in one library call.  Queries whose lists name the same rows share one list."""
+        if len(ids_per_query) != len(queries):
+            raise ValueError(f"ids_per_query has {len(ids_per_query)} lists for {len(queries)} queries")
+        try:
+            lists, which, seen = [], [], {}
+            for ids in ids_per_query:
+                rows = self.rows_of(ids)
+                key = rows.tobytes()
+                if key not in seen:
+                    seen[key] = len(lists)
+                    lists.append(rows)
+                which.append(seen[key])
+        except Exception as e:
+            logger.error("Error mapping ids of HIP index: %s", e)
+            if self.swallow_errors:
+                return [[] for _ in range(len(queries))]
+            raise
+        raw = self.search_row_lists_raw(queries, limit, lists, which)
+        if raw is None:
+            return [[] for _ in range(len(queries))]
+        return [self._map(i, s) for i, s in zip(*raw)]
+
     async def search_async(self, query_vector: np.ndarray, limit: int = 10) -> List[Tuple[str, float]]:
         loop = asyncio.get_event_loop()
         return await loop.run_in_executor(self.thread_pool, self.search, query_vector, limit)

@@ -853,7 +853,8 @@ class VectorStore:
                               prefilter: Optional[bool]) -> List[List[Result]]:
         """``search_batch`` with one filter (or None) PER QUERY.  With push-down every shard gets the distinct filters' row
         masks and the per-query index in ONE call (one pass over the int8 tiles for all filters together); a shard for which
-        some filter travels as a ``RowList`` keeps one call per filter.  Without push-down every query's top-``limit`` is
+        some filter travels as a ``RowList`` keeps one call per filter -- or, with config ``FILTER_GATHER_PER_QUERY``, sends those
+        queries in one call with a row list per query and the others in the call with a mask per query.  Without push-down every query's top-``limit`` is
         post-filtered by its own filter.  Shard by shard: the shard group takes no per-query masks."""
         if len(filters) != queries.shape[0]:
             raise ValueError(f"filter_metadata lists {len(filters)} filters for {queries.shape[0]} queries")
@@ -892,6 +893,21 @@ class VectorStore:
 
         cmax = _native.MAX_CALL_MASKS  # masks one library call takes: more distinct filters go in groups of that many
 
+        per_query = bool(self.config.get("FILTER_GATHER_PER_QUERY", False))
+
+        def masked(ix, members, masks, which):
+            """``members`` (queries of the batch) with row masks only: one call per group of at most cmax masks."""
+            if len(masks) <= cmax:
+                return ix.search_batch(queries[members], limit=limit, row_masks=masks, mask_of_query=which)
+            out: Dict[int, Any] = {}
+            # (the queries without a filter travel with the first group)
+            for c0 in range(0, len(masks), cmax):
+                part = [i for i, c in enumerate(which) if c0 <= c < c0 + cmax or (c0 == 0 and c < 0)]
+                res = ix.search_batch(queries[[members[i] for i in part]], limit=limit, row_masks=masks[c0:c0 + cmax],
+                                      mask_of_query=[which[i] - c0 if which[i] >= 0 else -1 for i in part])
+                out.update(zip(part, res))
+            return [out[i] for i in range(len(members))]
+
         def one(s):
             ix, masks = self.indices[s], [pf[s] for pf in per_filter]
             if not any(isinstance(m, RowList) for m in masks) and len(masks) <= cmax:
@@ -904,6 +920,28 @@ class VectorStore:
                     res = ix.search_batch(queries[members], limit=limit, row_masks=masks[c0:c0 + cmax],
                                           mask_of_query=[which[q] - c0 if which[q] >= 0 else -1 for q in members])
                     for q, r in zip(members, res):
+                        out[q] = r
+                return out
+            if per_query and getattr(ix, "supports_row_lists", False):
+                # FILTER_GATHER_PER_QUERY: the queries whose filter travels as its rows in ONE call with a list per query,
+                # the others (row masks, no filter) in the call with a mask per query; scattered back into query order
+                listed = [q for q in range(nq) if which[q] >= 0 and isinstance(masks[which[q]], RowList)]
+                used = sorted({which[q] for q in listed})
+                at = {c: i for i, c in enumerate(used)}
+                raw = ix.search_row_lists_raw(queries[listed], limit, [masks[c].rows for c in used],
+                                              [at[which[q]] for q in listed])
+                res = [[] for _ in listed] if raw is None else [ix._map(i, sc) for i, sc in zip(*raw)]
+                for q, r in zip(listed, res):
+                    out[q] = r
+                rest = [q for q in range(nq) if out[q] is None]
+                if rest:
+                    kept = [c for c, m in enumerate(masks) if not isinstance(m, RowList)]
+                    at = {c: i for i, c in enumerate(kept)}
+                    if any(which[q] >= 0 for q in rest):
+                        res = masked(ix, rest, [masks[c] for c in kept], [at[which[q]] if which[q] >= 0 else -1 for q in rest])
+                    else:
+                        res = ix.search_batch(queries[rest], limit=limit)
+                    for q, r in zip(rest, res):
                         out[q] = r
                 return out
             # (a filter that travels as its rows: one call per filter, as before)
@@ -977,6 +1015,31 @@ class VectorStore:
             return a[0].search_batch_among(queries, a[1], limit=limit)
         per_shard = list(self._shard_pool.map(one, work)) if len(work) > 1 else [one(work[0])]
         return [self._merge([res[q] for res in per_shard], limit, threshold, None) for q in range(queries.shape[0])]
+
+    def search_batch_among_each(self, queries, vector_id_lists, limit: int = 10, threshold: float = 0.0) -> List[List[Result]]:
+        """``search_batch_among`` with one id list PER QUERY (``vector_id_lists[i]`` is query i's; any other length raises
+        ``ValueError``): a rerank stage's candidates, a filter evaluated elsewhere per tenant.  Every query's ids are split
+        by shard, and every shard holding some answers ALL its queries in one library call with a row list per query
+        (``wdbx_index_search_row_lists``), on the shard pool; merged per query as ``search`` merges."""
+        queries = np.asarray(queries, dtype=np.float32)
+        if queries.ndim != 2 or queries.shape[1] != self.vector_dim:
+            raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {queries.shape}")
+        vector_id_lists = list(vector_id_lists)
+        if len(vector_id_lists) != queries.shape[0]:
+            raise ValueError(f"vector_id_lists holds {len(vector_id_lists)} lists for {queries.shape[0]} queries")
+        self.last_search_path = "threads"
+        nq = queries.shape[0]
+        if nq == 0:
+            return []
+        split = [self._ids_by_shard(ids) for ids in vector_id_lists]  # [query][shard]
+        work = [s for s in range(len(self.indices)) if any(split[q][s] for q in range(nq))]
+        if not work:
+            return [[] for _ in range(nq)]
+
+        def one(s):
+            return self.indices[s].search_batch_among_each(queries, [split[q][s] for q in range(nq)], limit=limit)
+        per_shard = list(self._shard_pool.map(one, work)) if len(work) > 1 else [one(work[0])]
+        return [self._merge([res[q] for res in per_shard], limit, threshold, None) for q in range(nq)]
 
     def search_among(self, query_vector: List[float], vector_ids, limit: int = 10, threshold: float = 0.0) -> List[Result]:
         query = _as_query(query_vector)

@@ -137,6 +137,14 @@ class WDBX:
             self._check_dim(q)
         return self.vector_store.search_batch_among(query_vectors, vector_ids, limit=limit, threshold=threshold)
 
+    def vector_search_batch_among_each(self, query_vectors, vector_id_lists, limit: int = 10,
+                                       threshold: float = 0.0) -> List[List[Result]]:
+        """Extension: ``vector_search_among`` for a batch whose queries each bring THEIR OWN id list (``vector_id_lists[i]``
+        is query i's; another length raises ``ValueError``), one library call per shard for the whole batch."""
+        for q in query_vectors:
+            self._check_dim(q)
+        return self.vector_store.search_batch_among_each(query_vectors, vector_id_lists, limit=limit, threshold=threshold)
+
     async def vector_search_among_async(self, query_vector: List[float], vector_ids, limit: int = 10,
                                         threshold: float = 0.0) -> List[Result]:
         self._check_dim(query_vector)
