@@ -248,13 +248,7 @@ static int group_load_queries(wdbx_group* g, const float* host, uint64_t seed, u
     const size_t bytes = (size_t)nq * ix->pitch * sizeof(float);
     if ((rc = grow((void**)&gs.d_q, &gs.q_bytes, bytes))) return rc;
     if (host) {
-      if (ix->pitch == ix->dim) {
-        HIP_TRY(hipMemcpyAsync(gs.d_q, host, bytes, hipMemcpyHostToDevice, ix->stream));
-      } else {
-        HIP_TRY(hipMemsetAsync(gs.d_q, 0, bytes, ix->stream));
-        HIP_TRY(hipMemcpy2DAsync(gs.d_q, (size_t)ix->pitch * sizeof(float), host, (size_t)ix->dim * sizeof(float),
-                                 (size_t)ix->dim * sizeof(float), nq, hipMemcpyHostToDevice, ix->stream));
-      }
+      if ((rc = copy_padded(ix, gs.d_q, host, (uint64_t)nq, ix->dim))) return rc;
       if (normalize && ix->metric == WDBX_METRIC_COSINE && (rc = launch_normalize(ix, gs.d_q, nq))) return rc;
     } else if ((rc = launch_fill(ix, gs.d_q, seed, row0, nq, normalize && ix->metric == WDBX_METRIC_COSINE))) {
       return rc;
@@ -328,10 +322,7 @@ static int group_enqueue_search(wdbx_group* g, int first, int nq, int k, int k_o
       if (g->exchange != GROUP_EXCHANGE_RCCL && !direct && (r = grow((void**)&gs.d_keys, &gs.keys_bytes, (size_t)c * k * sizeof(u64)))) return r;
       u64* const keys = direct ? g->sh[0].d_gathered + (size_t)s * c * k : gs.d_keys;
       const float* q = staged ? (const float*)gs.stage_dev + (size_t)c0 * ix->pitch : gs.d_q + (size_t)(first + c0) * ix->pitch;
-      struct MaskScope {  // the mask applies to this enqueue only (the kernels take the pointer at launch)
-        wdbx_index* ix;
-        ~MaskScope() { ix->active_mask = nullptr; }
-      } scope{ix};
+      MaskScope scope(ix, true);  // the mask applies to this enqueue only (the kernels take the pointer at launch)
       struct DeferScope {
         wdbx_index* ix;
         ~DeferScope() { ix->defer_flag_dev = nullptr; }

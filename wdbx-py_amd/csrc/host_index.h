@@ -217,14 +217,75 @@ static int set_active_mask(wdbx_index* ix, const uint32_t* mask_words) {
   int rc = grow((void**)&ix->d_mask, &ix->mask_bytes, words * sizeof(uint32_t));
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(ix->d_mask, mask_words, words * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
-  uint64_t allowed = 0;
-  for (size_t w = 0; w + 1 < words; ++w) allowed += (uint64_t)__builtin_popcount(mask_words[w]);
-  if (words) {
-    const uint32_t tail = (uint32_t)(ix->n & 31);
-    allowed += (uint64_t)__builtin_popcount(mask_words[words - 1] & (tail ? (1u << tail) - 1u : ~0u));
-  }
-  ix->mask_allowed = allowed;
+  ix->mask_allowed = mask_allowed_rows(mask_words, ix->n);
   ix->active_mask = ix->d_mask;
+  return WDBX_OK;
+}
+
+// ... and the reset: a row mask applies to one call (one enqueue of the shard group) only.  armed from the start where the
+// call sets a mask in every case, or by set() where it may return before it has changed the handle.
+struct MaskScope {
+  wdbx_index* ix;
+  bool armed;
+  explicit MaskScope(wdbx_index* ix_, bool armed_ = false) : ix(ix_), armed(armed_) {}
+  ~MaskScope() {
+    if (armed) ix->active_mask = nullptr;
+  }
+  int set(const uint32_t* mask_words) {
+    armed = true;
+    return set_active_mask(ix, mask_words);
+  }
+};
+
+// the one check of a mask's length against the row count (under the handle's lock: a mask built before a concurrent add is
+// refused instead of over-read); label says whose mask: "row mask", "row mask 3", "shard 2: row mask"
+static int check_mask_words(uint64_t n_rows, uint64_t mask_word_count, const char* label = "row mask") {
+  const uint64_t words = (n_rows + 31) / 32;
+  if (mask_word_count >= words) return WDBX_OK;
+  return fail(WDBX_E_INVALID, "%s of %llu words for %llu rows (%llu words needed)", label, (u64)mask_word_count, (u64)n_rows, (u64)words);
+}
+
+// n host rows of src_pitch floats (their first dim floats count) to dst at the row pitch, behind the stream's earlier work: one
+// copy when the pitches agree, else the padding is zeroed first
+static int copy_padded(wdbx_index* ix, float* dst, const float* src, uint64_t n, int src_pitch) {
+  const size_t bytes = (size_t)n * ix->pitch * sizeof(float);
+  if (src_pitch == ix->pitch) {
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ix->stream));
+  } else {
+    HIP_TRY(hipMemsetAsync(dst, 0, bytes, ix->stream));
+    HIP_TRY(hipMemcpy2DAsync(dst, (size_t)ix->pitch * sizeof(float), src, (size_t)src_pitch * sizeof(float), (size_t)ix->dim * sizeof(float), n,
+                             hipMemcpyHostToDevice, ix->stream));
+  }
+  return WDBX_OK;
+}
+
+// the result buffers of the blocking calls, for at least elems results (contents never preserved)
+static int ensure_out(wdbx_index* ix, size_t elems) {
+  if (elems <= ix->out_elems) return WDBX_OK;
+  if (ix->d_oidx) HIP_TRY(hipFree(ix->d_oidx));
+  if (ix->d_oscore) HIP_TRY(hipFree(ix->d_oscore));
+  ix->d_oidx = nullptr;
+  ix->d_oscore = nullptr;
+  ix->out_elems = 0;
+  HIP_TRY(hipMalloc((void**)&ix->d_oidx, elems * sizeof(int64_t)));
+  HIP_TRY(hipMalloc((void**)&ix->d_oscore, elems * sizeof(float)));
+  ix->out_elems = elems;
+  return WDBX_OK;
+}
+
+// Wait for a lone call's completion word (mapped host memory; the chain's last kernel writes seq behind its results,
+// merge_signal_done): a poll of the word -- 5 us less than the runtime's completion path (profiles/r04/poll/) -- with a look at
+// the event the caller recorded behind the chain every 4 096 spins, which is how a failed launch would surface.
+static inline int wait_done_word(volatile uint32_t* word, uint32_t seq, hipEvent_t ev) {
+  for (uint32_t spins = 1;; ++spins) {
+    if (*word == seq) break;
+    if ((spins & 0xFFFu) == 0) {
+      const hipError_t e = hipEventQuery(ev);
+      if (e == hipSuccess) break;  // (the kernel has ended: its stores are visible)
+      if (e != hipErrorNotReady) HIP_TRY(hipEventSynchronize(ev));
+    }
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);  // (the results are read after the word, not before)
   return WDBX_OK;
 }
 
@@ -2111,17 +2172,9 @@ static int reserve_locked(wdbx_index* ix, uint64_t cap) {
 
 static int upload_rows(wdbx_index* ix, uint64_t first, const float* rows, uint64_t n, int normalize) {
   float* dst = ix->d_rows + (size_t)first * ix->pitch;
-  if (ix->pitch == ix->dim) {
-    HIP_TRY(hipMemcpyAsync(dst, rows, (size_t)n * ix->dim * sizeof(float), hipMemcpyHostToDevice, ix->stream));
-  } else {
-    HIP_TRY(hipMemsetAsync(dst, 0, (size_t)n * ix->pitch * sizeof(float), ix->stream));
-    HIP_TRY(hipMemcpy2DAsync(dst, (size_t)ix->pitch * sizeof(float), rows, (size_t)ix->dim * sizeof(float),
-                             (size_t)ix->dim * sizeof(float), n, hipMemcpyHostToDevice, ix->stream));
-  }
-  if (normalize) {
-    int rc = launch_normalize(ix, dst, n);
-    if (rc) return rc;
-  }
+  int rc = copy_padded(ix, dst, rows, n, ix->dim);
+  if (rc) return rc;
+  if (normalize && (rc = launch_normalize(ix, dst, n))) return rc;
   // Derived copies (cached norms, bf16 and u8 shadows) of OVERWRITTEN rows are refreshed right here, for exactly
   // those rows: an update in the middle of a large corpus must not invalidate everything behind it.  Rows appended
   // past what a copy covers are picked up lazily by the next search, as before.
@@ -2166,4 +2219,46 @@ static int upload_rows(wdbx_index* ix, uint64_t first, const float* rows, uint64
   }
   HIP_TRY(hipStreamSynchronize(ix->stream));
   return WDBX_OK;
+}
+
+// ---- what the blocking entry points share (wdbx_hip.hip) ------------------------------------------------------------
+// nq of the caller's queries (src_pitch floats apart, 0 = dim) into d_q at the row pitch, normalised for cosine when asked
+static int upload_queries(wdbx_index* ix, const float* queries, uint64_t nq, int normalize_queries, int src_pitch = 0) {
+  int rc = grow((void**)&ix->d_q, &ix->q_bytes, (size_t)nq * ix->pitch * sizeof(float));
+  if (rc || (rc = copy_padded(ix, ix->d_q, queries, nq, src_pitch ? src_pitch : ix->dim))) return rc;
+  if (normalize_queries && ix->metric == WDBX_METRIC_COSINE) return launch_normalize(ix, ix->d_q, nq);
+  return WDBX_OK;
+}
+
+// the first elems results of d_oidx / d_oscore to the host; returns when they are there
+static int download_results(wdbx_index* ix, size_t elems, int64_t* out_idx, float* out_score) {
+  HIP_TRY(hipMemcpyAsync(out_idx, ix->d_oidx, elems * sizeof(int64_t), hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipMemcpyAsync(out_score, ix->d_oscore, elems * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  return WDBX_OK;
+}
+
+// ... of a call that placed its queries in slots: slot s holds the k results of the caller's query slot_query[s] (-1: a pad)
+static int download_results(wdbx_index* ix, const std::vector<int32_t>& slot_query, int k, int64_t* out_idx, float* out_score) {
+  const size_t slots = slot_query.size();
+  std::vector<int64_t> h_idx(slots * (size_t)k);
+  std::vector<float> h_score(slots * (size_t)k);
+  const int rc = download_results(ix, slots * (size_t)k, h_idx.data(), h_score.data());
+  if (rc) return rc;
+  for (size_t s = 0; s < slots; ++s) {
+    const int32_t q = slot_query[s];
+    if (q < 0) continue;
+    memcpy(out_idx + (size_t)q * k, &h_idx[s * k], (size_t)k * sizeof(int64_t));
+    memcpy(out_score + (size_t)q * k, &h_score[s * k], (size_t)k * sizeof(float));
+  }
+  return WDBX_OK;
+}
+
+// one query whose candidate buffer overflowed, again: straight to the fp32 scan (the selection would overflow again)
+static int enqueue_exact_rerun(wdbx_index* ix, const float* dq, int k, int64_t* out_idx, float* out_score) {
+  const int64_t keep = ix->opt_scan_shadow;
+  ix->opt_scan_shadow = 0;
+  const int rc = enqueue_search(ix, dq, 1, k, out_idx, out_score, SEARCH_FINAL);
+  ix->opt_scan_shadow = keep;
+  return rc;
 }

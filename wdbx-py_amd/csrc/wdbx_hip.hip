@@ -31,7 +31,10 @@
 //   kernels_rowlists.h      rowlists_kernel: the same scores for a call with one row list PER QUERY (wdbx_index_search_row_lists),
 //                           one workgroup per (chunk of a list, block of its queries) work item of host_rowlists.h
 //   host_multimask.h        a call with one row mask per query: the placement of its queries in the int8 tiles' query blocks
-//   host_index.h            the handle, kernel choice, and the enqueue functions of every search path
+//   host_calls.h            what the blocking entry points share, device-free: allowed rows of a mask, padded query copies, the host
+//                           ranking of a lone query's keys, the class-by-class fallback loop
+//   host_index.h            the handle, kernel choice, the enqueue functions of every search path, and what the blocking entry
+//                           points share on the device side: query upload, result buffers and download, mask scope and check
 //   host_group.h            the in-process shard group: per-shard host threads, exchange (RCCL all-gather / device copies), merge
 // The selection paths never decide a result: they keep every row whose score could reach the true k-th best
 // under a rigorous error bound, and the kept rows are re-scored in fp32 from the fp32 rows.
@@ -68,6 +71,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 // with plain g++ under -fsanitize=thread / address,undefined (tests/test_host_dispatch_sanitizers.py)
 #include "host_dispatch.h"
 #include "host_range.h"  // (device-free as well: CSR offsets, per-query sort and decoding of a range search's keys)
+#include "host_calls.h"  // (device-free as well: mask popcount, padded query copies, host ranking of keys, class-by-class loop)
 #include "host_subset.h"  // (device-free as well: row-list validation, route and grid sizing of a search among listed rows)
 #include "host_multimask.h"  // (device-free as well: where the queries of a call with a mask per query sit in the tile blocks)
 #include "host_rowlists.h"  // (device-free as well: slots, rounds, query blocks and work items of a call with a row list per query)
@@ -390,13 +394,7 @@ static int search_host(wdbx_index* ix, const float* queries, int nq, int k, int 
   if (!held) own = std::unique_lock<std::mutex>(ix->mu);
   std::unique_lock<std::mutex>& lk = held ? *held : own;
   DeviceGuard g(ix->device);
-  struct MaskScope {  // the mask applies to this call only (such a call keeps the mutex to its end: d_mask is one buffer)
-    wdbx_index* ix;
-    bool set = false;
-    ~MaskScope() {
-      if (set) ix->active_mask = nullptr;
-    }
-  } scope{ix};
+  MaskScope scope(ix);  // the mask applies to this call only (such a call keeps the mutex to its end: d_mask is one buffer)
   int rc;
   const size_t elems = (size_t)nq * k;
   const size_t q_bytes = (size_t)nq * ix->pitch * sizeof(float);
@@ -445,13 +443,7 @@ static int search_host(wdbx_index* ix, const float* queries, int nq, int k, int 
     if ((hold.slot = ix->slots.try_take()) >= 0) break;  // (taken without a wait: nothing can have changed)
     ix->slots.wait(lk);  // mutex released while waiting: decide again afterwards
   }
-  if (mask_words && ix->n) {
-    const size_t words = (size_t)((ix->n + 31) / 32);
-    if (mask_word_count < words)
-      return fail(WDBX_E_INVALID, "row mask of %llu words for %llu rows (%zu words needed)", (u64)mask_word_count, (u64)ix->n, words);
-    scope.set = true;
-    if ((rc = set_active_mask(ix, mask_words))) return rc;
-  }
+  if (mask_words && ix->n && ((rc = check_mask_words(ix->n, mask_word_count)) || (rc = scope.set(mask_words)))) return rc;
   if (!gemm) ix->last_batch_masked = 0;  // (what the last_batch_* options describe is the last call, whatever it ran)
   char* const hs = zero_copy ? ix->h_stage + (size_t)hold.slot * SLOT_BYTES : nullptr;      // this call's slot, host view
   char* const ds = zero_copy ? ix->h_stage_dev + (size_t)hold.slot * SLOT_BYTES : nullptr;  // ... and device view
@@ -468,22 +460,12 @@ static int search_host(wdbx_index* ix, const float* queries, int nq, int k, int 
     return WDBX_OK;
   };
   // ... or, when the call's last kernel reports into a word of the slot (merge_signal_done): the event still marks the call on
-  // the stream (and is how a failed launch would surface -- looked at every 4 096 spins); the wait itself is a poll of the word,
-  // which the kernel wrote behind its results: 5 us less than the runtime's completion path (profiles/r04/poll/)
+  // the stream; the wait itself is a poll of the word, which the kernel wrote behind its results (wait_done_word)
   auto wait_polled = [&](volatile uint32_t* word, uint32_t seq) -> int {
     HIP_TRY(hipEventRecord(ix->slot_done[hold.slot], ix->stream));
     hipEvent_t ev = ix->slot_done[hold.slot];
     lk.unlock();
-    for (uint32_t spins = 1;; ++spins) {
-      if (*word == seq) break;
-      if ((spins & 0xFFFu) == 0) {
-        const hipError_t e = hipEventQuery(ev);
-        if (e == hipSuccess) break;  // (the kernel has ended: its stores are visible)
-        if (e != hipErrorNotReady) HIP_TRY(hipEventSynchronize(ev));
-      }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);  // (the slot's contents are read after the word, not before)
-    return WDBX_OK;
+    return wait_done_word(word, seq, ev);
   };
   bool poll_tail = false;  // a small batch whose single merge launch took the signal: the common tail below polls
   uint32_t poll_seq = 0;
@@ -491,43 +473,16 @@ static int search_host(wdbx_index* ix, const float* queries, int nq, int k, int 
   int64_t* doidx;
   float* doscore;
   if (zero_copy) {
-    float* hq = (float*)hs;
-    if (ix->pitch == ix->dim) {
-      memcpy(hq, queries, q_bytes);
-    } else {
-      memset(hq, 0, q_bytes);
-      for (int q = 0; q < nq; ++q) memcpy(hq + (size_t)q * ix->pitch, queries + (size_t)q * ix->dim, (size_t)ix->dim * sizeof(float));
-    }
+    pad_queries((float*)hs, (size_t)ix->pitch, queries, (size_t)ix->dim, (size_t)nq);
     dq = (float*)ds;
     doidx = (int64_t*)(ds + STAGE_Q);
     doscore = (float*)(ds + STAGE_Q + STAGE_IDX);
+    if (normalize_queries && ix->metric == WDBX_METRIC_COSINE && (rc = launch_normalize(ix, dq, nq))) return rc;
   } else {
-    rc = grow((void**)&ix->d_q, &ix->q_bytes, q_bytes);
-    if (rc) return rc;
-    if (elems > ix->out_elems) {
-      if (ix->d_oidx) HIP_TRY(hipFree(ix->d_oidx));
-      if (ix->d_oscore) HIP_TRY(hipFree(ix->d_oscore));
-      ix->d_oidx = nullptr;
-      ix->d_oscore = nullptr;
-      ix->out_elems = 0;
-      HIP_TRY(hipMalloc((void**)&ix->d_oidx, elems * sizeof(int64_t)));
-      HIP_TRY(hipMalloc((void**)&ix->d_oscore, elems * sizeof(float)));
-      ix->out_elems = elems;
-    }
-    if (ix->pitch == ix->dim) {
-      HIP_TRY(hipMemcpyAsync(ix->d_q, queries, q_bytes, hipMemcpyHostToDevice, ix->stream));
-    } else {
-      HIP_TRY(hipMemsetAsync(ix->d_q, 0, q_bytes, ix->stream));
-      HIP_TRY(hipMemcpy2DAsync(ix->d_q, (size_t)ix->pitch * sizeof(float), queries, (size_t)ix->dim * sizeof(float),
-                               (size_t)ix->dim * sizeof(float), nq, hipMemcpyHostToDevice, ix->stream));
-    }
+    if ((rc = ensure_out(ix, elems)) || (rc = upload_queries(ix, queries, (uint64_t)nq, normalize_queries))) return rc;
     dq = ix->d_q;
     doidx = ix->d_oidx;
     doscore = ix->d_oscore;
-  }
-  if (normalize_queries && ix->metric == WDBX_METRIC_COSINE) {
-    rc = launch_normalize(ix, dq, nq);
-    if (rc) return rc;
   }
   if (gemm) {
     rc = enqueue_search_gemm(ix, dq, nq, k, doidx, doscore);
@@ -538,13 +493,9 @@ static int search_host(wdbx_index* ix, const float* queries, int nq, int k, int 
     // a query whose candidate buffer overflowed has been re-run exactly by the conditional repair launches queued behind
     // its block (enqueue_batch_repair); shapes without a device-side repair are re-run here
     for (int q = 0; q < nq && !ix->last_batch_repaired; ++q)
-      if (counts[q] > ix->last_batch_cap) {
-        const int64_t keep = ix->opt_scan_shadow;  // straight to the fp32 scan: the selection would overflow again
-        ix->opt_scan_shadow = 0;
-        rc = enqueue_search(ix, dq + (size_t)q * ix->pitch, 1, k, doidx + (size_t)q * k, doscore + (size_t)q * k, SEARCH_FINAL);
-        ix->opt_scan_shadow = keep;
-        if (rc) return rc;
-      }
+      if (counts[q] > ix->last_batch_cap &&
+          (rc = enqueue_exact_rerun(ix, dq + (size_t)q * ix->pitch, k, doidx + (size_t)q * k, doscore + (size_t)q * k)))
+        return rc;
   } else {
     // Lone query through mapped memory: the u8 selection scan skips its queued repair launches and its final merge --
     // the re-scored candidates' keys and their count land in the call's slot and THIS thread ranks them after its wait
@@ -616,25 +567,7 @@ static int search_host(wdbx_index* ix, const float* queries, int nq, int k, int 
         if (cnt > cap) {
           repair = true;
         } else {  // the exact keys of the kept rows: the k largest, in key order = (score descending, row ascending)
-          const u64* hk = (const u64*)(hs + STAGE_Q);
-          std::vector<u64> keys(hk, hk + cnt);
-          const size_t kk = std::min<size_t>((size_t)k, keys.size());
-          if (kk < keys.size()) std::nth_element(keys.begin(), keys.begin() + kk, keys.end(), std::greater<u64>());  // O(n) ...
-          std::sort(keys.begin(), keys.begin() + kk, std::greater<u64>());                                                // ... + k log k
-          size_t o = 0;
-          for (size_t i = 0; i < kk && keys[i]; ++i, ++o) {  // (a zero key = a NaN score: never a result)
-            const uint32_t ord = (uint32_t)(keys[i] >> 32);
-            const uint32_t u = (ord & 0x80000000u) ? (ord ^ 0x80000000u) : ~ord;
-            float sc;
-            memcpy(&sc, &u, sizeof sc);
-            if (metric == WDBX_METRIC_L2) sc = -sc + 0.0f;
-            out_idx[o] = (int64_t)(uint32_t)~(uint32_t)(keys[i] & 0xFFFFFFFFull);
-            out_score[o] = sc;
-          }
-          for (; o < (size_t)k; ++o) {
-            out_idx[o] = -1;
-            out_score[o] = 0.0f;
-          }
+          rank_keys_host((const uint64_t*)(hs + STAGE_Q), cnt, k, metric == WDBX_METRIC_L2, out_idx, out_score);
           return WDBX_OK;
         }
       } else if (over[0]) {
@@ -642,11 +575,7 @@ static int search_host(wdbx_index* ix, const float* queries, int nq, int k, int 
       }
       if (repair) {  // (rare: back under the mutex, the exact scan into the same slot)
         if (!lk.owns_lock()) lk.lock();
-        const int64_t keep = ix->opt_scan_shadow;
-        ix->opt_scan_shadow = 0;
-        rc = enqueue_search(ix, dq, nq, k, doidx, doscore, SEARCH_FINAL);
-        ix->opt_scan_shadow = keep;
-        if (rc) return rc;
+        if ((rc = enqueue_exact_rerun(ix, dq, k, doidx, doscore))) return rc;  // (a lone query: nq = 1)
         HIP_TRY(hipStreamSynchronize(ix->stream));
       }
       memcpy(out_idx, hs + STAGE_Q, elems * sizeof(int64_t));
@@ -660,10 +589,8 @@ static int search_host(wdbx_index* ix, const float* queries, int nq, int k, int 
     } else if ((rc = wait_for_gpu())) return rc;
     memcpy(out_idx, hs + STAGE_Q, elems * sizeof(int64_t));
     memcpy(out_score, hs + STAGE_Q + STAGE_IDX, elems * sizeof(float));
-  } else {
-    HIP_TRY(hipMemcpyAsync(out_idx, doidx, elems * sizeof(int64_t), hipMemcpyDeviceToHost, ix->stream));
-    HIP_TRY(hipMemcpyAsync(out_score, doscore, elems * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
-    HIP_TRY(hipStreamSynchronize(ix->stream));
+  } else if ((rc = download_results(ix, elems, out_idx, out_score))) {
+    return rc;
   }
   return WDBX_OK;
 }
@@ -710,38 +637,21 @@ int wdbx_index_search_multimask(wdbx_index* ix, const float* queries, int nq, in
   std::unique_lock<std::mutex> lk(ix->mu);
   DeviceGuard g(ix->device);
   const size_t words = (size_t)((ix->n + 31) / 32);
-  for (int m = 0; m < n_masks && ix->n; ++m)
-    if (mask_word_counts[m] < words)
-      return fail(WDBX_E_INVALID, "row mask %d of %llu words for %llu rows (%zu words needed)", m, (u64)mask_word_counts[m], (u64)ix->n, words);
   int rc;
+  for (int m = 0; m < n_masks && ix->n; ++m)
+    if ((rc = check_mask_words(ix->n, mask_word_counts[m], ("row mask " + std::to_string(m)).c_str()))) return rc;
   const bool l2 = ix->metric == WDBX_METRIC_L2;
   ix->last_batch_masked = 0;
   const bool tiles = ix->n && ix->n < 0xFFFFFF00ull && gemm_eligible(ix, nq, k) && masked_tiles_ready(ix, k);
   if (!tiles) {
     // class by class through the calls that existed before, in the caller's order inside a class; the lock stays held
-    std::vector<float> cq;
-    std::vector<int64_t> ci;
-    std::vector<float> cs;
-    std::vector<int> members;
-    for (int c = -1; c < n_masks; ++c) {
-      members.clear();
-      for (int q = 0; q < nq; ++q)
-        if (query_mask[q] == c) members.push_back(q);
-      if (members.empty()) continue;
-      const size_t nm = members.size();
-      cq.resize(nm * (size_t)ix->dim);
-      ci.resize(nm * (size_t)k);
-      cs.resize(nm * (size_t)k);
-      for (size_t i = 0; i < nm; ++i) memcpy(&cq[i * ix->dim], queries + (size_t)members[i] * ix->dim, (size_t)ix->dim * sizeof(float));
-      rc = search_host(ix, cq.data(), (int)nm, k, normalize_queries, c < 0 ? nullptr : mask_words[c], c < 0 ? 0 : mask_word_counts[c], ci.data(),
-                       cs.data(), &lk);
-      if (rc) return rc;
-      for (size_t i = 0; i < nm; ++i) {
-        memcpy(out_idx + (size_t)members[i] * k, &ci[i * k], (size_t)k * sizeof(int64_t));
-        memcpy(out_score + (size_t)members[i] * k, &cs[i * k], (size_t)k * sizeof(float));
-      }
-    }
-    return WDBX_OK;
+    std::vector<int32_t> classes((size_t)n_masks + 1);
+    for (int c = -1; c < n_masks; ++c) classes[(size_t)(c + 1)] = c;
+    return for_each_class(nq, ix->dim, k, queries, query_mask, classes, out_idx, out_score,
+                          [&](int32_t c, int nm, const float* cq, int64_t* ci, float* cs) {
+                            return search_host(ix, cq, nm, k, normalize_queries, c < 0 ? nullptr : mask_words[c],
+                                               c < 0 ? 0 : mask_word_counts[c], ci, cs, &lk);
+                          });
   }
   // ---- the tile route ----
   const int forced = (ix->opt_gemm_ct == 1 || ix->opt_gemm_ct == 2 || ix->opt_gemm_ct == 4) ? (int)ix->opt_gemm_ct : 4;
@@ -768,45 +678,19 @@ int wdbx_index_search_multimask(wdbx_index* ix, const float* queries, int nq, in
     class_mask[r] = (int32_t)r;
     const uint32_t* mw = mask_words[c];
     HIP_TRY(hipMemcpyAsync(d_masks + r * stride, mw, words * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
-    uint64_t al = 0;
-    for (size_t w = 0; w + 1 < words; ++w) al += (uint64_t)__builtin_popcount(mw[w]);
-    const uint32_t tail = (uint32_t)(ix->n & 31);
-    al += (uint64_t)__builtin_popcount(mw[words - 1] & (tail ? (1u << tail) - 1u : ~0u));
-    allowed[r] = al;
+    allowed[r] = mask_allowed_rows(mw, ix->n);
   }
   HIP_TRY(hipMemcpyAsync(d_slot_query, plan.slot_query.data(), slots * sizeof(int32_t), hipMemcpyHostToDevice, ix->stream));
   HIP_TRY(hipMemcpyAsync(d_class_mask, class_mask.data(), rows * sizeof(int32_t), hipMemcpyHostToDevice, ix->stream));
   // the queries as in search_host, then into their slots
-  const size_t q_bytes = (size_t)nq * ix->pitch * sizeof(float), elems = slots * (size_t)k;
-  if ((rc = grow((void**)&ix->d_q, &ix->q_bytes, q_bytes))) return rc;
-  if (elems > ix->out_elems) {
-    if (ix->d_oidx) HIP_TRY(hipFree(ix->d_oidx));
-    if (ix->d_oscore) HIP_TRY(hipFree(ix->d_oscore));
-    ix->d_oidx = nullptr;
-    ix->d_oscore = nullptr;
-    ix->out_elems = 0;
-    HIP_TRY(hipMalloc((void**)&ix->d_oidx, elems * sizeof(int64_t)));
-    HIP_TRY(hipMalloc((void**)&ix->d_oscore, elems * sizeof(float)));
-    ix->out_elems = elems;
-  }
-  if (ix->pitch == ix->dim) {
-    HIP_TRY(hipMemcpyAsync(ix->d_q, queries, q_bytes, hipMemcpyHostToDevice, ix->stream));
-  } else {
-    HIP_TRY(hipMemsetAsync(ix->d_q, 0, q_bytes, ix->stream));
-    HIP_TRY(hipMemcpy2DAsync(ix->d_q, (size_t)ix->pitch * sizeof(float), queries, (size_t)ix->dim * sizeof(float),
-                             (size_t)ix->dim * sizeof(float), nq, hipMemcpyHostToDevice, ix->stream));
-  }
-  if (normalize_queries && ix->metric == WDBX_METRIC_COSINE && (rc = launch_normalize(ix, ix->d_q, nq))) return rc;
+  if ((rc = ensure_out(ix, slots * (size_t)k)) || (rc = upload_queries(ix, queries, (uint64_t)nq, normalize_queries))) return rc;
   const uint32_t pitch4 = (uint32_t)(ix->pitch / 4);
   hipLaunchKernelGGL(place_queries_kernel, dim3((uint32_t)((slots * pitch4 + 255) / 256)), dim3(256), 0, ix->stream, (const f4*)ix->d_q,
                      (const int32_t*)d_slot_query, pitch4, (uint32_t)slots, (f4*)d_slots_q);
   HIP_TRY(hipGetLastError());
   ix->last_batch_repaired = false;
   MultiCall mc = {&plan, d_slot_query, d_masks, stride, d_class_mask, allowed.data()};
-  struct MaskScope {  // (the repair launches set the class's mask for their own duration; nothing outlives the call)
-    wdbx_index* ix;
-    ~MaskScope() { ix->active_mask = nullptr; }
-  } scope{ix};
+  MaskScope scope(ix, true);  // (the repair launches set the class's mask for their own duration; nothing outlives the call)
   if ((rc = enqueue_search_gemm8(ix, d_slots_q, (int)slots, k, ix->d_oidx, ix->d_oscore, SEARCH_FINAL, nullptr, &mc))) return rc;
   // what wdbx_index_batch_status reports: the caller's queries
   ix->last_batch_nq = (uint32_t)nq;
@@ -822,27 +706,13 @@ int wdbx_index_search_multimask(wdbx_index* ix, const float* queries, int nq, in
     if (plan.slot_query[s2] >= 0 && counts[s2] > ix->last_batch_cap) {
       const int c = plan.group_class[s2 / MULTIMASK_GROUP];
       const size_t r = (size_t)(std::lower_bound(plan.classes.begin(), plan.classes.end(), c) - plan.classes.begin());
-      const int64_t keep = ix->opt_scan_shadow;
-      ix->opt_scan_shadow = 0;
       ix->active_mask = c < 0 ? nullptr : d_masks + r * stride;
       ix->mask_allowed = allowed[r];
-      rc = enqueue_search(ix, d_slots_q + s2 * ix->pitch, 1, k, ix->d_oidx + s2 * k, ix->d_oscore + s2 * k, SEARCH_FINAL);
+      rc = enqueue_exact_rerun(ix, d_slots_q + s2 * ix->pitch, k, ix->d_oidx + s2 * k, ix->d_oscore + s2 * k);
       ix->active_mask = nullptr;
-      ix->opt_scan_shadow = keep;
       if (rc) return rc;
     }
-  std::vector<int64_t> h_idx(elems);
-  std::vector<float> h_score(elems);
-  HIP_TRY(hipMemcpyAsync(h_idx.data(), ix->d_oidx, elems * sizeof(int64_t), hipMemcpyDeviceToHost, ix->stream));
-  HIP_TRY(hipMemcpyAsync(h_score.data(), ix->d_oscore, elems * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
-  HIP_TRY(hipStreamSynchronize(ix->stream));
-  for (size_t s2 = 0; s2 < slots; ++s2) {
-    const int q = plan.slot_query[s2];
-    if (q < 0) continue;
-    memcpy(out_idx + (size_t)q * k, &h_idx[s2 * k], (size_t)k * sizeof(int64_t));
-    memcpy(out_score + (size_t)q * k, &h_score[s2 * k], (size_t)k * sizeof(float));
-  }
-  return WDBX_OK;
+  return download_results(ix, plan.slot_query, k, out_idx, out_score);
 } WDBX_CATCH
 
 // ---- search among listed rows (kernels_subset.h, host_subset.h) -------------------------------------
@@ -878,18 +748,7 @@ static int search_rows_host(wdbx_index* ix, const float* queries, int nq, int k,
   }
   DeviceGuard g(ix->device);
   int rc;
-  const size_t q_bytes = (size_t)nq * ix->pitch * sizeof(float);
-  if ((rc = grow((void**)&ix->d_q, &ix->q_bytes, q_bytes))) return rc;
-  if (elems > ix->out_elems) {
-    if (ix->d_oidx) HIP_TRY(hipFree(ix->d_oidx));
-    if (ix->d_oscore) HIP_TRY(hipFree(ix->d_oscore));
-    ix->d_oidx = nullptr;
-    ix->d_oscore = nullptr;
-    ix->out_elems = 0;
-    HIP_TRY(hipMalloc((void**)&ix->d_oidx, elems * sizeof(int64_t)));
-    HIP_TRY(hipMalloc((void**)&ix->d_oscore, elems * sizeof(float)));
-    ix->out_elems = elems;
-  }
+  if ((rc = ensure_out(ix, elems))) return rc;
   if ((rc = grow((void**)&ix->d_sub_ids, &ix->sub_ids_bytes, (size_t)n_ids * sizeof(uint32_t)))) return rc;
   const bool lists = sp.route == SUBSET_LISTS;
   if (lists) {
@@ -901,15 +760,8 @@ static int search_rows_host(wdbx_index* ix, const float* queries, int nq, int k,
     if ((rc = grow((void**)&ix->d_sel, &ix->sel_bytes, (size_t)WDBX_MAX_K * sizeof(u64)))) return rc;
     if ((rc = grow((void**)&ix->d_state, &ix->state_bytes, sizeof(SelectState)))) return rc;
   }
-  if (ix->pitch == ix->dim) {
-    HIP_TRY(hipMemcpyAsync(ix->d_q, queries, q_bytes, hipMemcpyHostToDevice, ix->stream));
-  } else {
-    HIP_TRY(hipMemsetAsync(ix->d_q, 0, q_bytes, ix->stream));
-    HIP_TRY(hipMemcpy2DAsync(ix->d_q, (size_t)ix->pitch * sizeof(float), queries, (size_t)ix->dim * sizeof(float),
-                             (size_t)ix->dim * sizeof(float), nq, hipMemcpyHostToDevice, ix->stream));
-  }
+  if ((rc = upload_queries(ix, queries, (uint64_t)nq, normalize_queries))) return rc;
   HIP_TRY(hipMemcpyAsync(ix->d_sub_ids, ids32.data(), (size_t)n_ids * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
-  if (normalize_queries && ix->metric == WDBX_METRIC_COSINE && (rc = launch_normalize(ix, ix->d_q, (uint64_t)nq))) return rc;
 
   const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
   const bool reg = k <= 128 && !ix->opt_lds_lists;
@@ -970,10 +822,7 @@ static int search_rows_host(wdbx_index* ix, const float* queries, int nq, int k,
     m.out_score = ix->d_oscore + (size_t)q0 * k;
     if ((rc = launch_merge(ix, m, b))) return rc;
   }
-  HIP_TRY(hipMemcpyAsync(out_idx, ix->d_oidx, elems * sizeof(int64_t), hipMemcpyDeviceToHost, ix->stream));
-  HIP_TRY(hipMemcpyAsync(out_score, ix->d_oscore, elems * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
-  HIP_TRY(hipStreamSynchronize(ix->stream));
-  return WDBX_OK;
+  return download_results(ix, elems, out_idx, out_score);
 }
 
 int wdbx_index_search_rows(wdbx_index* ix, const float* queries, int nq, int k, int normalize_queries, const uint64_t* row_ids,
@@ -1031,18 +880,7 @@ int wdbx_index_search_row_lists(wdbx_index* ix, const float* queries, int nq, in
   } else {
     DeviceGuard g(ix->device);
     int rc;
-    const size_t elems = slots * (size_t)k, q_bytes = slots * ix->pitch * sizeof(float);
-    if ((rc = grow((void**)&ix->d_q, &ix->q_bytes, q_bytes))) return rc;
-    if (elems > ix->out_elems) {
-      if (ix->d_oidx) HIP_TRY(hipFree(ix->d_oidx));
-      if (ix->d_oscore) HIP_TRY(hipFree(ix->d_oscore));
-      ix->d_oidx = nullptr;
-      ix->d_oscore = nullptr;
-      ix->out_elems = 0;
-      HIP_TRY(hipMalloc((void**)&ix->d_oidx, elems * sizeof(int64_t)));
-      HIP_TRY(hipMalloc((void**)&ix->d_oscore, elems * sizeof(float)));
-      ix->out_elems = elems;
-    }
+    if ((rc = ensure_out(ix, slots * (size_t)k))) return rc;
     size_t key_u64 = 0;
     for (const RowListsRound& r : plan.rounds) key_u64 = std::max(key_u64, (size_t)r.slots * (size_t)r.stride);
     const size_t items_bytes = (plan.items.size() * sizeof(RowListsItem) + 255) / 256 * 256;
@@ -1052,14 +890,12 @@ int wdbx_index_search_row_lists(wdbx_index* ix, const float* queries, int nq, in
     const RowListsItem* const d_items = (const RowListsItem*)ix->d_rl;
     const uint32_t* const d_len = (const uint32_t*)(ix->d_rl + items_bytes);
     // the queries in slot order, padded to the row pitch (host side: one upload whatever the order)
-    std::vector<float> hq(slots * (size_t)ix->pitch, 0.0f);
-    for (size_t s = 0; s < slots; ++s)
-      memcpy(&hq[s * ix->pitch], queries + (size_t)plan.slot_query[s] * ix->dim, (size_t)ix->dim * sizeof(float));
-    HIP_TRY(hipMemcpyAsync(ix->d_q, hq.data(), q_bytes, hipMemcpyHostToDevice, ix->stream));
+    std::vector<float> hq(slots * (size_t)ix->pitch);
+    pad_queries(hq.data(), (size_t)ix->pitch, queries, (size_t)ix->dim, slots, plan.slot_query.data());
+    if ((rc = upload_queries(ix, hq.data(), slots, normalize_queries, ix->pitch))) return rc;
     HIP_TRY(hipMemcpyAsync(ix->d_sub_ids, ids32.data(), (size_t)plan.pass_ids * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
     HIP_TRY(hipMemcpyAsync(ix->d_rl, plan.items.data(), plan.items.size() * sizeof(RowListsItem), hipMemcpyHostToDevice, ix->stream));
     HIP_TRY(hipMemcpyAsync(ix->d_rl + items_bytes, plan.slot_len.data(), slots * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
-    if (normalize_queries && ix->metric == WDBX_METRIC_COSINE && (rc = launch_normalize(ix, ix->d_q, (uint64_t)slots))) return rc;
     const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
     const rowlists_fn fn = pick_rowlists(ix->metric, plan.qb, pitch4);
     if (!fn) return fail(WDBX_E_STATE, "no row-lists instance with %d queries per block", plan.qb);
@@ -1093,39 +929,15 @@ int wdbx_index_search_row_lists(wdbx_index* ix, const float* queries, int nq, in
       m.out_score = ix->d_oscore + (size_t)r.slot0 * k;
       if ((rc = launch_merge(ix, m, (int)r.slots))) return rc;
     }
-    std::vector<int64_t> h_idx(elems);
-    std::vector<float> h_score(elems);
-    HIP_TRY(hipMemcpyAsync(h_idx.data(), ix->d_oidx, elems * sizeof(int64_t), hipMemcpyDeviceToHost, ix->stream));
-    HIP_TRY(hipMemcpyAsync(h_score.data(), ix->d_oscore, elems * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
-    HIP_TRY(hipStreamSynchronize(ix->stream));
-    for (size_t s = 0; s < slots; ++s) {
-      memcpy(out_idx + (size_t)plan.slot_query[s] * k, &h_idx[s * k], (size_t)k * sizeof(int64_t));
-      memcpy(out_score + (size_t)plan.slot_query[s] * k, &h_score[s * k], (size_t)k * sizeof(float));
-    }
+    if ((rc = download_results(ix, plan.slot_query, k, out_idx, out_score))) return rc;
   }
-  // the longer lists, each with its queries in the caller's order, through the call that existed before; the lock stays held
-  std::vector<float> cq;
-  std::vector<int64_t> ci;
-  std::vector<float> cs;
-  std::vector<int> members;
-  for (const int32_t l : plan.fallback_lists) {
-    members.clear();
-    for (int q = 0; q < nq; ++q)
-      if (query_list[q] == l) members.push_back(q);
-    const size_t nm = members.size();
-    cq.resize(nm * (size_t)ix->dim);
-    ci.resize(nm * (size_t)k);
-    cs.resize(nm * (size_t)k);
-    for (size_t i = 0; i < nm; ++i) memcpy(&cq[i * ix->dim], queries + (size_t)members[i] * ix->dim, (size_t)ix->dim * sizeof(float));
-    const int rc = search_rows_host(ix, cq.data(), (int)nm, k, normalize_queries, list_rows + list_offsets[l],
-                                    list_offsets[l + 1] - list_offsets[l], ci.data(), cs.data(), true);
-    if (rc) return rc;
-    for (size_t i = 0; i < nm; ++i) {
-      memcpy(out_idx + (size_t)members[i] * k, &ci[i * k], (size_t)k * sizeof(int64_t));
-      memcpy(out_score + (size_t)members[i] * k, &cs[i * k], (size_t)k * sizeof(float));
-    }
-  }
-  return WDBX_OK;
+  // the longer lists (each has queries: rowlists_plan), each with its queries in the caller's order, through the call that
+  // existed before; the lock stays held
+  return for_each_class(nq, ix->dim, k, queries, query_list, plan.fallback_lists, out_idx, out_score,
+                        [&](int32_t l, int nm, const float* cq, int64_t* ci, float* cs) {
+                          return search_rows_host(ix, cq, nm, k, normalize_queries, list_rows + list_offsets[l],
+                                                  list_offsets[l + 1] - list_offsets[l], ci, cs, true);
+                        });
 } WDBX_CATCH
 
 // ---- range search (range_u8_eligible, pick_range_scan: host_index.h) -------------------------------
@@ -1146,39 +958,16 @@ static int range_search_host(wdbx_index* ix, const float* queries, int nq, const
     if (thresholds[q] != thresholds[q]) return fail(WDBX_E_INVALID, "threshold of query %d is NaN", q);
   std::lock_guard<std::mutex> lk(ix->mu);
   DeviceGuard g(ix->device);
-  struct MaskScope {
-    wdbx_index* ix;
-    bool set = false;
-    ~MaskScope() {
-      if (set) ix->active_mask = nullptr;
-    }
-  } scope{ix};
+  MaskScope scope(ix);
   int rc;
   out_offsets[0] = 0;
   if (ix->n == 0) {
     for (int q = 0; q < nq; ++q) out_offsets[q + 1] = 0;
     return WDBX_OK;
   }
-  if (mask_words) {
-    const size_t words = (size_t)((ix->n + 31) / 32);
-    if (mask_word_count < words)
-      return fail(WDBX_E_INVALID, "row mask of %llu words for %llu rows (%zu words needed)", (u64)mask_word_count, (u64)ix->n, words);
-    if ((rc = grow((void**)&ix->d_mask, &ix->mask_bytes, words * sizeof(uint32_t)))) return rc;
-    HIP_TRY(hipMemcpyAsync(ix->d_mask, mask_words, words * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
-    ix->active_mask = ix->d_mask;
-    scope.set = true;
-  }
-  const size_t q_bytes = (size_t)nq * ix->pitch * sizeof(float);
-  if ((rc = grow((void**)&ix->d_q, &ix->q_bytes, q_bytes))) return rc;
-  if (ix->pitch == ix->dim) {
-    HIP_TRY(hipMemcpyAsync(ix->d_q, queries, q_bytes, hipMemcpyHostToDevice, ix->stream));
-  } else {
-    HIP_TRY(hipMemsetAsync(ix->d_q, 0, q_bytes, ix->stream));
-    HIP_TRY(hipMemcpy2DAsync(ix->d_q, (size_t)ix->pitch * sizeof(float), queries, (size_t)ix->dim * sizeof(float),
-                             (size_t)ix->dim * sizeof(float), nq, hipMemcpyHostToDevice, ix->stream));
-  }
+  if (mask_words && ((rc = check_mask_words(ix->n, mask_word_count)) || (rc = scope.set(mask_words)))) return rc;
+  if ((rc = upload_queries(ix, queries, (uint64_t)nq, normalize_queries))) return rc;
   const bool l2 = ix->metric == WDBX_METRIC_L2;
-  if (normalize_queries && !l2 && (rc = launch_normalize(ix, ix->d_q, (uint64_t)nq))) return rc;
   const bool u8 = range_u8_eligible(ix) && prepare_u8_shadow(ix);
   if (u8 && l2 && (rc = ensure_row_norms(ix))) return rc;
   ix->last_range_path = u8 ? 2 : 0;
@@ -1410,16 +1199,11 @@ int wdbx_index_search_batch_masked_device(wdbx_index* ix, const float* d_queries
   DeviceGuard g(ix->device);
   if (!gemm_eligible(ix, std::max(nq, (int)ix->opt_gemm_min_nq), k))
     return fail(WDBX_E_STATE, "batched MFMA path needs >= %lld rows and k*1024 <= rows", (long long)ix->opt_gemm_min_rows);
-  const uint64_t words = (ix->n + 31) / 32;
-  if (mask_word_count < words)
-    return fail(WDBX_E_INVALID, "row mask of %llu words for %llu rows (%llu words needed)", (u64)mask_word_count, (u64)ix->n, (u64)words);
-  struct MaskScope {
-    wdbx_index* ix;
-    ~MaskScope() { ix->active_mask = nullptr; }
-  } scope{ix};
   int rc;
+  if ((rc = check_mask_words(ix->n, mask_word_count))) return rc;
+  MaskScope scope(ix);
   const bool tiles = masked_tiles_ready(ix, k);
-  if ((rc = set_active_mask(ix, mask_words))) return rc;
+  if ((rc = scope.set(mask_words))) return rc;
   if (tiles) return enqueue_search_gemm(ix, d_queries, nq, k, d_out_idx, d_out_score);
   ix->last_batch_masked = false;
   return enqueue_search(ix, d_queries, nq, k, d_out_idx, d_out_score, SEARCH_FINAL);
@@ -1825,26 +1609,17 @@ static int group_search_host(wdbx_group* g, const float* queries, int nq, int k,
   if (k < 1 || k > WDBX_MAX_K) return fail(WDBX_E_INVALID, "k=%d outside [1, %d]", k, WDBX_MAX_K);
   std::lock_guard<std::mutex> lk(g->mu);
   GroupLocks locks(g);  // held until the results are on the host: the shards' own callers wait, as on any busy handle
+  int rc;
   if (masks && mask_word_counts)
-    for (size_t s = 0; s < g->sh.size(); ++s) {
-      const uint64_t need = (g->sh[s].ix->n + 31) / 32;
-      if (masks[s] && mask_word_counts[s] < need)
-        return fail(WDBX_E_INVALID, "shard %zu: row mask of %llu words for %llu rows (%llu words needed)", s, (u64)mask_word_counts[s],
-                    (u64)g->sh[s].ix->n, (u64)need);
-    }
+    for (size_t s = 0; s < g->sh.size(); ++s)
+      if (masks[s] && (rc = check_mask_words(g->sh[s].ix->n, mask_word_counts[s], ("shard " + std::to_string(s) + ": row mask").c_str())))
+        return rc;
   wdbx_index* root = g->sh[0].ix;
   const size_t elems = (size_t)nq * k_out, pitch = (size_t)root->pitch, dim = (size_t)root->dim;
-  int rc;
   // small calls (the facade's lone queries): queries and results through mapped host memory, no memcpy calls at all
   const bool cosine_norm = normalize_queries && root->metric == WDBX_METRIC_COSINE;
   if (g->h_stage && !cosine_norm && (size_t)nq * pitch * sizeof(float) <= GROUP_STAGE_Q && elems * sizeof(int64_t) <= GROUP_STAGE_IDX) {
-    float* hq = (float*)g->h_stage;
-    if (pitch == dim) {
-      memcpy(hq, queries, (size_t)nq * dim * sizeof(float));
-    } else {
-      memset(hq, 0, (size_t)nq * pitch * sizeof(float));
-      for (int q = 0; q < nq; ++q) memcpy(hq + (size_t)q * pitch, queries + (size_t)q * dim, dim * sizeof(float));
-    }
+    pad_queries((float*)g->h_stage, pitch, queries, dim, (size_t)nq);
     // a lone query: no repair launches are queued (two per shard); each shard leaves an overflow word instead, and the rare
     // call that finds one set is run again with the repairs in place
     volatile uint32_t* const flags = (volatile uint32_t*)(g->h_stage + GROUP_STAGE_Q + GROUP_STAGE_IDX + GROUP_STAGE_SCORE);
@@ -1876,15 +1651,7 @@ static int group_search_host(wdbx_group* g, const float* queries, int nq, int k,
     // device reads the staged queries any more and the results are in host memory)
     if (polled) {
       HIP_TRY(hipEventRecord(g->done_ev, root->stream));
-      for (uint32_t spins = 1;; ++spins) {
-        if (flags[64] == done_seq) break;
-        if ((spins & 0xFFFu) == 0) {
-          const hipError_t e = hipEventQuery(g->done_ev);
-          if (e == hipSuccess) break;
-          if (e != hipErrorNotReady) HIP_TRY(hipEventSynchronize(g->done_ev));
-        }
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
+      if ((rc = wait_done_word(flags + 64, done_seq, g->done_ev))) return rc;
     } else {
       HIP_TRY(hipStreamSynchronize(root->stream));
     }
