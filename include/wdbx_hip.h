@@ -203,6 +203,51 @@ int wdbx_index_search_row_lists(wdbx_index* idx, const float* queries, int nq, i
                                 const int32_t* query_list,     /* [nq]: which list query i is ranked in */
                                 int64_t* out_idx, float* out_score);
 
+/* ---- distinct search: exact top-k with at most one row per label --------------- */
+/* A label is any 32-bit value a caller attaches to a row (a document id for a corpus of chunks; Qdrant's search groups,
+ * Elasticsearch's collapse and Milvus' grouping search answer the same question, the reference has nothing: it cuts a top-k
+ * of rows, vector_store.py:323-345).  Labels need not be dense and the rows of one label need not be adjacent.  Rows added by
+ * wdbx_index_add / wdbx_index_fill_synthetic start as WDBX_LABEL_NONE: each such row is a label of its own.
+ * wdbx_index_set_rows leaves labels alone, wdbx_index_compact moves them with their rows, wdbx_index_clear drops them,
+ * wdbx_index_reserve keeps them.  A range reaching past the row count is WDBX_E_INVALID (checked under the handle's lock).
+ * The handle keeps the labels on the host and, built at the next distinct search after any label or row-count change, a
+ * device-resident label order (every row sorted by (label, row), the dense label index of each position, the item tables of
+ * the kernels); it counts in get_option "device_bytes_resident". */
+#define WDBX_LABEL_NONE 0xFFFFFFFFu /* the row is a label of its own */
+int wdbx_index_set_labels(wdbx_index* idx, uint64_t first_row, uint64_t n, const uint32_t* labels);
+int wdbx_index_get_labels(wdbx_index* idx, uint64_t first_row, uint64_t n, uint32_t* out_labels);
+
+/* For each of nq host queries [nq, dim]: take every live row the mask allows (mask_words NULL = every row; else
+ * mask_word_count words, at least ceil(rows / 32)) whose score is not NaN, rank them by (score descending, row ascending) --
+ * L2: (distance ascending, row ascending), positive squared distances --, keep the FIRST row of each label, cut at k.
+ * Blocking, host buffers.  Unused slots hold row -1, score 0 and label WDBX_LABEL_NONE; out_label (may be NULL) receives each
+ * slot's stored label.  A handle on which no label was ever set answers exactly as wdbx_index_search (or
+ * wdbx_index_search_masked_n with a mask) does, bit for bit, whatever the options say (path 1).
+ *   WDBX_E_INVALID: k outside [1, WDBX_MAX_K], nq < 1, a null query or result buffer, a mask shorter than ceil(rows / 32)
+ *   words -- the conditions of wdbx_index_search_masked_n.  A refused call leaves the handle usable.
+ *   Routes (get_option "last_distinct_path"): 0 = nothing launched (empty index, every slot -1); 1 = the over-fetch alone
+ *   answered every query; 2 = the over-fetch, then the full pass for the queries that fell short; 3 = the full pass for all.
+ *   Over-fetch (option "distinct_overfetch", default 4, 0 = never): the ordinary search -- the entry wdbx_index_search /
+ *   _masked_n use -- for k' = min(rows, WDBX_MAX_K, distinct_overfetch * k), walked per query on the host keeping the first row
+ *   of each label.  A query whose walk finds k labels, or whose k' reached every eligible row, is finished: exact, because
+ *   any row outside the top-k' ranks below all of them.
+ *   Full pass: waves walk spans of 64 positions of the label order, score each fetched row once against a block of up to 8
+ *   queries and keep the best key per (query, label run inside the span); a second kernel takes the best key of each label
+ *   and ranks the labels (per-workgroup top-k lists and the merge kernel below option "select_min_k", a key per label and
+ *   the radix-select chain from it).  Every key has exactly one writer: answers are bit-identical from run to run.  Rounds of at
+ *   most 256 queries keep their scratch within 256 MiB.  The scoring launches count as scan launches in
+ *   wdbx_index_profile_read.
+ *   Scores: a slot answered by the over-fetch (every slot on path 1; on path 2 the slots of the queries that did not fall
+ *   short) carries the score wdbx_index_search returned for that row; a slot answered by the full pass (every slot on path 3;
+ *   on path 2 the slots of the short queries) carries rescore_kernel's arithmetic, bit-identical to wdbx_index_search_rows
+ *   and wdbx_index_range_search for the same row.  The rows are the same either way.
+ *   get_option, read-only: "last_distinct_items" / "last_distinct_labels" the items and labels of the label order the call
+ *   used (0 when it was not needed), "last_distinct_short" the queries the full pass served.
+ *   The call holds the handle's mutex to its end. */
+int wdbx_index_search_distinct(wdbx_index* idx, const float* queries, int nq, int k, int normalize_queries,
+                               const uint32_t* mask_words, uint64_t mask_word_count, /* NULL = every row */
+                               int64_t* out_idx, float* out_score, uint32_t* out_label /* may be NULL */);
+
 /* ---- range search: every row within a similarity, no k ----------------------- */
 /* every row whose score reaches thresholds[q] (cosine/IP: score >= t; L2: squared distance <= t), exact fp32,
  * per query sorted like wdbx_index_search; replaces faiss' IndexFlat range_search, which the reference never reaches

@@ -170,6 +170,19 @@ struct wdbx_index {
   size_t rl_bytes = 0;
   int last_lists_path = 0;     // 0 nothing launched, 1 the batched pass only, 2 both, 3 list by list only
   int64_t last_lists_items = 0, last_lists_rounds = 0;
+  // distinct search (wdbx_index_search_distinct): the labels of rows [0, labels.size()) on the host (rows behind them are
+  // WDBX_LABEL_NONE; empty = no label was ever set) and the device copy of the label order (host_labels.h) in one allocation:
+  // rows | dense label of each position | first item of each span | first item of each label.  Rebuilt by the next full pass
+  // after a label change (lab_valid) or a row-count change (lab_n).  The pass's keys live in d_sub_keys, its lists in d_partials.
+  std::vector<uint32_t> labels;
+  char* d_lab = nullptr;
+  size_t lab_bytes = 0;
+  bool lab_valid = false;
+  uint64_t lab_n = 0;
+  uint32_t lab_items = 0, lab_labels = 0, lab_spans = 0;
+  size_t lab_off_dense = 0, lab_off_span = 0, lab_off_label = 0;
+  int last_distinct_path = 0;  // 0 nothing launched, 1 over-fetch alone, 2 over-fetch + full pass for the short queries, 3 full pass
+  int64_t last_distinct_items = 0, last_distinct_labels = 0, last_distinct_short = 0;
   // profiling
   bool profile = false;
   EventPool scan_ev, merge_ev, gemm_ev, sample_ev;
@@ -180,7 +193,7 @@ struct wdbx_index {
           opt_gemm8_refine = 1, opt_scan8_sample4 = 1, opt_gemm_l2 = 1, opt_gemm_l2_i8 = 1, opt_force_ragged = 0,
           opt_gemm_ct = 0, opt_wg_merge = 1, opt_zero_copy = 1, opt_lone_host_select = 1, opt_lds_lists = 0,
           opt_merge_fast = 1, opt_poll_done = 1, opt_scan_one_grid = 1, opt_select_min_k = 200, opt_gemm_min_nq = 4, opt_gemm_min_rows = 65536, opt_gemm_min_work = 800000,
-          opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0, opt_gemm_masked = 1, opt_rows_keys_max = 8192;
+          opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0, opt_gemm_masked = 1, opt_rows_keys_max = 8192, opt_distinct_overfetch = 4;
 };
 
 struct DeviceGuard {

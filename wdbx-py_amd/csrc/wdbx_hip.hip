@@ -30,6 +30,10 @@
 //                           row, per-workgroup top-k lists or a key per listed row
 //   kernels_rowlists.h      rowlists_kernel: the same scores for a call with one row list PER QUERY (wdbx_index_search_row_lists),
 //                           one workgroup per (chunk of a list, block of its queries) work item of host_rowlists.h
+//   kernels_labels.h        label_keys_kernel, label_rank_kernel: the full pass of wdbx_index_search_distinct (at most one row per
+//                           label): the best key of each label run inside a span of the label order, then of each label, ranked
+//   host_labels.h           the label order of a handle (rows sorted by (label, row), items, tables), the over-fetch's host walk, the
+//                           full pass's rounds, grids and scratch
 //   host_multimask.h        a call with one row mask per query: the placement of its queries in the int8 tiles' query blocks
 //   host_calls.h            what the blocking entry points share, device-free: allowed rows of a mask, padded query copies, the host
 //                           ranking of a lone query's keys, the class-by-class fallback loop
@@ -74,6 +78,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_calls.h"  // (device-free as well: mask popcount, padded query copies, host ranking of keys, class-by-class loop)
 #include "host_subset.h"  // (device-free as well: row-list validation, route and grid sizing of a search among listed rows)
 #include "host_multimask.h"  // (device-free as well: where the queries of a call with a mask per query sit in the tile blocks)
+#include "host_labels.h"  // (device-free as well: label order, items, over-fetch walk, rounds and scratch of a distinct search)
 #include "host_rowlists.h"  // (device-free as well: slots, rounds, query blocks and work items of a call with a row list per query)
 
 #define HIP_TRY(expr)                                                                        \
@@ -106,6 +111,8 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "kernels_range.h"
 #include "kernels_subset.h"
 #include "kernels_rowlists.h"
+#include "kernels_labels.h"
+static_assert(LABEL_SPAN_DEV == LABEL_SPAN, "the kernels walk the spans the host built");
 #include "host_index.h"
 #include "host_group.h"
 
@@ -124,7 +131,7 @@ static uint64_t device_bytes_resident(const wdbx_index* ix) {
   b += ix->qb8_bytes + ix->qpar_bytes + ix->pairs_bytes + ix->pair_count_bytes + ix->cnmax_bytes;
   b += ix->rcand_bytes + ix->rkeys_bytes + ix->rcnt_bytes + ix->rthr_bytes;
   b += ix->rows6_bytes + ix->count6_bytes;
-  b += ix->sub_ids_bytes + ix->sub_keys_bytes + ix->mm_bytes + ix->rl_bytes;
+  b += ix->sub_ids_bytes + ix->sub_keys_bytes + ix->mm_bytes + ix->rl_bytes + ix->lab_bytes;
   return b;
 }
 
@@ -202,7 +209,7 @@ void wdbx_index_destroy(wdbx_index* ix) try {
                     ix->d_state, ix->d_cn, ix->d_cnmax, ix->d_qb16, ix->d_rows16, ix->d_rows8, ix->d_scale8, ix->d_selsrc,
                     ix->d_gmax, ix->d_qn, ix->d_rows8g, ix->d_groups8, ix->d_gbad8, ix->d_gref8, ix->d_over_list, ix->d_qb8,
                     ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr, ix->d_rows6, ix->d_count6,
-                    ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys, ix->d_mm, ix->d_rl};
+                    ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys, ix->d_mm, ix->d_rl, ix->d_lab};
     for (void* p : bufs)
       if (p) (void)hipFree(p);
     if (ix->h_stage) (void)hipHostFree(ix->h_stage);
@@ -250,6 +257,8 @@ int wdbx_index_clear(wdbx_index* ix) try {
   ix->shadow6_rows = 0;
   ix->shadowg_rows = 0;
   ix->shadowg_tail_n = ~0ull;
+  ix->labels.clear();  // (back to "no label was ever set")
+  ix->lab_valid = false;
   return WDBX_OK;
 } WDBX_CATCH
 
@@ -360,6 +369,12 @@ int wdbx_index_compact(wdbx_index* ix, const uint64_t* src_rows, uint64_t n_keep
     if (d_src) (void)hipFree(d_src);
     if (e != hipSuccess) return fail(WDBX_E_HIP, "compaction failed: %s (the rows behind row %llu are undefined)", hipGetErrorString(e), (u64)first_moved);
   }
+  if (!ix->labels.empty()) {  // the labels move with their rows (src_rows is increasing: in place, front to back)
+    ix->labels.resize((size_t)ix->n, WDBX_LABEL_NONE);
+    for (uint64_t i = first_moved; i < n_keep; ++i) ix->labels[(size_t)i] = ix->labels[(size_t)src_rows[i]];
+    ix->labels.resize((size_t)n_keep);
+  }
+  ix->lab_valid = false;
   ix->n = n_keep;
   ix->cn_rows = std::min(ix->cn_rows, first_moved);
   ix->shadow_rows = std::min(ix->shadow_rows, first_moved);
@@ -938,6 +953,224 @@ int wdbx_index_search_row_lists(wdbx_index* ix, const float* queries, int nq, in
                           return search_rows_host(ix, cq, nm, k, normalize_queries, list_rows + list_offsets[l],
                                                   list_offsets[l + 1] - list_offsets[l], ci, cs, true);
                         });
+} WDBX_CATCH
+
+// ---- distinct search: at most one row per label (host_labels.h, kernels_labels.h) -------------
+int wdbx_index_set_labels(wdbx_index* ix, uint64_t first_row, uint64_t n, const uint32_t* labels) try {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  if (n && !labels) return fail(WDBX_E_INVALID, "labels is null");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (first_row > ix->n || n > ix->n - first_row)
+    return fail(WDBX_E_INVALID, "rows [%llu, +%llu) outside the %llu stored rows", (u64)first_row, (u64)n, (u64)ix->n);
+  if (!n) return WDBX_OK;
+  ix->labels.resize((size_t)ix->n, WDBX_LABEL_NONE);  // (rows added since the last call start as NONE)
+  std::copy(labels, labels + n, ix->labels.begin() + (size_t)first_row);
+  ix->lab_valid = false;
+  return WDBX_OK;
+} WDBX_CATCH
+
+int wdbx_index_get_labels(wdbx_index* ix, uint64_t first_row, uint64_t n, uint32_t* out_labels) try {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  if (n && !out_labels) return fail(WDBX_E_INVALID, "out_labels is null");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (first_row > ix->n || n > ix->n - first_row)
+    return fail(WDBX_E_INVALID, "rows [%llu, +%llu) outside the %llu stored rows", (u64)first_row, (u64)n, (u64)ix->n);
+  for (uint64_t i = 0; i < n; ++i)
+    out_labels[i] = first_row + i < ix->labels.size() ? ix->labels[(size_t)(first_row + i)] : WDBX_LABEL_NONE;
+  return WDBX_OK;
+} WDBX_CATCH
+
+// the device copy of the label order, for the labels and the row count as they are now (under the handle's mutex)
+static int ensure_label_order(wdbx_index* ix) {
+  if (ix->lab_valid && ix->lab_n == ix->n) return WDBX_OK;
+  LabelOrder lo;
+  label_order_build(ix->labels.data(), std::min<uint64_t>(ix->labels.size(), ix->n), ix->n, &lo);
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t rows_b = (size_t)ix->n * sizeof(uint32_t);
+  const size_t off_dense = up(rows_b), off_span = off_dense + up(rows_b),
+               off_label = off_span + up(lo.span_item0.size() * sizeof(uint32_t)),
+               total = off_label + lo.label_item0.size() * sizeof(uint32_t);
+  ix->lab_valid = false;
+  int rc = grow((void**)&ix->d_lab, &ix->lab_bytes, total);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(ix->d_lab, lo.rows.data(), rows_b, hipMemcpyHostToDevice, ix->stream));
+  HIP_TRY(hipMemcpyAsync(ix->d_lab + off_dense, lo.dense.data(), rows_b, hipMemcpyHostToDevice, ix->stream));
+  HIP_TRY(hipMemcpyAsync(ix->d_lab + off_span, lo.span_item0.data(), lo.span_item0.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+  HIP_TRY(hipMemcpyAsync(ix->d_lab + off_label, lo.label_item0.data(), lo.label_item0.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));  // (the host tables go away with this call)
+  ix->lab_off_dense = off_dense;
+  ix->lab_off_span = off_span;
+  ix->lab_off_label = off_label;
+  ix->lab_items = lo.n_items;
+  ix->lab_labels = lo.n_labels;
+  ix->lab_spans = lo.n_spans;
+  ix->lab_n = ix->n;
+  ix->lab_valid = true;
+  return WDBX_OK;
+}
+
+// The full pass for nq host queries, under the handle's mutex, on a non-empty index: per round (distinct_plan) label_keys_kernel
+// (bracketed as a scan launch), label_rank_kernel and merge_kernel over its partial lists, or per query the radix-select chain
+// over its label keys (bracketed as merge launches).  No memset: every item key, list entry and label key is written.
+static int distinct_full_pass(wdbx_index* ix, const float* queries, int nq, int k, int normalize_queries, const uint32_t* mask_words,
+                              int64_t* out_idx, float* out_score) {
+  int rc;
+  if ((rc = ensure_label_order(ix))) return rc;
+  ix->last_distinct_items = ix->lab_items;
+  ix->last_distinct_labels = ix->lab_labels;
+  const DistinctPlan dp = distinct_plan(ix->lab_items, ix->lab_labels, ix->lab_spans, nq, k, ix->cu_count, ix->opt_select_min_k);
+  const size_t elems = (size_t)nq * k;
+  if ((rc = ensure_out(ix, elems))) return rc;
+  if ((rc = grow((void**)&ix->d_sub_keys, &ix->sub_keys_bytes, (dp.keys_u64 + (dp.select ? dp.rank_u64 : 0)) * sizeof(u64)))) return rc;
+  if (dp.select) {
+    if ((rc = grow((void**)&ix->d_sel, &ix->sel_bytes, (size_t)WDBX_MAX_K * sizeof(u64)))) return rc;
+    if ((rc = grow((void**)&ix->d_state, &ix->state_bytes, sizeof(SelectState)))) return rc;
+  } else if ((rc = grow((void**)&ix->d_partials, &ix->partials_bytes, dp.rank_u64 * sizeof(u64)))) {
+    return rc;
+  }
+  if ((rc = upload_queries(ix, queries, (uint64_t)nq, normalize_queries))) return rc;
+  MaskScope scope(ix);
+  if (mask_words && (rc = scope.set(mask_words))) return rc;
+  const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
+  const label_keys_fn kfn = pick_label_keys(ix->metric, dp.qb, pitch4);
+  if (!kfn) return fail(WDBX_E_STATE, "no label-keys instance with %d queries per block", dp.qb);
+  const bool reg = k <= 128 && !ix->opt_lds_lists;
+  const label_rank_fn rfn = pick_label_rank(dp.select ? 2 : (reg ? 1 : 0));
+  if (dp.lds >= 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)rfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dp.lds));
+  u64* const d_label_keys = ix->d_sub_keys + dp.keys_u64;  // (select route)
+  for (int q0 = 0; q0 < nq; q0 += dp.round) {
+    const int b = std::min(dp.round, nq - q0);
+    LabelKeysArgs a = {};
+    a.rows = (const f4*)ix->d_rows;
+    a.queries = (const f4*)(ix->d_q + (size_t)q0 * ix->pitch);
+    a.order = (const uint32_t*)ix->d_lab;
+    a.dense = (const uint32_t*)(ix->d_lab + ix->lab_off_dense);
+    a.span_item0 = (const uint32_t*)(ix->d_lab + ix->lab_off_span);
+    a.mask = ix->active_mask;
+    a.keys = ix->d_sub_keys;
+    a.key_stride = ix->lab_items;
+    a.n = (uint32_t)ix->n;
+    a.n_spans = ix->lab_spans;
+    a.pitch4 = pitch4;
+    a.nq = (uint32_t)b;
+    const uint32_t qblocks = (uint32_t)((b + dp.qb - 1) / dp.qb);
+    if ((rc = record(ix->scan_ev, ix->profile, ix->stream, true))) return rc;
+    hipLaunchKernelGGL(kfn, dim3(dp.score_blocks, qblocks), dim3(256), 0, ix->stream, a);
+    HIP_TRY(hipGetLastError());
+    if ((rc = record(ix->scan_ev, ix->profile, ix->stream, false))) return rc;
+    LabelRankArgs r = {};
+    r.keys = ix->d_sub_keys;
+    r.key_stride = ix->lab_items;
+    r.label_item0 = (const uint32_t*)(ix->d_lab + ix->lab_off_label);
+    r.n_labels = ix->lab_labels;
+    r.out = dp.select ? d_label_keys : ix->d_partials;
+    r.k = k;
+    if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
+    hipLaunchKernelGGL(rfn, dim3(dp.rank_blocks, (uint32_t)b), dim3(256), dp.lds, ix->stream, r);
+    HIP_TRY(hipGetLastError());
+    if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
+    MergeArgs m = {};
+    m.k = k;
+    m.metric = ix->metric;
+    if (dp.select) {
+      const uint32_t sgrid = radix_select_grid(ix->lab_labels, ix->cu_count);
+      for (int q = 0; q < b; ++q) {
+        if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
+        HIP_TRY(enqueue_radix_select(ix->stream, (const u64*)d_label_keys + (size_t)q * ix->lab_labels, (u64)ix->lab_labels, nullptr,
+                                     (SelectState*)ix->d_state, (u64*)ix->d_sel, (uint32_t)k, sgrid));
+        m.out_idx = ix->d_oidx + (size_t)(q0 + q) * k;
+        m.out_score = ix->d_oscore + (size_t)(q0 + q) * k;
+        HIP_TRY(enqueue_sort_out(ix->stream, (const u64*)ix->d_sel, (const SelectState*)ix->d_state, m));
+        if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
+      }
+      continue;
+    }
+    m.in = ix->d_partials;
+    m.q_stride = (uint64_t)k * dp.rank_blocks;
+    m.i_stride = dp.rank_blocks;
+    m.p_stride = 1;
+    m.P = dp.rank_blocks;
+    m.list_len = k;
+    m.out_idx = ix->d_oidx + (size_t)q0 * k;
+    m.out_score = ix->d_oscore + (size_t)q0 * k;
+    if ((rc = launch_merge(ix, m, b))) return rc;
+  }
+  return download_results(ix, elems, out_idx, out_score);
+}
+
+int wdbx_index_search_distinct(wdbx_index* ix, const float* queries, int nq, int k, int normalize_queries, const uint32_t* mask_words,
+                               uint64_t mask_word_count, int64_t* out_idx, float* out_score, uint32_t* out_label) try {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  if (nq < 1) return fail(WDBX_E_INVALID, "nq=%d", nq);
+  if (!queries || !out_idx || !out_score) return fail(WDBX_E_INVALID, "null buffer");
+  if (k < 1 || k > WDBX_MAX_K) return fail(WDBX_E_INVALID, "k=%d outside [1, %d]", k, WDBX_MAX_K);
+  std::unique_lock<std::mutex> lk(ix->mu);
+  DeviceGuard g(ix->device);
+  int rc;
+  const size_t elems = (size_t)nq * k;
+  ix->last_distinct_path = DISTINCT_NONE;
+  ix->last_distinct_items = ix->last_distinct_labels = ix->last_distinct_short = 0;
+  if (ix->n == 0) {  // every slot empty, as wdbx_index_search leaves them
+    for (size_t i = 0; i < elems; ++i) {
+      out_idx[i] = -1;
+      out_score[i] = 0.0f;
+      if (out_label) out_label[i] = WDBX_LABEL_NONE;
+    }
+    return WDBX_OK;
+  }
+  if (mask_words && (rc = check_mask_words(ix->n, mask_word_count))) return rc;
+  if (ix->n >= 0xFFFFFF00ull) return fail(WDBX_E_INVALID, "shard holds too many rows for 32-bit row keys");
+  const uint32_t* const labels = ix->labels.data();
+  const uint64_t n_set = std::min<uint64_t>(ix->labels.size(), ix->n);
+  if (ix->labels.empty()) {  // no label was ever set: every row its own label, the ordinary search IS the answer
+    if ((rc = search_host(ix, queries, nq, k, normalize_queries, mask_words, mask_word_count, out_idx, out_score, &lk))) return rc;
+    if (out_label) std::fill(out_label, out_label + elems, WDBX_LABEL_NONE);
+    ix->last_distinct_path = DISTINCT_OVERFETCH;
+    return WDBX_OK;
+  }
+  // the over-fetch: the ordinary top-k', walked per query; the queries whose walk is not final are short
+  const int kp = distinct_overfetch_k(ix->n, k, ix->opt_distinct_overfetch, WDBX_MAX_K);
+  std::vector<int> short_q;
+  if (kp) {
+    std::vector<int64_t> fi((size_t)nq * kp);
+    std::vector<float> fs((size_t)nq * kp);
+    if ((rc = search_host(ix, queries, nq, kp, normalize_queries, mask_words, mask_word_count, fi.data(), fs.data(), &lk))) return rc;
+    for (int q = 0; q < nq; ++q)
+      if (!distinct_walk(fi.data() + (size_t)q * kp, fs.data() + (size_t)q * kp, kp, ix->n, labels, n_set, k, out_idx + (size_t)q * k,
+                         out_score + (size_t)q * k, out_label ? out_label + (size_t)q * k : nullptr))
+        short_q.push_back(q);
+    if (short_q.empty()) {
+      ix->last_distinct_path = DISTINCT_OVERFETCH;
+      return WDBX_OK;
+    }
+  } else {
+    short_q.resize((size_t)nq);
+    for (int q = 0; q < nq; ++q) short_q[(size_t)q] = q;
+  }
+  ix->last_distinct_short = (int64_t)short_q.size();
+  // the full pass for the short queries, gathered; their slots are overwritten
+  const int ns = (int)short_q.size();
+  std::vector<float> sq;
+  const float* fq = queries;
+  if (ns < nq) {
+    sq.resize((size_t)ns * ix->dim);
+    for (int i = 0; i < ns; ++i) memcpy(sq.data() + (size_t)i * ix->dim, queries + (size_t)short_q[(size_t)i] * ix->dim, (size_t)ix->dim * sizeof(float));
+    fq = sq.data();
+  }
+  std::vector<int64_t> ri((size_t)ns * k);
+  std::vector<float> rs((size_t)ns * k);
+  if ((rc = distinct_full_pass(ix, fq, ns, k, normalize_queries, mask_words, ri.data(), rs.data()))) return rc;
+  for (int i = 0; i < ns; ++i) {
+    const size_t o = (size_t)short_q[(size_t)i] * k;
+    for (int s = 0; s < k; ++s) {
+      const int64_t r = ri[(size_t)i * k + s];
+      out_idx[o + s] = r;
+      out_score[o + s] = rs[(size_t)i * k + s];
+      if (out_label) out_label[o + s] = (r >= 0 && (uint64_t)r < n_set) ? labels[r] : WDBX_LABEL_NONE;
+    }
+  }
+  ix->last_distinct_path = kp ? DISTINCT_BOTH : DISTINCT_FULL;
+  return WDBX_OK;
 } WDBX_CATCH
 
 // ---- range search (range_u8_eligible, pick_range_scan: host_index.h) -------------------------------
@@ -1772,6 +2005,7 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"gemm_sample_div", &wdbx_index::opt_gemm_sample_div},
     {"gemm_masked", &wdbx_index::opt_gemm_masked},
     {"rows_keys_max", &wdbx_index::opt_rows_keys_max},
+    {"distinct_overfetch", &wdbx_index::opt_distinct_overfetch},
 };
 
 static int64_t* option_slot(wdbx_index* ix, const char* name) { return find_option(ix, kOptions, name); }
@@ -1819,6 +2053,10 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "last_lists_path")) return *value = ix->last_lists_path, WDBX_OK;
   if (name && !strcmp(name, "last_lists_items")) return *value = ix->last_lists_items, WDBX_OK;
   if (name && !strcmp(name, "last_lists_rounds")) return *value = ix->last_lists_rounds, WDBX_OK;
+  if (name && !strcmp(name, "last_distinct_path")) return *value = ix->last_distinct_path, WDBX_OK;
+  if (name && !strcmp(name, "last_distinct_items")) return *value = ix->last_distinct_items, WDBX_OK;
+  if (name && !strcmp(name, "last_distinct_labels")) return *value = ix->last_distinct_labels, WDBX_OK;
+  if (name && !strcmp(name, "last_distinct_short")) return *value = ix->last_distinct_short, WDBX_OK;
   if (name && !strcmp(name, "last_sample_qn")) return *value = ix->last_sample_qn, WDBX_OK;
   if (name && !strcmp(name, "last_batch_repaired")) return *value = ix->last_batch_repaired ? 1 : 0, WDBX_OK;
   if (name && !strcmp(name, "last_batch_masked")) return *value = ix->last_batch_masked, WDBX_OK;

@@ -38,6 +38,8 @@ _i64p = C.POINTER(C.c_int64)
 _f32p = C.POINTER(C.c_float)
 _dblp = C.POINTER(C.c_double)
 
+LABEL_NONE = 0xFFFFFFFF  # WDBX_LABEL_NONE: the row is a label of its own
+
 # name -> (restype, argtypes); the one place the ABI is spelled out for Python.
 SIGNATURES = {
     "wdbx_hip_version": (C.c_int, []),
@@ -66,6 +68,10 @@ SIGNATURES = {
     "wdbx_index_search_rows": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _u64p, C.c_uint64, _i64p, _f32p]),
     "wdbx_index_search_row_lists": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _u64p, _u64p, C.c_int,
                                               C.POINTER(C.c_int32), _i64p, _f32p]),
+    "wdbx_index_set_labels": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "wdbx_index_get_labels": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "wdbx_index_search_distinct": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
+                                             _i64p, _f32p, C.POINTER(C.c_uint32)]),
     "wdbx_index_range_search": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
                                           C.c_uint64, _u64p, _i64p, _f32p]),
     "wdbx_device_alloc": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -377,6 +383,36 @@ class NativeIndex:
                                                      which.ctypes.data_as(C.POINTER(C.c_int32)), idx.ctypes.data_as(_i64p),
                                                      score.ctypes.data_as(_f32p)))
         return idx, score
+
+    # -- distinct search: at most one row per label --
+    def set_labels(self, first_row: int, labels) -> None:
+        """Labels (any uint32; :data:`LABEL_NONE` = the row is a label of its own) of rows ``first_row ..``."""
+        lab = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+        _check(self._lib.wdbx_index_set_labels(self._h, int(first_row), lab.size, lab.ctypes.data_as(C.POINTER(C.c_uint32))))
+
+    def get_labels(self, first_row: int, n: int) -> np.ndarray:
+        out = np.empty(int(n), np.uint32)
+        _check(self._lib.wdbx_index_get_labels(self._h, int(first_row), int(n), out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def search_distinct(self, queries, k: int, normalize_queries: bool = False,
+                        mask_words: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The exact top-``k`` with at most one row per label: per query the rows ranked as :meth:`search` ranks them, the
+        first row of each label kept, cut at ``k``.  Returns ``(rows int64, scores f32, labels uint32)``, each ``[nq, k]``;
+        unused slots hold -1 / 0 / :data:`LABEL_NONE`.  ``mask_words`` as in :meth:`search`."""
+        q = _as_f32(queries, self.dim)
+        nq = q.shape[0]
+        idx = np.empty((nq, int(k)), np.int64)
+        score = np.empty((nq, int(k)), np.float32)
+        label = np.empty((nq, int(k)), np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        m = None if mask_words is None else np.ascontiguousarray(mask_words, dtype=np.uint32)
+        # (k, nq and the mask's length are checked by the library, the length under the handle's lock)
+        _check(self._lib.wdbx_index_search_distinct(self._h, q.ctypes.data_as(_f32p), nq, int(k), int(normalize_queries),
+                                                    None if m is None else m.ctypes.data_as(u32p), 0 if m is None else m.size,
+                                                    idx.ctypes.data_as(_i64p), score.ctypes.data_as(_f32p),
+                                                    label.ctypes.data_as(u32p)))
+        return idx, score, label
 
     def range_search(self, queries, thresholds, normalize_queries: bool = False,
                      mask_words: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:

@@ -55,11 +55,18 @@ def _render(results) -> Dict[str, Any]:
 
 async def search_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
     """``POST /api/v1/vectors/search`` (server.py:141-152): body ``{"query_vector": [...], "limit": 10, "threshold": 0.0,
-    "filter_metadata": null}`` -> ``{"results": [{"vector_id", "similarity", "metadata"}, ...]}``."""
+    "filter_metadata": null}`` -> ``{"results": [{"vector_id", "similarity", "metadata"}, ...]}``.  ``"distinct": true``
+    (extension; absent, null or false = the plain search): at most one result per value of the store's ``DISTINCT_KEY``
+    metadata field (``wdbx.vector_search_distinct_async``)."""
     limit, threshold, flt = _parse_common(payload)
     if "query_vector" not in payload:
         raise ValueError("query_vector is required")
     query = _vector(payload["query_vector"], "query_vector")
+    distinct = payload.get("distinct")
+    if distinct is not None and not isinstance(distinct, bool):
+        raise ValueError("distinct must be true, false or null")
+    if distinct:
+        return _render(await wdbx.vector_search_distinct_async(query, limit, threshold, flt))
     return _render(await wdbx.vector_search_async(query, limit, threshold, flt))
 
 

@@ -87,6 +87,9 @@ class WDBXConfig:
         # search_async callers that push down DIFFERENT filters with one limit share one call per shard with a row mask per
         # query (wdbx_index_search_multimask) instead of one call per filter; off until a measurement recommends it
         "ASYNC_COALESCE_FILTERS": False,
+        # distinct search (``vector_search_distinct``: at most one result per value of this metadata field, e.g. the document
+        # a chunk belongs to); None = off: nothing is labelled and no existing call changes
+        "DISTINCT_KEY": None,
     }
 
     def __init__(self, config_dict: Optional[Dict[str, Any]] = None, config_path: Optional[str] = None):

@@ -787,6 +787,42 @@ class HipFlatIndex(VectorIndex):
             return [[] for _ in range(len(queries))]
         return [self._map(i, s) for i, s in zip(*raw)]
 
+    # ---- distinct search (extension: at most one result per label, wdbx_index_search_distinct) ----
+    def set_labels(self, vector_ids, labels) -> int:
+        """Attach a 32-bit label to each named vector (``_native.LABEL_NONE`` = a label of its own); unknown and removed ids
+        are skipped.  Consecutive rows go to the library in one call.  Returns how many rows were labelled."""
+        row_of = self._row_of
+        pairs = sorted((r, int(lab)) for r, lab in ((row_of(v), lab) for v, lab in zip(vector_ids, labels)) if r is not None)
+        i = 0
+        while i < len(pairs):
+            j = i + 1
+            while j < len(pairs) and pairs[j][0] == pairs[j - 1][0] + 1:
+                j += 1
+            self._native.set_labels(pairs[i][0], np.fromiter((lab for _, lab in pairs[i:j]), dtype=np.uint32, count=j - i))
+            i = j
+        return len(pairs)
+
+    def search_distinct(self, query_vector: np.ndarray, limit: int = 10, mask=None) -> List[Tuple[str, float, int]]:
+        """Exact top-``limit`` of this shard with at most one vector per label, best first: ``[(id, score, label)]``, scores
+        as ``search`` returns them.  ``mask`` as ``search``'s ``row_mask`` (bool per row or uint32 words).  Errors are
+        swallowed or raised as in ``search``."""
+        try:
+            actual_limit = min(int(limit), _native.MAX_K)
+            if self.next_index == 0 or actual_limit <= 0:
+                return []
+            q = self._prepare(query_vector)
+            words = None
+            if mask is not None:
+                words = mask if mask.dtype == np.uint32 else _native.pack_row_mask(mask)
+            idx, score, label = self._native.search_distinct(q, actual_limit, mask_words=words)
+            keep = idx[0] != -1
+            return [(vid, s, int(lab)) for (vid, s), lab in zip(self._map(idx[0], score[0]), label[0][keep])]
+        except Exception as e:
+            logger.error("Error in HIP distinct search: %s", e)
+            if self.swallow_errors:
+                return []
+            raise
+
     async def search_async(self, query_vector: np.ndarray, limit: int = 10) -> List[Tuple[str, float]]:
         loop = asyncio.get_event_loop()
         return await loop.run_in_executor(self.thread_pool, self.search, query_vector, limit)

@@ -163,6 +163,9 @@ class VectorStore:
         # shard of explicitly named bulk rows (placed by row range, not by hash)
         self._bulk_ranges: List[Tuple[str, int, int, int]] = []
         self._bulk_id_shard: Dict[str, int] = {}
+        # distinct search (config DISTINCT_KEY): the values of that metadata field interned into 32-bit labels, ONE table for the
+        # whole store so that the shards agree on a value's label
+        self._label_ids: Dict[Any, int] = {}
         self._bulk_rows = 0        # labels handed out to implicit-id bulk rows so far (the next label)
         # shard group (one library call per search, RCCL merge): created lazily, None = not tried, False = unavailable
         self._group: Any = None
@@ -236,6 +239,7 @@ class VectorStore:
             except Exception as e:
                 logger.error("Error loading vectors: %s", e)
         self._reconcile()
+        self._push_labels(self.metadata)
 
     def _reconcile(self) -> None:
         """Make the tables loaded above agree with what the shards' own files brought back into HBM (they are saved
@@ -264,6 +268,38 @@ class VectorStore:
             del self._bulk_id_shard[vid]
         if gone:
             logger.warning("dropping %d bulk ids that no shard holds any more", len(gone))
+
+    # ---- labels of the distinct search ----
+    def _label_of(self, metadata: Optional[Dict[str, Any]]) -> int:
+        """The 32-bit label of a vector with this metadata: its DISTINCT_KEY value interned store-wide (an unhashable value
+        by its JSON text); LABEL_NONE when the key is missing."""
+        key = self.config.get("DISTINCT_KEY")
+        if key is None or not isinstance(metadata, dict) or key not in metadata:
+            return _native.LABEL_NONE
+        value = metadata[key]
+        try:
+            hash(value)
+        except TypeError:
+            value = ("json", json.dumps(value, sort_keys=True, default=str))
+        label = self._label_ids.get(value)
+        if label is None:
+            label = len(self._label_ids)
+            if label >= _native.LABEL_NONE:
+                raise OverflowError("more distinct values than 32-bit labels")
+            self._label_ids[value] = label
+        return label
+
+    def _push_labels(self, vector_ids) -> None:
+        """Label the named vectors in their shards from their current metadata (nothing without DISTINCT_KEY)."""
+        if self.config.get("DISTINCT_KEY") is None:
+            return
+        per_shard: Dict[int, Tuple[List[str], List[int]]] = {}
+        for vid in vector_ids:
+            ids, labels = per_shard.setdefault(self._get_shard_for_id(vid), ([], []))
+            ids.append(vid)
+            labels.append(self._label_of(self.metadata.get(vid)))
+        for shard, (ids, labels) in per_shard.items():
+            self.indices[shard].set_labels(ids, labels)
 
     def _save_metadata(self) -> None:
         try:
@@ -343,6 +379,7 @@ class VectorStore:
         self._bulk_rows += n
         for vid, meta in (metadata or {}).items():
             self.metadata[vid] = meta
+        self._push_labels(metadata or {})
         self._meta_version += 1
         if persist or (persist is None and self.config.get("VECTOR_STORE_SAVE_IMMEDIATELY", False)):
             self._save_now()
@@ -400,6 +437,7 @@ class VectorStore:
         try:
             vec = self._remember(vector_id, vector, metadata)
             self.indices[self._get_shard_for_id(vector_id)].add(vector_id, vec)
+            self._push_labels([vector_id])
             if self.config.get("VECTOR_STORE_SAVE_IMMEDIATELY", False):
                 self._save_now()
             return True
@@ -412,6 +450,7 @@ class VectorStore:
         try:
             vec = self._remember(vector_id, vector, metadata)
             await self.indices[self._get_shard_for_id(vector_id)].add_async(vector_id, vec)
+            self._push_labels([vector_id])
             if self.config.get("VECTOR_STORE_SAVE_IMMEDIATELY", False):
                 await asyncio.get_event_loop().run_in_executor(self.thread_pool, self._save_now)
             return True
@@ -431,6 +470,7 @@ class VectorStore:
                     metadata: Optional[Dict[str, Dict[str, Any]]] = None) -> int:
         for shard, vecs in self._group_by_shard(vectors, metadata).items():
             self.indices[shard].batch_add(vecs)
+        self._push_labels(vectors)
         if self.config.get("VECTOR_STORE_SAVE_IMMEDIATELY", False):
             self._save_now()
         return len(vectors)
@@ -440,6 +480,7 @@ class VectorStore:
         groups = self._group_by_shard(vectors, metadata)
         if groups:
             await asyncio.gather(*[self.indices[s].batch_add_async(v) for s, v in groups.items()])
+        self._push_labels(vectors)
         if self.config.get("VECTOR_STORE_SAVE_IMMEDIATELY", False):
             await asyncio.get_event_loop().run_in_executor(self.thread_pool, self._save_now)
         return len(vectors)
@@ -1053,6 +1094,47 @@ class VectorStore:
         return await loop.run_in_executor(self.thread_pool, lambda: self.search_among(
             query_vector, vector_ids, limit=limit, threshold=threshold))
 
+    # ---- distinct search (extension: at most one result per value of the metadata field DISTINCT_KEY) ----
+    def search_distinct(self, query_vector: List[float], limit: int = 10, threshold: float = 0.0,
+                        filter_metadata: Optional[Dict[str, Any]] = None) -> List[Result]:
+        """The best ``limit`` vectors with at most ONE per value of the metadata field named by config ``DISTINCT_KEY`` (ten
+        documents, each by its best chunk, instead of the ten best chunks); a vector without the field stands for itself.
+        Exact: every shard answers its own top-``limit`` labels (``wdbx_index_search_distinct``) -- a label in the global
+        top-``limit`` is in the top-``limit`` of the shard that holds its best row --, the union keeps the best row of each
+        label, ordered by (score descending, shard, row) and cut at ``limit``.  ``filter_metadata`` always travels as the
+        shards' row masks (a post-filter could drop a label whose best row does not match); ``threshold`` as in
+        ``search``."""
+        if self.config.get("DISTINCT_KEY") is None:
+            raise ValueError("search_distinct needs config DISTINCT_KEY: the metadata field whose values label the vectors")
+        query = _as_query(query_vector)
+        if query.shape != (self.vector_dim,):
+            raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {query.shape}")
+        masks = self._row_masks(filter_metadata) if filter_metadata else [None] * len(self.indices)
+        work = list(zip(self.indices, masks))
+        one = lambda a: a[0].search_distinct(query, limit, mask=a[1])  # noqa: E731
+        per_shard = list(self._shard_pool.map(one, work)) if len(work) > 1 else [one(work[0])]
+        # (a shard's list is ordered by (score descending, row ascending): the position stands for the row among equal scores)
+        ranked = sorted(((-score, shard, pos, vid, label) for shard, res in enumerate(per_shard)
+                         for pos, (vid, score, label) in enumerate(res)), key=lambda t: t[:3])
+        seen, out = set(), []
+        for neg, _, _, vid, label in ranked:
+            if threshold > 0 and -neg < threshold:
+                break
+            if label != _native.LABEL_NONE:
+                if label in seen:
+                    continue
+                seen.add(label)
+            out.append((vid, -neg, self.metadata.get(vid, {})))
+            if len(out) >= limit:
+                break
+        return out
+
+    async def search_distinct_async(self, query_vector: List[float], limit: int = 10, threshold: float = 0.0,
+                                    filter_metadata: Optional[Dict[str, Any]] = None) -> List[Result]:
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(self.thread_pool, lambda: self.search_distinct(
+            query_vector, limit=limit, threshold=threshold, filter_metadata=filter_metadata))
+
     # ---- range search (extension: every vector within a similarity, no limit) ----
     def search_range(self, query_vector: List[float], threshold: float,
                      filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,
@@ -1114,6 +1196,7 @@ class VectorStore:
             return False
         self.metadata[vector_id] = metadata
         self._meta_version += 1
+        self._push_labels([vector_id])
         return True
 
     def update_metadata(self, vector_id: str, metadata: Dict[str, Any]) -> bool:

@@ -150,6 +150,20 @@ class WDBX:
         self._check_dim(query_vector)
         return await self.vector_store.search_among_async(query_vector, vector_ids, limit=limit, threshold=threshold)
 
+    def vector_search_distinct(self, query_vector: List[float], limit: int = 10, threshold: float = 0.0,
+                               filter_metadata: Optional[Dict[str, Any]] = None) -> List[Result]:
+        """Extension: the best ``limit`` vectors with at most one per value of the metadata field named by config
+        ``DISTINCT_KEY`` (search groups / collapse: ten documents, each by its best chunk).  Exact; a filter is pushed down."""
+        self._check_dim(query_vector)
+        return self.vector_store.search_distinct(query_vector, limit=limit, threshold=threshold,
+                                                 filter_metadata=filter_metadata)
+
+    async def vector_search_distinct_async(self, query_vector: List[float], limit: int = 10, threshold: float = 0.0,
+                                           filter_metadata: Optional[Dict[str, Any]] = None) -> List[Result]:
+        self._check_dim(query_vector)
+        return await self.vector_store.search_distinct_async(query_vector, limit=limit, threshold=threshold,
+                                                             filter_metadata=filter_metadata)
+
     def vector_search_range(self, query_vector: List[float], threshold: float,
                             filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,
                             max_results: Optional[int] = None) -> List[Result]:
