@@ -112,6 +112,16 @@ struct wdbx_index {
   uint32_t* d_count6 = nullptr;  // its candidate counters (d_count holds the cut's: what the repair launches look at)
   size_t count6_bytes = 0;
   int last_single_u6 = 0;      // 1: the last single-query search selected on the u6 shadow (last_single_path stays 2)
+  // the u6 codes once more in two planes (kernels_scan42.h): ONE allocation, the h plane in 64-row tiles of units42 units,
+  // the per-row {s, a4} pairs, the l records of lpitch42 dwords per row
+  uint32_t* d_rows42 = nullptr;
+  size_t rows42_bytes = 0;
+  uint64_t shadow42_rows = 0, rows42_tiles = 0;
+  uint32_t units42 = 0;
+  uint64_t u42_no_room_cap = ~0ull;
+  uint32_t* d_count42 = nullptr;  // rows that passed the four-bit bound, per query of the last round
+  size_t count42_bytes = 0;
+  int last_single_u42 = 0;     // 1: the last u6 round's full passes ran over the split planes
   uint32_t* defer_flag_dev = nullptr;  // non-null during a blocking call that repairs overflow itself (mapped host word)
   // a lone blocking call through a staging slot: the LAST kernel of its chain writes done_seq into done_flag_dev (a mapped
   // host word of the slot) and the caller polls that word instead of waiting on the runtime; done_signals counts the launches
@@ -193,7 +203,7 @@ struct wdbx_index {
           opt_gemm8_refine = 1, opt_scan8_sample4 = 1, opt_gemm_l2 = 1, opt_gemm_l2_i8 = 1, opt_force_ragged = 0,
           opt_gemm_ct = 0, opt_wg_merge = 1, opt_zero_copy = 1, opt_lone_host_select = 1, opt_lds_lists = 0,
           opt_merge_fast = 1, opt_poll_done = 1, opt_scan_one_grid = 1, opt_select_min_k = 200, opt_gemm_min_nq = 4, opt_gemm_min_rows = 65536, opt_gemm_min_work = 800000,
-          opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0, opt_gemm_masked = 1, opt_rows_keys_max = 8192, opt_distinct_overfetch = 4;
+          opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0, opt_scan_u42 = -1, opt_gemm_masked = 1, opt_rows_keys_max = 8192, opt_distinct_overfetch = 4;
 };
 
 struct DeviceGuard {
@@ -608,7 +618,9 @@ static bool prepare_u8_shadow(wdbx_index* ix);
 static bool u6_single_eligible(const wdbx_index* ix, int k, int nq_call);
 static bool prepare_u6_shadow(wdbx_index* ix);
 static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, int k, int64_t* d_out_idx, float* d_out_score,
-                              u64* keys_out);
+                              u64* keys_out, bool u42);
+static bool u42_single_eligible(const wdbx_index* ix);
+static bool prepare_u42_shadow(wdbx_index* ix);
 
 static int enqueue_search(wdbx_index* ix, const float* d_queries, int nq, int k, int64_t* d_out_idx,
                           float* d_out_score, int mode, u64* keys_dst = nullptr) {
@@ -669,6 +681,7 @@ static int enqueue_search(wdbx_index* ix, const float* d_queries, int nq, int k,
       const bool u8 = u8_single_eligible(ix, k, nq) && prepare_u8_shadow(ix);  // (also for the in-process group's local stage)
       ix->last_single_path = u8 ? 2 : 0;
       ix->last_single_u6 = 0;
+      ix->last_single_u42 = 0;
       SelectSrc* src = nullptr;
       if (u8) {
         if ((rc = grow((void**)&ix->d_count, &ix->count_bytes, ((size_t)batch + 2 * GB_N) * sizeof(uint32_t)))) return rc;
@@ -730,11 +743,14 @@ static int enqueue_search(wdbx_index* ix, const float* d_queries, int nq, int k,
       // rounds on a large shard select on the six-bit shadow instead (0.76 of the u8 bytes per pass; kernels_scan6.h)
       const bool u6 = u8 && u6_single_eligible(ix, k, nq) && prepare_u6_shadow(ix);
       ix->last_single_u6 = u6 ? 1 : 0;
+      // ... and make the full passes over the split planes where those serve the shape (0.68 of the u6 bytes; kernels_scan42.h)
+      const bool u42 = u6 && u42_single_eligible(ix) && prepare_u42_shadow(ix);
+      ix->last_single_u42 = u42 ? 1 : 0;
       if (shadow) {
         if ((rc = grow((void**)&ix->d_count, &ix->count_bytes, ((size_t)batch + 2 * GB_N) * sizeof(uint32_t)))) return rc;
         if (u6)
           rc = enqueue_singles_u6(ix, d_queries + (size_t)q0 * ix->pitch, b, k, d_out_idx ? d_out_idx + (size_t)q0 * k : nullptr,
-                                  d_out_score ? d_out_score + (size_t)q0 * k : nullptr, sharded ? lkeys : nullptr);
+                                  d_out_score ? d_out_score + (size_t)q0 * k : nullptr, sharded ? lkeys : nullptr, u42);
         else if (u8)  // the u8 selection scan: a quarter of the fp32 bytes per query
           rc = enqueue_singles_u8(ix, d_queries + (size_t)q0 * ix->pitch, b, k, d_out_idx ? d_out_idx + (size_t)q0 * k : nullptr,
                                   d_out_score ? d_out_score + (size_t)q0 * k : nullptr, sharded ? lkeys : nullptr);
@@ -1204,6 +1220,16 @@ static bool u6_single_eligible(const wdbx_index* ix, int k, int nq_call) {
   return true;
 }
 
+// the three parts of the split planes' allocation, and their quantiser over rows [first, end)
+static inline f2v* u42_sa4(const wdbx_index* ix) { return (f2v*)(ix->d_rows42 + (size_t)ix->rows42_tiles * ix->units42 * 256); }
+static inline uint32_t* u42_lrec(const wdbx_index* ix) { return (uint32_t*)(u42_sa4(ix) + (size_t)ix->rows42_tiles * 64); }
+static hipError_t launch_rows_to_u42(wdbx_index* ix, uint64_t first, uint64_t end) {
+  hipLaunchKernelGGL(rows_to_u42_kernel, dim3(rows_to_u42_grid(end - first)), dim3(256), 0, ix->stream, (const float*)ix->d_rows, (u64)first,
+                     (u64)end, (uint32_t)ix->dim, (uint32_t)ix->pitch, ix->units42, ix->d_rows42, u42_sa4(ix), u42_lrec(ix),
+                     u42_lpitch(ix->units42));
+  return hipGetLastError();
+}
+
 // Allocates / refreshes the u6 shadow for the rows added since the last search that took this path (the life cycle of
 // prepare_u8_shadow).  false = no room on the device (remembered per capacity): the caller stays on the u8 scan.
 static bool prepare_u6_shadow(wdbx_index* ix) {
@@ -1237,17 +1263,59 @@ static bool prepare_u6_shadow(wdbx_index* ix) {
   return true;
 }
 
+// The split planes behind a u6 round (kernels_scan42.h): rows of whole 32-element units.  Option scan_u42: -1 = where the u6
+// scan is taken by its size rule (the u8 shadow exceeds 1 GiB), 0 = never, 1 = wherever the u6 scan is taken.
+static bool u42_single_eligible(const wdbx_index* ix) {
+  if (ix->opt_scan_u42 == 0 || ix->pitch % 32 != 0 || !u42_unit_chunk((uint32_t)ix->pitch / 32)) return false;
+  const Scan8Shape* sh = scan8_shape((uint32_t)ix->dim);
+  if (ix->opt_scan_u42 < 0 && (!sh || (uint64_t)ix->n * sh->pieces * 16 <= (1ull << 30))) return false;
+  return true;
+}
+
+// Allocates / refreshes the planes for the rows added since the last round that read them (the life cycle of
+// prepare_u6_shadow).  false = no room on the device (remembered per capacity): the round stays on the u6 full pass.
+static bool prepare_u42_shadow(wdbx_index* ix) {
+  const uint32_t units = (uint32_t)ix->pitch / 32, lpitch = u42_lpitch(units);
+  const uint64_t tiles = ((uint64_t)ix->cap + 63) / 64;
+  const size_t need = (size_t)tiles * units * 1024 + (size_t)tiles * 64 * sizeof(f2v) + (size_t)tiles * 64 * lpitch * sizeof(uint32_t);
+  if (ix->rows42_bytes < need || ix->units42 != units || ix->rows42_tiles != tiles) {
+    if (ix->u42_no_room_cap == ix->cap) return false;
+    if (ix->d_rows42) (void)hipFree(ix->d_rows42);
+    ix->d_rows42 = nullptr;
+    ix->rows42_bytes = 0;
+    ix->shadow42_rows = 0;
+    if (hipMalloc((void**)&ix->d_rows42, need) != hipSuccess) {
+      (void)hipGetLastError();
+      ix->d_rows42 = nullptr;
+      ix->u42_no_room_cap = ix->cap;
+      return false;
+    }
+    ix->rows42_bytes = need;
+    ix->units42 = units;
+    ix->rows42_tiles = tiles;
+  }
+  if (ix->shadow42_rows < ix->n) {
+    if (launch_rows_to_u42(ix, ix->shadow42_rows, ix->n) != hipSuccess) return false;
+    ix->shadow42_rows = ix->n;
+  }
+  return true;
+}
+
 // nq single queries of a round, each with its own full pass over the u6 shadow: sample (4 queries per workgroup) ->
 // thresholds -> a pass per query -> exact re-scoring (rescore_kernel, as behind the u8 scan) -> cut -> final top-k.
 // The candidate counters live in d_count6; d_count[0 .. nq) are the CUT's counters against last_batch_cap = its capacity, and
 // end above it for a query whose candidate buffer or short list overflowed: what the callers' repair launches test.
+// u42: the full passes run over the split planes instead (scan_u42_kernel); everything in front of and behind them is the same.
 static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, int k, int64_t* d_out_idx, float* d_out_score,
-                              u64* keys_out) {
+                              u64* keys_out, bool u42) {
   const uint32_t units = (uint32_t)ix->pitch / 16;
   const int uc = u6_unit_chunk(units);
   scan6_fn f0 = pick_scan6(uc, true), f1 = pick_scan6(uc, false);
   if (!f0 || !f1) return fail(WDBX_E_STATE, "no u6 scan instance for %u units", units);
   if (!ix->d_rows6 || ix->units6 != units || ix->shadow6_rows < ix->n) return fail(WDBX_E_STATE, "u6 shadow not prepared");
+  const scan42_fn f42 = u42 ? pick_scan42(u42_unit_chunk(units / 2)) : nullptr;
+  if (u42 && (!f42 || !ix->d_rows42 || ix->units42 != units / 2 || ix->shadow42_rows < ix->n))
+    return fail(WDBX_E_STATE, "split planes not prepared");
   int rc;
   // sampled 256-row tiles (4 groups of 64 rows each), as on the u8 scan
   const uint32_t tiles = (uint32_t)((ix->n + 255) / 256);
@@ -1267,6 +1335,7 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
   if ((rc = grow((void**)&ix->d_tau, &ix->tau_bytes, (size_t)GB_N * sizeof(float)))) return rc;
   if ((rc = grow((void**)&ix->d_cand, &ix->cand_bytes, (size_t)ROUND * ((size_t)cap + cap2) * sizeof(u64)))) return rc;
   if ((rc = grow((void**)&ix->d_count6, &ix->count6_bytes, (size_t)ROUND * sizeof(uint32_t)))) return rc;
+  if (u42 && (rc = grow((void**)&ix->d_count42, &ix->count42_bytes, (size_t)ROUND * sizeof(uint32_t)))) return rc;
   if (ix->count_bytes < ((size_t)nq + GB_N) * sizeof(uint32_t)) return fail(WDBX_E_STATE, "candidate counters not sized by the caller");
   ix->last_batch_nq = (uint32_t)nq;
   ix->last_batch_cap = cap2;
@@ -1275,7 +1344,9 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
   // workgroups per CU of the full pass (option scan8_wgs).  Measured at 10 M x 384, whole steps: 2 -> 2222 q/s, 4 -> 2125,
   // 6 -> 2008, 8 -> 1990 (profiles/u6/README.md): eight waves per CU with 6 KiB in flight each keep HBM busy, more of them
   // only spread the stream over more pages at once
-  const uint32_t wgs = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(ix->opt_scan8_wgs > 0 ? ix->opt_scan8_wgs : 2, 8));
+  // The split planes' pass, same corpus: 1 -> 1879, 2 -> 2885, 3 -> 3028, 4 -> 2959, 6 -> 2885 (profiles/u42/README.md): a wave
+  // holds 6 KiB in flight as before but computes longer per byte, so a third workgroup still fills gaps
+  const uint32_t wgs = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(ix->opt_scan8_wgs > 0 ? ix->opt_scan8_wgs : u42 ? 3 : 2, 8));
   const uint32_t grid1 = scan_full_grid(tiles64, (uint32_t)ix->cu_count, wgs);
   const uint32_t grid0 = scan_sample_grid(ngroups, (uint32_t)ix->cu_count);
   const size_t pitch4 = ix->pitch / 4;
@@ -1330,7 +1401,29 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
     // the full passes: every query makes its own pass over all rows (one grid on small shards, as the u8 scan); one event
     // pair around them, the profile reports elapsed / passes
     if ((rc = record(ix->gemm_ev, ix->profile, ix->stream, true))) return rc;
-    if (one_grid && nv > 1) {
+    if (u42) {
+      Scan42Args b = {};
+      b.hcodes = ix->d_rows42;
+      b.sa4 = u42_sa4(ix);
+      b.lrec = u42_lrec(ix);
+      b.n_rows = a.n_rows;
+      b.units = ix->units42;
+      b.qpitch = a.qpitch;
+      b.lpitch = u42_lpitch(ix->units42);
+      b.cap = cap;
+      // (the survivors are counted for the probes only: an atomic per 64 of them)
+      HIP_TRY(hipMemsetAsync(ix->d_count42, 0, (size_t)nv * sizeof(uint32_t), ix->stream));
+      const bool grid_y = one_grid && nv > 1;
+      for (int i = 0; i < (grid_y ? 1 : nv); ++i) {
+        b.query = qsrc + (size_t)i * ix->pitch;
+        b.tau = ix->d_tau + i;
+        b.cand = ix->d_cand + (size_t)i * cap;
+        b.count = ix->d_count6 + i;
+        b.survivors = ix->d_count42 + i;
+        hipLaunchKernelGGL(f42, dim3(grid1, grid_y ? nv : 1), dim3(256), 0, ix->stream, b);
+        HIP_TRY(hipGetLastError());
+      }
+    } else if (one_grid && nv > 1) {
       hipLaunchKernelGGL(f1, dim3(grid1, nv), dim3(256), 0, ix->stream, a);
       HIP_TRY(hipGetLastError());
     } else {
@@ -2230,6 +2323,7 @@ static int upload_rows(wdbx_index* ix, uint64_t first, const float* rows, uint64
                        (f2v*)(ix->d_rows6 + (size_t)ix->rows6_tiles * ix->units6 * 192));
     HIP_TRY(hipGetLastError());
   }
+  if (first < ix->shadow42_rows && ix->d_rows42) HIP_TRY(launch_rows_to_u42(ix, first, std::min(end, ix->shadow42_rows)));
   HIP_TRY(hipStreamSynchronize(ix->stream));
   return WDBX_OK;
 }

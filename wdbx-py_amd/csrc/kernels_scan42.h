@@ -1,0 +1,257 @@
+// kernels_scan42.h -- the six-bit selection scan split in two planes: every query streams the codes' top four bits, the low
+// two bits are read only for the rows the four-bit bound cannot rule out ("u42").
+// Part of the single translation unit wdbx_hip.hip (included there, after kernels_scan6.h); not a standalone header.
+
+// ------------------------------------------------------------------------------------------------
+// The u6 full pass is the bytes it reads (288 B of codes + 8 B per row at d = 384).  The SAME six-bit code u = rint(c / s) + 32
+// (rows_to_u6_kernel's quantiser: u6_row_scale / u6_unit_codes) is stored as u = 4 h + l, h in 0 .. 15, l in 0 .. 3:
+//   h plane   tiles of 64 rows, unit-major, a unit = 32 codes = 16 bytes:  [tile][unit][row 0..63][4 dwords].  Lane = row; one
+//             16-byte load per lane and unit is 1 KiB contiguous per wave.  Dword t byte b holds h of element 8 t + b in its
+//             low nibble and of element 8 t + 4 + b in its high nibble: (d & 0x0F0F0F0F) and (d >> 4 & 0x0F0F0F0F) feed four
+//             byte converts each -- 3 logic ops + 8 converts + 4 v_pk_fma_f32 per dword of eight elements.
+//   {s, a4}   per row: the u6 scale and  a4 >= |c - s (4 h + 1.5 - 32)|_2,  the residual of the row against the MIDPOINT of
+//             what the low bits can add, rounded up with the allowances rows_to_u6_kernel derives for a (same arithmetic:
+//             rho4 = fmaf(-s, 4 h - 30.5, x) * inv -- 4 h - 30.5 is exact in fp32 --, a sum of at most dimp squares, one root).
+//             Padding elements (query 0 there) are left out of a4.
+//   l plane   row-major, one 128-byte-aligned record per row: dimp / 4 bytes of two-bit remainders (dword g of a unit holds
+//             elements 16 g .. 16 g + 15, element 4 j + b in bits [8 b + 2 j, 8 b + 2 j + 1]: (w >> 2 j) & 0x03030303 is four of
+//             them as bytes), then a6 = the u6 shadow's a, bit for bit (the same sum in the same order).
+// scan_u42_kernel, lane = row, forms P = sum h_i q_i (query through scalar loads, v_pk_fma_f32 as scan8_u6_kernel) and
+//   w4 = s (4 P - 30.5 sum q),   |w4 - c.q| <= m4 = a4 |q|_2 (1 + 1e-5) + 6e-6 (dimp + 8) s |q|_1 (1 + 1e-5).
+// First term: Cauchy-Schwarz on the stored residual, as in kernels_scan6.h.  Second term, the fp32 roundings of the kernel's
+// own arithmetic: the sum of dimp products |h_i q_i| <= 15 |q_i| in any order, times 4 exactly (gamma_dimp * 60 |q|_1), the sum
+// behind 30.5 sum q and that product (gamma_(dimp + 1) * 30.5 |q|_1), their difference (a fused multiply-add or two roundings)
+// and the product with s, of a value of at most 90.5 |q|_1: (dimp + 8) * 2^-24 * 90.5 < 5.4e-6 (dimp + 8), taken as 6e-6.
+// A row with !(w4 + m4 < tau) is a SURVIVOR: {row, P, s} go to a list of the wave in LDS.  When the list holds 64 (and once
+// more, masked, behind the wave's last tile) the wave refines densely, lane = survivor: the lane walks its own l record with
+// the same scalar query, Q = sum l_i q_i, and
+//   w6 = s ((4 P + Q) - 32 sum q),   |w6 - c.q| <= m6 = a6 |q|_2 (1 + 1e-5) + 6e-6 (dimp + 8) s |q|_1 (1 + 1e-5):
+// 4 P as above (gamma_dimp * 60 |q|_1), the sum of dimp products |l_i q_i| <= 3 |q_i| (gamma_dimp * 3 |q|_1), their sum (one
+// rounding of at most 63 |q|_1), 32 sum q (gamma_dimp * 32 |q|_1), the difference and the product with s (of at most 95 |q|_1):
+// (dimp + 8) * 2^-24 * 95 < 5.7e-6 (dimp + 8), the u6 scan's own term.  w6 estimates the u6 scan's w (the same codes) and m6
+// is its m; rows with !(w6 + m6 < tau) go to the candidate buffer through the WaveStage exactly as there.  Both bounds are
+// rigorous, so no row whose score reaches tau is lost; the re-scoring, the cut and the merge behind the pass are the u6
+// scan's, the threshold in front of it is too.  NaN / inf rows: a negative scale skips the row, a NaN scale makes w4 and w6
+// NaN, so the row survives both comparisons and is appended with +inf.
+// ------------------------------------------------------------------------------------------------
+typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+
+struct Scan42Args {
+  const uint32_t* hcodes;  // [tiles][units][64][4]
+  const f2v* sa4;          // [rows] {s, a4}
+  const uint32_t* lrec;    // [rows][lpitch]: units * 2 dwords of remainders, then a6
+  const float* query;      // fp32 [units * 32] per query, pitch qpitch floats (zero padded)
+  uint32_t n_rows, units, qpitch, lpitch;
+  const float* tau;
+  u64* cand;
+  uint32_t* count;
+  uint32_t* survivors;     // optional: rows that passed the four-bit bound, per query (probes and tests)
+  uint32_t cap;
+};
+
+// dwords of one l record: the remainders and a6, rounded up to whole 128-byte lines
+static inline uint32_t u42_lpitch(uint32_t units) { return (units * 2 + 1 + 31) / 32 * 32; }
+
+template <bool NT>
+__device__ __forceinline__ u4v u42_load(const uint32_t* p) {
+  const u4v* q = (const u4v*)p;
+  if constexpr (NT) return __builtin_nontemporal_load(q);
+  return *q;
+}
+
+// the eight nibbles of one dword as floats: elements 0 .. 3 from the low nibbles, 4 .. 7 from the high ones
+__device__ __forceinline__ void u42_unpack8(uint32_t d, float (&f)[8]) {
+  float t[4];
+  u6_cvt4(d & 0x0F0F0F0Fu, t);
+  f[0] = t[0], f[1] = t[1], f[2] = t[2], f[3] = t[3];
+  u6_cvt4((d >> 4) & 0x0F0F0F0Fu, t);
+  f[4] = t[0], f[5] = t[1], f[6] = t[2], f[7] = t[3];
+}
+
+// the wave's survivor list: 128 entries, < 64 held between tiles
+struct U42List {
+  uint32_t row[128];
+  float p[128];
+  float s[128];
+};
+
+__device__ __forceinline__ void u42_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// dense refine of the first n (<= 64) entries of the wave's list, lane = survivor; the rest moves to the front
+__device__ __forceinline__ void u42_refine(const Scan42Args& a, cfloat* q, U42List& ls, uint32_t& fill, uint32_t n, float qsum32,
+                                           float q2, float round1, float thr, WaveStage& st, int lane) {
+  u42_wave_sync();
+  const uint32_t l = (uint32_t)lane;
+  const bool active = l < n;
+  const uint32_t row = active ? ls.row[l] : 0u;  // (idle lanes walk record 0: always there)
+  const float p4 = active ? ls.p[l] : 0.f;
+  const float s = active ? ls.s[l] : 0.f;
+  const uint32_t rest = fill - n;  // (< 64)
+  const uint32_t m_row = l < rest ? ls.row[n + l] : 0u;
+  const float m_p = l < rest ? ls.p[n + l] : 0.f, m_s = l < rest ? ls.s[n + l] : 0.f;
+  u42_wave_sync();
+  if (l < rest) ls.row[l] = m_row, ls.p[l] = m_p, ls.s[l] = m_s;
+  fill = rest;
+  u42_wave_sync();
+  if (a.survivors && lane == 0) atomicAdd(a.survivors, n);
+  const uint32_t* rec = a.lrec + (size_t)row * a.lpitch;
+  f2v a0 = {0.f, 0.f}, a1 = {0.f, 0.f};
+  for (uint32_t u = 0; u < a.units; ++u) {
+    const uint32_t w0 = rec[2 * u], w1 = rec[2 * u + 1];
+    cfloat* qu = q + u * 32;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      const uint32_t w = g ? w1 : w0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float f[4];
+        u6_cvt4((w >> (2 * j)) & 0x03030303u, f);
+        const int i = 16 * g + 4 * j;
+        a0 = __builtin_elementwise_fma(f2v{f[0], f[1]}, f2v{qu[i], qu[i + 1]}, a0);
+        a1 = __builtin_elementwise_fma(f2v{f[2], f[3]}, f2v{qu[i + 2], qu[i + 3]}, a1);
+      }
+    }
+  }
+  const float a6 = __uint_as_float(rec[2 * a.units]);
+  const float qq = (a0.x + a0.y) + (a1.x + a1.y);
+  const float w = s * ((4.0f * p4 + qq) - qsum32);
+  const float m = fmaf(a6, q2, s * round1);
+  const bool keep = active && !(w + m < thr);
+  st.push(keep, make_key((w == w) ? w + 0.0f : INFINITY, row), a.cand, a.count, a.cap, lane);
+}
+
+// full pass: UC units in flight per wave (a last, shorter chunk when UC does not divide the row's units), one 64-row tile per
+// wave at a time
+template <int UC>
+__global__ __launch_bounds__(256) void scan_u42_kernel(Scan42Args a) {
+  __shared__ u64 stage42[4][128];
+  __shared__ U42List list42[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float* qg = a.query + (size_t)blockIdx.y * a.qpitch;
+  cfloat* q = (cfloat*)qg;
+  a.tau += blockIdx.y;
+  a.cand += (size_t)blockIdx.y * a.cap;
+  a.count += blockIdx.y;
+  if (a.survivors) a.survivors += blockIdx.y;
+  float qsum32, q1, q2;
+  u6_query_sums(qg, a.units * 32, lane, qsum32, q1, q2);
+  const float qsum305 = 30.5f * (qsum32 * 0.03125f);
+  const float thr = a.tau[0];
+  const float round1 = 6e-6f * (float)(a.units * 32 + 8) * q1;
+  WaveStage st = {stage42[wave], 0u};
+  U42List& ls = list42[wave];
+  uint32_t fill = 0;
+  const uint32_t tiles = (a.n_rows + 63) / 64;
+  const size_t tile_dw = (size_t)a.units * 256;
+  for (uint32_t tile = blockIdx.x * 4 + wave; tile < tiles; tile += gridDim.x * 4) {
+    const uint32_t row = tile * 64 + (uint32_t)lane;
+    const uint32_t* p = a.hcodes + tile * tile_dw + lane * 4;
+    const f2v sa = __builtin_nontemporal_load(a.sa4 + min(row, a.n_rows - 1));
+    f2v a0 = {0.f, 0.f}, a1 = {0.f, 0.f};
+    for (uint32_t u0 = 0; u0 < a.units; u0 += UC) {
+      u4v v[UC];
+#pragma unroll
+      for (int u = 0; u < UC; ++u) v[u] = u42_load<true>(p + (size_t)min(u0 + u, a.units - 1) * 256);  // (the last chunk may be short)
+#pragma unroll
+      for (int u = 0; u < UC; ++u) {
+        if (u0 + u < a.units) {  // (wave-uniform)
+          cfloat* qu = q + (u0 + u) * 32;
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            float f[8];
+            u42_unpack8(v[u][t], f);
+            a0 = __builtin_elementwise_fma(f2v{f[0], f[1]}, f2v{qu[8 * t], qu[8 * t + 1]}, a0);
+            a1 = __builtin_elementwise_fma(f2v{f[2], f[3]}, f2v{qu[8 * t + 2], qu[8 * t + 3]}, a1);
+            a0 = __builtin_elementwise_fma(f2v{f[4], f[5]}, f2v{qu[8 * t + 4], qu[8 * t + 5]}, a0);
+            a1 = __builtin_elementwise_fma(f2v{f[6], f[7]}, f2v{qu[8 * t + 6], qu[8 * t + 7]}, a1);
+          }
+        }
+      }
+    }
+    const float p4 = (a0.x + a0.y) + (a1.x + a1.y);
+    const float w = sa.x * (4.0f * p4 - qsum305);
+    const float m = fmaf(sa.y, q2, sa.x * round1);
+    // (as the u6 pass: a NaN bound keeps the row, a negative scale marks a row with a NaN element)
+    const bool surv = row < a.n_rows && !(sa.x < 0.f) && !(w + m < thr);
+    const u64 bal = __ballot(surv);
+    if (bal) {
+      const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+      if (surv) ls.row[fill + rank] = row, ls.p[fill + rank] = p4, ls.s[fill + rank] = sa.x;
+      fill += (uint32_t)__popcll(bal);
+      if (fill >= 64) u42_refine(a, q, ls, fill, 64u, qsum32, q2, round1, thr, st, lane);
+    }
+  }
+  if (fill) u42_refine(a, q, ls, fill, fill, qsum32, q2, round1, thr, st, lane);
+  st.finish(a.cand, a.count, a.cap, lane);
+}
+
+// rows [r0, n) fp32 -> h plane, {s, a4} and l records, one wave per row, one lane per 16 elements (half a unit): the walk of
+// rows_to_u6_kernel, so that a6 is its a bit for bit.  units = 32-element units (the pitch is a multiple of 32).
+__global__ __launch_bounds__(256) void rows_to_u42_kernel(const float* rows, u64 r0, u64 n, uint32_t dim, uint32_t pitch,
+                                                          uint32_t units, uint32_t* hcodes, f2v* sa4, uint32_t* lrec,
+                                                          uint32_t lpitch) {
+  const int lane = threadIdx.x & 63;
+  const u64 wave = (u64)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (u64)gridDim.x * 4;
+  for (u64 r = r0 + wave; r < n; r += nw) {
+    const float* p = rows + r * pitch;
+    const U6RowScale rs = u6_row_scale(p, dim, lane);
+    float rr = 0.f, rr4 = 0.f;  // sums of squared residuals in units of s: against the six-bit code, against 4 h + 1.5
+    uint32_t* hout = hcodes + ((size_t)(r >> 6) * units * 64 + (size_t)(r & 63)) * 4;
+    uint32_t* lout = lrec + (size_t)r * lpitch;
+    for (uint32_t u = lane; u < units * 2; u += 64) {
+      uint32_t code[16];
+      u6_unit_codes(p, u, dim, rs, code, rr);
+      uint32_t hw[2] = {0u, 0u}, lw = 0u;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const uint32_t c = u * 16 + i;
+        const uint32_t h = code[i] >> 2, l = code[i] & 3u;
+        hw[i >> 3] |= h << (8 * (i & 3) + 4 * ((i >> 2) & 1));
+        lw |= l << (8 * (i & 3) + 2 * (i >> 2));
+        if (c < dim && rs.quant) {
+          const float rho4 = fmaf(-rs.s, 4.0f * (float)h - 30.5f, p[c]) * rs.inv;
+          rr4 = fmaf(rho4, rho4, rr4);
+        }
+      }
+      hout[(size_t)(u >> 1) * 256 + 2 * (u & 1)] = hw[0];
+      hout[(size_t)(u >> 1) * 256 + 2 * (u & 1) + 1] = hw[1];
+      lout[u] = lw;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      rr += __shfl_xor(rr, o);
+      rr4 += __shfl_xor(rr4, o);
+    }
+    const f2v sa = u6_row_pair(rs, rr, dim);
+    if (lane == 0) {
+      sa4[r] = f2v{sa.x, u6_row_pair(rs, rr4, dim).y};
+      lout[units * 2] = __float_as_uint(sa.y);
+    }
+  }
+}
+
+// ---- host side ---------------------------------------------------------------------------------
+// workgroups of a rows_to_u42_kernel launch over `rows` rows: four waves = four rows per workgroup at a time
+static inline uint32_t rows_to_u42_grid(uint64_t rows) { return (uint32_t)std::min<uint64_t>((rows + 3) / 4, 65536); }
+
+// units in flight per wave: the largest of 8, 6, 4 that divides the row's units, else the smallest of them that holds the row
+// or 8 (13 units: 8 + 5); 6 x 16 bytes per lane are the 6 KiB per wave the u6 pass keeps in flight
+static int u42_unit_chunk(uint32_t units) {
+  if (!units) return 0;
+  for (int uc = 8; uc >= 4; uc -= 2)
+    if (units % (uint32_t)uc == 0) return uc;
+  return units <= 4 ? 4 : units <= 6 ? 6 : 8;
+}
+
+typedef void (*scan42_fn)(Scan42Args);
+static scan42_fn pick_scan42(int uc) {
+  switch (uc) {
+    case 4: return scan_u42_kernel<4>;
+    case 6: return scan_u42_kernel<6>;
+    case 8: return scan_u42_kernel<8>;
+  }
+  return nullptr;
+}

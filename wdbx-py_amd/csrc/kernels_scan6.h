@@ -210,6 +210,58 @@ __global__ __launch_bounds__(256) void scan8_u6_sample_kernel(Scan6Args a) {
   }
 }
 
+// ---- the six-bit quantiser, shared by rows_to_u6_kernel and the split planes of kernels_scan42.h ----
+// a row's scale, by the whole wave
+struct U6RowScale {
+  float mx, s, inv;
+  bool finite, has_nan, vanishing, quant;
+};
+__device__ __forceinline__ U6RowScale u6_row_scale(const float* p, uint32_t dim, int lane) {
+  U6RowScale rs;
+  float mx = 0.f;
+  bool finite = true, has_nan = false;
+  for (uint32_t c = lane; c < dim; c += 64) {
+    const float v = p[c];
+    finite = finite && (fabsf(v) <= 3.4028235e38f);
+    has_nan = has_nan || (v != v);
+    mx = fmaxf(mx, fabsf(v));
+  }
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  rs.mx = mx;
+  rs.finite = __all(finite);
+  rs.has_nan = __any(has_nan);
+  // rows of vanishing magnitude (31 / max would overflow): every code is 32, the scale 0 (w = 0 exactly) and
+  // a = max|c| (sqrt(dim) + 1) >= |c|_2 covers the whole (negligible) score
+  rs.vanishing = mx < 1.2e-30f;
+  rs.quant = rs.finite && !rs.vanishing;
+  rs.s = rs.quant ? mx / 31.0f : 0.f;
+  rs.inv = rs.quant ? 31.0f / mx : 0.f;
+  return rs;
+}
+
+// the 16 codes of elements [16 u, 16 u + 16) of the row; rr gathers the squared residuals in units of s
+__device__ __forceinline__ void u6_unit_codes(const float* p, uint32_t u, uint32_t dim, const U6RowScale& rs, uint32_t (&code)[16],
+                                              float& rr) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const uint32_t c = u * 16 + i;
+    const float x = (c < dim && rs.quant) ? p[c] : 0.f;
+    const float k = fminf(fmaxf(rintf(x * rs.inv), -31.f), 31.f);
+    const float rho = fmaf(-rs.s, k, x) * rs.inv;  // (c - s k) / s: one rounding in the residual, one in the quotient
+    rr = fmaf(rho, rho, rr);
+    code[i] = (uint32_t)((int)k + 32);
+  }
+}
+
+// {s, a} of the row from the wave's sum of squared residuals (NaN / inf rows: the conventions of the header comment).
+// a, rounded up: 5e-4 relative covers the roundings of the residuals (2^-24 each), of their quotients by s (s * inv = 1
+// within 3 * 2^-24), of the sum of dimp squares in any order (gamma_dimp <= 2.5e-4 up to 4096 elements, halved by the root)
+// and of the root and the product; 1e-4 s absolute covers residuals and squares that underflow
+__device__ __forceinline__ f2v u6_row_pair(const U6RowScale& rs, float rr, uint32_t dim) {
+  const float a = rs.quant ? rs.s * fmaf(sqrtf(rr), 1.0005f, 1e-4f) : rs.vanishing ? rs.mx * (sqrtf((float)dim) + 1.0f) : 0.f;
+  return rs.has_nan ? f2v{-1.0f, 0.f} : !rs.finite ? f2v{NAN, 0.f} : f2v{rs.s, a};
+}
+
 // rows [r0, n) fp32 -> u6 shadow + {s, a} per row, one wave per row, one lane per unit of 16 elements
 __global__ __launch_bounds__(256) void rows_to_u6_kernel(const float* rows, u64 r0, u64 n, uint32_t dim, uint32_t pitch,
                                                          uint32_t units, uint32_t* codes, f2v* sa) {
@@ -217,36 +269,12 @@ __global__ __launch_bounds__(256) void rows_to_u6_kernel(const float* rows, u64 
   const u64 wave = (u64)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (u64)gridDim.x * 4;
   for (u64 r = r0 + wave; r < n; r += nw) {
     const float* p = rows + r * pitch;
-    float mx = 0.f;
-    bool finite = true, has_nan = false;
-    for (uint32_t c = lane; c < dim; c += 64) {
-      const float v = p[c];
-      finite = finite && (fabsf(v) <= 3.4028235e38f);
-      has_nan = has_nan || (v != v);
-      mx = fmaxf(mx, fabsf(v));
-    }
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    finite = __all(finite);
-    has_nan = __any(has_nan);
-    // rows of vanishing magnitude (31 / max would overflow): every code is 32, the scale 0 (w = 0 exactly) and
-    // a = max|c| (sqrt(dim) + 1) >= |c|_2 covers the whole (negligible) score
-    const bool vanishing = mx < 1.2e-30f;
-    const bool quant = finite && !vanishing;
-    const float s = quant ? mx / 31.0f : 0.f;
-    const float inv = quant ? 31.0f / mx : 0.f;
+    const U6RowScale rs = u6_row_scale(p, dim, lane);
     float rr = 0.f;  // sum of squared residuals in units of s
     uint32_t* out = codes + ((size_t)(r >> 6) * units * 64 + (size_t)(r & 63)) * 3;
     for (uint32_t u = lane; u < units; u += 64) {
       uint32_t code[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const uint32_t c = u * 16 + i;
-        const float x = (c < dim && quant) ? p[c] : 0.f;
-        const float k = fminf(fmaxf(rintf(x * inv), -31.f), 31.f);
-        const float rho = fmaf(-s, k, x) * inv;  // (c - s k) / s: one rounding in the residual, one in the quotient
-        rr = fmaf(rho, rho, rr);
-        code[i] = (uint32_t)((int)k + 32);
-      }
+      u6_unit_codes(p, u, dim, rs, code, rr);
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
         uint32_t w = 0;
@@ -256,11 +284,8 @@ __global__ __launch_bounds__(256) void rows_to_u6_kernel(const float* rows, u64 
       }
     }
     for (int o = 32; o > 0; o >>= 1) rr += __shfl_xor(rr, o);
-    // a, rounded up: 5e-4 relative covers the roundings of the residuals (2^-24 each), of their quotients by s (s * inv = 1
-    // within 3 * 2^-24), of the sum of dimp squares in any order (gamma_dimp <= 2.5e-4 up to 4096 elements, halved by the root)
-    // and of the root and the product; 1e-4 s absolute covers residuals and squares that underflow
-    const float a = quant ? s * fmaf(sqrtf(rr), 1.0005f, 1e-4f) : vanishing ? mx * (sqrtf((float)dim) + 1.0f) : 0.f;
-    if (lane == 0) sa[r] = has_nan ? f2v{-1.0f, 0.f} : !finite ? f2v{NAN, 0.f} : f2v{s, a};
+    const f2v pair = u6_row_pair(rs, rr, dim);
+    if (lane == 0) sa[r] = pair;
   }
 }
 

@@ -24,6 +24,8 @@
 //                           synthetic fill / normalise, read probes
 //   kernels_scan6.h         scan8_u6_kernel: the same selection over the six-bit u6 shadow copy with a stored residual norm per
 //                           row (rounds of single queries on large shards), its quantiser and the cut behind the re-scoring
+//   kernels_scan42.h        scan_u42_kernel: that scan's full pass over the same codes split in two planes -- every row's top four
+//                           bits, the low two bits only of the rows the four-bit bound cannot rule out; its quantiser
 //   kernels_range.h         range search: range_scan_kernel (fp32, every row scored exactly), range_filter_kernel (exact
 //                           scores of the u8 selection's candidates); wave-aggregated appends, no k
 //   kernels_subset.h        subset_kernel: exact scores of LISTED rows (wdbx_index_search_rows), a block of queries per fetched
@@ -106,6 +108,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "kernels_tiles.h"
 #include "kernels_scan8.h"
 #include "kernels_scan6.h"
+#include "kernels_scan42.h"
 #include "kernels_tiles8.h"
 #include "kernels_aux.h"
 #include "kernels_range.h"
@@ -130,7 +133,7 @@ static uint64_t device_bytes_resident(const wdbx_index* ix) {
   b += ix->halfmax_bytes + ix->tau_bytes + ix->cand_bytes + ix->count_bytes + ix->qb16_bytes + ix->qn_bytes + ix->selsrc_bytes;
   b += ix->qb8_bytes + ix->qpar_bytes + ix->pairs_bytes + ix->pair_count_bytes + ix->cnmax_bytes;
   b += ix->rcand_bytes + ix->rkeys_bytes + ix->rcnt_bytes + ix->rthr_bytes;
-  b += ix->rows6_bytes + ix->count6_bytes;
+  b += ix->rows6_bytes + ix->count6_bytes + ix->rows42_bytes + ix->count42_bytes;
   b += ix->sub_ids_bytes + ix->sub_keys_bytes + ix->mm_bytes + ix->rl_bytes + ix->lab_bytes;
   return b;
 }
@@ -208,7 +211,7 @@ void wdbx_index_destroy(wdbx_index* ix) try {
                     ix->d_qblock, ix->d_halfmax, ix->d_tau, ix->d_cand, ix->d_count, ix->d_ticket, ix->d_mask, ix->d_dump, ix->d_sel,
                     ix->d_state, ix->d_cn, ix->d_cnmax, ix->d_qb16, ix->d_rows16, ix->d_rows8, ix->d_scale8, ix->d_selsrc,
                     ix->d_gmax, ix->d_qn, ix->d_rows8g, ix->d_groups8, ix->d_gbad8, ix->d_gref8, ix->d_over_list, ix->d_qb8,
-                    ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr, ix->d_rows6, ix->d_count6,
+                    ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr, ix->d_rows6, ix->d_count6, ix->d_rows42, ix->d_count42,
                     ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys, ix->d_mm, ix->d_rl, ix->d_lab};
     for (void* p : bufs)
       if (p) (void)hipFree(p);
@@ -255,6 +258,7 @@ int wdbx_index_clear(wdbx_index* ix) try {
   ix->shadow_rows = 0;
   ix->shadow8_rows = 0;
   ix->shadow6_rows = 0;
+  ix->shadow42_rows = 0;
   ix->shadowg_rows = 0;
   ix->shadowg_tail_n = ~0ull;
   ix->labels.clear();  // (back to "no label was ever set")
@@ -380,6 +384,7 @@ int wdbx_index_compact(wdbx_index* ix, const uint64_t* src_rows, uint64_t n_keep
   ix->shadow_rows = std::min(ix->shadow_rows, first_moved);
   ix->shadow8_rows = std::min(ix->shadow8_rows, first_moved);
   ix->shadow6_rows = std::min(ix->shadow6_rows, first_moved);
+  ix->shadow42_rows = std::min(ix->shadow42_rows, first_moved);
   ix->shadowg_rows = std::min(ix->shadowg_rows, first_moved / 64 * 64);  // (whole 64-row groups: a group's scale depends on all its rows)
   ix->shadowg_tail_n = ~0ull;  // the groups behind the new last row still describe dropped rows: rewritten by the next batch
   ix->cn_stats_dirty = true;  // the running maximum / sum still hold the dropped rows' norms
@@ -1993,6 +1998,7 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"scan8_per_query", &wdbx_index::opt_scan8_per_query},
     {"scan_u6", &wdbx_index::opt_scan_u6},
     {"scan_u6_cap", &wdbx_index::opt_scan_u6_cap},
+    {"scan_u42", &wdbx_index::opt_scan_u42},
     {"batch_repair", &wdbx_index::opt_batch_repair},
     {"single_min_rows", &wdbx_index::opt_single_min_rows},
     {"range_min_rows", &wdbx_index::opt_range_min_rows},
@@ -2046,6 +2052,20 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
     for (uint32_t v : c) sum += v, mx = std::max<int64_t>(mx, v);
     return *value = name[14] == 's' ? sum : mx, WDBX_OK;
   }
+  if (name && !strcmp(name, "last_single_u42")) return *value = ix->last_single_u42, WDBX_OK;
+  if (name && !strcmp(name, "u42_survivors_sum")) {
+    // rows that passed the four-bit bound in the last round's full passes; waits for the stream
+    const uint32_t nq = ix->last_single_u42 ? std::min<uint32_t>(ix->last_batch_nq, 64) : 0;
+    std::vector<uint32_t> c(std::max<uint32_t>(nq, 1), 0u);
+    DeviceGuard g(ix->device);
+    if (nq) HIP_TRY(hipMemcpyAsync(c.data(), ix->d_count42, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    int64_t sum = 0;
+    for (uint32_t v : c) sum += v;
+    return *value = sum, WDBX_OK;
+  }
+  if (name && !strcmp(name, "shadow42_rows")) return *value = (int64_t)ix->shadow42_rows, WDBX_OK;
+  if (name && !strcmp(name, "shadow42_bytes")) return *value = (int64_t)ix->rows42_bytes, WDBX_OK;
   if (name && !strcmp(name, "shadow6_rows")) return *value = (int64_t)ix->shadow6_rows, WDBX_OK;
   if (name && !strcmp(name, "shadow6_bytes")) return *value = (int64_t)ix->rows6_bytes, WDBX_OK;
   if (name && !strcmp(name, "last_range_path")) return *value = ix->last_range_path, WDBX_OK;
