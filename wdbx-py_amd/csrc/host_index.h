@@ -1876,68 +1876,16 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
 }
 
 // ---- batched queries on the int8 tiles (kernels_tiles8.h) ----------------------------------------
-// The instance of one epilogue form for a block of 32 * CT8 queries: rows of 384 and 768 bytes (d <= 768 in steps that cover
-// the reference's embedding sizes 384 and 768; L2: 768 = BASELINE config 3) get the compile-time pitch, everything else the
-// run-time form with `ring` k-steps in flight.
-template <int PHASE, int CT8, Epi8 EPI, int METRIC, bool MASKED>
-static void (*gemm8_instance(uint32_t pitch8, int ring))(Gemm8Args) {
-  if constexpr (CT8 == 8) {
-    // (256-query blocks: 128 accumulator registers leave room for 3 k-steps in flight with compile-time addressing, 2 without;
-    // L2 runs on query blocks of at most 128: its epilogue keeps 16 more values per lane)
-    if constexpr (METRIC == WDBX_METRIC_L2) return nullptr;
-    else if (pitch8 == 384) return gemm_i8_kernel<PHASE, 8, 3, 384, EPI, METRIC, MASKED>;
-    else return gemm_i8_kernel<PHASE, 8, 2, 0, EPI, METRIC, MASKED>;
-  } else {
-    if (pitch8 == 384) return gemm_i8_kernel<PHASE, CT8, 6, 384, EPI, METRIC, MASKED>;
-    if (pitch8 == 768) return gemm_i8_kernel<PHASE, CT8, 6, 768, EPI, METRIC, MASKED>;
-    if (ring == 6) return gemm_i8_kernel<PHASE, CT8, 6, 0, EPI, METRIC, MASKED>;
-    if (ring == 4) return gemm_i8_kernel<PHASE, CT8, 4, 0, EPI, METRIC, MASKED>;
-    return gemm_i8_kernel<PHASE, CT8, 2, 0, EPI, METRIC, MASKED>;
-  }
-}
-
-// The epilogue form.  The sample pass and L2 have the exact epilogue only.  The full pass of every inner-product instance
-// carries the prefilter, its tests in one block, since round 3 (-2 % against the round-2 form, identical candidates:
-// profiles/r03/c4_i8/); a call with a row mask (MASKED: the bad rows of g.gbad leave the hit set before pairs are appended)
-// runs that form and nothing else.  Option gemm8_variant (tools/probes/c4_i8_ab.py), for A/B: 13 = the round-2 form (exact
-// epilogue) everywhere, 12 = the prefilter with a branch per column group for 256-query blocks of 384-byte rows, 0 / 14 = the default.
-template <int PHASE, int CT8>
-static void (*pick_gemm8(uint32_t pitch8, int ring, bool l2, bool masked, int variant, bool multi))(Gemm8Args) {
-  constexpr int C = WDBX_METRIC_COSINE, L = WDBX_METRIC_L2;
-  if constexpr (PHASE == 0) {
-    if (multi) return l2 ? gemm8_instance<0, CT8, EPI8_MULTI_EXACT, L, false>(pitch8, ring) : gemm8_instance<0, CT8, EPI8_MULTI_EXACT, C, false>(pitch8, ring);
-    return l2 ? gemm8_instance<0, CT8, EPI8_EXACT, L, false>(pitch8, ring) : gemm8_instance<0, CT8, EPI8_EXACT, C, false>(pitch8, ring);
-  } else {
-    // (a mask per query: the same product forms, the mask word read per column group)
-    if (multi) return l2 ? gemm8_instance<1, CT8, EPI8_MULTI_EXACT, L, false>(pitch8, ring) : gemm8_instance<1, CT8, EPI8_MULTI_PRE_BLOCK, C, false>(pitch8, ring);
-    if (l2) return masked ? gemm8_instance<1, CT8, EPI8_EXACT, L, true>(pitch8, ring) : gemm8_instance<1, CT8, EPI8_EXACT, L, false>(pitch8, ring);
-    if (masked) return gemm8_instance<1, CT8, EPI8_PRE_BLOCK, C, true>(pitch8, ring);
-    if (variant == 13) return gemm8_instance<1, CT8, EPI8_EXACT, C, false>(pitch8, ring);
-    if constexpr (CT8 == 8)
-      if (variant == 12 && pitch8 == 384) return gemm_i8_kernel<1, 8, 3, 384, EPI8_PRE_GROUP>;
-    return gemm8_instance<1, CT8, EPI8_PRE_BLOCK, C, false>(pitch8, ring);
-  }
-}
-
+// (the instances, their pickers and the launch helpers: kernels_tiles8.h, behind the kernel)
 template <int PHASE>
 static int launch_gemm8(wdbx_index* ix, const Gemm8Args& g, int ct, bool masked = false, bool multi = false) {
-  // k-steps (64 bytes of a row: two A fragments) in flight per wave: a divisor of the row's k-steps (pitch8 is a multiple of
-  // 128).  256-query blocks leave room for 2 or 3 (128 accumulator + 32 query-fragment registers), narrower blocks for 6.
-  const uint32_t steps = g.pitch8 / 64;
-  const int ring = ct == 4 ? 2 : (steps % 6 == 0 ? 6 : steps % 4 == 0 ? 4 : 2);
-  const int var = (int)ix->opt_gemm8_variant;
-  const bool l2 = ix->metric == WDBX_METRIC_L2;
-  void (*fn)(Gemm8Args) = ct == 4   ? pick_gemm8<PHASE, 8>(g.pitch8, ring, l2, masked, var, multi)
-                          : ct == 2 ? pick_gemm8<PHASE, 4>(g.pitch8, ring, l2, masked, var, multi)
-                                    : pick_gemm8<PHASE, 2>(g.pitch8, ring, l2, masked, var, multi);
-  if (!fn) return fail(WDBX_E_STATE, "no int8 tile instance for this query block");
-  const size_t lds = (size_t)64 * ct * g.pitch8 + (size_t)64 * ct * sizeof(f4);  // the query block + its parameters
-  HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const uint32_t grid = std::min<uint32_t>(g.num_tiles, (uint32_t)ix->cu_count);  // one 8-wave workgroup per CU
+  const Gemm8Launch l = gemm8_launch_of<PHASE>(ct, g.pitch8, ix->metric, masked, multi, (int)ix->opt_gemm8_variant);
+  if (!l.fn) return fail(WDBX_E_STATE, "no int8 tile instance for this query block");
+  HIP_TRY(gemm8_prepare(l));
+  const uint32_t grid = gemm8_grid(g.num_tiles, (uint32_t)ix->cu_count);
   int rc = record(ix->gemm_ev, ix->profile, ix->stream, true);
   if (rc) return rc;
-  hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds, ix->stream, g);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(enqueue_gemm8(ix->stream, l, g, grid));
   return record(ix->gemm_ev, ix->profile, ix->stream, false);
 }
 
@@ -2063,7 +2011,7 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
     if (!ix->d_gref8) HIP_TRY(hipMalloc((void**)&ix->d_gref8, 8 * sizeof(float)));
     HIP_TRY(hipMemsetAsync(ix->d_gref8, 0, 8 * sizeof(float), ix->stream));
     const u64 ngroups = (ix->n + 63) / 64;
-    const uint32_t blocks = (uint32_t)std::min<u64>((ngroups + 255) / 256, 1024);
+    const uint32_t blocks = group_ref_grid(ngroups);
     for (int pass = 0; pass < 2; ++pass)
       hipLaunchKernelGGL(group_ref_kernel, dim3(blocks), dim3(256), 0, ix->stream, (const f4*)ix->d_groups8, ngroups, ix->d_gref8,
                          (uint32_t*)(ix->d_gref8 + 4), pass);

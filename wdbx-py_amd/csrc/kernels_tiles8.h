@@ -521,6 +521,91 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(Gemm8Args a) {
     if (lane == 0) a.pair_count[wave_id] = npairs;
 }
 
+// ---- the launch of one tile pass, as far as it does not need the index (host_index.h::launch_gemm8 adds the profile events
+// and the CU count; tests/kernel_harness/tile_harness.hip launches through the same helpers) ----
+typedef void (*gemm8_fn)(Gemm8Args);
+
+// The instance of one epilogue form for a block of 32 * CT8 queries: rows of 384 and 768 bytes (d <= 768 in steps that cover
+// the reference's embedding sizes 384 and 768; L2: 768 = BASELINE config 3) get the compile-time pitch, everything else the
+// run-time form with `ring` k-steps in flight.
+template <int PHASE, int CT8, Epi8 EPI, int METRIC, bool MASKED>
+static gemm8_fn gemm8_instance(uint32_t pitch8, int ring) {
+  if constexpr (CT8 == 8) {
+    // (256-query blocks: 128 accumulator registers leave room for 3 k-steps in flight with compile-time addressing, 2 without;
+    // L2 runs on query blocks of at most 128: its epilogue keeps 16 more values per lane)
+    if constexpr (METRIC == WDBX_METRIC_L2) return nullptr;
+    else if (pitch8 == 384) return gemm_i8_kernel<PHASE, 8, 3, 384, EPI, METRIC, MASKED>;
+    else return gemm_i8_kernel<PHASE, 8, 2, 0, EPI, METRIC, MASKED>;
+  } else {
+    if (pitch8 == 384) return gemm_i8_kernel<PHASE, CT8, 6, 384, EPI, METRIC, MASKED>;
+    if (pitch8 == 768) return gemm_i8_kernel<PHASE, CT8, 6, 768, EPI, METRIC, MASKED>;
+    if (ring == 6) return gemm_i8_kernel<PHASE, CT8, 6, 0, EPI, METRIC, MASKED>;
+    if (ring == 4) return gemm_i8_kernel<PHASE, CT8, 4, 0, EPI, METRIC, MASKED>;
+    return gemm_i8_kernel<PHASE, CT8, 2, 0, EPI, METRIC, MASKED>;
+  }
+}
+
+// The epilogue form.  The sample pass and L2 have the exact epilogue only.  The full pass of every inner-product instance
+// carries the prefilter, its tests in one block, since round 3 (-2 % against the round-2 form, identical candidates:
+// profiles/r03/c4_i8/); a call with a row mask (MASKED: the bad rows of g.gbad leave the hit set before pairs are appended)
+// runs that form and nothing else.  Option gemm8_variant (tools/probes/c4_i8_ab.py), for A/B: 13 = the round-2 form (exact
+// epilogue) everywhere, 12 = the prefilter with a branch per column group for 256-query blocks of 384-byte rows, 0 / 14 = the default.
+template <int PHASE, int CT8>
+static gemm8_fn pick_gemm8(uint32_t pitch8, int ring, bool l2, bool masked, int variant, bool multi) {
+  constexpr int C = WDBX_METRIC_COSINE, L = WDBX_METRIC_L2;
+  if constexpr (PHASE == 0) {
+    if (multi) return l2 ? gemm8_instance<0, CT8, EPI8_MULTI_EXACT, L, false>(pitch8, ring) : gemm8_instance<0, CT8, EPI8_MULTI_EXACT, C, false>(pitch8, ring);
+    return l2 ? gemm8_instance<0, CT8, EPI8_EXACT, L, false>(pitch8, ring) : gemm8_instance<0, CT8, EPI8_EXACT, C, false>(pitch8, ring);
+  } else {
+    // (a mask per query: the same product forms, the mask word read per column group)
+    if (multi) return l2 ? gemm8_instance<1, CT8, EPI8_MULTI_EXACT, L, false>(pitch8, ring) : gemm8_instance<1, CT8, EPI8_MULTI_PRE_BLOCK, C, false>(pitch8, ring);
+    if (l2) return masked ? gemm8_instance<1, CT8, EPI8_EXACT, L, true>(pitch8, ring) : gemm8_instance<1, CT8, EPI8_EXACT, L, false>(pitch8, ring);
+    if (masked) return gemm8_instance<1, CT8, EPI8_PRE_BLOCK, C, true>(pitch8, ring);
+    if (variant == 13) return gemm8_instance<1, CT8, EPI8_EXACT, C, false>(pitch8, ring);
+    if constexpr (CT8 == 8)
+      if (variant == 12 && pitch8 == 384) return gemm_i8_kernel<1, 8, 3, 384, EPI8_PRE_GROUP>;
+    return gemm8_instance<1, CT8, EPI8_PRE_BLOCK, C, false>(pitch8, ring);
+  }
+}
+
+// k-steps (64 bytes of a row: two A fragments) in flight per wave for query blocks of 64 * ct: a divisor of the row's k-steps
+// (pitch8 is a multiple of 128).  256-query blocks leave room for 2 or 3 (128 accumulator + 32 query-fragment registers),
+// narrower blocks for 6.
+static inline int gemm8_ring(int ct, uint32_t pitch8) {
+  const uint32_t steps = pitch8 / 64;
+  return ct == 4 ? 2 : (steps % 6 == 0 ? 6 : steps % 4 == 0 ? 4 : 2);
+}
+// dynamic LDS of a launch: the query block + its parameters
+static inline size_t gemm8_lds_bytes(int ct, uint32_t pitch8) { return (size_t)64 * ct * pitch8 + (size_t)64 * ct * sizeof(f4); }
+// one 8-wave workgroup per CU
+static inline uint32_t gemm8_grid(uint32_t num_tiles, uint32_t cus) { return std::min<uint32_t>(num_tiles, cus); }
+
+// the instance (null: the library has none), the ring it was compiled with and its LDS bytes for query blocks of 64 * ct
+// (ct = 1, 2, 4)
+struct Gemm8Launch {
+  gemm8_fn fn;
+  int ring;
+  size_t lds;
+};
+template <int PHASE>
+static Gemm8Launch gemm8_launch_of(int ct, uint32_t pitch8, int metric, bool masked, bool multi, int variant) {
+  const int ring = gemm8_ring(ct, pitch8);
+  const bool l2 = metric == WDBX_METRIC_L2;
+  gemm8_fn fn = ct == 4   ? pick_gemm8<PHASE, 8>(pitch8, ring, l2, masked, variant, multi)
+                : ct == 2 ? pick_gemm8<PHASE, 4>(pitch8, ring, l2, masked, variant, multi)
+                          : pick_gemm8<PHASE, 2>(pitch8, ring, l2, masked, variant, multi);
+  // (the compile-time pitches carry a ring of their own: see gemm8_instance)
+  const int used = pitch8 == 384 ? (ct == 4 ? 3 : 6) : (pitch8 == 768 && ct != 4) ? 6 : ring;
+  return Gemm8Launch{fn, used, gemm8_lds_bytes(ct, pitch8)};
+}
+static inline hipError_t gemm8_prepare(const Gemm8Launch& l) {
+  return hipFuncSetAttribute((const void*)l.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds);
+}
+static inline hipError_t enqueue_gemm8(hipStream_t stream, const Gemm8Launch& l, const Gemm8Args& g, uint32_t grid) {
+  hipLaunchKernelGGL(l.fn, dim3(grid), dim3(512), l.lds, stream, g);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // shadow copy G: one workgroup per 64-row group.  Pass 1: the group's largest finite |element| over its finite rows
 // -> s_g = max / 127.  Pass 2: every row as signed bytes n = rint(c / s_g) (non-finite rows: zeros), its |n|_2 and
@@ -976,3 +1061,5 @@ __global__ __launch_bounds__(256) void group_ref_kernel(const f4* groups, u64 n_
     }
   }
 }
+// workgroups of a group_ref_kernel pass over `groups` 64-row groups
+static inline uint32_t group_ref_grid(uint64_t groups) { return (uint32_t)std::min<uint64_t>((groups + 255) / 256, 1024); }
