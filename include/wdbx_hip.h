@@ -248,6 +248,48 @@ int wdbx_index_search_distinct(wdbx_index* idx, const float* queries, int nq, in
                                const uint32_t* mask_words, uint64_t mask_word_count, /* NULL = every row */
                                int64_t* out_idx, float* out_score, uint32_t* out_label /* may be NULL */);
 
+/* ---- multi-vector search: labels ranked by the sum of per-vector best scores ---- */
+/* Late interaction / MaxSim (ColBERT, Qdrant's multivector, Vespa; the reference has nothing): a document is stored as many
+ * rows under one label (wdbx_index_set_labels), a query is itself several vectors, and
+ *     score(query, label) = sum over the query's vectors t of ( best score of t among the label's rows ).
+ * Query i's vectors are rows vector_offsets[i] .. vector_offsets[i + 1] - 1 of `vectors`.  Blocking, host buffers; the call
+ * holds the handle's mutex to its end and nothing of it stays valid in the handle.
+ *   Eligible row: a live row the mask allows (mask_words NULL = every row; else mask_word_count words, at least
+ *   ceil(rows / 32)) whose score against vector t is not NaN -- the conditions of wdbx_index_search_distinct.
+ *   Per-vector best m(t, L): the best score of t among label L's eligible rows (L2: the smallest squared distance): the score
+ *   part of the maximum of the rows' (score, row) keys, exactly as the distinct search's full pass forms it.  A row's score
+ *   here is bit-identical to wdbx_index_search_rows and wdbx_index_range_search for the same row and vector.
+ *   Label score S(L): the fp32 left fold ((+0.0f + m(t0, L)) + m(t0 + 1, L)) + ... in the caller's vector order, plain adds
+ *   in the ranking domain (L2 adds the negated distances; out_score is the positive sum of squared distances).
+ *   Never returned: a label without an eligible row for SOME vector of the query, and a label whose sum is NaN (inf + -inf).
+ *   A row labelled WDBX_LABEL_NONE is a label of its own; on a handle without any labels every row is one (the same path).
+ *   Order: (S descending, position of the label in the label order ascending) -- L2: (sum ascending, same tie rule).  The
+ *   label order is stored label value ascending, then the unlabelled rows by row number.  Total and deterministic: every key
+ *   and every accumulator entry has one writer, answers are bit-identical from run to run.
+ *   Outputs [nq, k]: out_idx the label's SMALLEST row number (unique per label; what names an unlabelled row), out_label
+ *   (may be NULL) its stored label, out_score S.  Unused slots hold -1 / 0 / WDBX_LABEL_NONE.  An empty index: every slot
+ *   -1, nothing launched.  normalize_queries normalises each vector on its own.
+ *   WDBX_E_INVALID: nq < 1, k outside [1, WDBX_MAX_K], a null buffer, vector_offsets[0] != 0, a query with no vector or with
+ *   more than WDBX_MAX_QUERY_VECTORS, a mask shorter than ceil(rows / 32) words (checked under the handle's lock).  A refused
+ *   call leaves the handle usable.
+ *   Rounds: the call's vectors are cut into rounds of consecutive vectors, at most option "multivector_round_vectors"
+ *   (default 256, 1 .. 256; anything else is WDBX_E_INVALID) and at most what keeps a round's item keys and ranking scratch
+ *   within 256 MiB (one vector per round when one vector's keys alone pass that).  A round may hold several queries and may
+ *   cut a query in two: the one fp32 accumulator per label of the handle carries its fold into the next round (a dead label
+ *   is NaN in it).  Per round: the distinct search's scoring kernel with the round's vectors as its queries (every fetched
+ *   row scored once per block of 8 vectors; counted as scan launches in wdbx_index_profile_read), then one reduce-and-rank
+ *   kernel (per-workgroup top-k lists and the merge kernel below option "select_min_k", a key per label and the radix-select
+ *   chain from it).  The answer does not depend on the rounds.
+ *   get_option, read-only: "last_multivector_rounds", "last_multivector_vectors", "last_multivector_labels" (0 after a call
+ *   on an empty index). */
+#define WDBX_MAX_QUERY_VECTORS 1024
+int wdbx_index_search_multivector(wdbx_index* idx,
+                                  const float* vectors,           /* [vector_offsets[nq], dim]: the queries' vectors back to back */
+                                  const uint64_t* vector_offsets, /* [nq + 1], [0] == 0, strictly increasing */
+                                  int nq, int k, int normalize_queries,
+                                  const uint32_t* mask_words, uint64_t mask_word_count, /* NULL = every row */
+                                  int64_t* out_idx, float* out_score, uint32_t* out_label /* [nq, k]; out_label may be NULL */);
+
 /* ---- range search: every row within a similarity, no k ----------------------- */
 /* every row whose score reaches thresholds[q] (cosine/IP: score >= t; L2: squared distance <= t), exact fp32,
  * per query sorted like wdbx_index_search; replaces faiss' IndexFlat range_search, which the reference never reaches

@@ -193,6 +193,13 @@ struct wdbx_index {
   size_t lab_off_dense = 0, lab_off_span = 0, lab_off_label = 0;
   int last_distinct_path = 0;  // 0 nothing launched, 1 over-fetch alone, 2 over-fetch + full pass for the short queries, 3 full pass
   int64_t last_distinct_items = 0, last_distinct_labels = 0, last_distinct_short = 0;
+  // multi-vector search (wdbx_index_search_multivector): the smallest row of each label of that label order, on the host (what a
+  // ranked label position is reported as), and one allocation of the call's state: the fp32 accumulator of the query a round
+  // boundary cuts, [lab_labels], then the segments of every round (host_multivector.h).  Keys and lists as the distinct search.
+  std::vector<uint32_t> lab_row0;
+  char* d_mv = nullptr;
+  size_t mv_bytes = 0;
+  int64_t last_multivector_rounds = 0, last_multivector_vectors = 0, last_multivector_labels = 0;
   // profiling
   bool profile = false;
   EventPool scan_ev, merge_ev, gemm_ev, sample_ev;
@@ -203,7 +210,8 @@ struct wdbx_index {
           opt_gemm8_refine = 1, opt_scan8_sample4 = 1, opt_gemm_l2 = 1, opt_gemm_l2_i8 = 1, opt_force_ragged = 0,
           opt_gemm_ct = 0, opt_wg_merge = 1, opt_zero_copy = 1, opt_lone_host_select = 1, opt_lds_lists = 0,
           opt_merge_fast = 1, opt_poll_done = 1, opt_scan_one_grid = 1, opt_select_min_k = 200, opt_gemm_min_nq = 4, opt_gemm_min_rows = 65536, opt_gemm_min_work = 800000,
-          opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0, opt_scan_u42 = -1, opt_gemm_masked = 1, opt_rows_keys_max = 8192, opt_distinct_overfetch = 4;
+          opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0, opt_scan_u42 = -1, opt_gemm_masked = 1, opt_rows_keys_max = 8192, opt_distinct_overfetch = 4,
+          opt_multivector_round_vectors = 256;
 };
 
 struct DeviceGuard {

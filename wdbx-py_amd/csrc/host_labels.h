@@ -21,6 +21,7 @@ struct LabelOrder {
   std::vector<uint32_t> dense;        // [n] dense label index of each position (each NONE row its own)
   std::vector<uint32_t> span_item0;   // [n_spans + 1] first item of each span; the last entry = n_items
   std::vector<uint32_t> label_item0;  // [n_labels + 1] first item of each label; the last entry = n_items
+  std::vector<uint32_t> label_row0;   // [n_labels] smallest row of each label (host only: what a ranked label is reported as)
   uint32_t n_labels = 0, n_items = 0, n_spans = 0;
 };
 
@@ -42,6 +43,7 @@ static inline void label_order_build(const uint32_t* labels, uint64_t n_set, uin
     const bool new_span = p % LABEL_SPAN == 0;
     if (new_label) {
       o.label_item0.push_back(o.n_items);
+      o.label_row0.push_back((uint32_t)keyed[(size_t)p]);
       ++o.n_labels;
     }
     if (new_span) o.span_item0.push_back(o.n_items);

@@ -36,6 +36,9 @@
 //                           label): the best key of each label run inside a span of the label order, then of each label, ranked
 //   host_labels.h           the label order of a handle (rows sorted by (label, row), items, tables), the over-fetch's host walk, the
 //                           full pass's rounds, grids and scratch
+//   kernels_multivector.h   multivector_rank_kernel: the reduction and ranking of wdbx_index_search_multivector (late interaction): per
+//                           label the sum over a query's vectors of the vector's best key score, the labels ranked by that sum
+//   host_multivector.h      the rounds and segments of that call's vectors, its route, grids and scratch
 //   host_multimask.h        a call with one row mask per query: the placement of its queries in the int8 tiles' query blocks
 //   host_calls.h            what the blocking entry points share, device-free: allowed rows of a mask, padded query copies, the host
 //                           ranking of a lone query's keys, the class-by-class fallback loop
@@ -81,6 +84,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_subset.h"  // (device-free as well: row-list validation, route and grid sizing of a search among listed rows)
 #include "host_multimask.h"  // (device-free as well: where the queries of a call with a mask per query sit in the tile blocks)
 #include "host_labels.h"  // (device-free as well: label order, items, over-fetch walk, rounds and scratch of a distinct search)
+#include "host_multivector.h"  // (device-free as well: rounds, segments, route and scratch of a multi-vector search)
 #include "host_rowlists.h"  // (device-free as well: slots, rounds, query blocks and work items of a call with a row list per query)
 
 #define HIP_TRY(expr)                                                                        \
@@ -116,6 +120,8 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "kernels_rowlists.h"
 #include "kernels_labels.h"
 static_assert(LABEL_SPAN_DEV == LABEL_SPAN, "the kernels walk the spans the host built");
+#include "kernels_multivector.h"
+static_assert(MULTIVECTOR_MAX_VECTORS == WDBX_MAX_QUERY_VECTORS, "the plan's limit is the header's");
 #include "host_index.h"
 #include "host_group.h"
 
@@ -134,7 +140,7 @@ static uint64_t device_bytes_resident(const wdbx_index* ix) {
   b += ix->qb8_bytes + ix->qpar_bytes + ix->pairs_bytes + ix->pair_count_bytes + ix->cnmax_bytes;
   b += ix->rcand_bytes + ix->rkeys_bytes + ix->rcnt_bytes + ix->rthr_bytes;
   b += ix->rows6_bytes + ix->count6_bytes + ix->rows42_bytes + ix->count42_bytes;
-  b += ix->sub_ids_bytes + ix->sub_keys_bytes + ix->mm_bytes + ix->rl_bytes + ix->lab_bytes;
+  b += ix->sub_ids_bytes + ix->sub_keys_bytes + ix->mm_bytes + ix->rl_bytes + ix->lab_bytes + ix->mv_bytes;
   return b;
 }
 
@@ -212,7 +218,7 @@ void wdbx_index_destroy(wdbx_index* ix) try {
                     ix->d_state, ix->d_cn, ix->d_cnmax, ix->d_qb16, ix->d_rows16, ix->d_rows8, ix->d_scale8, ix->d_selsrc,
                     ix->d_gmax, ix->d_qn, ix->d_rows8g, ix->d_groups8, ix->d_gbad8, ix->d_gref8, ix->d_over_list, ix->d_qb8,
                     ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr, ix->d_rows6, ix->d_count6, ix->d_rows42, ix->d_count42,
-                    ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys, ix->d_mm, ix->d_rl, ix->d_lab};
+                    ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys, ix->d_mm, ix->d_rl, ix->d_lab, ix->d_mv};
     for (void* p : bufs)
       if (p) (void)hipFree(p);
     if (ix->h_stage) (void)hipHostFree(ix->h_stage);
@@ -1009,6 +1015,7 @@ static int ensure_label_order(wdbx_index* ix) {
   ix->lab_items = lo.n_items;
   ix->lab_labels = lo.n_labels;
   ix->lab_spans = lo.n_spans;
+  ix->lab_row0 = std::move(lo.label_row0);
   ix->lab_n = ix->n;
   ix->lab_valid = true;
   return WDBX_OK;
@@ -1175,6 +1182,155 @@ int wdbx_index_search_distinct(wdbx_index* ix, const float* queries, int nq, int
     }
   }
   ix->last_distinct_path = kp ? DISTINCT_BOTH : DISTINCT_FULL;
+  return WDBX_OK;
+} WDBX_CATCH
+
+// ---- multi-vector search: labels ranked by the sum of per-vector best scores (host_multivector.h, kernels_multivector.h,
+// DESIGN.md section 4.12) ----
+// Under the handle's mutex to its end.  Per round of vectors (multivector_plan): label_keys_kernel with the round's vectors as
+// its queries (bracketed as a scan launch), multivector_rank_kernel over the round's segments and, for the segments that end a
+// query, merge_kernel over their partial lists or per query the radix-select chain over its label keys (bracketed as merge
+// launches).  No memset: every item key, accumulator entry, list entry and label key that is read has been written.
+int wdbx_index_search_multivector(wdbx_index* ix, const float* vectors, const uint64_t* vector_offsets, int nq, int k,
+                                  int normalize_queries, const uint32_t* mask_words, uint64_t mask_word_count, int64_t* out_idx,
+                                  float* out_score, uint32_t* out_label) try {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  if (nq < 1) return fail(WDBX_E_INVALID, "nq=%d", nq);
+  if (!vectors || !vector_offsets || !out_idx || !out_score) return fail(WDBX_E_INVALID, "null buffer");
+  if (k < 1 || k > WDBX_MAX_K) return fail(WDBX_E_INVALID, "k=%d outside [1, %d]", k, WDBX_MAX_K);
+  if (vector_offsets[0] != 0) return fail(WDBX_E_INVALID, "vector_offsets[0]=%llu, not 0", (u64)vector_offsets[0]);
+  for (int q = 0; q < nq; ++q) {
+    if (vector_offsets[q + 1] <= vector_offsets[q]) return fail(WDBX_E_INVALID, "query %d has no vector", q);
+    if (vector_offsets[q + 1] - vector_offsets[q] > WDBX_MAX_QUERY_VECTORS)
+      return fail(WDBX_E_INVALID, "query %d has %llu vectors, more than %d", q, (u64)(vector_offsets[q + 1] - vector_offsets[q]), WDBX_MAX_QUERY_VECTORS);
+  }
+  std::lock_guard<std::mutex> lk(ix->mu);
+  DeviceGuard g(ix->device);
+  int rc;
+  const size_t elems = (size_t)nq * k;
+  ix->last_multivector_rounds = ix->last_multivector_vectors = ix->last_multivector_labels = 0;
+  if (ix->n == 0) {  // every slot empty, nothing launched
+    for (size_t i = 0; i < elems; ++i) {
+      out_idx[i] = -1;
+      out_score[i] = 0.0f;
+      if (out_label) out_label[i] = WDBX_LABEL_NONE;
+    }
+    return WDBX_OK;
+  }
+  if (mask_words && (rc = check_mask_words(ix->n, mask_word_count))) return rc;
+  if (ix->n >= 0xFFFFFF00ull) return fail(WDBX_E_INVALID, "shard holds too many rows for 32-bit row keys");
+  if ((rc = ensure_label_order(ix))) return rc;
+  const uint64_t total = vector_offsets[nq];
+  const MultivectorPlan mp = multivector_plan(vector_offsets, nq, ix->lab_items, ix->lab_labels, ix->lab_spans, k, ix->cu_count,
+                                              ix->opt_select_min_k, ix->opt_multivector_round_vectors);
+  if ((rc = ensure_out(ix, elems))) return rc;
+  if ((rc = grow((void**)&ix->d_sub_keys, &ix->sub_keys_bytes, (mp.keys_u64 + (mp.select ? mp.rank_u64 : 0)) * sizeof(u64)))) return rc;
+  if (mp.select) {
+    if ((rc = grow((void**)&ix->d_sel, &ix->sel_bytes, (size_t)WDBX_MAX_K * sizeof(u64)))) return rc;
+    if ((rc = grow((void**)&ix->d_state, &ix->state_bytes, sizeof(SelectState)))) return rc;
+  } else if ((rc = grow((void**)&ix->d_partials, &ix->partials_bytes, mp.rank_u64 * sizeof(u64)))) {
+    return rc;
+  }
+  const size_t acc_bytes = ((size_t)ix->lab_labels * sizeof(float) + 255) / 256 * 256;
+  const size_t seg_bytes = mp.segments.size() * sizeof(MultivectorSegment);
+  if ((rc = grow((void**)&ix->d_mv, &ix->mv_bytes, acc_bytes + seg_bytes))) return rc;
+  const MultivectorSegment* const d_segs = (const MultivectorSegment*)(ix->d_mv + acc_bytes);
+  HIP_TRY(hipMemcpyAsync(ix->d_mv + acc_bytes, mp.segments.data(), seg_bytes, hipMemcpyHostToDevice, ix->stream));
+  if ((rc = upload_queries(ix, vectors, total, normalize_queries))) return rc;
+  MaskScope scope(ix);
+  if (mask_words && (rc = scope.set(mask_words))) return rc;
+  const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
+  const label_keys_fn kfn = pick_label_keys(ix->metric, mp.qb, pitch4);
+  if (!kfn) return fail(WDBX_E_STATE, "no label-keys instance with %d vectors per block", mp.qb);
+  const bool reg = k <= 128 && !ix->opt_lds_lists;
+  const multivector_rank_fn rfn = pick_multivector_rank(mp.select ? 2 : (reg ? 1 : 0));
+  if (mp.lds >= 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)rfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mp.lds));
+  u64* const d_label_keys = ix->d_sub_keys + mp.keys_u64;  // (select route)
+  for (const MultivectorRound& r : mp.rounds) {
+    LabelKeysArgs a = {};
+    a.rows = (const f4*)ix->d_rows;
+    a.queries = (const f4*)(ix->d_q + (size_t)r.first * ix->pitch);
+    a.order = (const uint32_t*)ix->d_lab;
+    a.dense = (const uint32_t*)(ix->d_lab + ix->lab_off_dense);
+    a.span_item0 = (const uint32_t*)(ix->d_lab + ix->lab_off_span);
+    a.mask = ix->active_mask;
+    a.keys = ix->d_sub_keys;
+    a.key_stride = ix->lab_items;
+    a.n = (uint32_t)ix->n;
+    a.n_spans = ix->lab_spans;
+    a.pitch4 = pitch4;
+    a.nq = r.vectors;
+    const uint32_t vblocks = (r.vectors + (uint32_t)mp.qb - 1) / (uint32_t)mp.qb;
+    const uint32_t sblocks = r.vectors == (uint32_t)mp.round_max ? mp.score_blocks
+                                                                 : multivector_score_blocks(r.vectors, mp.qb, ix->lab_spans, ix->cu_count);
+    if ((rc = record(ix->scan_ev, ix->profile, ix->stream, true))) return rc;
+    hipLaunchKernelGGL(kfn, dim3(sblocks, vblocks), dim3(256), 0, ix->stream, a);
+    HIP_TRY(hipGetLastError());
+    if ((rc = record(ix->scan_ev, ix->profile, ix->stream, false))) return rc;
+    MultivectorRankArgs m = {};
+    m.keys = ix->d_sub_keys;
+    m.key_stride = ix->lab_items;
+    m.label_item0 = (const uint32_t*)(ix->d_lab + ix->lab_off_label);
+    m.n_labels = ix->lab_labels;
+    m.acc = (float*)ix->d_mv;
+    m.out = mp.select ? d_label_keys : ix->d_partials;
+    m.k = k;
+    // a first segment that reads the accumulator and a LAST one that writes it must not share a launch: the writer goes second
+    const MultivectorSegment& s_first = mp.segments[r.seg0];
+    const MultivectorSegment& s_last = mp.segments[r.seg0 + r.segs - 1];
+    const bool split = r.segs > 1 && (s_first.carry & MV_CARRY_IN) && (s_last.carry & MV_CARRY_OUT);
+    if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
+    m.segs = d_segs + r.seg0;
+    hipLaunchKernelGGL(rfn, dim3(mp.rank_blocks, r.segs - (split ? 1u : 0u)), dim3(256), mp.lds, ix->stream, m);
+    HIP_TRY(hipGetLastError());
+    if (split) {
+      m.segs = d_segs + r.seg0 + r.segs - 1;
+      hipLaunchKernelGGL(rfn, dim3(mp.rank_blocks, 1), dim3(256), mp.lds, ix->stream, m);
+      HIP_TRY(hipGetLastError());
+    }
+    if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
+    if (!r.ranked) continue;
+    MergeArgs mg = {};
+    mg.k = k;
+    mg.metric = ix->metric;
+    if (mp.select) {
+      const uint32_t sgrid = radix_select_grid(ix->lab_labels, ix->cu_count);
+      for (uint32_t s = 0; s < r.ranked; ++s) {
+        if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
+        HIP_TRY(enqueue_radix_select(ix->stream, (const u64*)d_label_keys + (size_t)s * ix->lab_labels, (u64)ix->lab_labels, nullptr,
+                                     (SelectState*)ix->d_state, (u64*)ix->d_sel, (uint32_t)k, sgrid));
+        mg.out_idx = ix->d_oidx + (size_t)(r.ranked_query0 + s) * k;
+        mg.out_score = ix->d_oscore + (size_t)(r.ranked_query0 + s) * k;
+        HIP_TRY(enqueue_sort_out(ix->stream, (const u64*)ix->d_sel, (const SelectState*)ix->d_state, mg));
+        if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
+      }
+      continue;
+    }
+    mg.in = ix->d_partials;
+    mg.q_stride = (uint64_t)k * mp.rank_blocks;
+    mg.i_stride = mp.rank_blocks;
+    mg.p_stride = 1;
+    mg.P = mp.rank_blocks;
+    mg.list_len = k;
+    mg.out_idx = ix->d_oidx + (size_t)r.ranked_query0 * k;
+    mg.out_score = ix->d_oscore + (size_t)r.ranked_query0 * k;
+    if ((rc = launch_merge(ix, mg, (int)r.ranked))) return rc;
+  }
+  if ((rc = download_results(ix, elems, out_idx, out_score))) return rc;
+  // label positions -> (smallest row of the label, its stored label)
+  const uint64_t n_set = std::min<uint64_t>(ix->labels.size(), ix->n);
+  for (size_t i = 0; i < elems; ++i) {
+    uint32_t lab = WDBX_LABEL_NONE;
+    if (out_idx[i] >= 0) {
+      const uint32_t row = ix->lab_row0[(size_t)out_idx[i]];
+      out_idx[i] = (int64_t)row;
+      if (row < n_set) lab = ix->labels[row];
+    }
+    if (out_label) out_label[i] = lab;
+  }
+  ix->last_multivector_rounds = (int64_t)mp.rounds.size();
+  ix->last_multivector_vectors = (int64_t)total;
+  ix->last_multivector_labels = ix->lab_labels;
   return WDBX_OK;
 } WDBX_CATCH
 
@@ -2012,6 +2168,7 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"gemm_masked", &wdbx_index::opt_gemm_masked},
     {"rows_keys_max", &wdbx_index::opt_rows_keys_max},
     {"distinct_overfetch", &wdbx_index::opt_distinct_overfetch},
+    {"multivector_round_vectors", &wdbx_index::opt_multivector_round_vectors},
 };
 
 static int64_t* option_slot(wdbx_index* ix, const char* name) { return find_option(ix, kOptions, name); }
@@ -2023,6 +2180,8 @@ int wdbx_index_set_option(wdbx_index* ix, const char* name, int64_t value) try {
   if (!slot) return fail(WDBX_E_INVALID, "unknown option '%s'", name ? name : "(null)");
   if (slot == &ix->opt_gemm8_variant && value != 0 && value != 12 && value != 13 && value != 14)
     return fail(WDBX_E_INVALID, "gemm8_variant %lld: 0 (= 14), 12 and 13 are the forms the library has", (long long)value);
+  if (slot == &ix->opt_multivector_round_vectors && (value < 1 || value > MULTIVECTOR_MAX_ROUND))
+    return fail(WDBX_E_INVALID, "multivector_round_vectors %lld outside [1, %d]", (long long)value, MULTIVECTOR_MAX_ROUND);
   *slot = value;
   if (!strcmp(name, "group_bounds")) ix->gmax_valid = false;  // re-decide (and rebuild the group maxima) at the next batch
   return WDBX_OK;
@@ -2077,6 +2236,9 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "last_distinct_items")) return *value = ix->last_distinct_items, WDBX_OK;
   if (name && !strcmp(name, "last_distinct_labels")) return *value = ix->last_distinct_labels, WDBX_OK;
   if (name && !strcmp(name, "last_distinct_short")) return *value = ix->last_distinct_short, WDBX_OK;
+  if (name && !strcmp(name, "last_multivector_rounds")) return *value = ix->last_multivector_rounds, WDBX_OK;
+  if (name && !strcmp(name, "last_multivector_vectors")) return *value = ix->last_multivector_vectors, WDBX_OK;
+  if (name && !strcmp(name, "last_multivector_labels")) return *value = ix->last_multivector_labels, WDBX_OK;
   if (name && !strcmp(name, "last_sample_qn")) return *value = ix->last_sample_qn, WDBX_OK;
   if (name && !strcmp(name, "last_batch_repaired")) return *value = ix->last_batch_repaired ? 1 : 0, WDBX_OK;
   if (name && !strcmp(name, "last_batch_masked")) return *value = ix->last_batch_masked, WDBX_OK;

@@ -72,6 +72,8 @@ SIGNATURES = {
     "wdbx_index_get_labels": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]),
     "wdbx_index_search_distinct": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
                                              _i64p, _f32p, C.POINTER(C.c_uint32)]),
+    "wdbx_index_search_multivector": (C.c_int, [C.c_void_p, _f32p, _u64p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32),
+                                                C.c_uint64, _i64p, _f32p, C.POINTER(C.c_uint32)]),
     "wdbx_index_range_search": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
                                           C.c_uint64, _u64p, _i64p, _f32p]),
     "wdbx_device_alloc": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -412,6 +414,31 @@ class NativeIndex:
                                                     None if m is None else m.ctypes.data_as(u32p), 0 if m is None else m.size,
                                                     idx.ctypes.data_as(_i64p), score.ctypes.data_as(_f32p),
                                                     label.ctypes.data_as(u32p)))
+        return idx, score, label
+
+    def search_multivector(self, vectors, offsets, k: int, normalize_queries: bool = False,
+                           mask_words: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Late interaction (MaxSim): query ``i`` is the vectors ``offsets[i] .. offsets[i + 1] - 1`` of ``vectors``; the
+        labels are ranked by the sum over the query's vectors of each vector's best score among the label's rows (fp32,
+        folded in vector order).  Returns ``(rows int64, scores f32, labels uint32)``, each ``[nq, k]``: a label's smallest
+        row, its sum and its stored label; unused slots hold -1 / 0 / :data:`LABEL_NONE`.  ``mask_words`` as in
+        :meth:`search`."""
+        v = _as_f32(vectors, self.dim)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        nq = off.size - 1
+        if nq >= 1 and int(off[-1]) != v.shape[0]:
+            raise ValueError(f"offsets end at {int(off[-1])}, {v.shape[0]} vectors given")
+        idx = np.empty((max(nq, 0), int(k)), np.int64)
+        score = np.empty((max(nq, 0), int(k)), np.float32)
+        label = np.empty((max(nq, 0), int(k)), np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        m = None if mask_words is None else np.ascontiguousarray(mask_words, dtype=np.uint32)
+        # (nq, k, the offsets and the mask's length are checked by the library, the length under the handle's lock)
+        _check(self._lib.wdbx_index_search_multivector(self._h, v.ctypes.data_as(_f32p), off.ctypes.data_as(_u64p), nq, int(k),
+                                                       int(normalize_queries),
+                                                       None if m is None else m.ctypes.data_as(u32p), 0 if m is None else m.size,
+                                                       idx.ctypes.data_as(_i64p), score.ctypes.data_as(_f32p),
+                                                       label.ctypes.data_as(u32p)))
         return idx, score, label
 
     def range_search(self, queries, thresholds, normalize_queries: bool = False,

@@ -57,8 +57,18 @@ async def search_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
     """``POST /api/v1/vectors/search`` (server.py:141-152): body ``{"query_vector": [...], "limit": 10, "threshold": 0.0,
     "filter_metadata": null}`` -> ``{"results": [{"vector_id", "similarity", "metadata"}, ...]}``.  ``"distinct": true``
     (extension; absent, null or false = the plain search): at most one result per value of the store's ``DISTINCT_KEY``
-    metadata field (``wdbx.vector_search_distinct_async``)."""
+    metadata field (``wdbx.vector_search_distinct_async``).  ``"query_vectors": [[...], ...]`` (extension, in place of
+    ``query_vector``): a query of several vectors, the documents ranked by late interaction
+    (``wdbx.vector_search_multivector_async``); not together with ``query_vector`` or ``distinct``."""
     limit, threshold, flt = _parse_common(payload)
+    if payload.get("query_vectors") is not None:
+        if "query_vector" in payload or payload.get("distinct"):
+            raise ValueError("query_vectors stands alone: neither query_vector nor distinct goes with it")
+        vectors = payload["query_vectors"]
+        if not isinstance(vectors, (list, tuple)) or not vectors:
+            raise ValueError("query_vectors must be a non-empty list of vectors")
+        queries = [_vector(v, f"query_vectors[{i}]") for i, v in enumerate(vectors)]
+        return _render(await wdbx.vector_search_multivector_async(queries, limit, threshold, flt))
     if "query_vector" not in payload:
         raise ValueError("query_vector is required")
     query = _vector(payload["query_vector"], "query_vector")

@@ -823,6 +823,28 @@ class HipFlatIndex(VectorIndex):
                 return []
             raise
 
+    def search_multivector(self, vectors, limit: int = 10, mask=None) -> List[Tuple[str, float, int]]:
+        """Late interaction (MaxSim) over this shard: the labels ranked by the sum over the query's ``vectors`` of each
+        vector's best score among the label's rows, best first: ``[(id of the label's first row, score, label)]``, scores in
+        the units ``search`` returns.  ``mask`` as ``search``'s ``row_mask`` (bool per row or uint32 words).  Errors are
+        swallowed or raised as in ``search``."""
+        try:
+            actual_limit = min(int(limit), _native.MAX_K)
+            if self.next_index == 0 or actual_limit <= 0:
+                return []
+            vs = np.stack([self._prepare(v) for v in vectors])
+            words = None
+            if mask is not None:
+                words = mask if mask.dtype == np.uint32 else _native.pack_row_mask(mask)
+            idx, score, label = self._native.search_multivector(vs, [0, len(vs)], actual_limit, mask_words=words)
+            keep = idx[0] != -1
+            return [(vid, s, int(lab)) for (vid, s), lab in zip(self._map(idx[0], score[0]), label[0][keep])]
+        except Exception as e:
+            logger.error("Error in HIP multi-vector search: %s", e)
+            if self.swallow_errors:
+                return []
+            raise
+
     async def search_async(self, query_vector: np.ndarray, limit: int = 10) -> List[Tuple[str, float]]:
         loop = asyncio.get_event_loop()
         return await loop.run_in_executor(self.thread_pool, self.search, query_vector, limit)

@@ -1135,6 +1135,44 @@ class VectorStore:
         return await loop.run_in_executor(self.thread_pool, lambda: self.search_distinct(
             query_vector, limit=limit, threshold=threshold, filter_metadata=filter_metadata))
 
+    # ---- multi-vector search (extension: late interaction over the documents DISTINCT_KEY names) ----
+    def search_multivector(self, query_vectors: List[List[float]], limit: int = 10, threshold: float = 0.0,
+                           filter_metadata: Optional[Dict[str, Any]] = None) -> List[Result]:
+        """Late interaction (MaxSim): the query is SEVERAL vectors, a document is every vector that shares a value of the
+        metadata field named by config ``DISTINCT_KEY`` (a vector without the field is a document of its own), and a
+        document's score is the sum over the query's vectors of that vector's best score among the document's vectors.
+        Returns the best ``limit`` documents as ``(vector_id, score, metadata)`` of each document's representative (its
+        first stored vector).  ``filter_metadata`` always travels as the row mask: only matching vectors stand for their
+        document.  ``threshold`` as in ``search``, on the summed score.  One shard only: vectors are placed by the hash of
+        their id, so a document's vectors lie in several shards, and per-vector maxima do not compose from per-shard
+        rankings."""
+        if self.config.get("DISTINCT_KEY") is None:
+            raise ValueError("search_multivector needs config DISTINCT_KEY: the metadata field whose values name the documents")
+        if len(self.indices) != 1:
+            raise ValueError(
+                f"search_multivector needs a store of one shard, this one has {len(self.indices)}: vectors are placed by the hash "
+                "of their id, so a document's vectors lie in several shards, and a document's per-vector maxima (and their sum) "
+                "do not compose from per-shard rankings")
+        queries = [_as_query(v) for v in query_vectors]
+        if not queries:
+            raise ValueError("query_vectors is empty")
+        for q in queries:
+            if q.shape != (self.vector_dim,):
+                raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {q.shape}")
+        mask = self._row_masks(filter_metadata)[0] if filter_metadata else None
+        out = []
+        for vid, score, _ in self.indices[0].search_multivector(queries, limit, mask=mask):
+            if threshold > 0 and score < threshold:
+                break
+            out.append((vid, score, self.metadata.get(vid, {})))
+        return out[:limit]
+
+    async def search_multivector_async(self, query_vectors: List[List[float]], limit: int = 10, threshold: float = 0.0,
+                                       filter_metadata: Optional[Dict[str, Any]] = None) -> List[Result]:
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(self.thread_pool, lambda: self.search_multivector(
+            query_vectors, limit=limit, threshold=threshold, filter_metadata=filter_metadata))
+
     # ---- range search (extension: every vector within a similarity, no limit) ----
     def search_range(self, query_vector: List[float], threshold: float,
                      filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,

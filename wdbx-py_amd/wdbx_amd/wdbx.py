@@ -164,6 +164,23 @@ class WDBX:
         return await self.vector_store.search_distinct_async(query_vector, limit=limit, threshold=threshold,
                                                              filter_metadata=filter_metadata)
 
+    def vector_search_multivector(self, query_vectors: List[List[float]], limit: int = 10, threshold: float = 0.0,
+                                  filter_metadata: Optional[Dict[str, Any]] = None) -> List[Result]:
+        """Extension: late interaction (MaxSim).  The query is several vectors; the documents named by config ``DISTINCT_KEY``
+        are ranked by the sum over the query's vectors of each vector's best score among the document's vectors.  Exact; a
+        filter is pushed down; a store of one shard only (``VectorStore.search_multivector`` says why)."""
+        for v in query_vectors:
+            self._check_dim(v)
+        return self.vector_store.search_multivector(query_vectors, limit=limit, threshold=threshold,
+                                                    filter_metadata=filter_metadata)
+
+    async def vector_search_multivector_async(self, query_vectors: List[List[float]], limit: int = 10, threshold: float = 0.0,
+                                              filter_metadata: Optional[Dict[str, Any]] = None) -> List[Result]:
+        for v in query_vectors:
+            self._check_dim(v)
+        return await self.vector_store.search_multivector_async(query_vectors, limit=limit, threshold=threshold,
+                                                                filter_metadata=filter_metadata)
+
     def vector_search_range(self, query_vector: List[float], threshold: float,
                             filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,
                             max_results: Optional[int] = None) -> List[Result]:
