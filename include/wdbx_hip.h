@@ -313,6 +313,35 @@ int wdbx_index_range_search(wdbx_index* idx, const float* queries, int nq, const
                             int normalize_queries, const uint32_t* mask_words, uint64_t mask_word_count,
                             uint64_t capacity, uint64_t* out_offsets, int64_t* out_rows, float* out_scores);
 
+/* ---- batched range search: one int8 tile pass per block of queries ------------ */
+/* wdbx_index_range_search for a BATCH of queries (near-duplicate detection, threshold retrieval for a page of items, cluster
+ * assignment): the same arguments, the same contract, word for word -- CSR offsets always true, the capacity retry rule,
+ * count-only with capacity 0, result set, order, NaN handling, +-inf thresholds, refusals, the handle's mutex held to the end.
+ * For every query the rows, their order and the bits of every score equal what wdbx_index_range_search returns for that
+ * query alone.
+ *   Route (get_option "last_range_batch_path": 0 = nothing launched, an empty index; 1 = the per-query path only; 2 = tiles
+ *   only; 3 = tiles, with some blocks answered per query).  The tile route is taken when the int8 tiles would serve a batch
+ *   (gemm_bf16 = 3, gemm8_variant = 0, an i8 row image of at most 1536 bytes, the shadow copy fits; with a mask also
+ *   gemm_masked), the row count passes the batched path's own row test (gemm_min_rows / gemm_min_work, as for top-k) and nq is
+ *   at least option "range_batch_min_queries" (default 4).  Otherwise the call runs wdbx_index_range_search's rounds
+ *   unchanged, under the same lock.
+ *   Tile route: blocks of up to 256 consecutive queries (128 for L2 and rows beyond 384 bytes of i8, 64 beyond 768).  Per
+ *   block the queries are quantised, their selection thresholds and a bound widened by the exact pass's own rounding are
+ *   set, ONE full pass of the int8 tile kernel keeps every (query, row) pair whose rigorous upper bound reaches the query's
+ *   threshold (with a mask: the masked instances, the mask's rows removed before pairs are appended), the pairs are sorted by
+ *   query and the exact pass of wdbx_index_range_search scores and filters them.  The tile launches count as gemm launches in
+ *   wdbx_index_profile_read_gemm.  No sample, no second selection stage.
+ *   Two overflows, both exact: a query's candidates past their buffer grow it to the exact count and the gather runs again,
+ *   once (a count that changes between the two runs is WDBX_E_STATE); a wave of the tile pass that ran out of pair room sends
+ *   every query of ITS block through the per-query path ("last_range_batch_fallback_queries" counts them; a -inf cosine
+ *   threshold in a batch ends here by design).  Option "range_pair_cap": pairs per wave, 0 = the default sizing (16 384),
+ *   else 64 .. 65 536 (anything else is WDBX_E_INVALID).
+ *   get_option, read-only: "last_range_batch_blocks" the blocks of the last call, "last_range_batch_pairs" the pairs its tile
+ *   passes kept. */
+int wdbx_index_range_search_batch(wdbx_index* idx, const float* queries, int nq, const float* thresholds,
+                                  int normalize_queries, const uint32_t* mask_words, uint64_t mask_word_count,
+                                  uint64_t capacity, uint64_t* out_offsets, int64_t* out_rows, float* out_scores);
+
 /* ---- device-resident path (inputs already in HBM; asynchronous) -------------- */
 int wdbx_device_alloc(wdbx_index* idx, uint64_t bytes, void** out_dev_ptr);
 int wdbx_device_free(wdbx_index* idx, void* dev_ptr);

@@ -168,6 +168,13 @@ struct wdbx_index {
   size_t rcand_bytes = 0, rkeys_bytes = 0, rcnt_bytes = 0, rthr_bytes = 0;
   uint32_t range_cand_cap = 16384, range_out_cap = 16384;
   int last_range_path = 0;     // 0 fp32 range scan, 2 u8 selection scan + exact filter (what the last range search ran on)
+  // batched range search (wdbx_index_range_search_batch): its candidates live in d_cand, its pairs in d_pairs, its result keys,
+  // counters and thresholds in the buffers above ([0, 256) each); what the last call did (host_range_batch.h)
+  // candidates per query of a block: grows to the exact count after an overflow and stays there up to RANGE_BATCH_KEEP_CAP
+  // (host_range_batch.h); a call that grew past that releases d_cand / d_rkeys at its end and falls back to it
+  uint32_t range_batch_cap = 1024;
+  int last_range_batch_path = 0;
+  int64_t last_range_batch_blocks = 0, last_range_batch_pairs = 0, last_range_batch_fallback = 0;
   // search among listed rows (wdbx_index_search_rows): the device copy of the call's row list and, on the key routes, one key
   // per listed row and query of a round; the partial lists of the list route live in d_partials
   uint32_t* d_sub_ids = nullptr;
@@ -211,7 +218,7 @@ struct wdbx_index {
           opt_gemm_ct = 0, opt_wg_merge = 1, opt_zero_copy = 1, opt_lone_host_select = 1, opt_lds_lists = 0,
           opt_merge_fast = 1, opt_poll_done = 1, opt_scan_one_grid = 1, opt_select_min_k = 200, opt_gemm_min_nq = 4, opt_gemm_min_rows = 65536, opt_gemm_min_work = 800000,
           opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0, opt_scan_u42 = -1, opt_gemm_masked = 1, opt_rows_keys_max = 8192, opt_distinct_overfetch = 4,
-          opt_multivector_round_vectors = 256;
+          opt_multivector_round_vectors = 256, opt_range_batch_min_queries = 4, opt_range_pair_cap = 0;
 };
 
 struct DeviceGuard {
@@ -1897,6 +1904,22 @@ static int launch_gemm8(wdbx_index* ix, const Gemm8Args& g, int ct, bool masked 
   return record(ix->gemm_ev, ix->profile, ix->stream, false);
 }
 
+// the ordinary-group bounds of the int8 tiles' prefilter epilogue (two passes over the group table, ~10 us), rebuilt after the
+// shadow copy changed; shared by the top-k batches and the batched range search
+static int ensure_group_ref(wdbx_index* ix) {
+  if (ix->gref_valid) return WDBX_OK;
+  if (!ix->d_gref8) HIP_TRY(hipMalloc((void**)&ix->d_gref8, 8 * sizeof(float)));
+  HIP_TRY(hipMemsetAsync(ix->d_gref8, 0, 8 * sizeof(float), ix->stream));
+  const u64 ngroups = (ix->n + 63) / 64;
+  const uint32_t blocks = group_ref_grid(ngroups);
+  for (int pass = 0; pass < 2; ++pass)
+    hipLaunchKernelGGL(group_ref_kernel, dim3(blocks), dim3(256), 0, ix->stream, (const f4*)ix->d_groups8, ngroups, ix->d_gref8,
+                       (uint32_t*)(ix->d_gref8 + 4), pass);
+  HIP_TRY(hipGetLastError());
+  ix->gref_valid = true;
+  return WDBX_OK;
+}
+
 // nq (any number) queries in blocks of up to 256 through the int8 tiles.  Same contract as enqueue_search_gemm: per-query
 // candidate counters in d_count[q] (a count above the capacity = that query must be re-run on the scan path), results are
 // the exact fp32 ranking of the kept rows (rescore_kernel + merge_kernel).
@@ -2015,17 +2038,7 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
   }
   const bool l2 = ix->metric == WDBX_METRIC_L2;
   if (l2 && (rc = ensure_row_norms(ix))) return rc;
-  if (!ix->gref_valid) {  // the ordinary-group bounds of the prefilter epilogue (two passes over the group table, ~10 us)
-    if (!ix->d_gref8) HIP_TRY(hipMalloc((void**)&ix->d_gref8, 8 * sizeof(float)));
-    HIP_TRY(hipMemsetAsync(ix->d_gref8, 0, 8 * sizeof(float), ix->stream));
-    const u64 ngroups = (ix->n + 63) / 64;
-    const uint32_t blocks = group_ref_grid(ngroups);
-    for (int pass = 0; pass < 2; ++pass)
-      hipLaunchKernelGGL(group_ref_kernel, dim3(blocks), dim3(256), 0, ix->stream, (const f4*)ix->d_groups8, ngroups, ix->d_gref8,
-                         (uint32_t*)(ix->d_gref8 + 4), pass);
-    HIP_TRY(hipGetLastError());
-    ix->gref_valid = true;
-  }
+  if ((rc = ensure_group_ref(ix))) return rc;
   const int max_ct = l2 ? std::min(2, i8g_max_ct(ix)) : i8g_max_ct(ix);  // (L2: query blocks of at most 128)
   // the class runs of a block with a mask per query: {first slot in the block, slots, class row} -- what reads ONE mask per
   // launch (the second selection stage, the repair scan) is launched per run

@@ -28,6 +28,9 @@
 //                           bits, the low two bits only of the rows the four-bit bound cannot rule out; its quantiser
 //   kernels_range.h         range search: range_scan_kernel (fp32, every row scored exactly), range_filter_kernel (exact
 //                           scores of the u8 selection's candidates); wave-aggregated appends, no k
+//   kernels_range_batch.h   range_batch_bound_kernel: the selection thresholds and the widened bound of a block of range queries in
+//                           front of the int8 tiles' full pass (wdbx_index_range_search_batch)
+//   host_range_batch.h      that call's route, its blocks of up to 256 queries, buffer sizes and per-query fallback bookkeeping
 //   kernels_subset.h        subset_kernel: exact scores of LISTED rows (wdbx_index_search_rows), a block of queries per fetched
 //                           row, per-workgroup top-k lists or a key per listed row
 //   kernels_rowlists.h      rowlists_kernel: the same scores for a call with one row list PER QUERY (wdbx_index_search_row_lists),
@@ -80,6 +83,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 // with plain g++ under -fsanitize=thread / address,undefined (tests/test_host_dispatch_sanitizers.py)
 #include "host_dispatch.h"
 #include "host_range.h"  // (device-free as well: CSR offsets, per-query sort and decoding of a range search's keys)
+#include "host_range_batch.h"  // (device-free as well: route, blocks, buffer sizes and fallback bookkeeping of a batched range search)
 #include "host_calls.h"  // (device-free as well: mask popcount, padded query copies, host ranking of keys, class-by-class loop)
 #include "host_subset.h"  // (device-free as well: row-list validation, route and grid sizing of a search among listed rows)
 #include "host_multimask.h"  // (device-free as well: where the queries of a call with a mask per query sit in the tile blocks)
@@ -116,6 +120,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "kernels_tiles8.h"
 #include "kernels_aux.h"
 #include "kernels_range.h"
+#include "kernels_range_batch.h"
 #include "kernels_subset.h"
 #include "kernels_rowlists.h"
 #include "kernels_labels.h"
@@ -1341,17 +1346,21 @@ int wdbx_index_search_multivector(wdbx_index* ix, const float* vectors, const ui
 // buffer to the exact count and the overflowed stage runs again -- once: the same inputs give the same count (a candidate
 // overflow reruns the filter too, whose input was cut).  Then the keys go to the caller's row array at their CSR offsets and
 // range_sort_decode (host_range.h) sorts and decodes them there.
-static int range_search_host(wdbx_index* ix, const float* queries, int nq, const float* thresholds, int normalize_queries,
-                             const uint32_t* mask_words, uint64_t mask_word_count, uint64_t capacity, uint64_t* out_offsets,
-                             int64_t* out_rows, float* out_scores) {
+// (the argument checks and the body under the lock are functions of their own: wdbx_index_range_search_batch makes the same
+// checks and runs the same rounds for the queries its tile blocks do not answer, under the lock IT took)
+static int range_check_args(wdbx_index* ix, const float* queries, int nq, const float* thresholds, uint64_t capacity,
+                            uint64_t* out_offsets, int64_t* out_rows, float* out_scores) {
   if (!ix) return fail(WDBX_E_INVALID, "null handle");
   if (nq < 1) return fail(WDBX_E_INVALID, "nq=%d", nq);
   if (!queries || !thresholds || !out_offsets) return fail(WDBX_E_INVALID, "null buffer");
   if (capacity && (!out_rows || !out_scores)) return fail(WDBX_E_INVALID, "capacity %llu without result buffers", (u64)capacity);
   for (int q = 0; q < nq; ++q)
     if (thresholds[q] != thresholds[q]) return fail(WDBX_E_INVALID, "threshold of query %d is NaN", q);
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DeviceGuard g(ix->device);
+  return WDBX_OK;
+}
+static int range_search_locked(wdbx_index* ix, const float* queries, int nq, const float* thresholds, int normalize_queries,
+                               const uint32_t* mask_words, uint64_t mask_word_count, uint64_t capacity, uint64_t* out_offsets,
+                               int64_t* out_rows, float* out_scores) {
   MaskScope scope(ix);
   int rc;
   out_offsets[0] = 0;
@@ -1487,11 +1496,275 @@ static int range_search_host(wdbx_index* ix, const float* queries, int nq, const
   return WDBX_OK;
 }
 
+static int range_search_host(wdbx_index* ix, const float* queries, int nq, const float* thresholds, int normalize_queries,
+                             const uint32_t* mask_words, uint64_t mask_word_count, uint64_t capacity, uint64_t* out_offsets,
+                             int64_t* out_rows, float* out_scores) {
+  const int rc = range_check_args(ix, queries, nq, thresholds, capacity, out_offsets, out_rows, out_scores);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(ix->mu);
+  DeviceGuard g(ix->device);
+  return range_search_locked(ix, queries, nq, thresholds, normalize_queries, mask_words, mask_word_count, capacity, out_offsets,
+                             out_rows, out_scores);
+}
+
 int wdbx_index_range_search(wdbx_index* ix, const float* queries, int nq, const float* thresholds, int normalize_queries,
                             const uint32_t* mask_words, uint64_t mask_word_count, uint64_t capacity, uint64_t* out_offsets,
                             int64_t* out_rows, float* out_scores) try {
   return range_search_host(ix, queries, nq, thresholds, normalize_queries, mask_words, mask_word_count, capacity, out_offsets,
                            out_rows, out_scores);
+} WDBX_CATCH
+
+// ---- batched range search (host_range_batch.h, kernels_range_batch.h) ------------------------
+// One full pass of the int8 tiles per block of up to 256 queries instead of one u8 scan per query.  Per block, all on the
+// handle's stream: queries_to_i8_kernel -> range_batch_bound_kernel (tau per query, the bound widened by the exact pass's own
+// rounding, result counters zeroed) -> gemm_i8_kernel<PHASE 1> -> scatter_pairs_kernel -> range_filter_kernel; one
+// synchronisation reads the candidate counters, the lost flag and the result counters.  A candidate counter past its buffer
+// grows the buffers to the exact count and runs scatter + filter again, once.  A wave that ran out of pair room (nobody knows
+// which query lost pairs) sends the block's queries through range_search_locked: the per-query rounds, under this call's lock.
+// The whole call holds the handle's mutex.
+// staged_q0: the caller's query that sits first in d_q (the queries are staged again, from the next block on, after a block
+// that went through the per-query rounds)
+static int range_batch_block(wdbx_index* ix, const RangeBatchBlock& b, int staged_q0, const float* queries, const float* thresholds,
+                             const u64* gbad, uint32_t pair_cap, uint32_t nwaves, std::vector<uint32_t>& hcand, std::vector<uint32_t>& hres,
+                             bool* lost) {
+  int rc;
+  const bool l2 = ix->metric == WDBX_METRIC_L2, masked = ix->active_mask != nullptr;
+  const int gbn = 64 * b.ct, nv = b.nv;
+  const uint32_t pitch8 = ix->pitch8g, pitch4 = (uint32_t)ix->pitch / 4;
+  const uint32_t tiles = (uint32_t)((ix->n + G8_ROWS - 1) / G8_ROWS);
+  const float* qsrc = ix->d_q + (size_t)(b.q0 - staged_q0) * ix->pitch;
+  constexpr int MB = RANGE_BATCH_MAX_BLOCK;
+  const RangeBatchSizes sz = range_batch_sizes(b, ix->range_batch_cap, pair_cap, nwaves, pitch8);
+  if ((rc = grow((void**)&ix->d_qb8, &ix->qb8_bytes, sz.qb8_bytes))) return rc;
+  if ((rc = grow((void**)&ix->d_qpar, &ix->qpar_bytes, sz.qpar_bytes))) return rc;
+  if ((rc = grow((void**)&ix->d_tau, &ix->tau_bytes, sz.tau_bytes))) return rc;
+  if ((rc = grow((void**)&ix->d_count, &ix->count_bytes, sz.count_bytes))) return rc;
+  if ((rc = grow((void**)&ix->d_pairs, &ix->pairs_bytes, sz.pairs_bytes))) return rc;
+  if ((rc = grow((void**)&ix->d_pair_count, &ix->pair_count_bytes, sz.pair_count_bytes))) return rc;
+  if ((rc = grow((void**)&ix->d_rcnt, &ix->rcnt_bytes, sz.rcnt_bytes))) return rc;
+  if ((rc = grow((void**)&ix->d_rthr, &ix->rthr_bytes, sz.thr_bytes))) return rc;
+  uint32_t* const d_lost = ix->d_count + MB;
+  // the exact thresholds [0, 256) and the selection thresholds [256, 512)
+  std::vector<float> hthr(2 * MB, INFINITY);
+  for (int i = 0; i < nv; ++i) {
+    const float t = thresholds[b.q0 + i];
+    hthr[i] = t;
+    if (l2) {
+      const float* qv = queries + (size_t)(b.q0 + i) * ix->dim;
+      double qq = 0.0;
+      for (int c = 0; c < ix->dim; ++c) qq += (double)qv[c] * qv[c];
+      hthr[MB + i] = range_selection_tau_l2(qq, t);
+    } else {
+      hthr[MB + i] = t;  // (the rounding of the exact pass widens the bound: range_batch_bound_kernel)
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(ix->d_rthr, hthr.data(), 2 * MB * sizeof(float), hipMemcpyHostToDevice, ix->stream));
+  hipLaunchKernelGGL(queries_to_i8_kernel, dim3(queries_to_i8_grid((uint32_t)gbn)), dim3(256), 0, ix->stream, qsrc, (uint32_t)ix->dim,
+                     (uint32_t)ix->pitch, (uint32_t)nv, ix->d_qb8, pitch8, (uint32_t)gbn, ix->d_qpar, ix->d_tau, ix->d_count, d_lost);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(range_batch_bound_kernel, dim3(range_batch_bound_grid((uint32_t)gbn)), dim3(256), 0, ix->stream, (uint32_t)nv,
+                     (uint32_t)gbn, ix->d_qpar, (const float*)(ix->d_rthr + MB), ix->d_tau, ix->d_rcnt);
+  HIP_TRY(hipGetLastError());
+  Gemm8Args g = {};
+  g.rows8 = ix->d_rows8g;
+  g.groups = ix->d_groups8;
+  g.cn = ix->d_cn;
+  g.gbad = gbad;
+  g.gref = ix->d_gref8;
+  g.qb8 = ix->d_qb8;
+  g.qpar = ix->d_qpar;
+  g.n_rows = (uint32_t)ix->n;
+  g.pitch8 = pitch8;
+  g.num_tiles = tiles;
+  g.tile_stride = 1;
+  g.tau = ix->d_tau;
+  g.pairs = ix->d_pairs;
+  g.pair_count = ix->d_pair_count;
+  g.pair_cap = pair_cap;
+  if ((rc = launch_gemm8<1>(ix, g, b.ct, masked, false))) return rc;
+  const range_fn ffilter = l2 ? range_filter_kernel<WDBX_METRIC_L2> : range_filter_kernel<WDBX_METRIC_COSINE>;
+  // pairs -> per-query candidates -> result keys; the counters are zero on entry (the block's first two kernels, or the memsets
+  // of the second run)
+  auto enqueue_gather = [&]() -> int {
+    const uint32_t cap = ix->range_batch_cap;
+    const RangeBatchSizes s2 = range_batch_sizes(b, cap, pair_cap, nwaves, pitch8);
+    int rc2;
+    if ((rc2 = grow((void**)&ix->d_cand, &ix->cand_bytes, s2.cand_bytes))) return rc2;
+    if ((rc2 = grow((void**)&ix->d_rkeys, &ix->rkeys_bytes, s2.keys_bytes))) return rc2;
+    hipLaunchKernelGGL(scatter_pairs_kernel, dim3((nwaves + SCATTER_LISTS - 1) / SCATTER_LISTS), dim3(1024), 0, ix->stream,
+                       (const u64*)ix->d_pairs, (const uint32_t*)ix->d_pair_count, nwaves, pair_cap, ix->d_cand, ix->d_count, cap, d_lost);
+    HIP_TRY(hipGetLastError());
+    RangeArgs r = {};
+    r.rows = (const f4*)ix->d_rows;
+    r.queries = (const f4*)qsrc;
+    r.thr = ix->d_rthr;
+    r.n_rows = (uint32_t)ix->n;
+    r.pitch4 = pitch4;
+    r.out = ix->d_rkeys;
+    r.count = ix->d_rcnt;
+    r.cap = cap;  // (results <= candidates: never past the buffer)
+    r.cand = ix->d_cand;
+    r.cand_count = ix->d_count;
+    r.cand_cap = cap;
+    if ((rc2 = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc2;
+    // (up to 256 queries share the device: about 32 workgroups per CU over all of them, at least 8 per query)
+    const uint32_t fgrid = std::min<uint32_t>((uint32_t)ix->cu_count * 8, std::max<uint32_t>(8, (uint32_t)ix->cu_count * 32 / (uint32_t)nv));
+    hipLaunchKernelGGL(ffilter, dim3(fgrid, nv), dim3(256), 0, ix->stream, r);
+    HIP_TRY(hipGetLastError());
+    if ((rc2 = record(ix->merge_ev, ix->profile, ix->stream, false, (uint32_t)nv))) return rc2;
+    HIP_TRY(hipMemcpyAsync(hcand.data(), ix->d_count, (MB + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipMemcpyAsync(hres.data(), ix->d_rcnt, MB * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    return WDBX_OK;
+  };
+  if ((rc = enqueue_gather())) return rc;
+  *lost = hcand[MB] != 0;
+  if (*lost) return WDBX_OK;
+  uint32_t most = 0;
+  for (int i = 0; i < nv; ++i) most = std::max(most, hcand[i]);
+  if (most > ix->range_batch_cap) {  // candidates past their buffers: grow to the exact count, scatter + filter again
+    if (!range_batch_cap_fits(b, most)) {
+      *lost = true;  // (buffers this large for 256 queries at once: the per-query rounds instead)
+      return WDBX_OK;
+    }
+    ix->range_batch_cap = most;
+    const std::vector<uint32_t> first(hcand.begin(), hcand.begin() + nv);
+    HIP_TRY(hipMemsetAsync(ix->d_count, 0, (size_t)gbn * sizeof(uint32_t), ix->stream));
+    HIP_TRY(hipMemsetAsync(ix->d_rcnt, 0, (size_t)gbn * sizeof(uint32_t), ix->stream));
+    if ((rc = enqueue_gather())) return rc;
+    // (the same pairs scattered again: every query's count must be what the first run counted)
+    if (hcand[MB] || !std::equal(first.begin(), first.end(), hcand.begin()))
+      return fail(WDBX_E_STATE, "batched range search: candidate count changed between two passes");
+  }
+  return WDBX_OK;
+}
+
+int wdbx_index_range_search_batch(wdbx_index* ix, const float* queries, int nq, const float* thresholds, int normalize_queries,
+                                  const uint32_t* mask_words, uint64_t mask_word_count, uint64_t capacity, uint64_t* out_offsets,
+                                  int64_t* out_rows, float* out_scores) try {
+  int rc = range_check_args(ix, queries, nq, thresholds, capacity, out_offsets, out_rows, out_scores);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(ix->mu);
+  DeviceGuard g(ix->device);
+  ix->last_range_batch_path = RANGE_BATCH_NONE;
+  ix->last_range_batch_blocks = ix->last_range_batch_pairs = ix->last_range_batch_fallback = 0;
+  out_offsets[0] = 0;
+  if (ix->n == 0) {
+    for (int q = 0; q < nq; ++q) out_offsets[q + 1] = 0;
+    return WDBX_OK;
+  }
+  if (mask_words && (rc = check_mask_words(ix->n, mask_word_count))) return rc;
+  const bool l2 = ix->metric == WDBX_METRIC_L2;
+  RangeBatchShape shape = {};
+  shape.n_rows = ix->n;
+  shape.nq = nq;
+  shape.metric_l2 = l2 ? 1 : 0;
+  shape.i8_pitch = i8_tiles_shape_ok(ix) ? i8g_pitch(ix) : 0u;
+  shape.shadow_fits = 1;
+  shape.gemm_bf16 = ix->opt_gemm_bf16;
+  shape.gemm8_variant = ix->opt_gemm8_variant;
+  shape.gemm_masked = ix->opt_gemm_masked;
+  shape.gemm_min_rows = ix->opt_gemm_min_rows;
+  shape.gemm_min_work = ix->opt_gemm_min_work;
+  shape.min_queries = ix->opt_range_batch_min_queries;
+  shape.has_mask = mask_words ? 1 : 0;
+  // (the shadow copy is built only when everything else says tiles: a per-query call must not allocate it)
+  const bool tiles = range_batch_use_tiles(shape) && prepare_i8g_shadow(ix);
+  if (!tiles) {
+    ix->last_range_batch_path = RANGE_BATCH_PER_QUERY;
+    ix->last_range_batch_fallback = nq;
+    return range_search_locked(ix, queries, nq, thresholds, normalize_queries, mask_words, mask_word_count, capacity, out_offsets,
+                               out_rows, out_scores);
+  }
+  if (l2 && (rc = ensure_row_norms(ix))) return rc;
+  if ((rc = ensure_group_ref(ix))) return rc;
+  const std::vector<RangeBatchBlock> blocks =
+      range_batch_blocks(nq, range_batch_block_queries(shape.metric_l2, shape.i8_pitch), (int)ix->opt_gemm_ct);
+  const uint32_t pair_cap = range_batch_pair_cap(ix->opt_range_pair_cap);
+  const uint32_t nwaves = range_batch_waves(ix->n, (uint32_t)ix->cu_count);
+  RangeBatchTally tally;
+  tally.start(nq);
+  std::vector<uint32_t> hcand(RANGE_BATCH_MAX_BLOCK + 1), hres(RANGE_BATCH_MAX_BLOCK);
+  std::vector<uint64_t> cnt(RANGE_BATCH_MAX_BLOCK), sub_offsets(RANGE_BATCH_MAX_BLOCK + 1);
+  MaskScope scope(ix);
+  // The call's queries sit in d_q from query staged_q0 on, its mask in d_mask and its bad-row table in d_call_bad.  A block
+  // answered by the per-query rounds overwrites d_q with its own queries and clears active_mask (the mask's words and the
+  // table stay what they are): only the queries BEHIND that block are staged again, and the mask is re-armed.
+  if (mask_words && (rc = scope.set(mask_words))) return rc;
+  if ((rc = upload_queries(ix, queries, (uint64_t)nq, normalize_queries))) return rc;
+  int staged_q0 = 0;
+  bool staged = true;
+  const u64* gbad = ix->d_gbad8;
+  if (mask_words) {  // this call's bad-row table: removed rows, rows past the end, rows the mask leaves out
+    const u64 ngroups = ix->groups8_bytes / sizeof(f4);
+    if ((rc = grow((void**)&ix->d_call_bad, &ix->call_bad_bytes, (size_t)ngroups * sizeof(u64)))) return rc;
+    hipLaunchKernelGGL(gbad_with_mask_kernel, dim3(gbad_with_mask_grid(ngroups), 1), dim3(256), 0, ix->stream, (const u64*)ix->d_gbad8,
+                       (const uint32_t*)ix->active_mask, (u64)((ix->n + 31) / 32), ngroups, ix->d_call_bad, (u64)0, (const int32_t*)nullptr);
+    HIP_TRY(hipGetLastError());
+    gbad = ix->d_call_bad;
+  }
+  for (const RangeBatchBlock& b : blocks) {
+    if (!staged) {
+      if ((rc = upload_queries(ix, queries + (size_t)b.q0 * ix->dim, (uint64_t)(nq - b.q0), normalize_queries))) return rc;
+      staged_q0 = b.q0;
+      if (mask_words) {
+        ix->active_mask = ix->d_mask;
+        scope.armed = true;
+      }
+      staged = true;
+    }
+    bool lost = false;
+    if ((rc = range_batch_block(ix, b, staged_q0, queries, thresholds, gbad, pair_cap, nwaves, hcand, hres, &lost))) return rc;
+    uint64_t kept = 0;
+    for (int i = 0; i < b.nv; ++i) kept += hcand[i];
+    const uint64_t base = out_offsets[b.q0];
+    if (lost) {  // every query of the block through the per-query rounds; its results land sorted and decoded
+      tally.lost(b, kept);
+      const uint64_t room = capacity > base ? capacity - base : 0;
+      if ((rc = range_search_locked(ix, queries + (size_t)b.q0 * ix->dim, b.nv, thresholds + b.q0, normalize_queries, mask_words,
+                                    mask_word_count, room, sub_offsets.data(), room ? out_rows + base : nullptr,
+                                    room ? out_scores + base : nullptr)))
+        return rc;
+      for (int i = 0; i < b.nv; ++i) out_offsets[b.q0 + i + 1] = base + sub_offsets[i + 1];
+      staged = false;
+      continue;
+    }
+    tally.tiles(b, kept);
+    for (int i = 0; i < b.nv; ++i) cnt[i] = hres[i];
+    const uint64_t total = range_csr_offsets(cnt.data(), b.nv, out_offsets + b.q0);
+    if (total <= capacity) {  // the keys, straight into the caller's row array at their offsets (u64 slots)
+      for (int i = 0; i < b.nv; ++i)
+        if (cnt[i])
+          HIP_TRY(hipMemcpyAsync(out_rows + out_offsets[b.q0 + i], ix->d_rkeys + (size_t)i * ix->range_batch_cap, cnt[i] * sizeof(u64),
+                                 hipMemcpyDeviceToHost, ix->stream));
+      HIP_TRY(hipStreamSynchronize(ix->stream));
+    }
+  }
+  if (out_offsets[nq] <= capacity) {  // sort and decode the tile blocks' keys (a per-query block's are done)
+    for (const RangeBatchBlock& b : blocks) {
+      if (tally.per_query[(size_t)b.q0]) continue;
+      const uint64_t base = out_offsets[b.q0];
+      for (int i = 0; i <= b.nv; ++i) sub_offsets[i] = out_offsets[b.q0 + i] - base;
+      if (sub_offsets[b.nv]) range_sort_decode(l2 ? 1 : 0, b.nv, sub_offsets.data(), out_rows + base, out_scores + base);
+    }
+  }
+  // One query with very many hits must not pin gigabytes for the handle's life, nor size every later block's 256 buffers by
+  // it: beyond RANGE_BATCH_KEEP_CAP candidates per query the grown buffers are released and the next call starts from that
+  // capacity again (and regrows, once, if it meets such a query).
+  if (ix->range_batch_cap > RANGE_BATCH_KEEP_CAP) {
+    ix->range_batch_cap = RANGE_BATCH_KEEP_CAP;
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    if (ix->d_cand) HIP_TRY(hipFree(ix->d_cand));
+    if (ix->d_rkeys) HIP_TRY(hipFree(ix->d_rkeys));
+    ix->d_cand = nullptr;
+    ix->d_rkeys = nullptr;
+    ix->cand_bytes = ix->rkeys_bytes = 0;
+  }
+  ix->last_range_batch_path = tally.path();
+  ix->last_range_batch_blocks = tally.blocks;
+  ix->last_range_batch_pairs = tally.pairs;
+  ix->last_range_batch_fallback = tally.fallback_queries;
+  return WDBX_OK;
 } WDBX_CATCH
 
 int wdbx_device_alloc(wdbx_index* ix, uint64_t bytes, void** out_dev_ptr) try {
@@ -2169,6 +2442,8 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"rows_keys_max", &wdbx_index::opt_rows_keys_max},
     {"distinct_overfetch", &wdbx_index::opt_distinct_overfetch},
     {"multivector_round_vectors", &wdbx_index::opt_multivector_round_vectors},
+    {"range_batch_min_queries", &wdbx_index::opt_range_batch_min_queries},
+    {"range_pair_cap", &wdbx_index::opt_range_pair_cap},
 };
 
 static int64_t* option_slot(wdbx_index* ix, const char* name) { return find_option(ix, kOptions, name); }
@@ -2182,6 +2457,9 @@ int wdbx_index_set_option(wdbx_index* ix, const char* name, int64_t value) try {
     return fail(WDBX_E_INVALID, "gemm8_variant %lld: 0 (= 14), 12 and 13 are the forms the library has", (long long)value);
   if (slot == &ix->opt_multivector_round_vectors && (value < 1 || value > MULTIVECTOR_MAX_ROUND))
     return fail(WDBX_E_INVALID, "multivector_round_vectors %lld outside [1, %d]", (long long)value, MULTIVECTOR_MAX_ROUND);
+  if (slot == &ix->opt_range_pair_cap && value != 0 && (value < (int64_t)RANGE_PAIR_CAP_MIN || value > (int64_t)RANGE_PAIR_CAP_MAX))
+    return fail(WDBX_E_INVALID, "range_pair_cap %lld: 0 (the default sizing) or [%u, %u] pairs per wave", (long long)value,
+                RANGE_PAIR_CAP_MIN, RANGE_PAIR_CAP_MAX);
   *slot = value;
   if (!strcmp(name, "group_bounds")) ix->gmax_valid = false;  // re-decide (and rebuild the group maxima) at the next batch
   return WDBX_OK;
@@ -2228,6 +2506,10 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "shadow6_rows")) return *value = (int64_t)ix->shadow6_rows, WDBX_OK;
   if (name && !strcmp(name, "shadow6_bytes")) return *value = (int64_t)ix->rows6_bytes, WDBX_OK;
   if (name && !strcmp(name, "last_range_path")) return *value = ix->last_range_path, WDBX_OK;
+  if (name && !strcmp(name, "last_range_batch_path")) return *value = ix->last_range_batch_path, WDBX_OK;
+  if (name && !strcmp(name, "last_range_batch_blocks")) return *value = ix->last_range_batch_blocks, WDBX_OK;
+  if (name && !strcmp(name, "last_range_batch_pairs")) return *value = ix->last_range_batch_pairs, WDBX_OK;
+  if (name && !strcmp(name, "last_range_batch_fallback_queries")) return *value = ix->last_range_batch_fallback, WDBX_OK;
   if (name && !strcmp(name, "last_rows_path")) return *value = ix->last_rows_path, WDBX_OK;
   if (name && !strcmp(name, "last_lists_path")) return *value = ix->last_lists_path, WDBX_OK;
   if (name && !strcmp(name, "last_lists_items")) return *value = ix->last_lists_items, WDBX_OK;

@@ -76,6 +76,8 @@ SIGNATURES = {
                                                 C.c_uint64, _i64p, _f32p, C.POINTER(C.c_uint32)]),
     "wdbx_index_range_search": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
                                           C.c_uint64, _u64p, _i64p, _f32p]),
+    "wdbx_index_range_search_batch": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
+                                                C.c_uint64, _u64p, _i64p, _f32p]),
     "wdbx_device_alloc": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "wdbx_device_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "wdbx_device_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
@@ -449,6 +451,16 @@ class NativeIndex:
         ``[offsets[i], offsets[i + 1])``.  A first call guesses the capacity (the previous answer's size, at least 4096 per
         query); if the answer is larger, one more call with the exact total (a third only if rows were added in between;
         after three the call raises)."""
+        return self._range_call(self._lib.wdbx_index_range_search, queries, thresholds, normalize_queries, mask_words)
+
+    def range_search_batch(self, queries, thresholds, normalize_queries: bool = False,
+                           mask_words: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """:meth:`range_search` for a batch: the same arguments and the same answer, bit for bit, through
+        ``wdbx_index_range_search_batch`` -- one int8 tile pass per block of up to 256 queries where the library's route
+        allows it (``get_option("last_range_batch_path")``), the per-query path otherwise."""
+        return self._range_call(self._lib.wdbx_index_range_search_batch, queries, thresholds, normalize_queries, mask_words)
+
+    def _range_call(self, entry, queries, thresholds, normalize_queries, mask_words):
         q = _as_f32(queries, self.dim)
         nq = q.shape[0]
         t = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, dtype=np.float32), (nq,)))
@@ -463,7 +475,7 @@ class NativeIndex:
         for _ in range(3):
             rows = np.empty(capacity, np.int64)
             scores = np.empty(capacity, np.float32)
-            _check(self._lib.wdbx_index_range_search(
+            _check(entry(
                 self._h, q.ctypes.data_as(_f32p), nq, t.ctypes.data_as(_f32p), int(normalize_queries),
                 m.ctypes.data_as(C.POINTER(C.c_uint32)) if m is not None else None, m.size if m is not None else 0,
                 capacity, offsets.ctypes.data_as(_u64p), rows.ctypes.data_as(_i64p), scores.ctypes.data_as(_f32p)))

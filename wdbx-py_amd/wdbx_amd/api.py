@@ -11,6 +11,7 @@ same validation outcome (a malformed body is a 422 there; here a ``ValueError`` 
         return await search_endpoint(wdbx, body)
 
 ``range_search_endpoint`` answers "every vector within this similarity" (no limit; the extension the reference lacks).
+``range_search_batch_endpoint`` is its batch form: many range queries in one request, one call per shard.
 ``search_batch_endpoint`` is the batch form the reference lacks: many queries in one request, answered by
 one batched pass per shard (``vector_search_batch``).  Concurrent single requests need no batch route: they are
 coalesced at ``VectorStore.search_async`` (what the reference's server produces, api/server.py:143).
@@ -142,3 +143,42 @@ async def range_search_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]
     query = _vector(payload["query_vector"], "query_vector")
     return _render(await wdbx.vector_search_range_async(query, float(threshold), filter_metadata=flt,
                                                         max_results=max_results))
+
+
+async def range_search_batch_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
+    """Batched range form (extension): body ``{"query_vectors": [[...], ...], "threshold": 0.8 | "thresholds": [...],
+    "filter_metadata": null, "max_results": null}`` -> ``{"results": [<one range_search_endpoint result list per query>]}``
+    (``wdbx.vector_search_range_batch_async``).  ``threshold`` serves every query, ``thresholds`` holds one per query (any
+    other length is refused); exactly one of the two.  One filter for the batch; ``max_results`` cuts each query's list."""
+    if not isinstance(payload, dict):
+        raise ValueError("request body must be an object")
+    if "query_vectors" not in payload or not isinstance(payload["query_vectors"], (list, tuple)):
+        raise ValueError("query_vectors is required and must be a list of vectors")
+    queries = [_vector(v, f"query_vectors[{i}]") for i, v in enumerate(payload["query_vectors"])]
+
+    def number(x):
+        return not isinstance(x, bool) and isinstance(x, (int, float)) and x == x
+
+    if ("threshold" in payload) == ("thresholds" in payload):
+        raise ValueError("exactly one of threshold and thresholds is required")
+    if "threshold" in payload:
+        if not number(payload["threshold"]):
+            raise ValueError("threshold must be a number")
+        thresholds = [float(payload["threshold"])] * len(queries)
+    else:
+        thresholds = payload["thresholds"]
+        if not isinstance(thresholds, (list, tuple)) or not all(number(x) for x in thresholds):
+            raise ValueError("thresholds must be a list of numbers")
+        if len(thresholds) != len(queries):
+            raise ValueError(f"thresholds holds {len(thresholds)} values for {len(queries)} queries")
+        thresholds = [float(x) for x in thresholds]
+    flt = payload.get("filter_metadata")
+    if flt is not None and not isinstance(flt, dict):
+        raise ValueError("filter_metadata must be an object")
+    max_results = payload.get("max_results")
+    if max_results is not None and (isinstance(max_results, bool) or not isinstance(max_results, int) or max_results < 0):
+        raise ValueError("max_results must be a non-negative integer or null")
+    if not queries:
+        return {"results": []}
+    per_query = await wdbx.vector_search_range_batch_async(queries, thresholds, filter_metadata=flt, max_results=max_results)
+    return {"results": [_render(r)["results"] for r in per_query]}

@@ -635,6 +635,36 @@ class HipFlatIndex(VectorIndex):
                 return []
             raise
 
+    def range_search_batch(self, queries: np.ndarray, thresholds,
+                           row_mask: Optional[np.ndarray] = None) -> List[List[Tuple[str, float]]]:
+        """``range_search`` for many queries in one call (``wdbx_index_range_search_batch``: one int8 tile pass per block of
+        up to 256 queries where the library's route allows it).  ``thresholds``: a scalar or one per query, in the
+        convention of ``range_search``; ``row_mask``: one for the whole batch.  One list per query, each exactly what
+        ``range_search`` returns for that query alone."""
+        queries = np.asarray(queries, dtype=np.float32)
+        if queries.ndim != 2 or queries.shape[1] != self.vector_dim:
+            raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {queries.shape}")
+        nq = queries.shape[0]
+        t = np.broadcast_to(np.asarray(thresholds, dtype=np.float64), (nq,)) if nq else np.zeros(0)
+        if np.isnan(t).any():
+            raise ValueError("threshold is NaN")
+        try:
+            if self.next_index == 0 or nq == 0:
+                return [[] for _ in range(nq)]
+            q = np.stack([self._prepare(r) for r in queries])
+            words = None
+            if row_mask is not None:
+                words = row_mask if row_mask.dtype == np.uint32 else _native.pack_row_mask(row_mask)
+            # (L2: score = -distance >= threshold  <=>  distance <= -threshold, as range_search)
+            tt = (t if self.metric == _native.METRIC_COSINE else -t).astype(np.float32)
+            offsets, rows, scores = self._native.range_search_batch(q, tt, mask_words=words)
+            return [self._map(rows[offsets[i]:offsets[i + 1]], scores[offsets[i]:offsets[i + 1]]) for i in range(nq)]
+        except Exception as e:
+            logger.error("Error in HIP batched range search: %s", e)
+            if self.swallow_errors:
+                return [[] for _ in range(nq)]
+            raise
+
     def row_mask_for(self, predicate) -> np.ndarray:
         """uint32 mask words of the rows whose id satisfies ``predicate(id)``; unmapped (removed)
         rows are excluded."""

@@ -1201,6 +1201,45 @@ class VectorStore:
         return await loop.run_in_executor(self.thread_pool, lambda: self.search_range(
             query_vector, threshold, filter_metadata=filter_metadata, prefilter=prefilter, max_results=max_results))
 
+    def search_range_batch(self, query_vectors: List[List[float]], thresholds,
+                           filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,
+                           max_results: Optional[int] = None) -> List[List[Result]]:
+        """``search_range`` for a batch of queries: one result list per query, each exactly what ``search_range`` returns for
+        that query (near-duplicate detection, threshold retrieval for a page of items, cluster assignment).  ``thresholds``
+        is a scalar or one per query.  One call per shard for the whole batch (the library's batched range search: one int8
+        tile pass per block of up to 256 queries), then ``merge_range`` per query over the shards.  ONE filter for the
+        batch: the row mask of every shard's call when ``prefilter`` / FILTER_PUSHDOWN says so, else the post-filter of
+        ``search_range``; ``max_results`` cuts each query's list."""
+        queries = [_as_query(v) for v in query_vectors]
+        for q in queries:
+            if q.shape != (self.vector_dim,):
+                raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {q.shape}")
+        nq = len(queries)
+        t = np.asarray(thresholds, dtype=np.float64)
+        if t.ndim > 1 or (t.ndim == 1 and t.shape[0] != nq):
+            raise ValueError(f"thresholds: a scalar or one per query ({nq}), got shape {t.shape}")
+        if np.isnan(t).any():
+            raise ValueError("threshold is NaN")
+        if nq == 0:
+            return []
+        t = np.ascontiguousarray(np.broadcast_to(t, (nq,)))
+        batch = np.stack(queries)
+        masks = self._masks_for(filter_metadata, prefilter)
+        if len(self.indices) > 1:
+            per_shard = list(self._shard_pool.map(lambda a: a[0].range_search_batch(batch, t, row_mask=a[1]),
+                                                  zip(self.indices, masks)))
+        else:
+            per_shard = [ix.range_search_batch(batch, t, row_mask=m) for ix, m in zip(self.indices, masks)]
+        return [merge_range([shard[i] for shard in per_shard], self.metadata, filter_metadata, max_results)
+                for i in range(nq)]
+
+    async def search_range_batch_async(self, query_vectors: List[List[float]], thresholds,
+                                       filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,
+                                       max_results: Optional[int] = None) -> List[List[Result]]:
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(self.thread_pool, lambda: self.search_range_batch(
+            query_vectors, thresholds, filter_metadata=filter_metadata, prefilter=prefilter, max_results=max_results))
+
     # ---- row management ----
     def _known(self, vector_id: str) -> bool:
         return vector_id in self.vectors or self._is_bulk(vector_id)

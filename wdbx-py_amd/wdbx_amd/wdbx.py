@@ -198,6 +198,25 @@ class WDBX:
         return await self.vector_store.search_range_async(query_vector, threshold, filter_metadata=filter_metadata,
                                                           prefilter=prefilter, max_results=max_results)
 
+    def vector_search_range_batch(self, query_vectors: List[List[float]], thresholds,
+                                  filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,
+                                  max_results: Optional[int] = None) -> List[List[Result]]:
+        """Extension: ``vector_search_range`` for a batch of queries -- one list per query, each exactly what
+        ``vector_search_range`` returns for it; ``thresholds`` a scalar or one per query; one filter for the batch."""
+        for v in query_vectors:
+            self._check_dim(v)
+        return self.vector_store.search_range_batch(query_vectors, thresholds, filter_metadata=filter_metadata,
+                                                    prefilter=prefilter, max_results=max_results)
+
+    async def vector_search_range_batch_async(self, query_vectors: List[List[float]], thresholds,
+                                              filter_metadata: Optional[Dict[str, Any]] = None,
+                                              prefilter: Optional[bool] = None,
+                                              max_results: Optional[int] = None) -> List[List[Result]]:
+        for v in query_vectors:
+            self._check_dim(v)
+        return await self.vector_store.search_range_batch_async(query_vectors, thresholds, filter_metadata=filter_metadata,
+                                                                prefilter=prefilter, max_results=max_results)
+
     # ---- row management ----
     def delete_vector(self, vector_id: str) -> bool:
         return self.vector_store.delete(vector_id)
