@@ -1360,7 +1360,8 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
   // 6 -> 2008, 8 -> 1990 (profiles/u6/README.md): eight waves per CU with 6 KiB in flight each keep HBM busy, more of them
   // only spread the stream over more pages at once
   // The split planes' pass, same corpus: 1 -> 1879, 2 -> 2885, 3 -> 3028, 4 -> 2959, 6 -> 2885 (profiles/u42/README.md): a wave
-  // holds 6 KiB in flight as before but computes longer per byte, so a third workgroup still fills gaps
+  // holds 6 KiB in flight as before but computes longer per byte, so a third workgroup still fills gaps.  With the packed
+  // converts: 1 -> 1991, 2 -> 3005, 3 -> 3032 (mean of six), 4 -> 2935, 6 -> 2929 (profiles/u42_pipe/README.md)
   const uint32_t wgs = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(ix->opt_scan8_wgs > 0 ? ix->opt_scan8_wgs : u42 ? 3 : 2, 8));
   const uint32_t grid1 = scan_full_grid(tiles64, (uint32_t)ix->cu_count, wgs);
   const uint32_t grid0 = scan_sample_grid(ngroups, (uint32_t)ix->cu_count);

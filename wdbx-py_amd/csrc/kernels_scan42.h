@@ -7,8 +7,8 @@
 // (rows_to_u6_kernel's quantiser: u6_row_scale / u6_unit_codes) is stored as u = 4 h + l, h in 0 .. 15, l in 0 .. 3:
 //   h plane   tiles of 64 rows, unit-major, a unit = 32 codes = 16 bytes:  [tile][unit][row 0..63][4 dwords].  Lane = row; one
 //             16-byte load per lane and unit is 1 KiB contiguous per wave.  Dword t byte b holds h of element 8 t + b in its
-//             low nibble and of element 8 t + 4 + b in its high nibble: (d & 0x0F0F0F0F) and (d >> 4 & 0x0F0F0F0F) feed four
-//             byte converts each -- 3 logic ops + 8 converts + 4 v_pk_fma_f32 per dword of eight elements.
+//             low nibble and of element 8 t + 4 + b in its high nibble: (d & 0x0F0F0F0F) and (d >> 4 & 0x0F0F0F0F) feed two
+//             packed converts each (u42_cvt4) -- 3 logic ops + 4 converts + 4 v_pk_fma_f32 per dword of eight elements.
 //   {s, a4}   per row: the u6 scale and  a4 >= |c - s (4 h + 1.5 - 32)|_2,  the residual of the row against the MIDPOINT of
 //             what the low bits can add, rounded up with the allowances rows_to_u6_kernel derives for a (same arithmetic:
 //             rho4 = fmaf(-s, 4 h - 30.5, x) * inv -- 4 h - 30.5 is exact in fp32 --, a sum of at most dimp squares, one root).
@@ -33,6 +33,21 @@
 // rigorous, so no row whose score reaches tau is lost; the re-scoring, the cut and the merge behind the pass are the u6
 // scan's, the threshold in front of it is too.  NaN / inf rows: a negative scale skips the row, a NaN scale makes w4 and w6
 // NaN, so the row survives both comparisons and is appended with +inf.
+// The converts return h_i 2^-9 and l_i 2^-9 (u42_cvt4), so the kernel carries P' = 2^-9 P and Q' = 2^-9 Q and forms 2048 P' and
+// 512 Q'.  Every fma sees the operands above in the order above scaled by an exact power of two, so 512 P' is P bit for bit
+// unless a partial sum falls below 2^-126: there a rounding errs by at most 2^-150 instead of relatively (unscaled, sums of
+// the multiples h_i q_i of 2^-149 are exact down there).  dimp fmas feed P', dimp feed Q': 2048 P' is off by at most
+// dimp 2^-139 and 512 Q' by dimp 2^-141, together below dimp 2^-138, which the kernel adds to the rounding term inside the
+// product with s: m = a |q|_2 (1 + 1e-5) + s (6e-6 (dimp + 8) |q|_1 (1 + 1e-5) + dimp 2^-138).  For |q|_1 above 1e-33 the
+// addend vanishes in the sum's own rounding and m is the number it was.  Premise: the kernel runs with fp32 denormals KEPT
+// (the compiler's default for this target, float_denorm_mode_32 = 3 in the kernel descriptor; the build sets no flush flag):
+// flushed, a rounding down there would err by 2^-126 and the addend itself would be 0
+// (tests/test_gpu_u42_edges.py runs a query of magnitude 1e-36, whose partial sums are all subnormal, against -inf: it checks
+// the returned w6; NO device test exercises the addend in a decision w + m < tau, since at that magnitude the squares in
+// u6_query_sums underflow and q2 is its floor of 1e-37).  The product with s
+// has its own underflow, as before the scaling: s * (...) and w = s * (...) round to within 2^-150 once they fall below
+// 2^-126, so for rows whose bounds are of the order of 1e-40 and less m can lose the addend or part of the term; the
+// comparison w + m < tau then decides between scores no fp32 re-scoring tells apart from 0.
 // ------------------------------------------------------------------------------------------------
 typedef uint32_t u4v __attribute__((ext_vector_type(4)));
 
@@ -59,16 +74,25 @@ __device__ __forceinline__ u4v u42_load(const uint32_t* p) {
   return *q;
 }
 
-// the eight nibbles of one dword as floats: elements 0 .. 3 from the low nibbles, 4 .. 7 from the high ones
-__device__ __forceinline__ void u42_unpack8(uint32_t d, float (&f)[8]) {
-  float t[4];
-  u6_cvt4(d & 0x0F0F0F0Fu, t);
-  f[0] = t[0], f[1] = t[1], f[2] = t[2], f[3] = t[3];
-  u6_cvt4((d >> 4) & 0x0F0F0F0Fu, t);
-  f[4] = t[0], f[5] = t[1], f[6] = t[2], f[7] = t[3];
+// four masked bytes 0 .. 15 of one dword as two float pairs SCALED BY 2^-9: {byte 0, byte 1} and {byte 2, byte 3}.  Read as OCP
+// e4m3 the byte 0x0h is exactly h * 2^-9 (0 .. 7: the subnormals m * 2^-9; 8 .. 15: exponent field 1, (8 + m) * 2^-9), so one
+// v_cvt_pk_f32_fp8 makes the pair a v_pk_fma_f32 takes (tests/test_gpu_u42_convert.py: every value in every position, bitwise)
+__device__ __forceinline__ void u42_cvt4(uint32_t w, f2v& lo, f2v& hi) {
+  asm volatile("" : "+v"(w));  // (the masked dword stays ONE value, as in u6_cvt4)
+  lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+  hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
 }
 
-// the wave's survivor list: 128 entries, < 64 held between tiles
+// the eight nibbles of one dword as pairs scaled by 2^-9: elements {0,1} {2,3} from the low nibbles, {4,5} {6,7} from the high ones
+__device__ __forceinline__ void u42_unpack8(uint32_t d, f2v (&f)[4]) {
+  u42_cvt4(d & 0x0F0F0F0Fu, f[0], f[1]);
+  u42_cvt4((d >> 4) & 0x0F0F0F0Fu, f[2], f[3]);
+}
+
+// remainders 4 j .. 4 j + 3 of one l dword as pairs scaled by 2^-9
+__device__ __forceinline__ void u42_rem4(uint32_t w, int j, f2v& lo, f2v& hi) { u42_cvt4((w >> (2 * j)) & 0x03030303u, lo, hi); }
+
+// the wave's survivor list: 128 entries, < 64 held between tiles; p = 2^-9 P
 struct U42List {
   uint32_t row[128];
   float p[128];
@@ -108,17 +132,17 @@ __device__ __forceinline__ void u42_refine(const Scan42Args& a, cfloat* q, U42Li
       const uint32_t w = g ? w1 : w0;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        float f[4];
-        u6_cvt4((w >> (2 * j)) & 0x03030303u, f);
+        f2v lo, hi;
+        u42_rem4(w, j, lo, hi);
         const int i = 16 * g + 4 * j;
-        a0 = __builtin_elementwise_fma(f2v{f[0], f[1]}, f2v{qu[i], qu[i + 1]}, a0);
-        a1 = __builtin_elementwise_fma(f2v{f[2], f[3]}, f2v{qu[i + 2], qu[i + 3]}, a1);
+        a0 = __builtin_elementwise_fma(lo, f2v{qu[i], qu[i + 1]}, a0);
+        a1 = __builtin_elementwise_fma(hi, f2v{qu[i + 2], qu[i + 3]}, a1);
       }
     }
   }
   const float a6 = __uint_as_float(rec[2 * a.units]);
   const float qq = (a0.x + a0.y) + (a1.x + a1.y);
-  const float w = s * ((4.0f * p4 + qq) - qsum32);
+  const float w = s * (fmaf(2048.0f, p4, 512.0f * qq) - qsum32);  // (= 4 P + Q in one rounding: both products are exact)
   const float m = fmaf(a6, q2, s * round1);
   const bool keep = active && !(w + m < thr);
   st.push(keep, make_key((w == w) ? w + 0.0f : INFINITY, row), a.cand, a.count, a.cap, lane);
@@ -141,7 +165,7 @@ __global__ __launch_bounds__(256) void scan_u42_kernel(Scan42Args a) {
   u6_query_sums(qg, a.units * 32, lane, qsum32, q1, q2);
   const float qsum305 = 30.5f * (qsum32 * 0.03125f);
   const float thr = a.tau[0];
-  const float round1 = 6e-6f * (float)(a.units * 32 + 8) * q1;
+  const float round1 = fmaf(6e-6f * (float)(a.units * 32 + 8), q1, (float)(a.units * 32) * 0x1p-138f);
   WaveStage st = {stage42[wave], 0u};
   U42List& ls = list42[wave];
   uint32_t fill = 0;
@@ -162,18 +186,18 @@ __global__ __launch_bounds__(256) void scan_u42_kernel(Scan42Args a) {
           cfloat* qu = q + (u0 + u) * 32;
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
-            float f[8];
+            f2v f[4];
             u42_unpack8(v[u][t], f);
-            a0 = __builtin_elementwise_fma(f2v{f[0], f[1]}, f2v{qu[8 * t], qu[8 * t + 1]}, a0);
-            a1 = __builtin_elementwise_fma(f2v{f[2], f[3]}, f2v{qu[8 * t + 2], qu[8 * t + 3]}, a1);
-            a0 = __builtin_elementwise_fma(f2v{f[4], f[5]}, f2v{qu[8 * t + 4], qu[8 * t + 5]}, a0);
-            a1 = __builtin_elementwise_fma(f2v{f[6], f[7]}, f2v{qu[8 * t + 6], qu[8 * t + 7]}, a1);
+            a0 = __builtin_elementwise_fma(f[0], f2v{qu[8 * t], qu[8 * t + 1]}, a0);
+            a1 = __builtin_elementwise_fma(f[1], f2v{qu[8 * t + 2], qu[8 * t + 3]}, a1);
+            a0 = __builtin_elementwise_fma(f[2], f2v{qu[8 * t + 4], qu[8 * t + 5]}, a0);
+            a1 = __builtin_elementwise_fma(f[3], f2v{qu[8 * t + 6], qu[8 * t + 7]}, a1);
           }
         }
       }
     }
-    const float p4 = (a0.x + a0.y) + (a1.x + a1.y);
-    const float w = sa.x * (4.0f * p4 - qsum305);
+    const float p4 = (a0.x + a0.y) + (a1.x + a1.y);  // = 2^-9 P
+    const float w = sa.x * (2048.0f * p4 - qsum305);
     const float m = fmaf(sa.y, q2, sa.x * round1);
     // (as the u6 pass: a NaN bound keeps the row, a negative scale marks a row with a NaN element)
     const bool surv = row < a.n_rows && !(sa.x < 0.f) && !(w + m < thr);
