@@ -109,6 +109,9 @@ struct DistinctPlan {
 
 constexpr uint64_t DISTINCT_SCRATCH_BYTES = 256ull << 20;  // what a round's keys and lists may take (as subset_plan)
 
+// dynamic LDS of label_rank_kernel's list instances: a list of k keys per wave (four waves)
+static inline size_t label_rank_lds(int k) { return (size_t)4 * k * sizeof(uint64_t); }
+
 // n_items >= n_labels >= 1, n_spans >= 1.  A label order whose items alone pass the budget for ONE query still runs, a query
 // at a time (the scratch is then what one query needs).
 static inline DistinctPlan distinct_plan(uint32_t n_items, uint32_t n_labels, uint32_t n_spans, int nq, int k, int cu_count,
@@ -126,7 +129,7 @@ static inline DistinctPlan distinct_plan(uint32_t n_items, uint32_t n_labels, ui
   const uint32_t qblocks = (uint32_t)((round + p.qb - 1) / p.qb);
   const uint64_t want = std::max<uint64_t>(1, ((uint64_t)cu_count * 2 + qblocks - 1) / qblocks);
   p.score_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, ((uint64_t)n_spans + 3) / 4));
-  p.lds = p.select ? 0 : (size_t)4 * k * sizeof(uint64_t);
+  p.lds = p.select ? 0 : label_rank_lds(k);
   p.keys_u64 = (size_t)round * n_items;
   p.rank_u64 = (size_t)round * (p.select ? (size_t)n_labels : (size_t)k * p.rank_blocks);
   return p;

@@ -57,6 +57,9 @@ static inline uint64_t multivector_rank_u64_per_segment(bool select, uint32_t n_
   return select ? (uint64_t)n_labels : (uint64_t)k * rank_blocks;
 }
 
+// dynamic LDS of multivector_rank_kernel's list instances: a list of k keys per wave (four waves)
+static inline size_t multivector_rank_lds(int k) { return (size_t)4 * k * sizeof(uint64_t); }
+
 // scoring grid.x for a round of `vectors`: two workgroups per CU over all vector blocks TOGETHER and never one more (the 8-vector
 // instances run two workgroups per CU: with 3 blocks, 171 x 3 = 513 workgroups left one behind a full machine and the round
 // took twice its time, profiles/multivector/), four spans per workgroup at least
@@ -83,7 +86,7 @@ static inline MultivectorPlan multivector_plan(const uint64_t* vector_offsets, i
   const uint64_t opt = (uint64_t)std::min<int64_t>(std::max<int64_t>(round_vectors, 1), MULTIVECTOR_MAX_ROUND);
   p.round_max = (int)std::max<uint64_t>(1, std::min<uint64_t>(opt, fit));
   p.qb = (p.round_max == 1 || total <= 1) ? 1 : MULTIVECTOR_BLOCK;
-  p.lds = p.select ? 0 : (size_t)4 * k * sizeof(uint64_t);
+  p.lds = p.select ? 0 : multivector_rank_lds(k);
   p.score_blocks = multivector_score_blocks((uint32_t)std::min<uint64_t>(total, (uint64_t)p.round_max), p.qb, n_spans, cu_count);
   int q = 0;  // the query of the next vector
   for (uint64_t first = 0; first < total;) {

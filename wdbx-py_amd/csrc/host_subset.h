@@ -58,6 +58,9 @@ struct SubsetPlan {
   size_t scratch_u64 = 0;  // u64s of scratch per round: partial lists (LISTS) or keys (KEYS, SELECT)
 };
 
+// dynamic LDS of subset_kernel's list instances: a list of k keys per wave and query of the block (four waves)
+static inline size_t subset_lists_lds(int qb, int k) { return (size_t)4 * qb * k * sizeof(uint64_t); }
+
 // cu_count: compute units; the grid holds about two workgroups per CU over all query blocks (eight waves per CU, each with
 // several rows' loads in flight) and never more waves than listed rows.  A round's scratch stays within 256 MiB.
 static inline SubsetPlan subset_plan(uint64_t n_ids, int nq, int k, int cu_count, int64_t keys_max, int64_t select_min_k,
@@ -80,7 +83,7 @@ static inline SubsetPlan subset_plan(uint64_t n_ids, int nq, int k, int cu_count
   p.blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, (n_ids + 3) / 4));
   if (p.route == SUBSET_LISTS) {
     p.P = p.blocks;
-    p.lds = (size_t)4 * p.qb * k * sizeof(uint64_t);
+    p.lds = subset_lists_lds(p.qb, k);
     p.scratch_u64 = (size_t)round * k * p.P;
   } else {
     p.scratch_u64 = (size_t)round * n_ids;
