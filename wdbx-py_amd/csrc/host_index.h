@@ -593,6 +593,99 @@ static int launch_merge(wdbx_index* ix, const MergeArgs& m_in, int nq) {
   return record(ix->merge_ev, ix->profile, ix->stream, false);
 }
 
+// ---- the steps the selection rounds share (their plan: host_selection.h) ------------------------------------------
+static_assert(SELECTION_BLOCK_QUERIES == GB_N, "host_selection.h sizes the pair lists for the widest query block");
+
+// The thresholds of nv queries from their sampled lower bounds in d_halfmax (`bounds` per query) into d_tau: the k-th largest
+// bound, a rigorous lower bound of each query's true k-th best score.  allow_kth: by kth_score_kernel where the bounds fit it
+// (at most 2^-15 relative below the k-th largest), else -- and always on the legacy tiles -- by the list merge.
+static int enqueue_sample_threshold(wdbx_index* ix, uint32_t bounds, int k, int nv, bool allow_kth) {
+  int rc;
+  if (allow_kth && bounds <= (uint32_t)KTH_R * 1024 && !ix->opt_lds_lists) {
+    KthArgs ka = {ix->d_halfmax, (u64)bounds, bounds, k, ix->d_tau};
+    if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
+    HIP_TRY(enqueue_kth(ix->stream, ka, nv));
+    return record(ix->merge_ev, ix->profile, ix->stream, false);
+  }
+  MergeArgs m = {};
+  m.in = ix->d_halfmax;
+  m.q_stride = bounds;
+  m.i_stride = 0;
+  m.p_stride = 1;
+  m.P = bounds;
+  m.list_len = 1;
+  m.k = k;
+  m.metric = ix->metric;
+  m.out_kth = ix->d_tau;
+  return launch_merge(ix, m, nv);
+}
+
+// The final ranking of a round: per query the best k of its d_count[q] (at most cap) re-scored keys at in + q * cap.
+static MergeArgs final_topk_args(const wdbx_index* ix, const u64* in, uint32_t cap, const uint32_t* d_count, int k) {
+  MergeArgs f = {};
+  f.in = in;
+  f.q_stride = cap;
+  f.i_stride = 0;
+  f.p_stride = 1;
+  f.P = cap;
+  f.P_dev = d_count;
+  f.list_len = 1;
+  f.k = k;
+  f.metric = ix->metric;
+  return f;
+}
+
+// ... and where it goes, for the queries from q0 on: keys with global rows for the caller's own exchange (keys_out), this
+// shard's lists with global rows for the exchange that follows (sharded), or the results themselves
+static void final_topk_output(const wdbx_index* ix, MergeArgs* f, u64* keys_out, bool sharded, int64_t* d_out_idx, float* d_out_score,
+                              int q0, int k) {
+  if (keys_out) {
+    f->row_base = (uint32_t)ix->row_base;
+    f->out_keys = keys_out + (size_t)q0 * k;
+  } else if (sharded) {
+    f->row_base = (uint32_t)ix->row_base;
+    f->out_keys = ix->d_local_keys;
+  } else {
+    f->out_idx = d_out_idx + (size_t)q0 * k;
+    f->out_score = d_out_score + (size_t)q0 * k;
+  }
+}
+
+// The life cycle of a shadow copy's allocations (u8: codes and scales; u6, u42: one each).  Nothing to do while the shape is
+// the same and every part is large enough.  Else the parts are freed and allocated anew and *shadow_rows restarts at 0;
+// false = no room on the device, remembered per capacity in *no_room_cap so that the next calls do not try again.
+struct ShadowPart {
+  void** p;
+  size_t* bytes;
+  size_t need;
+};
+static bool shadow_room(wdbx_index* ix, bool shape_changed, std::initializer_list<ShadowPart> parts, uint64_t* shadow_rows,
+                        uint64_t* no_room_cap) {
+  bool stale = shape_changed;
+  for (const ShadowPart& s : parts) stale = stale || *s.bytes < s.need;
+  if (!stale) return true;
+  if (*no_room_cap == ix->cap) return false;
+  auto release = [&] {
+    for (const ShadowPart& s : parts) {
+      if (*s.p) (void)hipFree(*s.p);
+      *s.p = nullptr;
+      *s.bytes = 0;
+    }
+  };
+  release();
+  *shadow_rows = 0;
+  for (const ShadowPart& s : parts) {
+    if (hipMalloc(s.p, s.need) == hipSuccess) continue;
+    (void)hipGetLastError();
+    *s.p = nullptr;
+    release();
+    *no_room_cap = ix->cap;
+    return false;
+  }
+  for (const ShadowPart& s : parts) *s.bytes = s.need;
+  return true;
+}
+
 // all-gather this rank's key lists [b, k] (global rows) and merge the nranks lists per query
 static int exchange_and_merge(wdbx_index* ix, int b, int k, int64_t* d_out_idx, float* d_out_score) {
   int rc = grow((void**)&ix->d_gathered, &ix->gathered_bytes, (size_t)ix->nranks * b * k * sizeof(u64));
@@ -963,25 +1056,10 @@ static bool prepare_u8_shadow(wdbx_index* ix) {
   if (!sh) return false;
   const uint32_t pitch8 = sh->pieces * 16;
   const size_t need = ((size_t)ix->cap + TILE_PAD_ROWS) * pitch8, need_s = ((size_t)ix->cap + TILE_PAD_ROWS) * sizeof(float);
-  if (ix->rows8_bytes < need || ix->scale8_bytes < need_s || ix->pitch8 != pitch8) {
-    if (ix->u8_no_room_cap == ix->cap) return false;
-    if (ix->d_rows8) (void)hipFree(ix->d_rows8);
-    if (ix->d_scale8) (void)hipFree(ix->d_scale8);
-    ix->d_rows8 = nullptr;
-    ix->d_scale8 = nullptr;
-    ix->rows8_bytes = ix->scale8_bytes = 0;
-    ix->shadow8_rows = 0;
-    if (hipMalloc((void**)&ix->d_rows8, need) != hipSuccess || hipMalloc((void**)&ix->d_scale8, need_s) != hipSuccess) {
-      (void)hipGetLastError();
-      if (ix->d_rows8) (void)hipFree(ix->d_rows8);
-      ix->d_rows8 = nullptr;
-      ix->u8_no_room_cap = ix->cap;
-      return false;
-    }
-    ix->rows8_bytes = need;
-    ix->scale8_bytes = need_s;
-    ix->pitch8 = pitch8;
-  }
+  if (!shadow_room(ix, ix->pitch8 != pitch8, {{(void**)&ix->d_rows8, &ix->rows8_bytes, need}, {(void**)&ix->d_scale8, &ix->scale8_bytes, need_s}},
+                   &ix->shadow8_rows, &ix->u8_no_room_cap))
+    return false;
+  ix->pitch8 = pitch8;
   if (ix->shadow8_rows < ix->n) {
     const uint32_t blocks = rows_to_u8_grid(ix->n - ix->shadow8_rows);
     hipLaunchKernelGGL(rows_to_u8_kernel, dim3(blocks), dim3(256), 0, ix->stream, (const float*)ix->d_rows, (u64)ix->shadow8_rows,
@@ -1053,15 +1131,12 @@ static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, in
   if (ix->rows8_bytes < ((size_t)ix->cap + TILE_PAD_ROWS) * pitch8 || ix->pitch8 != pitch8 || ix->shadow8_rows < ix->n)
     return fail(WDBX_E_STATE, "u8 shadow not prepared");
   if (l2 && (rc = ensure_row_norms(ix))) return rc;  // squared fp32 norms of the rows (the 2 w - |c|^2 form)
-  // sampled 256-row tiles (4 groups of 64 rows each), as on the tile path
-  const uint32_t tiles = (uint32_t)((ix->n + 255) / 256);
-  const uint32_t div = ix->opt_gemm_sample_div > 0 ? (uint32_t)ix->opt_gemm_sample_div : std::min(32u, std::max(4u, 1024u / (uint32_t)k));
-  uint32_t sample_tiles = std::max<uint32_t>(tiles / div, (8u * k + 3) / 4);
-  sample_tiles = std::max<uint32_t>(1, std::min(sample_tiles, tiles));
-  const uint32_t stride = tiles / sample_tiles, ngroups = 4 * sample_tiles;
+  // the plan (host_selection.h): sampled 256-row tiles of 4 groups of 64 rows each, as on the tile path; a larger sample for
+  // a larger k; 32 x the expected rows as candidates
+  const SelectionSample s = selection_sample(ix->n, 256, 4, k, selection_div(ix->opt_gemm_sample_div, k, true));
+  const uint32_t sample_tiles = s.sample_tiles, stride = s.stride, ngroups = s.bounds;
   if (ngroups < (uint32_t)k) return fail(WDBX_E_STATE, "corpus too small for the selection scan at k=%d", k);
-  const uint64_t expect = (uint64_t)k * (tiles / sample_tiles + 1);
-  const uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(4096, expect * 32), 1u << 22);
+  const uint32_t cap = selection_cap(s.expect, 32);
   constexpr int ROUND = 64;  // queries per round at most (the caller hands over `exchange_batch` = 32 queries at a time by default)
   if ((rc = grow((void**)&ix->d_halfmax, &ix->halfmax_bytes, (size_t)ROUND * ngroups * sizeof(u64)))) return rc;
   if ((rc = grow((void**)&ix->d_tau, &ix->tau_bytes, (size_t)GB_N * sizeof(float)))) return rc;
@@ -1079,8 +1154,8 @@ static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, in
   // shorter workgroups per pass the tail of one query's pass overlaps the start of the next one's instead of the two resident
   // workgroups of every CU walking through prologue and tail in step (1.25 M rows 12 545 -> 12 782 q/s, 2.5 M 6 246 -> 6 512;
   // 400 k rows lose with more than 2, 5 M and 10 M rows do not care: profiles/r04/small_shard/summary.txt).  -1 = by size.
-  const uint64_t shadow_bytes = (uint64_t)ix->n * pitch8;
-  const int64_t wgs_auto = (nq > 1 && shadow_bytes >= (400ull << 20) && shadow_bytes <= (1ull << 30)) ? 6 : 2;  // (measured on rounds)
+  const bool over_1gib = shadow_over_1gib(ix->n, pitch8);
+  const int64_t wgs_auto = (nq > 1 && (uint64_t)ix->n * pitch8 >= (400ull << 20) && !over_1gib) ? 6 : 2;  // (measured on rounds)
   const uint32_t wgs = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(ix->opt_scan8_wgs > 0 ? ix->opt_scan8_wgs : wgs_auto, 8));
   const uint32_t grid1 = scan_full_grid(groups1, (uint32_t)ix->cu_count, wgs);
   const uint32_t grid0 = scan_sample_grid(ngroups, (uint32_t)ix->cu_count);
@@ -1139,24 +1214,8 @@ static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, in
       hipLaunchKernelGGL(select_kth_value_kernel, dim3(1), dim3(64), 0, ix->stream, (const SelectState*)ix->d_state, (uint32_t)k,
                          ix->d_tau);
       HIP_TRY(hipGetLastError());
-    } else if (ngroups <= (uint32_t)KTH_R * 1024 && !ix->opt_lds_lists) {
-      // a threshold from the k-th largest sampled lower bound (at most 2^-15 relative below it: kth_score_kernel)
-      KthArgs ka = {ix->d_halfmax, (u64)ngroups, ngroups, k, ix->d_tau};
-      if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
-      HIP_TRY(enqueue_kth(ix->stream, ka, nv));
-      if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
-    } else {
-      MergeArgs m = {};
-      m.in = ix->d_halfmax;
-      m.q_stride = ngroups;
-      m.i_stride = 0;
-      m.p_stride = 1;
-      m.P = ngroups;
-      m.list_len = 1;
-      m.k = k;
-      m.metric = ix->metric;
-      m.out_kth = ix->d_tau;  // = a rigorous lower bound of each query's true k-th best score
-      if ((rc = launch_merge(ix, m, nv))) return rc;
+    } else if ((rc = enqueue_sample_threshold(ix, ngroups, k, nv, true))) {
+      return rc;
     }
     // phase 1: every row whose upper bound reaches the threshold.  Every query makes its own pass over all rows; the
     // round's passes go out as ONE grid on small shards (grid.y = query: no launch gaps, ramps and tails overlap; option
@@ -1174,7 +1233,7 @@ static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, in
     }
     // (measured, d = 384: 1.25 M rows 84.5 vs 86.9 us per pass in one grid; 10 M rows 603 vs 591 us -- two passes streaming
     // different regions at once cost more there than the gaps between launches.  -1 = by size: one grid up to 1 GiB of shadow)
-    const bool one_grid = ix->opt_scan8_per_query == 0 || (ix->opt_scan8_per_query < 0 && (uint64_t)ix->n * pitch8 <= (1ull << 30));
+    const bool one_grid = ix->opt_scan8_per_query == 0 || (ix->opt_scan8_per_query < 0 && !over_1gib);
     if (one_grid && nv > 1) {
       hipLaunchKernelGGL(f1, dim3(grid1, nv), dim3(256), 0, ix->stream, a);
       HIP_TRY(hipGetLastError());
@@ -1200,24 +1259,9 @@ static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, in
       ix->lone_used = true;
       continue;
     }
-    MergeArgs f = {};
-    f.in = ix->d_cand;
-    f.q_stride = cap;
-    f.i_stride = 0;
-    f.p_stride = 1;
-    f.P = cap;
-    f.P_dev = ix->d_count + q0;
-    f.list_len = 1;
-    f.k = k;
-    f.metric = ix->metric;
+    MergeArgs f = final_topk_args(ix, ix->d_cand, cap, ix->d_count + q0, k);
     f.over_out = ix->defer_flag_dev ? ix->defer_flag_dev + q0 : nullptr;
-    if (keys_out) {
-      f.row_base = (uint32_t)ix->row_base;
-      f.out_keys = keys_out + (size_t)q0 * k;
-    } else {
-      f.out_idx = d_out_idx + (size_t)q0 * k;
-      f.out_score = d_out_score + (size_t)q0 * k;
-    }
+    final_topk_output(ix, &f, keys_out, false, d_out_idx, d_out_score, q0, k);
     if ((rc = launch_merge(ix, f, nv))) return rc;
   }
   return WDBX_OK;
@@ -1231,7 +1275,7 @@ static bool u6_single_eligible(const wdbx_index* ix, int k, int nq_call) {
   if (ix->opt_scan_u6 == 0 || ix->metric == WDBX_METRIC_L2 || ix->active_mask || k > 32 || nq_call < 2) return false;
   if (ix->pitch % 16 != 0 || ix->pitch > 4096 || !u6_unit_chunk((uint32_t)ix->pitch / 16)) return false;
   const Scan8Shape* sh = scan8_shape((uint32_t)ix->dim);
-  if (ix->opt_scan_u6 < 0 && (!sh || (uint64_t)ix->n * sh->pieces * 16 <= (1ull << 30))) return false;
+  if (ix->opt_scan_u6 < 0 && (!sh || !shadow_over_1gib(ix->n, sh->pieces * 16))) return false;
   return true;
 }
 
@@ -1251,22 +1295,11 @@ static bool prepare_u6_shadow(wdbx_index* ix) {
   const uint32_t units = (uint32_t)ix->pitch / 16;
   const uint64_t tiles = ((uint64_t)ix->cap + 63) / 64;
   const size_t need = (size_t)tiles * units * 768 + (size_t)tiles * 64 * sizeof(f2v);
-  if (ix->rows6_bytes < need || ix->units6 != units || ix->rows6_tiles != tiles) {
-    if (ix->u6_no_room_cap == ix->cap) return false;
-    if (ix->d_rows6) (void)hipFree(ix->d_rows6);
-    ix->d_rows6 = nullptr;
-    ix->rows6_bytes = 0;
-    ix->shadow6_rows = 0;
-    if (hipMalloc((void**)&ix->d_rows6, need) != hipSuccess) {
-      (void)hipGetLastError();
-      ix->d_rows6 = nullptr;
-      ix->u6_no_room_cap = ix->cap;
-      return false;
-    }
-    ix->rows6_bytes = need;
-    ix->units6 = units;
-    ix->rows6_tiles = tiles;
-  }
+  if (!shadow_room(ix, ix->units6 != units || ix->rows6_tiles != tiles, {{(void**)&ix->d_rows6, &ix->rows6_bytes, need}}, &ix->shadow6_rows,
+                   &ix->u6_no_room_cap))
+    return false;
+  ix->units6 = units;
+  ix->rows6_tiles = tiles;
   if (ix->shadow6_rows < ix->n) {
     const uint32_t blocks = rows_to_u6_grid(ix->n - ix->shadow6_rows);
     hipLaunchKernelGGL(rows_to_u6_kernel, dim3(blocks), dim3(256), 0, ix->stream, (const float*)ix->d_rows, (u64)ix->shadow6_rows,
@@ -1283,7 +1316,7 @@ static bool prepare_u6_shadow(wdbx_index* ix) {
 static bool u42_single_eligible(const wdbx_index* ix) {
   if (ix->opt_scan_u42 == 0 || ix->pitch % 32 != 0 || !u42_unit_chunk((uint32_t)ix->pitch / 32)) return false;
   const Scan8Shape* sh = scan8_shape((uint32_t)ix->dim);
-  if (ix->opt_scan_u42 < 0 && (!sh || (uint64_t)ix->n * sh->pieces * 16 <= (1ull << 30))) return false;
+  if (ix->opt_scan_u42 < 0 && (!sh || !shadow_over_1gib(ix->n, sh->pieces * 16))) return false;
   return true;
 }
 
@@ -1293,22 +1326,11 @@ static bool prepare_u42_shadow(wdbx_index* ix) {
   const uint32_t units = (uint32_t)ix->pitch / 32, lpitch = u42_lpitch(units);
   const uint64_t tiles = ((uint64_t)ix->cap + 63) / 64;
   const size_t need = (size_t)tiles * units * 1024 + (size_t)tiles * 64 * sizeof(f2v) + (size_t)tiles * 64 * lpitch * sizeof(uint32_t);
-  if (ix->rows42_bytes < need || ix->units42 != units || ix->rows42_tiles != tiles) {
-    if (ix->u42_no_room_cap == ix->cap) return false;
-    if (ix->d_rows42) (void)hipFree(ix->d_rows42);
-    ix->d_rows42 = nullptr;
-    ix->rows42_bytes = 0;
-    ix->shadow42_rows = 0;
-    if (hipMalloc((void**)&ix->d_rows42, need) != hipSuccess) {
-      (void)hipGetLastError();
-      ix->d_rows42 = nullptr;
-      ix->u42_no_room_cap = ix->cap;
-      return false;
-    }
-    ix->rows42_bytes = need;
-    ix->units42 = units;
-    ix->rows42_tiles = tiles;
-  }
+  if (!shadow_room(ix, ix->units42 != units || ix->rows42_tiles != tiles, {{(void**)&ix->d_rows42, &ix->rows42_bytes, need}},
+                   &ix->shadow42_rows, &ix->u42_no_room_cap))
+    return false;
+  ix->units42 = units;
+  ix->rows42_tiles = tiles;
   if (ix->shadow42_rows < ix->n) {
     if (launch_rows_to_u42(ix, ix->shadow42_rows, ix->n) != hipSuccess) return false;
     ix->shadow42_rows = ix->n;
@@ -1332,18 +1354,13 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
   if (u42 && (!f42 || !ix->d_rows42 || ix->units42 != units / 2 || ix->shadow42_rows < ix->n))
     return fail(WDBX_E_STATE, "split planes not prepared");
   int rc;
-  // sampled 256-row tiles (4 groups of 64 rows each), as on the u8 scan
-  const uint32_t tiles = (uint32_t)((ix->n + 255) / 256);
-  const uint32_t div = ix->opt_gemm_sample_div > 0 ? (uint32_t)ix->opt_gemm_sample_div : std::min(32u, std::max(4u, 1024u / (uint32_t)k));
-  uint32_t sample_tiles = std::max<uint32_t>(tiles / div, (8u * k + 3) / 4);
-  sample_tiles = std::max<uint32_t>(1, std::min(sample_tiles, tiles));
-  const uint32_t stride = tiles / sample_tiles, ngroups = 4 * sample_tiles;
+  // the plan (host_selection.h): sampled 256-row tiles of 4 groups of 64 rows each and the divisor of the u8 scan
+  const SelectionSample s = selection_sample(ix->n, 256, 4, k, selection_div(ix->opt_gemm_sample_div, k, true));
+  const uint32_t sample_tiles = s.sample_tiles, stride = s.stride, ngroups = s.bounds;
   if (ngroups < (uint32_t)k) return fail(WDBX_E_STATE, "corpus too small for the selection scan at k=%d", k);
   // candidates: 256 x the k * (stride + 1) rows expected above the threshold (10 M x 384 top-10: 84 480; measured 3.8 k per
   // query on the bench corpus, an estimated 25 k on Gaussian rows)
-  const uint64_t expect = (uint64_t)k * (tiles / sample_tiles + 1);
-  const uint32_t cap = ix->opt_scan_u6_cap > 0 ? (uint32_t)std::min<int64_t>(ix->opt_scan_u6_cap, 1 << 22)
-                                               : (uint32_t)std::min<uint64_t>(std::max<uint64_t>(4096, expect * 256), 1u << 22);
+  const uint32_t cap = ix->opt_scan_u6_cap > 0 ? (uint32_t)std::min<int64_t>(ix->opt_scan_u6_cap, 1 << 22) : selection_cap(s.expect, 256);
   constexpr uint32_t cap2 = 4096;  // the cut's short list: a few keys beyond k per segment
   constexpr int ROUND = 64;
   if ((rc = grow((void**)&ix->d_halfmax, &ix->halfmax_bytes, (size_t)ROUND * ngroups * sizeof(u64)))) return rc;
@@ -1367,8 +1384,7 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
   const uint32_t grid0 = scan_sample_grid(ngroups, (uint32_t)ix->cu_count);
   const size_t pitch4 = ix->pitch / 4;
   const Scan8Shape* sh = scan8_shape((uint32_t)ix->dim);
-  const bool one_grid = ix->opt_scan8_per_query == 0 ||
-                        (ix->opt_scan8_per_query < 0 && sh && (uint64_t)ix->n * sh->pieces * 16 <= (1ull << 30));
+  const bool one_grid = ix->opt_scan8_per_query == 0 || (ix->opt_scan8_per_query < 0 && sh && !shadow_over_1gib(ix->n, sh->pieces * 16));
 
   for (int q0 = 0; q0 < nq; q0 += ROUND) {
     const int nv = std::min(ROUND, nq - q0);
@@ -1395,25 +1411,7 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
     hipLaunchKernelGGL(f0, dim3(grid0, (nv + 3) / 4), dim3(256), 0, ix->stream, a);
     HIP_TRY(hipGetLastError());
     if ((rc = record(ix->sample_ev, ix->profile, ix->stream, false))) return rc;
-    if (ngroups <= (uint32_t)KTH_R * 1024 && !ix->opt_lds_lists) {
-      // a threshold from the k-th largest sampled lower bound (at most 2^-15 relative below it: kth_score_kernel)
-      KthArgs ka = {ix->d_halfmax, (u64)ngroups, ngroups, k, ix->d_tau};
-      if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
-      HIP_TRY(enqueue_kth(ix->stream, ka, nv));
-      if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
-    } else {
-      MergeArgs m = {};
-      m.in = ix->d_halfmax;
-      m.q_stride = ngroups;
-      m.i_stride = 0;
-      m.p_stride = 1;
-      m.P = ngroups;
-      m.list_len = 1;
-      m.k = k;
-      m.metric = ix->metric;
-      m.out_kth = ix->d_tau;  // = a rigorous lower bound of each query's true k-th best score
-      if ((rc = launch_merge(ix, m, nv))) return rc;
-    }
+    if ((rc = enqueue_sample_threshold(ix, ngroups, k, nv, true))) return rc;
     // the full passes: every query makes its own pass over all rows (one grid on small shards, as the u8 scan); one event
     // pair around them, the profile reports elapsed / passes
     if ((rc = record(ix->gemm_ev, ix->profile, ix->stream, true))) return rc;
@@ -1461,24 +1459,9 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
     hipLaunchKernelGGL(u6_cut_kernel, dim3((cap + U6_CUT_SEG - 1) / U6_CUT_SEG, nv), dim3(1024), 0, ix->stream, (const u64*)ix->d_cand,
                        (const uint32_t*)ix->d_count6, cap, k, cand2, ix->d_count + q0, cap2);
     HIP_TRY(hipGetLastError());
-    MergeArgs f = {};
-    f.in = cand2;
-    f.q_stride = cap2;
-    f.i_stride = 0;
-    f.p_stride = 1;
-    f.P = cap2;
-    f.P_dev = ix->d_count + q0;
-    f.list_len = 1;
-    f.k = k;
-    f.metric = ix->metric;
+    MergeArgs f = final_topk_args(ix, cand2, cap2, ix->d_count + q0, k);
     f.over_out = ix->defer_flag_dev ? ix->defer_flag_dev + q0 : nullptr;
-    if (keys_out) {
-      f.row_base = (uint32_t)ix->row_base;
-      f.out_keys = keys_out + (size_t)q0 * k;
-    } else {
-      f.out_idx = d_out_idx + (size_t)q0 * k;
-      f.out_score = d_out_score + (size_t)q0 * k;
-    }
+    final_topk_output(ix, &f, keys_out, false, d_out_idx, d_out_score, q0, k);
     if ((rc = launch_merge(ix, f, nv))) return rc;
   }
   return WDBX_OK;
@@ -1687,19 +1670,14 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
   ix->last_gemm_mode = family;
   const bool l2 = ix->metric == WDBX_METRIC_L2, bf16 = family != GEMM_FP32;
   const bool inexact = l2 || bf16;  // selection scores differ from the final ones: margin + exact re-scoring
-  const uint32_t tile_rows = gemm_tile_rows(family), rw = tile_rows / 64;  // rw: PHASE 0 keys per tile and query
-  const uint32_t tiles = (uint32_t)((ix->n + tile_rows - 1) / tile_rows);
-  // sampled fraction 1/div: the bf16 tiles make the sample pass cheap and their error margin multiplies the
-  // candidates, so a larger k gets a larger sample (a tighter threshold) there
-  const uint32_t div = ix->opt_gemm_sample_div > 0 ? (uint32_t)ix->opt_gemm_sample_div
-                       : bf16 ? std::min(32u, std::max(4u, 1024u / (uint32_t)k)) : 32u;
-  uint32_t sample_tiles = std::max<uint32_t>(tiles / div, (8u * k + rw - 1) / rw);
-  sample_tiles = std::max<uint32_t>(1, std::min(sample_tiles, tiles));
-  const uint32_t stride = tiles / sample_tiles;
-  if (rw * sample_tiles < (uint32_t)k) return fail(WDBX_E_STATE, "corpus too small for the batched path at k=%d", k);
-  // expected candidates per query ~ k * tiles / sample_tiles; capacity leaves a wide margin
-  const uint64_t expect = (uint64_t)k * (tiles / sample_tiles + 1);
-  const uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(4096, expect * (bf16 ? 32 : 8)), 1u << 22);
+  // the plan (host_selection.h): the family's tiles, a PHASE 0 key per 64 rows of a tile and query (rw).  The bf16 tiles make
+  // the sample pass cheap and their error margin multiplies the candidates, so a larger k gets a larger sample (a tighter
+  // threshold) there, and 32 x the expected candidates as capacity against 8 x on the exact fp32 tiles
+  const uint32_t tile_rows = gemm_tile_rows(family), rw = tile_rows / 64;
+  const SelectionSample s = selection_sample(ix->n, tile_rows, rw, k, selection_div(ix->opt_gemm_sample_div, k, bf16));
+  const uint32_t tiles = s.tiles, sample_tiles = s.sample_tiles, stride = s.stride;
+  if (s.bounds < (uint32_t)k) return fail(WDBX_E_STATE, "corpus too small for the batched path at k=%d", k);
+  const uint32_t cap = selection_cap(s.expect, bf16 ? 32 : 8);
   const size_t pitch4 = ix->pitch / 4;
   if ((rc = grow((void**)&ix->d_qblock, &ix->qblock_bytes, (size_t)GB_N * ix->pitch * sizeof(float)))) return rc;
   if ((rc = grow((void**)&ix->d_halfmax, &ix->halfmax_bytes, (size_t)GB_N * rw * sample_tiles * sizeof(u64)))) return rc;
@@ -1824,17 +1802,7 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
       if (group_bounds) g.qn = ix->d_qn + (per_query ? i : 0);
       if ((rc = launch_gemm<0>(ix, g, ct, family))) return rc;
     }
-    MergeArgs m = {};
-    m.in = ix->d_halfmax;
-    m.q_stride = (u64)rw * sample_tiles;
-    m.i_stride = 0;
-    m.p_stride = 1;
-    m.P = rw * sample_tiles;
-    m.list_len = 1;
-    m.k = k;
-    m.metric = ix->metric;
-    m.out_kth = ix->d_tau;
-    if ((rc = launch_merge(ix, m, nv))) return rc;
+    if ((rc = enqueue_sample_threshold(ix, s.bounds, k, nv, false))) return rc;  // (these families never took kth_score_kernel)
     if (inexact && !group_bounds) {  // one global rounding-error margin below the sampled threshold
       hipLaunchKernelGGL(tau_margin_kernel, dim3(nv), dim3(64), 0, ix->stream, ix->d_tau, qsrc, (uint32_t)ix->pitch, nv,
                          (const uint32_t*)ix->d_cnmax, ix->metric, (int)bf16, sel_floor);
@@ -1858,26 +1826,8 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
                          (const uint32_t*)(d_count + q0), cap, (u64*)nullptr, (uint32_t*)nullptr);
       HIP_TRY(hipGetLastError());
     }
-    MergeArgs f = {};
-    f.in = ix->d_cand;
-    f.q_stride = cap;
-    f.i_stride = 0;
-    f.p_stride = 1;
-    f.P = cap;
-    f.P_dev = d_count + q0;
-    f.list_len = 1;
-    f.k = k;
-    f.metric = ix->metric;
-    if (keys_out) {  // keys with global rows for the caller's own exchange
-      f.row_base = (uint32_t)ix->row_base;
-      f.out_keys = keys_out + (size_t)q0 * k;
-    } else if (sharded) {  // this shard's lists with global rows, then the exchange
-      f.row_base = (uint32_t)ix->row_base;
-      f.out_keys = ix->d_local_keys;
-    } else {
-      f.out_idx = d_out_idx + (size_t)q0 * k;
-      f.out_score = d_out_score + (size_t)q0 * k;
-    }
+    MergeArgs f = final_topk_args(ix, ix->d_cand, cap, d_count + q0, k);
+    final_topk_output(ix, &f, keys_out, sharded, d_out_idx, d_out_score, q0, k);
     if ((rc = launch_merge(ix, f, nv))) return rc;
     if (!per_query) {  // (the single-query caller queues its own repair launches)
       bool done = false;
@@ -1943,29 +1893,14 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
   const bool masked = ix->active_mask != nullptr, multi = mc != nullptr;
   if (multi && (masked || sharded || keys_out)) return fail(WDBX_E_STATE, "a mask per query: the plain blocking call only");
   const uint32_t pitch8 = ix->pitch8g;
-  const uint32_t tiles = (uint32_t)((ix->n + G8_ROWS - 1) / G8_ROWS), rw = G8_ROWS / 32;  // a lower bound per 32-row block
-  const uint32_t div = ix->opt_gemm_sample_div > 0 ? (uint32_t)ix->opt_gemm_sample_div : std::min(32u, std::max(4u, 1024u / (uint32_t)k));
+  // the plan (host_selection.h): tiles of G8_ROWS rows, a lower bound per 32-row block, the divisor of the selection scans,
+  // 32 x the expected rows as candidates.  A row mask grows the sample (selection_sample_masked).
+  constexpr uint32_t rw = G8_ROWS / 32;
+  const SelectionSample base = selection_sample(ix->n, G8_ROWS, rw, k, selection_div(ix->opt_gemm_sample_div, k, true));
+  const uint32_t tiles = base.tiles;
   // the sampled tiles of a call (or, with a mask per query, of one block) whose mask allows `allowed` rows
   auto sample_for = [&](bool masked, uint64_t allowed) -> uint32_t {
-    uint32_t sample_tiles = std::max<uint32_t>(tiles / div, (8u * k + rw - 1) / rw);
-    // (a mask of at most 16 384 rows: the candidate buffers hold ALL of them, see below, so tau = -inf is answered from the
-    // candidates and a larger sample would buy nothing: the sample stays what an unmasked call takes)
-    if (masked && allowed > 16384) {
-      // A row mask that allows a fraction f of the rows: only blocks holding an allowed row vouch, and each for the best of its
-      // ~32 f allowed rows.  tau is then the k-th best of ~(sampled rows) x f rows and the full pass keeps ~k x rows / (sampled
-      // rows) of the allowed ones: the candidates per query do not grow with 1 / f, but the VOUCHING blocks shrink -- a fraction
-      // 1 - (1 - f)^32 of the sampled ones.  So the sample grows by 1 / f, up to 8 x (a quarter of the corpus at the default
-      // 1 / 32: beyond that the sample pass would cost what the full pass does), and further only while fewer than 8 k sampled
-      // blocks are expected to vouch; clamped to all tiles.  Fewer than k vouching blocks leave tau = -inf: every allowed row is a
-      // candidate, what does not fit is repaired by the masked fp32 scan.  
-      const double f = ix->n ? (double)allowed / (double)ix->n : 0.0;
-      if (f > 0.0) {
-        const double pv = 1.0 - std::pow(1.0 - std::min(f, 1.0), 32.0);
-        const double scaled = (double)sample_tiles * std::min(1.0 / f, 8.0), vouch = (8.0 * k) / (rw * std::max(pv, 1e-9));
-        sample_tiles = (uint32_t)std::min<double>(std::ceil(std::max(scaled, vouch)), (double)tiles);
-      }
-    }
-    return std::max<uint32_t>(1, std::min(sample_tiles, tiles));
+    return masked ? selection_sample_masked(base.sample_tiles, tiles, rw, k, ix->n, allowed) : base.sample_tiles;
   };
   // A mask per query: the rule per BLOCK, for its most selective class above 16 384 rows (the class whose vouching blocks
   // are fewest; the block's other classes get a larger sample than they need, never a smaller one).  Sizes below: the
@@ -1996,9 +1931,9 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
     sample_tiles = sample_max = sample_for(masked, ix->mask_allowed);
     if (masked && ix->mask_allowed <= 16384) small_class = ix->mask_allowed;
   }
-  if (rw * sample_tiles < (uint32_t)k) return fail(WDBX_E_STATE, "corpus too small for the batched path at k=%d", k);
-  const uint64_t expect = (uint64_t)k * (tiles / sample_tiles + 1);
-  uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(4096, expect * 32), 1u << 22);
+  const SelectionSample s = selection_of(tiles, sample_tiles, rw, k);  // (the call's smallest sample: the most candidates per query)
+  if (s.bounds < (uint32_t)k) return fail(WDBX_E_STATE, "corpus too small for the batched path at k=%d", k);
+  uint32_t cap = selection_cap(s.expect, 32);
   // (a mask that allows few rows: room for ALL of them, so that tau = -inf -- no sampled block held an allowed row -- is
   // answered from the candidates, not by a repair scan per query; 16 384 rows = 32 MiB of candidate buffers)
   cap = std::max<uint32_t>(cap, (uint32_t)small_class);
@@ -2013,9 +1948,7 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
   if ((rc = grow((void**)&ix->d_qpar, &ix->qpar_bytes, (size_t)GB_N * sizeof(f4)))) return rc;
   // per-wave candidate pair lists of the full pass: room for 4x the expected share of a wave, at least 2048 pairs
   const uint32_t nwaves = std::min<uint32_t>(tiles, (uint32_t)ix->cu_count) * 8;
-  // (16384: two tiles' worth of "every row of the wave's group is a candidate for every query", so a few outlier groups
-  // do not turn the call into per-query repairs)
-  const uint32_t pair_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(16384, (uint64_t)GB_N * expect * 16 / nwaves), 1u << 16);
+  const uint32_t pair_cap = selection_pair_cap(s.expect, nwaves);
   if ((rc = grow((void**)&ix->d_pairs, &ix->pairs_bytes, (size_t)nwaves * pair_cap * sizeof(u64)))) return rc;
   if ((rc = grow((void**)&ix->d_pair_count, &ix->pair_count_bytes, (size_t)nwaves * sizeof(uint32_t)))) return rc;
   if (sharded && (rc = grow((void**)&ix->d_local_keys, &ix->local_keys_bytes, (size_t)GB_N * k * sizeof(u64)))) return rc;
@@ -2088,24 +2021,7 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
     }
     if ((rc = launch_gemm8<0>(ix, g, ct, false, multi))) return rc;
     // the k-th largest of the groups' LOWER bounds: a valid threshold by itself (no margin)
-    if (rw * sample_tiles <= KTH_R * 1024 && !ix->opt_lds_lists) {
-      KthArgs ka = {ix->d_halfmax, (u64)rw * sample_tiles, rw * sample_tiles, k, ix->d_tau};
-      if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
-      HIP_TRY(enqueue_kth(ix->stream, ka, nv));
-      if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
-    } else {
-      MergeArgs m = {};
-      m.in = ix->d_halfmax;
-      m.q_stride = (u64)rw * sample_tiles;
-      m.i_stride = 0;
-      m.p_stride = 1;
-      m.P = rw * sample_tiles;
-      m.list_len = 1;
-      m.k = k;
-      m.metric = ix->metric;
-      m.out_kth = ix->d_tau;
-      if ((rc = launch_merge(ix, m, nv))) return rc;
-    }
+    if ((rc = enqueue_sample_threshold(ix, rw * sample_tiles, k, nv, true))) return rc;
     if (multi) {  // the pad slots inside the block are padded queries
       hipLaunchKernelGGL(pad_tau_kernel, dim3((nv + 255) / 256), dim3(256), 0, ix->stream, ix->d_tau, mc->d_slot_query + q0, (uint32_t)nv);
       HIP_TRY(hipGetLastError());
@@ -2158,26 +2074,8 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
                        (const f4*)ix->d_rows, (uint32_t)pitch4, (const f4*)qsrc, ix->d_cand, (const uint32_t*)(ix->d_count + q0), cap,
                        (u64*)nullptr, (uint32_t*)nullptr);
     HIP_TRY(hipGetLastError());
-    MergeArgs f = {};
-    f.in = ix->d_cand;
-    f.q_stride = cap;
-    f.i_stride = 0;
-    f.p_stride = 1;
-    f.P = cap;
-    f.P_dev = ix->d_count + q0;
-    f.list_len = 1;
-    f.k = k;
-    f.metric = ix->metric;
-    if (keys_out) {  // keys with global rows for the caller's own exchange (the in-process shard group)
-      f.row_base = (uint32_t)ix->row_base;
-      f.out_keys = keys_out + (size_t)q0 * k;
-    } else if (sharded) {  // this shard's lists with global rows, then the exchange
-      f.row_base = (uint32_t)ix->row_base;
-      f.out_keys = ix->d_local_keys;
-    } else {
-      f.out_idx = d_out_idx + (size_t)q0 * k;
-      f.out_score = d_out_score + (size_t)q0 * k;
-    }
+    MergeArgs f = final_topk_args(ix, ix->d_cand, cap, ix->d_count + q0, k);
+    final_topk_output(ix, &f, keys_out, sharded, d_out_idx, d_out_score, q0, k);
     if ((rc = launch_merge(ix, f, nv))) return rc;
     if (multi) {
       // an overflowed query is repaired by the scan with ITS mask: the repair launches per class run, each with its class's

@@ -43,6 +43,8 @@
 //                           label the sum over a query's vectors of the vector's best key score, the labels ranked by that sum
 //   host_multivector.h      the rounds and segments of that call's vectors, its route, grids and scratch
 //   host_multimask.h        a call with one row mask per query: the placement of its queries in the int8 tiles' query blocks
+//   host_selection.h        the plan of the selection rounds: sampled tiles, stride, candidate and pair capacities of the tile paths and
+//                           the u8 / u6 rounds, the masked sample's growth, the 1 GiB shadow rule
 //   host_calls.h            what the blocking entry points share, device-free: allowed rows of a mask, padded query copies, the host
 //                           ranking of a lone query's keys, the class-by-class fallback loop
 //   host_index.h            the handle, kernel choice, the enqueue functions of every search path, and what the blocking entry
@@ -87,6 +89,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_calls.h"  // (device-free as well: mask popcount, padded query copies, host ranking of keys, class-by-class loop)
 #include "host_subset.h"  // (device-free as well: row-list validation, route and grid sizing of a search among listed rows)
 #include "host_multimask.h"  // (device-free as well: where the queries of a call with a mask per query sit in the tile blocks)
+#include "host_selection.h"  // (device-free as well: the sample, stride and capacities of the selection rounds)
 #include "host_labels.h"  // (device-free as well: label order, items, over-fetch walk, rounds and scratch of a distinct search)
 #include "host_multivector.h"  // (device-free as well: rounds, segments, route and scratch of a multi-vector search)
 #include "host_rowlists.h"  // (device-free as well: slots, rounds, query blocks and work items of a call with a row list per query)
