@@ -290,6 +290,50 @@ int wdbx_index_search_multivector(wdbx_index* idx,
                                   const uint32_t* mask_words, uint64_t mask_word_count, /* NULL = every row */
                                   int64_t* out_idx, float* out_score, uint32_t* out_label /* [nq, k]; out_label may be NULL */);
 
+/* ---- MMR search: a diversified top-k picked from the pool of the best rows ------ */
+/* Maximal marginal relevance (LangChain's max_marginal_relevance_search on every vector store; Qdrant, Milvus, Weaviate and
+ * Vespa ship it or a rerank stage for it; the reference has nothing: it cuts a top-k of rows, vector_store.py:323-345, and a
+ * distinct search only removes rows of one label): each of nq host queries [nq, dim] gets k rows picked greedily from its
+ * fetch_k best, every pick trading relevance against similarity to the rows already picked.  Blocking, host buffers; the
+ * call holds the handle's mutex to its end and nothing of it stays valid in the handle.  Both metrics.
+ *   Pool: query i's candidates are the exact top-fetch_k of the rows the mask allows (mask_words NULL = every row; else
+ *   mask_word_count words, at least ceil(rows / 32)): the answer of wdbx_index_search / wdbx_index_search_masked_n for
+ *   k' = fetch_k, reached through the internal entry those calls (and the distinct search's over-fetch) use.  Position
+ *   0 .. m - 1 is that ranking; rel_i is the returned score in the ranking domain (L2: the negated squared distance); m may be
+ *   below fetch_k (few eligible rows, -1 slots).  A NaN-scored row is never a candidate, as everywhere else.
+ *   Similarity: G[i][j] is the score of candidate row i with candidate row j's STORED row as the query, in exact_score's
+ *   arithmetic (lane order, fma chain, fold and xor tree as every exact score of this library), in the ranking domain.  So
+ *   G[i][j] is bit-identical to what wdbx_index_search_rows returns for row i with wdbx_index_get_rows(row j) as the query
+ *   (L2: negated), and G[i][j] == G[j][i] bit for bit: the products commute and the order of summation depends on the element
+ *   index only.  (A NaN similarity is NaN both ways; its sign and payload are not specified, and the selection ignores it.)
+ *   Selection: greedy, in fp32, no contraction -- every (x) and (-) below is ONE correctly rounded fp32 operation, never an
+ *   fma.  Pick 0 is position 0, its value lambda (x) rel_0.  Every candidate starts with maxsim_i = -inf; after each pick p,
+ *   maxsim_i = fmaxf(maxsim_i, G[p][i]), a NaN similarity ignored.  The next pick is the unpicked candidate with the largest
+ *       v_i = (lambda (x) rel_i) (-) ((1.0f (-) lambda) (x) maxsim_i);
+ *   ties (-0 and +0 are one value) go to the smaller position; a NaN v_i ranks below every non-NaN value, NaN values among
+ *   themselves by position.  Selection stops after min(k, m) picks.
+ *   Outputs [nq, k], in pick order: out_idx the row, out_score the row's relevance exactly as wdbx_index_search returned it
+ *   (L2: the positive squared distance), out_mmr (may be NULL) the value the pick won with.  Unused slots hold -1 / 0 / 0.  An
+ *   empty index: every slot -1, nothing launched.
+ *   Consequences: with lambda == 1.0f on finite rows the answer equals the first k columns of wdbx_index_search(.., fetch_k),
+ *   ids and score bits.  Answers are bit-identical from run to run: every word of G, every maxsim and every output slot has
+ *   one writer.
+ *   WDBX_E_INVALID: nq < 1, k outside [1, WDBX_MAX_K], fetch_k outside [k, WDBX_MAX_K], lambda NaN or outside [0, 1], a null
+ *   query or result buffer, a mask shorter than ceil(rows / 32) words (checked under the handle's lock).  A refused call leaves
+ *   the handle usable.
+ *   Rounds: the pool's row numbers come back to the host with the pool (as the distinct search's over-fetch hands them to its
+ *   host walk) and go up again as the gather's list.  A round holds as many consecutive queries as keep their gathered rows
+ *   ([sum m, row pitch]) and similarity squares (m x m floats each) within option "mmr_scratch_mib" MiB (default and largest
+ *   256, smallest 1; anything else is WDBX_E_INVALID); a query that passes it alone is a round of its own.  Per round: the
+ *   gather, one launch of the pairs kernel (one wave per candidate row, scored against blocks of 8 candidate columns), one
+ *   launch of the selection kernel (one workgroup per query).  The answer does not depend on the rounds.
+ *   get_option, read-only: "last_mmr_path" 0 nothing launched, 1 ran; "last_mmr_rounds" the rounds of the last call;
+ *   "last_mmr_candidates" the sum of m over the call's queries. */
+int wdbx_index_search_mmr(wdbx_index* idx, const float* queries, int nq, int k, int fetch_k, float lambda,
+                          int normalize_queries,
+                          const uint32_t* mask_words, uint64_t mask_word_count, /* NULL = every row */
+                          int64_t* out_idx, float* out_score, float* out_mmr /* [nq, k]; out_mmr may be NULL */);
+
 /* ---- range search: every row within a similarity, no k ----------------------- */
 /* every row whose score reaches thresholds[q] (cosine/IP: score >= t; L2: squared distance <= t), exact fp32,
  * per query sorted like wdbx_index_search; replaces faiss' IndexFlat range_search, which the reference never reaches

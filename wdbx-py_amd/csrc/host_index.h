@@ -207,6 +207,12 @@ struct wdbx_index {
   char* d_mv = nullptr;
   size_t mv_bytes = 0;
   int64_t last_multivector_rounds = 0, last_multivector_vectors = 0, last_multivector_labels = 0;
+  // MMR search (wdbx_index_search_mmr): one allocation of the largest round's state (host_mmr.h): the query table | the candidates'
+  // row numbers | their relevance | the picks' values | the gathered rows | the similarity squares
+  char* d_mmr = nullptr;
+  size_t mmr_bytes = 0;
+  int last_mmr_path = 0;  // 0 nothing launched, 1 ran
+  int64_t last_mmr_rounds = 0, last_mmr_candidates = 0;
   // profiling
   bool profile = false;
   EventPool scan_ev, merge_ev, gemm_ev, sample_ev;
@@ -218,7 +224,8 @@ struct wdbx_index {
           opt_gemm_ct = 0, opt_wg_merge = 1, opt_zero_copy = 1, opt_lone_host_select = 1, opt_lds_lists = 0,
           opt_merge_fast = 1, opt_poll_done = 1, opt_scan_one_grid = 1, opt_select_min_k = 200, opt_gemm_min_nq = 4, opt_gemm_min_rows = 65536, opt_gemm_min_work = 800000,
           opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0, opt_scan_u42 = -1, opt_gemm_masked = 1, opt_rows_keys_max = 8192, opt_distinct_overfetch = 4,
-          opt_multivector_round_vectors = 256, opt_range_batch_min_queries = 4, opt_range_pair_cap = 0;
+          opt_multivector_round_vectors = 256, opt_range_batch_min_queries = 4, opt_range_pair_cap = 0,
+          opt_mmr_scratch_mib = MMR_SCRATCH_MIB_MAX;
 };
 
 struct DeviceGuard {

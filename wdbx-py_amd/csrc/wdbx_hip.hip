@@ -42,6 +42,9 @@
 //   kernels_multivector.h   multivector_rank_kernel: the reduction and ranking of wdbx_index_search_multivector (late interaction): per
 //                           label the sum over a query's vectors of the vector's best key score, the labels ranked by that sum
 //   host_multivector.h      the rounds and segments of that call's vectors, its route, grids and scratch
+//   kernels_mmr.h           mmr_pairs_kernel, mmr_select_kernel: wdbx_index_search_mmr (maximal marginal relevance) behind its pool -- the
+//                           similarity square of a query's gathered candidates and the greedy selection over it
+//   host_mmr.h              that call's argument checks, pools, rounds and grids
 //   host_multimask.h        a call with one row mask per query: the placement of its queries in the int8 tiles' query blocks
 //   host_selection.h        the plan of the selection rounds: sampled tiles, stride, candidate and pair capacities of the tile paths and
 //                           the u8 / u6 rounds, the masked sample's growth, the 1 GiB shadow rule
@@ -93,6 +96,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_labels.h"  // (device-free as well: label order, items, over-fetch walk, rounds and scratch of a distinct search)
 #include "host_multivector.h"  // (device-free as well: rounds, segments, route and scratch of a multi-vector search)
 #include "host_rowlists.h"  // (device-free as well: slots, rounds, query blocks and work items of a call with a row list per query)
+#include "host_mmr.h"  // (device-free as well: argument checks, pools, rounds and grids of an MMR search)
 
 #define HIP_TRY(expr)                                                                        \
   do {                                                                                       \
@@ -130,6 +134,8 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 static_assert(LABEL_SPAN_DEV == LABEL_SPAN, "the kernels walk the spans the host built");
 #include "kernels_multivector.h"
 static_assert(MULTIVECTOR_MAX_VECTORS == WDBX_MAX_QUERY_VECTORS, "the plan's limit is the header's");
+#include "kernels_mmr.h"
+static_assert(MMR_MAX_POOL == WDBX_MAX_K, "a pool is a top-k answer");
 #include "host_index.h"
 #include "host_group.h"
 
@@ -148,7 +154,7 @@ static uint64_t device_bytes_resident(const wdbx_index* ix) {
   b += ix->qb8_bytes + ix->qpar_bytes + ix->pairs_bytes + ix->pair_count_bytes + ix->cnmax_bytes;
   b += ix->rcand_bytes + ix->rkeys_bytes + ix->rcnt_bytes + ix->rthr_bytes;
   b += ix->rows6_bytes + ix->count6_bytes + ix->rows42_bytes + ix->count42_bytes;
-  b += ix->sub_ids_bytes + ix->sub_keys_bytes + ix->mm_bytes + ix->rl_bytes + ix->lab_bytes + ix->mv_bytes;
+  b += ix->sub_ids_bytes + ix->sub_keys_bytes + ix->mm_bytes + ix->rl_bytes + ix->lab_bytes + ix->mv_bytes + ix->mmr_bytes;
   return b;
 }
 
@@ -226,7 +232,7 @@ void wdbx_index_destroy(wdbx_index* ix) try {
                     ix->d_state, ix->d_cn, ix->d_cnmax, ix->d_qb16, ix->d_rows16, ix->d_rows8, ix->d_scale8, ix->d_selsrc,
                     ix->d_gmax, ix->d_qn, ix->d_rows8g, ix->d_groups8, ix->d_gbad8, ix->d_gref8, ix->d_over_list, ix->d_qb8,
                     ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr, ix->d_rows6, ix->d_count6, ix->d_rows42, ix->d_count42,
-                    ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys, ix->d_mm, ix->d_rl, ix->d_lab, ix->d_mv};
+                    ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys, ix->d_mm, ix->d_rl, ix->d_lab, ix->d_mv, ix->d_mmr};
     for (void* p : bufs)
       if (p) (void)hipFree(p);
     if (ix->h_stage) (void)hipHostFree(ix->h_stage);
@@ -1342,6 +1348,121 @@ int wdbx_index_search_multivector(wdbx_index* ix, const float* vectors, const ui
   return WDBX_OK;
 } WDBX_CATCH
 
+// ---- MMR search: a diversified top-k picked greedily from the pool of the best rows (host_mmr.h, kernels_mmr.h, DESIGN.md
+// section 4.14) ----
+// Under the handle's mutex to its end.  The pool is the ordinary search for k' = fetch_k (search_host under the lock this call
+// took, as the distinct search's over-fetch); its row numbers and scores come back to the host, where the pools are measured and
+// the rounds planned (mmr_plan_rounds), and go up again per round as the gather's list and the relevance table.  Per round:
+// gather_rows_kernel into the round's contiguous rows, mmr_pairs_kernel (bracketed as a scan launch), mmr_select_kernel
+// (bracketed as a merge launch).  No memset: every word of G that is read and every output slot has been written.
+int wdbx_index_search_mmr(wdbx_index* ix, const float* queries, int nq, int k, int fetch_k, float lambda, int normalize_queries,
+                          const uint32_t* mask_words, uint64_t mask_word_count, int64_t* out_idx, float* out_score,
+                          float* out_mmr) try {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  const MmrArg bad = mmr_check_args(nq, k, fetch_k, lambda, queries && out_idx && out_score, WDBX_MAX_K);
+  if (bad != MMR_ARG_OK) return fail(WDBX_E_INVALID, "%s (nq=%d k=%d fetch_k=%d lambda=%g)", mmr_arg_message(bad), nq, k, fetch_k, (double)lambda);
+  std::unique_lock<std::mutex> lk(ix->mu);
+  DeviceGuard g(ix->device);
+  int rc;
+  const size_t elems = (size_t)nq * k;
+  ix->last_mmr_path = 0;
+  ix->last_mmr_rounds = ix->last_mmr_candidates = 0;
+  if (ix->n == 0) {  // every slot empty, nothing launched
+    for (size_t i = 0; i < elems; ++i) {
+      out_idx[i] = -1;
+      out_score[i] = 0.0f;
+      if (out_mmr) out_mmr[i] = 0.0f;
+    }
+    return WDBX_OK;
+  }
+  if (mask_words && (rc = check_mask_words(ix->n, mask_word_count))) return rc;
+  // the pool: the exact top-fetch_k, on the host
+  std::vector<int64_t> fi((size_t)nq * fetch_k);
+  std::vector<float> fs((size_t)nq * fetch_k);
+  if ((rc = search_host(ix, queries, nq, fetch_k, normalize_queries, mask_words, mask_word_count, fi.data(), fs.data(), &lk))) return rc;
+  const bool l2 = ix->metric == WDBX_METRIC_L2;
+  const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
+  std::vector<uint32_t> m((size_t)nq);
+  uint64_t total = 0;
+  for (int q = 0; q < nq; ++q) total += m[(size_t)q] = mmr_pool_size(fi.data() + (size_t)q * fetch_k, fetch_k);
+  const std::vector<MmrRound> rounds = mmr_plan_rounds(m.data(), nq, pitch4, (uint64_t)ix->opt_mmr_scratch_mib << 20);
+  // the largest round's layout: table | candidates | relevance | values | rows | G, each part on a 256-byte boundary
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  size_t max_nq = 0, max_rows = 0, max_g = 0;
+  for (const MmrRound& r : rounds) {
+    max_nq = std::max<size_t>(max_nq, r.nq);
+    max_rows = std::max<size_t>(max_rows, (size_t)r.rows);
+    max_g = std::max<size_t>(max_g, (size_t)r.g_floats);
+  }
+  const size_t off_cand = up(max_nq * sizeof(MmrQuery)), off_rel = off_cand + up(max_rows * sizeof(u64)),
+               off_val = off_rel + up(max_rows * sizeof(float)), off_rows = off_val + up(max_nq * (size_t)k * sizeof(float)),
+               off_g = off_rows + up(max_rows * (size_t)pitch4 * sizeof(f4)), need = off_g + up(max_g * sizeof(float));
+  if ((rc = grow((void**)&ix->d_mmr, &ix->mmr_bytes, need))) return rc;
+  if ((rc = ensure_out(ix, max_nq * (size_t)k))) return rc;
+  const mmr_pairs_fn pfn = pick_mmr_pairs(ix->metric, pitch4);
+  std::vector<MmrQuery> table;
+  std::vector<u64> cand;
+  std::vector<float> rel;
+  for (const MmrRound& r : rounds) {
+    mmr_round_queries(m.data(), r, &table);
+    cand.clear();
+    rel.clear();
+    for (uint32_t i = 0; i < r.nq; ++i) {
+      const size_t at = (size_t)(r.q0 + i) * fetch_k;
+      for (uint32_t c = 0; c < m[r.q0 + i]; ++c) {
+        cand.push_back((u64)fi[at + c]);
+        rel.push_back(l2 ? -fs[at + c] : fs[at + c]);
+      }
+    }
+    const MmrQuery* const d_table = (const MmrQuery*)ix->d_mmr;
+    u64* const d_cand = (u64*)(ix->d_mmr + off_cand);
+    float* const d_rel = (float*)(ix->d_mmr + off_rel);
+    float* const d_val = (float*)(ix->d_mmr + off_val);
+    f4* const d_gathered = (f4*)(ix->d_mmr + off_rows);
+    float* const d_g = (float*)(ix->d_mmr + off_g);
+    HIP_TRY(hipMemcpyAsync(ix->d_mmr, table.data(), table.size() * sizeof(MmrQuery), hipMemcpyHostToDevice, ix->stream));
+    if (r.rows) {
+      HIP_TRY(hipMemcpyAsync(d_cand, cand.data(), cand.size() * sizeof(u64), hipMemcpyHostToDevice, ix->stream));
+      HIP_TRY(hipMemcpyAsync(d_rel, rel.data(), rel.size() * sizeof(float), hipMemcpyHostToDevice, ix->stream));
+      if ((rc = record(ix->scan_ev, ix->profile, ix->stream, true))) return rc;
+      hipLaunchKernelGGL(gather_rows_kernel, dim3(mmr_gather_grid(r.rows)), dim3(256), 0, ix->stream, (const f4*)ix->d_rows, pitch4,
+                         (const u64*)d_cand, (u64)r.rows, d_gathered);
+      HIP_TRY(hipGetLastError());
+      MmrPairsArgs pa = {};
+      pa.rows = d_gathered;
+      pa.qs = d_table;
+      pa.G = d_g;
+      pa.pitch4 = pitch4;
+      const MmrGrid pg = mmr_pairs_grid(r);
+      hipLaunchKernelGGL(pfn, dim3(pg.x, pg.y, pg.z), dim3(256), 0, ix->stream, pa);
+      HIP_TRY(hipGetLastError());
+      if ((rc = record(ix->scan_ev, ix->profile, ix->stream, false, 2))) return rc;
+    }
+    MmrSelectArgs sa = {};
+    sa.qs = d_table;
+    sa.G = d_g;
+    sa.cand = d_cand;
+    sa.rel = d_rel;
+    sa.out_idx = ix->d_oidx;
+    sa.out_score = ix->d_oscore;
+    sa.out_mmr = d_val;
+    sa.lambda = lambda;
+    sa.k = k;
+    sa.negate = l2 ? 1 : 0;
+    if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
+    hipLaunchKernelGGL(mmr_select_kernel, dim3(r.nq), dim3(256), 0, ix->stream, sa);
+    HIP_TRY(hipGetLastError());
+    if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
+    const size_t o = (size_t)r.q0 * k, e = (size_t)r.nq * k;
+    if (out_mmr) HIP_TRY(hipMemcpyAsync(out_mmr + o, d_val, e * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+    if ((rc = download_results(ix, e, out_idx + o, out_score + o))) return rc;  // (waits: the host tables are rebuilt for the next round)
+  }
+  ix->last_mmr_path = 1;
+  ix->last_mmr_rounds = (int64_t)rounds.size();
+  ix->last_mmr_candidates = (int64_t)total;
+  return WDBX_OK;
+} WDBX_CATCH
+
 // ---- range search (range_u8_eligible, pick_range_scan: host_index.h) -------------------------------
 // The whole call holds the handle's mutex (like a masked search: the key buffers are the handle's).  Per round of up to 64
 // queries: [u8 path: memset counters, scan8_kernel<PHASE 2> -> candidates] -> memset, range_filter_kernel / range_scan_kernel
@@ -2447,6 +2568,7 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"multivector_round_vectors", &wdbx_index::opt_multivector_round_vectors},
     {"range_batch_min_queries", &wdbx_index::opt_range_batch_min_queries},
     {"range_pair_cap", &wdbx_index::opt_range_pair_cap},
+    {"mmr_scratch_mib", &wdbx_index::opt_mmr_scratch_mib},
 };
 
 static int64_t* option_slot(wdbx_index* ix, const char* name) { return find_option(ix, kOptions, name); }
@@ -2463,6 +2585,8 @@ int wdbx_index_set_option(wdbx_index* ix, const char* name, int64_t value) try {
   if (slot == &ix->opt_range_pair_cap && value != 0 && (value < (int64_t)RANGE_PAIR_CAP_MIN || value > (int64_t)RANGE_PAIR_CAP_MAX))
     return fail(WDBX_E_INVALID, "range_pair_cap %lld: 0 (the default sizing) or [%u, %u] pairs per wave", (long long)value,
                 RANGE_PAIR_CAP_MIN, RANGE_PAIR_CAP_MAX);
+  if (slot == &ix->opt_mmr_scratch_mib && (value < 1 || value > MMR_SCRATCH_MIB_MAX))
+    return fail(WDBX_E_INVALID, "mmr_scratch_mib %lld outside [1, %lld]", (long long)value, (long long)MMR_SCRATCH_MIB_MAX);
   *slot = value;
   if (!strcmp(name, "group_bounds")) ix->gmax_valid = false;  // re-decide (and rebuild the group maxima) at the next batch
   return WDBX_OK;
@@ -2524,6 +2648,9 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "last_multivector_rounds")) return *value = ix->last_multivector_rounds, WDBX_OK;
   if (name && !strcmp(name, "last_multivector_vectors")) return *value = ix->last_multivector_vectors, WDBX_OK;
   if (name && !strcmp(name, "last_multivector_labels")) return *value = ix->last_multivector_labels, WDBX_OK;
+  if (name && !strcmp(name, "last_mmr_path")) return *value = ix->last_mmr_path, WDBX_OK;
+  if (name && !strcmp(name, "last_mmr_rounds")) return *value = ix->last_mmr_rounds, WDBX_OK;
+  if (name && !strcmp(name, "last_mmr_candidates")) return *value = ix->last_mmr_candidates, WDBX_OK;
   if (name && !strcmp(name, "last_sample_qn")) return *value = ix->last_sample_qn, WDBX_OK;
   if (name && !strcmp(name, "last_batch_repaired")) return *value = ix->last_batch_repaired ? 1 : 0, WDBX_OK;
   if (name && !strcmp(name, "last_batch_masked")) return *value = ix->last_batch_masked, WDBX_OK;

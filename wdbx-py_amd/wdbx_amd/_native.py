@@ -74,6 +74,8 @@ SIGNATURES = {
                                              _i64p, _f32p, C.POINTER(C.c_uint32)]),
     "wdbx_index_search_multivector": (C.c_int, [C.c_void_p, _f32p, _u64p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32),
                                                 C.c_uint64, _i64p, _f32p, C.POINTER(C.c_uint32)]),
+    "wdbx_index_search_mmr": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
+                                        C.POINTER(C.c_uint32), C.c_uint64, _i64p, _f32p, _f32p]),
     "wdbx_index_range_search": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
                                           C.c_uint64, _u64p, _i64p, _f32p]),
     "wdbx_index_range_search_batch": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
@@ -442,6 +444,27 @@ class NativeIndex:
                                                        idx.ctypes.data_as(_i64p), score.ctypes.data_as(_f32p),
                                                        label.ctypes.data_as(u32p)))
         return idx, score, label
+
+    def search_mmr(self, queries, k: int, fetch_k: int, lambda_mult: float, normalize_queries: bool = False,
+                   mask: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Maximal marginal relevance: per query ``k`` rows picked greedily from its exact top-``fetch_k``, each pick the
+        candidate with the largest ``lambda_mult * relevance - (1 - lambda_mult) * (largest similarity to a row already
+        picked)`` (fp32, include/wdbx_hip.h states every rounding).  Returns ``(rows int64, scores f32, mmr f32)``, each
+        ``[nq, k]`` in pick order: the row, its relevance as :meth:`search` returns it, the value it won with; unused slots
+        hold -1 / 0 / 0.  ``mask``: uint32 words as in :meth:`search` (``mask_words``)."""
+        q = _as_f32(queries, self.dim)
+        nq = q.shape[0]
+        idx = np.empty((nq, int(k)), np.int64)
+        score = np.empty((nq, int(k)), np.float32)
+        mmr = np.empty((nq, int(k)), np.float32)
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint32)
+        # (nq, k, fetch_k, lambda and the mask's length are checked by the library, the length under the handle's lock)
+        _check(self._lib.wdbx_index_search_mmr(self._h, q.ctypes.data_as(_f32p), nq, int(k), int(fetch_k), float(lambda_mult),
+                                               int(normalize_queries),
+                                               None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                               0 if m is None else m.size, idx.ctypes.data_as(_i64p), score.ctypes.data_as(_f32p),
+                                               mmr.ctypes.data_as(_f32p)))
+        return idx, score, mmr
 
     def range_search(self, queries, thresholds, normalize_queries: bool = False,
                      mask_words: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:

@@ -60,8 +60,28 @@ async def search_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
     (extension; absent, null or false = the plain search): at most one result per value of the store's ``DISTINCT_KEY``
     metadata field (``wdbx.vector_search_distinct_async``).  ``"query_vectors": [[...], ...]`` (extension, in place of
     ``query_vector``): a query of several vectors, the documents ranked by late interaction
-    (``wdbx.vector_search_multivector_async``); not together with ``query_vector`` or ``distinct``."""
+    (``wdbx.vector_search_multivector_async``); not together with ``query_vector`` or ``distinct``.  ``"mmr": {"lambda": 0.5,
+    "fetch_k": 40}`` (extension; absent or null = the plain search; both members optional, ``lambda`` in [0, 1], ``fetch_k``
+    an integer >= ``limit`` or null): the results are picked by maximal marginal relevance from the ``fetch_k`` best and come
+    in pick order (``wdbx.vector_search_mmr_async``); not together with ``distinct`` or ``query_vectors``."""
     limit, threshold, flt = _parse_common(payload)
+    mmr = payload.get("mmr")
+    if mmr is not None:
+        if not isinstance(mmr, dict) or set(mmr) - {"lambda", "fetch_k"}:
+            raise ValueError('mmr must be an object with the members "lambda" and "fetch_k"')
+        if payload.get("distinct") or payload.get("query_vectors") is not None:
+            raise ValueError("mmr goes with query_vector alone: neither distinct nor query_vectors")
+        lam = mmr.get("lambda", 0.5)
+        lam = 0.5 if lam is None else lam
+        if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not 0.0 <= lam <= 1.0:
+            raise ValueError("mmr.lambda must be a number in [0, 1]")
+        fetch_k = mmr.get("fetch_k")
+        if fetch_k is not None and (isinstance(fetch_k, bool) or not isinstance(fetch_k, int) or fetch_k < limit):
+            raise ValueError("mmr.fetch_k must be an integer >= limit, or null")
+        if "query_vector" not in payload:
+            raise ValueError("query_vector is required")
+        query = _vector(payload["query_vector"], "query_vector")
+        return _render(await wdbx.vector_search_mmr_async(query, limit, fetch_k, float(lam), threshold, flt))
     if payload.get("query_vectors") is not None:
         if "query_vector" in payload or payload.get("distinct"):
             raise ValueError("query_vectors stands alone: neither query_vector nor distinct goes with it")

@@ -875,6 +875,30 @@ class HipFlatIndex(VectorIndex):
                 return []
             raise
 
+    def search_mmr(self, query_vector: np.ndarray, limit: int = 10, fetch_k: Optional[int] = None, lambda_mult: float = 0.5,
+                   mask=None) -> List[Tuple[str, float, float]]:
+        """Maximal marginal relevance over this shard: ``limit`` vectors picked greedily from the exact top-``fetch_k``
+        (default ``min(MAX_K, 4 * limit)``), in pick order: ``[(id, score, mmr value)]``, scores as ``search`` returns them.
+        ``mask`` as ``search``'s ``row_mask`` (bool per row or uint32 words).  Errors are swallowed or raised as in
+        ``search``."""
+        try:
+            actual_limit = min(int(limit), _native.MAX_K)
+            if self.next_index == 0 or actual_limit <= 0:
+                return []
+            pool = min(_native.MAX_K, 4 * actual_limit) if fetch_k is None else min(max(int(fetch_k), actual_limit), _native.MAX_K)
+            q = self._prepare(query_vector)
+            words = None
+            if mask is not None:
+                words = mask if mask.dtype == np.uint32 else _native.pack_row_mask(mask)
+            idx, score, mmr = self._native.search_mmr(q, actual_limit, pool, float(lambda_mult), mask=words)
+            keep = idx[0] != -1
+            return [(vid, s, float(v)) for (vid, s), v in zip(self._map(idx[0], score[0]), mmr[0][keep])]
+        except Exception as e:
+            logger.error("Error in HIP MMR search: %s", e)
+            if self.swallow_errors:
+                return []
+            raise
+
     async def search_async(self, query_vector: np.ndarray, limit: int = 10) -> List[Tuple[str, float]]:
         loop = asyncio.get_event_loop()
         return await loop.run_in_executor(self.thread_pool, self.search, query_vector, limit)

@@ -1173,6 +1173,44 @@ class VectorStore:
         return await loop.run_in_executor(self.thread_pool, lambda: self.search_multivector(
             query_vectors, limit=limit, threshold=threshold, filter_metadata=filter_metadata))
 
+    # ---- MMR search (extension: a diversified top-limit picked from the pool of the best vectors) ----
+    def search_mmr(self, query_vector: List[float], limit: int = 10, fetch_k: Optional[int] = None, lambda_mult: float = 0.5,
+                   threshold: float = 0.0, filter_metadata: Optional[Dict[str, Any]] = None) -> List[Result]:
+        """Maximal marginal relevance: ``limit`` vectors picked greedily from the ``fetch_k`` best (default
+        ``min(WDBX_MAX_K, 4 * limit)``), each pick the candidate with the largest ``lambda_mult * relevance - (1 -
+        lambda_mult) * (its largest similarity to a vector already picked)`` -- ten near-identical chunks no longer fill the
+        answer.  Returned in PICK order as ``(vector_id, score, metadata)``, scores as ``search`` returns them.
+        ``filter_metadata`` always travels as the row mask, so the pool holds matching vectors only; ``threshold`` drops the
+        picks whose relevance is below it, as in ``search``.  One shard only: the pairwise similarities need both rows on
+        one device, and a pick depends on every earlier pick, so per-shard answers do not compose; cross-shard MMR is out of
+        scope."""
+        if len(self.indices) != 1:
+            raise ValueError(
+                f"search_mmr needs a store of one shard, this one has {len(self.indices)}: the similarity of two candidates "
+                "needs both rows on one device, and per-shard selections do not compose")
+        query = _as_query(query_vector)
+        if query.shape != (self.vector_dim,):
+            raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {query.shape}")
+        if not 0.0 <= float(lambda_mult) <= 1.0:
+            raise ValueError(f"lambda_mult must lie in [0, 1], got {lambda_mult}")
+        if fetch_k is not None and int(fetch_k) < int(limit):
+            raise ValueError(f"fetch_k={fetch_k} is below limit={limit}")
+        mask = self._row_masks(filter_metadata)[0] if filter_metadata else None
+        out = []
+        for vid, score, _ in self.indices[0].search_mmr(query, limit, fetch_k=fetch_k, lambda_mult=lambda_mult, mask=mask):
+            if threshold > 0 and score < threshold:
+                continue  # (pick order is not score order: a later pick may still pass)
+            out.append((vid, score, self.metadata.get(vid, {})))
+        return out[:limit]
+
+    async def search_mmr_async(self, query_vector: List[float], limit: int = 10, fetch_k: Optional[int] = None,
+                               lambda_mult: float = 0.5, threshold: float = 0.0,
+                               filter_metadata: Optional[Dict[str, Any]] = None) -> List[Result]:
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(self.thread_pool, lambda: self.search_mmr(
+            query_vector, limit=limit, fetch_k=fetch_k, lambda_mult=lambda_mult, threshold=threshold,
+            filter_metadata=filter_metadata))
+
     # ---- range search (extension: every vector within a similarity, no limit) ----
     def search_range(self, query_vector: List[float], threshold: float,
                      filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,

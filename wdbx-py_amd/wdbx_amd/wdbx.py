@@ -181,6 +181,24 @@ class WDBX:
         return await self.vector_store.search_multivector_async(query_vectors, limit=limit, threshold=threshold,
                                                                 filter_metadata=filter_metadata)
 
+    def vector_search_mmr(self, query_vector: List[float], limit: int = 10, fetch_k: Optional[int] = None,
+                          lambda_mult: float = 0.5, threshold: float = 0.0,
+                          filter_metadata: Optional[Dict[str, Any]] = None) -> List[Result]:
+        """Extension: maximal marginal relevance.  ``limit`` vectors picked greedily from the ``fetch_k`` best (default
+        ``min(2048, 4 * limit)``), trading relevance (weight ``lambda_mult``) against similarity to the vectors already
+        picked; returned in pick order.  A filter is pushed down; a store of one shard only (``VectorStore.search_mmr`` says
+        why)."""
+        self._check_dim(query_vector)
+        return self.vector_store.search_mmr(query_vector, limit=limit, fetch_k=fetch_k, lambda_mult=lambda_mult,
+                                            threshold=threshold, filter_metadata=filter_metadata)
+
+    async def vector_search_mmr_async(self, query_vector: List[float], limit: int = 10, fetch_k: Optional[int] = None,
+                                      lambda_mult: float = 0.5, threshold: float = 0.0,
+                                      filter_metadata: Optional[Dict[str, Any]] = None) -> List[Result]:
+        self._check_dim(query_vector)
+        return await self.vector_store.search_mmr_async(query_vector, limit=limit, fetch_k=fetch_k, lambda_mult=lambda_mult,
+                                                        threshold=threshold, filter_metadata=filter_metadata)
+
     def vector_search_range(self, query_vector: List[float], threshold: float,
                             filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,
                             max_results: Optional[int] = None) -> List[Result]:
