@@ -122,6 +122,7 @@ struct wdbx_index {
   uint32_t* d_count42 = nullptr;  // rows that passed the four-bit bound, per query of the last round
   size_t count42_bytes = 0;
   int last_single_u42 = 0;     // 1: the last u6 round's full passes ran over the split planes
+  int last_u42_share = 0;      // ... the widest group of queries that shared one read of the four-bit plane in the last call (0: none ran)
   uint32_t* defer_flag_dev = nullptr;  // non-null during a blocking call that repairs overflow itself (mapped host word)
   // a lone blocking call through a staging slot: the LAST kernel of its chain writes done_seq into done_flag_dev (a mapped
   // host word of the slot) and the caller polls that word instead of waiting on the runtime; done_signals counts the launches
@@ -223,7 +224,7 @@ struct wdbx_index {
           opt_gemm8_refine = 1, opt_scan8_sample4 = 1, opt_gemm_l2 = 1, opt_gemm_l2_i8 = 1, opt_force_ragged = 0,
           opt_gemm_ct = 0, opt_wg_merge = 1, opt_zero_copy = 1, opt_lone_host_select = 1, opt_lds_lists = 0,
           opt_merge_fast = 1, opt_poll_done = 1, opt_scan_one_grid = 1, opt_select_min_k = 200, opt_gemm_min_nq = 4, opt_gemm_min_rows = 65536, opt_gemm_min_work = 800000,
-          opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0, opt_scan_u42 = -1, opt_gemm_masked = 1, opt_rows_keys_max = 8192, opt_distinct_overfetch = 4,
+          opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0, opt_scan_u42 = -1, opt_scan_u42_share = -1, opt_gemm_masked = 1, opt_rows_keys_max = 8192, opt_distinct_overfetch = 4,
           opt_multivector_round_vectors = 256, opt_range_batch_min_queries = 4, opt_range_pair_cap = 0,
           opt_mmr_scratch_mib = MMR_SCRATCH_MIB_MAX;
 };
@@ -784,6 +785,7 @@ static int enqueue_search(wdbx_index* ix, const float* d_queries, int nq, int k,
   }
 
   u64* const lbase = keys_dst ? keys_dst : ix->d_local_keys;  // (keys_only: one batch, so offsets within it are offsets in keys_dst)
+  ix->last_u42_share = 0;
   for (int q0 = 0; q0 < nq; q0 += batch) {
     const int b = std::min(batch, nq - q0);
     u64* const lkeys = lbase ? lbase + (size_t)(q0 % xch) * k : nullptr;  // this round's lists inside the exchange chunk
@@ -1345,11 +1347,19 @@ static bool prepare_u42_shadow(wdbx_index* ix) {
   return true;
 }
 
+// queries per read of the four-bit plane where option scan_u42_share leaves it to the library.  10 M x 384, 2000 steps, whole
+// steps, means of three at 3 workgroups per CU: 1 -> 3095.7 q/s (the lone passes), 2 -> 5186.4, 4 -> 7039.7
+// (profiles/u42_share/README.md, sweep_share/)
+constexpr uint32_t U42_SHARE_DEFAULT = 4;
+
 // nq single queries of a round, each with its own full pass over the u6 shadow: sample (4 queries per workgroup) ->
 // thresholds -> a pass per query -> exact re-scoring (rescore_kernel, as behind the u8 scan) -> cut -> final top-k.
 // The candidate counters live in d_count6; d_count[0 .. nq) are the CUT's counters against last_batch_cap = its capacity, and
 // end above it for a query whose candidate buffer or short list overflowed: what the callers' repair launches test.
 // u42: the full passes run over the split planes instead (scan_u42_kernel); everything in front of and behind them is the same.
+// There up to scan_u42_share consecutive queries of the round make their pass TOGETHER: one read and one unpack of the four-bit
+// plane and of {s, a4} per group (u42_share_groups).  Still the query's own: its fp32 query, threshold, bounds, survivors, refine,
+// candidates and counters -- its answer is bit for bit that of a pass of its own.
 static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, int k, int64_t* d_out_idx, float* d_out_score,
                               u64* keys_out, bool u42) {
   const uint32_t units = (uint32_t)ix->pitch / 16;
@@ -1357,8 +1367,12 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
   scan6_fn f0 = pick_scan6(uc, true), f1 = pick_scan6(uc, false);
   if (!f0 || !f1) return fail(WDBX_E_STATE, "no u6 scan instance for %u units", units);
   if (!ix->d_rows6 || ix->units6 != units || ix->shadow6_rows < ix->n) return fail(WDBX_E_STATE, "u6 shadow not prepared");
-  const scan42_fn f42 = u42 ? pick_scan42(u42_unit_chunk(units / 2)) : nullptr;
-  if (u42 && (!f42 || !ix->d_rows42 || ix->units42 != units / 2 || ix->shadow42_rows < ix->n))
+  // option scan_u42_share: how many queries of a round share one read of the four-bit plane (-1: U42_SHARE_DEFAULT; 1: none)
+  const uint32_t share = ix->opt_scan_u42_share == 1 || ix->opt_scan_u42_share == 2 || ix->opt_scan_u42_share == 4
+                             ? (uint32_t)ix->opt_scan_u42_share : U42_SHARE_DEFAULT;
+  scan42_fn f42[5] = {};  // by group width: 1, 2, 4
+  for (int w = 1; u42 && w <= 4; w *= 2) f42[w] = pick_scan42(u42_unit_chunk(units / 2), w);
+  if (u42 && (!f42[1] || !f42[2] || !f42[4] || !ix->d_rows42 || ix->units42 != units / 2 || ix->shadow42_rows < ix->n))
     return fail(WDBX_E_STATE, "split planes not prepared");
   int rc;
   // the plan (host_selection.h): sampled 256-row tiles of 4 groups of 64 rows each and the divisor of the u8 scan
@@ -1386,8 +1400,14 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
   // The split planes' pass, same corpus: 1 -> 1879, 2 -> 2885, 3 -> 3028, 4 -> 2959, 6 -> 2885 (profiles/u42/README.md): a wave
   // holds 6 KiB in flight as before but computes longer per byte, so a third workgroup still fills gaps.  With the packed
   // converts: 1 -> 1991, 2 -> 3005, 3 -> 3032 (mean of six), 4 -> 2935, 6 -> 2929 (profiles/u42_pipe/README.md)
-  const uint32_t wgs = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(ix->opt_scan8_wgs > 0 ? ix->opt_scan8_wgs : u42 ? 3 : 2, 8));
-  const uint32_t grid1 = scan_full_grid(tiles64, (uint32_t)ix->cu_count, wgs);
+  // Groups that share a read compute longer still per byte, 2000 steps: four queries per read 2 -> 6469, 3 -> 7057, 4 -> 7097,
+  // 6 -> 6844 (means of three, spreads 8 / 30 / 18 / 22); two per read 2 -> 4855, 3 -> 5186, 4 -> 5279, 6 -> 4400
+  // (profiles/u42_share/README.md): 4 for them, 3 stays for the lone passes of a round's remainder
+  const auto wgs_of = [&](uint32_t width) {
+    return (uint32_t)std::max<int64_t>(1, std::min<int64_t>(ix->opt_scan8_wgs > 0 ? ix->opt_scan8_wgs : !u42 ? 2 : width > 1 ? 4 : 3, 8));
+  };
+  const uint32_t grid1 = scan_full_grid(tiles64, (uint32_t)ix->cu_count, wgs_of(1));
+  const uint32_t grid_shared = scan_full_grid(tiles64, (uint32_t)ix->cu_count, wgs_of(2));
   const uint32_t grid0 = scan_sample_grid(ngroups, (uint32_t)ix->cu_count);
   const size_t pitch4 = ix->pitch / 4;
   const Scan8Shape* sh = scan8_shape((uint32_t)ix->dim);
@@ -1419,8 +1439,8 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
     HIP_TRY(hipGetLastError());
     if ((rc = record(ix->sample_ev, ix->profile, ix->stream, false))) return rc;
     if ((rc = enqueue_sample_threshold(ix, ngroups, k, nv, true))) return rc;
-    // the full passes: every query makes its own pass over all rows (one grid on small shards, as the u8 scan); one event
-    // pair around them, the profile reports elapsed / passes
+    // the full passes: every query makes its own pass over all rows, on the split planes together with up to three neighbours
+    // (one grid on small shards, as the u8 scan); one event pair around them, the profile reports elapsed / nv passes
     if ((rc = record(ix->gemm_ev, ix->profile, ix->stream, true))) return rc;
     if (u42) {
       Scan42Args b = {};
@@ -1434,15 +1454,22 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
       b.cap = cap;
       // (the survivors are counted for the probes only: an atomic per 64 of them)
       HIP_TRY(hipMemsetAsync(ix->d_count42, 0, (size_t)nv * sizeof(uint32_t), ix->stream));
-      const bool grid_y = one_grid && nv > 1;
-      for (int i = 0; i < (grid_y ? 1 : nv); ++i) {
+      // the groups that share a read (host_selection.h): a launch per group, or (one grid) per run of groups of one width
+      uint32_t first[ROUND], width[ROUND];
+      const uint32_t ng = u42_share_groups((uint32_t)nv, share, first, width);
+      for (uint32_t g = 0; g < ng;) {
+        uint32_t run = 1;
+        while (one_grid && g + run < ng && width[g + run] == width[g]) ++run;
+        const uint32_t i = first[g];
         b.query = qsrc + (size_t)i * ix->pitch;
         b.tau = ix->d_tau + i;
         b.cand = ix->d_cand + (size_t)i * cap;
         b.count = ix->d_count6 + i;
         b.survivors = ix->d_count42 + i;
-        hipLaunchKernelGGL(f42, dim3(grid1, grid_y ? nv : 1), dim3(256), 0, ix->stream, b);
+        hipLaunchKernelGGL(f42[width[g]], dim3(width[g] > 1 ? grid_shared : grid1, run), dim3(256), 0, ix->stream, b);
         HIP_TRY(hipGetLastError());
+        ix->last_u42_share = std::max(ix->last_u42_share, (int)width[g]);
+        g += run;
       }
     } else if (one_grid && nv > 1) {
       hipLaunchKernelGGL(f1, dim3(grid1, nv), dim3(256), 0, ix->stream, a);

@@ -83,6 +83,18 @@ static inline uint32_t selection_pair_cap(uint64_t expect, uint32_t nwaves) {
   return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(16384, (uint64_t)SELECTION_BLOCK_QUERIES * expect * 16 / nwaves), 1u << 16);
 }
 
+// The split planes' full passes of a round (kernels_scan42.h): up to qp (1, 2 or 4) consecutive queries share one read of the
+// four-bit plane.  The round's nv queries go as nv / qp groups of qp; what is left goes as one group of 2 and / or one lone
+// query (5 at qp = 4: {0 .. 3} {4}; 7: {0 .. 3} {4, 5} {6}) -- no dummy query is scanned, at most two groups are narrower than
+// qp.  first[i], width[i]: group i's first query and its number of queries (a width the kernel has an instance for); both hold
+// nv entries at least.  Returns the number of groups.
+static inline uint32_t u42_share_groups(uint32_t nv, uint32_t qp, uint32_t* first, uint32_t* width) {
+  uint32_t n = 0, at = 0;
+  for (uint32_t w = qp >= 4 ? 4 : qp >= 2 ? 2 : 1; w >= 1; w /= 2)
+    for (; nv - at >= w; at += w) first[n] = at, width[n++] = w;
+  return n;
+}
+
 // "the u8 shadow exceeds 1 GiB": the size from which a pass per launch is the rule (u8_pitch bytes per row).  The u6 and u42
 // scans are taken by size above it, a round's passes go out as one grid up to it.
 static inline bool shadow_over_1gib(uint64_t n_rows, uint32_t u8_pitch) { return n_rows * u8_pitch > (1ull << 30); }

@@ -149,33 +149,57 @@ __device__ __forceinline__ void u42_refine(const Scan42Args& a, cfloat* q, U42Li
 }
 
 // full pass: UC units in flight per wave (a last, shorter chunk when UC does not divide the row's units), one 64-row tile per
-// wave at a time
-template <int UC>
+// wave at a time.  QP consecutive queries of the round (blockIdx.y = the group) share the wave's loads: the unit loads, the
+// {s, a4} load and the unpack of every dword happen once, the four packed fmas follow once per query with that query's scalar
+// operands in the lone pass's order of t and of a0 / a1.  Everything behind the sum -- threshold, bounds, survivor list, refine,
+// stage, candidate buffer and counters -- is the query's own, so P', w, m, the survivors and the candidate keys of a query are
+// bit for bit what its lone pass (QP = 1) computes; only the order in which waves append to a buffer differs, as it does from
+// run to run.  LDS: QP x (4 KiB stage + 6 KiB lists) per workgroup.
+// QP = 1 is the kernel as it was before the parameter existed in its vector instructions (at UC = 6: 128 packed fmas, 128
+// packed converts, 60 VGPRs, the same loop), NOT in its scalar bookkeeping: six more scalar instructions in the prologue and
+// another register assignment.  The per-query state lives in arrays here (a copy of the arguments per query, aq[j] = a plus
+// the pointer adds, where the lone kernel advanced `a` in place); indexing the survivor lists directly instead of through
+// ls[] did not bring the old code back, nothing else was tried.  Measured, the instance runs at the old kernel's rate
+// (profiles/u42_share/README.md).
+template <int UC, int QP = 1>
 __global__ __launch_bounds__(256) void scan_u42_kernel(Scan42Args a) {
-  __shared__ u64 stage42[4][128];
-  __shared__ U42List list42[4];
+  __shared__ u64 stage42[QP][4][128];
+  __shared__ U42List list42[QP][4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const float* qg = a.query + (size_t)blockIdx.y * a.qpitch;
-  cfloat* q = (cfloat*)qg;
-  a.tau += blockIdx.y;
-  a.cand += (size_t)blockIdx.y * a.cap;
-  a.count += blockIdx.y;
-  if (a.survivors) a.survivors += blockIdx.y;
-  float qsum32, q1, q2;
-  u6_query_sums(qg, a.units * 32, lane, qsum32, q1, q2);
-  const float qsum305 = 30.5f * (qsum32 * 0.03125f);
-  const float thr = a.tau[0];
-  const float round1 = fmaf(6e-6f * (float)(a.units * 32 + 8), q1, (float)(a.units * 32) * 0x1p-138f);
-  WaveStage st = {stage42[wave], 0u};
-  U42List& ls = list42[wave];
-  uint32_t fill = 0;
+  Scan42Args aq[QP];  // (the query's own tau, cand, count and survivors; the planes are the group's)
+  cfloat* q[QP];
+  float qsum32[QP], qsum305[QP], q2[QP], thr[QP], round1[QP];
+  WaveStage st[QP];
+  U42List* ls[QP];
+  uint32_t fill[QP];
+#pragma unroll
+  for (int j = 0; j < QP; ++j) {
+    const uint32_t qi = blockIdx.y * QP + j;
+    const float* qg = a.query + (size_t)qi * a.qpitch;
+    q[j] = (cfloat*)qg;
+    aq[j] = a;
+    aq[j].tau += qi;
+    aq[j].cand += (size_t)qi * a.cap;
+    aq[j].count += qi;
+    if (a.survivors) aq[j].survivors += qi;
+    float q1;
+    u6_query_sums(qg, a.units * 32, lane, qsum32[j], q1, q2[j]);
+    qsum305[j] = 30.5f * (qsum32[j] * 0.03125f);
+    thr[j] = aq[j].tau[0];
+    round1[j] = fmaf(6e-6f * (float)(a.units * 32 + 8), q1, (float)(a.units * 32) * 0x1p-138f);
+    st[j] = {stage42[j][wave], 0u};
+    ls[j] = &list42[j][wave];
+    fill[j] = 0;
+  }
   const uint32_t tiles = (a.n_rows + 63) / 64;
   const size_t tile_dw = (size_t)a.units * 256;
   for (uint32_t tile = blockIdx.x * 4 + wave; tile < tiles; tile += gridDim.x * 4) {
     const uint32_t row = tile * 64 + (uint32_t)lane;
     const uint32_t* p = a.hcodes + tile * tile_dw + lane * 4;
     const f2v sa = __builtin_nontemporal_load(a.sa4 + min(row, a.n_rows - 1));
-    f2v a0 = {0.f, 0.f}, a1 = {0.f, 0.f};
+    f2v a0[QP], a1[QP];
+#pragma unroll
+    for (int j = 0; j < QP; ++j) a0[j] = f2v{0.f, 0.f}, a1[j] = f2v{0.f, 0.f};
     for (uint32_t u0 = 0; u0 < a.units; u0 += UC) {
       u4v v[UC];
 #pragma unroll
@@ -183,34 +207,43 @@ __global__ __launch_bounds__(256) void scan_u42_kernel(Scan42Args a) {
 #pragma unroll
       for (int u = 0; u < UC; ++u) {
         if (u0 + u < a.units) {  // (wave-uniform)
-          cfloat* qu = q + (u0 + u) * 32;
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
             f2v f[4];
             u42_unpack8(v[u][t], f);
-            a0 = __builtin_elementwise_fma(f[0], f2v{qu[8 * t], qu[8 * t + 1]}, a0);
-            a1 = __builtin_elementwise_fma(f[1], f2v{qu[8 * t + 2], qu[8 * t + 3]}, a1);
-            a0 = __builtin_elementwise_fma(f[2], f2v{qu[8 * t + 4], qu[8 * t + 5]}, a0);
-            a1 = __builtin_elementwise_fma(f[3], f2v{qu[8 * t + 6], qu[8 * t + 7]}, a1);
+#pragma unroll
+            for (int j = 0; j < QP; ++j) {
+              cfloat* qu = q[j] + (u0 + u) * 32;
+              a0[j] = __builtin_elementwise_fma(f[0], f2v{qu[8 * t], qu[8 * t + 1]}, a0[j]);
+              a1[j] = __builtin_elementwise_fma(f[1], f2v{qu[8 * t + 2], qu[8 * t + 3]}, a1[j]);
+              a0[j] = __builtin_elementwise_fma(f[2], f2v{qu[8 * t + 4], qu[8 * t + 5]}, a0[j]);
+              a1[j] = __builtin_elementwise_fma(f[3], f2v{qu[8 * t + 6], qu[8 * t + 7]}, a1[j]);
+            }
           }
         }
       }
     }
-    const float p4 = (a0.x + a0.y) + (a1.x + a1.y);  // = 2^-9 P
-    const float w = sa.x * (2048.0f * p4 - qsum305);
-    const float m = fmaf(sa.y, q2, sa.x * round1);
-    // (as the u6 pass: a NaN bound keeps the row, a negative scale marks a row with a NaN element)
-    const bool surv = row < a.n_rows && !(sa.x < 0.f) && !(w + m < thr);
-    const u64 bal = __ballot(surv);
-    if (bal) {
-      const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-      if (surv) ls.row[fill + rank] = row, ls.p[fill + rank] = p4, ls.s[fill + rank] = sa.x;
-      fill += (uint32_t)__popcll(bal);
-      if (fill >= 64) u42_refine(a, q, ls, fill, 64u, qsum32, q2, round1, thr, st, lane);
+#pragma unroll
+    for (int j = 0; j < QP; ++j) {
+      const float p4 = (a0[j].x + a0[j].y) + (a1[j].x + a1[j].y);  // = 2^-9 P
+      const float w = sa.x * (2048.0f * p4 - qsum305[j]);
+      const float m = fmaf(sa.y, q2[j], sa.x * round1[j]);
+      // (as the u6 pass: a NaN bound keeps the row, a negative scale marks a row with a NaN element)
+      const bool surv = row < a.n_rows && !(sa.x < 0.f) && !(w + m < thr[j]);
+      const u64 bal = __ballot(surv);
+      if (bal) {
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+        if (surv) ls[j]->row[fill[j] + rank] = row, ls[j]->p[fill[j] + rank] = p4, ls[j]->s[fill[j] + rank] = sa.x;
+        fill[j] += (uint32_t)__popcll(bal);
+        if (fill[j] >= 64) u42_refine(aq[j], q[j], *ls[j], fill[j], 64u, qsum32[j], q2[j], round1[j], thr[j], st[j], lane);
+      }
     }
   }
-  if (fill) u42_refine(a, q, ls, fill, fill, qsum32, q2, round1, thr, st, lane);
-  st.finish(a.cand, a.count, a.cap, lane);
+#pragma unroll
+  for (int j = 0; j < QP; ++j) {
+    if (fill[j]) u42_refine(aq[j], q[j], *ls[j], fill[j], fill[j], qsum32[j], q2[j], round1[j], thr[j], st[j], lane);
+    st[j].finish(aq[j].cand, aq[j].count, aq[j].cap, lane);
+  }
 }
 
 // rows [r0, n) fp32 -> h plane, {s, a4} and l records, one wave per row, one lane per 16 elements (half a unit): the walk of
@@ -271,11 +304,21 @@ static int u42_unit_chunk(uint32_t units) {
 }
 
 typedef void (*scan42_fn)(Scan42Args);
-static scan42_fn pick_scan42(int uc) {
+// the instance for uc units in flight and qp (1, 2 or 4) queries per group
+template <int QP>
+static scan42_fn pick_scan42_qp(int uc) {
   switch (uc) {
-    case 4: return scan_u42_kernel<4>;
-    case 6: return scan_u42_kernel<6>;
-    case 8: return scan_u42_kernel<8>;
+    case 4: return scan_u42_kernel<4, QP>;
+    case 6: return scan_u42_kernel<6, QP>;
+    case 8: return scan_u42_kernel<8, QP>;
+  }
+  return nullptr;
+}
+static scan42_fn pick_scan42(int uc, int qp = 1) {
+  switch (qp) {
+    case 1: return pick_scan42_qp<1>(uc);
+    case 2: return pick_scan42_qp<2>(uc);
+    case 4: return pick_scan42_qp<4>(uc);
   }
   return nullptr;
 }

@@ -2552,6 +2552,7 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"scan_u6", &wdbx_index::opt_scan_u6},
     {"scan_u6_cap", &wdbx_index::opt_scan_u6_cap},
     {"scan_u42", &wdbx_index::opt_scan_u42},
+    {"scan_u42_share", &wdbx_index::opt_scan_u42_share},
     {"batch_repair", &wdbx_index::opt_batch_repair},
     {"single_min_rows", &wdbx_index::opt_single_min_rows},
     {"range_min_rows", &wdbx_index::opt_range_min_rows},
@@ -2587,6 +2588,8 @@ int wdbx_index_set_option(wdbx_index* ix, const char* name, int64_t value) try {
                 RANGE_PAIR_CAP_MIN, RANGE_PAIR_CAP_MAX);
   if (slot == &ix->opt_mmr_scratch_mib && (value < 1 || value > MMR_SCRATCH_MIB_MAX))
     return fail(WDBX_E_INVALID, "mmr_scratch_mib %lld outside [1, %lld]", (long long)value, (long long)MMR_SCRATCH_MIB_MAX);
+  if (slot == &ix->opt_scan_u42_share && value != -1 && value != 1 && value != 2 && value != 4)
+    return fail(WDBX_E_INVALID, "scan_u42_share %lld: -1 (the default), 1, 2 or 4 queries per read", (long long)value);
   *slot = value;
   if (!strcmp(name, "group_bounds")) ix->gmax_valid = false;  // re-decide (and rebuild the group maxima) at the next batch
   return WDBX_OK;
@@ -2617,6 +2620,7 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
     return *value = name[14] == 's' ? sum : mx, WDBX_OK;
   }
   if (name && !strcmp(name, "last_single_u42")) return *value = ix->last_single_u42, WDBX_OK;
+  if (name && !strcmp(name, "last_u42_share")) return *value = ix->last_u42_share, WDBX_OK;
   if (name && !strcmp(name, "u42_survivors_sum")) {
     // rows that passed the four-bit bound in the last round's full passes; waits for the stream
     const uint32_t nq = ix->last_single_u42 ? std::min<uint32_t>(ix->last_batch_nq, 64) : 0;
