@@ -334,6 +334,57 @@ int wdbx_index_search_mmr(wdbx_index* idx, const float* queries, int nq, int k, 
                           const uint32_t* mask_words, uint64_t mask_word_count, /* NULL = every row */
                           int64_t* out_idx, float* out_score, float* out_mmr /* [nq, k]; out_mmr may be NULL */);
 
+/* ---- recommend search: rank rows by positive and negative examples ("more like these, less like those") ---------------
+ * Each of nq queries is a set of example vectors, positives and negatives; every eligible row is scored against all of them
+ * in one pass over the corpus and ranked by the fold below.  Blocking, host buffers; the call holds the handle's mutex to
+ * its end and nothing of it stays valid in the handle.  Both metrics.
+ *   Examples: examples is [example_offsets[2 * nq], dim], back to back; example_offsets is [2 * nq + 1], [0] == 0,
+ *   non-decreasing: query i's positives are [off[2i], off[2i + 1]), its negatives [off[2i + 1], off[2i + 2]).  At least one
+ *   positive and at most WDBX_MAX_EXAMPLES examples per query.  normalize_examples as normalize_queries elsewhere.
+ *   Scores and eligibility: r(row, e) is the score of row with example e as the query, in the ranking domain (L2: the
+ *   negated squared distance), in exact_score's arithmetic (lane order, fma chain, fold and xor tree as every exact score of
+ *   this library): bit-identical to what wdbx_index_search_rows and wdbx_index_range_search return for that row and that
+ *   vector.  An eligible row is a live row that the mask allows (mask_words NULL = every row; else mask_word_count words, at
+ *   least ceil(rows / 32)) and that is not in exclude_rows (strictly increasing row numbers, at most WDBX_MAX_EXCLUDE_ROWS;
+ *   NULL / 0 = none).  A row with a NaN r for any example of the query is never returned.
+ *   The fold: p = max r over the query's positives, n = max r over its negatives, or -inf when there are none.  A row is
+ *   FAVOURED when p > n; otherwise, ties included, it is DISFAVOURED.
+ *   Order: every favoured row ranks before every disfavoured row.  Favoured rows by (p descending, row ascending);
+ *   disfavoured rows by (n ascending, row ascending) -- the row farthest from its nearest negative first; the key value is
+ *   (-n) + 0.0f.  This is the order of Qdrant's current best_score strategy without its sigmoid, which is monotone and in fp32
+ *   would only create ties.  Each query's answer is cut at k.
+ *   Outputs [nq, k]: out_idx the row; out_score the value the row was ranked by in the caller's units -- p for favoured, n
+ *   for disfavoured (L2: the positive squared distance to the nearest positive or negative; -0 comes back as +0, as
+ *   everywhere); out_side (may be NULL) 1 for favoured, 0 for disfavoured.  Unused slots hold -1 / 0 / 0.  An empty index:
+ *   every slot -1, nothing launched.
+ *   Consequences: one positive and no negatives gives ids and score bits equal to the exact top-k of that vector in
+ *   exact_score's arithmetic, i.e. to the head of wdbx_index_range_search or to wdbx_index_search_rows over every row
+ *   (wdbx_index_search may sum a row in its scan's own lane order: the same ids unless two scores lie within an ulp, but not
+ *   necessarily the same score bits).  A negative equal to a positive makes every row disfavoured.  Answers are bit-identical from run to run: every list slot and every
+ *   key has one writer.  The answer does not depend on how the examples are cut into blocks (a maximum), nor on the rounds.
+ *   WDBX_E_INVALID: nq < 1, k outside [1, WDBX_MAX_K], a null buffer, a query with no positive example or with more than
+ *   WDBX_MAX_EXAMPLES examples, offsets that decrease or example_offsets[0] != 0, a mask shorter than ceil(rows / 32) words,
+ *   exclude_rows that is not strictly increasing, reaches the row count or is longer than WDBX_MAX_EXCLUDE_ROWS (the mask and
+ *   exclude_rows are checked under the handle's lock).  A refused call leaves the handle usable.
+ *   Passes: the 64-bit key has no spare bit for the side, so there are two: the favoured pass for all queries (favoured rows
+ *   emit make_key(p + 0.0f, row), all others 0), then the disfavoured pass for the queries that came back short of k only
+ *   (disfavoured rows emit make_key((-n) + 0.0f, row)); the host splices the two lists.  Each pass fetches every row once per
+ *   query (one wave per row, examples in blocks of up to 8) and ranks as the listed-row paths do: per-workgroup lists merged
+ *   by the merge kernel, or from select_min_k on a key per row and the radix-select chain, in rounds whose keys stay within
+ *   256 MiB.  The exclusion list lives on the device at its own size.  The scoring launches count as scan launches in
+ *   wdbx_index_profile_read.
+ *   get_option, read-only: "last_recommend_path" 0 nothing launched, 1 favoured pass only, 2 both passes;
+ *   "last_recommend_short" the queries the second pass served. */
+#define WDBX_MAX_EXAMPLES 64        /* positives + negatives of one query */
+#define WDBX_MAX_EXCLUDE_ROWS 1024
+int wdbx_index_search_recommend(wdbx_index* idx,
+                                const float* examples,           /* [example_offsets[2 * nq], dim], back to back */
+                                const uint64_t* example_offsets, /* [2 * nq + 1] */
+                                int nq, int k, int normalize_examples,
+                                const uint32_t* mask_words, uint64_t mask_word_count, /* NULL = every row */
+                                const uint64_t* exclude_rows, uint64_t n_exclude,     /* strictly increasing; may be NULL / 0 */
+                                int64_t* out_idx, float* out_score, uint8_t* out_side /* [nq, k]; out_side may be NULL */);
+
 /* ---- range search: every row within a similarity, no k ----------------------- */
 /* every row whose score reaches thresholds[q] (cosine/IP: score >= t; L2: squared distance <= t), exact fp32,
  * per query sorted like wdbx_index_search; replaces faiss' IndexFlat range_search, which the reference never reaches

@@ -214,6 +214,12 @@ struct wdbx_index {
   size_t mmr_bytes = 0;
   int last_mmr_path = 0;  // 0 nothing launched, 1 ran
   int64_t last_mmr_rounds = 0, last_mmr_candidates = 0;
+  // recommend search (wdbx_index_search_recommend): one allocation of the call's tables (host_recommend.h): the example table of
+  // every query | that of the short queries | the exclusion list.  The examples live in d_q, keys in d_sub_keys, lists in d_partials.
+  char* d_rec = nullptr;
+  size_t rec_bytes = 0;
+  int last_recommend_path = 0;  // 0 nothing launched, 1 favoured pass only, 2 both passes
+  int64_t last_recommend_short = 0;
   // profiling
   bool profile = false;
   EventPool scan_ev, merge_ev, gemm_ev, sample_ev;
@@ -2270,4 +2276,126 @@ static int enqueue_exact_rerun(wdbx_index* ix, const float* dq, int k, int64_t* 
   const int rc = enqueue_search(ix, dq, 1, k, out_idx, out_score, SEARCH_FINAL);
   ix->opt_scan_shadow = keep;
   return rc;
+}
+
+// ---- recommend search (kernels_recommend.h, host_recommend.h): one side's pass for `slots` queries ------------------------
+// d_table holds the slots' example table, the examples are in d_q, the mask (if any) is the active one.  Rounds of rp.round
+// slots: recommend_kernel (bracketed as a scan launch), then one merge launch over the round's partial lists or per slot the
+// radix-select chain.  Results: d_oidx / d_oscore [slots, k].  The disfavoured side's key value is -n in the ranking domain, so
+// the merge converts it with the OTHER metric's sign: out_score is n in the caller's units.
+static int enqueue_recommend_pass(wdbx_index* ix, const RecommendPlan& rp, const uint32_t* d_table, int slots, int k, int side,
+                                  const uint32_t* d_exclude, uint32_t n_exclude) {
+  const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
+  const recommend_fn fn = pick_recommend(ix->metric, rp.mode, pitch4);
+  if (!fn) return fail(WDBX_E_STATE, "no recommend instance for mode %d", rp.mode);
+  const bool lists = rp.mode != 2;
+  const size_t lds = lists ? rp.lds : 0;
+  if (lds >= 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  int rc;
+  for (const std::pair<int, int>& r : recommend_rounds(slots, rp.round)) {
+    const int q0 = r.first, b = r.second;
+    RecommendArgs a = {};
+    a.rows = (const f4*)ix->d_rows;
+    a.examples = (const f4*)ix->d_q;
+    a.table = d_table + (size_t)q0 * 3;
+    a.mask = ix->active_mask;
+    a.exclude = d_exclude;
+    a.out = lists ? ix->d_partials : ix->d_sub_keys;
+    a.key_stride = ix->n;
+    a.n_exclude = n_exclude;
+    a.n_rows = (uint32_t)ix->n;
+    a.pitch4 = pitch4;
+    a.k = k;
+    a.side = side;
+    if ((rc = record(ix->scan_ev, ix->profile, ix->stream, true))) return rc;
+    hipLaunchKernelGGL(fn, dim3(rp.blocks, (uint32_t)b), dim3(256), lds, ix->stream, a);
+    HIP_TRY(hipGetLastError());
+    if ((rc = record(ix->scan_ev, ix->profile, ix->stream, false))) return rc;
+    MergeArgs m = {};
+    m.k = k;
+    m.metric = side ? ix->metric : (ix->metric == WDBX_METRIC_L2 ? WDBX_METRIC_COSINE : WDBX_METRIC_L2);
+    if (!lists) {
+      const uint32_t sgrid = radix_select_grid(ix->n, ix->cu_count);
+      for (int q = 0; q < b; ++q) {
+        if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
+        HIP_TRY(enqueue_radix_select(ix->stream, (const u64*)ix->d_sub_keys + (size_t)q * ix->n, (u64)ix->n, nullptr,
+                                     (SelectState*)ix->d_state, (u64*)ix->d_sel, (uint32_t)k, sgrid));
+        m.out_idx = ix->d_oidx + (size_t)(q0 + q) * k;
+        m.out_score = ix->d_oscore + (size_t)(q0 + q) * k;
+        HIP_TRY(enqueue_sort_out(ix->stream, (const u64*)ix->d_sel, (const SelectState*)ix->d_state, m));
+        if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
+      }
+      continue;
+    }
+    m.in = ix->d_partials;
+    m.q_stride = (uint64_t)k * rp.P;
+    m.i_stride = rp.P;
+    m.p_stride = 1;
+    m.P = rp.P;
+    m.list_len = k;
+    m.out_idx = ix->d_oidx + (size_t)q0 * k;
+    m.out_score = ix->d_oscore + (size_t)q0 * k;
+    if ((rc = launch_merge(ix, m, b))) return rc;
+  }
+  return WDBX_OK;
+}
+
+// The call under the handle's lock (the caller holds it, has checked the arguments that need no lock, and resets the mask):
+//   1. the favoured pass for all queries;  2. the disfavoured pass for the queries that came back short of k only;
+//   3. the splice (host_recommend.h).
+static int recommend_locked(wdbx_index* ix, const float* examples, const uint64_t* off, int nq, int k, int normalize_examples,
+                            const uint32_t* mask_words, const std::vector<uint32_t>& exclude32, MaskScope& scope, int64_t* out_idx,
+                            float* out_score, uint8_t* out_side) {
+  const size_t elems = (size_t)nq * k;
+  const RecommendPlan rp = recommend_plan(ix->n, nq, k, ix->cu_count, ix->opt_select_min_k, ix->opt_lds_lists != 0);
+  int rc;
+  if ((rc = ensure_out(ix, elems))) return rc;
+  const size_t n_ex = exclude32.size();
+  const size_t tab_words = (size_t)nq * 3;
+  if ((rc = grow((void**)&ix->d_rec, &ix->rec_bytes, (2 * tab_words + std::max<size_t>(n_ex, 1)) * sizeof(uint32_t)))) return rc;
+  uint32_t* d_tab = (uint32_t*)ix->d_rec;
+  uint32_t* d_tab_short = d_tab + tab_words;
+  uint32_t* d_exclude = d_tab_short + tab_words;
+  if (rp.mode != 2) {
+    if ((rc = grow((void**)&ix->d_partials, &ix->partials_bytes, rp.scratch_u64 * sizeof(u64)))) return rc;
+  } else {
+    if ((rc = grow((void**)&ix->d_sub_keys, &ix->sub_keys_bytes, rp.scratch_u64 * sizeof(u64)))) return rc;
+    if ((rc = grow((void**)&ix->d_sel, &ix->sel_bytes, (size_t)WDBX_MAX_K * sizeof(u64)))) return rc;
+    if ((rc = grow((void**)&ix->d_state, &ix->state_bytes, sizeof(SelectState)))) return rc;
+  }
+  if ((rc = upload_queries(ix, examples, off[2 * nq], normalize_examples))) return rc;
+  if (mask_words && (rc = scope.set(mask_words))) return rc;
+  std::vector<uint32_t> all((size_t)nq), tab(tab_words);
+  for (int q = 0; q < nq; ++q) all[(size_t)q] = (uint32_t)q;
+  recommend_table(off, all.data(), all.size(), tab.data());
+  HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), tab_words * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+  if (n_ex) HIP_TRY(hipMemcpyAsync(d_exclude, exclude32.data(), n_ex * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+  if ((rc = enqueue_recommend_pass(ix, rp, d_tab, nq, k, 1, d_exclude, (uint32_t)n_ex))) return rc;
+  std::vector<int64_t> fav_idx(elems), dis_idx;
+  std::vector<float> fav_score(elems), dis_score;
+  if ((rc = download_results(ix, elems, fav_idx.data(), fav_score.data()))) return rc;
+  ix->last_recommend_path = 1;
+  std::vector<uint32_t> short_queries;
+  std::vector<int> gaps;
+  recommend_short(fav_idx.data(), nq, k, &short_queries, &gaps);
+  if (!short_queries.empty()) {
+    const int ns = (int)short_queries.size();
+    std::vector<uint32_t> tab_short((size_t)ns * 3);
+    recommend_table(off, short_queries.data(), short_queries.size(), tab_short.data());
+    HIP_TRY(hipMemcpyAsync(d_tab_short, tab_short.data(), tab_short.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+    const RecommendPlan rs = recommend_plan(ix->n, ns, k, ix->cu_count, ix->opt_select_min_k, ix->opt_lds_lists != 0);
+    if (rs.mode != 2) {  // (fewer queries: a wider grid, so longer partial lists per query)
+      if ((rc = grow((void**)&ix->d_partials, &ix->partials_bytes, rs.scratch_u64 * sizeof(u64)))) return rc;
+    } else {
+      if ((rc = grow((void**)&ix->d_sub_keys, &ix->sub_keys_bytes, rs.scratch_u64 * sizeof(u64)))) return rc;
+    }
+    if ((rc = enqueue_recommend_pass(ix, rs, d_tab_short, ns, k, 0, d_exclude, (uint32_t)n_ex))) return rc;
+    dis_idx.resize((size_t)ns * k);
+    dis_score.resize((size_t)ns * k);
+    if ((rc = download_results(ix, (size_t)ns * k, dis_idx.data(), dis_score.data()))) return rc;
+    ix->last_recommend_path = 2;
+    ix->last_recommend_short = ns;
+  }
+  recommend_splice(fav_idx.data(), fav_score.data(), dis_idx.data(), dis_score.data(), short_queries, nq, k, out_idx, out_score, out_side);
+  return WDBX_OK;
 }

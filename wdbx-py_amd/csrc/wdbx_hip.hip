@@ -45,6 +45,9 @@
 //   kernels_mmr.h           mmr_pairs_kernel, mmr_select_kernel: wdbx_index_search_mmr (maximal marginal relevance) behind its pool -- the
 //                           similarity square of a query's gathered candidates and the greedy selection over it
 //   host_mmr.h              that call's argument checks, pools, rounds and grids
+//   kernels_recommend.h     recommend_kernel: the pass of wdbx_index_search_recommend over the whole corpus -- every row scored against
+//                           a query's positive and negative examples, the scores folded into one key per side
+//   host_recommend.h        that call's offset and exclusion checks, plan, short queries and the splice of the two sides
 //   host_multimask.h        a call with one row mask per query: the placement of its queries in the int8 tiles' query blocks
 //   host_selection.h        the plan of the selection rounds: sampled tiles, stride, candidate and pair capacities of the tile paths and
 //                           the u8 / u6 rounds, the masked sample's growth, the 1 GiB shadow rule
@@ -97,6 +100,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_multivector.h"  // (device-free as well: rounds, segments, route and scratch of a multi-vector search)
 #include "host_rowlists.h"  // (device-free as well: slots, rounds, query blocks and work items of a call with a row list per query)
 #include "host_mmr.h"  // (device-free as well: argument checks, pools, rounds and grids of an MMR search)
+#include "host_recommend.h"  // (device-free as well: offsets, exclusion list, plan, short queries and splice of a recommend search)
 
 #define HIP_TRY(expr)                                                                        \
   do {                                                                                       \
@@ -136,6 +140,8 @@ static_assert(LABEL_SPAN_DEV == LABEL_SPAN, "the kernels walk the spans the host
 static_assert(MULTIVECTOR_MAX_VECTORS == WDBX_MAX_QUERY_VECTORS, "the plan's limit is the header's");
 #include "kernels_mmr.h"
 static_assert(MMR_MAX_POOL == WDBX_MAX_K, "a pool is a top-k answer");
+#include "kernels_recommend.h"
+static_assert(RECOMMEND_MAX_EXAMPLES == WDBX_MAX_EXAMPLES && RECOMMEND_MAX_EXCLUDE == WDBX_MAX_EXCLUDE_ROWS, "the plan's limits are the header's");
 #include "host_index.h"
 #include "host_group.h"
 
@@ -154,7 +160,7 @@ static uint64_t device_bytes_resident(const wdbx_index* ix) {
   b += ix->qb8_bytes + ix->qpar_bytes + ix->pairs_bytes + ix->pair_count_bytes + ix->cnmax_bytes;
   b += ix->rcand_bytes + ix->rkeys_bytes + ix->rcnt_bytes + ix->rthr_bytes;
   b += ix->rows6_bytes + ix->count6_bytes + ix->rows42_bytes + ix->count42_bytes;
-  b += ix->sub_ids_bytes + ix->sub_keys_bytes + ix->mm_bytes + ix->rl_bytes + ix->lab_bytes + ix->mv_bytes + ix->mmr_bytes;
+  b += ix->sub_ids_bytes + ix->sub_keys_bytes + ix->mm_bytes + ix->rl_bytes + ix->lab_bytes + ix->mv_bytes + ix->mmr_bytes + ix->rec_bytes;
   return b;
 }
 
@@ -232,7 +238,7 @@ void wdbx_index_destroy(wdbx_index* ix) try {
                     ix->d_state, ix->d_cn, ix->d_cnmax, ix->d_qb16, ix->d_rows16, ix->d_rows8, ix->d_scale8, ix->d_selsrc,
                     ix->d_gmax, ix->d_qn, ix->d_rows8g, ix->d_groups8, ix->d_gbad8, ix->d_gref8, ix->d_over_list, ix->d_qb8,
                     ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr, ix->d_rows6, ix->d_count6, ix->d_rows42, ix->d_count42,
-                    ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys, ix->d_mm, ix->d_rl, ix->d_lab, ix->d_mv, ix->d_mmr};
+                    ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys, ix->d_mm, ix->d_rl, ix->d_lab, ix->d_mv, ix->d_mmr, ix->d_rec};
     for (void* p : bufs)
       if (p) (void)hipFree(p);
     if (ix->h_stage) (void)hipHostFree(ix->h_stage);
@@ -1463,6 +1469,46 @@ int wdbx_index_search_mmr(wdbx_index* ix, const float* queries, int nq, int k, i
   return WDBX_OK;
 } WDBX_CATCH
 
+// ---- recommend search: rows ranked by positive and negative examples (host_recommend.h, kernels_recommend.h, DESIGN.md
+// section 4.15) ----------------------------------------------------------------------------------------------------------
+// The whole call holds the handle's mutex.  The offsets need no lock; the mask's length and the exclusion list are checked
+// against the row count under it.  Then recommend_locked (host_index.h): the favoured pass for all queries, the disfavoured
+// pass for the short ones, the splice.
+int wdbx_index_search_recommend(wdbx_index* ix, const float* examples, const uint64_t* example_offsets, int nq, int k,
+                                int normalize_examples, const uint32_t* mask_words, uint64_t mask_word_count,
+                                const uint64_t* exclude_rows, uint64_t n_exclude, int64_t* out_idx, float* out_score,
+                                uint8_t* out_side) try {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  if (nq < 1) return fail(WDBX_E_INVALID, "nq=%d", nq);
+  if (k < 1 || k > WDBX_MAX_K) return fail(WDBX_E_INVALID, "k=%d outside [1, %d]", k, WDBX_MAX_K);
+  if (!examples || !example_offsets || !out_idx || !out_score) return fail(WDBX_E_INVALID, "null buffer");
+  if (n_exclude && !exclude_rows) return fail(WDBX_E_INVALID, "exclude_rows is null");
+  std::string msg;
+  if (!recommend_validate_offsets(example_offsets, nq, &msg)) return fail(WDBX_E_INVALID, "%s", msg.c_str());
+  std::unique_lock<std::mutex> lk(ix->mu);
+  if (ix->n >= 0xFFFFFF00ull) return fail(WDBX_E_INVALID, "shard holds too many rows for 32-bit row keys");
+  if (mask_words) {
+    const int rc = check_mask_words(ix->n, mask_word_count);
+    if (rc) return rc;
+  }
+  std::vector<uint32_t> exclude32((size_t)std::min<uint64_t>(n_exclude, RECOMMEND_MAX_EXCLUDE));
+  if (!recommend_validate_exclude(exclude_rows, n_exclude, ix->n, exclude32.data(), &msg)) return fail(WDBX_E_INVALID, "%s", msg.c_str());
+  ix->last_recommend_path = 0;
+  ix->last_recommend_short = 0;
+  if (ix->n == 0) {  // every slot empty, nothing launched
+    for (size_t i = 0; i < (size_t)nq * k; ++i) {
+      out_idx[i] = -1;
+      out_score[i] = 0.0f;
+      if (out_side) out_side[i] = 0;
+    }
+    return WDBX_OK;
+  }
+  DeviceGuard g(ix->device);
+  MaskScope scope(ix);
+  return recommend_locked(ix, examples, example_offsets, nq, k, normalize_examples, mask_words, exclude32, scope, out_idx, out_score,
+                          out_side);
+} WDBX_CATCH
+
 // ---- range search (range_u8_eligible, pick_range_scan: host_index.h) -------------------------------
 // The whole call holds the handle's mutex (like a masked search: the key buffers are the handle's).  Per round of up to 64
 // queries: [u8 path: memset counters, scan8_kernel<PHASE 2> -> candidates] -> memset, range_filter_kernel / range_scan_kernel
@@ -2653,6 +2699,8 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "last_multivector_vectors")) return *value = ix->last_multivector_vectors, WDBX_OK;
   if (name && !strcmp(name, "last_multivector_labels")) return *value = ix->last_multivector_labels, WDBX_OK;
   if (name && !strcmp(name, "last_mmr_path")) return *value = ix->last_mmr_path, WDBX_OK;
+  if (name && !strcmp(name, "last_recommend_path")) return *value = ix->last_recommend_path, WDBX_OK;
+  if (name && !strcmp(name, "last_recommend_short")) return *value = ix->last_recommend_short, WDBX_OK;
   if (name && !strcmp(name, "last_mmr_rounds")) return *value = ix->last_mmr_rounds, WDBX_OK;
   if (name && !strcmp(name, "last_mmr_candidates")) return *value = ix->last_mmr_candidates, WDBX_OK;
   if (name && !strcmp(name, "last_sample_qn")) return *value = ix->last_sample_qn, WDBX_OK;

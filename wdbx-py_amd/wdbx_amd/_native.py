@@ -17,6 +17,8 @@ import numpy as np
 METRIC_COSINE = 0
 METRIC_L2 = 1
 MAX_K = 2048
+MAX_EXAMPLES = 64        # WDBX_MAX_EXAMPLES: positives + negatives of one recommend query
+MAX_EXCLUDE_ROWS = 1024  # WDBX_MAX_EXCLUDE_ROWS
 UNIQUE_ID_BYTES = 128
 
 _LIB_NAME = "libwdbx_hip.so"
@@ -76,6 +78,8 @@ SIGNATURES = {
                                                 C.c_uint64, _i64p, _f32p, C.POINTER(C.c_uint32)]),
     "wdbx_index_search_mmr": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
                                         C.POINTER(C.c_uint32), C.c_uint64, _i64p, _f32p, _f32p]),
+    "wdbx_index_search_recommend": (C.c_int, [C.c_void_p, _f32p, _u64p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32),
+                                              C.c_uint64, _u64p, C.c_uint64, _i64p, _f32p, C.POINTER(C.c_uint8)]),
     "wdbx_index_range_search": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
                                           C.c_uint64, _u64p, _i64p, _f32p]),
     "wdbx_index_range_search_batch": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
@@ -465,6 +469,38 @@ class NativeIndex:
                                                0 if m is None else m.size, idx.ctypes.data_as(_i64p), score.ctypes.data_as(_f32p),
                                                mmr.ctypes.data_as(_f32p)))
         return idx, score, mmr
+
+    def search_recommend(self, examples, offsets, k: int, normalize_examples: bool = False,
+                         mask_words: Optional[np.ndarray] = None,
+                         exclude_rows=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Rows ranked by positive and negative examples: query ``i``'s positives are the vectors ``offsets[2 i] ..
+        offsets[2 i + 1] - 1`` of ``examples``, its negatives ``offsets[2 i + 1] .. offsets[2 i + 2] - 1``.  Per row ``p`` is
+        the best score over the positives and ``n`` over the negatives; rows with ``p > n`` (favoured) come first by ``p``, the
+        others follow by ``n`` ascending.  Returns ``(rows int64, scores f32, sides uint8)``, each ``[nq, k]``: the row, the
+        value it was ranked by (``p`` or ``n``, as :meth:`search` returns scores) and 1 for favoured / 0 for disfavoured;
+        unused slots hold -1 / 0 / 0.  ``mask_words`` as in :meth:`search`; ``exclude_rows``: strictly increasing row numbers
+        that never come back."""
+        v = _as_f32(examples, self.dim)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if off.size < 3 or off.size % 2 == 0:
+            raise ValueError(f"offsets holds {off.size} entries: 2 * queries + 1 needed")
+        nq = (off.size - 1) // 2
+        if int(off[-1]) != v.shape[0]:
+            raise ValueError(f"offsets end at {int(off[-1])}, {v.shape[0]} examples given")
+        idx = np.empty((nq, int(k)), np.int64)
+        score = np.empty((nq, int(k)), np.float32)
+        side = np.empty((nq, int(k)), np.uint8)
+        m = None if mask_words is None else np.ascontiguousarray(mask_words, dtype=np.uint32)
+        ex = None if exclude_rows is None else np.ascontiguousarray(exclude_rows, dtype=np.uint64).reshape(-1)
+        # (nq, k, the offsets, the mask's length and the exclusion list are checked by the library, the last two under the lock)
+        _check(self._lib.wdbx_index_search_recommend(self._h, v.ctypes.data_as(_f32p), off.ctypes.data_as(_u64p), nq, int(k),
+                                                     int(normalize_examples),
+                                                     None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                     0 if m is None else m.size,
+                                                     None if ex is None or not ex.size else ex.ctypes.data_as(_u64p),
+                                                     0 if ex is None else ex.size, idx.ctypes.data_as(_i64p),
+                                                     score.ctypes.data_as(_f32p), side.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return idx, score, side
 
     def range_search(self, queries, thresholds, normalize_queries: bool = False,
                      mask_words: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:

@@ -141,6 +141,40 @@ async def search_batch_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]
     return {"results": [_render(r)["results"] for r in per_query]}
 
 
+async def recommend_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
+    """Recommend form (extension): body ``{"positive": [...], "negative": [...], "limit": 10, "strategy": "best_score",
+    "filter_metadata": null}`` -> the ``search_endpoint`` response shape with a ``"side"`` member per result (1: nearer to a
+    positive than to any negative, 0: not) (``wdbx.vector_recommend_async``).  The items of ``positive`` (at least one) and
+    ``negative`` (absent or null = none) are stored vector ids (strings) or vectors (lists of numbers); ``strategy`` is
+    ``"best_score"`` (absent or null) or ``"average_vector"``."""
+    if not isinstance(payload, dict):
+        raise ValueError("request body must be an object")
+    limit = payload.get("limit", 10)
+    limit = 10 if limit is None else limit
+    if isinstance(limit, bool) or not isinstance(limit, int):
+        raise ValueError("limit must be an integer")
+    flt = payload.get("filter_metadata")
+    if flt is not None and not isinstance(flt, dict):
+        raise ValueError("filter_metadata must be an object")
+    strategy = payload.get("strategy")
+    strategy = "best_score" if strategy is None else strategy
+    if strategy not in ("best_score", "average_vector"):
+        raise ValueError('strategy must be "best_score" or "average_vector"')
+
+    def examples(name: str, required: bool):
+        items = payload.get(name)
+        if items is None and not required:
+            return []
+        if not isinstance(items, (list, tuple)) or (required and not items):
+            raise ValueError(f"{name} must be a {'non-empty ' if required else ''}list of vector ids and vectors")
+        return [e if isinstance(e, str) else _vector(e, f"{name}[{i}]") for i, e in enumerate(items)]
+
+    positive, negative = examples("positive", True), examples("negative", False)
+    found = await wdbx.vector_recommend_async(positive, negative, limit=limit, strategy=strategy, filter_metadata=flt,
+                                              with_side=True)
+    return {"results": [{"vector_id": vid, "similarity": sim, "metadata": meta, "side": side} for vid, sim, meta, side in found]}
+
+
 async def range_search_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
     """Range form (extension): body ``{"query_vector": [...], "threshold": 0.8, "filter_metadata": null,
     "max_results": null}`` -> the ``search_endpoint`` response shape with EVERY vector whose similarity reaches

@@ -899,6 +899,35 @@ class HipFlatIndex(VectorIndex):
                 return []
             raise
 
+    def recommend(self, positives, negatives=(), limit: int = 10, mask=None, exclude_ids=()) -> List[Tuple[str, float, int]]:
+        """Rows of this shard ranked by example vectors ("more like ``positives``, less like ``negatives``",
+        ``wdbx_index_search_recommend``): per row the best score over the positives (``p``) and over the negatives (``n``);
+        rows with ``p > n`` first by ``p``, then the others by ``n`` ascending.  ``[(id, score, side)]``: the score is ``p``
+        (side 1, favoured) or ``n`` (side 0), in the units ``search`` returns.  ``mask`` as ``search``'s ``row_mask``;
+        ``exclude_ids``: ids that never come back (those this shard does not hold are ignored).  Errors are swallowed or
+        raised as in ``search``."""
+        try:
+            actual_limit = min(int(limit), _native.MAX_K)
+            if self.next_index == 0 or actual_limit <= 0:
+                return []
+            pos = [self._prepare(v) for v in positives]
+            neg = [self._prepare(v) for v in negatives]
+            if not pos:
+                raise ValueError("recommend needs at least one positive example")
+            words = None
+            if mask is not None:
+                words = mask if mask.dtype == np.uint32 else _native.pack_row_mask(mask)
+            rows = sorted({r for r in (self._row_of(i) for i in exclude_ids) if r is not None})
+            idx, score, side = self._native.search_recommend(np.stack(pos + neg), [0, len(pos), len(pos) + len(neg)], actual_limit,
+                                                             mask_words=words, exclude_rows=rows or None)
+            keep = idx[0] != -1
+            return [(vid, s, int(sd)) for (vid, s), sd in zip(self._map(idx[0], score[0]), side[0][keep])]
+        except Exception as e:
+            logger.error("Error in HIP recommend search: %s", e)
+            if self.swallow_errors:
+                return []
+            raise
+
     async def search_async(self, query_vector: np.ndarray, limit: int = 10) -> List[Tuple[str, float]]:
         loop = asyncio.get_event_loop()
         return await loop.run_in_executor(self.thread_pool, self.search, query_vector, limit)

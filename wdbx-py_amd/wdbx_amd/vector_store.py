@@ -1211,6 +1211,73 @@ class VectorStore:
             query_vector, limit=limit, fetch_k=fetch_k, lambda_mult=lambda_mult, threshold=threshold,
             filter_metadata=filter_metadata))
 
+    # ---- recommend search (extension: rank by positive and negative examples) ----
+    def _resolve_examples(self, examples, what: str):
+        """Examples are stored vector ids or raw vectors: ``(vectors, ids)``, the ids resolved with :meth:`get`."""
+        vectors, ids = [], []
+        for i, e in enumerate(examples or ()):
+            if isinstance(e, str):
+                got = self.get(e)
+                if got is None:
+                    raise ValueError(f"{what}[{i}]: no stored vector has the id {e!r}")
+                ids.append(e)
+                e = got[0]
+            v = _as_query(e)
+            if v.shape != (self.vector_dim,):
+                raise ValueError(f"{what}[{i}]: vector dimension mismatch: expected {self.vector_dim}, got {v.shape}")
+            vectors.append(v)
+        return vectors, ids
+
+    def recommend(self, positive, negative=None, limit: int = 10, strategy: str = "best_score",
+                  filter_metadata: Optional[Dict[str, Any]] = None, with_side: bool = False) -> List[tuple]:
+        """"More like these, less like those": ``positive`` and ``negative`` are lists whose items are stored vector ids or
+        raw vectors; every example that is an id never comes back.  ``strategy="best_score"`` (Qdrant's, without its
+        sigmoid): per vector ``p`` is its best score over the positives and ``n`` over the negatives; vectors with ``p > n``
+        (favoured) come first by ``p`` descending, the others follow by ``n`` ascending.  The fold is per vector, so any
+        number of shards serves: every shard returns its own top-``limit`` (``wdbx_index_search_recommend``, the id examples
+        excluded on the shard that holds them), the merge takes favoured results by (score descending, shard, position),
+        then disfavoured ones by (``n`` ascending, shard, position), cut at ``limit``.  ``strategy="average_vector"`` needs
+        no pass of its own: the query is ``avg(pos) + (avg(pos) - avg(neg))`` through :meth:`search` with ``limit`` + the
+        number of id examples, which are then dropped.  ``filter_metadata`` always travels as the row masks.  Returns
+        ``(vector_id, score, metadata)``, with ``side`` (1 favoured, 0 disfavoured; always 1 for ``average_vector``) appended
+        when ``with_side`` is set."""
+        if strategy not in ("best_score", "average_vector"):
+            raise ValueError(f'strategy must be "best_score" or "average_vector", got {strategy!r}')
+        pos, pos_ids = self._resolve_examples(positive, "positive")
+        neg, neg_ids = self._resolve_examples(negative, "negative")
+        if not pos:
+            raise ValueError("recommend needs at least one positive example")
+        if len(pos) + len(neg) > _native.MAX_EXAMPLES:
+            raise ValueError(f"{len(pos) + len(neg)} examples, at most {_native.MAX_EXAMPLES} are served")
+        example_ids = set(pos_ids) | set(neg_ids)
+        if limit <= 0:
+            return []
+        if strategy == "average_vector":
+            avg = np.mean(np.stack(pos), axis=0, dtype=np.float32)
+            query = avg + (avg - np.mean(np.stack(neg), axis=0, dtype=np.float32)) if neg else avg
+            found = self.search(query.tolist(), limit=limit + len(example_ids), threshold=0.0, filter_metadata=filter_metadata,
+                                **({"prefilter": True} if filter_metadata else {}))
+            out = [(vid, score, meta) + ((1,) if with_side else ()) for vid, score, meta in found if vid not in example_ids]
+            return out[:limit]
+        masks = self._row_masks(filter_metadata) if filter_metadata else [None] * len(self.indices)
+        by_shard = [[] for _ in self.indices]
+        for vid in example_ids:
+            by_shard[self._get_shard_for_id(vid)].append(vid)
+        work = list(zip(self.indices, masks, by_shard))
+        one = lambda a: a[0].recommend(pos, neg, limit, mask=a[1], exclude_ids=a[2])  # noqa: E731
+        per_shard = list(self._shard_pool.map(one, work)) if len(work) > 1 else [one(work[0])]
+        # (a shard's list is favoured first by (p descending, row), then disfavoured by (n ascending, row): within a side the
+        # position stands for the row among equal scores)
+        ranked = sorted(((0, -score, shard, at) if side else (1, score, shard, at), vid, score, side)
+                        for shard, res in enumerate(per_shard) for at, (vid, score, side) in enumerate(res))
+        return [(vid, score, self.metadata.get(vid, {})) + ((side,) if with_side else ()) for _, vid, score, side in ranked[:limit]]
+
+    async def recommend_async(self, positive, negative=None, limit: int = 10, strategy: str = "best_score",
+                              filter_metadata: Optional[Dict[str, Any]] = None, with_side: bool = False) -> List[tuple]:
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(self.thread_pool, lambda: self.recommend(
+            positive, negative, limit=limit, strategy=strategy, filter_metadata=filter_metadata, with_side=with_side))
+
     # ---- range search (extension: every vector within a similarity, no limit) ----
     def search_range(self, query_vector: List[float], threshold: float,
                      filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,

@@ -199,6 +199,22 @@ class WDBX:
         return await self.vector_store.search_mmr_async(query_vector, limit=limit, fetch_k=fetch_k, lambda_mult=lambda_mult,
                                                         threshold=threshold, filter_metadata=filter_metadata)
 
+    def vector_recommend(self, positive, negative=None, limit: int = 10, strategy: str = "best_score",
+                         filter_metadata: Optional[Dict[str, Any]] = None, with_side: bool = False) -> List[tuple]:
+        """Extension: "more like these, less like those".  ``positive`` / ``negative``: lists of stored vector ids or raw
+        vectors; id examples never come back.  ``strategy="best_score"``: vectors nearer to their best positive than to
+        their best negative first, by that positive's score; the others follow, the one farthest from its nearest negative
+        first.  ``"average_vector"``: one plain search with ``avg(pos) + (avg(pos) - avg(neg))``.  A filter is pushed down;
+        any number of shards.  ``(vector_id, score, metadata)``, with ``side`` appended when ``with_side`` is set
+        (``VectorStore.recommend`` states the order)."""
+        return self.vector_store.recommend(positive, negative, limit=limit, strategy=strategy,
+                                           filter_metadata=filter_metadata, with_side=with_side)
+
+    async def vector_recommend_async(self, positive, negative=None, limit: int = 10, strategy: str = "best_score",
+                                     filter_metadata: Optional[Dict[str, Any]] = None, with_side: bool = False) -> List[tuple]:
+        return await self.vector_store.recommend_async(positive, negative, limit=limit, strategy=strategy,
+                                                       filter_metadata=filter_metadata, with_side=with_side)
+
     def vector_search_range(self, query_vector: List[float], threshold: float,
                             filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,
                             max_results: Optional[int] = None) -> List[Result]:
