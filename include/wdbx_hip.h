@@ -248,6 +248,57 @@ int wdbx_index_search_distinct(wdbx_index* idx, const float* queries, int nq, in
                                const uint32_t* mask_words, uint64_t mask_word_count, /* NULL = every row */
                                int64_t* out_idx, float* out_score, uint32_t* out_label /* may be NULL */);
 
+/* ---- search groups: the k best labels, each with its best group_size rows ------- */
+/* wdbx_index_search_distinct with a group size (Qdrant's search groups with group_size, Elasticsearch's collapse with
+ * inner_hits, Milvus' grouping search with group_size; the reference has nothing): "ten documents, each with its three best
+ * chunks".  Blocking, host buffers, both metrics.
+ * Groups: the groups of query i, their order and out_label are what wdbx_index_search_distinct returns for the same queries, k,
+ *   mask and options -- stage 1 runs the very steps of that call, so option "distinct_overfetch" and the read-only
+ *   "last_distinct_*" options keep their meaning for it.  A WDBX_LABEL_NONE row is a group of its own; on a handle without labels
+ *   every row is one.
+ * Members: slot s of query i holds the first group_size eligible rows of that label -- eligible: live, allowed by the mask
+ *   (mask_words NULL = every row; else mask_word_count words, at least ceil(rows / 32)), with a score that is not NaN -- ranked
+ *   by (score descending, row ascending), L2 by (distance ascending, row ascending).  Every member's score is computed in
+ *   rescore_kernel's arithmetic: bit-identical to what wdbx_index_search_rows and wdbx_index_range_search return for that row
+ *   and query; -0 comes back as +0 and L2 scores are positive squared distances.  out_idx / out_score are
+ *   [nq, k, group_size]; out_label (may be NULL) and out_count (may be NULL; the members found, 1 .. group_size) are [nq, k].
+ *   Unused member slots hold -1 / 0; unused group slots hold -1 / 0 / WDBX_LABEL_NONE / count 0.  An empty index gives every
+ *   slot -1 and launches nothing.
+ *   With group_size = 1 out_idx[., ., 0] and out_label equal the distinct search's, with one exception: where two rows of one
+ *   label score within an ulp of each other and the distinct search answered from its over-fetch (whose scan may sum in its
+ *   own lane order), member 0 -- always the label's best row in rescore_kernel's arithmetic -- may be the other of the two.
+ *   Answers are bit-identical from run to run (every key and every output word has one writer) and do not depend on option
+ *   "groups_segment_rows" or on the rounds.
+ * Stage 2: the rows of a label lie contiguous in the device-resident label order (above).  The host finds each winner's run,
+ *   cuts it into tasks of at most "groups_segment_rows" positions (option, default 2048, range 4 .. 65536, anything else is
+ *   WDBX_E_INVALID) -- an unlabelled winner is one direct row -- and per round (partial lists and task table within 256 MiB; a
+ *   slot that passes it alone still runs) launches one scoring kernel (a workgroup per task, a register list of group_size keys
+ *   per wave; counted as a scan launch in wdbx_index_profile_read) and one merge kernel (a wave per slot merges the slot's
+ *   sorted lists and writes members, scores and count).  One download.
+ *   get_option, read-only: "last_groups_path" 0 = nothing launched, 1 = ran; "last_groups_tasks"; "last_groups_rounds".
+ *   WDBX_E_INVALID, the handle stays usable: nq < 1, k outside [1, WDBX_MAX_K], group_size outside
+ *   [1, WDBX_MAX_GROUP_SIZE], a null query / out_idx / out_score, a mask shorter than ceil(rows / 32) words (checked under the
+ *   handle's lock), 2^32 - 256 rows or more (the distinct search's condition).
+ *   The call holds the handle's mutex to its end and leaves nothing valid in the handle. */
+#define WDBX_MAX_GROUP_SIZE 64
+int wdbx_index_search_groups(wdbx_index* idx, const float* queries, int nq, int k, int group_size, int normalize_queries,
+                             const uint32_t* mask_words, uint64_t mask_word_count, /* NULL = every row */
+                             int64_t* out_idx, float* out_score,                   /* [nq, k, group_size] */
+                             uint32_t* out_label, int32_t* out_count /* [nq, k]; each may be NULL */);
+
+/* Stage 2 alone, on the caller's slots (what a store of several shards needs: a label of the global top-k is in the top-k of
+ * the shard that holds its best row, its other rows may lie on shards where it did not make the top-k).  slot_labels /
+ * slot_rows are [nq, k]: slot_rows < 0 = the slot is unused (-1 / 0, count 0); slot_labels == WDBX_LABEL_NONE = the group is
+ * the single row slot_rows (eligibility still applies); any other label = that label's rows on this handle, whatever
+ * slot_rows (>= 0) says -- a label this handle does not hold gives count 0, not an error.  Members, scores, counts, options and
+ * refusals as wdbx_index_search_groups; also WDBX_E_INVALID: a null slot_labels / slot_rows, a slot_rows at or past the row
+ * count (checked under the lock). */
+int wdbx_index_search_group_members(wdbx_index* idx, const float* queries, int nq, int k, int group_size, int normalize_queries,
+                                    const uint32_t* mask_words, uint64_t mask_word_count, /* NULL = every row */
+                                    const uint32_t* slot_labels, const int64_t* slot_rows, /* [nq, k] */
+                                    int64_t* out_idx, float* out_score,                    /* [nq, k, group_size] */
+                                    int32_t* out_count /* [nq, k]; may be NULL */);
+
 /* ---- multi-vector search: labels ranked by the sum of per-vector best scores ---- */
 /* Late interaction / MaxSim (ColBERT, Qdrant's multivector, Vespa; the reference has nothing): a document is stored as many
  * rows under one label (wdbx_index_set_labels), a query is itself several vectors, and

@@ -220,6 +220,14 @@ struct wdbx_index {
   size_t rec_bytes = 0;
   int last_recommend_path = 0;  // 0 nothing launched, 1 favoured pass only, 2 both passes
   int64_t last_recommend_short = 0;
+  // search groups (wdbx_index_search_groups / _group_members): where each dense label's run lies in the label order, on the host
+  // (host_groups.h; rebuilt with the label order), and one allocation of a call's tables: the slot table | the round's tasks |
+  // the slots' counts.  Queries in d_q, partial lists in d_partials, members in d_oidx / d_oscore.
+  LabelRuns lab_runs;
+  char* d_grp = nullptr;
+  size_t grp_bytes = 0;
+  int last_groups_path = 0;  // 0 nothing launched, 1 ran
+  int64_t last_groups_tasks = 0, last_groups_rounds = 0;
   // profiling
   bool profile = false;
   EventPool scan_ev, merge_ev, gemm_ev, sample_ev;
@@ -232,7 +240,7 @@ struct wdbx_index {
           opt_merge_fast = 1, opt_poll_done = 1, opt_scan_one_grid = 1, opt_select_min_k = 200, opt_gemm_min_nq = 4, opt_gemm_min_rows = 65536, opt_gemm_min_work = 800000,
           opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0, opt_scan_u42 = -1, opt_scan_u42_share = -1, opt_gemm_masked = 1, opt_rows_keys_max = 8192, opt_distinct_overfetch = 4,
           opt_multivector_round_vectors = 256, opt_range_batch_min_queries = 4, opt_range_pair_cap = 0,
-          opt_mmr_scratch_mib = MMR_SCRATCH_MIB_MAX;
+          opt_mmr_scratch_mib = MMR_SCRATCH_MIB_MAX, opt_groups_segment_rows = GROUPS_SEGMENT_DEFAULT;
 };
 
 struct DeviceGuard {

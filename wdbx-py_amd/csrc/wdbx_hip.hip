@@ -48,6 +48,9 @@
 //   kernels_recommend.h     recommend_kernel: the pass of wdbx_index_search_recommend over the whole corpus -- every row scored against
 //                           a query's positive and negative examples, the scores folded into one key per side
 //   host_recommend.h        that call's offset and exclusion checks, plan, short queries and the splice of the two sides
+//   kernels_groups.h        group_members_kernel, group_merge_kernel: stage 2 of wdbx_index_search_groups -- the best group_size rows of
+//                           each chosen label, scored along the label's run of the label order, and the merge of a run's segments
+//   host_groups.h           the runs of the label order, the dense label of a label value, that call's tasks, slot table and rounds
 //   host_multimask.h        a call with one row mask per query: the placement of its queries in the int8 tiles' query blocks
 //   host_selection.h        the plan of the selection rounds: sampled tiles, stride, candidate and pair capacities of the tile paths and
 //                           the u8 / u6 rounds, the masked sample's growth, the 1 GiB shadow rule
@@ -101,6 +104,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_rowlists.h"  // (device-free as well: slots, rounds, query blocks and work items of a call with a row list per query)
 #include "host_mmr.h"  // (device-free as well: argument checks, pools, rounds and grids of an MMR search)
 #include "host_recommend.h"  // (device-free as well: offsets, exclusion list, plan, short queries and splice of a recommend search)
+#include "host_groups.h"  // (device-free as well: label runs, dense label lookup, tasks, slot table and rounds of a groups search)
 
 #define HIP_TRY(expr)                                                                        \
   do {                                                                                       \
@@ -142,6 +146,9 @@ static_assert(MULTIVECTOR_MAX_VECTORS == WDBX_MAX_QUERY_VECTORS, "the plan's lim
 static_assert(MMR_MAX_POOL == WDBX_MAX_K, "a pool is a top-k answer");
 #include "kernels_recommend.h"
 static_assert(RECOMMEND_MAX_EXAMPLES == WDBX_MAX_EXAMPLES && RECOMMEND_MAX_EXCLUDE == WDBX_MAX_EXCLUDE_ROWS, "the plan's limits are the header's");
+#include "kernels_groups.h"
+static_assert(GROUPS_MAX_SIZE_DEV == GROUPS_MAX_SIZE && GROUPS_MAX_SIZE == WDBX_MAX_GROUP_SIZE, "a wave's register list holds a group");
+static_assert(sizeof(GroupTaskDev) == sizeof(GroupTask) && sizeof(GroupTask) == 16, "the device reads the host's tasks");
 #include "host_index.h"
 #include "host_group.h"
 
@@ -160,7 +167,7 @@ static uint64_t device_bytes_resident(const wdbx_index* ix) {
   b += ix->qb8_bytes + ix->qpar_bytes + ix->pairs_bytes + ix->pair_count_bytes + ix->cnmax_bytes;
   b += ix->rcand_bytes + ix->rkeys_bytes + ix->rcnt_bytes + ix->rthr_bytes;
   b += ix->rows6_bytes + ix->count6_bytes + ix->rows42_bytes + ix->count42_bytes;
-  b += ix->sub_ids_bytes + ix->sub_keys_bytes + ix->mm_bytes + ix->rl_bytes + ix->lab_bytes + ix->mv_bytes + ix->mmr_bytes + ix->rec_bytes;
+  b += ix->sub_ids_bytes + ix->sub_keys_bytes + ix->mm_bytes + ix->rl_bytes + ix->lab_bytes + ix->mv_bytes + ix->mmr_bytes + ix->rec_bytes + ix->grp_bytes;
   return b;
 }
 
@@ -238,7 +245,7 @@ void wdbx_index_destroy(wdbx_index* ix) try {
                     ix->d_state, ix->d_cn, ix->d_cnmax, ix->d_qb16, ix->d_rows16, ix->d_rows8, ix->d_scale8, ix->d_selsrc,
                     ix->d_gmax, ix->d_qn, ix->d_rows8g, ix->d_groups8, ix->d_gbad8, ix->d_gref8, ix->d_over_list, ix->d_qb8,
                     ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr, ix->d_rows6, ix->d_count6, ix->d_rows42, ix->d_count42,
-                    ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys, ix->d_mm, ix->d_rl, ix->d_lab, ix->d_mv, ix->d_mmr, ix->d_rec};
+                    ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys, ix->d_mm, ix->d_rl, ix->d_lab, ix->d_mv, ix->d_mmr, ix->d_rec, ix->d_grp};
     for (void* p : bufs)
       if (p) (void)hipFree(p);
     if (ix->h_stage) (void)hipHostFree(ix->h_stage);
@@ -1035,6 +1042,7 @@ static int ensure_label_order(wdbx_index* ix) {
   ix->lab_items = lo.n_items;
   ix->lab_labels = lo.n_labels;
   ix->lab_spans = lo.n_spans;
+  label_runs_build(lo, ix->labels.data(), std::min<uint64_t>(ix->labels.size(), ix->n), &ix->lab_runs);
   ix->lab_row0 = std::move(lo.label_row0);
   ix->lab_n = ix->n;
   ix->lab_valid = true;
@@ -1130,14 +1138,11 @@ static int distinct_full_pass(wdbx_index* ix, const float* queries, int nq, int 
   return download_results(ix, elems, out_idx, out_score);
 }
 
-int wdbx_index_search_distinct(wdbx_index* ix, const float* queries, int nq, int k, int normalize_queries, const uint32_t* mask_words,
-                               uint64_t mask_word_count, int64_t* out_idx, float* out_score, uint32_t* out_label) try {
-  if (!ix) return fail(WDBX_E_INVALID, "null handle");
-  if (nq < 1) return fail(WDBX_E_INVALID, "nq=%d", nq);
-  if (!queries || !out_idx || !out_score) return fail(WDBX_E_INVALID, "null buffer");
-  if (k < 1 || k > WDBX_MAX_K) return fail(WDBX_E_INVALID, "k=%d outside [1, %d]", k, WDBX_MAX_K);
-  std::unique_lock<std::mutex> lk(ix->mu);
-  DeviceGuard g(ix->device);
+// The distinct search under the handle's mutex (lk holds it; the device is set; nq, k and the buffers are checked): what
+// wdbx_index_search_distinct answers and stage 1 of wdbx_index_search_groups.
+static int distinct_locked(wdbx_index* ix, const float* queries, int nq, int k, int normalize_queries, const uint32_t* mask_words,
+                           uint64_t mask_word_count, int64_t* out_idx, float* out_score, uint32_t* out_label,
+                           std::unique_lock<std::mutex>& lk) {
   int rc;
   const size_t elems = (size_t)nq * k;
   ix->last_distinct_path = DISTINCT_NONE;
@@ -1203,6 +1208,167 @@ int wdbx_index_search_distinct(wdbx_index* ix, const float* queries, int nq, int
   }
   ix->last_distinct_path = kp ? DISTINCT_BOTH : DISTINCT_FULL;
   return WDBX_OK;
+}
+
+int wdbx_index_search_distinct(wdbx_index* ix, const float* queries, int nq, int k, int normalize_queries, const uint32_t* mask_words,
+                               uint64_t mask_word_count, int64_t* out_idx, float* out_score, uint32_t* out_label) try {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  if (nq < 1) return fail(WDBX_E_INVALID, "nq=%d", nq);
+  if (!queries || !out_idx || !out_score) return fail(WDBX_E_INVALID, "null buffer");
+  if (k < 1 || k > WDBX_MAX_K) return fail(WDBX_E_INVALID, "k=%d outside [1, %d]", k, WDBX_MAX_K);
+  std::unique_lock<std::mutex> lk(ix->mu);
+  DeviceGuard g(ix->device);
+  return distinct_locked(ix, queries, nq, k, normalize_queries, mask_words, mask_word_count, out_idx, out_score, out_label, lk);
+} WDBX_CATCH
+
+// ---- search groups: the best group_size rows of each of the k best labels (host_groups.h, kernels_groups.h, DESIGN.md
+// section 4.16) ----
+// Stage 2 under the handle's mutex, on a non-empty index: slots [nq * k] say what each (query, slot) ranks.  The task table is
+// built on the host (groups_tasks) and served in rounds (groups_plan): per round group_members_kernel with a workgroup per task
+// (bracketed as a scan launch; none when the round has no task), then group_merge_kernel with a wave per slot, which writes
+// every member slot and count of the round -- no memset.  One download at the end.  out_count may be null.
+static int group_members_pass(wdbx_index* ix, const float* queries, int nq, int k, int g, int normalize_queries,
+                              const uint32_t* mask_words, const std::vector<GroupSlot>& slots, int64_t* out_idx, float* out_score,
+                              int32_t* out_count) {
+  int rc;
+  std::vector<GroupTask> tasks;
+  std::vector<uint64_t> slot_task0;
+  groups_tasks(slots.data(), slots.size(), k, (uint32_t)ix->opt_groups_segment_rows, &tasks, &slot_task0);
+  const std::vector<GroupsRound> rounds = groups_plan(slot_task0, g);
+  const size_t n_slots = slots.size(), elems = n_slots * (size_t)g;
+  uint64_t max_tasks = 1;
+  for (const GroupsRound& r : rounds) max_tasks = std::max(max_tasks, r.tasks);
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t off_tasks = up((n_slots + 1) * sizeof(uint64_t)), off_count = off_tasks + up((size_t)max_tasks * sizeof(GroupTask));
+  if ((rc = ensure_out(ix, elems))) return rc;
+  if ((rc = grow((void**)&ix->d_partials, &ix->partials_bytes, (size_t)max_tasks * g * sizeof(u64)))) return rc;
+  if ((rc = grow((void**)&ix->d_grp, &ix->grp_bytes, off_count + n_slots * sizeof(int32_t)))) return rc;
+  if ((rc = upload_queries(ix, queries, (uint64_t)nq, normalize_queries))) return rc;
+  MaskScope scope(ix);
+  if (mask_words && (rc = scope.set(mask_words))) return rc;
+  u64* const d_slot_task0 = (u64*)ix->d_grp;
+  GroupTaskDev* const d_tasks = (GroupTaskDev*)(ix->d_grp + off_tasks);
+  int32_t* const d_count = (int32_t*)(ix->d_grp + off_count);
+  HIP_TRY(hipMemcpyAsync(d_slot_task0, slot_task0.data(), (n_slots + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ix->stream));
+  const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
+  const group_members_fn mfn = pick_group_members(ix->metric, pitch4);
+  const group_merge_fn gfn = pick_group_merge(ix->metric);
+  for (const GroupsRound& r : rounds) {
+    if (r.tasks) {
+      HIP_TRY(hipMemcpyAsync(d_tasks, tasks.data() + r.task0, (size_t)r.tasks * sizeof(GroupTask), hipMemcpyHostToDevice, ix->stream));
+      GroupMembersArgs a = {};
+      a.rows = (const f4*)ix->d_rows;
+      a.queries = (const f4*)ix->d_q;
+      a.order = ix->lab_valid ? (const uint32_t*)ix->d_lab : nullptr;
+      a.mask = ix->active_mask;
+      a.tasks = d_tasks;
+      a.partial = ix->d_partials;
+      a.pitch4 = pitch4;
+      a.g = g;
+      if ((rc = record(ix->scan_ev, ix->profile, ix->stream, true))) return rc;
+      hipLaunchKernelGGL(mfn, dim3((uint32_t)r.tasks), dim3(256), 0, ix->stream, a);
+      HIP_TRY(hipGetLastError());
+      if ((rc = record(ix->scan_ev, ix->profile, ix->stream, false))) return rc;
+    }
+    GroupMergeArgs m = {};
+    m.partial = ix->d_partials;
+    m.slot_task0 = d_slot_task0 + r.slot0;
+    m.task_base = r.task0;
+    m.n_slots = (uint32_t)(r.slot1 - r.slot0);
+    m.g = g;
+    m.out_idx = ix->d_oidx + r.slot0 * (size_t)g;
+    m.out_score = ix->d_oscore + r.slot0 * (size_t)g;
+    m.out_count = d_count + r.slot0;
+    if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
+    hipLaunchKernelGGL(gfn, dim3(r.merge_blocks), dim3(256), 0, ix->stream, m);
+    HIP_TRY(hipGetLastError());
+    if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
+  }
+  ix->last_groups_path = 1;
+  ix->last_groups_tasks = (int64_t)tasks.size();
+  ix->last_groups_rounds = (int64_t)rounds.size();
+  if (out_count) HIP_TRY(hipMemcpyAsync(out_count, d_count, n_slots * sizeof(int32_t), hipMemcpyDeviceToHost, ix->stream));
+  return download_results(ix, elems, out_idx, out_score);
+}
+
+// what every (query, slot) of a call ranks, from its label and row (under the handle's mutex; builds the label order when a
+// slot names a label and the handle has labels)
+static int group_slots(wdbx_index* ix, const uint32_t* slot_labels, const int64_t* slot_rows, size_t n_slots, std::vector<GroupSlot>* slots) {
+  int rc;
+  bool any_label = false;
+  for (size_t s = 0; s < n_slots && !any_label; ++s) any_label = slot_rows[s] >= 0 && slot_labels[s] != WDBX_LABEL_NONE;
+  static const LabelRuns no_runs;
+  const bool use = any_label && !ix->labels.empty();
+  if (use && (rc = ensure_label_order(ix))) return rc;
+  const LabelRuns& runs = use ? ix->lab_runs : no_runs;
+  slots->resize(n_slots);
+  for (size_t s = 0; s < n_slots; ++s) (*slots)[s] = groups_slot(ix->labels.data(), ix->lab_row0.data(), runs, slot_labels[s], slot_rows[s]);
+  return WDBX_OK;
+}
+
+static int groups_check(const wdbx_index* ix, const float* queries, int nq, int k, int group_size, const void* out_idx, const void* out_score) {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  if (nq < 1) return fail(WDBX_E_INVALID, "nq=%d", nq);
+  if (!queries || !out_idx || !out_score) return fail(WDBX_E_INVALID, "null buffer");
+  if (k < 1 || k > WDBX_MAX_K) return fail(WDBX_E_INVALID, "k=%d outside [1, %d]", k, WDBX_MAX_K);
+  if (group_size < 1 || group_size > WDBX_MAX_GROUP_SIZE)
+    return fail(WDBX_E_INVALID, "group_size=%d outside [1, %d]", group_size, WDBX_MAX_GROUP_SIZE);
+  return WDBX_OK;
+}
+
+int wdbx_index_search_groups(wdbx_index* ix, const float* queries, int nq, int k, int group_size, int normalize_queries,
+                             const uint32_t* mask_words, uint64_t mask_word_count, int64_t* out_idx, float* out_score,
+                             uint32_t* out_label, int32_t* out_count) try {
+  int rc;
+  if ((rc = groups_check(ix, queries, nq, k, group_size, out_idx, out_score))) return rc;
+  std::unique_lock<std::mutex> lk(ix->mu);
+  DeviceGuard g(ix->device);
+  ix->last_groups_path = 0;
+  ix->last_groups_tasks = ix->last_groups_rounds = 0;
+  const size_t n_slots = (size_t)nq * k;
+  // stage 1: the distinct search, through the steps its public entry runs
+  std::vector<int64_t> d_idx(n_slots);
+  std::vector<float> d_score(n_slots);
+  std::vector<uint32_t> d_label(n_slots);
+  if ((rc = distinct_locked(ix, queries, nq, k, normalize_queries, mask_words, mask_word_count, d_idx.data(), d_score.data(), d_label.data(), lk)))
+    return rc;
+  if (out_label) std::copy(d_label.begin(), d_label.end(), out_label);
+  if (ix->n == 0) {  // every slot empty, nothing launched
+    std::fill(out_idx, out_idx + n_slots * (size_t)group_size, (int64_t)-1);
+    std::fill(out_score, out_score + n_slots * (size_t)group_size, 0.0f);
+    if (out_count) std::fill(out_count, out_count + n_slots, 0);
+    return WDBX_OK;
+  }
+  std::vector<GroupSlot> slots;
+  if ((rc = group_slots(ix, d_label.data(), d_idx.data(), n_slots, &slots))) return rc;
+  return group_members_pass(ix, queries, nq, k, group_size, normalize_queries, mask_words, slots, out_idx, out_score, out_count);
+} WDBX_CATCH
+
+int wdbx_index_search_group_members(wdbx_index* ix, const float* queries, int nq, int k, int group_size, int normalize_queries,
+                                    const uint32_t* mask_words, uint64_t mask_word_count, const uint32_t* slot_labels,
+                                    const int64_t* slot_rows, int64_t* out_idx, float* out_score, int32_t* out_count) try {
+  int rc;
+  if ((rc = groups_check(ix, queries, nq, k, group_size, out_idx, out_score))) return rc;
+  if (!slot_labels || !slot_rows) return fail(WDBX_E_INVALID, "null slot buffer");
+  std::unique_lock<std::mutex> lk(ix->mu);
+  DeviceGuard g(ix->device);
+  ix->last_groups_path = 0;
+  ix->last_groups_tasks = ix->last_groups_rounds = 0;
+  const size_t n_slots = (size_t)nq * k;
+  for (size_t s = 0; s < n_slots; ++s)
+    if (slot_rows[s] >= 0 && (uint64_t)slot_rows[s] >= ix->n)
+      return fail(WDBX_E_INVALID, "slot %llu: row %lld of %llu stored rows", (u64)s, (long long)slot_rows[s], (u64)ix->n);
+  if (ix->n == 0) {  // (every slot is unused then)
+    std::fill(out_idx, out_idx + n_slots * (size_t)group_size, (int64_t)-1);
+    std::fill(out_score, out_score + n_slots * (size_t)group_size, 0.0f);
+    if (out_count) std::fill(out_count, out_count + n_slots, 0);
+    return WDBX_OK;
+  }
+  if (mask_words && (rc = check_mask_words(ix->n, mask_word_count))) return rc;
+  if (ix->n >= 0xFFFFFF00ull) return fail(WDBX_E_INVALID, "shard holds too many rows for 32-bit row keys");
+  std::vector<GroupSlot> slots;
+  if ((rc = group_slots(ix, slot_labels, slot_rows, n_slots, &slots))) return rc;
+  return group_members_pass(ix, queries, nq, k, group_size, normalize_queries, mask_words, slots, out_idx, out_score, out_count);
 } WDBX_CATCH
 
 // ---- multi-vector search: labels ranked by the sum of per-vector best scores (host_multivector.h, kernels_multivector.h,
@@ -2616,6 +2782,7 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"range_batch_min_queries", &wdbx_index::opt_range_batch_min_queries},
     {"range_pair_cap", &wdbx_index::opt_range_pair_cap},
     {"mmr_scratch_mib", &wdbx_index::opt_mmr_scratch_mib},
+    {"groups_segment_rows", &wdbx_index::opt_groups_segment_rows},
 };
 
 static int64_t* option_slot(wdbx_index* ix, const char* name) { return find_option(ix, kOptions, name); }
@@ -2634,6 +2801,9 @@ int wdbx_index_set_option(wdbx_index* ix, const char* name, int64_t value) try {
                 RANGE_PAIR_CAP_MIN, RANGE_PAIR_CAP_MAX);
   if (slot == &ix->opt_mmr_scratch_mib && (value < 1 || value > MMR_SCRATCH_MIB_MAX))
     return fail(WDBX_E_INVALID, "mmr_scratch_mib %lld outside [1, %lld]", (long long)value, (long long)MMR_SCRATCH_MIB_MAX);
+  if (slot == &ix->opt_groups_segment_rows && (value < GROUPS_SEGMENT_MIN || value > GROUPS_SEGMENT_MAX))
+    return fail(WDBX_E_INVALID, "groups_segment_rows %lld outside [%lld, %lld]", (long long)value, (long long)GROUPS_SEGMENT_MIN,
+                (long long)GROUPS_SEGMENT_MAX);
   if (slot == &ix->opt_scan_u42_share && value != -1 && value != 1 && value != 2 && value != 4)
     return fail(WDBX_E_INVALID, "scan_u42_share %lld: -1 (the default), 1, 2 or 4 queries per read", (long long)value);
   *slot = value;
@@ -2701,6 +2871,9 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "last_mmr_path")) return *value = ix->last_mmr_path, WDBX_OK;
   if (name && !strcmp(name, "last_recommend_path")) return *value = ix->last_recommend_path, WDBX_OK;
   if (name && !strcmp(name, "last_recommend_short")) return *value = ix->last_recommend_short, WDBX_OK;
+  if (name && !strcmp(name, "last_groups_path")) return *value = ix->last_groups_path, WDBX_OK;
+  if (name && !strcmp(name, "last_groups_tasks")) return *value = ix->last_groups_tasks, WDBX_OK;
+  if (name && !strcmp(name, "last_groups_rounds")) return *value = ix->last_groups_rounds, WDBX_OK;
   if (name && !strcmp(name, "last_mmr_rounds")) return *value = ix->last_mmr_rounds, WDBX_OK;
   if (name && !strcmp(name, "last_mmr_candidates")) return *value = ix->last_mmr_candidates, WDBX_OK;
   if (name && !strcmp(name, "last_sample_qn")) return *value = ix->last_sample_qn, WDBX_OK;

@@ -19,6 +19,7 @@ METRIC_L2 = 1
 MAX_K = 2048
 MAX_EXAMPLES = 64        # WDBX_MAX_EXAMPLES: positives + negatives of one recommend query
 MAX_EXCLUDE_ROWS = 1024  # WDBX_MAX_EXCLUDE_ROWS
+MAX_GROUP_SIZE = 64      # WDBX_MAX_GROUP_SIZE: members one group of wdbx_index_search_groups holds
 UNIQUE_ID_BYTES = 128
 
 _LIB_NAME = "libwdbx_hip.so"
@@ -74,6 +75,11 @@ SIGNATURES = {
     "wdbx_index_get_labels": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]),
     "wdbx_index_search_distinct": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
                                              _i64p, _f32p, C.POINTER(C.c_uint32)]),
+    "wdbx_index_search_groups": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32),
+                                           C.c_uint64, _i64p, _f32p, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
+    "wdbx_index_search_group_members": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32),
+                                                  C.c_uint64, C.POINTER(C.c_uint32), _i64p, _i64p, _f32p,
+                                                  C.POINTER(C.c_int32)]),
     "wdbx_index_search_multivector": (C.c_int, [C.c_void_p, _f32p, _u64p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32),
                                                 C.c_uint64, _i64p, _f32p, C.POINTER(C.c_uint32)]),
     "wdbx_index_search_mmr": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
@@ -423,6 +429,55 @@ class NativeIndex:
                                                     idx.ctypes.data_as(_i64p), score.ctypes.data_as(_f32p),
                                                     label.ctypes.data_as(u32p)))
         return idx, score, label
+
+    # -- search groups: the k best labels, each with its best group_size rows --
+    def search_groups(self, queries, k: int, group_size: int, normalize_queries: bool = False,
+                      mask_words: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """:meth:`search_distinct` with a group size: the groups are its labels, in its order, and each slot holds the
+        label's best ``group_size`` eligible rows, ranked as :meth:`search_rows` ranks them (the same score bits).  Returns
+        ``(rows int64 [nq, k, g], scores f32 [nq, k, g], labels uint32 [nq, k], counts int32 [nq, k])``; unused member
+        slots hold -1 / 0, unused groups -1 / 0 / :data:`LABEL_NONE` / 0.  ``mask_words`` as in :meth:`search`."""
+        q = _as_f32(queries, self.dim)
+        nq = q.shape[0]
+        shape = (nq, max(int(k), 0), max(int(group_size), 0))
+        idx = np.empty(shape, np.int64)
+        score = np.empty(shape, np.float32)
+        label = np.empty(shape[:2], np.uint32)
+        count = np.empty(shape[:2], np.int32)
+        u32p = C.POINTER(C.c_uint32)
+        m = None if mask_words is None else np.ascontiguousarray(mask_words, dtype=np.uint32)
+        # (k, group_size, nq and the mask's length are checked by the library, the length under the handle's lock)
+        _check(self._lib.wdbx_index_search_groups(self._h, q.ctypes.data_as(_f32p), nq, int(k), int(group_size),
+                                                  int(normalize_queries), None if m is None else m.ctypes.data_as(u32p),
+                                                  0 if m is None else m.size, idx.ctypes.data_as(_i64p),
+                                                  score.ctypes.data_as(_f32p), label.ctypes.data_as(u32p),
+                                                  count.ctypes.data_as(C.POINTER(C.c_int32))))
+        return idx, score, label, count
+
+    def search_group_members(self, queries, slot_labels, slot_rows, group_size: int, normalize_queries: bool = False,
+                             mask_words: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Stage 2 of :meth:`search_groups` on given slots ``[nq, k]``: a slot with ``slot_rows < 0`` is unused, one with
+        label :data:`LABEL_NONE` is the single row ``slot_rows``, any other label means that label's rows on this handle
+        (none: count 0).  Returns ``(rows [nq, k, g], scores [nq, k, g], counts [nq, k])``."""
+        q = _as_f32(queries, self.dim)
+        nq = q.shape[0]
+        lab = np.ascontiguousarray(slot_labels, dtype=np.uint32).reshape(nq, -1)
+        row = np.ascontiguousarray(slot_rows, dtype=np.int64).reshape(nq, -1)
+        if lab.shape != row.shape:
+            raise ValueError(f"slot_labels {lab.shape} and slot_rows {row.shape} differ")
+        k = lab.shape[1]
+        shape = (nq, k, max(int(group_size), 0))
+        idx = np.empty(shape, np.int64)
+        score = np.empty(shape, np.float32)
+        count = np.empty((nq, k), np.int32)
+        u32p = C.POINTER(C.c_uint32)
+        m = None if mask_words is None else np.ascontiguousarray(mask_words, dtype=np.uint32)
+        _check(self._lib.wdbx_index_search_group_members(self._h, q.ctypes.data_as(_f32p), nq, k, int(group_size),
+                                                         int(normalize_queries), None if m is None else m.ctypes.data_as(u32p),
+                                                         0 if m is None else m.size, lab.ctypes.data_as(u32p),
+                                                         row.ctypes.data_as(_i64p), idx.ctypes.data_as(_i64p),
+                                                         score.ctypes.data_as(_f32p), count.ctypes.data_as(C.POINTER(C.c_int32))))
+        return idx, score, count
 
     def search_multivector(self, vectors, offsets, k: int, normalize_queries: bool = False,
                            mask_words: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:

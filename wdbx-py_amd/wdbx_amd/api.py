@@ -63,8 +63,18 @@ async def search_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
     (``wdbx.vector_search_multivector_async``); not together with ``query_vector`` or ``distinct``.  ``"mmr": {"lambda": 0.5,
     "fetch_k": 40}`` (extension; absent or null = the plain search; both members optional, ``lambda`` in [0, 1], ``fetch_k``
     an integer >= ``limit`` or null): the results are picked by maximal marginal relevance from the ``fetch_k`` best and come
-    in pick order (``wdbx.vector_search_mmr_async``); not together with ``distinct`` or ``query_vectors``."""
+    in pick order (``wdbx.vector_search_mmr_async``); not together with ``distinct`` or ``query_vectors``.  ``"group_size": n``
+    (extension; an integer >= 1; absent or null = no groups): the best ``limit`` values of ``DISTINCT_KEY``, each with its
+    best ``n`` vectors (``wdbx.vector_search_groups_async``); the response is ``{"groups": [{"key", "hits": [{"vector_id",
+    "similarity", "metadata"}, ...]}, ...]}``; with or without ``"distinct": true``, not together with ``mmr`` or
+    ``query_vectors``."""
     limit, threshold, flt = _parse_common(payload)
+    group_size = payload.get("group_size")
+    if group_size is not None:
+        if isinstance(group_size, bool) or not isinstance(group_size, int) or group_size < 1:
+            raise ValueError("group_size must be an integer >= 1, or null")
+        if payload.get("mmr") is not None or payload.get("query_vectors") is not None:
+            raise ValueError("group_size goes with query_vector alone: neither mmr nor query_vectors")
     mmr = payload.get("mmr")
     if mmr is not None:
         if not isinstance(mmr, dict) or set(mmr) - {"lambda", "fetch_k"}:
@@ -96,6 +106,9 @@ async def search_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
     distinct = payload.get("distinct")
     if distinct is not None and not isinstance(distinct, bool):
         raise ValueError("distinct must be true, false or null")
+    if group_size is not None:
+        groups = await wdbx.vector_search_groups_async(query, limit, group_size, threshold, flt)
+        return {"groups": [{"key": g["key"], "hits": _render(g["hits"])["results"]} for g in groups]}
     if distinct:
         return _render(await wdbx.vector_search_distinct_async(query, limit, threshold, flt))
     return _render(await wdbx.vector_search_async(query, limit, threshold, flt))

@@ -853,6 +853,63 @@ class HipFlatIndex(VectorIndex):
                 return []
             raise
 
+    # ---- search groups (extension: the best labels, each with its best group_size vectors, wdbx_index_search_groups) ----
+    def search_groups(self, query_vector: np.ndarray, limit: int = 10, group_size: int = 3,
+                      mask=None) -> List[Tuple[int, List[Tuple[str, float]]]]:
+        """The best ``limit`` labels of this shard as ``search_distinct`` ranks them, each with its best ``group_size``
+        vectors, best first: ``[(label, [(id, score), ...])]``.  ``mask`` as ``search``'s ``row_mask``.  Errors are swallowed
+        or raised as in ``search``."""
+        try:
+            actual_limit = min(int(limit), _native.MAX_K)
+            g = min(int(group_size), _native.MAX_GROUP_SIZE)
+            if self.next_index == 0 or actual_limit <= 0 or g <= 0:
+                return []
+            q = self._prepare(query_vector)
+            words = None
+            if mask is not None:
+                words = mask if mask.dtype == np.uint32 else _native.pack_row_mask(mask)
+            idx, score, label, _ = self._native.search_groups(q, actual_limit, g, mask_words=words)
+            return [(int(lab), self._map(i, s)) for i, s, lab in zip(idx[0], score[0], label[0]) if i[0] != -1]
+        except Exception as e:
+            logger.error("Error in HIP groups search: %s", e)
+            if self.swallow_errors:
+                return []
+            raise
+
+    def group_members(self, query_vector: np.ndarray, groups, group_size: int = 3, mask=None) -> List[List[Tuple[str, float]]]:
+        """For each of ``groups`` -- ``(label, vector_id)``: a label other than ``_native.LABEL_NONE`` means this shard's
+        vectors under it, LABEL_NONE means the single vector ``vector_id`` (nothing when this shard does not hold it) -- the
+        best ``group_size`` vectors, best first: one ``[(id, score)]`` per group, in order.  ``mask`` as ``search``'s
+        ``row_mask``.  Errors are swallowed or raised as in ``search``."""
+        groups = list(groups)
+        try:
+            g = min(int(group_size), _native.MAX_GROUP_SIZE)
+            if self.next_index == 0 or not groups or g <= 0:
+                return [[] for _ in groups]
+            q = self._prepare(query_vector)
+            words = None
+            if mask is not None:
+                words = mask if mask.dtype == np.uint32 else _native.pack_row_mask(mask)
+            labels = np.full(len(groups), _native.LABEL_NONE, np.uint32)
+            rows = np.full(len(groups), -1, np.int64)
+            for i, (label, vid) in enumerate(groups):
+                if label != _native.LABEL_NONE:
+                    labels[i], rows[i] = label, 0
+                else:
+                    row = self._row_of(vid)
+                    rows[i] = -1 if row is None else row
+            out: List[List[Tuple[str, float]]] = []
+            for c0 in range(0, len(groups), _native.MAX_K):  # (a call takes MAX_K slots per query)
+                idx, score, _ = self._native.search_group_members(q, labels[None, c0:c0 + _native.MAX_K],
+                                                                  rows[None, c0:c0 + _native.MAX_K], g, mask_words=words)
+                out.extend(self._map(i, s) for i, s in zip(idx[0], score[0]))
+            return out
+        except Exception as e:
+            logger.error("Error in HIP group members search: %s", e)
+            if self.swallow_errors:
+                return [[] for _ in groups]
+            raise
+
     def search_multivector(self, vectors, limit: int = 10, mask=None) -> List[Tuple[str, float, int]]:
         """Late interaction (MaxSim) over this shard: the labels ranked by the sum over the query's ``vectors`` of each
         vector's best score among the label's rows, best first: ``[(id of the label's first row, score, label)]``, scores in

@@ -1135,6 +1135,64 @@ class VectorStore:
         return await loop.run_in_executor(self.thread_pool, lambda: self.search_distinct(
             query_vector, limit=limit, threshold=threshold, filter_metadata=filter_metadata))
 
+    # ---- search groups (extension: the best values of DISTINCT_KEY, each with its best group_size vectors) ----
+    def search_groups(self, query_vector: List[float], limit: int = 10, group_size: int = 3, threshold: float = 0.0,
+                      filter_metadata: Optional[Dict[str, Any]] = None) -> List[Tuple[int, List[Result]]]:
+        """``search_distinct`` with a group size: the best ``limit`` values of the metadata field named by config
+        ``DISTINCT_KEY``, each with its best ``group_size`` vectors (ten documents, each with its three best chunks); a
+        vector without the field is a group of its own.  Returns ``[(label, [(vector_id, score, metadata), ...])]``, groups
+        and members best first.  One shard: one ``wdbx_index_search_groups`` call.  Several shards: every shard answers
+        ``search_distinct``, the merge of ``search_distinct`` picks the global labels, every shard then answers
+        ``group_members`` for them (a label's other rows may lie on shards where it did not make the top-``limit``), and
+        each label's members are merged by (score descending, shard, position) and cut at ``group_size``.
+        ``filter_metadata`` always travels as the shards' row masks.  ``threshold`` drops the groups whose best member is
+        below it, and the members below it."""
+        if self.config.get("DISTINCT_KEY") is None:
+            raise ValueError("search_groups needs config DISTINCT_KEY: the metadata field whose values label the vectors")
+        if int(group_size) < 1:
+            raise ValueError(f"group_size must be at least 1, got {group_size}")
+        query = _as_query(query_vector)
+        if query.shape != (self.vector_dim,):
+            raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {query.shape}")
+        masks = self._row_masks(filter_metadata) if filter_metadata else [None] * len(self.indices)
+        work = list(zip(self.indices, masks))
+        if len(work) == 1:
+            groups = work[0][0].search_groups(query, limit, group_size, mask=work[0][1])
+        else:
+            one = lambda a: a[0].search_distinct(query, limit, mask=a[1])  # noqa: E731
+            per_shard = list(self._shard_pool.map(one, work))
+            ranked = sorted(((-score, shard, pos, vid, label) for shard, res in enumerate(per_shard)
+                             for pos, (vid, score, label) in enumerate(res)), key=lambda t: t[:3])
+            seen, chosen = set(), []
+            for _, _, _, vid, label in ranked:
+                if label != _native.LABEL_NONE:
+                    if label in seen:
+                        continue
+                    seen.add(label)
+                chosen.append((label, vid))
+                if len(chosen) >= limit:
+                    break
+            two = lambda a: a[0].group_members(query, chosen, group_size, mask=a[1])  # noqa: E731
+            members = list(self._shard_pool.map(two, work))  # [shard][group] -> [(vid, score)]
+            groups = []
+            for gi, (label, _) in enumerate(chosen):
+                merged = sorted(((-score, shard, pos, vid) for shard, res in enumerate(members)
+                                 for pos, (vid, score) in enumerate(res[gi])), key=lambda t: t[:3])
+                groups.append((label, [(vid, -neg) for neg, _, _, vid in merged[:int(group_size)]]))
+        out = []
+        for label, hits in groups:
+            if threshold > 0:
+                hits = [(vid, score) for vid, score in hits if score >= threshold]
+            if hits:
+                out.append((label, [(vid, score, self.metadata.get(vid, {})) for vid, score in hits]))
+        return out
+
+    async def search_groups_async(self, query_vector: List[float], limit: int = 10, group_size: int = 3, threshold: float = 0.0,
+                                  filter_metadata: Optional[Dict[str, Any]] = None) -> List[Tuple[int, List[Result]]]:
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(self.thread_pool, lambda: self.search_groups(
+            query_vector, limit=limit, group_size=group_size, threshold=threshold, filter_metadata=filter_metadata))
+
     # ---- multi-vector search (extension: late interaction over the documents DISTINCT_KEY names) ----
     def search_multivector(self, query_vectors: List[List[float]], limit: int = 10, threshold: float = 0.0,
                            filter_metadata: Optional[Dict[str, Any]] = None) -> List[Result]:

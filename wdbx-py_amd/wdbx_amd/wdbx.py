@@ -164,6 +164,31 @@ class WDBX:
         return await self.vector_store.search_distinct_async(query_vector, limit=limit, threshold=threshold,
                                                              filter_metadata=filter_metadata)
 
+    def _render_groups(self, groups) -> List[Dict[str, Any]]:
+        key = self.vector_store.config.get("DISTINCT_KEY")
+        out = []
+        for _, hits in groups:
+            meta = hits[0][2]
+            out.append({"key": meta[key] if isinstance(meta, dict) and key in meta else hits[0][0], "hits": hits})
+        return out
+
+    def vector_search_groups(self, query_vector: List[float], limit: int = 10, group_size: int = 3, threshold: float = 0.0,
+                             filter_metadata: Optional[Dict[str, Any]] = None) -> List[Dict[str, Any]]:
+        """Extension: ``vector_search_distinct`` with a group size -- the best ``limit`` values of the metadata field named
+        by config ``DISTINCT_KEY``, each with its best ``group_size`` vectors (ten documents, each with its three best
+        chunks).  Each group is ``{"key": <the DISTINCT_KEY value, or the vector id of a vector without the field>, "hits":
+        [(vector_id, score, metadata), ...]}``, groups and hits best first.  Exact; a filter is pushed down."""
+        self._check_dim(query_vector)
+        return self._render_groups(self.vector_store.search_groups(query_vector, limit=limit, group_size=group_size,
+                                                                   threshold=threshold, filter_metadata=filter_metadata))
+
+    async def vector_search_groups_async(self, query_vector: List[float], limit: int = 10, group_size: int = 3,
+                                         threshold: float = 0.0,
+                                         filter_metadata: Optional[Dict[str, Any]] = None) -> List[Dict[str, Any]]:
+        self._check_dim(query_vector)
+        return self._render_groups(await self.vector_store.search_groups_async(
+            query_vector, limit=limit, group_size=group_size, threshold=threshold, filter_metadata=filter_metadata))
+
     def vector_search_multivector(self, query_vectors: List[List[float]], limit: int = 10, threshold: float = 0.0,
                                   filter_metadata: Optional[Dict[str, Any]] = None) -> List[Result]:
         """Extension: late interaction (MaxSim).  The query is several vectors; the documents named by config ``DISTINCT_KEY``
