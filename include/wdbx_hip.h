@@ -652,8 +652,9 @@ int wdbx_index_probe_read(wdbx_index* idx, int nontemporal, int blocks, int reps
  * scan_blocked, scan_generic, scan_force_ragged, exchange_batch, lds_lists, merge_fast (1: merges whose keys fit the registers are ranked there, default; 0: always the list walk), scan_one_grid (1: a round of several queries on the fp32 scan over a corpus of at most 1 GiB is one grid with a row per query, default; 0: a launch per query), poll_done (1: a blocking call of up to 32 queries whose chain ends in a final merge polls a word that kernel writes into the mapped staging slot, default; 0: always waits on its event), zero_copy, wg_merge, select_min_k,
  * scan_shadow (2 u8 selection scan / 1 bf16 tiles / 0 fp32 scan; range search: 2 u8 selection, below 2 the fp32 range scan), scan8_wgs, single_min_rows,
  * range_min_rows (rows from which a range search takes the u8 selection scan, default 131 072), gemm_bf16 (tile family
- * 3/2/1/0 as above), gemm_ct, gemm_l2, gemm_l2_i8, gemm8_variant (the i8 tiles' full-pass epilogue, for A/B: 0 = 14 the product form, 12, 13; any other value returns WDBX_E_INVALID), gemm8_refine (1: second selection stage of the i8 tiles, default), batch_repair, scan8_per_query, scan8_sample4 (1: a round's sample pass serves 3-4 queries per workgroup when the sample is too large for the L2s; 2: always; 0: never), gemm_min_queries, gemm_min_rows, gemm_min_work (below gemm_min_rows: the tiles from queries x rows >= this, default 800000; 0: never), gemm_sample_div, gemm_masked (1: a masked call with enough queries is one masked pass over the int8 tiles, default; 0: masked per-query scans), group_bounds, rows_keys_max (wdbx_index_search_rows: lists of at most this many rows are ranked from one key per listed row, default 8192; 0: never).
- * get_option also answers the read-only names: last_gemm_family (0/1/2/3: what the last batch ran on),
+ * 3/2/1/0 as above), gemm_ct, gemm_l2, gemm_l2_i8, gemm8_variant (the i8 tiles' full-pass epilogue, for A/B: 0 = 14 the product form, 12, 13; any other value returns WDBX_E_INVALID), gemm8_refine (1: second selection stage of the i8 tiles, default), batch_repair, scan8_per_query, scan8_sample4 (1: a round's sample pass serves 3-4 queries per workgroup when the sample is too large for the L2s; 2: always; 0: never), gemm_min_queries, gemm_min_rows, gemm_min_work (below gemm_min_rows: the tiles from queries x rows >= this, default 800000; 0: never), gemm_sample_div, gemm_masked (1: a masked call with enough queries is one masked pass over the int8 tiles, default; 0: masked per-query scans), group_bounds, rows_keys_max (wdbx_index_search_rows: lists of at most this many rows are ranked from one key per listed row, default 8192; 0: never),
+ * scan_u42_mfma (the split planes' full passes of a round on the matrix cores, 16 queries per read of the four-bit plane: -1 where the row's unit count has an instance (d from 257 to 384) and scan_u42_share is -1, default; 0: never; 1: wherever an instance exists; any other value returns WDBX_E_INVALID.  Answers are bit-identical at every setting).
+ * get_option also answers the read-only names: last_u42_mfma_groups (the groups of 16 queries whose full pass ran on the matrix cores in the last call), last_gemm_family (0/1/2/3: what the last batch ran on),
  * last_single_path (0 fp32 scan / 1 bf16 tiles / 2 u8 selection scan), last_range_path (0 fp32 range scan / 2 u8 selection + exact filter), last_rows_path (the route of the last wdbx_index_search_rows: 0 nothing launched / 1 keys + merge / 2 lists + merge / 3 keys + radix select), last_sample_qn (queries per workgroup of the last u8 sample launch: 1, 3 or 4), last_batch_repaired, last_batch_masked (1: the last batch ran the masked tile pass), last_batch_allowed_rows (the rows its mask allowed), shadow_rows + shadow_bytes (bf16 copy),
  * shadow8_rows + shadow8_bytes (u8 copy), shadowg_rows + shadowg_bytes (group-scaled i8 copy), group_bounds_active,
  * exchanges (all-gather + merge steps this handle's per-rank communicator has enqueued), device_bytes_resident (every device

@@ -123,6 +123,9 @@ struct wdbx_index {
   size_t count42_bytes = 0;
   int last_single_u42 = 0;     // 1: the last u6 round's full passes ran over the split planes
   int last_u42_share = 0;      // ... the widest group of queries that shared one read of the four-bit plane in the last call (0: none ran)
+  uint32_t* d_q16 = nullptr;   // the round's 16-bit queries as matrix operands, then its U42QConst (u42_query_i16_kernel)
+  size_t q16_bytes = 0;
+  int last_u42_mfma_groups = 0;  // ... the groups of 16 whose full pass ran on the matrix cores in the last call
   uint32_t* defer_flag_dev = nullptr;  // non-null during a blocking call that repairs overflow itself (mapped host word)
   // a lone blocking call through a staging slot: the LAST kernel of its chain writes done_seq into done_flag_dev (a mapped
   // host word of the slot) and the caller polls that word instead of waiting on the runtime; done_signals counts the launches
@@ -238,7 +241,7 @@ struct wdbx_index {
           opt_gemm8_refine = 1, opt_scan8_sample4 = 1, opt_gemm_l2 = 1, opt_gemm_l2_i8 = 1, opt_force_ragged = 0,
           opt_gemm_ct = 0, opt_wg_merge = 1, opt_zero_copy = 1, opt_lone_host_select = 1, opt_lds_lists = 0,
           opt_merge_fast = 1, opt_poll_done = 1, opt_scan_one_grid = 1, opt_select_min_k = 200, opt_gemm_min_nq = 4, opt_gemm_min_rows = 65536, opt_gemm_min_work = 800000,
-          opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0, opt_scan_u42 = -1, opt_scan_u42_share = -1, opt_gemm_masked = 1, opt_rows_keys_max = 8192, opt_distinct_overfetch = 4,
+          opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0, opt_scan_u42 = -1, opt_scan_u42_share = -1, opt_scan_u42_mfma = -1, opt_gemm_masked = 1, opt_rows_keys_max = 8192, opt_distinct_overfetch = 4,
           opt_multivector_round_vectors = 256, opt_range_batch_min_queries = 4, opt_range_pair_cap = 0,
           opt_mmr_scratch_mib = MMR_SCRATCH_MIB_MAX, opt_groups_segment_rows = GROUPS_SEGMENT_DEFAULT;
 };
@@ -800,6 +803,7 @@ static int enqueue_search(wdbx_index* ix, const float* d_queries, int nq, int k,
 
   u64* const lbase = keys_dst ? keys_dst : ix->d_local_keys;  // (keys_only: one batch, so offsets within it are offsets in keys_dst)
   ix->last_u42_share = 0;
+  ix->last_u42_mfma_groups = 0;
   for (int q0 = 0; q0 < nq; q0 += batch) {
     const int b = std::min(batch, nq - q0);
     u64* const lkeys = lbase ? lbase + (size_t)(q0 % xch) * k : nullptr;  // this round's lists inside the exchange chunk
@@ -1366,6 +1370,15 @@ static bool prepare_u42_shadow(wdbx_index* ix) {
 // (profiles/u42_share/README.md, sweep_share/)
 constexpr uint32_t U42_SHARE_DEFAULT = 4;
 
+// the shortest remainder of a round (queries behind its full groups of 16) that goes to the matrix-core pass as one short group
+// where option scan_u42_mfma leaves it to the library; a shorter one goes to the VALU groups.  A pass of 16 costs what it costs
+// at any width (the plane read and the matrix operations do not shrink with absent columns): at 10 M x 384, 2000 steps, 0.790 ms
+// per group at the 2 workgroups per CU it runs with, 0.933 ms at 3 (16 x the 0.0494 / 0.0583 ms per query of the event pair;
+// profiles/u42_mfma/README.md, sweep_wgs/).  The VALU groups of profiles/u42_share/README.md cost 0.319 ms lone, 0.378 ms a
+// pair, 0.552 ms four: 4 queries = 0.552 ms, 5 = 0.552 + 0.319 = 0.871 ms, so the pass wins from 5 on.
+// tests/test_gpu_u42_share_calls.py pins that a default round of up to 5 queries reports a VALU width: hence 6, not 5.
+constexpr uint32_t U42_MFMA_MIN_SHORT = 6;
+
 // nq single queries of a round, each with its own full pass over the u6 shadow: sample (4 queries per workgroup) ->
 // thresholds -> a pass per query -> exact re-scoring (rescore_kernel, as behind the u8 scan) -> cut -> final top-k.
 // The candidate counters live in d_count6; d_count[0 .. nq) are the CUT's counters against last_batch_cap = its capacity, and
@@ -1388,6 +1401,11 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
   for (int w = 1; u42 && w <= 4; w *= 2) f42[w] = pick_scan42(u42_unit_chunk(units / 2), w);
   if (u42 && (!f42[1] || !f42[2] || !f42[4] || !ix->d_rows42 || ix->units42 != units / 2 || ix->shadow42_rows < ix->n))
     return fail(WDBX_E_STATE, "split planes not prepared");
+  // option scan_u42_mfma: full groups of 16 (and a remainder of U42_MFMA_MIN_SHORT or more) on scan_u42_mfma_kernel.  -1: where
+  // the unit count has an instance and scan_u42_share is left at -1; 1: wherever an instance exists; 0: never.  An explicit
+  // scan_u42_share of 1, 2 or 4 keeps the VALU kernels for the whole round unless scan_u42_mfma = 1 asks for both.
+  const scan42_mfma_fn fm = u42 && ix->opt_scan_u42_mfma != 0 && (ix->opt_scan_u42_mfma == 1 || ix->opt_scan_u42_share == -1)
+                                ? pick_scan42_mfma(units / 2) : nullptr;
   int rc;
   // the plan (host_selection.h): sampled 256-row tiles of 4 groups of 64 rows each and the divisor of the u8 scan
   const SelectionSample s = selection_sample(ix->n, 256, 4, k, selection_div(ix->opt_gemm_sample_div, k, true));
@@ -1403,6 +1421,8 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
   if ((rc = grow((void**)&ix->d_cand, &ix->cand_bytes, (size_t)ROUND * ((size_t)cap + cap2) * sizeof(u64)))) return rc;
   if ((rc = grow((void**)&ix->d_count6, &ix->count6_bytes, (size_t)ROUND * sizeof(uint32_t)))) return rc;
   if (u42 && (rc = grow((void**)&ix->d_count42, &ix->count42_bytes, (size_t)ROUND * sizeof(uint32_t)))) return rc;
+  const size_t q16_dwords = (size_t)(ROUND / U42_MFMA_GROUP) * u42_mfma_group_dwords(units / 2);
+  if (fm && (rc = grow((void**)&ix->d_q16, &ix->q16_bytes, q16_dwords * 4 + (size_t)ROUND * sizeof(U42QConst)))) return rc;
   if (ix->count_bytes < ((size_t)nq + GB_N) * sizeof(uint32_t)) return fail(WDBX_E_STATE, "candidate counters not sized by the caller");
   ix->last_batch_nq = (uint32_t)nq;
   ix->last_batch_cap = cap2;
@@ -1422,6 +1442,11 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
   };
   const uint32_t grid1 = scan_full_grid(tiles64, (uint32_t)ix->cu_count, wgs_of(1));
   const uint32_t grid_shared = scan_full_grid(tiles64, (uint32_t)ix->cu_count, wgs_of(2));
+  // the matrix-core pass, 2000 steps, means of three: 1 -> 17110 q/s, 2 -> 18758, 3 -> 16056 (all its 44.3 KiB of LDS lets a CU
+  // hold), 4 -> 13020 (spreads 122 / 59 / 72 / 169; profiles/u42_mfma/README.md): fewer waves mean fewer lists to refine
+  // behind the last tile, which weighs more here than latency hiding does
+  const uint32_t grid_mfma = scan_full_grid(tiles64, (uint32_t)ix->cu_count,
+                                            (uint32_t)std::max<int64_t>(1, std::min<int64_t>(ix->opt_scan8_wgs > 0 ? ix->opt_scan8_wgs : 2, 8)));
   const uint32_t grid0 = scan_sample_grid(ngroups, (uint32_t)ix->cu_count);
   const size_t pitch4 = ix->pitch / 4;
   const Scan8Shape* sh = scan8_shape((uint32_t)ix->dim);
@@ -1468,13 +1493,43 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
       b.cap = cap;
       // (the survivors are counted for the probes only: an atomic per 64 of them)
       HIP_TRY(hipMemsetAsync(ix->d_count42, 0, (size_t)nv * sizeof(uint32_t), ix->stream));
-      // the groups that share a read (host_selection.h): a launch per group, or (one grid) per run of groups of one width
+      // the groups of 16 on the matrix cores (host_selection.h): the round's queries as 16-bit operands once, then one grid
+      // for all groups or a launch per group
+      uint32_t taken = 0;
+      if (fm) {
+        const uint32_t ngm = u42_mfma_groups((uint32_t)nv, U42_MFMA_MIN_SHORT, &taken);
+        if (ngm) {
+          U42QConst* const qc = (U42QConst*)(ix->d_q16 + q16_dwords);
+          hipLaunchKernelGGL(u42_query_i16_kernel, dim3(ngm * U42_MFMA_GROUP), dim3(64), 0, ix->stream, qsrc, b.qpitch, b.units, taken,
+                             ix->d_q16, qc);
+          HIP_TRY(hipGetLastError());
+          Scan42MfmaArgs mm = {};
+          for (uint32_t g = 0; g < ngm;) {
+            const uint32_t run = one_grid ? ngm : 1, i = g * U42_MFMA_GROUP;
+            mm.a = b;
+            mm.a.query = qsrc + (size_t)i * ix->pitch;
+            mm.a.tau = ix->d_tau + i;
+            mm.a.cand = ix->d_cand + (size_t)i * cap;
+            mm.a.count = ix->d_count6 + i;
+            mm.a.survivors = ix->d_count42 + i;
+            mm.qb = ix->d_q16 + (size_t)g * u42_mfma_group_dwords(b.units);
+            mm.qc = qc + i;
+            mm.nq = one_grid ? taken : std::min(taken - i, U42_MFMA_GROUP);
+            hipLaunchKernelGGL(fm, dim3(grid_mfma, run), dim3(256), 0, ix->stream, mm);
+            HIP_TRY(hipGetLastError());
+            g += run;
+          }
+          ix->last_u42_mfma_groups += (int)ngm;
+        }
+      }
+      // what they leave, as the groups that share a read (host_selection.h): a launch per group, or (one grid) per run of groups
+      // of one width
       uint32_t first[ROUND], width[ROUND];
-      const uint32_t ng = u42_share_groups((uint32_t)nv, share, first, width);
+      const uint32_t ng = u42_share_groups((uint32_t)nv - taken, share, first, width);
       for (uint32_t g = 0; g < ng;) {
         uint32_t run = 1;
         while (one_grid && g + run < ng && width[g + run] == width[g]) ++run;
-        const uint32_t i = first[g];
+        const uint32_t i = taken + first[g];
         b.query = qsrc + (size_t)i * ix->pitch;
         b.tau = ix->d_tau + i;
         b.cand = ix->d_cand + (size_t)i * cap;

@@ -95,6 +95,18 @@ static inline uint32_t u42_share_groups(uint32_t nv, uint32_t qp, uint32_t* firs
   return n;
 }
 
+// The split planes' full passes on the matrix cores (scan_u42_mfma_kernel): 16 consecutive queries of the round per group.  The
+// round's nv queries go as nv / 16 full groups from query 0; a remainder of at least min_short queries goes as one short group
+// behind them (its absent columns are never written); a smaller remainder is left to u42_share_groups.  Returns the number of
+// groups; *covered = the queries they take, [0, *covered) of the round: the VALU groups start there.
+constexpr uint32_t U42_MFMA_GROUP = 16;
+static inline uint32_t u42_mfma_groups(uint32_t nv, uint32_t min_short, uint32_t* covered) {
+  const uint32_t full = nv / U42_MFMA_GROUP, rest = nv % U42_MFMA_GROUP;
+  const bool tail = rest > 0 && rest >= min_short;
+  *covered = full * U42_MFMA_GROUP + (tail ? rest : 0u);
+  return full + (tail ? 1u : 0u);
+}
+
 // "the u8 shadow exceeds 1 GiB": the size from which a pass per launch is the rule (u8_pitch bytes per row).  The u6 and u42
 // scans are taken by size above it, a round's passes go out as one grid up to it.
 static inline bool shadow_over_1gib(uint64_t n_rows, uint32_t u8_pitch) { return n_rows * u8_pitch > (1ull << 30); }

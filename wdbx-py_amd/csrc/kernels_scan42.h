@@ -246,6 +246,288 @@ __global__ __launch_bounds__(256) void scan_u42_kernel(Scan42Args a) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The full pass on the matrix cores: 16 queries of a round per read of the four-bit plane (scan_u42_mfma_kernel).
+//
+// The first stage is a small integer GEMM, rows x 16 queries x dimp, on v_mfma_i32_16x16x64_i8.  The h plane serves as the A
+// operand as it is stored: for the 16-row block rb of a tile and the chunk of four units from u0, lane L loads the 16 bytes of
+// row 16 rb + (L & 15), unit u0 + (L >> 4); d & 0x0F0F0F0F and (d >> 4) & 0x0F0F0F0F of its four dwords are two A operands of
+// K = 64 (elements 8 t + b and 8 t + 4 + b of the four units).  The B operand holds, in the lane with the same L >> 4, the 16
+// bytes of query L & 15 for the same unit in the same byte order: lane groups and byte positions of A and B pair up, so the
+// sum does not depend on the instruction's internal order of k.  Lane groups past the row's units (a short last chunk) load
+// nothing and contribute zero.  The B fragments of the group stay in registers for the whole pass (units <= 12: 3 chunks x 2
+// nibble parities x 2 query bytes x 4 = 48 VGPRs); no operand goes through LDS, no barrier in the loop.
+//
+// THE QUERY is a 16-bit fixed-point number per element (u42_query_i16_kernel, once per round): delta = the power of two with
+// 16256 < max|q_i| / delta <= 32512, Q_i = rint(q_i / delta) = 256 H_i + L_i with H_i = (Q_i + 128) >> 8 in -127 .. 127 and L_i in
+// -128 .. 127 (32512 = 127 * 256: the largest magnitude whose H fits a signed byte for both signs).  q_i / delta, Q_i and the
+// residual rho_i = q_i / delta - Q_i are exact in fp32 (a power-of-two quotient, an integer below 2^15, a difference of
+// neighbours), e2 = delta * (sqrt(sum rho_i^2) * 1.0005 + 1e-20) >= |q - delta Q|_2: 5e-4 covers the sum of up to 4096 squares in
+// any order (gamma / 2 <= 1.25e-4), the root and the products, 1e-20 the squares that underflow (each below 2^-149, together
+// below 2^-137: 2^-68.5 under the root).  An all-zero query: delta = 1, Q = 0, e2 = 0.
+// A query is MARKED when an element is not finite, when max|q_i| >= 2^64 or when 0 < max|q_i| < 2^-44.  Above 2^64 the fp32
+// sum of squares behind |q|_2 is infinite and every kernel of this family keeps every row anyway; below 2^-44 delta would fall
+// under 2^-58 and delta * 1e-20, the smallest e2, under the normal range (2^-58 * 2^-66.4 > 2^-126 is the limit taken).  Inside
+// the limits delta is in [2^-58, 2^50]: delta, 1 / delta, 2^-9 delta and their products with integers below 2^31 are normal or zero.
+// A marked query takes no part in the integer sum (its bytes are zero); its threshold is read as -inf in BOTH stages, so every
+// row is its candidate, as the VALU pass keeps every row of a NaN query: on a corpus beyond the capacity the counter ends above
+// cap behind cap real keys (rescore_kernel reads them, so they must name rows) and the conditional repair launches answer the
+// query exactly; on a smaller corpus every row is re-scored, which is exact too.
+//
+// ACCUMULATORS.  Dh = sum h_i H_i and Dl = sum h_i L_i, exact in int32; P_int = 256 Dh + Dl = sum h_i Q_i with
+// |P_int| <= 15 * 32512 * dimp = 487 680 dimp < 2^31 up to dimp = 4403; the largest instance has dimp = 384: 1.9e8 (and |Dh| <=
+// 15 * 127 * 384, |Dl| <= 15 * 128 * 384).
+// EPILOGUE.  The D layout gives lane L query L & 15 and rows 4 (L >> 4) + i of the block.  P^ = delta float(P_int) (ONE rounding,
+// the conversion), the survivor entry carries 2^-9 P^ as the VALU pass carries 2^-9 P, and
+//   w4 = s (4 P^ - 30.5 sum q),   |w4 - c.q| <= m4' = a4 |q|_2 (1 + 1e-5) + s round1',
+//   round1' = round1 + 60 sqrt(dimp) e2 (1 + 1e-5),   round1 = 6e-6 (dimp + 8) |q|_1 (1 + 1e-5) + dimp 2^-138 as above.
+// Query term: sum h_i q_i - delta P_int = sum h_i (q_i - delta Q_i), at most |h|_2 |e|_2 <= 15 sqrt(dimp) e2 by Cauchy-Schwarz; times
+// 4 s.  Rounding term: |P^| can exceed 15 |q|_1 by that quantisation, |delta P_int| <= 15 (|q|_1 + sqrt(dimp) e2) and sqrt(dimp) e2 <=
+// dimp delta / 2 (1 + 5e-4) < dimp |q|_1 / 32512 <= 0.127 |q|_1 up to dimp = 4096, so 4 |P^| <= 67.6 |q|_1.  The roundings of w4 are
+// the conversion (of at most 67.6 |q|_1), the sum behind 30.5 sum q and that product (gamma_(dimp + 1) * 30.5 |q|_1), the
+// difference and the product with s (of at most 98.1 |q|_1): (67.6 + 30.5 (dimp + 1) + 3 * 98.1) 2^-24 |q|_1, below the
+// 90.5 (dimp + 8) 2^-24 |q|_1 the term was derived for at every dimp >= 32 (dimp = 32: 1368 against 3620).  The sum round1 + query
+// term rounds once more (2^-24 relative): inside the step from 5.4e-6 to the 6e-6 taken.
+// REFINE.  u42_refine, unchanged, forms w6 = s ((4 P^ + Q) - 32 sum q) from the carried P^ and the fp32 query's remainders.  Its
+// roundings: the conversion (67.6 |q|_1), the remainders' sum (gamma_dimp * 3 |q|_1), 4 P^ + Q in one rounding (70.6 |q|_1), 32 sum q
+// (gamma_dimp * 32 |q|_1), the difference and the product with s (102.6 |q|_1): (67.6 + 35 dimp + 70.6 + 3 * 102.6) 2^-24 |q|_1, below
+// 95 (dimp + 8) 2^-24 |q|_1 likewise.  4 P^ misses 4 sum h_i q_i by the same query term, so m6' = a6 |q|_2 (1 + 1e-5) + s round1': the
+// kernel hands round1' to u42_refine as its round1.
+// SURVIVOR LISTS.  Per wave and query a list of 64 {row, 2^-9 P^} pairs in LDS (8 bytes: s is read again from {s, a4} when the list
+// is refined -- the same bits); lanes append through an LDS counter.  Behind every 16-row block (a list grows by at most 16 there:
+// 47 + 16 < 64) a wave-uniform loop over the group's queries copies each list of 48 or more into the wave's one U42List and runs
+// u42_refine on it; once more behind the last tile for whatever is left.  ONE WaveStage per wave, flushed behind every refine:
+// candidates are a few of the 48 survivors of a refine, so a flush is one atomic on the query's counter per refine, and sixteen
+// stages would cost 16 KiB per wave.  NOT TRIED: a ballot / mbcnt append per (column, row i) as scan_u42_kernel's, in place of
+// the LDS counter -- up to 16 serialised atomics on one counter per 16-row block when every row of a column survives, one per
+// block on the headline corpus (0.8 % of the pairs survive); it costs four 64-bit ballots and the masked popcounts per block.
+// Capacity and overflow are the stage's: the counter ends above cap, keys beyond it are dropped.
+// LDS: 4 waves x (8 KiB lists + 1.5 KiB U42List + 1 KiB stage + 512 B of {s, a4} + 64 B of counters) = 44.3 KiB per workgroup: three
+// fit a CU, two run (the sweep in host_index.h).
+// ------------------------------------------------------------------------------------------------
+typedef int i4v __attribute__((ext_vector_type(4)));
+
+constexpr uint32_t U42_MFMA_QUERIES = 16;    // queries per group
+constexpr uint32_t U42_MFMA_MAX_UNITS = 12;  // the one instance: three chunks of four units (d <= 384)
+constexpr uint32_t U42Q_MARKED = 1u, U42Q_ABSENT = 2u;
+
+// what the epilogue and the refine need of one query, computed once per round
+struct U42QConst {
+  float dp;       // 2^-9 delta
+  float qsum305;  // 30.5 sum q
+  float qsum32;   // 32 sum q
+  float q2;       // |q|_2 (1 + 1e-5) + 1e-37
+  float round1;   // round1'
+  float e2;
+  float delta;
+  uint32_t flags;
+};
+
+// chunks of four units, fragments of 64 lanes x 16 bytes per group (chunk x nibble parity x query byte)
+__host__ __device__ static inline uint32_t u42_mfma_chunks(uint32_t units) { return (units + 3) / 4; }
+static inline uint32_t u42_mfma_group_dwords(uint32_t units) { return u42_mfma_chunks(units) * 4 * 256; }
+// THE dispatch rule: unit counts with an instance of scan_u42_mfma_kernel; every other count stays on scan_u42_kernel
+static inline bool u42_mfma_has_instance(uint32_t units) { return units >= 9 && units <= U42_MFMA_MAX_UNITS; }
+
+// query `blockIdx.x` of the round -> its B fragments in group blockIdx.x / 16, column blockIdx.x % 16, and its U42QConst; one wave
+// per query.  Queries [nq, gridDim.x) are absent columns of a short group: zero bytes, flag U42Q_ABSENT.
+// qb: [groups][chunk][parity][H, L][64 lanes][4 dwords]; lane (kg, col) dword t byte b = element 32 (4 chunk + kg) + 8 t + 4 parity + b.
+__global__ __launch_bounds__(64) void u42_query_i16_kernel(const float* queries, uint32_t qpitch, uint32_t units, uint32_t nq,
+                                                           uint32_t* qb, U42QConst* qc) {
+  const int lane = threadIdx.x;
+  const uint32_t qi = blockIdx.x, dimp = units * 32, chunks = u42_mfma_chunks(units);
+  const bool present = qi < nq;
+  const float* qg = queries + (size_t)(present ? qi : 0u) * qpitch;
+  float qsum32, q1, q2;
+  u6_query_sums(qg, dimp, lane, qsum32, q1, q2);
+  float mx = 0.f;
+  bool finite = true;
+  for (uint32_t i = (uint32_t)lane; i < dimp; i += 64) {
+    const float v = fabsf(qg[i]);
+    finite = finite && v < INFINITY;  // (false for NaN too)
+    mx = fmaxf(mx, v);
+  }
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  finite = __ballot(!finite) == 0ull;
+  const bool marked = !finite || mx >= 0x1p64f || (mx > 0.f && mx < 0x1p-44f);
+  const bool zero = !present || marked || mx == 0.f;
+  float delta = 1.0f, inv = 1.0f;
+  if (!zero) {
+    const uint32_t e = __float_as_uint(mx) >> 23;  // mx in [2^(e - 127), 2^(e - 126)): mx / 2^(e - 141) in [2^14, 2^15)
+    delta = __uint_as_float((e - 14u) << 23);
+    if (mx * __uint_as_float((254u - (e - 14u)) << 23) > 32512.0f) delta *= 2.0f;
+    inv = 1.0f / delta;  // (a power of two in [2^-50, 2^58]: exact)
+  }
+  float rr = 0.f;
+  uint32_t* out = qb + (size_t)(qi / U42_MFMA_QUERIES) * (chunks * 4 * 256) + (qi % U42_MFMA_QUERIES) * 4;
+  // a lane per quad of elements: unit u, dword t, nibble parity par
+  for (uint32_t j = (uint32_t)lane; j < chunks * 32; j += 64) {
+    const uint32_t u = j >> 3, t = (j >> 1) & 3u, par = j & 1u;
+    uint32_t hw = 0u, lw = 0u;
+    if (!zero && u < units) {
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const float x = qg[u * 32 + 8 * t + 4 * par + b] * inv;
+        const float r = rintf(x);
+        const float rho = x - r;
+        rr = fmaf(rho, rho, rr);
+        const int qv = (int)r, h = (qv + 128) >> 8, l = qv - 256 * h;
+        hw |= ((uint32_t)h & 0xFFu) << (8 * b);
+        lw |= ((uint32_t)l & 0xFFu) << (8 * b);
+      }
+    }
+    uint32_t* frag = out + (size_t)((u >> 2) * 2 + par) * 2 * 256 + (u & 3u) * 64 + t;
+    frag[0] = hw;
+    frag[256] = lw;
+  }
+  for (int o = 32; o > 0; o >>= 1) rr += __shfl_xor(rr, o);
+  if (lane == 0) {
+    const float e2 = zero ? 0.f : delta * fmaf(sqrtf(rr), 1.0005f, 1e-20f);
+    const float round1 = fmaf(6e-6f * (float)(dimp + 8), q1, (float)dimp * 0x1p-138f);
+    U42QConst c;
+    c.dp = delta * 0x1p-9f;
+    c.qsum305 = 30.5f * (qsum32 * 0.03125f);
+    c.qsum32 = qsum32;
+    c.q2 = q2;
+    c.round1 = round1 + 60.0f * sqrtf((float)dimp) * e2 * (1.0f + 1e-5f);
+    c.e2 = e2;
+    c.delta = delta;
+    c.flags = !present ? U42Q_ABSENT : marked ? U42Q_MARKED : 0u;
+    qc[qi] = c;
+  }
+}
+
+struct Scan42MfmaArgs {
+  Scan42Args a;         // planes; query, tau, cand, count, survivors of the launch's first query; grid y = its groups of 16
+  const uint32_t* qb;   // the launch's first group's fragments (u42_query_i16_kernel)
+  const U42QConst* qc;  // the launch's first query's constants
+  uint32_t nq;          // queries of the launch: the last group may be short
+  uint32_t* surv_p;     // optional: [nq][n_rows], the bits of 2^-9 P^ of every survivor entry, other words untouched (tests)
+};
+
+// one list of the wave: copy its n (<= 64) pairs into the wave's U42List, refine them (query c of the group), flush the stage
+__device__ __forceinline__ void u42_mfma_refine(const Scan42MfmaArgs& m, uint32_t q0, uint32_t c, uint32_t n, const uint2* list,
+                                                U42List& one, u64* stage, int lane) {
+  const uint32_t qi = q0 + c;
+  if ((uint32_t)lane < n) {
+    const uint2 e = list[lane];
+    one.row[lane] = e.x;
+    one.p[lane] = __uint_as_float(e.y);
+    one.s[lane] = m.a.sa4[e.x].x;
+  }
+  Scan42Args aq = m.a;
+  aq.tau += qi;
+  aq.cand += (size_t)qi * m.a.cap;
+  aq.count += qi;
+  if (m.a.survivors) aq.survivors += qi;
+  const __attribute__((address_space(4))) U42QConst* kc = (const __attribute__((address_space(4))) U42QConst*)(m.qc + qi);
+  const float thr = (kc->flags & U42Q_MARKED) ? -INFINITY : aq.tau[0];
+  WaveStage st = {stage, 0u};
+  uint32_t fill = n;
+  u42_refine(aq, (cfloat*)(m.a.query + (size_t)qi * m.a.qpitch), one, fill, n, kc->qsum32, kc->q2, kc->round1, thr, st, lane);
+  st.finish(aq.cand, aq.count, aq.cap, lane);
+}
+
+// NCH chunks of four units: units in (4 NCH - 4, 4 NCH]
+template <int NCH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void scan_u42_mfma_kernel(Scan42MfmaArgs m) {
+  __shared__ uint2 lists[4][U42_MFMA_QUERIES][64];
+  __shared__ U42List one42[4];
+  __shared__ u64 stage42m[4][128];
+  __shared__ f2v sas[4][64];
+  __shared__ uint32_t fills[4][U42_MFMA_QUERIES];
+  const Scan42Args& a = m.a;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t col = (uint32_t)lane & 15u, kg = (uint32_t)lane >> 4;
+  const uint32_t q0 = blockIdx.y * U42_MFMA_QUERIES;
+  const bool present = q0 + col < m.nq;
+  const U42QConst kc = m.qc[min(q0 + col, m.nq - 1)];
+  const float thr = !present ? INFINITY : (kc.flags & U42Q_MARKED) ? -INFINITY : a.tau[q0 + col];
+  i4v bf[NCH][2][2];
+  {
+    const i4v* src = (const i4v*)(m.qb + (size_t)blockIdx.y * (NCH * 4 * 256)) + lane;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+#pragma unroll
+      for (int par = 0; par < 2; ++par)
+#pragma unroll
+        for (int hl = 0; hl < 2; ++hl) bf[c][par][hl] = src[((c * 2 + par) * 2 + hl) * 64];
+  }
+  if (lane < (int)U42_MFMA_QUERIES) fills[wave][lane] = 0u;
+  u42_wave_sync();
+  const uint32_t tiles = (a.n_rows + 63) / 64;
+  const size_t tile_dw = (size_t)a.units * 256;
+  for (uint32_t tile = blockIdx.x * 4 + wave; tile < tiles; tile += gridDim.x * 4) {
+    const uint32_t* p = a.hcodes + tile * tile_dw + kg * 256 + col * 4;
+    const f2v sa = __builtin_nontemporal_load(a.sa4 + min(tile * 64 + (uint32_t)lane, a.n_rows - 1));
+    u4v v[4][NCH];
+#pragma unroll
+    for (int rb = 0; rb < 4; ++rb)
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        if (c < NCH - 1 || 4 * c + kg < a.units) v[rb][c] = u42_load<true>(p + (size_t)c * 1024 + rb * 64);
+        else v[rb][c] = u4v{0u, 0u, 0u, 0u};  // (a short last chunk: this lane group's unit is past the row)
+      }
+    u42_wave_sync();  // (the last tile's reads of sas are done)
+    sas[wave][lane] = sa;
+    u42_wave_sync();
+#pragma unroll
+    for (int rb = 0; rb < 4; ++rb) {
+      i4v dh = {0, 0, 0, 0}, dl = {0, 0, 0, 0};
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const u4v lo = v[rb][c] & 0x0F0F0F0Fu, hi = (v[rb][c] >> 4) & 0x0F0F0F0Fu;
+        dh = __builtin_amdgcn_mfma_i32_16x16x64_i8((i4v)lo, bf[c][0][0], dh, 0, 0, 0);
+        dl = __builtin_amdgcn_mfma_i32_16x16x64_i8((i4v)lo, bf[c][0][1], dl, 0, 0, 0);
+        dh = __builtin_amdgcn_mfma_i32_16x16x64_i8((i4v)hi, bf[c][1][0], dh, 0, 0, 0);
+        dl = __builtin_amdgcn_mfma_i32_16x16x64_i8((i4v)hi, bf[c][1][1], dl, 0, 0, 0);
+      }
+      const uint32_t r0 = 16u * rb + 4u * kg;  // this lane's rows of the tile: r0 .. r0 + 3
+      bool any = false;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const f2v s = sas[wave][r0 + i];
+        const uint32_t row = tile * 64 + r0 + i;
+        const float p4 = (float)(dh[i] * 256 + dl[i]) * kc.dp;  // = 2^-9 P^
+        const float w = s.x * fmaf(2048.0f, p4, -kc.qsum305);
+        const float mm = fmaf(s.y, kc.q2, s.x * kc.round1);
+        const bool surv = present && row < a.n_rows && !(s.x < 0.f) && !(w + mm < thr);
+        if (surv) {
+          const uint32_t slot = atomicAdd(&fills[wave][col], 1u);
+          lists[wave][col][slot] = make_uint2(row, __float_as_uint(p4));
+          if (m.surv_p) m.surv_p[(size_t)(q0 + col) * a.n_rows + row] = __float_as_uint(p4);
+        }
+        any = any || surv;
+      }
+      if (__ballot(any)) {
+        u42_wave_sync();
+        u64 due = __ballot(kg == 0 && fills[wave][col] >= 48u);
+        while (due) {
+          const uint32_t c = (uint32_t)__builtin_ctzll(due);
+          due &= due - 1;
+          const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)fills[wave][c]);
+          u42_wave_sync();
+          if (lane == 0) fills[wave][c] = 0u;
+          u42_mfma_refine(m, q0, c, n, lists[wave][c], one42[wave], stage42m[wave], lane);
+        }
+      }
+    }
+  }
+  u42_wave_sync();
+  u64 due = __ballot(kg == 0 && fills[wave][col] > 0u);
+  while (due) {
+    const uint32_t c = (uint32_t)__builtin_ctzll(due);
+    due &= due - 1;
+    const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)fills[wave][c]);
+    u42_wave_sync();
+    if (lane == 0) fills[wave][c] = 0u;
+    u42_mfma_refine(m, q0, c, n, lists[wave][c], one42[wave], stage42m[wave], lane);
+  }
+}
+
+typedef void (*scan42_mfma_fn)(Scan42MfmaArgs);
+static scan42_mfma_fn pick_scan42_mfma(uint32_t units) { return u42_mfma_has_instance(units) ? scan_u42_mfma_kernel<3> : nullptr; }
+
 // rows [r0, n) fp32 -> h plane, {s, a4} and l records, one wave per row, one lane per 16 elements (half a unit): the walk of
 // rows_to_u6_kernel, so that a6 is its a bit for bit.  units = 32-element units (the pitch is a multiple of 32).
 __global__ __launch_bounds__(256) void rows_to_u42_kernel(const float* rows, u64 r0, u64 n, uint32_t dim, uint32_t pitch,

@@ -166,7 +166,7 @@ static uint64_t device_bytes_resident(const wdbx_index* ix) {
   b += ix->halfmax_bytes + ix->tau_bytes + ix->cand_bytes + ix->count_bytes + ix->qb16_bytes + ix->qn_bytes + ix->selsrc_bytes;
   b += ix->qb8_bytes + ix->qpar_bytes + ix->pairs_bytes + ix->pair_count_bytes + ix->cnmax_bytes;
   b += ix->rcand_bytes + ix->rkeys_bytes + ix->rcnt_bytes + ix->rthr_bytes;
-  b += ix->rows6_bytes + ix->count6_bytes + ix->rows42_bytes + ix->count42_bytes;
+  b += ix->rows6_bytes + ix->count6_bytes + ix->rows42_bytes + ix->count42_bytes + ix->q16_bytes;
   b += ix->sub_ids_bytes + ix->sub_keys_bytes + ix->mm_bytes + ix->rl_bytes + ix->lab_bytes + ix->mv_bytes + ix->mmr_bytes + ix->rec_bytes + ix->grp_bytes;
   return b;
 }
@@ -244,7 +244,7 @@ void wdbx_index_destroy(wdbx_index* ix) try {
                     ix->d_qblock, ix->d_halfmax, ix->d_tau, ix->d_cand, ix->d_count, ix->d_ticket, ix->d_mask, ix->d_dump, ix->d_sel,
                     ix->d_state, ix->d_cn, ix->d_cnmax, ix->d_qb16, ix->d_rows16, ix->d_rows8, ix->d_scale8, ix->d_selsrc,
                     ix->d_gmax, ix->d_qn, ix->d_rows8g, ix->d_groups8, ix->d_gbad8, ix->d_gref8, ix->d_over_list, ix->d_qb8,
-                    ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr, ix->d_rows6, ix->d_count6, ix->d_rows42, ix->d_count42,
+                    ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr, ix->d_rows6, ix->d_count6, ix->d_rows42, ix->d_count42, ix->d_q16,
                     ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys, ix->d_mm, ix->d_rl, ix->d_lab, ix->d_mv, ix->d_mmr, ix->d_rec, ix->d_grp};
     for (void* p : bufs)
       if (p) (void)hipFree(p);
@@ -2765,6 +2765,7 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"scan_u6_cap", &wdbx_index::opt_scan_u6_cap},
     {"scan_u42", &wdbx_index::opt_scan_u42},
     {"scan_u42_share", &wdbx_index::opt_scan_u42_share},
+    {"scan_u42_mfma", &wdbx_index::opt_scan_u42_mfma},
     {"batch_repair", &wdbx_index::opt_batch_repair},
     {"single_min_rows", &wdbx_index::opt_single_min_rows},
     {"range_min_rows", &wdbx_index::opt_range_min_rows},
@@ -2806,6 +2807,8 @@ int wdbx_index_set_option(wdbx_index* ix, const char* name, int64_t value) try {
                 (long long)GROUPS_SEGMENT_MAX);
   if (slot == &ix->opt_scan_u42_share && value != -1 && value != 1 && value != 2 && value != 4)
     return fail(WDBX_E_INVALID, "scan_u42_share %lld: -1 (the default), 1, 2 or 4 queries per read", (long long)value);
+  if (slot == &ix->opt_scan_u42_mfma && value != -1 && value != 0 && value != 1)
+    return fail(WDBX_E_INVALID, "scan_u42_mfma %lld: -1 (the default), 0 or 1", (long long)value);
   *slot = value;
   if (!strcmp(name, "group_bounds")) ix->gmax_valid = false;  // re-decide (and rebuild the group maxima) at the next batch
   return WDBX_OK;
@@ -2837,6 +2840,7 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   }
   if (name && !strcmp(name, "last_single_u42")) return *value = ix->last_single_u42, WDBX_OK;
   if (name && !strcmp(name, "last_u42_share")) return *value = ix->last_u42_share, WDBX_OK;
+  if (name && !strcmp(name, "last_u42_mfma_groups")) return *value = ix->last_u42_mfma_groups, WDBX_OK;
   if (name && !strcmp(name, "u42_survivors_sum")) {
     // rows that passed the four-bit bound in the last round's full passes; waits for the stream
     const uint32_t nq = ix->last_single_u42 ? std::min<uint32_t>(ix->last_batch_nq, 64) : 0;
