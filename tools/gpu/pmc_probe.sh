@@ -1,5 +1,6 @@
 #!/bin/bash
-# usage: pmc_probe.sh <outdir> <kernel-name-substring> <program> [args...] ; one rocprofv3 --pmc pass per counter group
+# usage: pmc_probe.sh <outdir> <kernel-name-substring> <program> [args...] ; one rocprofv3 --pmc pass per counter group,
+# each under its own time limit (PMC_PASS_SECONDS, default 300); a pass that fails ends the script
 set -e
 OUT=$1; KERN=$2; shift 2
 mkdir -p $OUT
@@ -11,7 +12,7 @@ for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_I
            "GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_MFMA SQ_INSTS_SALU" \
            "SQ_INST_LEVEL_VMEM SQ_INST_LEVEL_LDS SQ_LEVEL_WAVES SQ_WAVES SQ_IFETCH SQ_IFETCH_LEVEL"; do
   i=$((i+1))
-  rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $OUT/g$i -o p -- "$@" > $OUT/run$i.log 2>&1
+  timeout -k 10 ${PMC_PASS_SECONDS:-300} rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $OUT/g$i -o p -- "$@" > $OUT/run$i.log 2>&1
 done
 python3 - $OUT $KERN <<'PY'
 import sys, csv, glob, collections

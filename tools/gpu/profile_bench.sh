@@ -1,7 +1,8 @@
 #!/bin/bash
 # rocprofv3 record of one bench.py command line: kernel trace + stats, then FETCH_SIZE / WRITE_SIZE in passes of their own
 # (MI355X_MICROARCH.md: counters in their own runs, gfx950 FETCH_SIZE counts half of wide streaming reads).
-# usage (on the GPU box): tools/gpu/profile_bench.sh <outdir> [bench.py arguments...]
+# usage (on the GPU box): tools/gpu/profile_bench.sh <outdir> [bench.py arguments...]; every pass under its own time limit
+# (PROFILE_PASS_SECONDS, default 300), a pass that fails ends the script
 set -e
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}
@@ -10,10 +11,10 @@ mkdir -p $O
 O=$(cd $O && pwd)   # (absolute: the passes run from /tmp)
 cd /tmp
 ARGS="--full --no-other-configs --no-cpu-baseline --no-facade --no-live-traffic $*"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o t -- python3 $R/bench.py $ARGS > $O/bench_under_rocprof.json 2> $O/stats.err
+timeout -k 10 ${PROFILE_PASS_SECONDS:-300} rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o t -- python3 $R/bench.py $ARGS > $O/bench_under_rocprof.json 2> $O/stats.err
 cp $(find $O/stats -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -o t -- python3 $R/bench.py $ARGS > $O/fetch.json 2> $O/fetch.err
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -o t -- python3 $R/bench.py $ARGS > $O/write.json 2> $O/write.err
+timeout -k 10 ${PROFILE_PASS_SECONDS:-300} rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -o t -- python3 $R/bench.py $ARGS > $O/fetch.json 2> $O/fetch.err
+timeout -k 10 ${PROFILE_PASS_SECONDS:-300} rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -o t -- python3 $R/bench.py $ARGS > $O/write.json 2> $O/write.err
 cd $R
 python3 - $O <<'PY'
 import csv, glob, collections, json, sys

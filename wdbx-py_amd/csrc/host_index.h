@@ -1442,9 +1442,9 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
   };
   const uint32_t grid1 = scan_full_grid(tiles64, (uint32_t)ix->cu_count, wgs_of(1));
   const uint32_t grid_shared = scan_full_grid(tiles64, (uint32_t)ix->cu_count, wgs_of(2));
-  // the matrix-core pass, 2000 steps, means of three: 1 -> 17110 q/s, 2 -> 18758, 3 -> 16056 (all its 44.3 KiB of LDS lets a CU
-  // hold), 4 -> 13020 (spreads 122 / 59 / 72 / 169; profiles/u42_mfma/README.md): fewer waves mean fewer lists to refine
-  // behind the last tile, which weighs more here than latency hiding does
+  // the matrix-core pass, 2000 steps, means of three: 1 -> 22579 q/s, 2 -> 30096, 3 -> 22514 (spreads 73 / 352 / 66;
+  // profiles/u42_mfma_pipe/README.md).  Its 70.8 KiB of LDS let a CU hold two workgroups: a grid of three per CU runs them in two
+  // uneven rounds.  No load is in flight while a wave computes its tile, so the second wave of a SIMD is what overlaps
   const uint32_t grid_mfma = scan_full_grid(tiles64, (uint32_t)ix->cu_count,
                                             (uint32_t)std::max<int64_t>(1, std::min<int64_t>(ix->opt_scan8_wgs > 0 ? ix->opt_scan8_wgs : 2, 8)));
   const uint32_t grid0 = scan_sample_grid(ngroups, (uint32_t)ix->cu_count);

@@ -288,22 +288,33 @@ __global__ __launch_bounds__(256) void scan_u42_kernel(Scan42Args a) {
 // difference and the product with s (of at most 98.1 |q|_1): (67.6 + 30.5 (dimp + 1) + 3 * 98.1) 2^-24 |q|_1, below the
 // 90.5 (dimp + 8) 2^-24 |q|_1 the term was derived for at every dimp >= 32 (dimp = 32: 1368 against 3620).  The sum round1 + query
 // term rounds once more (2^-24 relative): inside the step from 5.4e-6 to the 6e-6 taken.
-// REFINE.  u42_refine, unchanged, forms w6 = s ((4 P^ + Q) - 32 sum q) from the carried P^ and the fp32 query's remainders.  Its
+// REFINE.  u42_mfma_finish forms u42_refine's w6 = s ((4 P^ + Q) - 32 sum q) from the carried P^ and the fp32 query's remainders.  Its
 // roundings: the conversion (67.6 |q|_1), the remainders' sum (gamma_dimp * 3 |q|_1), 4 P^ + Q in one rounding (70.6 |q|_1), 32 sum q
 // (gamma_dimp * 32 |q|_1), the difference and the product with s (102.6 |q|_1): (67.6 + 35 dimp + 70.6 + 3 * 102.6) 2^-24 |q|_1, below
 // 95 (dimp + 8) 2^-24 |q|_1 likewise.  4 P^ misses 4 sum h_i q_i by the same query term, so m6' = a6 |q|_2 (1 + 1e-5) + s round1': the
-// kernel hands round1' to u42_refine as its round1.
-// SURVIVOR LISTS.  Per wave and query a list of 64 {row, 2^-9 P^} pairs in LDS (8 bytes: s is read again from {s, a4} when the list
-// is refined -- the same bits); lanes append through an LDS counter.  Behind every 16-row block (a list grows by at most 16 there:
-// 47 + 16 < 64) a wave-uniform loop over the group's queries copies each list of 48 or more into the wave's one U42List and runs
-// u42_refine on it; once more behind the last tile for whatever is left.  ONE WaveStage per wave, flushed behind every refine:
-// candidates are a few of the 48 survivors of a refine, so a flush is one atomic on the query's counter per refine, and sixteen
-// stages would cost 16 KiB per wave.  NOT TRIED: a ballot / mbcnt append per (column, row i) as scan_u42_kernel's, in place of
-// the LDS counter -- up to 16 serialised atomics on one counter per 16-row block when every row of a column survives, one per
-// block on the headline corpus (0.8 % of the pairs survive); it costs four 64-bit ballots and the masked popcounts per block.
-// Capacity and overflow are the stage's: the counter ends above cap, keys beyond it are dropped.
-// LDS: 4 waves x (8 KiB lists + 1.5 KiB U42List + 1 KiB stage + 512 B of {s, a4} + 64 B of counters) = 44.3 KiB per workgroup: three
-// fit a CU, two run (the sweep in host_index.h).
+// refine takes round1' where u42_refine takes round1.
+// SURVIVOR LISTS.  Per wave and query a list of U42_MFMA_LIST_CAP = 128 {row, 2^-9 P^} pairs in LDS (8 bytes: s is read again from
+// {s, a4} when the list is refined -- the same bits); lanes append through an LDS counter, one add per survivor.  A tile adds at
+// most 64 entries to a list and a list holds fewer than U42_MFMA_TRIGGER = 64 between tiles (63 + 64 < 128); behind a tile in which
+// any lane appended, ONE ballot finds the lists of 64 or more and the wave refines the LAST 64 entries of each (what stays is in
+// front already, nothing moves).  MEASURED AND LEFT OUT (profiles/u42_mfma_pipe/README.md): deciding a lane's sixteen pairs into a
+// mask first and appending with one LDS add of popcount(mask) per lane and tile -- no faster than the add per survivor once the
+// refine is short (0.8 % of the pairs survive on the headline corpus: about six adds per tile and wave); the next tile's twelve
+// loads in flight under this tile's MFMAs (203 VGPRs) -- 3.5 % on the pass alone at two workgroups per CU, below the bar.
+// REFINE in two halves.  u42_mfma_gather issues every load of up to 64 entries, lane = entry, all addressed by the entry's row:
+// the row's scale and the 128-byte l record as six 16-byte loads plus a6 -- no load waits for another.  u42_mfma_finish forms
+// u42_refine's sums in its order (units, dwords, j; a0 / a1), w6, m6 and the key.  Behind the last tile about sixteen short lists
+// are left per wave (on the headline corpus a wave meets about 40 survivors per query, below the trigger): the gather of the next
+// list is issued before the finish of the current one.
+// ONE STAGE for the sixteen columns (U42Stage16): kept keys wait in LDS with their column and go out 64 at a time or at the wave's
+// end.  A flush ranks the 64 keys inside their columns (sixteen ballots), the first lane of every column adds the column's number
+// to the column's counter -- one atomic instruction of up to sixteen lanes -- and every lane stores at base + rank of its column.
+// Capacity and overflow are per column as before: the counter ends above cap, keys at base + rank >= cap are dropped, the keys below
+// cap name real rows.  A wave keeps about two candidates per query, so this is one atomic latency per wave where a stage flushed
+// per refine paid sixteen; only the order of the keys inside a buffer differs.  The survivors counter takes the wave's sum per
+// column in one instruction of sixteen lanes at the wave's end.
+// LDS: 4 waves x (16 KiB lists + 1 KiB + 128 B stage + 512 B of {s, a4} + 64 B of counters) = 70.6 KiB per workgroup: two fit a CU and
+// two run, one wave of each per SIMD (the sweep in host_index.h).
 // ------------------------------------------------------------------------------------------------
 typedef int i4v __attribute__((ext_vector_type(4)));
 
@@ -405,35 +416,128 @@ struct Scan42MfmaArgs {
   uint32_t* surv_p;     // optional: [nq][n_rows], the bits of 2^-9 P^ of every survivor entry, other words untouched (tests)
 };
 
-// one list of the wave: copy its n (<= 64) pairs into the wave's U42List, refine them (query c of the group), flush the stage
-__device__ __forceinline__ void u42_mfma_refine(const Scan42MfmaArgs& m, uint32_t q0, uint32_t c, uint32_t n, const uint2* list,
-                                                U42List& one, u64* stage, int lane) {
-  const uint32_t qi = q0 + c;
-  if ((uint32_t)lane < n) {
-    const uint2 e = list[lane];
-    one.row[lane] = e.x;
-    one.p[lane] = __uint_as_float(e.y);
-    one.s[lane] = m.a.sa4[e.x].x;
+constexpr uint32_t U42_MFMA_TRIGGER = 64;    // a list of this many entries is refined behind the tile that filled it
+constexpr uint32_t U42_MFMA_LIST_CAP = 128;  // TRIGGER - 1 held between tiles + the 64 a tile can append
+
+// the wave's ONE stage for the sixteen columns of its group: keys with their column, flushed 64 at a time.  A flush is one atomic
+// instruction (a lane per column that has keys among the 64 adds that column's number to the column's counter) and one store
+// instruction; capacity and overflow stay per column: the counter ends at the exact total, keys at base + rank >= cap are dropped.
+struct U42Stage16 {
+  u64* key;       // 128 keys of LDS, this wave's
+  uint8_t* col;   // their columns
+  uint32_t fill;  // keys staged (wave-uniform, < 64 between pushes)
+  // cand, count: of the group's first query
+  __device__ __forceinline__ void push(bool keep, u64 k, uint32_t c, u64* cand, uint32_t* count, uint32_t cap, int lane) {
+    const u64 bal = __ballot(keep);
+    if (!bal) return;
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+    if (keep) key[fill + rank] = k, col[fill + rank] = (uint8_t)c;
+    fill += (uint32_t)__popcll(bal);
+    if (fill >= 64) flush(64, cand, count, cap, lane);
   }
-  Scan42Args aq = m.a;
-  aq.tau += qi;
-  aq.cand += (size_t)qi * m.a.cap;
-  aq.count += qi;
-  if (m.a.survivors) aq.survivors += qi;
+  __device__ __forceinline__ void finish(u64* cand, uint32_t* count, uint32_t cap, int lane) {
+    if (fill) flush(fill, cand, count, cap, lane);
+  }
+  __device__ __forceinline__ void flush(uint32_t n, u64* cand, uint32_t* count, uint32_t cap, int lane) {
+    u42_wave_sync();
+    const uint32_t l = (uint32_t)lane;
+    const bool on = l < n;
+    const u64 k = on ? key[l] : 0ull;
+    const uint32_t c = on ? (uint32_t)col[l] : U42_MFMA_QUERIES;  // (no column)
+    const uint32_t rest = fill - n;                                // (< 64) moved to the front
+    const u64 mk = l < rest ? key[n + l] : 0ull;
+    const uint8_t mc = l < rest ? col[n + l] : (uint8_t)0;
+    uint32_t rank = 0, cnt = 0, lead = 0;  // among the lanes of this lane's column: its rank, their number, the first of them
+#pragma unroll
+    for (uint32_t cc = 0; cc < U42_MFMA_QUERIES; ++cc) {
+      const u64 b = __ballot(c == cc);
+      if (c == cc) {
+        rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+        cnt = (uint32_t)__popcll(b);
+        lead = (uint32_t)__builtin_ctzll(b);
+      }
+    }
+    uint32_t base = 0;
+    if (on && rank == 0) base = atomicAdd(count + c, cnt);
+    base = (uint32_t)__shfl((int)base, (int)lead);
+    if (on && base + rank < cap) cand[(size_t)c * cap + base + rank] = k;
+    u42_wave_sync();
+    if (l < rest) key[l] = mk, col[l] = mc;
+    fill = rest;
+    u42_wave_sync();
+  }
+};
+
+// what the refine of one list entry reads, all of it addressed by the entry's row alone: the row's scale and its l record as
+// six 16-byte loads (the record is 128-byte aligned and a whole line for units <= 15) plus a6
+struct U42Gather {
+  uint32_t row;
+  float p4, s;
+  u4v w[U42_MFMA_MAX_UNITS / 2];
+  uint32_t a6;
+};
+
+// the loads of the refine of n (<= 64) list entries, lane = entry; idle lanes walk record 0 (always there)
+__device__ __forceinline__ U42Gather u42_mfma_gather(const Scan42Args& a, const uint2* list, uint32_t n, int lane) {
+  U42Gather g;
+  const uint2 e = (uint32_t)lane < n ? list[lane] : make_uint2(0u, 0u);
+  g.row = e.x;
+  g.p4 = __uint_as_float(e.y);
+  const uint32_t* rec = a.lrec + (size_t)e.x * a.lpitch;
+  g.s = a.sa4[e.x].x;
+#pragma unroll
+  for (uint32_t i = 0; i < U42_MFMA_MAX_UNITS / 2; ++i) g.w[i] = *(const u4v*)(rec + 4 * i);
+  g.a6 = rec[2 * a.units];
+  return g;
+}
+
+// u42_refine's sums, bounds and key on gathered entries of query c of the group (the same operations in the same order), kept
+// keys to the wave's stage
+__device__ __forceinline__ void u42_mfma_finish(const Scan42MfmaArgs& m, uint32_t q0, uint32_t c, uint32_t n, const U42Gather& g,
+                                                U42Stage16& st, int lane) {
+  const Scan42Args& a = m.a;
+  const uint32_t qi = q0 + c;
   const __attribute__((address_space(4))) U42QConst* kc = (const __attribute__((address_space(4))) U42QConst*)(m.qc + qi);
-  const float thr = (kc->flags & U42Q_MARKED) ? -INFINITY : aq.tau[0];
-  WaveStage st = {stage, 0u};
-  uint32_t fill = n;
-  u42_refine(aq, (cfloat*)(m.a.query + (size_t)qi * m.a.qpitch), one, fill, n, kc->qsum32, kc->q2, kc->round1, thr, st, lane);
-  st.finish(aq.cand, aq.count, aq.cap, lane);
+  const float thr = (kc->flags & U42Q_MARKED) ? -INFINITY : a.tau[qi];
+  const float qsum32 = kc->qsum32, q2 = kc->q2, round1 = kc->round1;
+  cfloat* q = (cfloat*)(a.query + (size_t)qi * a.qpitch);
+  const bool active = (uint32_t)lane < n;
+  const float p4 = active ? g.p4 : 0.f, s = active ? g.s : 0.f;
+  f2v a0 = {0.f, 0.f}, a1 = {0.f, 0.f};
+#pragma unroll
+  for (uint32_t u = 0; u < U42_MFMA_MAX_UNITS; ++u) {
+    if (u < a.units) {  // (wave-uniform)
+      cfloat* qu = q + u * 32;
+#pragma unroll
+      for (int gg = 0; gg < 2; ++gg) {
+        const uint32_t w = g.w[u >> 1][2 * (u & 1) + gg];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          f2v lo, hi;
+          u42_rem4(w, j, lo, hi);
+          const int i = 16 * gg + 4 * j;
+          a0 = __builtin_elementwise_fma(lo, f2v{qu[i], qu[i + 1]}, a0);
+          a1 = __builtin_elementwise_fma(hi, f2v{qu[i + 2], qu[i + 3]}, a1);
+        }
+      }
+    }
+  }
+  const float a6 = __uint_as_float(g.a6);
+  const float qq = (a0.x + a0.y) + (a1.x + a1.y);
+  const float w = s * (fmaf(2048.0f, p4, 512.0f * qq) - qsum32);
+  const float mm = fmaf(a6, q2, s * round1);
+  const bool keep = active && !(w + mm < thr);
+  st.push(keep, make_key((w == w) ? w + 0.0f : INFINITY, g.row), c, a.cand + (size_t)q0 * a.cap, a.count + q0, a.cap, lane);
 }
 
 // NCH chunks of four units: units in (4 NCH - 4, 4 NCH]
 template <int NCH>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void scan_u42_mfma_kernel(Scan42MfmaArgs m) {
-  __shared__ uint2 lists[4][U42_MFMA_QUERIES][64];
-  __shared__ U42List one42[4];
-  __shared__ u64 stage42m[4][128];
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_u42_mfma_kernel(Scan42MfmaArgs m) {
+  static_assert(4 * NCH <= (int)U42_MFMA_MAX_UNITS, "the refine gathers six 16-byte loads per record");
+  static_assert(U42_MFMA_TRIGGER == 64 && U42_MFMA_LIST_CAP >= U42_MFMA_TRIGGER - 1 + 64, "a refine takes 64 entries, a tile adds up to 64");
+  __shared__ uint2 lists[4][U42_MFMA_QUERIES][U42_MFMA_LIST_CAP];
+  __shared__ u64 stage_key[4][128];
+  __shared__ uint8_t stage_col[4][128];
   __shared__ f2v sas[4][64];
   __shared__ uint32_t fills[4][U42_MFMA_QUERIES];
   const Scan42Args& a = m.a;
@@ -454,6 +558,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         for (int hl = 0; hl < 2; ++hl) bf[c][par][hl] = src[((c * 2 + par) * 2 + hl) * 64];
   }
   if (lane < (int)U42_MFMA_QUERIES) fills[wave][lane] = 0u;
+  U42Stage16 st = {stage_key[wave], stage_col[wave], 0u};
+  uint32_t refined = 0;  // lane c < 16: entries of column c this wave has refined
   u42_wave_sync();
   const uint32_t tiles = (a.n_rows + 63) / 64;
   const size_t tile_dw = (size_t)a.units * 256;
@@ -471,6 +577,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     u42_wave_sync();  // (the last tile's reads of sas are done)
     sas[wave][lane] = sa;
     u42_wave_sync();
+    bool any = false;
 #pragma unroll
     for (int rb = 0; rb < 4; ++rb) {
       i4v dh = {0, 0, 0, 0}, dl = {0, 0, 0, 0};
@@ -483,7 +590,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         dl = __builtin_amdgcn_mfma_i32_16x16x64_i8((i4v)hi, bf[c][1][1], dl, 0, 0, 0);
       }
       const uint32_t r0 = 16u * rb + 4u * kg;  // this lane's rows of the tile: r0 .. r0 + 3
-      bool any = false;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const f2v s = sas[wave][r0 + i];
@@ -499,30 +605,46 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         }
         any = any || surv;
       }
-      if (__ballot(any)) {
+    }
+    if (__ballot(any)) {
+      u42_wave_sync();
+      u64 due = __ballot(kg == 0 && fills[wave][col] >= U42_MFMA_TRIGGER);
+      while (due) {  // refine the list's LAST 64 entries: what stays is in front already
+        const uint32_t c = (uint32_t)__builtin_ctzll(due);
+        due &= due - 1;
+        const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)fills[wave][c]) - 64u;
         u42_wave_sync();
-        u64 due = __ballot(kg == 0 && fills[wave][col] >= 48u);
-        while (due) {
-          const uint32_t c = (uint32_t)__builtin_ctzll(due);
-          due &= due - 1;
-          const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)fills[wave][c]);
-          u42_wave_sync();
-          if (lane == 0) fills[wave][c] = 0u;
-          u42_mfma_refine(m, q0, c, n, lists[wave][c], one42[wave], stage42m[wave], lane);
-        }
+        if (lane == 0) fills[wave][c] = n;
+        const U42Gather g = u42_mfma_gather(a, lists[wave][c] + n, 64u, lane);
+        u42_wave_sync();  // (the entries are read before the next tile appends over them)
+        if ((uint32_t)lane == c) refined += 64u;
+        u42_mfma_finish(m, q0, c, 64u, g, st, lane);
       }
     }
   }
+  // behind the last tile: what is left in the sixteen lists, the loads of the next list in flight while this one is finished
   u42_wave_sync();
   u64 due = __ballot(kg == 0 && fills[wave][col] > 0u);
-  while (due) {
-    const uint32_t c = (uint32_t)__builtin_ctzll(due);
+  if (due) {
+    uint32_t c = (uint32_t)__builtin_ctzll(due);
     due &= due - 1;
-    const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)fills[wave][c]);
-    u42_wave_sync();
-    if (lane == 0) fills[wave][c] = 0u;
-    u42_mfma_refine(m, q0, c, n, lists[wave][c], one42[wave], stage42m[wave], lane);
+    uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)fills[wave][c]);
+    U42Gather g = u42_mfma_gather(a, lists[wave][c], n, lane);
+    while (due) {
+      const uint32_t c1 = (uint32_t)__builtin_ctzll(due);
+      due &= due - 1;
+      const uint32_t n1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)fills[wave][c1]);
+      const U42Gather g1 = u42_mfma_gather(a, lists[wave][c1], n1, lane);
+      if ((uint32_t)lane == c) refined += n;
+      u42_mfma_finish(m, q0, c, n, g, st, lane);
+      g = g1, c = c1, n = n1;
+    }
+    if ((uint32_t)lane == c) refined += n;
+    u42_mfma_finish(m, q0, c, n, g, st, lane);
   }
+  st.finish(a.cand + (size_t)q0 * a.cap, a.count + q0, a.cap, lane);
+  // (only present columns have entries, so every address is a query's of the launch)
+  if (a.survivors && lane < (int)U42_MFMA_QUERIES && refined) atomicAdd(a.survivors + q0 + lane, refined);
 }
 
 typedef void (*scan42_mfma_fn)(Scan42MfmaArgs);
