@@ -10,6 +10,7 @@ typedef unsigned long long u64;
 typedef float f4 __attribute__((ext_vector_type(4)));
 #include "wdbx_hip.h"
 #include "host_dispatch.h"
+#include "host_scan_plan.h"
 #include "kernels_common.h"
 #include "kernels_scan.h"
 #include "kernels_merge_select.h"

@@ -353,7 +353,6 @@ static inline int wait_done_word(volatile uint32_t* word, uint32_t seq, hipEvent
 }
 
 // ---- scan dispatch ------------------------------------------------------------------------------
-typedef void (*scan_fn)(ScanArgs);
 struct ScanChoice {
   scan_fn fn = nullptr;
   int L = 8;
@@ -361,180 +360,29 @@ struct ScanChoice {
   size_t lds_extra = 0;  // bytes beyond the 4 lists
 };
 
-template <int L, int QPL, int METRIC, bool NT, bool RAGGED>
-static scan_fn pick_mode(int mode) {
-  switch (mode) {
-    case 0: return scan_kernel<L, QPL, METRIC, NT, 0, RAGGED>;
-    case 1: return scan_kernel<L, QPL, METRIC, NT, 1, RAGGED>;
-    default: return scan_kernel<L, QPL, METRIC, NT, 2, RAGGED>;
-  }
-}
-
-template <int L, int QPL, int METRIC>
-static scan_fn pick_flags(bool nt, int mode, bool ragged) {
-  if (ragged) return pick_mode<L, QPL, METRIC, true, true>(mode);  // ragged instances are non-temporal only
-  return nt ? pick_mode<L, QPL, METRIC, true, false>(mode) : pick_mode<L, QPL, METRIC, false, false>(mode);
-}
-
-template <int L, int QPL>
-static scan_fn pick_variant(int metric, bool nt, int reg, bool ragged) {
-  return metric == WDBX_METRIC_COSINE ? pick_flags<L, QPL, WDBX_METRIC_COSINE>(nt, reg, ragged)
-                                      : pick_flags<L, QPL, WDBX_METRIC_L2>(nt, reg, ragged);
-}
-
-template <int L>
-static scan_fn pick_qpl(int qpl, int metric, bool nt, int reg, bool ragged) {
-  if constexpr (L >= 16) {  // short rows on wide lane groups (d = 68 ... 256 when rows are not line aligned)
-    if (qpl == 1) return pick_variant<L, 1>(metric, nt, reg, ragged);
-    if (qpl == 2) return pick_variant<L, 2>(metric, nt, reg, ragged);
-  }
-  switch (qpl) {
-    case 3: return pick_variant<L, 3>(metric, nt, reg, ragged);
-    case 4: return pick_variant<L, 4>(metric, nt, reg, ragged);
-    case 6: return pick_variant<L, 6>(metric, nt, reg, ragged);
-    case 8: return pick_variant<L, 8>(metric, nt, reg, ragged);
-    case 12: return pick_variant<L, 12>(metric, nt, reg, ragged);
-    default: return nullptr;
-  }
-}
-
-// short rows (d <= 48): L = 4 or 8 with 1..3 quads per lane, 4..8 passes in flight
-template <int L>
-static scan_fn pick_qpl_short(int qpl, int metric, bool nt, int reg, bool ragged) {
-  switch (qpl) {
-    case 1: return pick_variant<L, 1>(metric, nt, reg, ragged);
-    case 2: return pick_variant<L, 2>(metric, nt, reg, ragged);
-    case 3: return L == 4 ? pick_variant<4, 3>(metric, nt, reg, ragged) : nullptr;
-    default: return nullptr;
-  }
-}
-
-static scan_fn pick_specialised(int L, int qpl, int metric, bool nt, int reg, bool ragged) {
-  if (L == 1 && qpl == 1) return pick_variant<1, 1>(metric, nt, reg, ragged);  // d <= 4: one lane per row
-  if (L == 2 && qpl == 1) return pick_variant<2, 1>(metric, nt, reg, ragged);  // d <= 8
-  if (L == 4) return pick_qpl_short<4>(qpl, metric, nt, reg, ragged);
-  if (L == 8 && qpl <= 2) return pick_qpl_short<8>(qpl, metric, nt, reg, ragged);
-  switch (L) {
-    case 8: return pick_qpl<8>(qpl, metric, nt, reg, ragged);
-    case 16: return pick_qpl<16>(qpl, metric, nt, reg, ragged);
-    case 32: return pick_qpl<32>(qpl, metric, nt, reg, ragged);
-    case 64: return pick_qpl<64>(qpl, metric, nt, reg, ragged);
-    default: return nullptr;
-  }
-}
-
-template <int L, int METRIC>
-static scan_fn pick_generic_mode(int mode) {
-  switch (mode) {
-    case 0: return scan_kernel_generic<L, METRIC, 0>;
-    case 1: return scan_kernel_generic<L, METRIC, 1>;
-    default: return scan_kernel_generic<L, METRIC, 2>;
-  }
-}
-
-template <int L>
-static scan_fn pick_generic_metric(int metric, int mode) {
-  return metric == WDBX_METRIC_COSINE ? pick_generic_mode<L, WDBX_METRIC_COSINE>(mode)
-                                      : pick_generic_mode<L, WDBX_METRIC_L2>(mode);
-}
-
-static scan_fn pick_generic(int L, int metric, int reg) {
-  switch (L) {
-    case 64: return pick_generic_metric<64>(metric, reg);
-    case 1: return pick_generic_metric<1>(metric, reg);
-    case 2: return pick_generic_metric<2>(metric, reg);
-    case 4: return pick_generic_metric<4>(metric, reg);
-    default: return pick_generic_metric<8>(metric, reg);
-  }
-}
-
-template <int L>
-static scan_fn pick_listed_metric(int metric, int reg) {
-  if (metric == WDBX_METRIC_COSINE) return reg ? scan_kernel_listed<L, WDBX_METRIC_COSINE, 1> : scan_kernel_listed<L, WDBX_METRIC_COSINE, 0>;
-  return reg ? scan_kernel_listed<L, WDBX_METRIC_L2, 1> : scan_kernel_listed<L, WDBX_METRIC_L2, 0>;
-}
-
-// the listed repair scan (generic body): reg = 1 register lists (k <= 128), 0 LDS lists
-static scan_fn pick_listed(int L, int metric, int reg) {
-  switch (L) {
-    case 64: return pick_listed_metric<64>(metric, reg);
-    case 1: return pick_listed_metric<1>(metric, reg);
-    case 2: return pick_listed_metric<2>(metric, reg);
-    case 4: return pick_listed_metric<4>(metric, reg);
-    default: return pick_listed_metric<8>(metric, reg);
-  }
-}
-
 static bool use_select(const wdbx_index* ix, int k) { return ix->opt_select_min_k > 0 && k >= ix->opt_select_min_k; }
 
-static ScanChoice choose_scan(const wdbx_index* ix, int k) {
-  const int reg = use_select(ix, k) ? 2 : (k <= 128 && !ix->opt_lds_lists) ? 1 : 0;
+static ScanChoice scan_choice_of(const ScanForm& f, scan_fn fn, int pitch4) {
   ScanChoice c;
-  const int pitch4 = ix->pitch / 4;
-  const bool nt = ix->opt_nt != 0;
-  if (!ix->opt_generic && pitch4 < 16 && !ix->opt_lanes) {
-    // short rows (d < 64): the smallest instance that holds the row, up to 3/8 of its slots idle
-    const int cand[7][2] = {{1, 1}, {2, 1}, {4, 1}, {8, 1}, {4, 2}, {4, 3}, {8, 2}};
-    for (int t = 0; t < 7; ++t) {
-      const int slots = cand[t][0] * cand[t][1], waste = slots - pitch4;
-      if (waste < 0 || waste * 8 > slots * 3) continue;
-      scan_fn f = pick_specialised(cand[t][0], cand[t][1], ix->metric, nt, reg, waste != 0 || ix->opt_force_ragged);
-      if (f) {
-        c.fn = f;
-        c.L = cand[t][0];
-        return c;
-      }
-    }
-  }
-  if (!ix->opt_generic && pitch4 >= 16) {
-    // unrolled instances exist for L in {8,16,32,64} x QPL in {3,4,6,8,12} (+ {1,2} for L >= 16); slots past the row end idle
-    // (RAGGED form), at most a third of them.  Rows whose byte pitch is a multiple of 128 take the
-    // instance with the fewest idle slots (smaller L on ties: all L measure alike there).  Rows that
-    // do NOT start on cache-line boundaries take the LARGEST admissible L: a lane group then reads one
-    // long contiguous span per instruction instead of many short ones that each straddle two lines
-    // (d=300: L=8 5.35 TB/s, L=32 6.89 TB/s; d=200: L=8 5.87, L=16 6.84; profiles/r01/bench_dims.txt)
-    const int Ls[4] = {8, 16, 32, 64}, Qs[7] = {1, 2, 3, 4, 6, 8, 12};
-    const bool line_aligned = pitch4 % 8 == 0;
-    int bestL = 0, bestQ = 0, best_waste = 1 << 30;
-    // tier 0: QPL >= 3 (enough loads in flight per pass, several rows per pass).  tier 1, only for
-    // misaligned short rows that tier 0 can serve with L = 8 at best: QPL 1 or 2 on L = 16 / 32
-    // (d=100: (8,4) 5.63 TB/s, (32,1) 6.08 TB/s; for d=200 the wide short form is slower, 5.3 vs 6.6)
-    for (int tier = 0; tier < 2; ++tier) {
-      if (tier == 1 && (line_aligned || bestL >= 16)) break;
-      for (int li = 0; li < 4; ++li) {
-        if (ix->opt_lanes && Ls[li] != ix->opt_lanes) continue;
-        if (tier == 1 && (Ls[li] < 16 || Ls[li] > 32)) continue;
-        for (int qi = (tier == 0 ? 2 : 0); qi < (tier == 0 ? 7 : 2); ++qi) {
-          const int slots = Ls[li] * Qs[qi], waste = slots - pitch4;
-          if (waste < 0 || waste * 3 > slots) continue;
-          const bool better = line_aligned ? waste < best_waste
-                                           : (Ls[li] > bestL || (Ls[li] == bestL && waste < best_waste));
-          if (better) {
-            best_waste = waste;
-            bestL = Ls[li];
-            bestQ = Qs[qi];
-          }
-        }
-      }
-    }
-    // a ragged instance may idle at most a third of its slots; beyond that the generic kernel is better
-    if (bestL && best_waste * 3 <= bestL * bestQ) {
-      scan_fn f = pick_specialised(bestL, bestQ, ix->metric, nt, reg, best_waste != 0 || ix->opt_force_ragged);
-      if (f) {
-        c.fn = f;
-        c.L = bestL;
-        return c;
-      }
-    }
-  }
-  int L = 1;
-  while (L < 8 && L < pitch4) L <<= 1;
-  if (pitch4 > 768) L = 64;  // rows longer than the largest unrolled instance
-  c.fn = pick_generic(L, ix->metric, reg);
-  c.L = L;
-  c.generic = true;
-  c.lds_extra = (size_t)pitch4 * 16;
+  c.fn = fn;
+  c.L = f.L;
+  c.generic = f.generic;
+  c.lds_extra = scan_lds_extra(f.generic, pitch4);
   return c;
+}
+
+// the handle's scan kernel at this k: the form by the shape rule (host_scan_plan.h: scan_form), the instance by the pickers next
+// to the kernels (kernels_scan.h)
+static ScanChoice choose_scan(const wdbx_index* ix, int k) {
+  const int reg = scan_list_mode(use_select(ix, k), k, ix->opt_lds_lists != 0);
+  const int pitch4 = ix->pitch / 4;
+  ScanForm f = scan_form(pitch4, ix->opt_lanes, ix->opt_generic != 0, ix->opt_force_ragged != 0);
+  scan_fn fn = pick_scan_form(f, ix->metric, ix->opt_nt != 0, reg);
+  if (!fn) {  // (scan_has_instance and pick_specialised disagree: the generic kernel serves any pitch)
+    f = scan_generic_form(pitch4);
+    fn = pick_scan_form(f, ix->metric, false, reg);
+  }
+  return scan_choice_of(f, fn, pitch4);
 }
 
 struct LaunchPlan {
@@ -549,33 +397,22 @@ static int plan_scan(wdbx_index* ix, int k, LaunchPlan* out, bool listed = false
   LaunchPlan lp;
   if (listed) {
     const int pitch4 = ix->pitch / 4;
-    int L = 1;
-    while (L < 8 && L < pitch4) L <<= 1;
-    if (pitch4 > 768) L = 64;
-    lp.sc.fn = pick_listed(L, ix->metric, (k <= 128 && !ix->opt_lds_lists) ? 1 : 0);
-    lp.sc.L = L;
-    lp.sc.generic = true;
-    lp.sc.lds_extra = (size_t)pitch4 * 16;
+    const ScanForm f = scan_generic_form(pitch4);
+    lp.sc = scan_choice_of(f, pick_listed(f.L, ix->metric, scan_list_mode(false, k, ix->opt_lds_lists != 0)), pitch4);
   } else {
     lp.sc = choose_scan(ix, k);
   }
-  const int R = 64 / lp.sc.L;
-  lp.groups = (uint32_t)((ix->n + R - 1) / R);
-  lp.lds = (use_select(ix, k) ? 0 : (size_t)4 * k * sizeof(u64)) + lp.sc.lds_extra;
-  if (lp.lds > 64 * 1024)
+  lp.groups = scan_groups(ix->n, lp.sc.L);
+  lp.lds = scan_lds_bytes(use_select(ix, k), k, lp.sc.lds_extra);
+  if (scan_lds_needs_attribute(lp.lds))
     HIP_TRY(hipFuncSetAttribute((const void*)lp.sc.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lp.lds));
   int per_cu = 0;
   HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)lp.sc.fn, 256, lp.lds));
   if (per_cu < 1) return fail(WDBX_E_INVALID, "scan kernel does not fit a CU at k=%d (LDS %zu B)", k, lp.lds);
-  uint32_t blocks = (uint32_t)ix->cu_count * (uint32_t)std::min(per_cu, 2);  // 8 waves/CU x 8 KiB in flight: sweep in profiles/sweep_r01.txt
-  if (ix->opt_blocks > 0) blocks = (uint32_t)ix->opt_blocks;
-  // every wave should have a few passes of work; small corpora get a smaller grid
-  const uint32_t min_groups_per_wave = 1;
-  const uint32_t max_blocks = std::max<uint32_t>(1, (lp.groups + 4 * min_groups_per_wave - 1) / (4 * min_groups_per_wave));
-  lp.blocks = std::max<uint32_t>(1, std::min(blocks, max_blocks));
+  lp.blocks = scan_blocks((uint32_t)ix->cu_count, per_cu, ix->opt_blocks, lp.groups);
   lp.wg_merge = ix->opt_wg_merge != 0;
-  lp.P = lp.wg_merge ? lp.blocks : lp.blocks * 4;  // partial lists: one per workgroup or one per wave
-  lp.chunk = ix->opt_blocked ? (lp.groups + lp.blocks * 4 - 1) / (lp.blocks * 4) : 0;
+  lp.P = scan_partial_lists(lp.wg_merge, lp.blocks);
+  lp.chunk = scan_chunk(ix->opt_blocked != 0, lp.groups, lp.blocks);
   *out = lp;
   return WDBX_OK;
 }
@@ -1104,23 +941,6 @@ static bool range_u8_eligible(const wdbx_index* ix) {
   const Scan8Shape* sh = scan8_shape((uint32_t)ix->dim);
   if (!sh || (uint64_t)sh->pieces * 16 * 10 > (uint64_t)ix->pitch * 4 * 6) return false;
   return (int64_t)ix->n >= ix->opt_range_min_rows;
-}
-
-typedef void (*range_fn)(RangeArgs);
-// lanes per row = the row's quads rounded up to a power of two (up to 64), and the unrolled loads per lane (0: the loop)
-template <int METRIC>
-static range_fn pick_range_scan(uint32_t pitch4) {
-  if (pitch4 <= 1) return range_scan_kernel<METRIC, 1, 1>;
-  if (pitch4 <= 2) return range_scan_kernel<METRIC, 2, 1>;
-  if (pitch4 <= 4) return range_scan_kernel<METRIC, 4, 1>;
-  if (pitch4 <= 8) return range_scan_kernel<METRIC, 8, 1>;
-  if (pitch4 <= 16) return range_scan_kernel<METRIC, 16, 1>;
-  if (pitch4 <= 32) return range_scan_kernel<METRIC, 32, 1>;
-  if (pitch4 <= 64) return range_scan_kernel<METRIC, 64, 1>;
-  if (pitch4 <= 128) return range_scan_kernel<METRIC, 64, 2>;
-  if (pitch4 <= 192) return range_scan_kernel<METRIC, 64, 3>;
-  if (pitch4 <= 256) return range_scan_kernel<METRIC, 64, 4>;
-  return range_scan_kernel<METRIC, 64, 0>;
 }
 
 // squared fp32 norms of the rows added since they were last computed (the L2 selection paths' |c|^2 term), and their

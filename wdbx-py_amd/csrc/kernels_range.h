@@ -101,3 +101,36 @@ __global__ __launch_bounds__(256) void range_filter_kernel(RangeArgs a) {
     wave_append(keep, key, out, a.count + q, a.cap, lane);
   }
 }
+
+// the instance of a form (host_scan_plan.h: range_scan_form): host-side picker, shared by the range search (wdbx_hip.hip) and
+// the tests' launcher (tests/kernel_harness/scan_harness.hip).  null: the form names no instance
+typedef void (*range_fn)(RangeArgs);
+template <int METRIC>
+static range_fn pick_range_scan_form(int P, int NI) {
+  if (P == 64) {
+    switch (NI) {
+      case 0: return range_scan_kernel<METRIC, 64, 0>;
+      case 1: return range_scan_kernel<METRIC, 64, 1>;
+      case 2: return range_scan_kernel<METRIC, 64, 2>;
+      case 3: return range_scan_kernel<METRIC, 64, 3>;
+      case 4: return range_scan_kernel<METRIC, 64, 4>;
+      default: return nullptr;
+    }
+  }
+  if (NI != 1) return nullptr;
+  switch (P) {
+    case 1: return range_scan_kernel<METRIC, 1, 1>;
+    case 2: return range_scan_kernel<METRIC, 2, 1>;
+    case 4: return range_scan_kernel<METRIC, 4, 1>;
+    case 8: return range_scan_kernel<METRIC, 8, 1>;
+    case 16: return range_scan_kernel<METRIC, 16, 1>;
+    case 32: return range_scan_kernel<METRIC, 32, 1>;
+    default: return nullptr;
+  }
+}
+
+template <int METRIC>
+static range_fn pick_range_scan(uint32_t pitch4) {
+  const RangeForm f = range_scan_form(pitch4);
+  return pick_range_scan_form<METRIC>(f.P, f.NI);
+}

@@ -238,3 +238,119 @@ __global__ __launch_bounds__(256) void scan_kernel_listed(ScanArgs a) {
     __syncthreads();  // (the next query's lists and staged query reuse the LDS)
   }
 }
+
+// ------------------------------------------------------------------------------------------------
+// the instance of a form (host_scan_plan.h: scan_form, scan_generic_lanes): host-side pickers, shared by choose_scan /
+// plan_scan (host_index.h) and the tests' launcher (tests/kernel_harness/scan_harness.hip)
+// ------------------------------------------------------------------------------------------------
+typedef void (*scan_fn)(ScanArgs);
+
+template <int L, int QPL, int METRIC, bool NT, bool RAGGED>
+static scan_fn pick_mode(int mode) {
+  switch (mode) {
+    case 0: return scan_kernel<L, QPL, METRIC, NT, 0, RAGGED>;
+    case 1: return scan_kernel<L, QPL, METRIC, NT, 1, RAGGED>;
+    default: return scan_kernel<L, QPL, METRIC, NT, 2, RAGGED>;
+  }
+}
+
+template <int L, int QPL, int METRIC>
+static scan_fn pick_flags(bool nt, int mode, bool ragged) {
+  if (ragged) return pick_mode<L, QPL, METRIC, true, true>(mode);  // ragged instances are non-temporal only
+  return nt ? pick_mode<L, QPL, METRIC, true, false>(mode) : pick_mode<L, QPL, METRIC, false, false>(mode);
+}
+
+template <int L, int QPL>
+static scan_fn pick_variant(int metric, bool nt, int reg, bool ragged) {
+  return metric == WDBX_METRIC_COSINE ? pick_flags<L, QPL, WDBX_METRIC_COSINE>(nt, reg, ragged)
+                                      : pick_flags<L, QPL, WDBX_METRIC_L2>(nt, reg, ragged);
+}
+
+template <int L>
+static scan_fn pick_qpl(int qpl, int metric, bool nt, int reg, bool ragged) {
+  if constexpr (L >= 16) {  // short rows on wide lane groups (d = 68 ... 256 when rows are not line aligned)
+    if (qpl == 1) return pick_variant<L, 1>(metric, nt, reg, ragged);
+    if (qpl == 2) return pick_variant<L, 2>(metric, nt, reg, ragged);
+  }
+  switch (qpl) {
+    case 3: return pick_variant<L, 3>(metric, nt, reg, ragged);
+    case 4: return pick_variant<L, 4>(metric, nt, reg, ragged);
+    case 6: return pick_variant<L, 6>(metric, nt, reg, ragged);
+    case 8: return pick_variant<L, 8>(metric, nt, reg, ragged);
+    case 12: return pick_variant<L, 12>(metric, nt, reg, ragged);
+    default: return nullptr;
+  }
+}
+
+// short rows (d <= 48): L = 4 or 8 with 1..3 quads per lane, 4..8 passes in flight
+template <int L>
+static scan_fn pick_qpl_short(int qpl, int metric, bool nt, int reg, bool ragged) {
+  switch (qpl) {
+    case 1: return pick_variant<L, 1>(metric, nt, reg, ragged);
+    case 2: return pick_variant<L, 2>(metric, nt, reg, ragged);
+    case 3: return L == 4 ? pick_variant<4, 3>(metric, nt, reg, ragged) : nullptr;
+    default: return nullptr;
+  }
+}
+
+// reg: the list mode (scan_list_mode: 0 LDS lists, 1 register lists, 2 key dump).  null: no such instance (scan_has_instance)
+static scan_fn pick_specialised(int L, int qpl, int metric, bool nt, int reg, bool ragged) {
+  if (L == 1 && qpl == 1) return pick_variant<1, 1>(metric, nt, reg, ragged);  // d <= 4: one lane per row
+  if (L == 2 && qpl == 1) return pick_variant<2, 1>(metric, nt, reg, ragged);  // d <= 8
+  if (L == 4) return pick_qpl_short<4>(qpl, metric, nt, reg, ragged);
+  if (L == 8 && qpl <= 2) return pick_qpl_short<8>(qpl, metric, nt, reg, ragged);
+  switch (L) {
+    case 8: return pick_qpl<8>(qpl, metric, nt, reg, ragged);
+    case 16: return pick_qpl<16>(qpl, metric, nt, reg, ragged);
+    case 32: return pick_qpl<32>(qpl, metric, nt, reg, ragged);
+    case 64: return pick_qpl<64>(qpl, metric, nt, reg, ragged);
+    default: return nullptr;
+  }
+}
+
+template <int L, int METRIC>
+static scan_fn pick_generic_mode(int mode) {
+  switch (mode) {
+    case 0: return scan_kernel_generic<L, METRIC, 0>;
+    case 1: return scan_kernel_generic<L, METRIC, 1>;
+    default: return scan_kernel_generic<L, METRIC, 2>;
+  }
+}
+
+template <int L>
+static scan_fn pick_generic_metric(int metric, int mode) {
+  return metric == WDBX_METRIC_COSINE ? pick_generic_mode<L, WDBX_METRIC_COSINE>(mode)
+                                      : pick_generic_mode<L, WDBX_METRIC_L2>(mode);
+}
+
+static scan_fn pick_generic(int L, int metric, int reg) {
+  switch (L) {
+    case 64: return pick_generic_metric<64>(metric, reg);
+    case 1: return pick_generic_metric<1>(metric, reg);
+    case 2: return pick_generic_metric<2>(metric, reg);
+    case 4: return pick_generic_metric<4>(metric, reg);
+    default: return pick_generic_metric<8>(metric, reg);
+  }
+}
+
+template <int L>
+static scan_fn pick_listed_metric(int metric, int reg) {
+  if (metric == WDBX_METRIC_COSINE) return reg ? scan_kernel_listed<L, WDBX_METRIC_COSINE, 1> : scan_kernel_listed<L, WDBX_METRIC_COSINE, 0>;
+  return reg ? scan_kernel_listed<L, WDBX_METRIC_L2, 1> : scan_kernel_listed<L, WDBX_METRIC_L2, 0>;
+}
+
+// the listed repair scan (generic body): reg = 1 register lists (k <= 128), 0 LDS lists
+static scan_fn pick_listed(int L, int metric, int reg) {
+  switch (L) {
+    case 64: return pick_listed_metric<64>(metric, reg);
+    case 1: return pick_listed_metric<1>(metric, reg);
+    case 2: return pick_listed_metric<2>(metric, reg);
+    case 4: return pick_listed_metric<4>(metric, reg);
+    default: return pick_listed_metric<8>(metric, reg);
+  }
+}
+
+// the kernel of a form (scan_form's answer): null when the form names no instance
+static scan_fn pick_scan_form(const ScanForm& f, int metric, bool nt, int mode) {
+  return f.generic ? pick_generic(f.L, metric, mode) : pick_specialised(f.L, f.QPL, metric, nt, mode, f.ragged);
+}

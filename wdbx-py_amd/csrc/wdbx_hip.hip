@@ -99,6 +99,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_subset.h"  // (device-free as well: row-list validation, route and grid sizing of a search among listed rows)
 #include "host_multimask.h"  // (device-free as well: where the queries of a call with a mask per query sit in the tile blocks)
 #include "host_selection.h"  // (device-free as well: the sample, stride and capacities of the selection rounds)
+#include "host_scan_plan.h"  // (device-free as well: the fp32 scan and range forms of a pitch, grid / list / chunk / LDS numbers of a scan)
 #include "host_labels.h"  // (device-free as well: label order, items, over-fetch walk, rounds and scratch of a distinct search)
 #include "host_multivector.h"  // (device-free as well: rounds, segments, route and scratch of a multi-vector search)
 #include "host_rowlists.h"  // (device-free as well: slots, rounds, query blocks and work items of a call with a row list per query)
@@ -1675,7 +1676,7 @@ int wdbx_index_search_recommend(wdbx_index* ix, const float* examples, const uin
                           out_side);
 } WDBX_CATCH
 
-// ---- range search (range_u8_eligible, pick_range_scan: host_index.h) -------------------------------
+// ---- range search (range_u8_eligible: host_index.h; pick_range_scan: kernels_range.h) --------------
 // The whole call holds the handle's mutex (like a masked search: the key buffers are the handle's).  Per round of up to 64
 // queries: [u8 path: memset counters, scan8_kernel<PHASE 2> -> candidates] -> memset, range_filter_kernel / range_scan_kernel
 // -> result keys; one synchronisation reads both counters.  A counter past its buffer (the counters count on) grows that
