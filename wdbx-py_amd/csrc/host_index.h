@@ -1390,10 +1390,7 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
   return WDBX_OK;
 }
 
-// tile kernel families of the batched path (option gemm_bf16): 0 = exact fp32 tiles, 1 = bf16 selection tiles
-// reading the fp32 rows, 2 = bf16 selection tiles reading the bf16 shadow copy (falls back to 1 when the
-// shadow does not fit in device memory)
-enum { GEMM_FP32 = 0, GEMM_BF16 = 1, GEMM_BF16_SHADOW = 2, GEMM_I8 = 3 };
+// (the tile kernel families GEMM_FP32 / GEMM_BF16 / GEMM_BF16_SHADOW / GEMM_I8: kernels_tiles.h, behind the kernels)
 static inline int gemm_family(const wdbx_index* ix) {
   return ix->opt_gemm_bf16 <= 0 ? GEMM_FP32 : ix->opt_gemm_bf16 == 1 ? GEMM_BF16 : GEMM_BF16_SHADOW;
 }
@@ -1481,54 +1478,17 @@ static bool masked_tiles_ready(wdbx_index* ix, int k) {
   if (ix->opt_gemm_masked <= 0 || ix->opt_gemm8_variant != 0 || use_select(ix, k) || !ix->n) return false;
   return i8_tiles_shape_ok(ix) && prepare_i8g_shadow(ix);
 }
-static inline uint32_t gemm_tile_rows(int family) { return family == GEMM_FP32 ? GB_M : GW_M; }
-
-template <int PHASE, int CT, int METRIC, bool GROUPB>
-static void (*pick_gemm_kernel_gb(int family, bool ktail))(GemmArgs) {
-  if constexpr (CT >= 2) {
-    // (L2 with per-group bounds on the shadow tiles exists for query blocks of 128 only: the 256-wide form of that one
-    // combination does not fit the register file without spilling; enqueue_search_gemm never asks for it)
-    if constexpr (CT == 4 && GROUPB && METRIC == WDBX_METRIC_L2) {
-      if (family == GEMM_BF16_SHADOW) return nullptr;
-    } else if (family == GEMM_BF16_SHADOW) {
-      return gemm_bf16w8_kernel<PHASE, false, CT, METRIC, true, GROUPB>;
-    }
-    if (family == GEMM_BF16)
-      return ktail ? gemm_bf16w8_kernel<PHASE, true, CT, METRIC, false, GROUPB> : gemm_bf16w8_kernel<PHASE, false, CT, METRIC, false, GROUPB>;
-  }
-  if constexpr (GROUPB && METRIC == WDBX_METRIC_COSINE) return nullptr;  // exact fp32 inner-product tiles: nothing to bound
-  else return ktail ? gemm_topk_kernel<PHASE, true, CT, METRIC, GROUPB> : gemm_topk_kernel<PHASE, false, CT, METRIC, GROUPB>;
-}
-
-template <int PHASE, int CT, int METRIC>
-static void (*pick_gemm_kernel(int family, bool ktail, bool groupb))(GemmArgs) {
-  return groupb ? pick_gemm_kernel_gb<PHASE, CT, METRIC, true>(family, ktail) : pick_gemm_kernel_gb<PHASE, CT, METRIC, false>(family, ktail);
-}
-
+// (the instances, their pickers and the launch helpers: kernels_tiles.h, behind the kernels)
 template <int PHASE, int CT>
 static int launch_gemm_ct(wdbx_index* ix, const GemmArgs& g, int family) {
   if (family != GEMM_FP32 && CT < 2) return fail(WDBX_E_STATE, "bf16 tiles need a query block of at least 128");
-  const int bk = family == GEMM_BF16_SHADOW ? 64 : 32;  // elements per LDS chunk
-  const uint32_t tile_rows = gemm_tile_rows(family);
-  // (+ 64 floats per wave behind the tiles: the L2 epilogue's row norms)
-  const size_t lds = (family == GEMM_FP32 ? (size_t)(2 * GB_M + 2 * 64 * CT) * 36 * sizeof(float) + 4 * 64 * sizeof(float)
-                                          : (size_t)(2 * tile_rows + 2 * 64 * CT) * (bk * 2 + 16) + 8 * 64 * sizeof(float));
-  // K tail: the fp32 tiles step 8 quads at a time, the bf16 tiles a pair of chunks of 8 quads (never on the
-  // shadow, which is padded)
-  const bool ktail = family != GEMM_BF16_SHADOW && (g.pitch4 % (family == GEMM_FP32 ? 8u : 16u)) != 0;
-  const bool l2 = ix->metric == WDBX_METRIC_L2;
-  void (*fn)(GemmArgs) = l2 ? pick_gemm_kernel<PHASE, CT, WDBX_METRIC_L2>(family, ktail, g.gmax != nullptr)
-                            : pick_gemm_kernel<PHASE, CT, WDBX_METRIC_COSINE>(family, ktail, g.gmax != nullptr);
-  if (!fn) return fail(WDBX_E_STATE, "no tile kernel for this family with per-group bounds");
-  HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  // fp32 tiles, CT = 1, 2: the tile's LDS footprint (55 / 74 KiB) lets two workgroups share a CU.
-  // bf16 tiles: one 8-wave workgroup per CU (two waves per SIMD).
-  const uint32_t per_cu = (family != GEMM_FP32 || CT == 4) ? 1 : 2;
-  const uint32_t grid = std::min<uint32_t>(g.num_tiles, (uint32_t)ix->cu_count * per_cu);
+  const GemmLaunch l = gemm_launch_ct<PHASE, CT>(family, ix->metric, g.gmax != nullptr, g.pitch4);
+  if (!l.fn) return fail(WDBX_E_STATE, "no tile kernel for this family with per-group bounds");
+  HIP_TRY(gemm_prepare(l));
+  const uint32_t grid = gemm_grid(l, g.num_tiles, (uint32_t)ix->cu_count);
   int rc = record(ix->gemm_ev, ix->profile, ix->stream, true);
   if (rc) return rc;
-  hipLaunchKernelGGL(fn, dim3(grid), dim3(family == GEMM_FP32 ? 256 : 512), lds, ix->stream, g);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(enqueue_gemm(ix->stream, l, g, grid));
   return record(ix->gemm_ev, ix->profile, ix->stream, false);
 }
 
@@ -1662,6 +1622,7 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
   const float gamma = 1.02f * nu / (1.0f - nu);
   const float sel_eps = (gamma + (bf16 ? 1.05f * 0.0078125f : 0.0f)) * 1.0102f, sel_gam = gamma * 1.01f;
   const float sel_floor = bf16 ? 7.5e-37f * sqrtf((float)ix->pitch) : 0.0f;  // 2^-120 sqrt(d): see GemmArgs::floor_abs
+  const float sel_under = ldexpf((float)(ix->pitch + 18), -149);  // gradual underflow of the fma chain: GemmArgs::under_abs
 
   // per_query: the single-query caller.  Every query makes its OWN pass pair (a 128-column tile with one live
   // column), but the small kernels around the passes (conversion, thresholds, margins, re-scoring, final
@@ -1710,6 +1671,7 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
       g.eps = sel_eps;
       g.gam = sel_gam;
       g.floor_abs = sel_floor;
+      g.under_abs = sel_under;
     }
     const size_t qb_block = (size_t)gbn * kpad;  // bf16 elements per query block
     if (bf16) {
@@ -1728,7 +1690,7 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
     if ((rc = enqueue_sample_threshold(ix, s.bounds, k, nv, false))) return rc;  // (these families never took kth_score_kernel)
     if (inexact && !group_bounds) {  // one global rounding-error margin below the sampled threshold
       hipLaunchKernelGGL(tau_margin_kernel, dim3(nv), dim3(64), 0, ix->stream, ix->d_tau, qsrc, (uint32_t)ix->pitch, nv,
-                         (const uint32_t*)ix->d_cnmax, ix->metric, (int)bf16, sel_floor);
+                         (const uint32_t*)ix->d_cnmax, ix->metric, (int)bf16, sel_floor, sel_under);
       HIP_TRY(hipGetLastError());
     }  // (with per-group bounds the k-th largest reported LOWER bound is already a valid threshold)
     g.num_tiles = tiles;

@@ -101,9 +101,11 @@ __global__ void query_norm_kernel(const float* queries, uint32_t pitch, int nv, 
 //                        in fp32, so |dot_bf16 - c.q| <= (2^-7 + 2^-16 + gamma) |c||q|  (Cauchy-Schwarz);
 //                        cosine: v = dot;  L2: v = 2 dot - |c|^2 with the fp32 bound on the second term.
 // Both the threshold (a maximum of such values) and every candidate carry that error, hence 2x.
+// Scores in the fp32 denormal range: every fma there rounds to a multiple of 2^-149 whatever its operands, an ABSOLUTE
+// error of at most under_abs = (pitch + 18) 2^-149 per dot product (GemmArgs::under_abs), twice that for the L2 form.
 // (fp32 tiles with the cosine metric need no margin: selection and final scores are the same numbers.)
 __global__ void tau_margin_kernel(float* tau, const float* queries, uint32_t pitch, int nv, const uint32_t* cn_max_bits,
-                                  int metric, int bf16, float floor_abs) {
+                                  int metric, int bf16, float floor_abs, float under_abs) {
   const int q = blockIdx.x, lane = threadIdx.x;  // one wave per query
   if (q >= nv) return;
   const float* p = queries + (size_t)q * pitch;
@@ -118,7 +120,9 @@ __global__ void tau_margin_kernel(float* tau, const float* queries, uint32_t pit
     const float cq = sqrtf(cmax * s) * 1.0001f;
     float margin = metric == WDBX_METRIC_L2 ? 2.0f * (2.0f * eps_dot * cq + gamma * cmax) : 2.0f * eps_dot * cq;
     // + the absolute term for operands in the denormal range (see GemmArgs::floor_abs)
-    margin = margin * 1.01f + 2.0f * (metric == WDBX_METRIC_L2 ? 2.0f : 1.0f) * floor_abs * (sqrtf(cmax) + sqrtf(s));
+    const float two = metric == WDBX_METRIC_L2 ? 2.0f : 1.0f;
+    margin = margin * 1.01f + 2.0f * two * floor_abs * (sqrtf(cmax) + sqrtf(s));
+    margin += 2.0f * two * under_abs;  // gradual underflow: an absolute term, a multiple of 2^-149
     if (!(margin == margin)) margin = INFINITY;  // NaN query: select everything, the exact pass decides
     if (tau[q] > -INFINITY) tau[q] -= margin;
   }

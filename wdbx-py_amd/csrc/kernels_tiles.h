@@ -43,6 +43,9 @@ struct GemmArgs {
   float eps, gam;
   float floor_abs;     // absolute term: operands in the denormal range lose their RELATIVE precision when rounded to bf16
                        // (or are flushed); each costs at most 2^-126 per product, covered by floor_abs * (|c| + |q|)
+  float under_abs;     // absolute term of every family: an fma whose result lies in the fp32 denormal range rounds to a
+                       // multiple of 2^-149 (gradual underflow: at most 2^-150 each, which no relative bound covers), so a
+                       // chain over the row is off by at most (pitch + 18) 2^-149 on top of the relative bound; L2: twice
 };
 
 // Tile epilogue shared by the fp32 and bf16 tile kernels.  acc holds the wave's 64 rows x 32*CT queries in
@@ -81,7 +84,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f16v (&acc)[2][
     const float g = gm_pref;  // = a.gmax[this wave's 64-row group], loaded by the caller before the K loop
     const float sg = sqrtf(g), two = METRIC == WDBX_METRIC_L2 ? 2.0f : 1.0f;
     bscale = two * (a.eps * sg + a.floor_abs);
-    bconst = (METRIC == WDBX_METRIC_L2 ? a.gam * g : 0.f) + two * a.floor_abs * sg;
+    bconst = ((METRIC == WDBX_METRIC_L2 ? a.gam * g : 0.f) + two * a.floor_abs * sg) + two * a.under_abs;
   }
   auto bound = [&](int ct) -> float {
     if constexpr (GROUPB) return fmaf(bscale, a.qn[ch * (32 * CT) + ct * 32 + l31], bconst);
@@ -609,4 +612,87 @@ __global__ __launch_bounds__(256) void queries_to_bf16_kernel(const float* q, ui
     const uint32_t src = blk * live + r;
     out[e] = to_bf16_sel((r < live && src < nv && c < pitch) ? q[(size_t)src * pitch + c] : 0.0f);
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The instances of the two tile kernels, their pickers and the launch helpers (what host_index.h::launch_gemm_ct and the
+// tests' launcher, tests/kernel_harness/gemm_harness.hip, call).
+// ------------------------------------------------------------------------------------------------
+// tile kernel families of the batched path (option gemm_bf16): 0 = exact fp32 tiles, 1 = bf16 selection tiles
+// reading the fp32 rows, 2 = bf16 selection tiles reading the bf16 shadow copy (falls back to 1 when the
+// shadow does not fit in device memory); 3 = the int8 tiles of kernels_tiles8.h (no instance here)
+enum { GEMM_FP32 = 0, GEMM_BF16 = 1, GEMM_BF16_SHADOW = 2, GEMM_I8 = 3 };
+static inline uint32_t gemm_tile_rows(int family) { return family == GEMM_FP32 ? GB_M : GW_M; }
+
+typedef void (*gemm_fn)(GemmArgs);
+
+template <int PHASE, int CT, int METRIC, bool GROUPB>
+static gemm_fn pick_gemm_kernel_gb(int family, bool ktail) {
+  if constexpr (CT >= 2) {
+    // (L2 with per-group bounds on the shadow tiles exists for query blocks of 128 only: the 256-wide form of that one
+    // combination does not fit the register file without spilling; enqueue_search_gemm never asks for it)
+    if constexpr (CT == 4 && GROUPB && METRIC == WDBX_METRIC_L2) {
+      if (family == GEMM_BF16_SHADOW) return nullptr;
+    } else if (family == GEMM_BF16_SHADOW) {
+      return gemm_bf16w8_kernel<PHASE, false, CT, METRIC, true, GROUPB>;
+    }
+    if (family == GEMM_BF16)
+      return ktail ? gemm_bf16w8_kernel<PHASE, true, CT, METRIC, false, GROUPB> : gemm_bf16w8_kernel<PHASE, false, CT, METRIC, false, GROUPB>;
+  }
+  if constexpr (GROUPB && METRIC == WDBX_METRIC_COSINE) return nullptr;  // exact fp32 inner-product tiles: nothing to bound
+  else return ktail ? gemm_topk_kernel<PHASE, true, CT, METRIC, GROUPB> : gemm_topk_kernel<PHASE, false, CT, METRIC, GROUPB>;
+}
+
+template <int PHASE, int CT, int METRIC>
+static gemm_fn pick_gemm_kernel(int family, bool ktail, bool groupb) {
+  return groupb ? pick_gemm_kernel_gb<PHASE, CT, METRIC, true>(family, ktail) : pick_gemm_kernel_gb<PHASE, CT, METRIC, false>(family, ktail);
+}
+
+// the instance (null: the library has none), its dynamic LDS bytes, threads per workgroup, whether it is the K-tail form and
+// how many workgroups share a CU, for query blocks of 64 * ct (ct = 1, 2, 4) and rows of pitch4 16-byte pieces
+struct GemmLaunch {
+  gemm_fn fn;
+  size_t lds;
+  uint32_t threads;
+  bool ktail;
+  uint32_t per_cu;
+};
+template <int PHASE, int CT>
+static GemmLaunch gemm_launch_ct(int family, int metric, bool groupb, uint32_t pitch4) {
+  const int bk = family == GEMM_BF16_SHADOW ? 64 : 32;  // elements per LDS chunk
+  const uint32_t tile_rows = gemm_tile_rows(family);
+  // (+ 64 floats per wave behind the tiles: the L2 epilogue's row norms)
+  const size_t lds = (family == GEMM_FP32 ? (size_t)(2 * GB_M + 2 * 64 * CT) * 36 * sizeof(float) + 4 * 64 * sizeof(float)
+                                          : (size_t)(2 * tile_rows + 2 * 64 * CT) * (bk * 2 + 16) + 8 * 64 * sizeof(float));
+  // K tail: the fp32 tiles step 8 quads at a time, the bf16 tiles a pair of chunks of 8 quads (never on the
+  // shadow, which is padded)
+  const bool ktail = family != GEMM_BF16_SHADOW && (pitch4 % (family == GEMM_FP32 ? 8u : 16u)) != 0;
+  // fp32 tiles, CT = 1, 2: the tile's LDS footprint (55 / 74 KiB) lets two workgroups share a CU.
+  // bf16 tiles: one 8-wave workgroup per CU (two waves per SIMD).
+  const uint32_t per_cu = (family != GEMM_FP32 || CT == 4) ? 1 : 2;
+  gemm_fn fn = nullptr;
+  // (the bf16 tiles need a query block of at least 128)
+  if (family == GEMM_FP32 || ((family == GEMM_BF16 || family == GEMM_BF16_SHADOW) && CT >= 2))
+    fn = metric == WDBX_METRIC_L2 ? pick_gemm_kernel<PHASE, CT, WDBX_METRIC_L2>(family, ktail, groupb)
+                                  : pick_gemm_kernel<PHASE, CT, WDBX_METRIC_COSINE>(family, ktail, groupb);
+  return GemmLaunch{fn, lds, family == GEMM_FP32 ? 256u : 512u, ktail, per_cu};
+}
+template <int PHASE>
+static GemmLaunch gemm_launch_of(int family, int ct, int metric, bool groupb, uint32_t pitch4) {
+  switch (ct) {
+    case 1: return gemm_launch_ct<PHASE, 1>(family, metric, groupb, pitch4);
+    case 2: return gemm_launch_ct<PHASE, 2>(family, metric, groupb, pitch4);
+    case 4: return gemm_launch_ct<PHASE, 4>(family, metric, groupb, pitch4);
+    default: return GemmLaunch{nullptr, 0, 0, false, 1};
+  }
+}
+static inline uint32_t gemm_grid(const GemmLaunch& l, uint32_t num_tiles, uint32_t cus) {
+  return std::min<uint32_t>(num_tiles, cus * l.per_cu);
+}
+static inline hipError_t gemm_prepare(const GemmLaunch& l) {
+  return hipFuncSetAttribute((const void*)l.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds);
+}
+static inline hipError_t enqueue_gemm(hipStream_t stream, const GemmLaunch& l, const GemmArgs& g, uint32_t grid) {
+  hipLaunchKernelGGL(l.fn, dim3(grid), dim3(l.threads), l.lds, stream, g);
+  return hipGetLastError();
 }
