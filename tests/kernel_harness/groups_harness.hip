@@ -2,7 +2,8 @@
 // tests/test_gpu_groups_kernels.py).
 //
 // Built from the very headers libwdbx_hip.so is built from, in wdbx_hip.hip's order: kernels_common.h, kernels_aux.h
-// (exact_finish next to accum), kernels_subset.h (exact_score_block), host_groups.h and kernels_groups.h.  The instances come
+// (exact_finish next to accum), host_subset.h (row_block_ni), host_groups.h, kernels_rowblock.h (the members kernel's frame:
+// exact_score_block, the key rule, the mask bit) and kernels_groups.h.  The instances come
 // from pick_group_members / pick_group_merge.  This file defines no kernel of its own.  The entry points take HOST pointers
 // with their lengths: copy in, launch on the null stream, synchronise, copy out; they return the HIP error code, or -1 when the
 // arguments would make a kernel read or write outside the uploaded arrays (checked here, before anything is launched).  Output
@@ -23,8 +24,9 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 
 #include "kernels_common.h"
 #include "kernels_aux.h"
-#include "kernels_subset.h"
+#include "host_subset.h"
 #include "host_groups.h"
+#include "kernels_rowblock.h"
 #include "kernels_groups.h"
 static_assert(GROUPS_MAX_SIZE_DEV == GROUPS_MAX_SIZE && GROUPS_MAX_SIZE == WDBX_MAX_GROUP_SIZE, "a wave's register list holds a group");
 static_assert(sizeof(GroupTaskDev) == sizeof(GroupTask) && sizeof(GroupTask) == 16, "the device reads the host's tasks");

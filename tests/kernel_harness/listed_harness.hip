@@ -4,8 +4,8 @@
 //
 // Built from the very headers libwdbx_hip.so is built from, in wdbx_hip.hip's order: kernels_common.h, kernels_aux.h (for
 // exact_finish next to accum; its own kernels need nothing else), the device-free host headers of the four calls (the structs
-// the kernels read and the sizes of their dynamic LDS: subset_lists_lds, label_rank_lds, multivector_rank_lds) and the four
-// kernel headers.  The instance of every launch comes from the pickers that live next to the kernels (pick_subset,
+// the kernels read and the sizes of their dynamic LDS: subset_lists_lds, label_rank_lds, multivector_rank_lds), kernels_rowblock.h
+// (the frame of the first three kernels; its loads per lane come from host_subset.h's row_block_ni) and the four kernel headers.  The instance of every launch comes from the pickers that live next to the kernels (pick_subset,
 // pick_rowlists, pick_label_keys, pick_label_rank, pick_multivector_rank); a null picker result returns -1.  This file defines
 // no kernel of its own.  Each entry point takes HOST pointers with their lengths, an explicit grid.x and the scalar fields of
 // the kernel's argument struct: copy in, launch on the null stream, synchronise, copy out; it returns the HIP error code, or
@@ -31,6 +31,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_rowlists.h"
 #include "host_labels.h"
 #include "host_multivector.h"
+#include "kernels_rowblock.h"
 #include "kernels_subset.h"
 #include "kernels_rowlists.h"
 #include "kernels_labels.h"

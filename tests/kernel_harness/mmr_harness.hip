@@ -2,7 +2,8 @@
 // tests/test_gpu_mmr_kernels.py): mmr_pairs_kernel and mmr_select_kernel.
 //
 // Built from the very headers libwdbx_hip.so is built from, in wdbx_hip.hip's order: kernels_common.h, kernels_aux.h (exact_finish
-// next to accum), host_mmr.h (the query table, the grids), kernels_subset.h (exact_score_block) and kernels_mmr.h.  The pairs
+// next to accum), host_subset.h (row_block_ni), host_mmr.h (the query table, the grids), kernels_rowblock.h (the pairs kernel's
+// frame: exact_score_block) and kernels_mmr.h.  The pairs
 // instance comes from pick_mmr_pairs, its grid from mmr_pairs_grid.  This file defines no kernel of its own.  Each entry point
 // takes HOST pointers with their lengths: copy in, launch on the null stream, synchronise, copy out; it returns the HIP error
 // code, or -1 when the arguments would make a kernel read or write outside the uploaded arrays (checked here, before anything
@@ -22,8 +23,9 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 
 #include "kernels_common.h"
 #include "kernels_aux.h"
+#include "host_subset.h"
 #include "host_mmr.h"
-#include "kernels_subset.h"
+#include "kernels_rowblock.h"
 #include "kernels_mmr.h"
 static_assert(MMR_MAX_POOL == WDBX_MAX_K, "a pool is a top-k answer");
 static_assert(sizeof(MmrQuery) == 4 * sizeof(uint32_t), "the query table is four 32-bit words per query");

@@ -2,7 +2,8 @@
 // tests/test_gpu_recommend_kernels.py): both sides, all three ranking modes.
 //
 // Built from the very headers libwdbx_hip.so is built from, in wdbx_hip.hip's order: kernels_common.h, kernels_aux.h
-// (exact_finish next to accum), kernels_subset.h (exact_score_block), host_recommend.h and kernels_recommend.h.  The instance
+// (exact_finish next to accum), host_subset.h (row_block_ni), host_recommend.h, kernels_rowblock.h (the kernel's frame:
+// exact_score_block, the mask bit) and kernels_recommend.h.  The instance
 // comes from pick_recommend.  This file defines no kernel of its own.  The entry point takes HOST pointers with their lengths:
 // copy in, launch on the null stream, synchronise, copy out; it returns the HIP error code, or -1 when the arguments would
 // make the kernel read or write outside the uploaded arrays (checked here, before anything is launched).  The output array is
@@ -23,8 +24,9 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 
 #include "kernels_common.h"
 #include "kernels_aux.h"
-#include "kernels_subset.h"
+#include "host_subset.h"
 #include "host_recommend.h"
+#include "kernels_rowblock.h"
 #include "kernels_recommend.h"
 static_assert(RECOMMEND_MAX_EXAMPLES == WDBX_MAX_EXAMPLES && RECOMMEND_MAX_EXCLUDE == WDBX_MAX_EXCLUDE_ROWS, "the plan's limits are the header's");
 

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "host_labels.h"
+#include "host_subset.h"
 
 constexpr int MMR_MAX_POOL = 2048;        // (= WDBX_MAX_K) candidates of one query; 8 per thread of the selection workgroup
 constexpr int MMR_BLOCK = 8;              // candidate columns one wave scores a fetched row against (mmr_pairs_kernel's QB)
@@ -105,8 +106,7 @@ static inline void mmr_round_queries(const uint32_t* m, const MmrRound& r, std::
   }
 }
 
-// loads per lane of a row in the pairs kernel: subset_kernel's choice (0 = the loop, above 256 quads)
-static inline int mmr_pairs_ni(uint32_t pitch4) { return pitch4 <= 128 ? 2 : pitch4 <= 256 ? 4 : 0; }
+static inline int mmr_pairs_ni(uint32_t pitch4) { return row_block_ni(pitch4); }  // (the pairs kernel's loads per lane: the shared ladder)
 
 // grid of the pairs kernel for a round: x = chunks of MMR_CHUNK_ROWS candidate rows, y = blocks of MMR_BLOCK candidate columns
 // (both of the round's largest pool: a workgroup past its query's pool returns at once), z = the round's queries

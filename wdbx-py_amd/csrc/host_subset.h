@@ -7,6 +7,19 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
+
+// loads per lane of a gathered row in every kernel built on kernels_rowblock.h: 2 up to 128 quads, 4 up to 256, 0 = the loop
+constexpr int row_block_ni(uint32_t pitch4) { return pitch4 <= 128 ? 2 : pitch4 <= 256 ? 4 : 0; }
+// f(std::integral_constant<int, NI>()) for that value: a picker instantiates its kernel with NI = decltype(ni)::value
+template <typename F>
+static inline auto with_row_block_ni(uint32_t pitch4, F f) {
+  switch (row_block_ni(pitch4)) {
+    case 2: return f(std::integral_constant<int, 2>());
+    case 4: return f(std::integral_constant<int, 4>());
+    default: return f(std::integral_constant<int, 0>());
+  }
+}
 
 // The list must be strictly increasing row numbers below n_rows (so every key of the call is unique, which the merges rely
 // on, and one pass validates it).  Returns n_ids when the list is valid, else the index of the first offending entry.

@@ -22,13 +22,12 @@ struct GroupMembersArgs {
 };
 
 // Grid: x = the round's tasks.  Wave w of the workgroup takes positions w, w + 4, ... of the task, U rows' loads in flight (as
-// label_keys_kernel).  A row's score is exact_score_block's (kernels_subset.h): rescore_kernel's arithmetic bit for bit, wave-
+// label_keys_kernel).  A row's score is exact_score_block's (kernels_rowblock.h): rescore_kernel's arithmetic bit for bit, wave-
 // uniform, so is its key; a masked-out row (tested on the wave-uniform row, before the scoring) and a NaN score give no key.
 // Each wave keeps its g best keys in registers (one per lane); wave 0 merges the four lists as subset_kernel does.
 template <int METRIC, int NI>
 __global__ __launch_bounds__(256) void group_members_kernel(GroupMembersArgs a) {
-  constexpr int U = NI == 0 ? 1 : (NI <= 2 ? 4 : 2);
-  constexpr int NR = NI > 0 ? NI : 1;
+  constexpr int U = row_block_u(NI), NR = row_block_nr(NI);
   __shared__ u64 lists[4 * GROUPS_MAX_SIZE_DEV];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t j = (uint32_t)lane;
@@ -61,12 +60,10 @@ __global__ __launch_bounds__(256) void group_members_kernel(GroupMembersArgs a) 
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       if (cur + (uint32_t)u * 4 >= t.count) break;  // (wave-uniform)
-      const bool allowed = !a.mask || ((a.mask[row[u] >> 5] >> (row[u] & 31)) & 1u);
-      if (!allowed) continue;  // (wave-uniform)
+      if (!row_allowed(a.mask, row[u])) continue;  // (wave-uniform)
       float s[1];
       exact_score_block<METRIC, 1, NI>(c[u], a.rows + (size_t)row[u] * a.pitch4, q, qp, a.pitch4, j, s);
-      const u64 mine = (s[0] == s[0]) ? make_key(s[0] + 0.0f, row[u]) : 0ull;  // a NaN score is never a member
-      const u64 key = readlane64(mine, 0);
+      const u64 key = readlane64(row_key(s[0], row[u]), 0);
       if (key > thr) thr = top.insert(key, lane);
     }
   }
@@ -81,15 +78,11 @@ __global__ __launch_bounds__(256) void group_members_kernel(GroupMembersArgs a) 
 
 typedef void (*group_members_fn)(GroupMembersArgs);
 
-template <int METRIC>
-static group_members_fn pick_group_members_ni(uint32_t pitch4) {
-  if (pitch4 <= 128) return group_members_kernel<METRIC, 2>;
-  if (pitch4 <= 256) return group_members_kernel<METRIC, 4>;
-  return group_members_kernel<METRIC, 0>;
-}
-
 static group_members_fn pick_group_members(int metric, uint32_t pitch4) {
-  return metric == WDBX_METRIC_L2 ? pick_group_members_ni<WDBX_METRIC_L2>(pitch4) : pick_group_members_ni<WDBX_METRIC_COSINE>(pitch4);
+  return with_row_block_ni(pitch4, [&](auto ni) -> group_members_fn {
+    constexpr int NI = decltype(ni)::value;
+    return metric == WDBX_METRIC_L2 ? group_members_kernel<WDBX_METRIC_L2, NI> : group_members_kernel<WDBX_METRIC_COSINE, NI>;
+  });
 }
 
 struct GroupMergeArgs {

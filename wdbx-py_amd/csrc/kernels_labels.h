@@ -22,13 +22,12 @@ struct LabelKeysArgs {
 };
 
 // Grid: x = workgroups along the spans (wave w of the grid takes spans w, w + W, ...; U rows' loads in flight per wave), y =
-// query blocks.  A row's QB scores are exact_score_block's (kernels_subset.h): rescore_kernel's arithmetic bit for bit, wave-
+// query blocks.  A row's QB scores are exact_score_block's (kernels_rowblock.h): rescore_kernel's arithmetic bit for bit, wave-
 // uniform.  A masked-out row, a NaN score (removed rows) give key 0.  The wave keeps the running maximum of make_key(score, row)
 // per query; at every label boundary and at the span's end lane b stores query b's maximum as the item's key (0 = no row).
 template <int METRIC, int QB, int NI>
 __global__ __launch_bounds__(256) void label_keys_kernel(LabelKeysArgs a) {
-  constexpr int U = NI == 0 ? 1 : (NI <= 2 ? 4 : 2);
-  constexpr int NR = NI > 0 ? NI : 1;
+  constexpr int U = row_block_u(NI), NR = row_block_nr(NI);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t j = (uint32_t)lane;
   const uint32_t q0 = blockIdx.y * QB;
@@ -87,12 +86,9 @@ __global__ __launch_bounds__(256) void label_keys_kernel(LabelKeysArgs a) {
           ++item;
           cur_label = lab[u];
         }
-        const bool allowed = !a.mask || ((a.mask[row[u] >> 5] >> (row[u] & 31)) & 1u);
+        const bool allowed = row_allowed(a.mask, row[u]);
 #pragma unroll
-        for (int b = 0; b < QB; ++b) {
-          const u64 key = (allowed && s[b] == s[b]) ? make_key(s[b] + 0.0f, row[u]) : 0ull;  // a NaN score is never a result
-          best[b] = max(best[b], key);
-        }
+        for (int b = 0; b < QB; ++b) best[b] = max(best[b], allowed ? row_key(s[b], row[u]) : 0ull);
       }
     }
     flush(item);
@@ -101,19 +97,15 @@ __global__ __launch_bounds__(256) void label_keys_kernel(LabelKeysArgs a) {
 
 typedef void (*label_keys_fn)(LabelKeysArgs);
 
-template <int METRIC, int QB>
-static label_keys_fn pick_label_keys_ni(uint32_t pitch4) {
-  if (pitch4 <= 128) return label_keys_kernel<METRIC, QB, 2>;
-  if (pitch4 <= 256) return label_keys_kernel<METRIC, QB, 4>;
-  return label_keys_kernel<METRIC, QB, 0>;
-}
-
 // qb as distinct_plan (host_labels.h) chooses it: 1 or 8; null for any other
 static label_keys_fn pick_label_keys(int metric, int qb, uint32_t pitch4) {
-  const bool l2 = metric == WDBX_METRIC_L2;
-  if (qb == 1) return l2 ? pick_label_keys_ni<WDBX_METRIC_L2, 1>(pitch4) : pick_label_keys_ni<WDBX_METRIC_COSINE, 1>(pitch4);
-  if (qb == 8) return l2 ? pick_label_keys_ni<WDBX_METRIC_L2, 8>(pitch4) : pick_label_keys_ni<WDBX_METRIC_COSINE, 8>(pitch4);
-  return nullptr;
+  return with_row_block_ni(pitch4, [&](auto ni) -> label_keys_fn {
+    constexpr int NI = decltype(ni)::value;
+    const bool l2 = metric == WDBX_METRIC_L2;
+    if (qb == 1) return l2 ? label_keys_kernel<WDBX_METRIC_L2, 1, NI> : label_keys_kernel<WDBX_METRIC_COSINE, 1, NI>;
+    if (qb == 8) return l2 ? label_keys_kernel<WDBX_METRIC_L2, 8, NI> : label_keys_kernel<WDBX_METRIC_COSINE, 8, NI>;
+    return nullptr;
+  });
 }
 
 struct LabelRankArgs {

@@ -10,7 +10,7 @@ struct MmrPairsArgs {
 };
 
 // G[i][j] = the score of candidate row i with candidate row j as the query, exact_score's arithmetic (exact_score_block,
-// kernels_subset.h: lane order, fma chain, fold and xor tree of kernels_aux.h), in the ranking domain: the inner product + 0.0f
+// kernels_rowblock.h: lane order, fma chain, fold and xor tree of kernels_aux.h), in the ranking domain: the inner product + 0.0f
 // (as every key normalises it), the negated squared distance as it is.  EVERY (i, j) is computed, nothing is mirrored: the
 // products (and the squared differences) commute and the order of summation depends on the element index only, so G[i][j] and
 // G[j][i] are the same bits anyway, and each word has the one writer below.
@@ -20,8 +20,7 @@ struct MmrPairsArgs {
 // short last block repeat the last candidate and write nothing.  Every lane of a wave ends with the same sum; lane 0 writes.
 template <int METRIC, int QB, int NI>
 __global__ __launch_bounds__(256) void mmr_pairs_kernel(MmrPairsArgs a) {
-  constexpr int U = NI == 0 ? 1 : (NI <= 2 ? 4 : 2);
-  constexpr int NR = NI > 0 ? NI : 1;
+  constexpr int U = row_block_u(NI), NR = row_block_nr(NI);
   const MmrQuery mq = a.qs[blockIdx.z];
   const uint32_t m = mq.m, j0 = blockIdx.y * QB, i0 = blockIdx.x * MMR_CHUNK_ROWS;
   if (j0 >= m || i0 >= m) return;  // (workgroup-uniform)
@@ -69,17 +68,11 @@ __global__ __launch_bounds__(256) void mmr_pairs_kernel(MmrPairsArgs a) {
 
 typedef void (*mmr_pairs_fn)(MmrPairsArgs);
 
-template <int METRIC>
-static mmr_pairs_fn pick_mmr_pairs_metric(uint32_t pitch4) {
-  switch (mmr_pairs_ni(pitch4)) {
-    case 2: return mmr_pairs_kernel<METRIC, MMR_BLOCK, 2>;
-    case 4: return mmr_pairs_kernel<METRIC, MMR_BLOCK, 4>;
-    default: return mmr_pairs_kernel<METRIC, MMR_BLOCK, 0>;
-  }
-}
-
 static mmr_pairs_fn pick_mmr_pairs(int metric, uint32_t pitch4) {
-  return metric == WDBX_METRIC_L2 ? pick_mmr_pairs_metric<WDBX_METRIC_L2>(pitch4) : pick_mmr_pairs_metric<WDBX_METRIC_COSINE>(pitch4);
+  return with_row_block_ni(pitch4, [&](auto ni) -> mmr_pairs_fn {
+    constexpr int NI = decltype(ni)::value;
+    return metric == WDBX_METRIC_L2 ? mmr_pairs_kernel<WDBX_METRIC_L2, MMR_BLOCK, NI> : mmr_pairs_kernel<WDBX_METRIC_COSINE, MMR_BLOCK, NI>;
+  });
 }
 
 struct MmrSelectArgs {

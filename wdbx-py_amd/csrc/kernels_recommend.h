@@ -1,6 +1,6 @@
 // kernels_recommend.h -- wdbx_index_search_recommend on the device: one pass over the WHOLE corpus per query, one wave per row,
 // every fetched row scored against all of the query's examples (positives and negatives) and the scores folded in registers
-// into one key.  subset_kernel's frame (kernels_subset.h) with another row source and a fold between the scores and the key.
+// into one key.  The frame of kernels_rowblock.h with the corpus as row source and a fold between the scores and the key.
 // Part of the single translation unit wdbx_hip.hip (included there, in order); not a standalone header.
 
 constexpr int RECOMMEND_EXAMPLE_BLOCK = 8;  // examples scored per pass over a loaded row (then 4, then one by one)
@@ -25,7 +25,7 @@ struct RecommendArgs {
 template <int METRIC, int EB, int NI>
 __device__ __forceinline__ void recommend_fold_block(const f4 (&c)[NI > 0 ? NI : 1], const f4* cp, const f4* examples, uint32_t e,
                                                      uint32_t pitch4, uint32_t j, float& best, bool& nan) {
-  constexpr int NR = NI > 0 ? NI : 1;
+  constexpr int NR = row_block_nr(NI);
   const f4* qp[EB];
   f4 q[EB][NR];
 #pragma unroll
@@ -84,8 +84,8 @@ __device__ __forceinline__ bool recommend_excluded(const uint32_t* list, uint32_
 template <int METRIC, int NI, int MODE>
 __global__ __launch_bounds__(256) void recommend_kernel(RecommendArgs a) {
   constexpr bool REG = MODE == 1;
-  constexpr int U = NI == 0 ? 1 : 2;
-  constexpr int NR = NI > 0 ? NI : 1;
+  constexpr int U = NI == 0 ? 1 : 2;  // (this kernel's own, not row_block_u: the figures of DESIGN.md 4.15 were measured with it)
+  constexpr int NR = row_block_nr(NI);
   extern __shared__ u64 lds_lists[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void recommend_kernel(RecommendArgs a) {
       const bool live = idx < a.n_rows;  // (wave-uniform, as everything about the row number)
       const uint32_t row = min(idx, a.n_rows - 1);
       bool ok = live;
-      if (ok && a.mask) ok = (a.mask[row >> 5] >> (row & 31)) & 1u;
+      if (ok && a.mask) ok = row_allowed(a.mask, row);
       if (ok && a.n_exclude) ok = !recommend_excluded(a.exclude, a.n_exclude, row);
       u64 mine = 0;
       if (ok) {
@@ -146,19 +146,15 @@ __global__ __launch_bounds__(256) void recommend_kernel(RecommendArgs a) {
 
 typedef void (*recommend_fn)(RecommendArgs);
 
-template <int METRIC, int MODE>
-static recommend_fn pick_recommend_ni(uint32_t pitch4) {  // (the row's loads per lane: as pick_subset_ni)
-  if (pitch4 <= 128) return recommend_kernel<METRIC, 2, MODE>;
-  if (pitch4 <= 256) return recommend_kernel<METRIC, 4, MODE>;
-  return recommend_kernel<METRIC, 0, MODE>;
-}
-
 template <int METRIC>
 static recommend_fn pick_recommend_metric(int mode, uint32_t pitch4) {
-  if (mode == 0) return pick_recommend_ni<METRIC, 0>(pitch4);
-  if (mode == 1) return pick_recommend_ni<METRIC, 1>(pitch4);
-  if (mode == 2) return pick_recommend_ni<METRIC, 2>(pitch4);
-  return nullptr;
+  return with_row_block_ni(pitch4, [&](auto ni) -> recommend_fn {
+    constexpr int NI = decltype(ni)::value;
+    if (mode == 0) return recommend_kernel<METRIC, NI, 0>;
+    if (mode == 1) return recommend_kernel<METRIC, NI, 1>;
+    if (mode == 2) return recommend_kernel<METRIC, NI, 2>;
+    return nullptr;
+  });
 }
 
 static recommend_fn pick_recommend(int metric, int mode, uint32_t pitch4) {

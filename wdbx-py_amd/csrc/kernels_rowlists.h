@@ -1,6 +1,6 @@
 // kernels_rowlists.h -- exact scores among LISTED rows with one row list PER QUERY (wdbx_index_search_row_lists): one
 // workgroup per work item of host_rowlists.h, a (chunk of one list, block of that list's queries) pair.  The scores are
-// subset_kernel's (exact_score_block, kernels_subset.h), so an answer equals wdbx_index_search_rows' bit for bit.
+// subset_kernel's (the frame of kernels_rowblock.h), so an answer equals wdbx_index_search_rows' bit for bit.
 // Part of the single translation unit wdbx_hip.hip (included there, behind kernels_subset.h); not a standalone header.
 
 struct RowListsArgs {
@@ -19,8 +19,7 @@ struct RowListsArgs {
 // query and write nothing.  No LDS, no list, no atomic: ranking is merge_kernel's, over the slot's keys as unsorted candidates.
 template <int METRIC, int QB, int NI>
 __global__ __launch_bounds__(256) void rowlists_kernel(RowListsArgs a) {
-  constexpr int U = NI == 0 ? 1 : (NI <= 2 ? 4 : 2);
-  constexpr int NR = NI > 0 ? NI : 1;
+  constexpr int U = row_block_u(NI), NR = row_block_nr(NI);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t j = (uint32_t)lane;
   const RowListsItem it = a.items[blockIdx.x];  // (uniform over the workgroup)
@@ -59,7 +58,7 @@ __global__ __launch_bounds__(256) void rowlists_kernel(RowListsArgs a) {
       exact_score_block<METRIC, QB, NI>(c[u], a.rows + (size_t)row[u] * a.pitch4, q, qp, a.pitch4, j, s);
 #pragma unroll
       for (int b = 0; b < QB; ++b) {
-        const u64 mine = s[b] == s[b] ? make_key(s[b] + 0.0f, row[u]) : 0ull;  // a NaN score is never a result
+        const u64 mine = row_key(s[b], row[u]);
         if (lane == 0 && live && (uint32_t)b < it.nq) out[(size_t)b * a.stride + idx] = mine;
       }
     }
@@ -68,17 +67,13 @@ __global__ __launch_bounds__(256) void rowlists_kernel(RowListsArgs a) {
 
 typedef void (*rowlists_fn)(RowListsArgs);
 
-template <int METRIC, int QB>
-static rowlists_fn pick_rowlists_ni(uint32_t pitch4) {  // (the row's loads per lane: as pick_subset_ni)
-  if (pitch4 <= 128) return rowlists_kernel<METRIC, QB, 2>;
-  if (pitch4 <= 256) return rowlists_kernel<METRIC, QB, 4>;
-  return rowlists_kernel<METRIC, QB, 0>;
-}
-
 // qb as rowlists_plan (host_rowlists.h) chooses it: 1 or 8; null for anything else
 static rowlists_fn pick_rowlists(int metric, int qb, uint32_t pitch4) {
-  const bool l2 = metric == WDBX_METRIC_L2;
-  if (qb == 1) return l2 ? pick_rowlists_ni<WDBX_METRIC_L2, 1>(pitch4) : pick_rowlists_ni<WDBX_METRIC_COSINE, 1>(pitch4);
-  if (qb == ROWLISTS_QB) return l2 ? pick_rowlists_ni<WDBX_METRIC_L2, ROWLISTS_QB>(pitch4) : pick_rowlists_ni<WDBX_METRIC_COSINE, ROWLISTS_QB>(pitch4);
-  return nullptr;
+  return with_row_block_ni(pitch4, [&](auto ni) -> rowlists_fn {
+    constexpr int NI = decltype(ni)::value;
+    const bool l2 = metric == WDBX_METRIC_L2;
+    if (qb == 1) return l2 ? rowlists_kernel<WDBX_METRIC_L2, 1, NI> : rowlists_kernel<WDBX_METRIC_COSINE, 1, NI>;
+    if (qb == ROWLISTS_QB) return l2 ? rowlists_kernel<WDBX_METRIC_L2, ROWLISTS_QB, NI> : rowlists_kernel<WDBX_METRIC_COSINE, ROWLISTS_QB, NI>;
+    return nullptr;
+  });
 }

@@ -1,5 +1,6 @@
 // kernels_subset.h -- exact top-k among LISTED rows (wdbx_index_search_rows): the kernel walks the device copy of the caller's
-// row list instead of the corpus, one wave per listed row, and scores every fetched row against a block of QB queries.
+// row list instead of the corpus, one wave per listed row, and scores every fetched row against a block of QB queries (the
+// frame of kernels_rowblock.h; its row source is the list, its sink a top-k list per query or a key per listed row).
 // Part of the single translation unit wdbx_hip.hip (included there, in order); not a standalone header.
 
 struct SubsetArgs {
@@ -14,35 +15,6 @@ struct SubsetArgs {
   int k;
 };
 
-// One loaded row against QB queries, each with exact_score's arithmetic (kernels_aux.h): lane j accumulates quads j, j + 64,
-// ... in that order with accum<METRIC> and exact_finish folds and reduces, so a score here is rescore_kernel's score bit for
-// bit -- the row's quads are simply used QB times once they are in registers.
-//   NI > 0 (pitch4 <= 64 NI): the queries' quads live in registers for the whole launch (q), the row's NI loads are issued by
-//   the caller (c), nothing is loaded here.  NI = 0: any pitch4, the loop, the queries read through the caches (qp).
-template <int METRIC, int QB, int NI>
-__device__ __forceinline__ void exact_score_block(const f4 (&c)[NI > 0 ? NI : 1], const f4* cp, const f4 (&q)[QB][NI > 0 ? NI : 1],
-                                                  const f4* const (&qp)[QB], uint32_t pitch4, uint32_t j, float (&s)[QB]) {
-  f4 acc[QB];
-#pragma unroll
-  for (int b = 0; b < QB; ++b) acc[b] = f4{0.f, 0.f, 0.f, 0.f};
-  if constexpr (NI == 0) {
-    for (uint32_t i = j; i < pitch4; i += 64) {
-      const f4 v = ld16<true>(cp + i);
-#pragma unroll
-      for (int b = 0; b < QB; ++b) acc[b] = accum<METRIC>(acc[b], v, qp[b][i]);
-    }
-  } else {
-#pragma unroll
-    for (int t = 0; t < NI; ++t)
-      if (j + (uint32_t)t * 64 < pitch4) {
-#pragma unroll
-        for (int b = 0; b < QB; ++b) acc[b] = accum<METRIC>(acc[b], c[t], q[b][t]);
-      }
-  }
-#pragma unroll
-  for (int b = 0; b < QB; ++b) s[b] = exact_finish<METRIC, 64>(acc[b]);
-}
-
 // MODE 0: a sorted list of k keys per wave and query in LDS (QB = 1), 1: in registers (k <= 128), 2: no list, every listed
 // row's key goes to out[query][i] (ranked by merge_kernel as unsorted candidates, or by the radix-select chain).
 // Grid: x = workgroups along the list (wave w of the grid takes listed rows w, w + W, ...; U rows' loads in flight per
@@ -53,8 +25,7 @@ __device__ __forceinline__ void exact_score_block(const f4 (&c)[NI > 0 ? NI : 1]
 template <int METRIC, int QB, int NI, int MODE>
 __global__ __launch_bounds__(256) void subset_kernel(SubsetArgs a) {
   constexpr bool REG = MODE == 1;
-  constexpr int U = NI == 0 ? 1 : (NI <= 2 ? 4 : 2);
-  constexpr int NR = NI > 0 ? NI : 1;
+  constexpr int U = row_block_u(NI), NR = row_block_nr(NI);
   extern __shared__ u64 lds_lists[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t j = (uint32_t)lane;
@@ -97,7 +68,7 @@ __global__ __launch_bounds__(256) void subset_kernel(SubsetArgs a) {
       exact_score_block<METRIC, QB, NI>(c[u], a.rows + (size_t)row[u] * a.pitch4, q, qp, a.pitch4, j, s);
 #pragma unroll
       for (int b = 0; b < QB; ++b) {
-        const u64 mine = (live && s[b] == s[b]) ? make_key(s[b] + 0.0f, row[u]) : 0ull;  // a NaN score is never a result
+        const u64 mine = live ? row_key(s[b], row[u]) : 0ull;
         if constexpr (MODE == 2) {
           if (lane == 0 && live && q0 + (uint32_t)b < a.nq) a.out[(size_t)(q0 + b) * a.key_stride + idx] = mine;
         } else {
@@ -126,24 +97,20 @@ __global__ __launch_bounds__(256) void subset_kernel(SubsetArgs a) {
 
 typedef void (*subset_fn)(SubsetArgs);
 
-template <int METRIC, int QB, int MODE>
-static subset_fn pick_subset_ni(uint32_t pitch4) {
-  if (pitch4 <= 128) return subset_kernel<METRIC, QB, 2, MODE>;
-  if (pitch4 <= 256) return subset_kernel<METRIC, QB, 4, MODE>;
-  return subset_kernel<METRIC, QB, 0, MODE>;
-}
-
 // mode / qb as subset_query_block (host_subset.h) pairs them: lists in LDS only with the block of one, register lists with
 // 1, 4 or 8, keys with 1 or 8; null for any other pair
 template <int METRIC>
 static subset_fn pick_subset_metric(int mode, int qb, uint32_t pitch4) {
-  if (mode == 0 && qb == 1) return pick_subset_ni<METRIC, 1, 0>(pitch4);
-  if (mode == 1 && qb == 1) return pick_subset_ni<METRIC, 1, 1>(pitch4);
-  if (mode == 1 && qb == 4) return pick_subset_ni<METRIC, 4, 1>(pitch4);
-  if (mode == 1 && qb == 8) return pick_subset_ni<METRIC, 8, 1>(pitch4);
-  if (mode == 2 && qb == 1) return pick_subset_ni<METRIC, 1, 2>(pitch4);
-  if (mode == 2 && qb == 8) return pick_subset_ni<METRIC, 8, 2>(pitch4);
-  return nullptr;
+  return with_row_block_ni(pitch4, [&](auto ni) -> subset_fn {
+    constexpr int NI = decltype(ni)::value;
+    if (mode == 0 && qb == 1) return subset_kernel<METRIC, 1, NI, 0>;
+    if (mode == 1 && qb == 1) return subset_kernel<METRIC, 1, NI, 1>;
+    if (mode == 1 && qb == 4) return subset_kernel<METRIC, 4, NI, 1>;
+    if (mode == 1 && qb == 8) return subset_kernel<METRIC, 8, NI, 1>;
+    if (mode == 2 && qb == 1) return subset_kernel<METRIC, 1, NI, 2>;
+    if (mode == 2 && qb == 8) return subset_kernel<METRIC, 8, NI, 2>;
+    return nullptr;
+  });
 }
 
 static subset_fn pick_subset(int metric, int mode, int qb, uint32_t pitch4) {

@@ -31,6 +31,8 @@
 //   kernels_range_batch.h   range_batch_bound_kernel: the selection thresholds and the widened bound of a block of range queries in
 //                           front of the int8 tiles' full pass (wdbx_index_range_search_batch)
 //   host_range_batch.h      that call's route, its blocks of up to 256 queries, buffer sizes and per-query fallback bookkeeping
+//   kernels_rowblock.h      the frame of the six kernels that score gathered fp32 rows against a block of queries in registers:
+//                           rows in flight, exact_score_block, the key rule, the mask bit
 //   kernels_subset.h        subset_kernel: exact scores of LISTED rows (wdbx_index_search_rows), a block of queries per fetched
 //                           row, per-workgroup top-k lists or a key per listed row
 //   kernels_rowlists.h      rowlists_kernel: the same scores for a call with one row list PER QUERY (wdbx_index_search_row_lists),
@@ -137,6 +139,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "kernels_aux.h"
 #include "kernels_range.h"
 #include "kernels_range_batch.h"
+#include "kernels_rowblock.h"
 #include "kernels_subset.h"
 #include "kernels_rowlists.h"
 #include "kernels_labels.h"
