@@ -436,6 +436,57 @@ int wdbx_index_search_recommend(wdbx_index* idx,
                                 const uint64_t* exclude_rows, uint64_t n_exclude,     /* strictly increasing; may be NULL / 0 */
                                 int64_t* out_idx, float* out_score, uint8_t* out_side /* [nq, k]; out_side may be NULL */);
 
+/* ---- discovery search: rank rows by context pairs and a target ---------------------------------------------------------
+ * Each of nq queries is a list of context PAIRS (positive, negative) and, when targets is not NULL, a target vector.  A pair
+ * splits the space into the side nearer its positive and the side nearer its negative.  Every eligible row is scored against
+ * all of a query's vectors in one pass over the corpus and ranked by the per-pair fold below.  Blocking, host buffers; the
+ * call holds the handle's mutex to its end and nothing of it stays valid in the handle.  Both metrics.
+ *   Vectors: targets is [nq, dim], or NULL = context search for every query.  context is [2 * pair_offsets[nq], dim]: pair i
+ *   is vectors 2i (positive) and 2i + 1 (negative).  pair_offsets is [nq + 1], [0] == 0, non-decreasing: query q's pairs are
+ *   [off[q], off[q + 1]).  normalize_vectors as normalize_queries elsewhere, for the targets and the context alike.
+ *   Scores and eligibility: r(row, v) is the score of row with vector v as the query, in the ranking domain (L2: the negated
+ *   squared distance), in exact_score's arithmetic: bit-identical to what wdbx_index_search_rows and
+ *   wdbx_index_range_search return for that row and that vector.  Eligible rows, the mask and exclude_rows are exactly those
+ *   of wdbx_index_search_recommend.  A row is never returned if any r for it is NaN, or if any r(p_i) - r(n_i) is NaN
+ *   (inf - inf).
+ *   Target mode (targets != NULL): 0 to WDBX_MAX_CONTEXT_PAIRS pairs per query.  wins = #{i : r(p_i) > r(n_i)}; a tie is not
+ *   a win.  t = r(target) + 0.0f.  Order: (wins descending, t descending, row ascending), cut at k.  out_score is t in the
+ *   caller's units (L2: the positive squared distance), out_wins the row's wins.  With zero pairs the ids and score bits
+ *   equal wdbx_index_search_recommend with one positive and no negative.
+ *   Context mode (targets == NULL): every query needs at least one pair.  loss = sum over i of fminf(r(p_i) - r(n_i), 0.0f),
+ *   accumulated in fp32 from 0.0f in pair order (no multiply: nothing to contract).  Order: (loss + 0.0f descending, row
+ *   ascending): rows on the right side of every pair all have loss 0 and come out in row order.  out_score is the loss as
+ *   computed: <= 0, in the ranking domain, no unit conversion for either metric.  out_wins slots are 0.
+ *   Outputs [nq, k]; out_wins may be NULL.  Unused slots hold -1 / 0 / 0.  An empty index: every slot -1, nothing launched.
+ *   Answers are bit-identical from run to run and do not depend on how the vectors are cut into blocks (the loss terms are
+ *   added in pair order whatever the cut, and a pair never straddles a block) nor on the rounds: every record, list slot and
+ *   key has one writer, and the only atomics add integers.
+ *   WDBX_E_INVALID: nq < 1, k outside [1, WDBX_MAX_K], a null buffer (context may be NULL only when the call has no pair at
+ *   all), pair_offsets[0] != 0 or decreasing offsets, more than WDBX_MAX_CONTEXT_PAIRS pairs in a query, a context-mode query
+ *   with no pair, and recommend's mask and exclusion errors (checked under the handle's lock).  A refused call leaves the
+ *   handle usable.
+ *   Stages: a query's vectors are staged as [target?, p0, n0, p1, n1, ...] and go through exact_score_block in blocks of 8,
+ *   4 and 2 (the target: a block of one), one wave per row.  Context mode ranks in the pass itself, as recommend does
+ *   (per-workgroup lists and the merge kernel, or from select_min_k on a key per row and the radix-select chain), with
+ *   make_key(loss + 0.0f, row).  Target mode needs two levels and the 64-bit key has no spare bit, so the pass -- ONE read of
+ *   the corpus per query, however many wins values the answer spans -- writes a record per row, make_key(t, row) (0 when the
+ *   row is ineligible or NaN) and the wins byte, and counts the rows per wins value ("zone").  The host downloads the counts,
+ *   picks per query the zones from the top down that cover k, and a second kernel ranks each (query, zone) slot from the 9
+ *   bytes per row of the records with the same list or select modes; the host splices the zones' lists.  Rounds keep the
+ *   records, keys or lists within 256 MiB.  The scoring launches count as scan launches in wdbx_index_profile_read, the zone
+ *   launches as merge launches.
+ *   get_option, read-only: "last_discover_path" 0 nothing launched, 1 context mode, 2 target mode;
+ *   "last_discover_zone_slots" the (query, zone) slots the second stage ranked. */
+#define WDBX_MAX_CONTEXT_PAIRS 32
+int wdbx_index_search_discover(wdbx_index* idx,
+                               const float* targets,           /* [nq, dim], or NULL = context search for every query */
+                               const float* context,           /* [2 * pair_offsets[nq], dim]: pair i is vectors 2i (positive), 2i + 1 (negative) */
+                               const uint64_t* pair_offsets,   /* [nq + 1], [0] == 0, non-decreasing: query q's pairs are [off[q], off[q + 1]) */
+                               int nq, int k, int normalize_vectors,
+                               const uint32_t* mask_words, uint64_t mask_word_count, /* NULL = every row */
+                               const uint64_t* exclude_rows, uint64_t n_exclude,     /* strictly increasing; may be NULL / 0 */
+                               int64_t* out_idx, float* out_score, uint8_t* out_wins /* [nq, k]; out_wins may be NULL */);
+
 /* ---- range search: every row within a similarity, no k ----------------------- */
 /* every row whose score reaches thresholds[q] (cosine/IP: score >= t; L2: squared distance <= t), exact fp32,
  * per query sorted like wdbx_index_search; replaces faiss' IndexFlat range_search, which the reference never reaches

@@ -223,6 +223,13 @@ struct wdbx_index {
   size_t rec_bytes = 0;
   int last_recommend_path = 0;  // 0 nothing launched, 1 favoured pass only, 2 both passes
   int64_t last_recommend_short = 0;
+  // discovery search (wdbx_index_search_discover): one allocation of a round's state (host_discover.h): target mode's records (keys |
+  // wins) | the zones' counts | the query table | the zone table | the exclusion list.  Vectors in d_q, keys in d_sub_keys, lists
+  // in d_partials.
+  char* d_disc = nullptr;
+  size_t disc_bytes = 0;
+  int last_discover_path = 0;  // 0 nothing launched, 1 context mode, 2 target mode
+  int64_t last_discover_zone_slots = 0;
   // search groups (wdbx_index_search_groups / _group_members): where each dense label's run lies in the label order, on the host
   // (host_groups.h; rebuilt with the label order), and one allocation of a call's tables: the slot table | the round's tasks |
   // the slots' counts.  Queries in d_q, partial lists in d_partials, members in d_oidx / d_oscore.
@@ -2242,5 +2249,171 @@ static int recommend_locked(wdbx_index* ix, const float* examples, const uint64_
     ix->last_recommend_short = ns;
   }
   recommend_splice(fav_idx.data(), fav_score.data(), dis_idx.data(), dis_score.data(), short_queries, nq, k, out_idx, out_score, out_side);
+  return WDBX_OK;
+}
+
+// ---- discovery search (kernels_discover.h, host_discover.h) -----------------------------------------------------------------
+// the ranking tail of `b` slots whose partial lists (d_partials, P per slot) or keys per row (d_sub_keys) a launch just wrote:
+// one merge launch, or per slot the radix-select chain; results to d_oidx / d_oscore from slot `first` on
+static int enqueue_discover_tail(wdbx_index* ix, bool lists, uint32_t P, int first, int b, int k, int metric) {
+  int rc;
+  MergeArgs m = {};
+  m.k = k;
+  m.metric = metric;
+  if (!lists) {
+    const uint32_t sgrid = radix_select_grid(ix->n, ix->cu_count);
+    for (int q = 0; q < b; ++q) {
+      if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
+      HIP_TRY(enqueue_radix_select(ix->stream, (const u64*)ix->d_sub_keys + (size_t)q * ix->n, (u64)ix->n, nullptr,
+                                   (SelectState*)ix->d_state, (u64*)ix->d_sel, (uint32_t)k, sgrid));
+      m.out_idx = ix->d_oidx + (size_t)(first + q) * k;
+      m.out_score = ix->d_oscore + (size_t)(first + q) * k;
+      HIP_TRY(enqueue_sort_out(ix->stream, (const u64*)ix->d_sel, (const SelectState*)ix->d_state, m));
+      if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
+    }
+    return WDBX_OK;
+  }
+  m.in = ix->d_partials;
+  m.q_stride = (uint64_t)k * P;
+  m.i_stride = P;
+  m.p_stride = 1;
+  m.P = P;
+  m.list_len = k;
+  m.out_idx = ix->d_oidx + (size_t)first * k;
+  m.out_score = ix->d_oscore + (size_t)first * k;
+  return launch_merge(ix, m, b);
+}
+
+static int grow_discover_scratch(wdbx_index* ix, bool lists, size_t scratch_u64) {
+  int rc;
+  if (lists) return grow((void**)&ix->d_partials, &ix->partials_bytes, scratch_u64 * sizeof(u64));
+  if ((rc = grow((void**)&ix->d_sub_keys, &ix->sub_keys_bytes, scratch_u64 * sizeof(u64)))) return rc;
+  if ((rc = grow((void**)&ix->d_sel, &ix->sel_bytes, (size_t)WDBX_MAX_K * sizeof(u64)))) return rc;
+  return grow((void**)&ix->d_state, &ix->state_bytes, sizeof(SelectState));
+}
+
+// The call under the handle's lock (the caller holds it, has checked the arguments that need no lock, and resets the mask).
+// Context mode (no targets): per round the scoring pass ranks by the loss and the tail follows; the loss is a ranking-domain
+// value for either metric, so the tail never applies the L2 sign.  Target mode, per round of queries:
+//   1. the scoring pass writes every row's record and the zones' counts;  2. one small download of the counts;
+//   3. the zones each query needs (discover_zones), one zone launch per round of (query, zone) slots and its tail;
+//   4. the splice (host_discover.h).
+static int discover_locked(wdbx_index* ix, const float* targets, const float* context, const uint64_t* off, int nq, int k,
+                           int normalize_vectors, const uint32_t* mask_words, const std::vector<uint32_t>& exclude32, MaskScope& scope,
+                           int64_t* out_idx, float* out_score, uint8_t* out_wins) {
+  const bool target = targets != nullptr;
+  const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
+  const DiscoverPlan dp = discover_plan(ix->n, nq, k, target, ix->cu_count, ix->opt_select_min_k, ix->opt_lds_lists != 0);
+  const bool lists = dp.mode != 2;
+  const discover_fn fn = pick_discover(ix->metric, target ? 3 : dp.mode, pitch4);
+  if (!fn) return fail(WDBX_E_STATE, "no discover instance for mode %d", dp.mode);
+  int rc;
+  // the round's state: records (keys | wins) | counts | query table | zone table | exclusion list
+  const size_t n_ex = exclude32.size();
+  const size_t key_bytes = dp.record_rows * sizeof(u64);
+  const size_t counts_at = (key_bytes + dp.record_rows + 7) / 8 * 8;
+  const size_t counts_words = target ? (size_t)dp.round * DISCOVER_ZONES : 0;
+  const size_t qtab_at = counts_at + counts_words * sizeof(uint32_t);
+  const size_t ztab_at = qtab_at + (size_t)nq * 2 * sizeof(uint32_t);
+  const size_t ztab_words = counts_words * 2;
+  const size_t ex_at = ztab_at + ztab_words * sizeof(uint32_t);
+  if ((rc = grow((void**)&ix->d_disc, &ix->disc_bytes, ex_at + std::max<size_t>(n_ex, 1) * sizeof(uint32_t)))) return rc;
+  u64* d_rec_key = (u64*)ix->d_disc;
+  uint8_t* d_rec_wins = (uint8_t*)(ix->d_disc + key_bytes);
+  uint32_t* d_counts = (uint32_t*)(ix->d_disc + counts_at);
+  uint32_t* d_qtab = (uint32_t*)(ix->d_disc + qtab_at);
+  uint32_t* d_ztab = (uint32_t*)(ix->d_disc + ztab_at);
+  uint32_t* d_exclude = (uint32_t*)(ix->d_disc + ex_at);
+  if (!target && (rc = grow_discover_scratch(ix, lists, dp.scratch_u64))) return rc;
+  if ((rc = ensure_out(ix, (size_t)nq * k))) return rc;
+  // the staged vectors: context mode's are the caller's array as it is
+  const uint64_t staged = discover_staged_count(off, nq, target);
+  std::vector<float> stage;
+  if (target) {
+    stage.resize((size_t)staged * ix->dim);
+    discover_stage(targets, context, off, nq, ix->dim, stage.data());
+  }
+  if ((rc = upload_queries(ix, target ? stage.data() : context, staged, normalize_vectors))) return rc;
+  if (mask_words && (rc = scope.set(mask_words))) return rc;
+  std::vector<uint32_t> qtab((size_t)nq * 2);
+  discover_table(off, 0, nq, target, qtab.data());
+  HIP_TRY(hipMemcpyAsync(d_qtab, qtab.data(), qtab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+  if (n_ex) HIP_TRY(hipMemcpyAsync(d_exclude, exclude32.data(), n_ex * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+  const size_t lds = (!target && lists) ? dp.lds : 0;
+  if (lds >= 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  ix->last_discover_path = target ? 2 : 1;
+  for (const std::pair<int, int>& r : recommend_rounds(nq, dp.round)) {
+    const int q0 = r.first, b = r.second;
+    DiscoverArgs a = {};
+    a.rows = (const f4*)ix->d_rows;
+    a.vectors = (const f4*)ix->d_q;
+    a.table = d_qtab + (size_t)q0 * 2;
+    a.mask = ix->active_mask;
+    a.exclude = d_exclude;
+    a.out = target ? d_rec_key : (lists ? ix->d_partials : ix->d_sub_keys);
+    a.wins = d_rec_wins;
+    a.counts = d_counts;
+    a.key_stride = ix->n;
+    a.n_exclude = (uint32_t)n_ex;
+    a.n_rows = (uint32_t)ix->n;
+    a.pitch4 = pitch4;
+    a.k = k;
+    if (target) HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)b * DISCOVER_ZONES * sizeof(uint32_t), ix->stream));
+    if ((rc = record(ix->scan_ev, ix->profile, ix->stream, true))) return rc;
+    hipLaunchKernelGGL(fn, dim3(dp.blocks, (uint32_t)b), dim3(256), lds, ix->stream, a);
+    HIP_TRY(hipGetLastError());
+    if ((rc = record(ix->scan_ev, ix->profile, ix->stream, false))) return rc;
+    if (!target) {
+      if ((rc = enqueue_discover_tail(ix, lists, dp.P, q0, b, k, WDBX_METRIC_COSINE))) return rc;
+      continue;
+    }
+    std::vector<uint32_t> counts((size_t)b * DISCOVER_ZONES);
+    HIP_TRY(hipMemcpyAsync(counts.data(), d_counts, counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    std::vector<std::vector<DiscoverZone>> zones((size_t)b);
+    std::vector<uint32_t> ztab;
+    for (int q = 0; q < b; ++q) {
+      zones[(size_t)q] = discover_zones(&counts[(size_t)q * DISCOVER_ZONES], k);
+      for (const DiscoverZone& z : zones[(size_t)q]) {
+        ztab.push_back((uint32_t)q);
+        ztab.push_back(z.zone);
+      }
+    }
+    const int zslots = (int)(ztab.size() / 2);
+    std::vector<int64_t> z_idx((size_t)zslots * k);
+    std::vector<float> z_score((size_t)zslots * k);
+    if (zslots) {
+      const DiscoverZonePlan zp = discover_zone_plan(ix->n, zslots, k, dp.mode, ix->cu_count);
+      const discover_zone_fn zfn = pick_discover_zone(dp.mode);
+      if (!zfn) return fail(WDBX_E_STATE, "no discover zone instance for mode %d", dp.mode);
+      if ((rc = grow_discover_scratch(ix, lists, zp.scratch_u64))) return rc;
+      if ((rc = ensure_out(ix, (size_t)zslots * k))) return rc;
+      if (zp.lds >= 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)zfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)zp.lds));
+      HIP_TRY(hipMemcpyAsync(d_ztab, ztab.data(), ztab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+      for (const std::pair<int, int>& zr : recommend_rounds(zslots, zp.round)) {
+        DiscoverZoneArgs za = {};
+        za.rec_key = d_rec_key;
+        za.rec_wins = d_rec_wins;
+        za.table = d_ztab + (size_t)zr.first * 2;
+        za.out = lists ? ix->d_partials : ix->d_sub_keys;
+        za.rec_stride = ix->n;
+        za.n_rows = (uint32_t)ix->n;
+        za.k = k;
+        if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
+        hipLaunchKernelGGL(zfn, dim3(zp.blocks, (uint32_t)zr.second), dim3(256), zp.lds, ix->stream, za);
+        HIP_TRY(hipGetLastError());
+        if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
+        if ((rc = enqueue_discover_tail(ix, lists, zp.P, zr.first, zr.second, k, ix->metric))) return rc;
+      }
+      if ((rc = download_results(ix, (size_t)zslots * k, z_idx.data(), z_score.data()))) return rc;
+      ix->last_discover_zone_slots += zslots;
+    }
+    discover_splice(zones, z_idx.data(), z_score.data(), k, out_idx + (size_t)q0 * k, out_score + (size_t)q0 * k,
+                    out_wins ? out_wins + (size_t)q0 * k : nullptr);
+  }
+  if (!target) {
+    if ((rc = download_results(ix, (size_t)nq * k, out_idx, out_score))) return rc;
+    if (out_wins) memset(out_wins, 0, (size_t)nq * k);
+  }
   return WDBX_OK;
 }

@@ -50,6 +50,10 @@
 //   kernels_recommend.h     recommend_kernel: the pass of wdbx_index_search_recommend over the whole corpus -- every row scored against
 //                           a query's positive and negative examples, the scores folded into one key per side
 //   host_recommend.h        that call's offset and exclusion checks, plan, short queries and the splice of the two sides
+//   kernels_discover.h      discover_kernel, discover_zone_kernel: wdbx_index_search_discover -- every row scored against a query's
+//                           context pairs (and target), folded per pair into a loss key or a (target key, wins) record; the zones'
+//                           ranking from the records
+//   host_discover.h         that call's offset checks, plans of the pass and of the zone stage, staged vectors, zones and splice
 //   kernels_groups.h        group_members_kernel, group_merge_kernel: stage 2 of wdbx_index_search_groups -- the best group_size rows of
 //                           each chosen label, scored along the label's run of the label order, and the merge of a run's segments
 //   host_groups.h           the runs of the label order, the dense label of a label value, that call's tasks, slot table and rounds
@@ -107,6 +111,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_rowlists.h"  // (device-free as well: slots, rounds, query blocks and work items of a call with a row list per query)
 #include "host_mmr.h"  // (device-free as well: argument checks, pools, rounds and grids of an MMR search)
 #include "host_recommend.h"  // (device-free as well: offsets, exclusion list, plan, short queries and splice of a recommend search)
+#include "host_discover.h"  // (device-free as well: pair offsets, plans, staged vectors, zones and splice of a discovery search)
 #include "host_groups.h"  // (device-free as well: label runs, dense label lookup, tasks, slot table and rounds of a groups search)
 
 #define HIP_TRY(expr)                                                                        \
@@ -150,6 +155,8 @@ static_assert(MULTIVECTOR_MAX_VECTORS == WDBX_MAX_QUERY_VECTORS, "the plan's lim
 static_assert(MMR_MAX_POOL == WDBX_MAX_K, "a pool is a top-k answer");
 #include "kernels_recommend.h"
 static_assert(RECOMMEND_MAX_EXAMPLES == WDBX_MAX_EXAMPLES && RECOMMEND_MAX_EXCLUDE == WDBX_MAX_EXCLUDE_ROWS, "the plan's limits are the header's");
+#include "kernels_discover.h"
+static_assert(DISCOVER_MAX_PAIRS == WDBX_MAX_CONTEXT_PAIRS && DISCOVER_ZONES == DISCOVER_ZONE_COUNT, "the plan's limits are the header's and the kernel's");
 #include "kernels_groups.h"
 static_assert(GROUPS_MAX_SIZE_DEV == GROUPS_MAX_SIZE && GROUPS_MAX_SIZE == WDBX_MAX_GROUP_SIZE, "a wave's register list holds a group");
 static_assert(sizeof(GroupTaskDev) == sizeof(GroupTask) && sizeof(GroupTask) == 16, "the device reads the host's tasks");
@@ -171,7 +178,7 @@ static uint64_t device_bytes_resident(const wdbx_index* ix) {
   b += ix->qb8_bytes + ix->qpar_bytes + ix->pairs_bytes + ix->pair_count_bytes + ix->cnmax_bytes;
   b += ix->rcand_bytes + ix->rkeys_bytes + ix->rcnt_bytes + ix->rthr_bytes;
   b += ix->rows6_bytes + ix->count6_bytes + ix->rows42_bytes + ix->count42_bytes + ix->q16_bytes;
-  b += ix->sub_ids_bytes + ix->sub_keys_bytes + ix->mm_bytes + ix->rl_bytes + ix->lab_bytes + ix->mv_bytes + ix->mmr_bytes + ix->rec_bytes + ix->grp_bytes;
+  b += ix->sub_ids_bytes + ix->sub_keys_bytes + ix->mm_bytes + ix->rl_bytes + ix->lab_bytes + ix->mv_bytes + ix->mmr_bytes + ix->rec_bytes + ix->grp_bytes + ix->disc_bytes;
   return b;
 }
 
@@ -249,7 +256,7 @@ void wdbx_index_destroy(wdbx_index* ix) try {
                     ix->d_state, ix->d_cn, ix->d_cnmax, ix->d_qb16, ix->d_rows16, ix->d_rows8, ix->d_scale8, ix->d_selsrc,
                     ix->d_gmax, ix->d_qn, ix->d_rows8g, ix->d_groups8, ix->d_gbad8, ix->d_gref8, ix->d_over_list, ix->d_qb8,
                     ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr, ix->d_rows6, ix->d_count6, ix->d_rows42, ix->d_count42, ix->d_q16,
-                    ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys, ix->d_mm, ix->d_rl, ix->d_lab, ix->d_mv, ix->d_mmr, ix->d_rec, ix->d_grp};
+                    ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys, ix->d_mm, ix->d_rl, ix->d_lab, ix->d_mv, ix->d_mmr, ix->d_rec, ix->d_grp, ix->d_disc};
     for (void* p : bufs)
       if (p) (void)hipFree(p);
     if (ix->h_stage) (void)hipHostFree(ix->h_stage);
@@ -1679,6 +1686,46 @@ int wdbx_index_search_recommend(wdbx_index* ix, const float* examples, const uin
                           out_side);
 } WDBX_CATCH
 
+// ---- discovery search: rows ranked by context pairs and a target (host_discover.h, kernels_discover.h, DESIGN.md section
+// 4.17) ------------------------------------------------------------------------------------------------------------------
+// The whole call holds the handle's mutex.  The offsets need no lock; the mask's length and the exclusion list are checked
+// against the row count under it.  Then discover_locked (host_index.h).
+int wdbx_index_search_discover(wdbx_index* ix, const float* targets, const float* context, const uint64_t* pair_offsets, int nq, int k,
+                               int normalize_vectors, const uint32_t* mask_words, uint64_t mask_word_count,
+                               const uint64_t* exclude_rows, uint64_t n_exclude, int64_t* out_idx, float* out_score,
+                               uint8_t* out_wins) try {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  if (nq < 1) return fail(WDBX_E_INVALID, "nq=%d", nq);
+  if (k < 1 || k > WDBX_MAX_K) return fail(WDBX_E_INVALID, "k=%d outside [1, %d]", k, WDBX_MAX_K);
+  if (!pair_offsets || !out_idx || !out_score) return fail(WDBX_E_INVALID, "null buffer");
+  if (n_exclude && !exclude_rows) return fail(WDBX_E_INVALID, "exclude_rows is null");
+  std::string msg;
+  if (!discover_validate_offsets(pair_offsets, nq, targets != nullptr, &msg)) return fail(WDBX_E_INVALID, "%s", msg.c_str());
+  if (pair_offsets[nq] && !context) return fail(WDBX_E_INVALID, "null buffer: context");
+  std::unique_lock<std::mutex> lk(ix->mu);
+  if (ix->n >= 0xFFFFFF00ull) return fail(WDBX_E_INVALID, "shard holds too many rows for 32-bit row keys");
+  if (mask_words) {
+    const int rc = check_mask_words(ix->n, mask_word_count);
+    if (rc) return rc;
+  }
+  std::vector<uint32_t> exclude32((size_t)std::min<uint64_t>(n_exclude, RECOMMEND_MAX_EXCLUDE));
+  if (!recommend_validate_exclude(exclude_rows, n_exclude, ix->n, exclude32.data(), &msg)) return fail(WDBX_E_INVALID, "%s", msg.c_str());
+  ix->last_discover_path = 0;
+  ix->last_discover_zone_slots = 0;
+  if (ix->n == 0) {  // every slot empty, nothing launched
+    for (size_t i = 0; i < (size_t)nq * k; ++i) {
+      out_idx[i] = -1;
+      out_score[i] = 0.0f;
+      if (out_wins) out_wins[i] = 0;
+    }
+    return WDBX_OK;
+  }
+  DeviceGuard g(ix->device);
+  MaskScope scope(ix);
+  return discover_locked(ix, targets, context, pair_offsets, nq, k, normalize_vectors, mask_words, exclude32, scope, out_idx, out_score,
+                         out_wins);
+} WDBX_CATCH
+
 // ---- range search (range_u8_eligible: host_index.h; pick_range_scan: kernels_range.h) --------------
 // The whole call holds the handle's mutex (like a masked search: the key buffers are the handle's).  Per round of up to 64
 // queries: [u8 path: memset counters, scan8_kernel<PHASE 2> -> candidates] -> memset, range_filter_kernel / range_scan_kernel
@@ -2879,6 +2926,8 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "last_mmr_path")) return *value = ix->last_mmr_path, WDBX_OK;
   if (name && !strcmp(name, "last_recommend_path")) return *value = ix->last_recommend_path, WDBX_OK;
   if (name && !strcmp(name, "last_recommend_short")) return *value = ix->last_recommend_short, WDBX_OK;
+  if (name && !strcmp(name, "last_discover_path")) return *value = ix->last_discover_path, WDBX_OK;
+  if (name && !strcmp(name, "last_discover_zone_slots")) return *value = ix->last_discover_zone_slots, WDBX_OK;
   if (name && !strcmp(name, "last_groups_path")) return *value = ix->last_groups_path, WDBX_OK;
   if (name && !strcmp(name, "last_groups_tasks")) return *value = ix->last_groups_tasks, WDBX_OK;
   if (name && !strcmp(name, "last_groups_rounds")) return *value = ix->last_groups_rounds, WDBX_OK;

@@ -19,6 +19,7 @@ METRIC_L2 = 1
 MAX_K = 2048
 MAX_EXAMPLES = 64        # WDBX_MAX_EXAMPLES: positives + negatives of one recommend query
 MAX_EXCLUDE_ROWS = 1024  # WDBX_MAX_EXCLUDE_ROWS
+MAX_CONTEXT_PAIRS = 32   # WDBX_MAX_CONTEXT_PAIRS: (positive, negative) pairs of one discovery query
 MAX_GROUP_SIZE = 64      # WDBX_MAX_GROUP_SIZE: members one group of wdbx_index_search_groups holds
 UNIQUE_ID_BYTES = 128
 
@@ -86,6 +87,8 @@ SIGNATURES = {
                                         C.POINTER(C.c_uint32), C.c_uint64, _i64p, _f32p, _f32p]),
     "wdbx_index_search_recommend": (C.c_int, [C.c_void_p, _f32p, _u64p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32),
                                               C.c_uint64, _u64p, C.c_uint64, _i64p, _f32p, C.POINTER(C.c_uint8)]),
+    "wdbx_index_search_discover": (C.c_int, [C.c_void_p, _f32p, _f32p, _u64p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32),
+                                             C.c_uint64, _u64p, C.c_uint64, _i64p, _f32p, C.POINTER(C.c_uint8)]),
     "wdbx_index_range_search": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
                                           C.c_uint64, _u64p, _i64p, _f32p]),
     "wdbx_index_range_search_batch": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
@@ -556,6 +559,44 @@ class NativeIndex:
                                                      0 if ex is None else ex.size, idx.ctypes.data_as(_i64p),
                                                      score.ctypes.data_as(_f32p), side.ctypes.data_as(C.POINTER(C.c_uint8))))
         return idx, score, side
+
+    def search_discover(self, targets, context, pair_offsets, k: int, normalize_vectors: bool = False,
+                        mask_words: Optional[np.ndarray] = None,
+                        exclude_rows=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Rows ranked by context pairs and a target: query ``q``'s pairs are ``pair_offsets[q] .. pair_offsets[q + 1] - 1``,
+        pair ``i`` the vectors ``2 i`` (positive) and ``2 i + 1`` (negative) of ``context``.  With ``targets`` ([nq, dim]) rows
+        rank by (pairs won descending, target score descending, row); with ``targets=None`` (context search) by the loss, the
+        sum over the pairs of ``min(r(positive) - r(negative), 0)``, descending.  Returns ``(rows int64, scores f32, wins
+        uint8)``, each ``[nq, k]``: the score is the target's (as :meth:`search` returns scores) or the loss (<= 0, the
+        ranking domain for either metric); unused slots hold -1 / 0 / 0.  ``mask_words`` and ``exclude_rows`` as in
+        :meth:`search_recommend`."""
+        off = np.ascontiguousarray(pair_offsets, dtype=np.uint64).reshape(-1)
+        if off.size < 2:
+            raise ValueError(f"pair_offsets holds {off.size} entries: queries + 1 needed")
+        nq = off.size - 1
+        t = None if targets is None else _as_f32(targets, self.dim)
+        if t is not None and t.shape[0] != nq:
+            raise ValueError(f"{t.shape[0]} targets for {nq} queries")
+        c = None
+        if context is not None and np.size(context):
+            c = _as_f32(context, self.dim)
+        if 2 * int(off[-1]) != (0 if c is None else c.shape[0]):
+            raise ValueError(f"pair_offsets end at {int(off[-1])} pairs, {0 if c is None else c.shape[0]} context vectors given")
+        idx = np.empty((nq, int(k)), np.int64)
+        score = np.empty((nq, int(k)), np.float32)
+        wins = np.empty((nq, int(k)), np.uint8)
+        m = None if mask_words is None else np.ascontiguousarray(mask_words, dtype=np.uint32)
+        ex = None if exclude_rows is None else np.ascontiguousarray(exclude_rows, dtype=np.uint64).reshape(-1)
+        # (nq, k, the offsets, the mask's length and the exclusion list are checked by the library, the last two under the lock)
+        _check(self._lib.wdbx_index_search_discover(self._h, None if t is None else t.ctypes.data_as(_f32p),
+                                                    None if c is None else c.ctypes.data_as(_f32p), off.ctypes.data_as(_u64p),
+                                                    nq, int(k), int(normalize_vectors),
+                                                    None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                    0 if m is None else m.size,
+                                                    None if ex is None or not ex.size else ex.ctypes.data_as(_u64p),
+                                                    0 if ex is None else ex.size, idx.ctypes.data_as(_i64p),
+                                                    score.ctypes.data_as(_f32p), wins.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return idx, score, wins
 
     def range_search(self, queries, thresholds, normalize_queries: bool = False,
                      mask_words: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:

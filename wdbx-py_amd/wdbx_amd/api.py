@@ -188,6 +188,44 @@ async def recommend_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
     return {"results": [{"vector_id": vid, "similarity": sim, "metadata": meta, "side": side} for vid, sim, meta, side in found]}
 
 
+async def discover_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
+    """Discovery form (extension): body ``{"target": ..., "context": [{"positive": ..., "negative": ...}, ...], "limit": 10,
+    "filter_metadata": null}`` -> the ``search_endpoint`` response shape with a ``"wins"`` member per result, the context
+    pairs the vector is on the right side of (``wdbx.vector_discover_async``).  ``target`` (absent or null = context search,
+    then ``similarity`` is the loss, <= 0, and ``wins`` 0) and the members of every pair are stored vector ids (strings) or
+    vectors (lists of numbers); a pair may also be a two-item list [positive, negative]."""
+    if not isinstance(payload, dict):
+        raise ValueError("request body must be an object")
+    limit = payload.get("limit", 10)
+    limit = 10 if limit is None else limit
+    if isinstance(limit, bool) or not isinstance(limit, int):
+        raise ValueError("limit must be an integer")
+    flt = payload.get("filter_metadata")
+    if flt is not None and not isinstance(flt, dict):
+        raise ValueError("filter_metadata must be an object")
+
+    def example(e, name: str):
+        return e if isinstance(e, str) else _vector(e, name)
+
+    target = payload.get("target")
+    target = None if target is None else example(target, "target")
+    items = payload.get("context")
+    items = [] if items is None else items
+    if not isinstance(items, (list, tuple)):
+        raise ValueError("context must be a list of pairs")
+    context = []
+    for i, pair in enumerate(items):
+        if isinstance(pair, dict) and "positive" in pair and "negative" in pair:
+            pair = (pair["positive"], pair["negative"])
+        if not isinstance(pair, (list, tuple)) or len(pair) != 2:
+            raise ValueError(f"context[{i}] must be an object with positive and negative, or a list of the two")
+        context.append((example(pair[0], f"context[{i}].positive"), example(pair[1], f"context[{i}].negative")))
+    if target is None and not context:
+        raise ValueError("target or a non-empty context is required")
+    found = await wdbx.vector_discover_async(target, context, limit=limit, filter_metadata=flt, with_wins=True)
+    return {"results": [{"vector_id": vid, "similarity": sim, "metadata": meta, "wins": wins} for vid, sim, meta, wins in found]}
+
+
 async def range_search_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
     """Range form (extension): body ``{"query_vector": [...], "threshold": 0.8, "filter_metadata": null,
     "max_results": null}`` -> the ``search_endpoint`` response shape with EVERY vector whose similarity reaches

@@ -985,6 +985,37 @@ class HipFlatIndex(VectorIndex):
                 return []
             raise
 
+    def discover(self, target, pairs, limit: int = 10, mask=None, exclude_ids=()) -> List[Tuple[str, float, int]]:
+        """Rows of this shard ranked by context ``pairs`` [(positive, negative)] and a ``target`` vector
+        (``wdbx_index_search_discover``): by (pairs won descending, target score descending), or with ``target=None``
+        (context search) by the loss, the sum over the pairs of ``min(r(positive) - r(negative), 0)``, descending.
+        ``[(id, score, wins)]``: the score is the target's in the units ``search`` returns, or the loss (<= 0, never
+        converted; wins 0).  ``mask`` and ``exclude_ids`` as in ``recommend``.  Errors are swallowed or raised as in
+        ``search``."""
+        try:
+            actual_limit = min(int(limit), _native.MAX_K)
+            if self.next_index == 0 or actual_limit <= 0:
+                return []
+            ctx = [self._prepare(v) for pair in pairs for v in pair]
+            if target is None and not ctx:
+                raise ValueError("context search needs at least one pair")
+            tgt = None if target is None else self._prepare(target)[None, :]
+            words = None
+            if mask is not None:
+                words = mask if mask.dtype == np.uint32 else _native.pack_row_mask(mask)
+            rows = sorted({r for r in (self._row_of(i) for i in exclude_ids) if r is not None})
+            idx, score, wins = self._native.search_discover(tgt, np.stack(ctx) if ctx else None, [0, len(ctx) // 2], actual_limit,
+                                                            mask_words=words, exclude_rows=rows or None)
+            keep = idx[0] != -1
+            if target is None:  # (the loss stays in the ranking domain: no unit conversion for either metric)
+                return [(vid, float(s), 0) for (vid, _), s in zip(self._map(idx[0], score[0]), score[0][keep])]
+            return [(vid, s, int(w)) for (vid, s), w in zip(self._map(idx[0], score[0]), wins[0][keep])]
+        except Exception as e:
+            logger.error("Error in HIP discovery search: %s", e)
+            if self.swallow_errors:
+                return []
+            raise
+
     async def search_async(self, query_vector: np.ndarray, limit: int = 10) -> List[Tuple[str, float]]:
         loop = asyncio.get_event_loop()
         return await loop.run_in_executor(self.thread_pool, self.search, query_vector, limit)

@@ -1336,6 +1336,58 @@ class VectorStore:
         return await loop.run_in_executor(self.thread_pool, lambda: self.recommend(
             positive, negative, limit=limit, strategy=strategy, filter_metadata=filter_metadata, with_side=with_side))
 
+    # ---- discovery search (extension: rank by context pairs and a target) ----
+    def discover(self, target=None, context=(), limit: int = 10, filter_metadata: Optional[Dict[str, Any]] = None,
+                 with_wins: bool = False) -> List[tuple]:
+        """Discovery: ``context`` is a list of (positive, negative) pairs and ``target`` an optional vector; the target and
+        every pair element are each a stored vector id or a raw vector, and every one that is an id never comes back.  A
+        pair is won by a vector that scores higher against its positive than against its negative.  With a target, vectors
+        rank by (pairs won descending, target score descending); without one (context search, at least one pair) by the
+        loss, the sum over the pairs of ``min(score(positive) - score(negative), 0)``, descending: vectors on the right side
+        of every pair have loss 0.  The fold is per vector, so any number of shards serves: every shard gets the same
+        vectors and returns its own top-``limit`` (``wdbx_index_search_discover``, the id examples excluded on the shard that
+        holds them); the merge takes (wins descending, score descending, shard, position) with a target and (loss
+        descending, shard, position) without.  ``filter_metadata`` always travels as the row masks.  Returns ``(vector_id,
+        score, metadata)`` -- the score is the target's, or the loss -- with the pairs won appended when ``with_wins`` is
+        set (0 in a context search)."""
+        pairs, ids = [], []
+        for i, pair in enumerate(context or ()):
+            if isinstance(pair, dict):
+                pair = (pair.get("positive"), pair.get("negative"))
+            if isinstance(pair, (str, bytes)) or len(pair) != 2:
+                raise ValueError(f"context[{i}]: a pair (positive, negative) is needed")
+            vs, got = self._resolve_examples(list(pair), f"context[{i}]")
+            pairs.append((vs[0], vs[1]))
+            ids += got
+        tgt = None
+        if target is not None:
+            vs, got = self._resolve_examples([target], "target")
+            tgt = vs[0]
+            ids += got
+        if tgt is None and not pairs:
+            raise ValueError("discover needs a target or at least one context pair")
+        if len(pairs) > _native.MAX_CONTEXT_PAIRS:
+            raise ValueError(f"{len(pairs)} context pairs, at most {_native.MAX_CONTEXT_PAIRS} are served")
+        if limit <= 0:
+            return []
+        masks = self._row_masks(filter_metadata) if filter_metadata else [None] * len(self.indices)
+        by_shard = [[] for _ in self.indices]
+        for vid in set(ids):
+            by_shard[self._get_shard_for_id(vid)].append(vid)
+        work = list(zip(self.indices, masks, by_shard))
+        one = lambda a: a[0].discover(tgt, pairs, limit, mask=a[1], exclude_ids=a[2])  # noqa: E731
+        per_shard = list(self._shard_pool.map(one, work)) if len(work) > 1 else [one(work[0])]
+        # (a shard's list is already in the order below with the row last: the position stands for the row among equals)
+        ranked = sorted(((-wins, -score, shard, at), vid, score, wins)
+                        for shard, res in enumerate(per_shard) for at, (vid, score, wins) in enumerate(res))
+        return [(vid, score, self.metadata.get(vid, {})) + ((wins,) if with_wins else ()) for _, vid, score, wins in ranked[:limit]]
+
+    async def discover_async(self, target=None, context=(), limit: int = 10, filter_metadata: Optional[Dict[str, Any]] = None,
+                             with_wins: bool = False) -> List[tuple]:
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(self.thread_pool, lambda: self.discover(
+            target, context, limit=limit, filter_metadata=filter_metadata, with_wins=with_wins))
+
     # ---- range search (extension: every vector within a similarity, no limit) ----
     def search_range(self, query_vector: List[float], threshold: float,
                      filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,

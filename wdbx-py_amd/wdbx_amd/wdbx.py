@@ -240,6 +240,21 @@ class WDBX:
         return await self.vector_store.recommend_async(positive, negative, limit=limit, strategy=strategy,
                                                        filter_metadata=filter_metadata, with_side=with_side)
 
+    def vector_discover(self, target=None, context=(), limit: int = 10, filter_metadata: Optional[Dict[str, Any]] = None,
+                        with_wins: bool = False) -> List[tuple]:
+        """Extension: discovery.  ``context``: (positive, negative) pairs, ``target``: an optional vector; each a stored
+        vector id or a raw vector, and ids never come back.  With a target: vectors on the right side of the most pairs
+        first, by the target's score within equal wins.  Without: context search, vectors by how far they sit on the wrong
+        side of any pair (0 = on the right side of all).  A filter is pushed down; any number of shards.  ``(vector_id,
+        score, metadata)``, with the pairs won appended when ``with_wins`` is set (``VectorStore.discover`` states the
+        order)."""
+        return self.vector_store.discover(target, context, limit=limit, filter_metadata=filter_metadata, with_wins=with_wins)
+
+    async def vector_discover_async(self, target=None, context=(), limit: int = 10,
+                                    filter_metadata: Optional[Dict[str, Any]] = None, with_wins: bool = False) -> List[tuple]:
+        return await self.vector_store.discover_async(target, context, limit=limit, filter_metadata=filter_metadata,
+                                                      with_wins=with_wins)
+
     def vector_search_range(self, query_vector: List[float], threshold: float,
                             filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,
                             max_results: Optional[int] = None) -> List[Result]:
