@@ -216,6 +216,74 @@ def test_three_queries_equal_each_alone_and_runs_are_bit_equal(native, metric, k
         _assert_equal(first, _reference(case, metric, None, p, k), q)
 
 
+# (name, select_min_k, lds_lists): lists in registers up to k = 128 and in LDS above, the LDS lists whatever k is, the select chain
+ROUTES = [("lists", 200, 0), ("lds_lists", 200, 1), ("select", 1, 0)]
+
+
+@pytest.mark.parametrize("metric", [COS, L2])
+@pytest.mark.parametrize("d", [20, 100])
+def test_every_ranking_route_and_its_launch_counts(native, metric, d):
+    """2 500 rows never bind the scratch bound, so all queries and all (query, zone) slots are ONE round each.  Context mode:
+    the scoring launch (a scan launch), then one merge launch over the partial lists or one select-and-sort bracket per query.
+    Target mode: the scoring launch, the zone launch (a merge launch) and the same tail over the zone slots."""
+    case = _case(native, 2500, d, metric)
+    ix, pairs = case[0], case[3]
+    v = _vectors(case, np.random.default_rng(30 + d), 9)
+    more = pairs + [(v[5], v[6]), (v[7], v[7])]
+    five = [(v[0], []), (v[1], pairs[:1]), (v[2], more), (v[3], pairs), (v[4], pairs[1:])]
+    calls = []  # (queries, k, the reference of each; target mode: the zone slots) -- references first: they run range searches
+    for target in (True, False):
+        for queries in (five[2:3], five):
+            queries = [(t if target else None, p if target or p else pairs) for t, p in queries]
+            for k in (1, 10, 129):
+                want = [_reference(case, metric, t, p, k) for t, p in queries]
+                zones = sum(len(set(w[2][w[0] >= 0].tolist())) for w in want) if target else 0
+                calls.append((queries, k, want, zones))
+    ix.profile(True)
+    try:
+        for name, select_min_k, lds_lists in ROUTES:
+            ix.set_option("select_min_k", select_min_k)
+            ix.set_option("lds_lists", lds_lists)
+            for queries, k, want, zones in calls:
+                nq, target = len(queries), queries[0][0] is not None
+                ix.profile_read()
+                got = _call(ix, queries, k)
+                prof = ix.profile_read()
+                what = (name, target, nq, k, zones, prof)
+                for q in range(nq):
+                    _assert_equal(got, want[q], q)
+                assert ix.get_option("last_discover_path") == (2 if target else 1), what
+                assert ix.get_option("last_discover_zone_slots") == zones, what
+                assert prof["scan_launches"] == 1, what
+                slots = zones if target else nq
+                assert prof["merge_launches"] == (1 if target else 0) + (slots if name == "select" else 1), what
+            # 257 queries (the five, again and again): a round holds at most 256 queries, so the second round writes its one
+            # query's results from slot 256 on; the first round's (query, zone) slots pass 256 too, so its zone stage takes
+            # several rounds of at most 256 slots, each ranked from its first slot on
+            for five_queries, _, five_want, _ in (calls[4], calls[10]):
+                target = five_queries[0][0] is not None
+                want = [five_want[q % 5] for q in range(257)]
+                ix.profile_read()
+                got = _call(ix, [five_queries[q % 5] for q in range(257)], 10)
+                prof = ix.profile_read()
+                for q in range(257):
+                    _assert_equal(got, want[q], q)
+                assert prof["scan_launches"] == 2, (name, target, prof)
+                if not target:
+                    assert prof["merge_launches"] == (257 if name == "select" else 2), (name, prof)
+                    continue
+                zones = [len(set(w[2][w[0] >= 0].tolist())) for w in want]
+                per_round = [sum(zones[:256]), zones[256]]
+                zone_rounds = [-(-z // 256) for z in per_round]
+                assert zone_rounds[0] >= 2 and ix.get_option("last_discover_zone_slots") == sum(per_round), (name, per_round)
+                tails = sum(per_round) if name == "select" else sum(zone_rounds)
+                assert prof["merge_launches"] == sum(zone_rounds) + tails, (name, per_round, prof)
+    finally:
+        ix.profile(False)
+        ix.set_option("select_min_k", 200)
+        ix.set_option("lds_lists", 0)
+
+
 @pytest.mark.parametrize("metric", [COS, L2])
 def test_normalize_vectors(native, metric):
     """scaled vectors with normalize_vectors: the reference takes each r from the range search with normalize_queries, which

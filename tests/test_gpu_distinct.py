@@ -165,6 +165,61 @@ def test_full_pass_counts_its_scoring_launches_as_scan_launches(native):
     assert prof["scan_launches"] == 1 and prof["merge_launches"] >= 2  # one round: scoring, then ranking + merge
 
 
+# (name, select_min_k, lds_lists): lists in registers up to k = 128 and in LDS above, the LDS lists whatever k is, the select chain
+ROUTES = [("lists", 200, 0), ("lds_lists", 200, 1), ("select", 1, 0)]
+
+
+@pytest.mark.parametrize("metric", [COS, L2])
+@pytest.mark.parametrize("d", [20, 100])
+def test_full_pass_ranking_routes_and_their_launch_counts(native, d, metric):
+    """2 500 rows never bind the scratch bound, so the full pass is ONE round: the scoring launch (a scan launch), the label
+    ranking launch and then one merge launch over its partial lists or, on the select route, one select-and-sort bracket per
+    query (all merge launches)."""
+    n = 2500
+    rng = np.random.default_rng(5000 + 10 * d + metric)
+    rows = rng.integers(-2, 3, size=(n, d)).astype(np.int64)
+    queries = rng.integers(-2, 3, size=(257, d)).astype(np.int64)
+    score = queries @ rows.T if metric == COS else np.stack([((q[None, :] - rows) ** 2).sum(axis=1) for q in queries])
+    labels = (np.arange(n) // 10).astype(np.uint32)[rng.permutation(n)]
+    ranked = [_ranking(score[q], metric) for q in range(257)]
+    with native.NativeIndex(d, metric, 0, capacity_rows=n) as ix:
+        ix.add(rows.astype(np.float32), normalize=False)
+        ix.set_labels(0, labels)
+        ix.profile(True)
+        try:
+            for name, select_min_k, lds_lists in ROUTES:
+                ix.set_option("select_min_k", select_min_k)
+                ix.set_option("lds_lists", lds_lists)
+                for k in (1, 10, 129):
+                    for nq in (1, 5):
+                        want = [_expected(ranked[q], score[q], labels, k) for q in range(nq)]
+                        ix.profile_read()
+                        (idx, sc, lab), path = _distinct(ix, queries[:nq].astype(np.float32), k, 0)
+                        prof = ix.profile_read()
+                        what = (name, k, nq, path, prof)
+                        assert path == 3, what
+                        for i, got in enumerate((idx, sc, lab)):
+                            assert np.array_equal(got, np.stack([w[i] for w in want])), what
+                        assert prof["scan_launches"] == 1, what
+                        assert prof["merge_launches"] == 1 + (nq if name == "select" else 1), what
+                # 257 queries: a round holds at most 256, so the second round writes its one query's results from slot 256 on
+                want = [_expected(ranked[q], score[q], labels, 10) for q in range(257)]
+                ix.profile_read()
+                (idx, sc, lab), path = _distinct(ix, queries.astype(np.float32), 10, 0)
+                prof = ix.profile_read()
+                what = (name, "two rounds", path, prof)
+                assert path == 3, what
+                for i, got in enumerate((idx, sc, lab)):
+                    assert np.array_equal(got, np.stack([w[i] for w in want])), what
+                assert prof["scan_launches"] == 2, what
+                assert prof["merge_launches"] == 2 + (257 if name == "select" else 2), what
+        finally:
+            ix.profile(False)
+            ix.set_option("select_min_k", 200)
+            ix.set_option("lds_lists", 0)
+            ix.set_option("distinct_overfetch", 4)
+
+
 # ---- 2. float corpora: bit identity with the handle's other searches ---------------------------------------------------------
 def _dedupe(rows, scores, labels, k):
     keep = _first_per_label(rows, labels)

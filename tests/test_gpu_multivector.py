@@ -217,6 +217,66 @@ def test_radix_select_route_at_small_k_and_scan_launch_count(native):
     assert ix.get_option("multivector_round_vectors") == 256
 
 
+# (name, select_min_k, lds_lists): lists in registers up to k = 128 and in LDS above, the LDS lists whatever k is, the select chain
+ROUTES = [("lists", 200, 0), ("lds_lists", 200, 1), ("select", 1, 0)]
+
+
+def _planned_ranked(offsets, option):
+    """host_multivector.h on a small corpus: per round, how many queries END in it (those are ranked there)"""
+    total, ends = int(offsets[-1]), [int(o) for o in offsets[1:]]
+    out, first = [], 0
+    while first < total:
+        take = min(total - first, option)
+        if take < total - first and take >= 8:
+            take = take // 8 * 8
+        out.append(sum(first < e <= first + take for e in ends))
+        first += take
+    return out
+
+
+@pytest.mark.parametrize("metric", [COS, L2])
+@pytest.mark.parametrize("d", [20, 100])
+def test_ranking_routes_and_their_launch_counts(native, d, metric):
+    """per round: the scoring launch (a scan launch) and the reduce-and-rank bracket; a round that ends queries then ranks them
+    with one merge launch over their partial lists or, on the select route, one select-and-sort bracket per query.  Rounds of
+    3 vectors: queries that span rounds, rounds that rank none, one or two queries, and results written from a later query on."""
+    n = 2500
+    rng = np.random.default_rng(6000 + 10 * d + metric)
+    rows = rng.integers(-2, 3, size=(n, d))
+    labels = (np.arange(n) // 10).astype(np.uint32)[rng.permutation(n)]
+    dense, row0, lab = _label_order(labels)
+    with native.NativeIndex(d, metric, 0, capacity_rows=n) as ix:
+        ix.add(rows.astype(np.float32), normalize=False)
+        ix.set_labels(0, labels)
+        ix.profile(True)
+        try:
+            for counts in ((3,), (1, 3, 2, 4, 2)):
+                offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
+                vectors = rng.integers(-2, 3, size=(int(offsets[-1]), d))
+                m, has = _maxima(_domain(vectors, rows, metric), dense, len(row0))
+                for k in (1, 10, 129):
+                    want = _expected_call(m, has, offsets, row0, lab, k, metric)
+                    for name, select_min_k, lds_lists in ROUTES:
+                        ix.set_option("select_min_k", select_min_k)
+                        ix.set_option("lds_lists", lds_lists)
+                        for option in (256, 3):
+                            ranked = _planned_ranked(offsets, option)
+                            ix.profile_read()
+                            got = _search(ix, vectors.astype(np.float32), offsets, k, option)
+                            prof = ix.profile_read()
+                            what = (name, counts, k, option, ranked, prof)
+                            for g, w in zip(got, want):
+                                assert np.array_equal(g, w), what
+                            assert ix.get_option("last_multivector_rounds") == len(ranked), what
+                            assert prof["scan_launches"] == len(ranked), what
+                            tails = sum(ranked) if name == "select" else sum(r > 0 for r in ranked)
+                            assert prof["merge_launches"] == len(ranked) + tails, what
+        finally:
+            ix.profile(False)
+            ix.set_option("select_min_k", 200)
+            ix.set_option("lds_lists", 0)
+
+
 def test_a_handle_without_labels_ranks_every_row_by_its_sum(native):
     _, vectors, score, rows = _int_case(native, 3, COS)
     with native.NativeIndex(3, COS, 0, capacity_rows=N_INT) as plain:

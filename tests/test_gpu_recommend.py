@@ -295,3 +295,59 @@ def test_raw_abi_refusals_and_null_out_side(native):
     idx[:], score[:] = -9, -9
     assert call(sd=None) == 0
     assert idx.tobytes() == good[0].tobytes() and score.tobytes() == good[1].tobytes()
+
+
+# ---- every ranking route of the host call, and what each launches -------------------------------------------------------------
+# (name, select_min_k, lds_lists): lists in registers up to k = 128 and in LDS above, the LDS lists whatever k is, the select chain
+ROUTES = [("lists", 200, 0), ("lds_lists", 200, 1), ("select", 1, 0)]
+
+
+@pytest.mark.parametrize("metric", [COS, L2])
+@pytest.mark.parametrize("d", [20, 100])
+def test_every_ranking_route_and_its_launch_counts(native, metric, d):
+    """2 500 rows never bind the scratch bound, so a pass is ONE round: one scan launch, then one merge launch over the partial
+    lists or, on the select route, one select-and-sort bracket per slot.  The disfavoured pass runs for the short queries only
+    (here: a positive that is also the negative, and row 7 against the corpus mean), with the metric flipped in its tail."""
+    case = _case(native, 2500, d, metric)
+    ix, rows, _ = case
+    ex = _examples(case, np.random.default_rng(40 + d), 12)
+    mean = np.nanmean(rows.astype(np.float64), axis=0)
+    mean = (mean / np.linalg.norm(mean)).astype(_F32)
+    five = [(ex[:1], []), (ex[1:4], ex[4:5]), ([rows[7].copy()], [mean]), (ex[5:6], ex[5:6]), (ex[6:9], ex[9:12])]
+    calls = [(queries, k, [_reference(case, metric, pos, neg, k) for pos, neg in queries])
+             for queries in (five[3:4], five) for k in (1, 10, 129)]  # (references first: they run range searches)
+    ix.profile(True)
+    try:
+        for name, select_min_k, lds_lists in ROUTES:
+            ix.set_option("select_min_k", select_min_k)
+            ix.set_option("lds_lists", lds_lists)
+            for queries, k, want in calls:
+                nq, ns = len(queries), sum(w[3] < k for w in want)
+                assert ns >= 1
+                ix.profile_read()
+                got = _call(ix, queries, k)
+                prof = ix.profile_read()
+                what = (name, nq, k, prof)
+                for q in range(nq):
+                    _assert_equal(got, want[q], q)
+                assert ix.get_option("last_recommend_path") == 2 and ix.get_option("last_recommend_short") == ns, what
+                assert prof["scan_launches"] == 2, what  # (one round per side)
+                assert prof["merge_launches"] == (nq + ns if name == "select" else 2), what
+            # 257 queries (the five, again and again): a round holds at most 256, so the favoured pass's second round writes its
+            # one query's results from slot 256 on; the short queries (fewer than 256) are one round of the disfavoured pass
+            want = [calls[4][2][q % 5] for q in range(257)]
+            ns = sum(w[3] < 10 for w in want)
+            assert 1 <= ns <= 256
+            ix.profile_read()
+            got = _call(ix, [five[q % 5] for q in range(257)], 10)
+            prof = ix.profile_read()
+            what = (name, "two rounds", ns, prof)
+            for q in range(257):
+                _assert_equal(got, want[q], q)
+            assert ix.get_option("last_recommend_short") == ns, what
+            assert prof["scan_launches"] == 3, what
+            assert prof["merge_launches"] == (257 + ns if name == "select" else 3), what
+    finally:
+        ix.profile(False)
+        ix.set_option("select_min_k", 200)
+        ix.set_option("lds_lists", 0)

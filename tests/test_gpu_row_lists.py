@@ -149,6 +149,38 @@ def test_more_than_256_queries_take_two_rounds(native, metric):
     _same(got, _expected(score, metric, lists, which, k), (metric, "shared"))
 
 
+@pytest.mark.parametrize("metric", [COS, L2])
+@pytest.mark.parametrize("d", [20, 100])
+def test_launch_counts_per_round(native, d, metric):
+    """every round is one scoring launch (a scan launch) and one merge launch over the slots' keys with their list lengths as
+    counts; 300 queries are two rounds, the second writes its results from slot 256 on"""
+    n = 2500
+    rng = np.random.default_rng(7000 + 10 * d + metric)
+    rows = rng.integers(-2, 3, size=(n, d)).astype(np.int64)
+    queries = rng.integers(-2, 3, size=(300, d)).astype(np.int64)
+    score = queries @ rows.T if metric == COS else np.stack([((q[None, :] - rows) ** 2).sum(axis=1) for q in queries])
+    with native.NativeIndex(d, metric, 0, capacity_rows=n) as ix:
+        ix.add(rows.astype(np.float32), normalize=False)
+        keep = ix.get_option("rows_keys_max")
+        ix.set_option("rows_keys_max", 8192)
+        ix.profile(True)
+        try:
+            for nq, k, rounds in [(1, 1, 1), (1, 10, 1), (1, 129, 1), (5, 1, 1), (5, 10, 1), (5, 129, 1), (300, 10, 2)]:
+                lists = [np.sort(rng.choice(n, int(m), replace=False)).astype(np.uint64) for m in rng.integers(1, 400, min(nq, 7))]
+                which = rng.integers(0, len(lists), nq)
+                which[: len(lists)] = np.arange(len(lists))[:nq]  # (every list has a query)
+                ix.profile_read()
+                got = ix.search_row_lists(queries[:nq].astype(np.float32), k, lists, which)
+                prof = ix.profile_read()
+                what = (d, metric, nq, k, prof)
+                assert ix.get_option("last_lists_path") == 1 and ix.get_option("last_lists_rounds") == rounds, what
+                _same(got, _expected(score, metric, lists, which, k), what)
+                assert prof["scan_launches"] == rounds and prof["merge_launches"] == rounds, what
+        finally:
+            ix.profile(False)
+            ix.set_option("rows_keys_max", keep)
+
+
 # ---- 4. the list-by-list route, alone and mixed ----------------------------------------------------------------------------------
 @pytest.mark.parametrize("metric", [COS, L2])
 def test_fall_back_and_mixed_routes_give_the_same_answers(native, metric):

@@ -140,6 +140,52 @@ def test_integer_corpora_equal_the_int64_reference_on_every_route(native, d, met
         ix.set_option("lds_lists", 0)
 
 
+@pytest.mark.parametrize("metric", [COS, L2])
+@pytest.mark.parametrize("d", [20, 100])
+def test_launch_counts_of_every_route(native, d, metric):
+    """2 500 rows never bind the scratch bound, so a call is ONE round: the scoring launch (a scan launch), then one merge launch
+    over the keys or the partial lists or, on the select route, one select-and-sort bracket per query"""
+    n = 2500
+    rng = np.random.default_rng(8000 + 10 * d + metric)
+    rows = rng.integers(-2, 3, size=(n, d)).astype(np.int64)
+    queries = rng.integers(-2, 3, size=(257, d)).astype(np.int64)
+    score = queries @ rows.T if metric == COS else np.stack([((q[None, :] - rows) ** 2).sum(axis=1) for q in queries])
+    ids = np.sort(rng.choice(n, 1500, replace=False))
+    # (rows_keys_max, select_min_k, lds_lists) -> last_rows_path
+    routes = [((1 << 30, 200, 0), KEYS), ((0, 200, 0), LISTS), ((0, 200, 1), LISTS), ((0, 1, 0), SELECT)]
+    with native.NativeIndex(d, metric, 0, capacity_rows=n) as ix:
+        ix.add(rows.astype(np.float32), normalize=False)
+        keep = ix.get_option("rows_keys_max")
+        ix.profile(True)
+        try:
+            for route, path in routes:
+                ix.set_option("lds_lists", route[2])
+                for k in (1, 10, 129):
+                    for nq in (1, 5):
+                        want = _int_expected(score, metric, ids, nq, k)
+                        ix.profile_read()
+                        idx, sc = _search(ix, queries[:nq].astype(np.float32), k, ids, route, path)
+                        prof = ix.profile_read()
+                        what = (d, metric, route, k, nq, prof)
+                        assert np.array_equal(idx, want[0]) and np.array_equal(sc, want[1]), what
+                        assert prof["scan_launches"] == 1, what
+                        assert prof["merge_launches"] == (nq if path == SELECT else 1), what
+                # 257 queries: a round holds at most 256, so the second round writes its one query's results from slot 256 on
+                want = _int_expected(score, metric, ids, 257, 10)
+                ix.profile_read()
+                idx, sc = _search(ix, queries.astype(np.float32), 10, ids, route, path)
+                prof = ix.profile_read()
+                what = (d, metric, route, "two rounds", prof)
+                assert np.array_equal(idx, want[0]) and np.array_equal(sc, want[1]), what
+                assert prof["scan_launches"] == 2, what
+                assert prof["merge_launches"] == (257 if path == SELECT else 2), what
+        finally:
+            ix.profile(False)
+            ix.set_option("rows_keys_max", keep)
+            ix.set_option("select_min_k", 200)
+            ix.set_option("lds_lists", 0)
+
+
 # ---- 2. float data against float64 ----------------------------------------------------------------------------------------
 def _float_corpus(n, d, metric, seed):
     rng = np.random.default_rng(seed)

@@ -462,6 +462,74 @@ static int launch_merge(wdbx_index* ix, const MergeArgs& m_in, int nq) {
   return record(ix->merge_ev, ix->profile, ix->stream, false);
 }
 
+// ---- what the listed-row, label and corpus calls share ------------------------------------------------
+// One launch of 256-thread workgroups between the two records of `pool`; a kernel whose dynamic LDS passes 64 KiB gets its limit
+// raised first -- a runtime call on EVERY such launch, so a site that launches in a loop of rounds with lists in LDS raises the
+// limit once before the loop and keeps its bracket written out (today every caller passes lds = 0 and the raise is not reached);
+// so does a site that launches twice inside one bracket or counts more than one launch per bracket.
+template <typename Fn, typename Args>
+static int launch_bracketed(wdbx_index* ix, EventPool& pool, Fn fn, dim3 grid, size_t lds, const Args& a) {
+  if (lds >= 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  int rc = record(pool, ix->profile, ix->stream, true);
+  if (rc) return rc;
+  hipLaunchKernelGGL(fn, grid, dim3(256), lds, ix->stream, a);
+  HIP_TRY(hipGetLastError());
+  return record(pool, ix->profile, ix->stream, false);
+}
+
+// What a round's scoring launch left to rank, slot after slot:
+//   LISTS   n partial lists of k sorted keys per slot ([slot][k][n]) -> one merge launch
+//   SELECT  n keys per slot -> per slot the radix-select chain and the sort of its k keys, inside one merge bracket each
+//   KEYS    n keys per slot, ranked as unsorted candidates by one merge launch; P_dev (optional): each slot's own count
+struct RankSource {
+  enum Form { LISTS, SELECT, KEYS } form;
+  const u64* in;
+  uint64_t n;
+  const uint32_t* P_dev;
+};
+
+// the scratch of a round: partial lists, or keys and -- on the select route only -- the chain's state
+static int grow_rank_scratch(wdbx_index* ix, RankSource::Form form, size_t scratch_u64) {
+  int rc;
+  if (form == RankSource::LISTS) return grow((void**)&ix->d_partials, &ix->partials_bytes, scratch_u64 * sizeof(u64));
+  if ((rc = grow((void**)&ix->d_sub_keys, &ix->sub_keys_bytes, scratch_u64 * sizeof(u64))) || form == RankSource::KEYS) return rc;
+  if ((rc = grow((void**)&ix->d_sel, &ix->sel_bytes, (size_t)WDBX_MAX_K * sizeof(u64)))) return rc;
+  return grow((void**)&ix->d_state, &ix->state_bytes, sizeof(SelectState));
+}
+
+// The ranking tail of `b` slots: their best k into d_oidx / d_oscore from slot `first` on.  metric: what converts a key's value
+// to the caller's score (recommend's disfavoured side passes the other metric, discovery's context mode cosine).
+static int enqueue_rank_tail(wdbx_index* ix, const RankSource& src, int first, int b, int k, int metric) {
+  int rc;
+  MergeArgs m = {};
+  m.k = k;
+  m.metric = metric;
+  if (src.form == RankSource::SELECT) {
+    const uint32_t sgrid = radix_select_grid(src.n, ix->cu_count);
+    for (int q = 0; q < b; ++q) {
+      if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
+      HIP_TRY(enqueue_radix_select(ix->stream, src.in + (size_t)q * src.n, (u64)src.n, nullptr, (SelectState*)ix->d_state,
+                                   (u64*)ix->d_sel, (uint32_t)k, sgrid));
+      m.out_idx = ix->d_oidx + (size_t)(first + q) * k;
+      m.out_score = ix->d_oscore + (size_t)(first + q) * k;
+      HIP_TRY(enqueue_sort_out(ix->stream, (const u64*)ix->d_sel, (const SelectState*)ix->d_state, m));
+      if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
+    }
+    return WDBX_OK;
+  }
+  const bool lists = src.form == RankSource::LISTS;
+  m.in = src.in;
+  m.q_stride = lists ? (uint64_t)k * src.n : src.n;
+  m.i_stride = lists ? src.n : 0;
+  m.p_stride = 1;
+  m.P = (uint32_t)src.n;
+  m.P_dev = src.P_dev;
+  m.list_len = lists ? k : 1;
+  m.out_idx = ix->d_oidx + (size_t)first * k;
+  m.out_score = ix->d_oscore + (size_t)first * k;
+  return launch_merge(ix, m, b);
+}
+
 // ---- the steps the selection rounds share (their plan: host_selection.h) ------------------------------------------
 static_assert(SELECTION_BLOCK_QUERIES == GB_N, "host_selection.h sizes the pair lists for the widest query block");
 
@@ -1299,11 +1367,8 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
     a.count2 = ix->d_count + q0;
     a.cap = cap;
     // the sample, all queries of the round in one launch: maxima of the lower bounds over the sampled groups
-    if ((rc = record(ix->sample_ev, ix->profile, ix->stream, true))) return rc;
     ix->last_sample_qn = 4;
-    hipLaunchKernelGGL(f0, dim3(grid0, (nv + 3) / 4), dim3(256), 0, ix->stream, a);
-    HIP_TRY(hipGetLastError());
-    if ((rc = record(ix->sample_ev, ix->profile, ix->stream, false))) return rc;
+    if ((rc = launch_bracketed(ix, ix->sample_ev, f0, dim3(grid0, (nv + 3) / 4), 0, a))) return rc;
     if ((rc = enqueue_sample_threshold(ix, ngroups, k, nv, true))) return rc;
     // the full passes: every query makes its own pass over all rows, on the split planes together with up to three neighbours
     // (one grid on small shards, as the u8 scan); one event pair around them, the profile reports elapsed / nv passes
@@ -2132,9 +2197,13 @@ static int enqueue_exact_rerun(wdbx_index* ix, const float* dq, int k, int64_t* 
 
 // ---- recommend search (kernels_recommend.h, host_recommend.h): one side's pass for `slots` queries ------------------------
 // d_table holds the slots' example table, the examples are in d_q, the mask (if any) is the active one.  Rounds of rp.round
-// slots: recommend_kernel (bracketed as a scan launch), then one merge launch over the round's partial lists or per slot the
-// radix-select chain.  Results: d_oidx / d_oscore [slots, k].  The disfavoured side's key value is -n in the ranking domain, so
-// the merge converts it with the OTHER metric's sign: out_score is n in the caller's units.
+// slots: recommend_kernel (bracketed as a scan launch), then the ranking tail (enqueue_rank_tail).  Results: d_oidx / d_oscore
+// [slots, k].  The disfavoured side's key value is -n in the ranking domain, so the tail converts it with the OTHER metric's
+// sign: out_score is n in the caller's units.
+static RankSource corpus_rank_source(const wdbx_index* ix, bool lists, uint32_t P) {  // (a corpus pass: P lists, or a key per row)
+  return lists ? RankSource{RankSource::LISTS, ix->d_partials, P, nullptr} : RankSource{RankSource::SELECT, ix->d_sub_keys, ix->n, nullptr};
+}
+
 static int enqueue_recommend_pass(wdbx_index* ix, const RecommendPlan& rp, const uint32_t* d_table, int slots, int k, int side,
                                   const uint32_t* d_exclude, uint32_t n_exclude) {
   const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
@@ -2163,31 +2232,8 @@ static int enqueue_recommend_pass(wdbx_index* ix, const RecommendPlan& rp, const
     hipLaunchKernelGGL(fn, dim3(rp.blocks, (uint32_t)b), dim3(256), lds, ix->stream, a);
     HIP_TRY(hipGetLastError());
     if ((rc = record(ix->scan_ev, ix->profile, ix->stream, false))) return rc;
-    MergeArgs m = {};
-    m.k = k;
-    m.metric = side ? ix->metric : (ix->metric == WDBX_METRIC_L2 ? WDBX_METRIC_COSINE : WDBX_METRIC_L2);
-    if (!lists) {
-      const uint32_t sgrid = radix_select_grid(ix->n, ix->cu_count);
-      for (int q = 0; q < b; ++q) {
-        if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
-        HIP_TRY(enqueue_radix_select(ix->stream, (const u64*)ix->d_sub_keys + (size_t)q * ix->n, (u64)ix->n, nullptr,
-                                     (SelectState*)ix->d_state, (u64*)ix->d_sel, (uint32_t)k, sgrid));
-        m.out_idx = ix->d_oidx + (size_t)(q0 + q) * k;
-        m.out_score = ix->d_oscore + (size_t)(q0 + q) * k;
-        HIP_TRY(enqueue_sort_out(ix->stream, (const u64*)ix->d_sel, (const SelectState*)ix->d_state, m));
-        if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
-      }
-      continue;
-    }
-    m.in = ix->d_partials;
-    m.q_stride = (uint64_t)k * rp.P;
-    m.i_stride = rp.P;
-    m.p_stride = 1;
-    m.P = rp.P;
-    m.list_len = k;
-    m.out_idx = ix->d_oidx + (size_t)q0 * k;
-    m.out_score = ix->d_oscore + (size_t)q0 * k;
-    if ((rc = launch_merge(ix, m, b))) return rc;
+    const int metric = side ? ix->metric : (ix->metric == WDBX_METRIC_L2 ? WDBX_METRIC_COSINE : WDBX_METRIC_L2);
+    if ((rc = enqueue_rank_tail(ix, corpus_rank_source(ix, lists, rp.P), q0, b, k, metric))) return rc;
   }
   return WDBX_OK;
 }
@@ -2208,13 +2254,7 @@ static int recommend_locked(wdbx_index* ix, const float* examples, const uint64_
   uint32_t* d_tab = (uint32_t*)ix->d_rec;
   uint32_t* d_tab_short = d_tab + tab_words;
   uint32_t* d_exclude = d_tab_short + tab_words;
-  if (rp.mode != 2) {
-    if ((rc = grow((void**)&ix->d_partials, &ix->partials_bytes, rp.scratch_u64 * sizeof(u64)))) return rc;
-  } else {
-    if ((rc = grow((void**)&ix->d_sub_keys, &ix->sub_keys_bytes, rp.scratch_u64 * sizeof(u64)))) return rc;
-    if ((rc = grow((void**)&ix->d_sel, &ix->sel_bytes, (size_t)WDBX_MAX_K * sizeof(u64)))) return rc;
-    if ((rc = grow((void**)&ix->d_state, &ix->state_bytes, sizeof(SelectState)))) return rc;
-  }
+  if ((rc = grow_rank_scratch(ix, rp.mode != 2 ? RankSource::LISTS : RankSource::SELECT, rp.scratch_u64))) return rc;
   if ((rc = upload_queries(ix, examples, off[2 * nq], normalize_examples))) return rc;
   if (mask_words && (rc = scope.set(mask_words))) return rc;
   std::vector<uint32_t> all((size_t)nq), tab(tab_words);
@@ -2236,11 +2276,8 @@ static int recommend_locked(wdbx_index* ix, const float* examples, const uint64_
     recommend_table(off, short_queries.data(), short_queries.size(), tab_short.data());
     HIP_TRY(hipMemcpyAsync(d_tab_short, tab_short.data(), tab_short.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
     const RecommendPlan rs = recommend_plan(ix->n, ns, k, ix->cu_count, ix->opt_select_min_k, ix->opt_lds_lists != 0);
-    if (rs.mode != 2) {  // (fewer queries: a wider grid, so longer partial lists per query)
-      if ((rc = grow((void**)&ix->d_partials, &ix->partials_bytes, rs.scratch_u64 * sizeof(u64)))) return rc;
-    } else {
-      if ((rc = grow((void**)&ix->d_sub_keys, &ix->sub_keys_bytes, rs.scratch_u64 * sizeof(u64)))) return rc;
-    }
+    // (fewer queries: a wider grid, so longer partial lists per query; the mode is the first pass's: it goes by k alone)
+    if ((rc = grow_rank_scratch(ix, rs.mode != 2 ? RankSource::LISTS : RankSource::SELECT, rs.scratch_u64))) return rc;
     if ((rc = enqueue_recommend_pass(ix, rs, d_tab_short, ns, k, 0, d_exclude, (uint32_t)n_ex))) return rc;
     dis_idx.resize((size_t)ns * k);
     dis_score.resize((size_t)ns * k);
@@ -2253,45 +2290,6 @@ static int recommend_locked(wdbx_index* ix, const float* examples, const uint64_
 }
 
 // ---- discovery search (kernels_discover.h, host_discover.h) -----------------------------------------------------------------
-// the ranking tail of `b` slots whose partial lists (d_partials, P per slot) or keys per row (d_sub_keys) a launch just wrote:
-// one merge launch, or per slot the radix-select chain; results to d_oidx / d_oscore from slot `first` on
-static int enqueue_discover_tail(wdbx_index* ix, bool lists, uint32_t P, int first, int b, int k, int metric) {
-  int rc;
-  MergeArgs m = {};
-  m.k = k;
-  m.metric = metric;
-  if (!lists) {
-    const uint32_t sgrid = radix_select_grid(ix->n, ix->cu_count);
-    for (int q = 0; q < b; ++q) {
-      if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
-      HIP_TRY(enqueue_radix_select(ix->stream, (const u64*)ix->d_sub_keys + (size_t)q * ix->n, (u64)ix->n, nullptr,
-                                   (SelectState*)ix->d_state, (u64*)ix->d_sel, (uint32_t)k, sgrid));
-      m.out_idx = ix->d_oidx + (size_t)(first + q) * k;
-      m.out_score = ix->d_oscore + (size_t)(first + q) * k;
-      HIP_TRY(enqueue_sort_out(ix->stream, (const u64*)ix->d_sel, (const SelectState*)ix->d_state, m));
-      if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
-    }
-    return WDBX_OK;
-  }
-  m.in = ix->d_partials;
-  m.q_stride = (uint64_t)k * P;
-  m.i_stride = P;
-  m.p_stride = 1;
-  m.P = P;
-  m.list_len = k;
-  m.out_idx = ix->d_oidx + (size_t)first * k;
-  m.out_score = ix->d_oscore + (size_t)first * k;
-  return launch_merge(ix, m, b);
-}
-
-static int grow_discover_scratch(wdbx_index* ix, bool lists, size_t scratch_u64) {
-  int rc;
-  if (lists) return grow((void**)&ix->d_partials, &ix->partials_bytes, scratch_u64 * sizeof(u64));
-  if ((rc = grow((void**)&ix->d_sub_keys, &ix->sub_keys_bytes, scratch_u64 * sizeof(u64)))) return rc;
-  if ((rc = grow((void**)&ix->d_sel, &ix->sel_bytes, (size_t)WDBX_MAX_K * sizeof(u64)))) return rc;
-  return grow((void**)&ix->d_state, &ix->state_bytes, sizeof(SelectState));
-}
-
 // The call under the handle's lock (the caller holds it, has checked the arguments that need no lock, and resets the mask).
 // Context mode (no targets): per round the scoring pass ranks by the loss and the tail follows; the loss is a ranking-domain
 // value for either metric, so the tail never applies the L2 sign.  Target mode, per round of queries:
@@ -2324,7 +2322,8 @@ static int discover_locked(wdbx_index* ix, const float* targets, const float* co
   uint32_t* d_qtab = (uint32_t*)(ix->d_disc + qtab_at);
   uint32_t* d_ztab = (uint32_t*)(ix->d_disc + ztab_at);
   uint32_t* d_exclude = (uint32_t*)(ix->d_disc + ex_at);
-  if (!target && (rc = grow_discover_scratch(ix, lists, dp.scratch_u64))) return rc;
+  const RankSource::Form form = lists ? RankSource::LISTS : RankSource::SELECT;
+  if (!target && (rc = grow_rank_scratch(ix, form, dp.scratch_u64))) return rc;
   if ((rc = ensure_out(ix, (size_t)nq * k))) return rc;
   // the staged vectors: context mode's are the caller's array as it is
   const uint64_t staged = discover_staged_count(off, nq, target);
@@ -2364,7 +2363,7 @@ static int discover_locked(wdbx_index* ix, const float* targets, const float* co
     HIP_TRY(hipGetLastError());
     if ((rc = record(ix->scan_ev, ix->profile, ix->stream, false))) return rc;
     if (!target) {
-      if ((rc = enqueue_discover_tail(ix, lists, dp.P, q0, b, k, WDBX_METRIC_COSINE))) return rc;
+      if ((rc = enqueue_rank_tail(ix, corpus_rank_source(ix, lists, dp.P), q0, b, k, WDBX_METRIC_COSINE))) return rc;
       continue;
     }
     std::vector<uint32_t> counts((size_t)b * DISCOVER_ZONES);
@@ -2386,7 +2385,7 @@ static int discover_locked(wdbx_index* ix, const float* targets, const float* co
       const DiscoverZonePlan zp = discover_zone_plan(ix->n, zslots, k, dp.mode, ix->cu_count);
       const discover_zone_fn zfn = pick_discover_zone(dp.mode);
       if (!zfn) return fail(WDBX_E_STATE, "no discover zone instance for mode %d", dp.mode);
-      if ((rc = grow_discover_scratch(ix, lists, zp.scratch_u64))) return rc;
+      if ((rc = grow_rank_scratch(ix, form, zp.scratch_u64))) return rc;
       if ((rc = ensure_out(ix, (size_t)zslots * k))) return rc;
       if (zp.lds >= 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)zfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)zp.lds));
       HIP_TRY(hipMemcpyAsync(d_ztab, ztab.data(), ztab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
@@ -2403,7 +2402,7 @@ static int discover_locked(wdbx_index* ix, const float* targets, const float* co
         hipLaunchKernelGGL(zfn, dim3(zp.blocks, (uint32_t)zr.second), dim3(256), zp.lds, ix->stream, za);
         HIP_TRY(hipGetLastError());
         if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
-        if ((rc = enqueue_discover_tail(ix, lists, zp.P, zr.first, zr.second, k, ix->metric))) return rc;
+        if ((rc = enqueue_rank_tail(ix, corpus_rank_source(ix, lists, zp.P), zr.first, zr.second, k, ix->metric))) return rc;
       }
       if ((rc = download_results(ix, (size_t)zslots * k, z_idx.data(), z_score.data()))) return rc;
       ix->last_discover_zone_slots += zslots;

@@ -782,8 +782,8 @@ int wdbx_index_search_multimask(wdbx_index* ix, const float* queries, int nq, in
 // ---- search among listed rows (kernels_subset.h, host_subset.h) -------------------------------------
 // The whole call holds the handle's mutex (like a masked search: the list buffer is the handle's).  The list is validated
 // and narrowed under the lock (row numbers are checked against the row count a concurrent add cannot change meanwhile), goes
-// to the device once, and the queries are served in rounds (subset_plan): subset_kernel, then per round one merge launch
-// (lists or keys) or per query the radix-select chain.  The scoring launches are bracketed as scan launches.
+// to the device once, and the queries are served in rounds (subset_plan): subset_kernel, then the ranking tail
+// (enqueue_rank_tail, host_index.h).  The scoring launches are bracketed as scan launches.
 // held: the caller already holds the handle's mutex and keeps it (wdbx_index_search_row_lists' list-by-list route), as in search_host.
 static int search_rows_host(wdbx_index* ix, const float* queries, int nq, int k, int normalize_queries, const uint64_t* row_ids,
                             uint64_t n_ids, int64_t* out_idx, float* out_score, bool held = false) {
@@ -815,15 +815,8 @@ static int search_rows_host(wdbx_index* ix, const float* queries, int nq, int k,
   if ((rc = ensure_out(ix, elems))) return rc;
   if ((rc = grow((void**)&ix->d_sub_ids, &ix->sub_ids_bytes, (size_t)n_ids * sizeof(uint32_t)))) return rc;
   const bool lists = sp.route == SUBSET_LISTS;
-  if (lists) {
-    if ((rc = grow((void**)&ix->d_partials, &ix->partials_bytes, sp.scratch_u64 * sizeof(u64)))) return rc;
-  } else {
-    if ((rc = grow((void**)&ix->d_sub_keys, &ix->sub_keys_bytes, sp.scratch_u64 * sizeof(u64)))) return rc;
-  }
-  if (sp.route == SUBSET_SELECT) {
-    if ((rc = grow((void**)&ix->d_sel, &ix->sel_bytes, (size_t)WDBX_MAX_K * sizeof(u64)))) return rc;
-    if ((rc = grow((void**)&ix->d_state, &ix->state_bytes, sizeof(SelectState)))) return rc;
-  }
+  const RankSource::Form form = lists ? RankSource::LISTS : sp.route == SUBSET_SELECT ? RankSource::SELECT : RankSource::KEYS;
+  if ((rc = grow_rank_scratch(ix, form, sp.scratch_u64))) return rc;
   if ((rc = upload_queries(ix, queries, (uint64_t)nq, normalize_queries))) return rc;
   HIP_TRY(hipMemcpyAsync(ix->d_sub_ids, ids32.data(), (size_t)n_ids * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
 
@@ -851,40 +844,8 @@ static int search_rows_host(wdbx_index* ix, const float* queries, int nq, int k,
     hipLaunchKernelGGL(fn, dim3(sp.blocks, qblocks), dim3(256), lds, ix->stream, a);
     HIP_TRY(hipGetLastError());
     if ((rc = record(ix->scan_ev, ix->profile, ix->stream, false))) return rc;
-    MergeArgs m = {};
-    m.k = k;
-    m.metric = ix->metric;
-    if (sp.route == SUBSET_SELECT) {
-      const uint32_t sgrid = radix_select_grid(n_ids, ix->cu_count);
-      for (int q = 0; q < b; ++q) {
-        if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
-        HIP_TRY(enqueue_radix_select(ix->stream, (const u64*)ix->d_sub_keys + (size_t)q * n_ids, (u64)n_ids, nullptr,
-                                     (SelectState*)ix->d_state, (u64*)ix->d_sel, (uint32_t)k, sgrid));
-        m.out_idx = ix->d_oidx + (size_t)(q0 + q) * k;
-        m.out_score = ix->d_oscore + (size_t)(q0 + q) * k;
-        HIP_TRY(enqueue_sort_out(ix->stream, (const u64*)ix->d_sel, (const SelectState*)ix->d_state, m));
-        if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
-      }
-      continue;
-    }
-    if (lists) {
-      m.in = ix->d_partials;
-      m.q_stride = (uint64_t)k * sp.P;
-      m.i_stride = sp.P;
-      m.p_stride = 1;
-      m.P = sp.P;
-      m.list_len = k;
-    } else {
-      m.in = ix->d_sub_keys;
-      m.q_stride = n_ids;
-      m.i_stride = 0;
-      m.p_stride = 1;
-      m.P = (uint32_t)n_ids;
-      m.list_len = 1;
-    }
-    m.out_idx = ix->d_oidx + (size_t)q0 * k;
-    m.out_score = ix->d_oscore + (size_t)q0 * k;
-    if ((rc = launch_merge(ix, m, b))) return rc;
+    const RankSource src = lists ? RankSource{form, ix->d_partials, sp.P, nullptr} : RankSource{form, ix->d_sub_keys, n_ids, nullptr};
+    if ((rc = enqueue_rank_tail(ix, src, q0, b, k, ix->metric))) return rc;
   }
   return download_results(ix, elems, out_idx, out_score);
 }
@@ -974,24 +935,10 @@ int wdbx_index_search_row_lists(wdbx_index* ix, const float* queries, int nq, in
         a.keys = ix->d_sub_keys;
         a.stride = r.stride;
         a.pitch4 = pitch4;
-        if ((rc = record(ix->scan_ev, ix->profile, ix->stream, true))) return rc;
-        hipLaunchKernelGGL(fn, dim3((uint32_t)r.items), dim3(256), 0, ix->stream, a);
-        HIP_TRY(hipGetLastError());
-        if ((rc = record(ix->scan_ev, ix->profile, ix->stream, false))) return rc;
+        if ((rc = launch_bracketed(ix, ix->scan_ev, fn, dim3((uint32_t)r.items), 0, a))) return rc;
       }
-      MergeArgs m = {};
-      m.k = k;
-      m.metric = ix->metric;
-      m.in = ix->d_sub_keys;
-      m.q_stride = r.stride;
-      m.i_stride = 0;
-      m.p_stride = 1;
-      m.P = (uint32_t)r.stride;
-      m.P_dev = d_len + r.slot0;
-      m.list_len = 1;
-      m.out_idx = ix->d_oidx + (size_t)r.slot0 * k;
-      m.out_score = ix->d_oscore + (size_t)r.slot0 * k;
-      if ((rc = launch_merge(ix, m, (int)r.slots))) return rc;
+      const RankSource src = {RankSource::KEYS, ix->d_sub_keys, r.stride, d_len + r.slot0};
+      if ((rc = enqueue_rank_tail(ix, src, (int)r.slot0, (int)r.slots, k, ix->metric))) return rc;
     }
     if ((rc = download_results(ix, plan.slot_query, k, out_idx, out_score))) return rc;
   }
@@ -1060,9 +1007,40 @@ static int ensure_label_order(wdbx_index* ix) {
   return WDBX_OK;
 }
 
+// what the label calls (distinct, multi-vector) share: label_keys_kernel's arguments for nq queries from first_query on, ...
+static LabelKeysArgs label_keys_args(const wdbx_index* ix, uint64_t first_query, uint32_t nq, uint32_t pitch4) {
+  LabelKeysArgs a = {};
+  a.rows = (const f4*)ix->d_rows;
+  a.queries = (const f4*)(ix->d_q + (size_t)first_query * ix->pitch);
+  a.order = (const uint32_t*)ix->d_lab;
+  a.dense = (const uint32_t*)(ix->d_lab + ix->lab_off_dense);
+  a.span_item0 = (const uint32_t*)(ix->d_lab + ix->lab_off_span);
+  a.mask = ix->active_mask;
+  a.keys = ix->d_sub_keys;
+  a.key_stride = ix->lab_items;
+  a.n = (uint32_t)ix->n;
+  a.n_spans = ix->lab_spans;
+  a.pitch4 = pitch4;
+  a.nq = nq;
+  return a;
+}
+
+// ... their scratch: the item keys in d_sub_keys and behind them, on the select route, a key per label; else the partial lists
+static int grow_label_scratch(wdbx_index* ix, bool select, size_t keys_u64, size_t rank_u64) {
+  if (select) return grow_rank_scratch(ix, RankSource::SELECT, keys_u64 + rank_u64);
+  const int rc = grow((void**)&ix->d_sub_keys, &ix->sub_keys_bytes, keys_u64 * sizeof(u64));
+  return rc ? rc : grow_rank_scratch(ix, RankSource::LISTS, rank_u64);
+}
+
+// ... and what their ranking launch leaves to the tail
+static RankSource label_rank_source(const wdbx_index* ix, bool select, size_t keys_u64, uint32_t rank_blocks) {
+  return select ? RankSource{RankSource::SELECT, ix->d_sub_keys + keys_u64, ix->lab_labels, nullptr}
+                : RankSource{RankSource::LISTS, ix->d_partials, rank_blocks, nullptr};
+}
+
 // The full pass for nq host queries, under the handle's mutex, on a non-empty index: per round (distinct_plan) label_keys_kernel
-// (bracketed as a scan launch), label_rank_kernel and merge_kernel over its partial lists, or per query the radix-select chain
-// over its label keys (bracketed as merge launches).  No memset: every item key, list entry and label key is written.
+// (bracketed as a scan launch), label_rank_kernel (a merge launch) and the ranking tail over its partial lists or label keys
+// (enqueue_rank_tail, host_index.h).  No memset: every item key, list entry and label key is written.
 static int distinct_full_pass(wdbx_index* ix, const float* queries, int nq, int k, int normalize_queries, const uint32_t* mask_words,
                               int64_t* out_idx, float* out_score) {
   int rc;
@@ -1072,13 +1050,7 @@ static int distinct_full_pass(wdbx_index* ix, const float* queries, int nq, int 
   const DistinctPlan dp = distinct_plan(ix->lab_items, ix->lab_labels, ix->lab_spans, nq, k, ix->cu_count, ix->opt_select_min_k);
   const size_t elems = (size_t)nq * k;
   if ((rc = ensure_out(ix, elems))) return rc;
-  if ((rc = grow((void**)&ix->d_sub_keys, &ix->sub_keys_bytes, (dp.keys_u64 + (dp.select ? dp.rank_u64 : 0)) * sizeof(u64)))) return rc;
-  if (dp.select) {
-    if ((rc = grow((void**)&ix->d_sel, &ix->sel_bytes, (size_t)WDBX_MAX_K * sizeof(u64)))) return rc;
-    if ((rc = grow((void**)&ix->d_state, &ix->state_bytes, sizeof(SelectState)))) return rc;
-  } else if ((rc = grow((void**)&ix->d_partials, &ix->partials_bytes, dp.rank_u64 * sizeof(u64)))) {
-    return rc;
-  }
+  if ((rc = grow_label_scratch(ix, dp.select, dp.keys_u64, dp.rank_u64))) return rc;
   if ((rc = upload_queries(ix, queries, (uint64_t)nq, normalize_queries))) return rc;
   MaskScope scope(ix);
   if (mask_words && (rc = scope.set(mask_words))) return rc;
@@ -1088,63 +1060,23 @@ static int distinct_full_pass(wdbx_index* ix, const float* queries, int nq, int 
   const bool reg = k <= 128 && !ix->opt_lds_lists;
   const label_rank_fn rfn = pick_label_rank(dp.select ? 2 : (reg ? 1 : 0));
   if (dp.lds >= 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)rfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dp.lds));
-  u64* const d_label_keys = ix->d_sub_keys + dp.keys_u64;  // (select route)
   for (int q0 = 0; q0 < nq; q0 += dp.round) {
     const int b = std::min(dp.round, nq - q0);
-    LabelKeysArgs a = {};
-    a.rows = (const f4*)ix->d_rows;
-    a.queries = (const f4*)(ix->d_q + (size_t)q0 * ix->pitch);
-    a.order = (const uint32_t*)ix->d_lab;
-    a.dense = (const uint32_t*)(ix->d_lab + ix->lab_off_dense);
-    a.span_item0 = (const uint32_t*)(ix->d_lab + ix->lab_off_span);
-    a.mask = ix->active_mask;
-    a.keys = ix->d_sub_keys;
-    a.key_stride = ix->lab_items;
-    a.n = (uint32_t)ix->n;
-    a.n_spans = ix->lab_spans;
-    a.pitch4 = pitch4;
-    a.nq = (uint32_t)b;
     const uint32_t qblocks = (uint32_t)((b + dp.qb - 1) / dp.qb);
-    if ((rc = record(ix->scan_ev, ix->profile, ix->stream, true))) return rc;
-    hipLaunchKernelGGL(kfn, dim3(dp.score_blocks, qblocks), dim3(256), 0, ix->stream, a);
-    HIP_TRY(hipGetLastError());
-    if ((rc = record(ix->scan_ev, ix->profile, ix->stream, false))) return rc;
+    if ((rc = launch_bracketed(ix, ix->scan_ev, kfn, dim3(dp.score_blocks, qblocks), 0, label_keys_args(ix, (uint64_t)q0, (uint32_t)b, pitch4))))
+      return rc;
     LabelRankArgs r = {};
     r.keys = ix->d_sub_keys;
     r.key_stride = ix->lab_items;
     r.label_item0 = (const uint32_t*)(ix->d_lab + ix->lab_off_label);
     r.n_labels = ix->lab_labels;
-    r.out = dp.select ? d_label_keys : ix->d_partials;
+    r.out = dp.select ? ix->d_sub_keys + dp.keys_u64 : ix->d_partials;
     r.k = k;
     if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
     hipLaunchKernelGGL(rfn, dim3(dp.rank_blocks, (uint32_t)b), dim3(256), dp.lds, ix->stream, r);
     HIP_TRY(hipGetLastError());
     if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
-    MergeArgs m = {};
-    m.k = k;
-    m.metric = ix->metric;
-    if (dp.select) {
-      const uint32_t sgrid = radix_select_grid(ix->lab_labels, ix->cu_count);
-      for (int q = 0; q < b; ++q) {
-        if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
-        HIP_TRY(enqueue_radix_select(ix->stream, (const u64*)d_label_keys + (size_t)q * ix->lab_labels, (u64)ix->lab_labels, nullptr,
-                                     (SelectState*)ix->d_state, (u64*)ix->d_sel, (uint32_t)k, sgrid));
-        m.out_idx = ix->d_oidx + (size_t)(q0 + q) * k;
-        m.out_score = ix->d_oscore + (size_t)(q0 + q) * k;
-        HIP_TRY(enqueue_sort_out(ix->stream, (const u64*)ix->d_sel, (const SelectState*)ix->d_state, m));
-        if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
-      }
-      continue;
-    }
-    m.in = ix->d_partials;
-    m.q_stride = (uint64_t)k * dp.rank_blocks;
-    m.i_stride = dp.rank_blocks;
-    m.p_stride = 1;
-    m.P = dp.rank_blocks;
-    m.list_len = k;
-    m.out_idx = ix->d_oidx + (size_t)q0 * k;
-    m.out_score = ix->d_oscore + (size_t)q0 * k;
-    if ((rc = launch_merge(ix, m, b))) return rc;
+    if ((rc = enqueue_rank_tail(ix, label_rank_source(ix, dp.select, dp.keys_u64, dp.rank_blocks), q0, b, k, ix->metric))) return rc;
   }
   return download_results(ix, elems, out_idx, out_score);
 }
@@ -1276,10 +1208,7 @@ static int group_members_pass(wdbx_index* ix, const float* queries, int nq, int 
       a.partial = ix->d_partials;
       a.pitch4 = pitch4;
       a.g = g;
-      if ((rc = record(ix->scan_ev, ix->profile, ix->stream, true))) return rc;
-      hipLaunchKernelGGL(mfn, dim3((uint32_t)r.tasks), dim3(256), 0, ix->stream, a);
-      HIP_TRY(hipGetLastError());
-      if ((rc = record(ix->scan_ev, ix->profile, ix->stream, false))) return rc;
+      if ((rc = launch_bracketed(ix, ix->scan_ev, mfn, dim3((uint32_t)r.tasks), 0, a))) return rc;
     }
     GroupMergeArgs m = {};
     m.partial = ix->d_partials;
@@ -1290,10 +1219,7 @@ static int group_members_pass(wdbx_index* ix, const float* queries, int nq, int 
     m.out_idx = ix->d_oidx + r.slot0 * (size_t)g;
     m.out_score = ix->d_oscore + r.slot0 * (size_t)g;
     m.out_count = d_count + r.slot0;
-    if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
-    hipLaunchKernelGGL(gfn, dim3(r.merge_blocks), dim3(256), 0, ix->stream, m);
-    HIP_TRY(hipGetLastError());
-    if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
+    if ((rc = launch_bracketed(ix, ix->merge_ev, gfn, dim3(r.merge_blocks), 0, m))) return rc;
   }
   ix->last_groups_path = 1;
   ix->last_groups_tasks = (int64_t)tasks.size();
@@ -1421,13 +1347,7 @@ int wdbx_index_search_multivector(wdbx_index* ix, const float* vectors, const ui
   const MultivectorPlan mp = multivector_plan(vector_offsets, nq, ix->lab_items, ix->lab_labels, ix->lab_spans, k, ix->cu_count,
                                               ix->opt_select_min_k, ix->opt_multivector_round_vectors);
   if ((rc = ensure_out(ix, elems))) return rc;
-  if ((rc = grow((void**)&ix->d_sub_keys, &ix->sub_keys_bytes, (mp.keys_u64 + (mp.select ? mp.rank_u64 : 0)) * sizeof(u64)))) return rc;
-  if (mp.select) {
-    if ((rc = grow((void**)&ix->d_sel, &ix->sel_bytes, (size_t)WDBX_MAX_K * sizeof(u64)))) return rc;
-    if ((rc = grow((void**)&ix->d_state, &ix->state_bytes, sizeof(SelectState)))) return rc;
-  } else if ((rc = grow((void**)&ix->d_partials, &ix->partials_bytes, mp.rank_u64 * sizeof(u64)))) {
-    return rc;
-  }
+  if ((rc = grow_label_scratch(ix, mp.select, mp.keys_u64, mp.rank_u64))) return rc;
   const size_t acc_bytes = ((size_t)ix->lab_labels * sizeof(float) + 255) / 256 * 256;
   const size_t seg_bytes = mp.segments.size() * sizeof(MultivectorSegment);
   if ((rc = grow((void**)&ix->d_mv, &ix->mv_bytes, acc_bytes + seg_bytes))) return rc;
@@ -1442,35 +1362,18 @@ int wdbx_index_search_multivector(wdbx_index* ix, const float* vectors, const ui
   const bool reg = k <= 128 && !ix->opt_lds_lists;
   const multivector_rank_fn rfn = pick_multivector_rank(mp.select ? 2 : (reg ? 1 : 0));
   if (mp.lds >= 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)rfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mp.lds));
-  u64* const d_label_keys = ix->d_sub_keys + mp.keys_u64;  // (select route)
   for (const MultivectorRound& r : mp.rounds) {
-    LabelKeysArgs a = {};
-    a.rows = (const f4*)ix->d_rows;
-    a.queries = (const f4*)(ix->d_q + (size_t)r.first * ix->pitch);
-    a.order = (const uint32_t*)ix->d_lab;
-    a.dense = (const uint32_t*)(ix->d_lab + ix->lab_off_dense);
-    a.span_item0 = (const uint32_t*)(ix->d_lab + ix->lab_off_span);
-    a.mask = ix->active_mask;
-    a.keys = ix->d_sub_keys;
-    a.key_stride = ix->lab_items;
-    a.n = (uint32_t)ix->n;
-    a.n_spans = ix->lab_spans;
-    a.pitch4 = pitch4;
-    a.nq = r.vectors;
     const uint32_t vblocks = (r.vectors + (uint32_t)mp.qb - 1) / (uint32_t)mp.qb;
     const uint32_t sblocks = r.vectors == (uint32_t)mp.round_max ? mp.score_blocks
                                                                  : multivector_score_blocks(r.vectors, mp.qb, ix->lab_spans, ix->cu_count);
-    if ((rc = record(ix->scan_ev, ix->profile, ix->stream, true))) return rc;
-    hipLaunchKernelGGL(kfn, dim3(sblocks, vblocks), dim3(256), 0, ix->stream, a);
-    HIP_TRY(hipGetLastError());
-    if ((rc = record(ix->scan_ev, ix->profile, ix->stream, false))) return rc;
+    if ((rc = launch_bracketed(ix, ix->scan_ev, kfn, dim3(sblocks, vblocks), 0, label_keys_args(ix, r.first, r.vectors, pitch4)))) return rc;
     MultivectorRankArgs m = {};
     m.keys = ix->d_sub_keys;
     m.key_stride = ix->lab_items;
     m.label_item0 = (const uint32_t*)(ix->d_lab + ix->lab_off_label);
     m.n_labels = ix->lab_labels;
     m.acc = (float*)ix->d_mv;
-    m.out = mp.select ? d_label_keys : ix->d_partials;
+    m.out = mp.select ? ix->d_sub_keys + mp.keys_u64 : ix->d_partials;
     m.k = k;
     // a first segment that reads the accumulator and a LAST one that writes it must not share a launch: the writer goes second
     const MultivectorSegment& s_first = mp.segments[r.seg0];
@@ -1487,31 +1390,8 @@ int wdbx_index_search_multivector(wdbx_index* ix, const float* vectors, const ui
     }
     if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
     if (!r.ranked) continue;
-    MergeArgs mg = {};
-    mg.k = k;
-    mg.metric = ix->metric;
-    if (mp.select) {
-      const uint32_t sgrid = radix_select_grid(ix->lab_labels, ix->cu_count);
-      for (uint32_t s = 0; s < r.ranked; ++s) {
-        if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
-        HIP_TRY(enqueue_radix_select(ix->stream, (const u64*)d_label_keys + (size_t)s * ix->lab_labels, (u64)ix->lab_labels, nullptr,
-                                     (SelectState*)ix->d_state, (u64*)ix->d_sel, (uint32_t)k, sgrid));
-        mg.out_idx = ix->d_oidx + (size_t)(r.ranked_query0 + s) * k;
-        mg.out_score = ix->d_oscore + (size_t)(r.ranked_query0 + s) * k;
-        HIP_TRY(enqueue_sort_out(ix->stream, (const u64*)ix->d_sel, (const SelectState*)ix->d_state, mg));
-        if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
-      }
-      continue;
-    }
-    mg.in = ix->d_partials;
-    mg.q_stride = (uint64_t)k * mp.rank_blocks;
-    mg.i_stride = mp.rank_blocks;
-    mg.p_stride = 1;
-    mg.P = mp.rank_blocks;
-    mg.list_len = k;
-    mg.out_idx = ix->d_oidx + (size_t)r.ranked_query0 * k;
-    mg.out_score = ix->d_oscore + (size_t)r.ranked_query0 * k;
-    if ((rc = launch_merge(ix, mg, (int)r.ranked))) return rc;
+    const RankSource src = label_rank_source(ix, mp.select, mp.keys_u64, mp.rank_blocks);
+    if ((rc = enqueue_rank_tail(ix, src, (int)r.ranked_query0, (int)r.ranked, k, ix->metric))) return rc;
   }
   if ((rc = download_results(ix, elems, out_idx, out_score))) return rc;
   // label positions -> (smallest row of the label, its stored label)
@@ -1632,10 +1512,7 @@ int wdbx_index_search_mmr(wdbx_index* ix, const float* queries, int nq, int k, i
     sa.lambda = lambda;
     sa.k = k;
     sa.negate = l2 ? 1 : 0;
-    if ((rc = record(ix->merge_ev, ix->profile, ix->stream, true))) return rc;
-    hipLaunchKernelGGL(mmr_select_kernel, dim3(r.nq), dim3(256), 0, ix->stream, sa);
-    HIP_TRY(hipGetLastError());
-    if ((rc = record(ix->merge_ev, ix->profile, ix->stream, false))) return rc;
+    if ((rc = launch_bracketed(ix, ix->merge_ev, mmr_select_kernel, dim3(r.nq), 0, sa))) return rc;
     const size_t o = (size_t)r.q0 * k, e = (size_t)r.nq * k;
     if (out_mmr) HIP_TRY(hipMemcpyAsync(out_mmr + o, d_val, e * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
     if ((rc = download_results(ix, e, out_idx + o, out_score + o))) return rc;  // (waits: the host tables are rebuilt for the next round)
