@@ -1,5 +1,5 @@
 // dispatch_harness.cpp -- drives the device-free slice of the library's host side (wdbx-py_amd/csrc/host_dispatch.h: the
-// shard dispatcher, ordered locking, grow bookkeeping, option lookup, the exception barrier) hard enough for ThreadSanitizer /
+// shard dispatcher, ordered locking, buffer bookkeeping, option lookup, the exception barrier) hard enough for ThreadSanitizer /
 // AddressSanitizer / UBSan to see its hand-overs.  TEST INFRASTRUCTURE: built and run by tests/test_host_dispatch_sanitizers.py
 // with plain g++ (no HIP), never linked into the product.
 //
@@ -114,33 +114,110 @@ static void test_ordered_locks() {
   CHECK(total == 3L * 3000 * H + 5L * 8000);
 }
 
-// ---- 4. grow bookkeeping: sizes, failures, nothing dangling, nothing leaked (ASan watches the heap) ----
+// ---- 4. buffer bookkeeping: sizes, failures, nothing dangling, nothing leaked (ASan watches the heap) ----
 static int g_live = 0;
-static void test_grow() {
-  auto alloc = [](void** np, size_t bytes) -> int {
+struct HeapMem {  // malloc / free that count live blocks and refuse anything above 1 MiB
+  static int alloc(void** np, size_t bytes) {
     if (bytes > (1u << 20)) return fail(WDBX_E_NOMEM, "refused %zu bytes", bytes);
     *np = malloc(bytes);
     ++g_live;
     return *np ? WDBX_OK : WDBX_E_NOMEM;
-  };
-  auto release = [](void* p) -> int {
+  }
+  static int release(void* p) {
     free(p);
     --g_live;
     return WDBX_OK;
-  };
-  void* p = nullptr;
-  size_t have = 0;
-  CHECK(grow_with(&p, &have, 100, alloc, release) == WDBX_OK && p && have == 100);
-  memset(p, 0xAB, 100);
-  void* keep = p;
-  CHECK(grow_with(&p, &have, 64, alloc, release) == WDBX_OK && p == keep && have == 100);  // large enough: untouched
-  CHECK(grow_with(&p, &have, 4096, alloc, release) == WDBX_OK && have == 4096);
-  memset(p, 0xCD, 4096);
-  CHECK(grow_with(&p, &have, 2u << 20, alloc, release) == WDBX_E_NOMEM);                    // refused: the slot is EMPTY,
-  CHECK(p == nullptr && have == 0 && g_live == 0);                                          // not dangling
+  }
+};
+template <class T>
+using HeapBuf = Buf<T, HeapMem>;
+
+static void test_grow() {  // one buffer on its own
+  HeapBuf<char> b;
+  CHECK(b.grow(100) == WDBX_OK && b.p && b.bytes == 100);
+  memset(b, 0xAB, 100);
+  void* keep = b.p;
+  CHECK(b.grow(64) == WDBX_OK && b.p == keep && b.bytes == 100);  // large enough: untouched
+  CHECK(b.grow(4096) == WDBX_OK && b.bytes == 4096);
+  memset(b, 0xCD, 4096);
+  CHECK(b.grow(2u << 20) == WDBX_E_NOMEM);              // refused: the slot is EMPTY,
+  CHECK(b.p == nullptr && b.bytes == 0 && g_live == 0);  // not dangling
   CHECK(g_err.find("refused") != std::string::npos);
-  CHECK(grow_with(&p, &have, 10, alloc, release) == WDBX_OK && have == 10);                 // and usable again
-  release(p);
+  CHECK(b.grow(10) == WDBX_OK && b.bytes == 10);        // and usable again
+  CHECK(b.release() == WDBX_OK);
+  CHECK(g_live == 0);
+}
+
+struct Owner {  // the shape of the handle: the list first, then a line per buffer
+  BufList<HeapMem> bufs;
+  HeapBuf<float> a{&bufs};
+  HeapBuf<uint64_t> b{&bufs};
+  HeapBuf<char> c{&bufs};
+  HeapBuf<void> d{&bufs};
+  HeapBuf<uint32_t> e{&bufs};
+};
+
+static int local_buffer_early_return(bool early) {
+  HeapBuf<double> tmp, never_grown;  // list-less locals free themselves on every way out
+  const int rc = tmp.grow(256);
+  if (rc) return rc;
+  CHECK(g_live == 1);
+  if (early) return WDBX_E_STATE;
+  tmp[0] = 1.0;
+  return WDBX_OK;
+}
+
+static void test_buffers() {
+  Owner o;
+  CHECK(o.bufs.total_bytes() == 0 && g_live == 0);
+  CHECK(o.a.grow(400) == WDBX_OK && o.c.grow(33) == WDBX_OK && o.e.grow(8192) == WDBX_OK);
+  CHECK(o.bufs.total_bytes() == 400 + 33 + 8192 && g_live == 3);
+  o.a[99] = 1.5f;  // (reads and writes through the implicit T*)
+  o.e[2047] = 7u;
+  float* const keep = o.a;
+  CHECK(o.a.grow(400) == WDBX_OK && o.a.grow(1) == WDBX_OK && o.a == keep && o.a[99] == 1.5f);  // need <= bytes: same pointer,
+  CHECK(o.bufs.total_bytes() == 400 + 33 + 8192 && g_live == 3);                                //  same total
+  // a refused allocation: that slot is (nullptr, 0), the total drops by its old size, g_err has the allocator's message
+  g_err.clear();
+  CHECK(o.e.grow(2u << 20) == WDBX_E_NOMEM && o.e.p == nullptr && o.e.bytes == 0);
+  CHECK(o.bufs.total_bytes() == 400 + 33 && g_live == 2);
+  CHECK(g_err.find("refused 2097152 bytes") != std::string::npos);
+  // try_grow: false, the slot empty as well, and the thread's message as it was
+  g_err = "an earlier message";
+  CHECK(!o.c.try_grow(2u << 20) && o.c.p == nullptr && o.c.bytes == 0 && g_err == "an earlier message");
+  CHECK(o.c.try_grow(64) && o.c.bytes == 64 && o.c.try_grow(10) && o.c.bytes == 64 && g_err == "an earlier message");
+  CHECK(o.bufs.total_bytes() == 400 + 64 && g_live == 2);
+  // release of one buffer
+  CHECK(o.a.release() == WDBX_OK && !o.a && o.a.bytes == 0 && o.bufs.total_bytes() == 64 && g_live == 1);
+  CHECK(o.a.release() == WDBX_OK && g_live == 1);
+  // adopt: the owner's buffer takes over a local one's memory (and frees what it held), the local one is left empty
+  CHECK(o.b.grow(16) == WDBX_OK && g_live == 2);
+  {
+    HeapBuf<uint64_t> fresh;
+    CHECK(fresh.grow(800) == WDBX_OK && g_live == 3);
+    void* const mem = fresh.p;
+    CHECK(o.b.adopt(fresh) == WDBX_OK && o.b.p == mem && o.b.bytes == 800 && fresh.p == nullptr && fresh.bytes == 0);
+    CHECK(g_live == 2);
+  }
+  CHECK(g_live == 2 && o.bufs.total_bytes() == 64 + 800);
+  o.b[99] = 3;
+  CHECK(o.d.grow(5) == WDBX_OK && g_live == 3);
+  // release_all: everything freed, every slot empty; a second one finds nothing; the owner is usable again
+  o.bufs.release_all();
+  CHECK(g_live == 0 && o.bufs.total_bytes() == 0);
+  CHECK(!o.a.p && !o.b.p && !o.c.p && !o.d.p && !o.e.p && !o.a.bytes && !o.b.bytes && !o.c.bytes && !o.d.bytes && !o.e.bytes);
+  o.bufs.release_all();
+  CHECK(g_live == 0);
+  CHECK(o.d.grow(12) == WDBX_OK && o.bufs.total_bytes() == 12 && g_live == 1);
+  o.bufs.release_all();
+  CHECK(g_live == 0);
+  // a local buffer frees itself on an early return and on the ordinary one
+  CHECK(local_buffer_early_return(true) == WDBX_E_STATE && g_live == 0);
+  CHECK(local_buffer_early_return(false) == WDBX_OK && g_live == 0);
+  {
+    Owner dies_full;  // (an owner destroyed without release_all: the members' destructors free)
+    CHECK(dies_full.b.grow(24) == WDBX_OK && g_live == 1);
+  }
   CHECK(g_live == 0);
 }
 
@@ -275,10 +352,11 @@ int main(int argc, char** argv) {
   test_start_stop_churn();
   test_ordered_locks();
   test_grow();
+  test_buffers();
   test_options_and_barrier();
   test_two_groups();
   test_slot_pool();
-  printf("harness ok: %d dispatches over %d workers, start/stop churn, ordered locks, grow, options, exception barrier, two groups, slot pool\n",
+  printf("harness ok: %d dispatches over %d workers, start/stop churn, ordered locks, grow, owned buffers, options, exception barrier, two groups, slot pool\n",
          dispatches, workers);
   return 0;
 }

@@ -64,27 +64,87 @@ static int fail(int code, const char* fmt, ...) noexcept {
   catch (...) { (void)fail(WDBX_E_STATE, "internal error: unknown exception"); }
 
 // ------------------------------------------------------------------------------------------------
-// grow-and-free bookkeeping of the scratch buffers: *p holds *have bytes; a larger need frees and re-allocates (contents are
-// scratch).  alloc / release return 0 on success.  After a failed allocation the slot is EMPTY (null, 0), never dangling.
+// The allocations of an owner: Buf<T, Mem> is p and the bytes it holds, and links itself into the owner's BufList when it is
+// constructed with one (`BufList<Mem> bufs;` first, then `Buf<T, Mem> d_x{&bufs};` per buffer), so the owner's total and its
+// release are loops over that list and a new buffer is one line.  Mem supplies `int alloc(void**, size_t)` and
+// `int release(void*)` (0 = success; a failure has left its message with fail()): hipMalloc / hipFree in the library,
+// malloc / free in the harness.  The owner is never copied or moved.
+//   * grow(need): nothing when need <= bytes (one compare), else free, then allocate -- contents are NEVER preserved.  After a
+//     failed allocation the slot is EMPTY (null, 0), never dangling;
+//   * try_grow(need): the same as a bool, for callers with a fallback: the thread's error message stays as it was;
+//   * release(): free and empty;  adopt(from): release, then take over what `from` holds and leave it empty (the rows' reserve:
+//     allocate the new rows in a local buffer, copy, adopt);
+//   * the destructor releases: a local buffer without a list frees itself on every return path.  An owner that must free with
+//     a device current calls bufs.release_all() there, after which the members' destructors find nothing.
 // ------------------------------------------------------------------------------------------------
-template <class Alloc, class Release>
-static int grow_with(void** p, size_t* have, size_t need, Alloc alloc, Release release) {
-  if (need <= *have) return WDBX_OK;
-  if (*p) {
-    const int rc = release(*p);
-    *p = nullptr;
-    *have = 0;
-    if (rc) return rc;
+template <class Mem>
+struct BufBase;
+
+template <class Mem>
+struct BufList {
+  BufBase<Mem>* head = nullptr;
+  size_t total_bytes() const {
+    size_t sum = 0;
+    for (const BufBase<Mem>* b = head; b; b = b->next) sum += b->bytes;
+    return sum;
   }
-  *p = nullptr;
-  *have = 0;
-  void* np = nullptr;
-  const int rc = alloc(&np, need);
-  if (rc) return rc;
-  *p = np;
-  *have = need;
-  return WDBX_OK;
-}
+  void release_all() {
+    for (BufBase<Mem>* b = head; b; b = b->next) (void)b->release();
+  }
+};
+
+template <class Mem>
+struct BufBase {
+  void* p = nullptr;
+  size_t bytes = 0;
+  BufBase* next = nullptr;
+  explicit BufBase(BufList<Mem>* list) {
+    if (!list) return;
+    next = list->head;
+    list->head = this;
+  }
+  BufBase(const BufBase&) = delete;
+  BufBase& operator=(const BufBase&) = delete;
+  ~BufBase() { (void)release(); }
+  int release() {
+    void* const old = p;
+    p = nullptr;
+    bytes = 0;
+    return old ? Mem::release(old) : WDBX_OK;
+  }
+  int grow(size_t need) {
+    if (need <= bytes) return WDBX_OK;
+    int rc = release();
+    if (rc) return rc;
+    void* np = nullptr;
+    if ((rc = Mem::alloc(&np, need))) return rc;
+    p = np;
+    bytes = need;
+    return WDBX_OK;
+  }
+  bool try_grow(size_t need) {
+    if (need <= bytes) return true;
+    std::string keep;
+    keep.swap(g_err);
+    const bool ok = grow(need) == WDBX_OK;
+    keep.swap(g_err);
+    return ok;
+  }
+  int adopt(BufBase& from) {
+    const int rc = release();
+    p = from.p;
+    bytes = from.bytes;
+    from.p = nullptr;
+    from.bytes = 0;
+    return rc;
+  }
+};
+
+template <class T, class Mem>
+struct Buf : BufBase<Mem> {
+  explicit Buf(BufList<Mem>* list = nullptr) : BufBase<Mem>(list) {}
+  operator T*() const { return (T*)this->p; }
+};
 
 // ------------------------------------------------------------------------------------------------
 // several handle mutexes at once, always in the order given (the group passes its shards in shard order and is the only

@@ -36,13 +36,11 @@ constexpr size_t GROUP_STAGE_FLAGS = 80 * sizeof(uint32_t);
 struct GroupShard {
   wdbx_index* ix = nullptr;
   ncclComm_t comm = nullptr;
-  // group-owned buffers on this shard's device
-  float* d_q = nullptr;       // resident queries [q_rows, pitch]
-  size_t q_bytes = 0;
-  u64* d_keys = nullptr;      // this shard's key lists of the current chunk [c, k], global rows
-  size_t keys_bytes = 0;
-  u64* d_gathered = nullptr;  // [S, c, k]: RCCL receive buffer on every shard; COPY: on the root only
-  size_t gathered_bytes = 0;
+  // group-owned buffers on this shard's device (the shards are constructed in place and never moved)
+  DevBufs bufs;
+  DevBuf<float> d_q{&bufs};       // resident queries [q_rows, pitch]
+  DevBuf<u64> d_keys{&bufs};      // this shard's key lists of the current chunk [c, k], global rows
+  DevBuf<u64> d_gathered{&bufs};  // [S, c, k]: RCCL receive buffer on every shard; COPY: on the root only
   hipEvent_t ev = nullptr;    // COPY exchange: "this shard's key lists of the chunk are complete"
   char* stage_dev = nullptr;  // the group's mapped host staging area as this shard's device sees it (null: not mapped)
   bool writes_root = false;   // COPY exchange: this shard's kernels can write the root's gathered buffer directly
@@ -56,9 +54,9 @@ struct wdbx_group {
   bool owns_shards = true;     // false: wdbx_group_attach over handles that live on (the facade's per-shard indices)
   uint64_t q_rows = 0;         // resident queries held in every shard's d_q
   // results of the most recent search, on the root shard's device
-  int64_t* d_oidx = nullptr;
-  float* d_oscore = nullptr;
-  size_t out_elems = 0;
+  DevBufs bufs;
+  DevBuf<int64_t> d_oidx{&bufs};
+  DevBuf<float> d_oscore{&bufs};
   int last_nq = 0, last_k_out = 0;
   // pinned host memory mapped into every shard's device (small blocking searches: the kernels read the queries from and
   // the merge writes the results to host memory directly -- no memcpy calls on the latency path, as in search_host)
@@ -177,13 +175,10 @@ static void group_free(wdbx_group* g) {
     DeviceGuard dg(s.ix->device);
     (void)hipStreamSynchronize(s.ix->stream);
     if (s.comm) (void)ncclCommDestroy(s.comm);
-    if (s.d_q) (void)hipFree(s.d_q);
-    if (s.d_keys) (void)hipFree(s.d_keys);
-    if (s.d_gathered) (void)hipFree(s.d_gathered);
+    s.bufs.release_all();
     if (s.ev) (void)hipEventDestroy(s.ev);
     if (i == 0) {
-      if (g->d_oidx) (void)hipFree(g->d_oidx);
-      if (g->d_oscore) (void)hipFree(g->d_oscore);
+      g->bufs.release_all();
       if (g->h_stage) (void)hipHostFree(g->h_stage);
       if (g->done_ev) (void)hipEventDestroy(g->done_ev);
     }
@@ -246,7 +241,7 @@ static int group_load_queries(wdbx_group* g, const float* host, uint64_t seed, u
     wdbx_index* ix = gs.ix;
     int rc;
     const size_t bytes = (size_t)nq * ix->pitch * sizeof(float);
-    if ((rc = grow((void**)&gs.d_q, &gs.q_bytes, bytes))) return rc;
+    if ((rc = gs.d_q.grow(bytes))) return rc;
     if (host) {
       if ((rc = copy_padded(ix, gs.d_q, host, (uint64_t)nq, ix->dim))) return rc;
       if (normalize && ix->metric == WDBX_METRIC_COSINE && (rc = launch_normalize(ix, gs.d_q, nq))) return rc;
@@ -293,16 +288,9 @@ static int group_enqueue_search(wdbx_group* g, int first, int nq, int k, int k_o
   if (!staged) {
     DeviceGuard dg(root.ix->device);
     const size_t elems = (size_t)nq * k_out;
-    if (elems > g->out_elems) {
+    if (elems * sizeof(int64_t) > g->d_oidx.bytes || elems * sizeof(float) > g->d_oscore.bytes) {
       HIP_TRY(hipStreamSynchronize(root.ix->stream));
-      if (g->d_oidx) HIP_TRY(hipFree(g->d_oidx));
-      if (g->d_oscore) HIP_TRY(hipFree(g->d_oscore));
-      g->d_oidx = nullptr;
-      g->d_oscore = nullptr;
-      g->out_elems = 0;
-      HIP_TRY(hipMalloc((void**)&g->d_oidx, elems * sizeof(int64_t)));
-      HIP_TRY(hipMalloc((void**)&g->d_oscore, elems * sizeof(float)));
-      g->out_elems = elems;
+      if ((rc = g->d_oidx.grow(elems * sizeof(int64_t))) || (rc = g->d_oscore.grow(elems * sizeof(float)))) return rc;
     }
     out_idx = g->d_oidx;
     out_score = g->d_oscore;
@@ -319,7 +307,7 @@ static int group_enqueue_search(wdbx_group* g, int first, int nq, int k, int k_o
       const bool direct = g->exchange == GROUP_EXCHANGE_COPY && (s == 0 || gs.writes_root);
       // (RCCL: d_keys / d_gathered of EVERY shard were sized before the dispatch -- nothing below may fail between "the peers
       // have enqueued the collective" and "this shard enqueues it")
-      if (g->exchange != GROUP_EXCHANGE_RCCL && !direct && (r = grow((void**)&gs.d_keys, &gs.keys_bytes, (size_t)c * k * sizeof(u64)))) return r;
+      if (g->exchange != GROUP_EXCHANGE_RCCL && !direct && (r = gs.d_keys.grow((size_t)c * k * sizeof(u64)))) return r;
       u64* const keys = direct ? g->sh[0].d_gathered + (size_t)s * c * k : gs.d_keys;
       const float* q = staged ? (const float*)gs.stage_dev + (size_t)c0 * ix->pitch : gs.d_q + (size_t)(first + c0) * ix->pitch;
       MaskScope scope(ix, true);  // the mask applies to this enqueue only (the kernels take the pointer at launch)
@@ -365,13 +353,13 @@ static int group_enqueue_search(wdbx_group* g, int first, int nq, int k, int k_o
     };
     if (g->exchange == GROUP_EXCHANGE_COPY) {  // (the root's gathered buffer must exist before any shard writes into it)
       const size_t need = (size_t)S * c * k * sizeof(u64);
-      if (need > root.gathered_bytes)  // growing frees the old one: no shard (a peer device's stream included) may still write it
+      if (need > root.d_gathered.bytes)  // growing frees the old one: no shard (a peer device's stream included) may still write it
         for (int s = 0; s < S; ++s) {
           DeviceGuard ds(g->sh[s].ix->device);
           HIP_TRY(hipStreamSynchronize(g->sh[s].ix->stream));
         }
       DeviceGuard dg(root.ix->device);
-      if ((rc = grow((void**)&root.d_gathered, &root.gathered_bytes, need))) return rc;
+      if ((rc = root.d_gathered.grow(need))) return rc;
     }
     if (g->exchange == GROUP_EXCHANGE_RCCL) {
       // every buffer the collective touches, on every shard, before any shard's thread starts (grow() frees the old
@@ -379,8 +367,8 @@ static int group_enqueue_search(wdbx_group* g, int first, int nq, int k, int k_o
       for (int s = 0; s < S; ++s) {
         GroupShard& gs = g->sh[s];
         DeviceGuard ds(gs.ix->device);
-        if ((rc = grow((void**)&gs.d_keys, &gs.keys_bytes, (size_t)c * k * sizeof(u64)))) return rc;
-        if ((rc = grow((void**)&gs.d_gathered, &gs.gathered_bytes, (size_t)S * c * k * sizeof(u64)))) return rc;
+        if ((rc = gs.d_keys.grow((size_t)c * k * sizeof(u64)))) return rc;
+        if ((rc = gs.d_gathered.grow((size_t)S * c * k * sizeof(u64)))) return rc;
       }
     }
     rc = group_run(g, local);

@@ -12,25 +12,37 @@ struct EventPool {
 
 constexpr int STAGE_SLOTS = 4;
 
+// Device memory of the handle and of the shard group: every allocation is a DevBuf member of its owner (bookkeeping:
+// host_dispatch.h), allocated and freed here and nowhere else.
+struct HipMem {
+  static int alloc(void** p, size_t bytes) {
+    HIP_TRY(hipMalloc(p, bytes));
+    return WDBX_OK;
+  }
+  static int release(void* p) {
+    HIP_TRY(hipFree(p));
+    return WDBX_OK;
+  }
+};
+using DevBufs = BufList<HipMem>;
+template <class T>
+using DevBuf = Buf<T, HipMem>;
+
 struct wdbx_index {
+  DevBufs bufs;  // (first: the DevBuf members below link themselves in; option "device_bytes_resident" is its total)
   int device = 0, dim = 0, pitch = 0, metric = 0;
   int cu_count = 256;
   uint64_t n = 0, cap = 0;
-  float* d_rows = nullptr;
+  DevBuf<float> d_rows{&bufs};
   hipStream_t stream = nullptr;
   std::mutex mu;
   // scratch (grown on demand, reused)
-  u64* d_partials = nullptr;
-  size_t partials_bytes = 0;
-  u64* d_local_keys = nullptr;
-  size_t local_keys_bytes = 0;
-  u64* d_gathered = nullptr;
-  size_t gathered_bytes = 0;
-  float* d_q = nullptr;
-  size_t q_bytes = 0;
-  int64_t* d_oidx = nullptr;
-  float* d_oscore = nullptr;
-  size_t out_elems = 0;
+  DevBuf<u64> d_partials{&bufs};
+  DevBuf<u64> d_local_keys{&bufs};
+  DevBuf<u64> d_gathered{&bufs};
+  DevBuf<float> d_q{&bufs};
+  DevBuf<int64_t> d_oidx{&bufs};
+  DevBuf<float> d_oscore{&bufs};
   // communicator
   ncclComm_t comm = nullptr;
   int nranks = 1, rank = 0;
@@ -44,87 +56,65 @@ struct wdbx_index {
   // waits for the GPU on the slot's event with the handle's mutex released (search_host)
   SlotPool<4> slots;   // (host_dispatch.h; = STAGE_SLOTS)
   hipEvent_t slot_done[4] = {nullptr, nullptr, nullptr, nullptr};
-  u64* d_dump = nullptr;  // one key per row (large-k select)
-  size_t dump_bytes = 0;
-  u64* d_sel = nullptr;
-  size_t sel_bytes = 0;
-  SelectState* d_state = nullptr;
-  size_t state_bytes = 0;
-  uint32_t* d_mask = nullptr;
-  size_t mask_bytes = 0;
+  DevBuf<u64> d_dump{&bufs};  // one key per row (large-k select)
+  DevBuf<u64> d_sel{&bufs};
+  DevBuf<SelectState> d_state{&bufs};
+  DevBuf<uint32_t> d_mask{&bufs};
   const uint32_t* active_mask = nullptr;  // set only for the duration of a masked search (under the mutex)
   uint64_t mask_allowed = 0;              // ... and how many of the rows it allows (popcount of the host mask: set_active_mask)
   // the int8 tiles' bad-row table of ONE masked batch: d_gbad8 | ~mask (gbad_with_mask_kernel); d_gbad8 itself never changes
-  u64* d_call_bad = nullptr;
-  size_t call_bad_bytes = 0;
+  DevBuf<u64> d_call_bad{&bufs};
   int last_batch_masked = 0;              // the last batch ran the masked tile pass (1), or the pass with a mask per query (2)
   // a call with one row mask per query (wdbx_index_search_multimask): its queries in slot order, the slots' queries, its masks
   // and the classes' mask numbers in one scratch allocation; what the last such tile call looked like
-  char* d_mm = nullptr;
-  size_t mm_bytes = 0;
+  DevBuf<char> d_mm{&bufs};
   uint32_t last_batch_classes = 0, last_batch_blocks = 0;
   std::vector<int32_t> last_batch_slot;   // ... and the slot of each of the caller's queries (wdbx_index_batch_status)
   uint64_t last_batch_allowed = 0;        // ... over this many allowed rows
   // batched (GEMM) path scratch
-  float* d_qblock = nullptr;
-  size_t qblock_bytes = 0;
-  u64* d_halfmax = nullptr;
-  size_t halfmax_bytes = 0;
-  float* d_tau = nullptr;
-  size_t tau_bytes = 0;
-  u64* d_cand = nullptr;
-  size_t cand_bytes = 0;
-  uint32_t* d_count = nullptr;
-  size_t count_bytes = 0;
+  DevBuf<float> d_qblock{&bufs};
+  DevBuf<u64> d_halfmax{&bufs};
+  DevBuf<float> d_tau{&bufs};
+  DevBuf<u64> d_cand{&bufs};
+  DevBuf<uint32_t> d_count{&bufs};
   uint32_t last_batch_nq = 0, last_batch_cap = 0;
   bool last_batch_repaired = false;  // the last batch's overflowed queries were repaired on the device (conditional launches)
-  void* d_qb16 = nullptr;  // bf16 tiles: the query block as bf16
-  size_t qb16_bytes = 0;
-  float* d_cn = nullptr;  // L2 / bf16 batched path: squared row norms for rows [0, cn_rows), and their maximum
-  size_t cn_bytes = 0;
+  DevBuf<void> d_qb16{&bufs};  // bf16 tiles: the query block as bf16
+  DevBuf<float> d_cn{&bufs};  // L2 / bf16 batched path: squared row norms for rows [0, cn_rows), and their maximum
   uint64_t cn_rows = 0;
-  void* d_rows16 = nullptr;  // bf16 shadow copy of rows [0, shadow_rows), row pitch pitch16 elements (zero padded)
-  size_t rows16_bytes = 0;
+  DevBuf<void> d_rows16{&bufs};  // bf16 shadow copy of rows [0, shadow_rows), row pitch pitch16 elements (zero padded)
   uint64_t shadow_rows = 0;
   uint32_t pitch16 = 0;
   int last_gemm_mode = 0;  // tile kernel family the last batch ran on (GEMM_FP32 / GEMM_BF16 / GEMM_BF16_SHADOW)
-  uint8_t* d_rows8 = nullptr;  // u8 shadow copy of rows [0, shadow8_rows) for the single-query selection scan, pitch8 bytes
-  float* d_scale8 = nullptr;   // its per-row scales
-  float* d_gmax = nullptr;     // largest squared row norm per 64-row group (selection bounds of the tile kernels)
-  float* d_qn = nullptr;       // |q| per query of a block
-  size_t gmax_bytes = 0, qn_bytes = 0;
+  DevBuf<uint8_t> d_rows8{&bufs};  // u8 shadow copy of rows [0, shadow8_rows) for the single-query selection scan, pitch8 bytes
+  DevBuf<float> d_scale8{&bufs};   // its per-row scales
+  DevBuf<float> d_gmax{&bufs};     // largest squared row norm per 64-row group (selection bounds of the tile kernels)
+  DevBuf<float> d_qn{&bufs};       // |q| per query of a block
   bool gmax_valid = false;
   bool cn_stats_dirty = false; // cached norms were refreshed in place: recompute their statistics before deciding
   bool group_bounds = false;   // per-group bounds (norms vary a lot) or one global bound (they do not: cheaper epilogue)
-  void* d_selsrc = nullptr;    // device-side SelectSrc of the large-k selection epilogue
-  size_t selsrc_bytes = 0;
-  size_t rows8_bytes = 0, scale8_bytes = 0;
+  DevBuf<void> d_selsrc{&bufs};    // device-side SelectSrc of the large-k selection epilogue
   uint64_t shadow8_rows = 0;
   uint32_t pitch8 = 0;
   uint64_t u8_no_room_cap = ~0ull;  // capacity at which the u8 shadow last failed to allocate
   // u6 shadow copy of rows [0, shadow6_rows) for rounds of single queries (kernels_scan6.h): ONE allocation, the six-bit codes
   // in 64-row tiles of units6 units followed by the per-row {s, a} pairs
-  uint32_t* d_rows6 = nullptr;
-  size_t rows6_bytes = 0;
+  DevBuf<uint32_t> d_rows6{&bufs};
   uint64_t shadow6_rows = 0, rows6_tiles = 0;
   uint32_t units6 = 0;
   uint64_t u6_no_room_cap = ~0ull;
-  uint32_t* d_count6 = nullptr;  // its candidate counters (d_count holds the cut's: what the repair launches look at)
-  size_t count6_bytes = 0;
+  DevBuf<uint32_t> d_count6{&bufs};  // its candidate counters (d_count holds the cut's: what the repair launches look at)
   int last_single_u6 = 0;      // 1: the last single-query search selected on the u6 shadow (last_single_path stays 2)
   // the u6 codes once more in two planes (kernels_scan42.h): ONE allocation, the h plane in 64-row tiles of units42 units,
   // the per-row {s, a4} pairs, the l records of lpitch42 dwords per row
-  uint32_t* d_rows42 = nullptr;
-  size_t rows42_bytes = 0;
+  DevBuf<uint32_t> d_rows42{&bufs};
   uint64_t shadow42_rows = 0, rows42_tiles = 0;
   uint32_t units42 = 0;
   uint64_t u42_no_room_cap = ~0ull;
-  uint32_t* d_count42 = nullptr;  // rows that passed the four-bit bound, per query of the last round
-  size_t count42_bytes = 0;
+  DevBuf<uint32_t> d_count42{&bufs};  // rows that passed the four-bit bound, per query of the last round
   int last_single_u42 = 0;     // 1: the last u6 round's full passes ran over the split planes
   int last_u42_share = 0;      // ... the widest group of queries that shared one read of the four-bit plane in the last call (0: none ran)
-  uint32_t* d_q16 = nullptr;   // the round's 16-bit queries as matrix operands, then its U42QConst (u42_query_i16_kernel)
-  size_t q16_bytes = 0;
+  DevBuf<uint32_t> d_q16{&bufs};   // the round's 16-bit queries as matrix operands, then its U42QConst (u42_query_i16_kernel)
   int last_u42_mfma_groups = 0;  // ... the groups of 16 whose full pass ran on the matrix cores in the last call
   uint32_t* defer_flag_dev = nullptr;  // non-null during a blocking call that repairs overflow itself (mapped host word)
   // a lone blocking call through a staging slot: the LAST kernel of its chain writes done_seq into done_flag_dev (a mapped
@@ -133,7 +123,7 @@ struct wdbx_index {
   uint32_t* done_flag_dev = nullptr;
   uint32_t done_seq = 0, lone_seq = 0;
   int done_signals = 0;
-  uint32_t* d_ticket = nullptr;        // merge_kernel's workgroup ticket for that signal when a small batch is merged (zero between launches)
+  DevBuf<uint32_t> d_ticket{&bufs};        // merge_kernel's workgroup ticket for that signal when a small batch is merged (zero between launches)
   // a lone blocking query whose final top-k the HOST takes (search_host): the re-scored candidates' keys and their count go
   // to these mapped host locations and no final merge is launched; lone_cap_max = keys the host area holds
   u64* lone_keys_dev = nullptr;
@@ -142,34 +132,29 @@ struct wdbx_index {
   bool lone_used = false;              // set by the enqueue when it took that form
   int last_single_path = 0;    // 0 fp32 scan, 1 bf16 tiles, 2 u8 scan (what the last single-query search ran on)
   int last_sample_qn = 1;      // queries per workgroup of the last u8 sample launch (1, 3 or 4: scan8_sample4_kernel)
-  uint32_t* d_cnmax = nullptr;
-  size_t cnmax_bytes = 0;
+  DevBuf<uint32_t> d_cnmax{&bufs};
   // group-scaled i8 shadow copy of the rows for the int8 tiles (kernels_tiles8.h): rows [0, shadowg_rows) quantised
-  int8_t* d_rows8g = nullptr;
-  f4* d_groups8 = nullptr;       // per 64-row group {s_g, a_g, b_g, vouch}
-  uint32_t* d_over_list = nullptr;  // {n, q_0 ..}: the overflowed queries of a batch block, for its repair scan (mark_lost_kernel)
-  float* d_gref8 = nullptr;      // {a_ref, b_ref, sum a, sum b} + a counter: the prefilter epilogue's ordinary-group bounds
+  DevBuf<int8_t> d_rows8g{&bufs};
+  DevBuf<f4> d_groups8{&bufs};       // per 64-row group {s_g, a_g, b_g, vouch}
+  DevBuf<uint32_t> d_over_list{&bufs};  // {n, q_0 ..}: the overflowed queries of a batch block, for its repair scan (mark_lost_kernel)
+  DevBuf<float> d_gref8{&bufs};      // {a_ref, b_ref, sum a, sum b} + a counter: the prefilter epilogue's ordinary-group bounds
   bool gref_valid = false;       // (recomputed when the group table changed)
-  u64* d_gbad8 = nullptr;        // per 64-row group: bits of the rows that hold a NaN (removed rows) or lie past the end
-  size_t rows8g_bytes = 0, groups8_bytes = 0;
+  DevBuf<u64> d_gbad8{&bufs};        // per 64-row group: bits of the rows that hold a NaN (removed rows) or lie past the end
   uint64_t shadowg_rows = 0;
   uint64_t shadowg_tail_n = ~0ull;  // the row count for which the groups behind the last row (to the end of its 256-row tile) were last written
   uint32_t pitch8g = 0;
   uint64_t i8g_no_room_cap = ~0ull;
-  int8_t* d_qb8 = nullptr;       // the query block as i8
-  f4* d_qpar = nullptr;          // its per-query parameters
-  size_t qb8_bytes = 0, qpar_bytes = 0;
-  u64* d_pairs = nullptr;        // the tile waves' candidate (query, row) pairs and how many each wave produced
-  uint32_t* d_pair_count = nullptr;
-  size_t pairs_bytes = 0, pair_count_bytes = 0;
+  DevBuf<int8_t> d_qb8{&bufs};       // the query block as i8
+  DevBuf<f4> d_qpar{&bufs};          // its per-query parameters
+  DevBuf<u64> d_pairs{&bufs};        // the tile waves' candidate (query, row) pairs and how many each wave produced
+  DevBuf<uint32_t> d_pair_count{&bufs};
   // range search (wdbx_index_range_search): per-query key buffers of the selection candidates and of the results, their
   // counters ([0, 64) candidates, [64, 128) results) and thresholds ([0, 64) exact, [64, 128) selection scale); the per-query
   // capacities grow to the exact count after an overflow and stay there
-  u64* d_rcand = nullptr;
-  u64* d_rkeys = nullptr;
-  uint32_t* d_rcnt = nullptr;
-  float* d_rthr = nullptr;
-  size_t rcand_bytes = 0, rkeys_bytes = 0, rcnt_bytes = 0, rthr_bytes = 0;
+  DevBuf<u64> d_rcand{&bufs};
+  DevBuf<u64> d_rkeys{&bufs};
+  DevBuf<uint32_t> d_rcnt{&bufs};
+  DevBuf<float> d_rthr{&bufs};
   uint32_t range_cand_cap = 16384, range_out_cap = 16384;
   int last_range_path = 0;     // 0 fp32 range scan, 2 u8 selection scan + exact filter (what the last range search ran on)
   // batched range search (wdbx_index_range_search_batch): its candidates live in d_cand, its pairs in d_pairs, its result keys,
@@ -181,14 +166,12 @@ struct wdbx_index {
   int64_t last_range_batch_blocks = 0, last_range_batch_pairs = 0, last_range_batch_fallback = 0;
   // search among listed rows (wdbx_index_search_rows): the device copy of the call's row list and, on the key routes, one key
   // per listed row and query of a round; the partial lists of the list route live in d_partials
-  uint32_t* d_sub_ids = nullptr;
-  u64* d_sub_keys = nullptr;
-  size_t sub_ids_bytes = 0, sub_keys_bytes = 0;
+  DevBuf<uint32_t> d_sub_ids{&bufs};
+  DevBuf<u64> d_sub_keys{&bufs};
   int last_rows_path = 0;      // 0 nothing launched (empty list), 1 keys + merge, 2 lists + merge, 3 keys + radix select
   // one row list per query (wdbx_index_search_row_lists): the call's work items, then its slots' list lengths; the lists' rows
   // and the round's keys live in d_sub_ids / d_sub_keys
-  char* d_rl = nullptr;
-  size_t rl_bytes = 0;
+  DevBuf<char> d_rl{&bufs};
   int last_lists_path = 0;     // 0 nothing launched, 1 the batched pass only, 2 both, 3 list by list only
   int64_t last_lists_items = 0, last_lists_rounds = 0;
   // distinct search (wdbx_index_search_distinct): the labels of rows [0, labels.size()) on the host (rows behind them are
@@ -196,8 +179,7 @@ struct wdbx_index {
   // rows | dense label of each position | first item of each span | first item of each label.  Rebuilt by the next full pass
   // after a label change (lab_valid) or a row-count change (lab_n).  The pass's keys live in d_sub_keys, its lists in d_partials.
   std::vector<uint32_t> labels;
-  char* d_lab = nullptr;
-  size_t lab_bytes = 0;
+  DevBuf<char> d_lab{&bufs};
   bool lab_valid = false;
   uint64_t lab_n = 0;
   uint32_t lab_items = 0, lab_labels = 0, lab_spans = 0;
@@ -208,34 +190,29 @@ struct wdbx_index {
   // ranked label position is reported as), and one allocation of the call's state: the fp32 accumulator of the query a round
   // boundary cuts, [lab_labels], then the segments of every round (host_multivector.h).  Keys and lists as the distinct search.
   std::vector<uint32_t> lab_row0;
-  char* d_mv = nullptr;
-  size_t mv_bytes = 0;
+  DevBuf<char> d_mv{&bufs};
   int64_t last_multivector_rounds = 0, last_multivector_vectors = 0, last_multivector_labels = 0;
   // MMR search (wdbx_index_search_mmr): one allocation of the largest round's state (host_mmr.h): the query table | the candidates'
   // row numbers | their relevance | the picks' values | the gathered rows | the similarity squares
-  char* d_mmr = nullptr;
-  size_t mmr_bytes = 0;
+  DevBuf<char> d_mmr{&bufs};
   int last_mmr_path = 0;  // 0 nothing launched, 1 ran
   int64_t last_mmr_rounds = 0, last_mmr_candidates = 0;
   // recommend search (wdbx_index_search_recommend): one allocation of the call's tables (host_recommend.h): the example table of
   // every query | that of the short queries | the exclusion list.  The examples live in d_q, keys in d_sub_keys, lists in d_partials.
-  char* d_rec = nullptr;
-  size_t rec_bytes = 0;
+  DevBuf<char> d_rec{&bufs};
   int last_recommend_path = 0;  // 0 nothing launched, 1 favoured pass only, 2 both passes
   int64_t last_recommend_short = 0;
   // discovery search (wdbx_index_search_discover): one allocation of a round's state (host_discover.h): target mode's records (keys |
   // wins) | the zones' counts | the query table | the zone table | the exclusion list.  Vectors in d_q, keys in d_sub_keys, lists
   // in d_partials.
-  char* d_disc = nullptr;
-  size_t disc_bytes = 0;
+  DevBuf<char> d_disc{&bufs};
   int last_discover_path = 0;  // 0 nothing launched, 1 context mode, 2 target mode
   int64_t last_discover_zone_slots = 0;
   // search groups (wdbx_index_search_groups / _group_members): where each dense label's run lies in the label order, on the host
   // (host_groups.h; rebuilt with the label order), and one allocation of a call's tables: the slot table | the round's tasks |
   // the slots' counts.  Queries in d_q, partial lists in d_partials, members in d_oidx / d_oscore.
   LabelRuns lab_runs;
-  char* d_grp = nullptr;
-  size_t grp_bytes = 0;
+  DevBuf<char> d_grp{&bufs};
   int last_groups_path = 0;  // 0 nothing launched, 1 ran
   int64_t last_groups_tasks = 0, last_groups_rounds = 0;
   // profiling
@@ -264,27 +241,13 @@ struct DeviceGuard {
   }
 };
 
-// scratch buffers on the device: grown on demand, contents never preserved (bookkeeping: grow_with, host_dispatch.h)
-static int grow(void** p, size_t* have, size_t need) {
-  return grow_with(
-      p, have, need,
-      [](void** np, size_t bytes) -> int {
-        HIP_TRY(hipMalloc(np, bytes));
-        return WDBX_OK;
-      },
-      [](void* old) -> int {
-        HIP_TRY(hipFree(old));
-        return WDBX_OK;
-      });
-}
-
 // A call's row mask (uint32 words, bit r % 32 of word r / 32 = row r may be returned; the caller has checked that it holds
 // ceil(rows / 32) words): to the handle's one mask buffer, behind the stream's earlier work.  The caller keeps the handle's
 // mutex and resets active_mask at the end of the call.  The allowed rows are counted here, on the host copy (bits past the
 // last row do not count): the batched dispatch sizes its sample by them without asking the device.
 static int set_active_mask(wdbx_index* ix, const uint32_t* mask_words) {
   const size_t words = (size_t)((ix->n + 31) / 32);
-  int rc = grow((void**)&ix->d_mask, &ix->mask_bytes, words * sizeof(uint32_t));
+  int rc = ix->d_mask.grow(words * sizeof(uint32_t));
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(ix->d_mask, mask_words, words * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
   ix->mask_allowed = mask_allowed_rows(mask_words, ix->n);
@@ -331,16 +294,8 @@ static int copy_padded(wdbx_index* ix, float* dst, const float* src, uint64_t n,
 
 // the result buffers of the blocking calls, for at least elems results (contents never preserved)
 static int ensure_out(wdbx_index* ix, size_t elems) {
-  if (elems <= ix->out_elems) return WDBX_OK;
-  if (ix->d_oidx) HIP_TRY(hipFree(ix->d_oidx));
-  if (ix->d_oscore) HIP_TRY(hipFree(ix->d_oscore));
-  ix->d_oidx = nullptr;
-  ix->d_oscore = nullptr;
-  ix->out_elems = 0;
-  HIP_TRY(hipMalloc((void**)&ix->d_oidx, elems * sizeof(int64_t)));
-  HIP_TRY(hipMalloc((void**)&ix->d_oscore, elems * sizeof(float)));
-  ix->out_elems = elems;
-  return WDBX_OK;
+  const int rc = ix->d_oidx.grow(elems * sizeof(int64_t));
+  return rc ? rc : ix->d_oscore.grow(elems * sizeof(float));
 }
 
 // Wait for a lone call's completion word (mapped host memory; the chain's last kernel writes seq behind its results,
@@ -491,10 +446,10 @@ struct RankSource {
 // the scratch of a round: partial lists, or keys and -- on the select route only -- the chain's state
 static int grow_rank_scratch(wdbx_index* ix, RankSource::Form form, size_t scratch_u64) {
   int rc;
-  if (form == RankSource::LISTS) return grow((void**)&ix->d_partials, &ix->partials_bytes, scratch_u64 * sizeof(u64));
-  if ((rc = grow((void**)&ix->d_sub_keys, &ix->sub_keys_bytes, scratch_u64 * sizeof(u64))) || form == RankSource::KEYS) return rc;
-  if ((rc = grow((void**)&ix->d_sel, &ix->sel_bytes, (size_t)WDBX_MAX_K * sizeof(u64)))) return rc;
-  return grow((void**)&ix->d_state, &ix->state_bytes, sizeof(SelectState));
+  if (form == RankSource::LISTS) return ix->d_partials.grow(scratch_u64 * sizeof(u64));
+  if ((rc = ix->d_sub_keys.grow(scratch_u64 * sizeof(u64))) || form == RankSource::KEYS) return rc;
+  if ((rc = ix->d_sel.grow((size_t)WDBX_MAX_K * sizeof(u64)))) return rc;
+  return ix->d_state.grow(sizeof(SelectState));
 }
 
 // The ranking tail of `b` slots: their best k into d_oidx / d_oscore from slot `first` on.  metric: what converts a key's value
@@ -588,44 +543,35 @@ static void final_topk_output(const wdbx_index* ix, MergeArgs* f, u64* keys_out,
   }
 }
 
-// The life cycle of a shadow copy's allocations (u8: codes and scales; u6, u42: one each).  Nothing to do while the shape is
-// the same and every part is large enough.  Else the parts are freed and allocated anew and *shadow_rows restarts at 0;
-// false = no room on the device, remembered per capacity in *no_room_cap so that the next calls do not try again.
+// The life cycle of a shadow copy's allocations (u8: codes and scales; i8 groups: rows, table and bad-row bits; bf16, u6, u42: one
+// each).  SHADOW_KEPT: the shape is the same and every part is large enough, nothing was done.  Else the parts are released,
+// *shadow_rows restarts at 0 and they are allocated anew: SHADOW_FRESH, or SHADOW_NO_ROOM (= 0) with every part released and
+// the capacity remembered in *no_room_cap so that the next calls at this capacity do not try again.
+enum { SHADOW_NO_ROOM = 0, SHADOW_KEPT = 1, SHADOW_FRESH = 2 };
 struct ShadowPart {
-  void** p;
-  size_t* bytes;
+  BufBase<HipMem>* buf;
   size_t need;
 };
-static bool shadow_room(wdbx_index* ix, bool shape_changed, std::initializer_list<ShadowPart> parts, uint64_t* shadow_rows,
-                        uint64_t* no_room_cap) {
+static int shadow_room(wdbx_index* ix, bool shape_changed, std::initializer_list<ShadowPart> parts, uint64_t* shadow_rows,
+                       uint64_t* no_room_cap) {
   bool stale = shape_changed;
-  for (const ShadowPart& s : parts) stale = stale || *s.bytes < s.need;
-  if (!stale) return true;
-  if (*no_room_cap == ix->cap) return false;
-  auto release = [&] {
-    for (const ShadowPart& s : parts) {
-      if (*s.p) (void)hipFree(*s.p);
-      *s.p = nullptr;
-      *s.bytes = 0;
-    }
-  };
-  release();
+  for (const ShadowPart& s : parts) stale = stale || s.buf->bytes < s.need;
+  if (!stale) return SHADOW_KEPT;
+  if (*no_room_cap == ix->cap) return SHADOW_NO_ROOM;
+  for (const ShadowPart& s : parts) (void)s.buf->release();
   *shadow_rows = 0;
   for (const ShadowPart& s : parts) {
-    if (hipMalloc(s.p, s.need) == hipSuccess) continue;
-    (void)hipGetLastError();
-    *s.p = nullptr;
-    release();
+    if (s.buf->try_grow(s.need)) continue;
+    for (const ShadowPart& r : parts) (void)r.buf->release();
     *no_room_cap = ix->cap;
-    return false;
+    return SHADOW_NO_ROOM;
   }
-  for (const ShadowPart& s : parts) *s.bytes = s.need;
-  return true;
+  return SHADOW_FRESH;
 }
 
 // all-gather this rank's key lists [b, k] (global rows) and merge the nranks lists per query
 static int exchange_and_merge(wdbx_index* ix, int b, int k, int64_t* d_out_idx, float* d_out_score) {
-  int rc = grow((void**)&ix->d_gathered, &ix->gathered_bytes, (size_t)ix->nranks * b * k * sizeof(u64));
+  int rc = ix->d_gathered.grow((size_t)ix->nranks * b * k * sizeof(u64));
   if (rc) return rc;
   // per-shard records [b, k] -> [nranks, b, k] on every rank (tiny: latency-bound)
   NCCL_TRY(ncclAllGather(ix->d_local_keys, ix->d_gathered, (size_t)b * k, ncclUint64, ix->comm, ix->stream));
@@ -681,7 +627,7 @@ static int enqueue_search(wdbx_index* ix, const float* d_queries, int nq, int k,
   int rc;
   if (ix->n == 0 && !keys_dst) {
     // empty shard: every local list is empty (the reference returns [] at indexing.py:998)
-    rc = grow((void**)&ix->d_local_keys, &ix->local_keys_bytes, (size_t)batch * k * sizeof(u64));
+    rc = ix->d_local_keys.grow((size_t)batch * k * sizeof(u64));
     if (rc) return rc;
   }
   LaunchPlan lp;
@@ -690,11 +636,11 @@ static int enqueue_search(wdbx_index* ix, const float* d_queries, int nq, int k,
     rc = plan_scan(ix, k, &lp);
     if (rc) return rc;
     if (select) {
-      if ((rc = grow((void**)&ix->d_dump, &ix->dump_bytes, (size_t)ix->n * sizeof(u64)))) return rc;
-      if ((rc = grow((void**)&ix->d_sel, &ix->sel_bytes, (size_t)WDBX_MAX_K * sizeof(u64)))) return rc;
-      if ((rc = grow((void**)&ix->d_state, &ix->state_bytes, sizeof(SelectState)))) return rc;
+      if ((rc = ix->d_dump.grow((size_t)ix->n * sizeof(u64)))) return rc;
+      if ((rc = ix->d_sel.grow((size_t)WDBX_MAX_K * sizeof(u64)))) return rc;
+      if ((rc = ix->d_state.grow(sizeof(SelectState)))) return rc;
     } else {
-      rc = grow((void**)&ix->d_partials, &ix->partials_bytes, (size_t)batch * k * lp.P * sizeof(u64));
+      rc = ix->d_partials.grow((size_t)batch * k * lp.P * sizeof(u64));
       if (rc) return rc;
     }
   }
@@ -704,11 +650,11 @@ static int enqueue_search(wdbx_index* ix, const float* d_queries, int nq, int k,
   const int xch = keys_only ? nq : batch * std::max(1, 1024 / batch);
   if (sharded) {
     if (!keys_dst) {
-      rc = grow((void**)&ix->d_local_keys, &ix->local_keys_bytes, (size_t)std::min(xch, std::max(nq, batch)) * k * sizeof(u64));
+      rc = ix->d_local_keys.grow((size_t)std::min(xch, std::max(nq, batch)) * k * sizeof(u64));
       if (rc) return rc;
     }
     if (!keys_only) {
-      rc = grow((void**)&ix->d_gathered, &ix->gathered_bytes, (size_t)ix->nranks * std::min(xch, std::max(nq, batch)) * k * sizeof(u64));
+      rc = ix->d_gathered.grow((size_t)ix->nranks * std::min(xch, std::max(nq, batch)) * k * sizeof(u64));
       if (rc) return rc;
     }
   }
@@ -731,9 +677,9 @@ static int enqueue_search(wdbx_index* ix, const float* d_queries, int nq, int k,
       ix->last_single_u42 = 0;
       SelectSrc* src = nullptr;
       if (u8) {
-        if ((rc = grow((void**)&ix->d_count, &ix->count_bytes, ((size_t)batch + 2 * GB_N) * sizeof(uint32_t)))) return rc;
-        if ((rc = grow((void**)&ix->d_selsrc, &ix->selsrc_bytes, sizeof(SelectSrc)))) return rc;
-        src = (SelectSrc*)ix->d_selsrc;
+        if ((rc = ix->d_count.grow(((size_t)batch + 2 * GB_N) * sizeof(uint32_t)))) return rc;
+        if ((rc = ix->d_selsrc.grow(sizeof(SelectSrc)))) return rc;
+        src = (SelectSrc*)ix->d_selsrc.p;
       }
       for (int q = 0; q < b; ++q) {
         ScanArgs sa = {};
@@ -743,7 +689,7 @@ static int enqueue_search(wdbx_index* ix, const float* d_queries, int nq, int k,
           sa.only_if_over = ix->d_count;
           sa.over_cap = ix->last_batch_cap;
         }
-        sa.rows = (const f4*)ix->d_rows;
+        sa.rows = (const f4*)ix->d_rows.p;
         sa.query = (const f4*)(d_queries + (size_t)(q0 + q) * ix->pitch);
         sa.partials = ix->d_dump;
         sa.mask = ix->active_mask;
@@ -794,7 +740,7 @@ static int enqueue_search(wdbx_index* ix, const float* d_queries, int nq, int k,
       const bool u42 = u6 && u42_single_eligible(ix) && prepare_u42_shadow(ix);
       ix->last_single_u42 = u42 ? 1 : 0;
       if (shadow) {
-        if ((rc = grow((void**)&ix->d_count, &ix->count_bytes, ((size_t)batch + 2 * GB_N) * sizeof(uint32_t)))) return rc;
+        if ((rc = ix->d_count.grow(((size_t)batch + 2 * GB_N) * sizeof(uint32_t)))) return rc;
         if (u6)
           rc = enqueue_singles_u6(ix, d_queries + (size_t)q0 * ix->pitch, b, k, d_out_idx ? d_out_idx + (size_t)q0 * k : nullptr,
                                   d_out_score ? d_out_score + (size_t)q0 * k : nullptr, sharded ? lkeys : nullptr, u42);
@@ -822,7 +768,7 @@ static int enqueue_search(wdbx_index* ix, const float* d_queries, int nq, int k,
           sa.over_cap = ix->last_batch_cap;
         }
         if (shadow || one_grid) sa.y_partials = (uint32_t)((size_t)k * lp.P);
-        sa.rows = (const f4*)ix->d_rows;
+        sa.rows = (const f4*)ix->d_rows.p;
         sa.query = (const f4*)(d_queries + (size_t)(q0 + q) * ix->pitch);
         sa.partials = ix->d_partials + (size_t)q * k * lp.P;
         sa.mask = ix->active_mask;
@@ -894,7 +840,7 @@ static int enqueue_batch_repair(wdbx_index* ix, const float* qsrc, int nv, int k
     need = (size_t)nv * k * lp.P * sizeof(u64);
     if (need > ((size_t)256 << 20)) go = false;
   }
-  if (go && !ix->d_over_list) HIP_TRY(hipMalloc((void**)&ix->d_over_list, (GB_N + 1) * sizeof(uint32_t)));
+  if (go && (rc = ix->d_over_list.grow((GB_N + 1) * sizeof(uint32_t)))) return rc;
   // (after the exact passes consumed the buffers) a lost pair marks every query of the BLOCK as overflowed -- nobody knows
   // which of them lost a candidate; and the overflowed queries are listed for the repair scan
   if (go || d_lost) {
@@ -903,11 +849,11 @@ static int enqueue_batch_repair(wdbx_index* ix, const float* qsrc, int nv, int k
     HIP_TRY(hipGetLastError());
   }
   if (!go) return WDBX_OK;
-  if ((rc = grow((void**)&ix->d_partials, &ix->partials_bytes, need))) return rc;
+  if ((rc = ix->d_partials.grow(need))) return rc;
   ScanArgs sa = {};
   sa.over_list = ix->d_over_list;
   sa.y_partials = (uint32_t)((size_t)k * lp.P);
-  sa.rows = (const f4*)ix->d_rows;
+  sa.rows = (const f4*)ix->d_rows.p;
   sa.query = (const f4*)qsrc;
   sa.partials = ix->d_partials;
   sa.mask = ix->active_mask;  // (a masked batch: its overflowed queries are repaired by the masked scan)
@@ -995,7 +941,7 @@ static bool prepare_u8_shadow(wdbx_index* ix) {
   if (!sh) return false;
   const uint32_t pitch8 = sh->pieces * 16;
   const size_t need = ((size_t)ix->cap + TILE_PAD_ROWS) * pitch8, need_s = ((size_t)ix->cap + TILE_PAD_ROWS) * sizeof(float);
-  if (!shadow_room(ix, ix->pitch8 != pitch8, {{(void**)&ix->d_rows8, &ix->rows8_bytes, need}, {(void**)&ix->d_scale8, &ix->scale8_bytes, need_s}},
+  if (!shadow_room(ix, ix->pitch8 != pitch8, {{&ix->d_rows8, need}, {&ix->d_scale8, need_s}},
                    &ix->shadow8_rows, &ix->u8_no_room_cap))
     return false;
   ix->pitch8 = pitch8;
@@ -1022,9 +968,9 @@ static bool range_u8_eligible(const wdbx_index* ix) {
 // running maximum / sum / count
 static int ensure_row_norms(wdbx_index* ix) {
   int rc;
-  if ((rc = grow((void**)&ix->d_cnmax, &ix->cnmax_bytes, 4 * sizeof(uint32_t)))) return rc;
-  if (ix->cn_bytes < (size_t)ix->n * sizeof(float)) {
-    if ((rc = grow((void**)&ix->d_cn, &ix->cn_bytes, (size_t)ix->cap * sizeof(float)))) return rc;
+  if ((rc = ix->d_cnmax.grow(4 * sizeof(uint32_t)))) return rc;
+  if (ix->d_cn.bytes < (size_t)ix->n * sizeof(float)) {
+    if ((rc = ix->d_cn.grow((size_t)ix->cap * sizeof(float)))) return rc;
     ix->cn_rows = 0;
   }
   if (ix->cn_rows == 0) HIP_TRY(hipMemsetAsync(ix->d_cnmax, 0, 4 * sizeof(uint32_t), ix->stream));
@@ -1050,7 +996,7 @@ static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, in
   const bool l2 = ix->metric == WDBX_METRIC_L2;
   const uint32_t pitch8 = sh->pieces * 16;
   int rc;
-  if (ix->rows8_bytes < ((size_t)ix->cap + TILE_PAD_ROWS) * pitch8 || ix->pitch8 != pitch8 || ix->shadow8_rows < ix->n)
+  if (ix->d_rows8.bytes < ((size_t)ix->cap + TILE_PAD_ROWS) * pitch8 || ix->pitch8 != pitch8 || ix->shadow8_rows < ix->n)
     return fail(WDBX_E_STATE, "u8 shadow not prepared");
   if (l2 && (rc = ensure_row_norms(ix))) return rc;  // squared fp32 norms of the rows (the 2 w - |c|^2 form)
   // the plan (host_selection.h): sampled 256-row tiles of 4 groups of 64 rows each, as on the tile path; a larger sample for
@@ -1060,10 +1006,10 @@ static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, in
   if (ngroups < (uint32_t)k) return fail(WDBX_E_STATE, "corpus too small for the selection scan at k=%d", k);
   const uint32_t cap = selection_cap(s.expect, 32);
   constexpr int ROUND = 64;  // queries per round at most (the caller hands over `exchange_batch` = 32 queries at a time by default)
-  if ((rc = grow((void**)&ix->d_halfmax, &ix->halfmax_bytes, (size_t)ROUND * ngroups * sizeof(u64)))) return rc;
-  if ((rc = grow((void**)&ix->d_tau, &ix->tau_bytes, (size_t)GB_N * sizeof(float)))) return rc;
-  if ((rc = grow((void**)&ix->d_cand, &ix->cand_bytes, (size_t)ROUND * cap * sizeof(u64)))) return rc;
-  if (ix->count_bytes < ((size_t)nq + GB_N) * sizeof(uint32_t)) return fail(WDBX_E_STATE, "candidate counters not sized by the caller");
+  if ((rc = ix->d_halfmax.grow((size_t)ROUND * ngroups * sizeof(u64)))) return rc;
+  if ((rc = ix->d_tau.grow((size_t)GB_N * sizeof(float)))) return rc;
+  if ((rc = ix->d_cand.grow((size_t)ROUND * cap * sizeof(u64)))) return rc;
+  if (ix->d_count.bytes < ((size_t)nq + GB_N) * sizeof(uint32_t)) return fail(WDBX_E_STATE, "candidate counters not sized by the caller");
   ix->last_batch_nq = (uint32_t)nq;  // (the sample launch resets each query's candidate counter)
   ix->last_batch_cap = cap;
   scan8_fn f0 = l2 ? pick_scan8<0, WDBX_METRIC_L2>(sh->L, sh->QPL) : pick_scan8<0, WDBX_METRIC_COSINE>(sh->L, sh->QPL);
@@ -1087,7 +1033,7 @@ static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, in
     const int nv = std::min(ROUND, nq - q0);
     const float* qsrc = d_queries + (size_t)q0 * ix->pitch;
     Scan8Args a = {};
-    a.rows8 = (const u4v*)ix->d_rows8;
+    a.rows8 = (const u4v*)ix->d_rows8.p;
     a.scale = ix->d_scale8;
     a.cn = ix->d_cn;
     a.n_rows = (uint32_t)ix->n;
@@ -1129,7 +1075,7 @@ static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, in
       // (phase 1 takes the k-th largest sampled lower bound itself)
     } else if (candidates_only) {  // large k: the k-th largest sampled lower bound by radix select (the list kernels are insert-bound)
       if (nv != 1) return fail(WDBX_E_STATE, "large-k selection runs one query per call");
-      if ((rc = grow((void**)&ix->d_state, &ix->state_bytes, sizeof(SelectState)))) return rc;
+      if ((rc = ix->d_state.grow(sizeof(SelectState)))) return rc;
       const uint32_t hgrid = std::min<uint32_t>((ngroups + 255) / 256, (uint32_t)ix->cu_count * 4);
       HIP_TRY(enqueue_radix_select(ix->stream, (const u64*)ix->d_halfmax, (u64)ngroups, nullptr, (SelectState*)ix->d_state, nullptr,
                                    (uint32_t)k, hgrid));
@@ -1172,7 +1118,7 @@ static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, in
     if ((rc = record(ix->gemm_ev, ix->profile, ix->stream, false, (uint32_t)nv))) return rc;
     // exact fp32 scores for the candidates, from the fp32 rows
     hipLaunchKernelGGL(l2 ? rescore_kernel<WDBX_METRIC_L2> : rescore_kernel<WDBX_METRIC_COSINE>, dim3(256, nv), dim3(256), 0,
-                       ix->stream, (const f4*)ix->d_rows, (uint32_t)pitch4, (const f4*)qsrc, ix->d_cand,
+                       ix->stream, (const f4*)ix->d_rows.p, (uint32_t)pitch4, (const f4*)qsrc, ix->d_cand,
                        (const uint32_t*)(ix->d_count + q0), cap, lone ? ix->lone_keys_dev : (u64*)nullptr,
                        lone ? ix->lone_count_dev : (uint32_t*)nullptr);
     HIP_TRY(hipGetLastError());
@@ -1217,7 +1163,7 @@ static bool prepare_u6_shadow(wdbx_index* ix) {
   const uint32_t units = (uint32_t)ix->pitch / 16;
   const uint64_t tiles = ((uint64_t)ix->cap + 63) / 64;
   const size_t need = (size_t)tiles * units * 768 + (size_t)tiles * 64 * sizeof(f2v);
-  if (!shadow_room(ix, ix->units6 != units || ix->rows6_tiles != tiles, {{(void**)&ix->d_rows6, &ix->rows6_bytes, need}}, &ix->shadow6_rows,
+  if (!shadow_room(ix, ix->units6 != units || ix->rows6_tiles != tiles, {{&ix->d_rows6, need}}, &ix->shadow6_rows,
                    &ix->u6_no_room_cap))
     return false;
   ix->units6 = units;
@@ -1248,7 +1194,7 @@ static bool prepare_u42_shadow(wdbx_index* ix) {
   const uint32_t units = (uint32_t)ix->pitch / 32, lpitch = u42_lpitch(units);
   const uint64_t tiles = ((uint64_t)ix->cap + 63) / 64;
   const size_t need = (size_t)tiles * units * 1024 + (size_t)tiles * 64 * sizeof(f2v) + (size_t)tiles * 64 * lpitch * sizeof(uint32_t);
-  if (!shadow_room(ix, ix->units42 != units || ix->rows42_tiles != tiles, {{(void**)&ix->d_rows42, &ix->rows42_bytes, need}},
+  if (!shadow_room(ix, ix->units42 != units || ix->rows42_tiles != tiles, {{&ix->d_rows42, need}},
                    &ix->shadow42_rows, &ix->u42_no_room_cap))
     return false;
   ix->units42 = units;
@@ -1311,14 +1257,14 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
   const uint32_t cap = ix->opt_scan_u6_cap > 0 ? (uint32_t)std::min<int64_t>(ix->opt_scan_u6_cap, 1 << 22) : selection_cap(s.expect, 256);
   constexpr uint32_t cap2 = 4096;  // the cut's short list: a few keys beyond k per segment
   constexpr int ROUND = 64;
-  if ((rc = grow((void**)&ix->d_halfmax, &ix->halfmax_bytes, (size_t)ROUND * ngroups * sizeof(u64)))) return rc;
-  if ((rc = grow((void**)&ix->d_tau, &ix->tau_bytes, (size_t)GB_N * sizeof(float)))) return rc;
-  if ((rc = grow((void**)&ix->d_cand, &ix->cand_bytes, (size_t)ROUND * ((size_t)cap + cap2) * sizeof(u64)))) return rc;
-  if ((rc = grow((void**)&ix->d_count6, &ix->count6_bytes, (size_t)ROUND * sizeof(uint32_t)))) return rc;
-  if (u42 && (rc = grow((void**)&ix->d_count42, &ix->count42_bytes, (size_t)ROUND * sizeof(uint32_t)))) return rc;
+  if ((rc = ix->d_halfmax.grow((size_t)ROUND * ngroups * sizeof(u64)))) return rc;
+  if ((rc = ix->d_tau.grow((size_t)GB_N * sizeof(float)))) return rc;
+  if ((rc = ix->d_cand.grow((size_t)ROUND * ((size_t)cap + cap2) * sizeof(u64)))) return rc;
+  if ((rc = ix->d_count6.grow((size_t)ROUND * sizeof(uint32_t)))) return rc;
+  if (u42 && (rc = ix->d_count42.grow((size_t)ROUND * sizeof(uint32_t)))) return rc;
   const size_t q16_dwords = (size_t)(ROUND / U42_MFMA_GROUP) * u42_mfma_group_dwords(units / 2);
-  if (fm && (rc = grow((void**)&ix->d_q16, &ix->q16_bytes, q16_dwords * 4 + (size_t)ROUND * sizeof(U42QConst)))) return rc;
-  if (ix->count_bytes < ((size_t)nq + GB_N) * sizeof(uint32_t)) return fail(WDBX_E_STATE, "candidate counters not sized by the caller");
+  if (fm && (rc = ix->d_q16.grow(q16_dwords * 4 + (size_t)ROUND * sizeof(U42QConst)))) return rc;
+  if (ix->d_count.bytes < ((size_t)nq + GB_N) * sizeof(uint32_t)) return fail(WDBX_E_STATE, "candidate counters not sized by the caller");
   ix->last_batch_nq = (uint32_t)nq;
   ix->last_batch_cap = cap2;
   u64* const cand2 = ix->d_cand + (size_t)ROUND * cap;
@@ -1447,7 +1393,7 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
     }
     if ((rc = record(ix->gemm_ev, ix->profile, ix->stream, false, (uint32_t)nv))) return rc;
     // exact fp32 scores for the candidates, from the fp32 rows
-    hipLaunchKernelGGL(rescore_kernel<WDBX_METRIC_COSINE>, dim3(256, nv), dim3(256), 0, ix->stream, (const f4*)ix->d_rows,
+    hipLaunchKernelGGL(rescore_kernel<WDBX_METRIC_COSINE>, dim3(256, nv), dim3(256), 0, ix->stream, (const f4*)ix->d_rows.p,
                        (uint32_t)pitch4, (const f4*)qsrc, ix->d_cand, (const uint32_t*)ix->d_count6, cap, (u64*)nullptr,
                        (uint32_t*)nullptr);
     // the cut: per segment of the re-scored keys those that can be among the best k
@@ -1494,33 +1440,17 @@ static bool prepare_i8g_shadow(wdbx_index* ix) {
   const uint32_t pitch8 = i8g_pitch(ix);
   const size_t need = (((size_t)ix->cap + G8_ROWS - 1) / G8_ROWS + 1) * G8_ROWS * pitch8;  // whole tiles (fragment order) + one of slack
   const size_t need_g = (((size_t)ix->cap + TILE_PAD_ROWS + 63) / 64 + 1) * sizeof(f4);
-  if (ix->rows8g_bytes < need || ix->groups8_bytes < need_g || ix->pitch8g != pitch8) {
-    if (ix->i8g_no_room_cap == ix->cap) return false;
-    if (ix->d_rows8g) (void)hipFree(ix->d_rows8g);
-    if (ix->d_groups8) (void)hipFree(ix->d_groups8);
-    if (ix->d_gbad8) (void)hipFree(ix->d_gbad8);
-    ix->d_rows8g = nullptr;
-    ix->d_groups8 = nullptr;
-    ix->d_gbad8 = nullptr;
-    ix->rows8g_bytes = ix->groups8_bytes = 0;
-    ix->shadowg_rows = 0;
-    ix->shadowg_tail_n = ~0ull;
-    if (hipMalloc((void**)&ix->d_rows8g, need) != hipSuccess || hipMalloc((void**)&ix->d_groups8, need_g) != hipSuccess ||
-        hipMalloc((void**)&ix->d_gbad8, need_g / 2) != hipSuccess) {
-      (void)hipGetLastError();
-      if (ix->d_rows8g) (void)hipFree(ix->d_rows8g);
-      if (ix->d_groups8) (void)hipFree(ix->d_groups8);
-      ix->d_rows8g = nullptr;
-      ix->d_groups8 = nullptr;
-      ix->i8g_no_room_cap = ix->cap;
-      return false;
-    }
+  const int room = shadow_room(ix, ix->pitch8g != pitch8, {{&ix->d_rows8g, need}, {&ix->d_groups8, need_g}, {&ix->d_gbad8, need_g / 2}},
+                               &ix->shadowg_rows, &ix->i8g_no_room_cap);
+  if (room != SHADOW_KEPT) ix->shadowg_tail_n = ~0ull;
+  if (room == SHADOW_NO_ROOM) return false;
+  if (room == SHADOW_FRESH) {
     // (the table entries of the pad groups are read by the last tile's waves and must not be garbage that traps: zero;
     // pad groups hold no row: all their bad-row bits set)
-    if (hipMemsetAsync(ix->d_groups8, 0, need_g, ix->stream) != hipSuccess) return false;
-    if (hipMemsetAsync(ix->d_gbad8, 0xFF, need_g / 2, ix->stream) != hipSuccess) return false;
-    ix->rows8g_bytes = need;
-    ix->groups8_bytes = need_g;
+    if (hipMemsetAsync(ix->d_groups8, 0, need_g, ix->stream) != hipSuccess || hipMemsetAsync(ix->d_gbad8, 0xFF, need_g / 2, ix->stream) != hipSuccess) {
+      (void)ix->d_groups8.release();  // (stale again: the next call starts over)
+      return false;
+    }
     ix->pitch8g = pitch8;
   }
   // Groups are (re)quantised up to the END OF THE LAST 256-ROW TILE of the current row count, not just up to the last row's
@@ -1600,24 +1530,15 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
   if (family == GEMM_BF16_SHADOW) {  // the bf16 shadow copy of the rows added since the last batch
     const uint32_t pitch16 = (uint32_t)((ix->pitch + 127) / 128 * 128);  // whole pairs of 64-element chunks
     const size_t need = ((size_t)ix->cap + TILE_PAD_ROWS) * pitch16 * 2;
-    if (ix->rows16_bytes < need || ix->pitch16 != pitch16) {
-      if (ix->d_rows16) (void)hipFree(ix->d_rows16);
-      ix->d_rows16 = nullptr;
-      ix->rows16_bytes = 0;
-      ix->shadow_rows = 0;
-      if (hipMalloc(&ix->d_rows16, need) == hipSuccess) {
-        ix->rows16_bytes = need;
-        ix->pitch16 = pitch16;
-      } else {
-        (void)hipGetLastError();  // no room for the shadow: the same tiles on the fp32 rows
-        family = GEMM_BF16;
-      }
-    }
+    uint64_t every_call = ~0ull;  // (a shadow that found no room is tried again by the next batch: nothing is remembered)
+    const int room = shadow_room(ix, ix->pitch16 != pitch16, {{&ix->d_rows16, need}}, &ix->shadow_rows, &every_call);
+    if (room == SHADOW_FRESH) ix->pitch16 = pitch16;
+    if (room == SHADOW_NO_ROOM) family = GEMM_BF16;  // the same tiles on the fp32 rows
     if (family == GEMM_BF16_SHADOW && ix->shadow_rows < ix->n) {
       const u64 pieces = (ix->n - ix->shadow_rows) * (pitch16 / 8);
       hipLaunchKernelGGL(rows_to_bf16_kernel, dim3((uint32_t)std::min<u64>((pieces + 255) / 256, 1u << 20)), dim3(256), 0,
                          ix->stream, (const float*)ix->d_rows, (u64)ix->shadow_rows, (u64)ix->n, (uint32_t)ix->pitch,
-                         (__bf16*)ix->d_rows16, pitch16);
+                         (__bf16*)ix->d_rows16.p, pitch16);
       HIP_TRY(hipGetLastError());
       ix->shadow_rows = ix->n;
     }
@@ -1634,22 +1555,22 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
   if (s.bounds < (uint32_t)k) return fail(WDBX_E_STATE, "corpus too small for the batched path at k=%d", k);
   const uint32_t cap = selection_cap(s.expect, bf16 ? 32 : 8);
   const size_t pitch4 = ix->pitch / 4;
-  if ((rc = grow((void**)&ix->d_qblock, &ix->qblock_bytes, (size_t)GB_N * ix->pitch * sizeof(float)))) return rc;
-  if ((rc = grow((void**)&ix->d_halfmax, &ix->halfmax_bytes, (size_t)GB_N * rw * sample_tiles * sizeof(u64)))) return rc;
-  if ((rc = grow((void**)&ix->d_tau, &ix->tau_bytes, (size_t)GB_N * sizeof(float)))) return rc;
-  if ((rc = grow((void**)&ix->d_cand, &ix->cand_bytes, (size_t)GB_N * cap * sizeof(u64)))) return rc;
+  if ((rc = ix->d_qblock.grow((size_t)GB_N * ix->pitch * sizeof(float)))) return rc;
+  if ((rc = ix->d_halfmax.grow((size_t)GB_N * rw * sample_tiles * sizeof(u64)))) return rc;
+  if ((rc = ix->d_tau.grow((size_t)GB_N * sizeof(float)))) return rc;
+  if ((rc = ix->d_cand.grow((size_t)GB_N * cap * sizeof(u64)))) return rc;
   if (count_slot < 0) {
-    if ((rc = grow((void**)&ix->d_count, &ix->count_bytes, ((size_t)nq + GB_N) * sizeof(uint32_t)))) return rc;
-  } else if (ix->count_bytes < ((size_t)count_slot + nq + GB_N) * sizeof(uint32_t)) {
+    if ((rc = ix->d_count.grow(((size_t)nq + GB_N) * sizeof(uint32_t)))) return rc;
+  } else if (ix->d_count.bytes < ((size_t)count_slot + nq + GB_N) * sizeof(uint32_t)) {
     return fail(WDBX_E_STATE, "candidate counters not sized by the caller");
   }
   uint32_t* const d_count = ix->d_count + std::max(count_slot, 0);
-  if (sharded && (rc = grow((void**)&ix->d_local_keys, &ix->local_keys_bytes, (size_t)GB_N * k * sizeof(u64)))) return rc;
+  if (sharded && (rc = ix->d_local_keys.grow((size_t)GB_N * k * sizeof(u64)))) return rc;
   HIP_TRY(hipMemsetAsync(d_count, 0, (count_slot < 0 ? (size_t)nq + GB_N : (size_t)nq) * sizeof(uint32_t), ix->stream));
   // bf16 query block: zero padded to the K extent the tile kernel walks (a ring of 4 chunks / a pair of chunks)
   const uint32_t kring = family == GEMM_BF16_SHADOW ? 128u : 64u;
   const uint32_t kpad = (uint32_t)((ix->pitch + kring - 1) / kring * kring);
-  if (bf16 && (rc = grow((void**)&ix->d_qb16, &ix->qb16_bytes, (size_t)GB_N * kpad * 2))) return rc;
+  if (bf16 && (rc = ix->d_qb16.grow((size_t)GB_N * kpad * 2))) return rc;
   if (inexact) {  // squared norms of the rows added since the last such batch (L2 term, and the error margin)
     if ((rc = ensure_row_norms(ix))) return rc;
     // How the selection error is bounded.  Norms all alike (the reference normalises its rows): ONE bound from the
@@ -1676,14 +1597,14 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
       // sends such a group's rows to the exact pass whatever the selection scores say (kernels_tiles.h)
       ix->group_bounds = ix->opt_group_bounds == 1 || !(cmax < INFINITY) || (ix->opt_group_bounds != 0 && !(cmax <= 1.5f * mean));
       if (ix->group_bounds) {
-        if ((rc = grow((void**)&ix->d_gmax, &ix->gmax_bytes, ((size_t)ix->cap + 63) / 64 * sizeof(float)))) return rc;
+        if ((rc = ix->d_gmax.grow(((size_t)ix->cap + 63) / 64 * sizeof(float)))) return rc;
         const uint32_t gblocks = (uint32_t)std::min<uint64_t>(((ix->n + 63) / 64 + 255) / 256, 4096);
         hipLaunchKernelGGL(group_max_kernel, dim3(gblocks), dim3(256), 0, ix->stream, (const float*)ix->d_cn, (u64)ix->n, ix->d_gmax);
         HIP_TRY(hipGetLastError());
       }
       ix->gmax_valid = true;
     }
-    if ((rc = grow((void**)&ix->d_qn, &ix->qn_bytes, (size_t)2 * GB_N * sizeof(float)))) return rc;
+    if ((rc = ix->d_qn.grow((size_t)2 * GB_N * sizeof(float)))) return rc;
   }
   const bool group_bounds = inexact && ix->group_bounds;
   ix->last_batch_nq = (uint32_t)nq;
@@ -1702,7 +1623,7 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
   const bool per_query = count_slot >= 0;
   constexpr int PQ_ROUND = 32;
   if (per_query && !bf16) return fail(WDBX_E_STATE, "single-query passes need the bf16 tiles");
-  if (per_query && (rc = grow((void**)&ix->d_qb16, &ix->qb16_bytes, (size_t)PQ_ROUND * 128 * kpad * 2))) return rc;
+  if (per_query && (rc = ix->d_qb16.grow((size_t)PQ_ROUND * 128 * kpad * 2))) return rc;
   for (int q0 = 0; q0 < nq;) {
     // query block: 256, 128 or 64 wide -- a small batch does not pay for 256 columns (the bf16 tiles: 256 or 128)
     const int rem = nq - q0;
@@ -1722,12 +1643,12 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
     // tau = +inf for padded queries so they never append
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->d_tau, 0x7F800000, GB_N, ix->stream));
     GemmArgs g = {};
-    g.rows = (const f4*)ix->d_rows;
+    g.rows = (const f4*)ix->d_rows.p;
     g.queries = (const f4*)qsrc;
     g.n_rows = (uint32_t)ix->n;
     g.pitch4 = (uint32_t)pitch4;
     if (family == GEMM_BF16_SHADOW) {
-      g.rows = (const f4*)ix->d_rows16;
+      g.rows = (const f4*)ix->d_rows16.p;
       g.pitch4 = ix->pitch16 / 8;
     }
     g.num_tiles = sample_tiles;
@@ -1748,13 +1669,13 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
     const size_t qb_block = (size_t)gbn * kpad;  // bf16 elements per query block
     if (bf16) {
       hipLaunchKernelGGL(queries_to_bf16_kernel, dim3((uint32_t)((passes * qb_block + 255) / 256)), dim3(256), 0, ix->stream, qsrc,
-                         (uint32_t)ix->pitch, (uint32_t)nv, (__bf16*)ix->d_qb16, kpad, (uint32_t)gbn,
+                         (uint32_t)ix->pitch, (uint32_t)nv, (__bf16*)ix->d_qb16.p, kpad, (uint32_t)gbn,
                          (uint32_t)(per_query ? 1 : gbn), (uint32_t)passes);
       HIP_TRY(hipGetLastError());
       g.qb_pitch16 = kpad / 8;
     }
     for (int i = 0; i < passes; ++i) {  // phase 0: maxima of the sampled tiles
-      g.qb16 = bf16 ? (const void*)((const __bf16*)ix->d_qb16 + (size_t)i * qb_block) : nullptr;
+      g.qb16 = bf16 ? (const void*)((const __bf16*)ix->d_qb16.p + (size_t)i * qb_block) : nullptr;
       g.halfmax = ix->d_halfmax + (size_t)i * rw * sample_tiles;
       if (group_bounds) g.qn = ix->d_qn + (per_query ? i : 0);
       if ((rc = launch_gemm<0>(ix, g, ct, family))) return rc;
@@ -1770,7 +1691,7 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
     g.halfmax = nullptr;
     g.cap = cap;
     for (int i = 0; i < passes; ++i) {  // phase 1: every score above the threshold becomes a candidate
-      g.qb16 = bf16 ? (const void*)((const __bf16*)ix->d_qb16 + (size_t)i * qb_block) : nullptr;
+      g.qb16 = bf16 ? (const void*)((const __bf16*)ix->d_qb16.p + (size_t)i * qb_block) : nullptr;
       g.tau = ix->d_tau + i;
       g.cand = ix->d_cand + (size_t)i * cap;
       g.count = d_count + q0 + i;
@@ -1779,7 +1700,7 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
     }
     if (inexact) {  // exact fp32 scores for the selected candidates
       hipLaunchKernelGGL(l2 ? rescore_kernel<WDBX_METRIC_L2> : rescore_kernel<WDBX_METRIC_COSINE>, dim3(64, nv), dim3(256), 0,
-                         ix->stream, (const f4*)ix->d_rows, (uint32_t)pitch4, (const f4*)qsrc, ix->d_cand,
+                         ix->stream, (const f4*)ix->d_rows.p, (uint32_t)pitch4, (const f4*)qsrc, ix->d_cand,
                          (const uint32_t*)(d_count + q0), cap, (u64*)nullptr, (uint32_t*)nullptr);
       HIP_TRY(hipGetLastError());
     }
@@ -1816,7 +1737,8 @@ static int launch_gemm8(wdbx_index* ix, const Gemm8Args& g, int ct, bool masked 
 // shadow copy changed; shared by the top-k batches and the batched range search
 static int ensure_group_ref(wdbx_index* ix) {
   if (ix->gref_valid) return WDBX_OK;
-  if (!ix->d_gref8) HIP_TRY(hipMalloc((void**)&ix->d_gref8, 8 * sizeof(float)));
+  const int rc = ix->d_gref8.grow(8 * sizeof(float));
+  if (rc) return rc;
   HIP_TRY(hipMemsetAsync(ix->d_gref8, 0, 8 * sizeof(float), ix->stream));
   const u64 ngroups = (ix->n + 63) / 64;
   const uint32_t blocks = group_ref_grid(ngroups);
@@ -1895,20 +1817,20 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
   // answered from the candidates, not by a repair scan per query; 16 384 rows = 32 MiB of candidate buffers)
   cap = std::max<uint32_t>(cap, (uint32_t)small_class);
   const size_t pitch4 = ix->pitch / 4;
-  if ((rc = grow((void**)&ix->d_halfmax, &ix->halfmax_bytes, (size_t)GB_N * rw * sample_max * sizeof(u64)))) return rc;
-  if ((rc = grow((void**)&ix->d_tau, &ix->tau_bytes, (size_t)GB_N * sizeof(float)))) return rc;
-  if ((rc = grow((void**)&ix->d_cand, &ix->cand_bytes, (size_t)GB_N * cap * sizeof(u64)))) return rc;
+  if ((rc = ix->d_halfmax.grow((size_t)GB_N * rw * sample_max * sizeof(u64)))) return rc;
+  if ((rc = ix->d_tau.grow((size_t)GB_N * sizeof(float)))) return rc;
+  if ((rc = ix->d_cand.grow((size_t)GB_N * cap * sizeof(u64)))) return rc;
   // (+ 1 word behind the counters: "a wave's pair list overflowed" -- see scatter_pairs_kernel)
-  if ((rc = grow((void**)&ix->d_count, &ix->count_bytes, ((size_t)nq + GB_N + 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ix->d_count.grow(((size_t)nq + GB_N + 1) * sizeof(uint32_t)))) return rc;
   uint32_t* const d_lost = ix->d_count + nq + GB_N;
-  if ((rc = grow((void**)&ix->d_qb8, &ix->qb8_bytes, (size_t)GB_N * pitch8))) return rc;
-  if ((rc = grow((void**)&ix->d_qpar, &ix->qpar_bytes, (size_t)GB_N * sizeof(f4)))) return rc;
+  if ((rc = ix->d_qb8.grow((size_t)GB_N * pitch8))) return rc;
+  if ((rc = ix->d_qpar.grow((size_t)GB_N * sizeof(f4)))) return rc;
   // per-wave candidate pair lists of the full pass: room for 4x the expected share of a wave, at least 2048 pairs
   const uint32_t nwaves = std::min<uint32_t>(tiles, (uint32_t)ix->cu_count) * 8;
   const uint32_t pair_cap = selection_pair_cap(s.expect, nwaves);
-  if ((rc = grow((void**)&ix->d_pairs, &ix->pairs_bytes, (size_t)nwaves * pair_cap * sizeof(u64)))) return rc;
-  if ((rc = grow((void**)&ix->d_pair_count, &ix->pair_count_bytes, (size_t)nwaves * sizeof(uint32_t)))) return rc;
-  if (sharded && (rc = grow((void**)&ix->d_local_keys, &ix->local_keys_bytes, (size_t)GB_N * k * sizeof(u64)))) return rc;
+  if ((rc = ix->d_pairs.grow((size_t)nwaves * pair_cap * sizeof(u64)))) return rc;
+  if ((rc = ix->d_pair_count.grow((size_t)nwaves * sizeof(uint32_t)))) return rc;
+  if (sharded && (rc = ix->d_local_keys.grow((size_t)GB_N * k * sizeof(u64)))) return rc;
   // (the counters of every block, tau and the lost flag are initialised by the block's queries_to_i8_kernel: no memsets)
   ix->last_batch_nq = (uint32_t)nq;
   ix->last_batch_cap = cap;
@@ -1917,10 +1839,10 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
   ix->last_batch_classes = multi ? (uint32_t)mc->plan->classes.size() : 0u;
   ix->last_batch_blocks = multi ? mc->plan->blocks() : 0u;
   const u64* gbad = ix->d_gbad8;
-  const u64 ngroups = ix->groups8_bytes / sizeof(f4);  // (d_gbad8's entries: to the end of the last tile + the pad groups)
+  const u64 ngroups = ix->d_groups8.bytes / sizeof(f4);  // (d_gbad8's entries: to the end of the last tile + the pad groups)
   if (masked || multi) {  // this call's bad-row table(s): one launch over the whole group table (8 bytes per 64 rows), no synchronisation
     const uint32_t rows = multi ? (uint32_t)mc->plan->classes.size() : 1u;
-    if ((rc = grow((void**)&ix->d_call_bad, &ix->call_bad_bytes, (size_t)rows * ngroups * sizeof(u64)))) return rc;
+    if ((rc = ix->d_call_bad.grow((size_t)rows * ngroups * sizeof(u64)))) return rc;
     hipLaunchKernelGGL(gbad_with_mask_kernel, dim3(gbad_with_mask_grid(ngroups), rows), dim3(256), 0, ix->stream, (const u64*)ix->d_gbad8,
                        multi ? mc->d_masks : ix->active_mask, (u64)((ix->n + 31) / 32), ngroups, ix->d_call_bad,
                        (u64)(multi ? mc->mask_stride : 0), multi ? mc->d_class_mask : (const int32_t*)nullptr);
@@ -2028,7 +1950,7 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
     }
     // exact fp32 scores of the kept rows (L2: the direct form sum (c - q)^2)
     hipLaunchKernelGGL(l2 ? rescore_kernel<WDBX_METRIC_L2> : rescore_kernel<WDBX_METRIC_COSINE>, dim3(64, nv), dim3(256), 0, ix->stream,
-                       (const f4*)ix->d_rows, (uint32_t)pitch4, (const f4*)qsrc, ix->d_cand, (const uint32_t*)(ix->d_count + q0), cap,
+                       (const f4*)ix->d_rows.p, (uint32_t)pitch4, (const f4*)qsrc, ix->d_cand, (const uint32_t*)(ix->d_count + q0), cap,
                        (u64*)nullptr, (uint32_t*)nullptr);
     HIP_TRY(hipGetLastError());
     MergeArgs f = final_topk_args(ix, ix->d_cand, cap, ix->d_count + q0, k);
@@ -2082,23 +2004,20 @@ static int launch_fill(wdbx_index* ix, float* d, uint64_t seed, uint64_t row0, u
 static int reserve_locked(wdbx_index* ix, uint64_t cap) {
   if (cap <= ix->cap) return WDBX_OK;
   if (cap >= 0xFFFFFF00ull) return fail(WDBX_E_INVALID, "capacity %llu exceeds the 2^32 - 256 rows one shard can number", (u64)cap);
-  float* nd = nullptr;
   // (+ TILE_PAD_ROWS rows of slack: the 8-wave tile kernels read whole 256-row tiles and mask rows past the end)
   const size_t bytes = ((size_t)cap + TILE_PAD_ROWS) * ix->pitch * sizeof(float);
-  HIP_TRY(hipMalloc((void**)&nd, bytes));
+  DevBuf<float> nd;  // (frees itself unless the handle adopts it)
+  int rc = nd.grow(bytes);
+  if (rc) return rc;
   if (ix->n) {
     hipError_t e = hipMemcpyAsync(nd, ix->d_rows, (size_t)ix->n * ix->pitch * sizeof(float), hipMemcpyDeviceToDevice,
                                   ix->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
-    if (e != hipSuccess) {
-      (void)hipFree(nd);
-      return fail(WDBX_E_HIP, "row copy during reserve failed: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(WDBX_E_HIP, "row copy during reserve failed: %s", hipGetErrorString(e));
   }
-  if (ix->d_rows) HIP_TRY(hipFree(ix->d_rows));
-  ix->d_rows = nd;
+  rc = ix->d_rows.adopt(nd);
   ix->cap = cap;
-  return WDBX_OK;
+  return rc;
 }
 
 static int upload_rows(wdbx_index* ix, uint64_t first, const float* rows, uint64_t n, int normalize) {
@@ -2122,7 +2041,7 @@ static int upload_rows(wdbx_index* ix, uint64_t first, const float* rows, uint64
     const uint64_t e = std::min(end, ix->shadow_rows);
     const u64 pieces = (e - first) * (ix->pitch16 / 8);
     hipLaunchKernelGGL(rows_to_bf16_kernel, dim3((uint32_t)std::min<u64>((pieces + 255) / 256, 1u << 20)), dim3(256), 0, ix->stream,
-                       (const float*)ix->d_rows, (u64)first, (u64)e, (uint32_t)ix->pitch, (__bf16*)ix->d_rows16, ix->pitch16);
+                       (const float*)ix->d_rows, (u64)first, (u64)e, (uint32_t)ix->pitch, (__bf16*)ix->d_rows16.p, ix->pitch16);
     HIP_TRY(hipGetLastError());
   }
   if (first < ix->shadowg_rows && ix->d_rows8g) {  // whole groups: a group's scale depends on all of its rows
@@ -2156,7 +2075,7 @@ static int upload_rows(wdbx_index* ix, uint64_t first, const float* rows, uint64
 // ---- what the blocking entry points share (wdbx_hip.hip) ------------------------------------------------------------
 // nq of the caller's queries (src_pitch floats apart, 0 = dim) into d_q at the row pitch, normalised for cosine when asked
 static int upload_queries(wdbx_index* ix, const float* queries, uint64_t nq, int normalize_queries, int src_pitch = 0) {
-  int rc = grow((void**)&ix->d_q, &ix->q_bytes, (size_t)nq * ix->pitch * sizeof(float));
+  int rc = ix->d_q.grow((size_t)nq * ix->pitch * sizeof(float));
   if (rc || (rc = copy_padded(ix, ix->d_q, queries, nq, src_pitch ? src_pitch : ix->dim))) return rc;
   if (normalize_queries && ix->metric == WDBX_METRIC_COSINE) return launch_normalize(ix, ix->d_q, nq);
   return WDBX_OK;
@@ -2216,8 +2135,8 @@ static int enqueue_recommend_pass(wdbx_index* ix, const RecommendPlan& rp, const
   for (const std::pair<int, int>& r : recommend_rounds(slots, rp.round)) {
     const int q0 = r.first, b = r.second;
     RecommendArgs a = {};
-    a.rows = (const f4*)ix->d_rows;
-    a.examples = (const f4*)ix->d_q;
+    a.rows = (const f4*)ix->d_rows.p;
+    a.examples = (const f4*)ix->d_q.p;
     a.table = d_table + (size_t)q0 * 3;
     a.mask = ix->active_mask;
     a.exclude = d_exclude;
@@ -2250,8 +2169,8 @@ static int recommend_locked(wdbx_index* ix, const float* examples, const uint64_
   if ((rc = ensure_out(ix, elems))) return rc;
   const size_t n_ex = exclude32.size();
   const size_t tab_words = (size_t)nq * 3;
-  if ((rc = grow((void**)&ix->d_rec, &ix->rec_bytes, (2 * tab_words + std::max<size_t>(n_ex, 1)) * sizeof(uint32_t)))) return rc;
-  uint32_t* d_tab = (uint32_t*)ix->d_rec;
+  if ((rc = ix->d_rec.grow((2 * tab_words + std::max<size_t>(n_ex, 1)) * sizeof(uint32_t)))) return rc;
+  uint32_t* d_tab = (uint32_t*)ix->d_rec.p;
   uint32_t* d_tab_short = d_tab + tab_words;
   uint32_t* d_exclude = d_tab_short + tab_words;
   if ((rc = grow_rank_scratch(ix, rp.mode != 2 ? RankSource::LISTS : RankSource::SELECT, rp.scratch_u64))) return rc;
@@ -2315,8 +2234,8 @@ static int discover_locked(wdbx_index* ix, const float* targets, const float* co
   const size_t ztab_at = qtab_at + (size_t)nq * 2 * sizeof(uint32_t);
   const size_t ztab_words = counts_words * 2;
   const size_t ex_at = ztab_at + ztab_words * sizeof(uint32_t);
-  if ((rc = grow((void**)&ix->d_disc, &ix->disc_bytes, ex_at + std::max<size_t>(n_ex, 1) * sizeof(uint32_t)))) return rc;
-  u64* d_rec_key = (u64*)ix->d_disc;
+  if ((rc = ix->d_disc.grow(ex_at + std::max<size_t>(n_ex, 1) * sizeof(uint32_t)))) return rc;
+  u64* d_rec_key = (u64*)ix->d_disc.p;
   uint8_t* d_rec_wins = (uint8_t*)(ix->d_disc + key_bytes);
   uint32_t* d_counts = (uint32_t*)(ix->d_disc + counts_at);
   uint32_t* d_qtab = (uint32_t*)(ix->d_disc + qtab_at);
@@ -2344,8 +2263,8 @@ static int discover_locked(wdbx_index* ix, const float* targets, const float* co
   for (const std::pair<int, int>& r : recommend_rounds(nq, dp.round)) {
     const int q0 = r.first, b = r.second;
     DiscoverArgs a = {};
-    a.rows = (const f4*)ix->d_rows;
-    a.vectors = (const f4*)ix->d_q;
+    a.rows = (const f4*)ix->d_rows.p;
+    a.vectors = (const f4*)ix->d_q.p;
     a.table = d_qtab + (size_t)q0 * 2;
     a.mask = ix->active_mask;
     a.exclude = d_exclude;

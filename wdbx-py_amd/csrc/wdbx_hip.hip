@@ -169,18 +169,7 @@ static_assert(sizeof(GroupTaskDev) == sizeof(GroupTask) && sizeof(GroupTask) == 
 static int drain(EventPool& pool, uint64_t* count, double* ms);
 
 // every device allocation the handle holds: the fp32 rows, each shadow copy with its tables, and the scratch buffers
-static uint64_t device_bytes_resident(const wdbx_index* ix) {
-  uint64_t b = ((uint64_t)ix->cap + TILE_PAD_ROWS) * (uint64_t)ix->pitch * sizeof(float);
-  b += ix->rows16_bytes + ix->rows8_bytes + ix->scale8_bytes + ix->rows8g_bytes + ix->groups8_bytes + ix->groups8_bytes / 2;
-  b += ix->cn_bytes + ix->gmax_bytes + ix->partials_bytes + ix->local_keys_bytes + ix->gathered_bytes + ix->q_bytes;
-  b += (uint64_t)ix->out_elems * 12 + ix->dump_bytes + ix->sel_bytes + ix->state_bytes + ix->mask_bytes + ix->qblock_bytes;
-  b += ix->halfmax_bytes + ix->tau_bytes + ix->cand_bytes + ix->count_bytes + ix->qb16_bytes + ix->qn_bytes + ix->selsrc_bytes;
-  b += ix->qb8_bytes + ix->qpar_bytes + ix->pairs_bytes + ix->pair_count_bytes + ix->cnmax_bytes;
-  b += ix->rcand_bytes + ix->rkeys_bytes + ix->rcnt_bytes + ix->rthr_bytes;
-  b += ix->rows6_bytes + ix->count6_bytes + ix->rows42_bytes + ix->count42_bytes + ix->q16_bytes;
-  b += ix->sub_ids_bytes + ix->sub_keys_bytes + ix->mm_bytes + ix->rl_bytes + ix->lab_bytes + ix->mv_bytes + ix->mmr_bytes + ix->rec_bytes + ix->grp_bytes + ix->disc_bytes;
-  return b;
-}
+static uint64_t device_bytes_resident(const wdbx_index* ix) { return ix->bufs.total_bytes(); }
 
 extern "C" {
 
@@ -251,14 +240,7 @@ void wdbx_index_destroy(wdbx_index* ix) try {
     for (hipEvent_t e : ix->merge_ev.ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : ix->gemm_ev.ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : ix->sample_ev.ev) (void)hipEventDestroy(e);
-    void* bufs[] = {ix->d_rows, ix->d_partials, ix->d_local_keys, ix->d_gathered, ix->d_q, ix->d_oidx, ix->d_oscore,
-                    ix->d_qblock, ix->d_halfmax, ix->d_tau, ix->d_cand, ix->d_count, ix->d_ticket, ix->d_mask, ix->d_dump, ix->d_sel,
-                    ix->d_state, ix->d_cn, ix->d_cnmax, ix->d_qb16, ix->d_rows16, ix->d_rows8, ix->d_scale8, ix->d_selsrc,
-                    ix->d_gmax, ix->d_qn, ix->d_rows8g, ix->d_groups8, ix->d_gbad8, ix->d_gref8, ix->d_over_list, ix->d_qb8,
-                    ix->d_qpar, ix->d_pairs, ix->d_pair_count, ix->d_rcand, ix->d_rkeys, ix->d_rcnt, ix->d_rthr, ix->d_rows6, ix->d_count6, ix->d_rows42, ix->d_count42, ix->d_q16,
-                    ix->d_call_bad, ix->d_sub_ids, ix->d_sub_keys, ix->d_mm, ix->d_rl, ix->d_lab, ix->d_mv, ix->d_mmr, ix->d_rec, ix->d_grp, ix->d_disc};
-    for (void* p : bufs)
-      if (p) (void)hipFree(p);
+    ix->bufs.release_all();
     if (ix->h_stage) (void)hipHostFree(ix->h_stage);
     for (hipEvent_t e : ix->slot_done)
       if (e) (void)hipEventDestroy(e);
@@ -396,25 +378,24 @@ int wdbx_index_compact(wdbx_index* ix, const uint64_t* src_rows, uint64_t n_keep
   HIP_TRY(hipStreamSynchronize(ix->stream));
   if (first_moved < n_keep) {
     const uint64_t chunk = std::max<uint64_t>(1024, (256ull << 20) / ((uint64_t)ix->pitch * sizeof(float)));  // 256 MiB of rows at a time
-    float* d_tmp = nullptr;
-    u64* d_src = nullptr;
+    DevBuf<float> d_tmp;  // (locals: freed on every way out)
+    DevBuf<u64> d_src;
     const uint64_t c_max = std::min(chunk, n_keep - first_moved);
-    HIP_TRY(hipMalloc((void**)&d_tmp, (size_t)c_max * ix->pitch * sizeof(float)));
-    hipError_t e = hipMalloc((void**)&d_src, (size_t)c_max * sizeof(u64));
+    const int rc = d_tmp.grow((size_t)c_max * ix->pitch * sizeof(float));
+    if (rc) return rc;
+    hipError_t e = d_src.try_grow((size_t)c_max * sizeof(u64)) ? hipSuccess : hipErrorOutOfMemory;
     for (uint64_t i0 = first_moved; e == hipSuccess && i0 < n_keep; i0 += chunk) {
       const uint64_t c = std::min(chunk, n_keep - i0);
       e = hipMemcpyAsync(d_src, src_rows + i0, (size_t)c * sizeof(u64), hipMemcpyHostToDevice, ix->stream);
       if (e != hipSuccess) break;
       hipLaunchKernelGGL(gather_rows_kernel, dim3((uint32_t)std::min<uint64_t>((c + 3) / 4, 65536)), dim3(256), 0, ix->stream,
-                         (const f4*)ix->d_rows, (uint32_t)(ix->pitch / 4), (const u64*)d_src, (u64)c, (f4*)d_tmp);
+                         (const f4*)ix->d_rows.p, (uint32_t)(ix->pitch / 4), (const u64*)d_src, (u64)c, (f4*)d_tmp.p);
       e = hipGetLastError();
       if (e == hipSuccess)
         e = hipMemcpyAsync(ix->d_rows + (size_t)i0 * ix->pitch, d_tmp, (size_t)c * ix->pitch * sizeof(float), hipMemcpyDeviceToDevice,
                            ix->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);  // (the host list and the scratch are reused by the next chunk)
     }
-    (void)hipFree(d_tmp);
-    if (d_src) (void)hipFree(d_src);
     if (e != hipSuccess) return fail(WDBX_E_HIP, "compaction failed: %s (the rows behind row %llu are undefined)", hipGetErrorString(e), (u64)first_moved);
   }
   if (!ix->labels.empty()) {  // the labels move with their rows (src_rows is increasing: in place, front to back)
@@ -591,7 +572,7 @@ static int search_host(wdbx_index* ix, const float* queries, int nq, int k, int 
     const bool batch_poll = !defer && narrow && nq > 1 && nq <= 32 && ix->opt_poll_done && !use_select(ix, k);
     if (batch_poll) {
       if (!ix->d_ticket) {
-        HIP_TRY(hipMalloc((void**)&ix->d_ticket, sizeof(uint32_t)));
+        if ((rc = ix->d_ticket.grow(sizeof(uint32_t)))) return rc;
         HIP_TRY(hipMemsetAsync(ix->d_ticket, 0, sizeof(uint32_t), ix->stream));
       }
       over[2] = 0;
@@ -731,7 +712,7 @@ int wdbx_index_search_multimask(wdbx_index* ix, const float* queries, int nq, in
   auto up = [](size_t b) { return (b + 255) / 256 * 256; };
   const size_t off_q = 0, off_slot = up(slots * ix->pitch * sizeof(float)), off_cm = off_slot + up(slots * sizeof(int32_t)),
                off_masks = off_cm + up(rows * sizeof(int32_t)), total = off_masks + rows * stride * sizeof(uint32_t);
-  if ((rc = grow((void**)&ix->d_mm, &ix->mm_bytes, total))) return rc;
+  if ((rc = ix->d_mm.grow(total))) return rc;
   float* const d_slots_q = (float*)(ix->d_mm + off_q);
   int32_t* const d_slot_query = (int32_t*)(ix->d_mm + off_slot);
   int32_t* const d_class_mask = (int32_t*)(ix->d_mm + off_cm);
@@ -749,7 +730,7 @@ int wdbx_index_search_multimask(wdbx_index* ix, const float* queries, int nq, in
   // the queries as in search_host, then into their slots
   if ((rc = ensure_out(ix, slots * (size_t)k)) || (rc = upload_queries(ix, queries, (uint64_t)nq, normalize_queries))) return rc;
   const uint32_t pitch4 = (uint32_t)(ix->pitch / 4);
-  hipLaunchKernelGGL(place_queries_kernel, dim3((uint32_t)((slots * pitch4 + 255) / 256)), dim3(256), 0, ix->stream, (const f4*)ix->d_q,
+  hipLaunchKernelGGL(place_queries_kernel, dim3((uint32_t)((slots * pitch4 + 255) / 256)), dim3(256), 0, ix->stream, (const f4*)ix->d_q.p,
                      (const int32_t*)d_slot_query, pitch4, (uint32_t)slots, (f4*)d_slots_q);
   HIP_TRY(hipGetLastError());
   ix->last_batch_repaired = false;
@@ -813,7 +794,7 @@ static int search_rows_host(wdbx_index* ix, const float* queries, int nq, int k,
   DeviceGuard g(ix->device);
   int rc;
   if ((rc = ensure_out(ix, elems))) return rc;
-  if ((rc = grow((void**)&ix->d_sub_ids, &ix->sub_ids_bytes, (size_t)n_ids * sizeof(uint32_t)))) return rc;
+  if ((rc = ix->d_sub_ids.grow((size_t)n_ids * sizeof(uint32_t)))) return rc;
   const bool lists = sp.route == SUBSET_LISTS;
   const RankSource::Form form = lists ? RankSource::LISTS : sp.route == SUBSET_SELECT ? RankSource::SELECT : RankSource::KEYS;
   if ((rc = grow_rank_scratch(ix, form, sp.scratch_u64))) return rc;
@@ -830,7 +811,7 @@ static int search_rows_host(wdbx_index* ix, const float* queries, int nq, int k,
   for (int q0 = 0; q0 < nq; q0 += sp.round) {
     const int b = std::min(sp.round, nq - q0);
     SubsetArgs a = {};
-    a.rows = (const f4*)ix->d_rows;
+    a.rows = (const f4*)ix->d_rows.p;
     a.queries = (const f4*)(ix->d_q + (size_t)q0 * ix->pitch);
     a.ids = ix->d_sub_ids;
     a.out = lists ? ix->d_partials : ix->d_sub_keys;
@@ -909,10 +890,10 @@ int wdbx_index_search_row_lists(wdbx_index* ix, const float* queries, int nq, in
     size_t key_u64 = 0;
     for (const RowListsRound& r : plan.rounds) key_u64 = std::max(key_u64, (size_t)r.slots * (size_t)r.stride);
     const size_t items_bytes = (plan.items.size() * sizeof(RowListsItem) + 255) / 256 * 256;
-    if ((rc = grow((void**)&ix->d_sub_ids, &ix->sub_ids_bytes, (size_t)plan.pass_ids * sizeof(uint32_t)))) return rc;
-    if ((rc = grow((void**)&ix->d_sub_keys, &ix->sub_keys_bytes, key_u64 * sizeof(u64)))) return rc;
-    if ((rc = grow((void**)&ix->d_rl, &ix->rl_bytes, items_bytes + slots * sizeof(uint32_t)))) return rc;
-    const RowListsItem* const d_items = (const RowListsItem*)ix->d_rl;
+    if ((rc = ix->d_sub_ids.grow((size_t)plan.pass_ids * sizeof(uint32_t)))) return rc;
+    if ((rc = ix->d_sub_keys.grow(key_u64 * sizeof(u64)))) return rc;
+    if ((rc = ix->d_rl.grow(items_bytes + slots * sizeof(uint32_t)))) return rc;
+    const RowListsItem* const d_items = (const RowListsItem*)ix->d_rl.p;
     const uint32_t* const d_len = (const uint32_t*)(ix->d_rl + items_bytes);
     // the queries in slot order, padded to the row pitch (host side: one upload whatever the order)
     std::vector<float> hq(slots * (size_t)ix->pitch);
@@ -928,7 +909,7 @@ int wdbx_index_search_row_lists(wdbx_index* ix, const float* queries, int nq, in
       if (r.items) {  // (a round of empty lists only scores nothing; the ranking below still empties its slots)
         if (r.items > 0x7FFFFFFFull) return fail(WDBX_E_INVALID, "%zu work items in one round", r.items);
         RowListsArgs a = {};
-        a.rows = (const f4*)ix->d_rows;
+        a.rows = (const f4*)ix->d_rows.p;
         a.queries = (const f4*)(ix->d_q + (size_t)r.slot0 * ix->pitch);
         a.ids = ix->d_sub_ids;
         a.items = d_items + r.item0;
@@ -987,7 +968,7 @@ static int ensure_label_order(wdbx_index* ix) {
                off_label = off_span + up(lo.span_item0.size() * sizeof(uint32_t)),
                total = off_label + lo.label_item0.size() * sizeof(uint32_t);
   ix->lab_valid = false;
-  int rc = grow((void**)&ix->d_lab, &ix->lab_bytes, total);
+  int rc = ix->d_lab.grow(total);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(ix->d_lab, lo.rows.data(), rows_b, hipMemcpyHostToDevice, ix->stream));
   HIP_TRY(hipMemcpyAsync(ix->d_lab + off_dense, lo.dense.data(), rows_b, hipMemcpyHostToDevice, ix->stream));
@@ -1010,9 +991,9 @@ static int ensure_label_order(wdbx_index* ix) {
 // what the label calls (distinct, multi-vector) share: label_keys_kernel's arguments for nq queries from first_query on, ...
 static LabelKeysArgs label_keys_args(const wdbx_index* ix, uint64_t first_query, uint32_t nq, uint32_t pitch4) {
   LabelKeysArgs a = {};
-  a.rows = (const f4*)ix->d_rows;
+  a.rows = (const f4*)ix->d_rows.p;
   a.queries = (const f4*)(ix->d_q + (size_t)first_query * ix->pitch);
-  a.order = (const uint32_t*)ix->d_lab;
+  a.order = (const uint32_t*)ix->d_lab.p;
   a.dense = (const uint32_t*)(ix->d_lab + ix->lab_off_dense);
   a.span_item0 = (const uint32_t*)(ix->d_lab + ix->lab_off_span);
   a.mask = ix->active_mask;
@@ -1028,7 +1009,7 @@ static LabelKeysArgs label_keys_args(const wdbx_index* ix, uint64_t first_query,
 // ... their scratch: the item keys in d_sub_keys and behind them, on the select route, a key per label; else the partial lists
 static int grow_label_scratch(wdbx_index* ix, bool select, size_t keys_u64, size_t rank_u64) {
   if (select) return grow_rank_scratch(ix, RankSource::SELECT, keys_u64 + rank_u64);
-  const int rc = grow((void**)&ix->d_sub_keys, &ix->sub_keys_bytes, keys_u64 * sizeof(u64));
+  const int rc = ix->d_sub_keys.grow(keys_u64 * sizeof(u64));
   return rc ? rc : grow_rank_scratch(ix, RankSource::LISTS, rank_u64);
 }
 
@@ -1184,12 +1165,12 @@ static int group_members_pass(wdbx_index* ix, const float* queries, int nq, int 
   auto up = [](size_t b) { return (b + 255) / 256 * 256; };
   const size_t off_tasks = up((n_slots + 1) * sizeof(uint64_t)), off_count = off_tasks + up((size_t)max_tasks * sizeof(GroupTask));
   if ((rc = ensure_out(ix, elems))) return rc;
-  if ((rc = grow((void**)&ix->d_partials, &ix->partials_bytes, (size_t)max_tasks * g * sizeof(u64)))) return rc;
-  if ((rc = grow((void**)&ix->d_grp, &ix->grp_bytes, off_count + n_slots * sizeof(int32_t)))) return rc;
+  if ((rc = ix->d_partials.grow((size_t)max_tasks * g * sizeof(u64)))) return rc;
+  if ((rc = ix->d_grp.grow(off_count + n_slots * sizeof(int32_t)))) return rc;
   if ((rc = upload_queries(ix, queries, (uint64_t)nq, normalize_queries))) return rc;
   MaskScope scope(ix);
   if (mask_words && (rc = scope.set(mask_words))) return rc;
-  u64* const d_slot_task0 = (u64*)ix->d_grp;
+  u64* const d_slot_task0 = (u64*)ix->d_grp.p;
   GroupTaskDev* const d_tasks = (GroupTaskDev*)(ix->d_grp + off_tasks);
   int32_t* const d_count = (int32_t*)(ix->d_grp + off_count);
   HIP_TRY(hipMemcpyAsync(d_slot_task0, slot_task0.data(), (n_slots + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ix->stream));
@@ -1200,9 +1181,9 @@ static int group_members_pass(wdbx_index* ix, const float* queries, int nq, int 
     if (r.tasks) {
       HIP_TRY(hipMemcpyAsync(d_tasks, tasks.data() + r.task0, (size_t)r.tasks * sizeof(GroupTask), hipMemcpyHostToDevice, ix->stream));
       GroupMembersArgs a = {};
-      a.rows = (const f4*)ix->d_rows;
-      a.queries = (const f4*)ix->d_q;
-      a.order = ix->lab_valid ? (const uint32_t*)ix->d_lab : nullptr;
+      a.rows = (const f4*)ix->d_rows.p;
+      a.queries = (const f4*)ix->d_q.p;
+      a.order = ix->lab_valid ? (const uint32_t*)ix->d_lab.p : nullptr;
       a.mask = ix->active_mask;
       a.tasks = d_tasks;
       a.partial = ix->d_partials;
@@ -1350,7 +1331,7 @@ int wdbx_index_search_multivector(wdbx_index* ix, const float* vectors, const ui
   if ((rc = grow_label_scratch(ix, mp.select, mp.keys_u64, mp.rank_u64))) return rc;
   const size_t acc_bytes = ((size_t)ix->lab_labels * sizeof(float) + 255) / 256 * 256;
   const size_t seg_bytes = mp.segments.size() * sizeof(MultivectorSegment);
-  if ((rc = grow((void**)&ix->d_mv, &ix->mv_bytes, acc_bytes + seg_bytes))) return rc;
+  if ((rc = ix->d_mv.grow(acc_bytes + seg_bytes))) return rc;
   const MultivectorSegment* const d_segs = (const MultivectorSegment*)(ix->d_mv + acc_bytes);
   HIP_TRY(hipMemcpyAsync(ix->d_mv + acc_bytes, mp.segments.data(), seg_bytes, hipMemcpyHostToDevice, ix->stream));
   if ((rc = upload_queries(ix, vectors, total, normalize_queries))) return rc;
@@ -1372,7 +1353,7 @@ int wdbx_index_search_multivector(wdbx_index* ix, const float* vectors, const ui
     m.key_stride = ix->lab_items;
     m.label_item0 = (const uint32_t*)(ix->d_lab + ix->lab_off_label);
     m.n_labels = ix->lab_labels;
-    m.acc = (float*)ix->d_mv;
+    m.acc = (float*)ix->d_mv.p;
     m.out = mp.select ? ix->d_sub_keys + mp.keys_u64 : ix->d_partials;
     m.k = k;
     // a first segment that reads the accumulator and a LAST one that writes it must not share a launch: the writer goes second
@@ -1460,7 +1441,7 @@ int wdbx_index_search_mmr(wdbx_index* ix, const float* queries, int nq, int k, i
   const size_t off_cand = up(max_nq * sizeof(MmrQuery)), off_rel = off_cand + up(max_rows * sizeof(u64)),
                off_val = off_rel + up(max_rows * sizeof(float)), off_rows = off_val + up(max_nq * (size_t)k * sizeof(float)),
                off_g = off_rows + up(max_rows * (size_t)pitch4 * sizeof(f4)), need = off_g + up(max_g * sizeof(float));
-  if ((rc = grow((void**)&ix->d_mmr, &ix->mmr_bytes, need))) return rc;
+  if ((rc = ix->d_mmr.grow(need))) return rc;
   if ((rc = ensure_out(ix, max_nq * (size_t)k))) return rc;
   const mmr_pairs_fn pfn = pick_mmr_pairs(ix->metric, pitch4);
   std::vector<MmrQuery> table;
@@ -1477,7 +1458,7 @@ int wdbx_index_search_mmr(wdbx_index* ix, const float* queries, int nq, int k, i
         rel.push_back(l2 ? -fs[at + c] : fs[at + c]);
       }
     }
-    const MmrQuery* const d_table = (const MmrQuery*)ix->d_mmr;
+    const MmrQuery* const d_table = (const MmrQuery*)ix->d_mmr.p;
     u64* const d_cand = (u64*)(ix->d_mmr + off_cand);
     float* const d_rel = (float*)(ix->d_mmr + off_rel);
     float* const d_val = (float*)(ix->d_mmr + off_val);
@@ -1488,7 +1469,7 @@ int wdbx_index_search_mmr(wdbx_index* ix, const float* queries, int nq, int k, i
       HIP_TRY(hipMemcpyAsync(d_cand, cand.data(), cand.size() * sizeof(u64), hipMemcpyHostToDevice, ix->stream));
       HIP_TRY(hipMemcpyAsync(d_rel, rel.data(), rel.size() * sizeof(float), hipMemcpyHostToDevice, ix->stream));
       if ((rc = record(ix->scan_ev, ix->profile, ix->stream, true))) return rc;
-      hipLaunchKernelGGL(gather_rows_kernel, dim3(mmr_gather_grid(r.rows)), dim3(256), 0, ix->stream, (const f4*)ix->d_rows, pitch4,
+      hipLaunchKernelGGL(gather_rows_kernel, dim3(mmr_gather_grid(r.rows)), dim3(256), 0, ix->stream, (const f4*)ix->d_rows.p, pitch4,
                          (const u64*)d_cand, (u64)r.rows, d_gathered);
       HIP_TRY(hipGetLastError());
       MmrPairsArgs pa = {};
@@ -1639,8 +1620,8 @@ static int range_search_locked(wdbx_index* ix, const float* queries, int nq, con
   if (u8 && l2 && (rc = ensure_row_norms(ix))) return rc;
   ix->last_range_path = u8 ? 2 : 0;
   constexpr int ROUND = 64;
-  if ((rc = grow((void**)&ix->d_rcnt, &ix->rcnt_bytes, 2 * ROUND * sizeof(uint32_t)))) return rc;
-  if ((rc = grow((void**)&ix->d_rthr, &ix->rthr_bytes, 2 * ROUND * sizeof(float)))) return rc;
+  if ((rc = ix->d_rcnt.grow(2 * ROUND * sizeof(uint32_t)))) return rc;
+  if ((rc = ix->d_rthr.grow(2 * ROUND * sizeof(float)))) return rc;
   const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
   const Scan8Shape* sh = u8 ? scan8_shape((uint32_t)ix->dim) : nullptr;
   const scan8_fn f2 = !u8 ? nullptr : l2 ? pick_scan8<2, WDBX_METRIC_L2>(sh->L, sh->QPL) : pick_scan8<2, WDBX_METRIC_COSINE>(sh->L, sh->QPL);
@@ -1668,11 +1649,11 @@ static int range_search_locked(wdbx_index* ix, const float* queries, int nq, con
     HIP_TRY(hipMemcpyAsync(ix->d_rthr, hthr.data(), 2 * ROUND * sizeof(float), hipMemcpyHostToDevice, ix->stream));
     auto enqueue_select = [&]() -> int {  // u8 path: the candidates
       const uint32_t cap = ix->range_cand_cap;
-      int rc2 = grow((void**)&ix->d_rcand, &ix->rcand_bytes, (size_t)nv * cap * sizeof(u64));
+      int rc2 = ix->d_rcand.grow((size_t)nv * cap * sizeof(u64));
       if (rc2) return rc2;
       HIP_TRY(hipMemsetAsync(ix->d_rcnt, 0, (size_t)nv * sizeof(uint32_t), ix->stream));
       Scan8Args a = {};
-      a.rows8 = (const u4v*)ix->d_rows8;
+      a.rows8 = (const u4v*)ix->d_rows8.p;
       a.scale = ix->d_scale8;
       a.cn = ix->d_cn;
       a.query = (const f4*)dq;
@@ -1693,11 +1674,11 @@ static int range_search_locked(wdbx_index* ix, const float* queries, int nq, con
     };
     auto enqueue_out = [&]() -> int {  // the exact pass: result keys
       const uint32_t cap = u8 ? ix->range_cand_cap : ix->range_out_cap;  // (u8: results <= candidates, never past the buffer)
-      int rc2 = grow((void**)&ix->d_rkeys, &ix->rkeys_bytes, (size_t)nv * cap * sizeof(u64));
+      int rc2 = ix->d_rkeys.grow((size_t)nv * cap * sizeof(u64));
       if (rc2) return rc2;
       HIP_TRY(hipMemsetAsync(ix->d_rcnt + ROUND, 0, (size_t)nv * sizeof(uint32_t), ix->stream));
       RangeArgs r = {};
-      r.rows = (const f4*)ix->d_rows;
+      r.rows = (const f4*)ix->d_rows.p;
       r.queries = (const f4*)dq;
       r.thr = ix->d_rthr;
       r.mask = ix->active_mask;
@@ -1799,14 +1780,14 @@ static int range_batch_block(wdbx_index* ix, const RangeBatchBlock& b, int stage
   const float* qsrc = ix->d_q + (size_t)(b.q0 - staged_q0) * ix->pitch;
   constexpr int MB = RANGE_BATCH_MAX_BLOCK;
   const RangeBatchSizes sz = range_batch_sizes(b, ix->range_batch_cap, pair_cap, nwaves, pitch8);
-  if ((rc = grow((void**)&ix->d_qb8, &ix->qb8_bytes, sz.qb8_bytes))) return rc;
-  if ((rc = grow((void**)&ix->d_qpar, &ix->qpar_bytes, sz.qpar_bytes))) return rc;
-  if ((rc = grow((void**)&ix->d_tau, &ix->tau_bytes, sz.tau_bytes))) return rc;
-  if ((rc = grow((void**)&ix->d_count, &ix->count_bytes, sz.count_bytes))) return rc;
-  if ((rc = grow((void**)&ix->d_pairs, &ix->pairs_bytes, sz.pairs_bytes))) return rc;
-  if ((rc = grow((void**)&ix->d_pair_count, &ix->pair_count_bytes, sz.pair_count_bytes))) return rc;
-  if ((rc = grow((void**)&ix->d_rcnt, &ix->rcnt_bytes, sz.rcnt_bytes))) return rc;
-  if ((rc = grow((void**)&ix->d_rthr, &ix->rthr_bytes, sz.thr_bytes))) return rc;
+  if ((rc = ix->d_qb8.grow(sz.qb8_bytes))) return rc;
+  if ((rc = ix->d_qpar.grow(sz.qpar_bytes))) return rc;
+  if ((rc = ix->d_tau.grow(sz.tau_bytes))) return rc;
+  if ((rc = ix->d_count.grow(sz.count_bytes))) return rc;
+  if ((rc = ix->d_pairs.grow(sz.pairs_bytes))) return rc;
+  if ((rc = ix->d_pair_count.grow(sz.pair_count_bytes))) return rc;
+  if ((rc = ix->d_rcnt.grow(sz.rcnt_bytes))) return rc;
+  if ((rc = ix->d_rthr.grow(sz.thr_bytes))) return rc;
   uint32_t* const d_lost = ix->d_count + MB;
   // the exact thresholds [0, 256) and the selection thresholds [256, 512)
   std::vector<float> hthr(2 * MB, INFINITY);
@@ -1853,13 +1834,13 @@ static int range_batch_block(wdbx_index* ix, const RangeBatchBlock& b, int stage
     const uint32_t cap = ix->range_batch_cap;
     const RangeBatchSizes s2 = range_batch_sizes(b, cap, pair_cap, nwaves, pitch8);
     int rc2;
-    if ((rc2 = grow((void**)&ix->d_cand, &ix->cand_bytes, s2.cand_bytes))) return rc2;
-    if ((rc2 = grow((void**)&ix->d_rkeys, &ix->rkeys_bytes, s2.keys_bytes))) return rc2;
+    if ((rc2 = ix->d_cand.grow(s2.cand_bytes))) return rc2;
+    if ((rc2 = ix->d_rkeys.grow(s2.keys_bytes))) return rc2;
     hipLaunchKernelGGL(scatter_pairs_kernel, dim3((nwaves + SCATTER_LISTS - 1) / SCATTER_LISTS), dim3(1024), 0, ix->stream,
                        (const u64*)ix->d_pairs, (const uint32_t*)ix->d_pair_count, nwaves, pair_cap, ix->d_cand, ix->d_count, cap, d_lost);
     HIP_TRY(hipGetLastError());
     RangeArgs r = {};
-    r.rows = (const f4*)ix->d_rows;
+    r.rows = (const f4*)ix->d_rows.p;
     r.queries = (const f4*)qsrc;
     r.thr = ix->d_rthr;
     r.n_rows = (uint32_t)ix->n;
@@ -1960,8 +1941,8 @@ int wdbx_index_range_search_batch(wdbx_index* ix, const float* queries, int nq, 
   bool staged = true;
   const u64* gbad = ix->d_gbad8;
   if (mask_words) {  // this call's bad-row table: removed rows, rows past the end, rows the mask leaves out
-    const u64 ngroups = ix->groups8_bytes / sizeof(f4);
-    if ((rc = grow((void**)&ix->d_call_bad, &ix->call_bad_bytes, (size_t)ngroups * sizeof(u64)))) return rc;
+    const u64 ngroups = ix->d_groups8.bytes / sizeof(f4);
+    if ((rc = ix->d_call_bad.grow((size_t)ngroups * sizeof(u64)))) return rc;
     hipLaunchKernelGGL(gbad_with_mask_kernel, dim3(gbad_with_mask_grid(ngroups), 1), dim3(256), 0, ix->stream, (const u64*)ix->d_gbad8,
                        (const uint32_t*)ix->active_mask, (u64)((ix->n + 31) / 32), ngroups, ix->d_call_bad, (u64)0, (const int32_t*)nullptr);
     HIP_TRY(hipGetLastError());
@@ -2018,11 +1999,7 @@ int wdbx_index_range_search_batch(wdbx_index* ix, const float* queries, int nq, 
   if (ix->range_batch_cap > RANGE_BATCH_KEEP_CAP) {
     ix->range_batch_cap = RANGE_BATCH_KEEP_CAP;
     HIP_TRY(hipStreamSynchronize(ix->stream));
-    if (ix->d_cand) HIP_TRY(hipFree(ix->d_cand));
-    if (ix->d_rkeys) HIP_TRY(hipFree(ix->d_rkeys));
-    ix->d_cand = nullptr;
-    ix->d_rkeys = nullptr;
-    ix->cand_bytes = ix->rkeys_bytes = 0;
+    if ((rc = ix->d_cand.release()) || (rc = ix->d_rkeys.release())) return rc;
   }
   ix->last_range_batch_path = tally.path();
   ix->last_range_batch_blocks = tally.blocks;
@@ -2260,7 +2237,7 @@ int wdbx_index_probe_read(wdbx_index* ix, int nontemporal, int blocks, int reps,
   std::lock_guard<std::mutex> lk(ix->mu);
   DeviceGuard g(ix->device);
   if (!ix->n) return fail(WDBX_E_STATE, "empty index");
-  int rc = grow((void**)&ix->d_tau, &ix->tau_bytes, (size_t)GB_N * sizeof(float));
+  int rc = ix->d_tau.grow((size_t)GB_N * sizeof(float));
   if (rc) return rc;
   const u64 quads = (u64)ix->n * (u64)(ix->pitch / 4);
   const uint32_t grid = blocks > 0 ? (uint32_t)blocks : (uint32_t)ix->cu_count * 8;
@@ -2271,9 +2248,9 @@ int wdbx_index_probe_read(wdbx_index* ix, int nontemporal, int blocks, int reps,
   for (int i = -2; i < reps; ++i) {
     if (i == 0) HIP_TRY(hipEventRecord(e0, ix->stream));
     if (nontemporal)
-      hipLaunchKernelGGL(probe_read_kernel<true>, dim3(grid), dim3(256), 0, ix->stream, (const f4*)ix->d_rows, quads, ix->d_tau);
+      hipLaunchKernelGGL(probe_read_kernel<true>, dim3(grid), dim3(256), 0, ix->stream, (const f4*)ix->d_rows.p, quads, ix->d_tau);
     else
-      hipLaunchKernelGGL(probe_read_kernel<false>, dim3(grid), dim3(256), 0, ix->stream, (const f4*)ix->d_rows, quads, ix->d_tau);
+      hipLaunchKernelGGL(probe_read_kernel<false>, dim3(grid), dim3(256), 0, ix->stream, (const f4*)ix->d_rows.p, quads, ix->d_tau);
   }
   HIP_TRY(hipEventRecord(e1, ix->stream));
   HIP_TRY(hipEventSynchronize(e1));
@@ -2304,15 +2281,11 @@ int wdbx_group_create(const int* device_ids, int n, int dim, int metric, uint64_
   g->cap_per_shard = cap_per_shard;
   g->dim = dim;
   g->metric = metric;
+  g->sh = std::vector<GroupShard>((size_t)n);  // (in place: a shard's buffers do not move)
   int rc = WDBX_OK;
   for (int i = 0; i < n && rc == WDBX_OK; ++i) {
-    wdbx_index* ix = nullptr;
-    rc = wdbx_index_create(device_ids[i], dim, metric, cap_per_shard, &ix);
-    if (rc == WDBX_OK) {
-      ix->row_base = (uint64_t)i * cap_per_shard;
-      g->sh.emplace_back();
-      g->sh.back().ix = ix;
-    }
+    rc = wdbx_index_create(device_ids[i], dim, metric, cap_per_shard, &g->sh[i].ix);
+    if (rc == WDBX_OK) g->sh[i].ix->row_base = (uint64_t)i * cap_per_shard;
   }
   if (rc == WDBX_OK) rc = group_finish_setup(g, 0);
   if (rc != WDBX_OK) {
@@ -2349,7 +2322,7 @@ int wdbx_group_attach_ex(wdbx_index* const* shards, int n, int exchange_mode, wd
   g->dim = shards[0]->dim;
   g->metric = shards[0]->metric;
   g->cap_per_shard = 0xFFFFFF00ull / (uint64_t)n;
-  g->sh.resize(n);
+  g->sh = std::vector<GroupShard>((size_t)n);
   for (int i = 0; i < n; ++i) g->sh[i].ix = shards[i];
   int rc = group_finish_setup(g, exchange_mode);
   if (rc != WDBX_OK) {
@@ -2622,9 +2595,9 @@ int wdbx_index_comm_allgather_host(wdbx_index* ix, const void* send, void* recv,
   std::lock_guard<std::mutex> lk(ix->mu);
   if (!ix->comm) return fail(WDBX_E_STATE, "no communicator on this handle");
   DeviceGuard g(ix->device);
-  int rc = grow((void**)&ix->d_gathered, &ix->gathered_bytes, (size_t)(ix->nranks + 1) * bytes);
+  int rc = ix->d_gathered.grow((size_t)(ix->nranks + 1) * bytes);
   if (rc) return rc;
-  char* base = (char*)ix->d_gathered;
+  char* base = (char*)ix->d_gathered.p;
   HIP_TRY(hipMemcpyAsync(base, send, bytes, hipMemcpyHostToDevice, ix->stream));
   NCCL_TRY(ncclAllGather(base, base + bytes, bytes, ncclUint8, ix->comm, ix->stream));
   HIP_TRY(hipMemcpyAsync(recv, base + bytes, (size_t)ix->nranks * bytes, hipMemcpyDeviceToHost, ix->stream));
@@ -2748,11 +2721,11 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   // read-only state of the batched path
   if (name && !strcmp(name, "last_gemm_family")) return *value = ix->last_gemm_mode, WDBX_OK;
   if (name && !strcmp(name, "shadow_rows")) return *value = (int64_t)ix->shadow_rows, WDBX_OK;
-  if (name && !strcmp(name, "shadow_bytes")) return *value = (int64_t)ix->rows16_bytes, WDBX_OK;
+  if (name && !strcmp(name, "shadow_bytes")) return *value = (int64_t)ix->d_rows16.bytes, WDBX_OK;
   if (name && !strcmp(name, "shadow8_rows")) return *value = (int64_t)ix->shadow8_rows, WDBX_OK;
-  if (name && !strcmp(name, "shadow8_bytes")) return *value = (int64_t)(ix->rows8_bytes + ix->scale8_bytes), WDBX_OK;
+  if (name && !strcmp(name, "shadow8_bytes")) return *value = (int64_t)(ix->d_rows8.bytes + ix->d_scale8.bytes), WDBX_OK;
   if (name && !strcmp(name, "shadowg_rows")) return *value = (int64_t)ix->shadowg_rows, WDBX_OK;
-  if (name && !strcmp(name, "shadowg_bytes")) return *value = (int64_t)(ix->rows8g_bytes + ix->groups8_bytes), WDBX_OK;
+  if (name && !strcmp(name, "shadowg_bytes")) return *value = (int64_t)(ix->d_rows8g.bytes + ix->d_groups8.bytes), WDBX_OK;
   if (name && !strcmp(name, "last_single_path")) return *value = ix->last_single_path, WDBX_OK;
   if (name && !strcmp(name, "last_single_u6")) return *value = ix->last_single_u6, WDBX_OK;
   if (name && (!strcmp(name, "u6_candidates_sum") || !strcmp(name, "u6_candidates_max"))) {
@@ -2781,9 +2754,9 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
     return *value = sum, WDBX_OK;
   }
   if (name && !strcmp(name, "shadow42_rows")) return *value = (int64_t)ix->shadow42_rows, WDBX_OK;
-  if (name && !strcmp(name, "shadow42_bytes")) return *value = (int64_t)ix->rows42_bytes, WDBX_OK;
+  if (name && !strcmp(name, "shadow42_bytes")) return *value = (int64_t)ix->d_rows42.bytes, WDBX_OK;
   if (name && !strcmp(name, "shadow6_rows")) return *value = (int64_t)ix->shadow6_rows, WDBX_OK;
-  if (name && !strcmp(name, "shadow6_bytes")) return *value = (int64_t)ix->rows6_bytes, WDBX_OK;
+  if (name && !strcmp(name, "shadow6_bytes")) return *value = (int64_t)ix->d_rows6.bytes, WDBX_OK;
   if (name && !strcmp(name, "last_range_path")) return *value = ix->last_range_path, WDBX_OK;
   if (name && !strcmp(name, "last_range_batch_path")) return *value = ix->last_range_batch_path, WDBX_OK;
   if (name && !strcmp(name, "last_range_batch_blocks")) return *value = ix->last_range_batch_blocks, WDBX_OK;
