@@ -177,6 +177,33 @@ int wdbx_index_search_multimask(wdbx_index* idx, const float* queries, int nq, i
 int wdbx_index_search_rows(wdbx_index* idx, const float* queries, int nq, int k, int normalize_queries,
                            const uint64_t* row_ids, uint64_t n_ids, int64_t* out_idx, float* out_score);
 
+/* ---- distance matrix among listed rows: each listed row's nearest among the others ---- */
+/* For every listed row row_ids[i] (host memory, the index's own row numbers) the exact fp32 top-k of the listed rows OTHER
+ * THAN row_ids[i] itself: what clustering, a UMAP / t-SNE layout or a near-duplicate report reads from a sample of stored
+ * vectors.  out_idx / out_score are host buffers [n_ids, k]; line i belongs to row_ids[i].  Blocking.
+ *   The query of line i is the STORED row row_ids[i], as stored (cosine rows were normalised when they were added; nothing is
+ *   normalised again), read on the device where it lies: no vector crosses the bus in either direction.
+ *   Self is the same list position, which is the same row number; it is left out by position, not by score.  Another listed
+ *   row holding an equal vector is a neighbour like any other.
+ *   Results: format, order, -1 / 0 unused slots and NaN handling as wdbx_index_search_rows; a candidate whose score is NaN is
+ *   never returned.  An anchor that was removed or holds a NaN has every slot -1.  With k >= n_ids a line has at most
+ *   n_ids - 1 results.
+ *   Scores: exact_score_block's arithmetic.  Line i is bit-identical, ids and score bits, to wdbx_index_search_rows called
+ *   with the query wdbx_index_get_rows(row_ids[i]), normalize_queries = 0 and the list with entry i removed.  The answer is
+ *   bit-identical from run to run and does not depend on how the anchors fall into rounds.
+ *   WDBX_E_INVALID: a list that is not strictly increasing or reaches the row count (checked under the handle's lock by the
+ *   pass wdbx_index_search_rows uses; the message names the entry), k outside [1, WDBX_MAX_K], a null buffer with n_ids > 0,
+ *   more than 2^31 - 1 listed rows.  n_ids == 0 is WDBX_OK and launches nothing.  A refused call leaves the handle usable.
+ *   Routes and anchor blocks are wdbx_index_search_rows' with the listed rows as its queries (get_option "last_matrix_path":
+ *   0 = nothing launched, 1 = a key per (anchor, listed row) ranked by the merge kernel, 2 = per-workgroup top-k lists, 3 = keys
+ *   and the radix-select chain per anchor; options "rows_keys_max" and "select_min_k" decide as they do there).  The anchors
+ *   run in rounds of at most 256 consecutive list positions (get_option "last_matrix_rounds"), each one scoring launch --
+ *   counted as a scan launch in wdbx_index_profile_read -- and one ranking launch (one per anchor on route 3) -- counted as
+ *   merge launches; a round's scratch stays within 256 MiB.
+ *   The call holds the handle's mutex to its end.  Nothing of the call's list stays valid in the handle. */
+int wdbx_index_search_matrix(wdbx_index* idx, const uint64_t* row_ids, uint64_t n_ids, int k,
+                             int64_t* out_idx /* [n_ids, k] */, float* out_score /* [n_ids, k] */);
+
 /* ---- search among listed rows, one row list PER QUERY in one batched call ------ */
 /* What wdbx_index_search_rows answers for one list, for a batch whose queries each name their own list (a rerank stage's
  * candidates, a selective filter per tenant): query i is ranked among the rows of list query_list[i].  The lists come back to

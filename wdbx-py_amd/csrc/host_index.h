@@ -169,6 +169,9 @@ struct wdbx_index {
   DevBuf<uint32_t> d_sub_ids{&bufs};
   DevBuf<u64> d_sub_keys{&bufs};
   int last_rows_path = 0;      // 0 nothing launched (empty list), 1 keys + merge, 2 lists + merge, 3 keys + radix select
+  // distance matrix among listed rows (wdbx_index_search_matrix): list, keys and lists live where the listed-row search keeps them
+  int last_matrix_path = 0;    // as last_rows_path
+  int64_t last_matrix_rounds = 0;
   // one row list per query (wdbx_index_search_row_lists): the call's work items, then its slots' list lengths; the lists' rows
   // and the round's keys live in d_sub_ids / d_sub_keys
   DevBuf<char> d_rl{&bufs};
@@ -420,7 +423,8 @@ static int launch_merge(wdbx_index* ix, const MergeArgs& m_in, int nq) {
 // ---- what the listed-row, label and corpus calls share ------------------------------------------------
 // One launch of 256-thread workgroups between the two records of `pool`; a kernel whose dynamic LDS passes 64 KiB gets its limit
 // raised first -- a runtime call on EVERY such launch, so a site that launches in a loop of rounds with lists in LDS raises the
-// limit once before the loop and keeps its bracket written out (today every caller passes lds = 0 and the raise is not reached);
+// limit once before the loop and keeps its bracket written out (wdbx_index_search_matrix passes its lists' LDS and reaches the raise
+// only with k = WDBX_MAX_K lists in LDS, once per round of 256 anchors; every other caller passes lds = 0);
 // so does a site that launches twice inside one bracket or counts more than one launch per bracket.
 template <typename Fn, typename Args>
 static int launch_bracketed(wdbx_index* ix, EventPool& pool, Fn fn, dim3 grid, size_t lds, const Args& a) {

@@ -35,6 +35,9 @@
 //                           rows in flight, exact_score_block, the key rule, the mask bit
 //   kernels_subset.h        subset_kernel: exact scores of LISTED rows (wdbx_index_search_rows), a block of queries per fetched
 //                           row, per-workgroup top-k lists or a key per listed row
+//   kernels_matrix.h        matrix_kernel: the distance matrix among listed rows (wdbx_index_search_matrix): subset_kernel with the
+//                           listed rows themselves as the queries, read where they lie, each one's own list position left out
+//   host_matrix.h           that call's plan: subset_plan's route, anchor block and grid, the instance and the rounds
 //   kernels_rowlists.h      rowlists_kernel: the same scores for a call with one row list PER QUERY (wdbx_index_search_row_lists),
 //                           one workgroup per (chunk of a list, block of its queries) work item of host_rowlists.h
 //   kernels_labels.h        label_keys_kernel, label_rank_kernel: the full pass of wdbx_index_search_distinct (at most one row per
@@ -103,6 +106,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_range_batch.h"  // (device-free as well: route, blocks, buffer sizes and fallback bookkeeping of a batched range search)
 #include "host_calls.h"  // (device-free as well: mask popcount, padded query copies, host ranking of keys, class-by-class loop)
 #include "host_subset.h"  // (device-free as well: row-list validation, route and grid sizing of a search among listed rows)
+#include "host_matrix.h"  // (device-free as well: route, anchor block, instance and rounds of a distance matrix among listed rows)
 #include "host_multimask.h"  // (device-free as well: where the queries of a call with a mask per query sit in the tile blocks)
 #include "host_selection.h"  // (device-free as well: the sample, stride and capacities of the selection rounds)
 #include "host_scan_plan.h"  // (device-free as well: the fp32 scan and range forms of a pitch, grid / list / chunk / LDS numbers of a scan)
@@ -146,6 +150,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "kernels_range_batch.h"
 #include "kernels_rowblock.h"
 #include "kernels_subset.h"
+#include "kernels_matrix.h"
 #include "kernels_rowlists.h"
 #include "kernels_labels.h"
 static_assert(LABEL_SPAN_DEV == LABEL_SPAN, "the kernels walk the spans the host built");
@@ -834,6 +839,60 @@ static int search_rows_host(wdbx_index* ix, const float* queries, int nq, int k,
 int wdbx_index_search_rows(wdbx_index* ix, const float* queries, int nq, int k, int normalize_queries, const uint64_t* row_ids,
                            uint64_t n_ids, int64_t* out_idx, float* out_score) try {
   return search_rows_host(ix, queries, nq, k, normalize_queries, row_ids, n_ids, out_idx, out_score);
+} WDBX_CATCH
+
+// ---- distance matrix among listed rows (kernels_matrix.h, host_matrix.h) --------------------
+// wdbx_index_search_rows with the listed rows themselves as the queries.  The whole call holds the handle's mutex.  Under it the
+// list is validated and narrowed by the pass wdbx_index_search_rows uses and goes to the device once; nothing else goes up: the
+// anchors are read from the corpus through the list.  Every round of consecutive anchors (matrix_plan) is one matrix_kernel
+// launch, bracketed as a scan launch, and the ranking tail writing from the round's first slot on; one download at the end.
+int wdbx_index_search_matrix(wdbx_index* ix, const uint64_t* row_ids, uint64_t n_ids, int k, int64_t* out_idx, float* out_score) try {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  if (k < 1 || k > WDBX_MAX_K) return fail(WDBX_E_INVALID, "k=%d outside [1, %d]", k, WDBX_MAX_K);
+  if (n_ids && (!row_ids || !out_idx || !out_score)) return fail(WDBX_E_INVALID, "null buffer");
+  std::unique_lock<std::mutex> lk(ix->mu);
+  if (ix->n >= 0xFFFFFF00ull) return fail(WDBX_E_INVALID, "shard holds too many rows for 32-bit row keys");
+  if (n_ids > ix->n) return fail(WDBX_E_INVALID, "%llu listed rows of %llu stored", (u64)n_ids, (u64)ix->n);
+  if (n_ids > MATRIX_MAX_IDS) return fail(WDBX_E_INVALID, "%llu listed rows in one call: at most 2^31 - 1", (u64)n_ids);
+  std::vector<uint32_t> ids32((size_t)n_ids);
+  const uint64_t bad = subset_validate(row_ids, n_ids, ix->n, ids32.data());
+  if (bad != n_ids)
+    return fail(WDBX_E_INVALID, "row_ids must be strictly increasing row numbers below %llu (entry %llu)", (u64)ix->n, (u64)bad);
+  const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
+  const MatrixPlan mp = matrix_plan(n_ids, k, pitch4, ix->cu_count, ix->opt_rows_keys_max, ix->opt_select_min_k, ix->opt_lds_lists != 0);
+  ix->last_matrix_path = mp.sp.route;
+  ix->last_matrix_rounds = (int64_t)mp.rounds;
+  if (mp.sp.route == SUBSET_NONE) return WDBX_OK;  // (nothing listed: nothing to write, nothing launched)
+  const size_t elems = (size_t)n_ids * k;
+  DeviceGuard g(ix->device);
+  int rc;
+  if ((rc = ensure_out(ix, elems))) return rc;
+  if ((rc = ix->d_sub_ids.grow((size_t)n_ids * sizeof(uint32_t)))) return rc;
+  const bool lists = mp.sp.route == SUBSET_LISTS;
+  const RankSource::Form form = lists ? RankSource::LISTS : mp.sp.route == SUBSET_SELECT ? RankSource::SELECT : RankSource::KEYS;
+  if ((rc = grow_rank_scratch(ix, form, mp.sp.scratch_u64))) return rc;
+  HIP_TRY(hipMemcpyAsync(ix->d_sub_ids, ids32.data(), (size_t)n_ids * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+  const matrix_fn fn = pick_matrix(ix->metric, mp.mode, mp.sp.qb, pitch4);
+  if (!fn) return fail(WDBX_E_STATE, "no distance-matrix instance for mode %d with %d anchors per block", mp.mode, mp.sp.qb);
+  const size_t lds = lists ? mp.sp.lds : 0;
+  for (uint64_t r = 0; r < mp.rounds; ++r) {
+    const uint64_t first = matrix_round_first(mp, r);
+    const int b = matrix_round_anchors(mp, n_ids, r);
+    MatrixArgs a = {};
+    a.rows = (const f4*)ix->d_rows.p;
+    a.ids = ix->d_sub_ids;
+    a.out = lists ? ix->d_partials : ix->d_sub_keys;
+    a.key_stride = n_ids;
+    a.n_ids = (uint32_t)n_ids;
+    a.pitch4 = pitch4;
+    a.first = (uint32_t)first;
+    a.na = (uint32_t)b;
+    a.k = k;
+    if ((rc = launch_bracketed(ix, ix->scan_ev, fn, dim3(mp.sp.blocks, matrix_anchor_blocks(mp, b)), lds, a))) return rc;
+    const RankSource src = lists ? RankSource{form, ix->d_partials, mp.sp.P, nullptr} : RankSource{form, ix->d_sub_keys, n_ids, nullptr};
+    if ((rc = enqueue_rank_tail(ix, src, (int)first, b, k, ix->metric))) return rc;
+  }
+  return download_results(ix, elems, out_idx, out_score);
 } WDBX_CATCH
 
 // ---- one row list PER QUERY in one batched call (host_rowlists.h, kernels_rowlists.h) --------
@@ -2763,6 +2822,8 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "last_range_batch_pairs")) return *value = ix->last_range_batch_pairs, WDBX_OK;
   if (name && !strcmp(name, "last_range_batch_fallback_queries")) return *value = ix->last_range_batch_fallback, WDBX_OK;
   if (name && !strcmp(name, "last_rows_path")) return *value = ix->last_rows_path, WDBX_OK;
+  if (name && !strcmp(name, "last_matrix_path")) return *value = ix->last_matrix_path, WDBX_OK;
+  if (name && !strcmp(name, "last_matrix_rounds")) return *value = ix->last_matrix_rounds, WDBX_OK;
   if (name && !strcmp(name, "last_lists_path")) return *value = ix->last_lists_path, WDBX_OK;
   if (name && !strcmp(name, "last_lists_items")) return *value = ix->last_lists_items, WDBX_OK;
   if (name && !strcmp(name, "last_lists_rounds")) return *value = ix->last_lists_rounds, WDBX_OK;

@@ -70,6 +70,7 @@ SIGNATURES = {
     "wdbx_index_search_multimask": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.POINTER(C.c_uint32)),
                                               _u64p, C.c_int, C.POINTER(C.c_int32), _i64p, _f32p]),
     "wdbx_index_search_rows": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _u64p, C.c_uint64, _i64p, _f32p]),
+    "wdbx_index_search_matrix": (C.c_int, [C.c_void_p, _u64p, C.c_uint64, C.c_int, _i64p, _f32p]),
     "wdbx_index_search_row_lists": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _u64p, _u64p, C.c_int,
                                               C.POINTER(C.c_int32), _i64p, _f32p]),
     "wdbx_index_set_labels": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]),
@@ -376,6 +377,18 @@ class NativeIndex:
         _check(self._lib.wdbx_index_search_rows(self._h, q.ctypes.data_as(_f32p), nq, int(k), int(normalize_queries),
                                                 ids.ctypes.data_as(_u64p), ids.size, idx.ctypes.data_as(_i64p),
                                                 score.ctypes.data_as(_f32p)))
+        return idx, score
+
+    def search_matrix(self, rows, k: int) -> Tuple[np.ndarray, np.ndarray]:
+        """The distance matrix among the listed rows (``rows``: strictly increasing row numbers of this index): line ``i`` is
+        the exact top-``k`` of the listed rows other than ``rows[i]`` itself, with the stored row ``rows[i]`` as the query,
+        in the format and order of :meth:`search_rows` and with its score bits.  Returns ``(idx[n, k], score[n, k])``."""
+        ids = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        idx = np.empty((ids.size, int(k)), np.int64)
+        score = np.empty((ids.size, int(k)), np.float32)
+        # (the list and k are checked by the library, the list under the handle's lock)
+        _check(self._lib.wdbx_index_search_matrix(self._h, ids.ctypes.data_as(_u64p), ids.size, int(k), idx.ctypes.data_as(_i64p),
+                                                  score.ctypes.data_as(_f32p)))
         return idx, score
 
     def search_row_lists(self, queries, k: int, lists, query_list,

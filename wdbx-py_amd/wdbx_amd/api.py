@@ -226,6 +226,44 @@ async def discover_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
     return {"results": [{"vector_id": vid, "similarity": sim, "metadata": meta, "wins": wins} for vid, sim, meta, wins in found]}
 
 
+def _matrix_arguments(payload) -> Dict[str, Any]:
+    """the body of the two distance-matrix forms: ``{"sample": 10, "limit": 3, "filter": null, "vector_ids": null, "seed": null}``"""
+    if not isinstance(payload, dict):
+        raise ValueError("request body must be an object")
+
+    def integer(name, default, optional=False):
+        value = payload.get(name)
+        if value is None:
+            return default
+        if isinstance(value, bool) or not isinstance(value, int) or (value < 0 and not optional):
+            raise ValueError(f"{name} must be a{'n' if optional else ' non-negative'} integer")
+        return value
+
+    flt = payload.get("filter")
+    if flt is not None and not isinstance(flt, dict):
+        raise ValueError("filter must be an object")
+    vector_ids = payload.get("vector_ids")
+    if vector_ids is not None and (not isinstance(vector_ids, (list, tuple)) or not all(isinstance(v, str) for v in vector_ids)):
+        raise ValueError("vector_ids must be a list of vector ids")
+    return {"sample": integer("sample", 10), "limit": integer("limit", 3), "filter_metadata": flt, "vector_ids": vector_ids,
+            "seed": integer("seed", None, optional=True)}
+
+
+async def search_matrix_pairs_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
+    """Distance-matrix form (extension), as pairs: body ``{"sample": 10, "limit": 3, "filter": null, "vector_ids": null,
+    "seed": null}`` -> ``{"pairs": [{"a": id, "b": id, "score": s}, ...]}`` (``wdbx.vector_search_matrix_pairs_async``): for each
+    sampled vector its ``limit`` nearest among the other sampled vectors.  ``vector_ids`` names the sample itself; else
+    ``sample`` vectors are drawn from those ``filter`` matches, reproducibly with ``seed``."""
+    return {"pairs": await wdbx.vector_search_matrix_pairs_async(**_matrix_arguments(payload))}
+
+
+async def search_matrix_offsets_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
+    """Distance-matrix form (extension), as a sparse matrix: the body of ``search_matrix_pairs_endpoint`` ->
+    ``{"offsets_row": [...], "offsets_col": [...], "scores": [...], "ids": [...]}`` (``wdbx.vector_search_matrix_offsets_async``);
+    rows and columns are positions in ``ids``."""
+    return await wdbx.vector_search_matrix_offsets_async(**_matrix_arguments(payload))
+
+
 async def range_search_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
     """Range form (extension): body ``{"query_vector": [...], "threshold": 0.8, "filter_metadata": null,
     "max_results": null}`` -> the ``search_endpoint`` response shape with EVERY vector whose similarity reaches

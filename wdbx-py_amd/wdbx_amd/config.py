@@ -90,6 +90,9 @@ class WDBXConfig:
         # distinct search (``vector_search_distinct``: at most one result per value of this metadata field, e.g. the document
         # a chunk belongs to); None = off: nothing is labelled and no existing call changes
         "DISTINCT_KEY": None,
+        # distance matrix (``vector_search_matrix_pairs`` / ``_offsets``): the largest sample one call accepts -- the work grows
+        # with its square, so an accidental "every vector" is refused instead of served
+        "MATRIX_MAX_SAMPLE": 10000,
     }
 
     def __init__(self, config_dict: Optional[Dict[str, Any]] = None, config_path: Optional[str] = None):

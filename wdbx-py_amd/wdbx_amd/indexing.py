@@ -727,9 +727,10 @@ class HipFlatIndex(VectorIndex):
         rows = {r for r in (row_of(i) for i in ids) if r is not None}
         return np.fromiter(sorted(rows), dtype=np.uint64, count=len(rows))
 
-    def search_rows_raw(self, queries: np.ndarray, limit: int, rows: np.ndarray):
+    def search_rows_raw(self, queries: np.ndarray, limit: int, rows: np.ndarray, normalize: bool = True):
         """``search_batch_raw`` over the listed rows only (``rows``: strictly increasing row numbers, as ``rows_of`` returns
-        them): (rows int64[nq, k], scores f32[nq, k]) or None for "no results"."""
+        them): (rows int64[nq, k], scores f32[nq, k]) or None for "no results".  ``normalize=False``: the queries are
+        stored rows of another shard (``stored_vectors``) and go to the library exactly as they are."""
         queries = np.asarray(queries, dtype=np.float32)
         if queries.ndim != 2 or queries.shape[1] != self.vector_dim:
             raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {queries.shape}")
@@ -737,7 +738,7 @@ class HipFlatIndex(VectorIndex):
         if self.next_index == 0 or queries.shape[0] == 0 or len(rows) == 0 or actual_limit <= 0:
             return None
         try:
-            q = np.stack([self._prepare(r) for r in queries])
+            q = np.stack([self._prepare(r) for r in queries]) if normalize else np.ascontiguousarray(queries)
             out = self._native.search_rows(q, actual_limit, rows)
             self.rows_searches += 1
             return out
@@ -752,8 +753,9 @@ class HipFlatIndex(VectorIndex):
         ignored), best first, scores as ``search`` returns them.  Errors are swallowed or raised as in ``search``."""
         return self.search_batch_among(np.asarray(query_vector, dtype=np.float32)[None, :], ids, limit)[0]
 
-    def search_batch_among(self, queries: np.ndarray, ids, limit: int = 10) -> List[List[Tuple[str, float]]]:
-        """``search_among`` for many queries over ONE list: every listed row is fetched once per block of queries."""
+    def search_batch_among(self, queries: np.ndarray, ids, limit: int = 10, normalize: bool = True) -> List[List[Tuple[str, float]]]:
+        """``search_among`` for many queries over ONE list: every listed row is fetched once per block of queries.
+        ``normalize`` as in ``search_rows_raw``."""
         try:
             rows = self.rows_of(ids)
         except Exception as e:
@@ -761,10 +763,52 @@ class HipFlatIndex(VectorIndex):
             if self.swallow_errors:
                 return [[] for _ in range(len(queries))]
             raise
-        raw = self.search_rows_raw(queries, limit, rows)
+        raw = self.search_rows_raw(queries, limit, rows, normalize=normalize)
         if raw is None:
             return [[] for _ in range(len(queries))]
         return [self._map(i, s) for i, s in zip(*raw)]
+
+    # ---- distance matrix (extension: each listed vector's nearest among the other listed vectors) ----
+    def mapped_ids(self, mask_words: Optional[np.ndarray] = None) -> List[str]:
+        """The ids of every row that still has one -- with ``mask_words`` (as ``row_mask_for`` returns them) only of the rows
+        the mask allows -- in no particular order: what a distance matrix samples from."""
+        if mask_words is None:
+            return [vid for _, vid in self.mapped_rows()]
+        words = np.asarray(mask_words, dtype=np.uint32)
+        return [vid for row, vid in self.mapped_rows() if row < 32 * words.size and (int(words[row >> 5]) >> (row & 31)) & 1]
+
+    def stored_vectors(self, ids) -> Tuple[List[str], np.ndarray]:
+        """The listed vectors AS STORED (cosine: as normalised when they were added), in row order with unknown and removed
+        ids dropped, as ``rows_of`` orders them: (ids, f32[n, dim]).  Runs of consecutive rows come back in one read each."""
+        rows = self.rows_of(ids).astype(np.int64)
+        out = np.empty((rows.size, self.vector_dim), np.float32)
+        cuts = np.flatnonzero(np.diff(rows) != 1) + 1 if rows.size else np.empty(0, np.int64)
+        for a, b in zip(np.concatenate([[0], cuts]).tolist(), np.concatenate([cuts, [rows.size]]).tolist()):
+            if b > a:
+                out[a:b] = self._native.get_rows(int(rows[a]), b - a)
+        return [self._id_of(int(r)) for r in rows], out
+
+    def search_matrix(self, ids, limit: int = 10) -> List[Tuple[str, List[Tuple[str, float]]]]:
+        """For every vector named by ``ids`` (any order, duplicates allowed; unknown and removed ids are dropped, as in
+        ``search_among``) its exact top-``limit`` among the OTHER listed vectors, the stored vector itself being the query:
+        ``[(id, [(neighbour id, score), ...]), ...]`` in row order, scores as ``search`` returns them.  One library call
+        (``wdbx_index_search_matrix``): nothing but the row list goes to the device.  Errors are swallowed or raised as in
+        ``search``."""
+        try:
+            rows = self.rows_of(ids)
+            actual_limit = min(int(limit), _native.MAX_K)
+            if self.next_index == 0 or rows.size == 0:
+                return []
+            anchors = [self._id_of(int(r)) for r in rows]
+            if actual_limit <= 0:
+                return [(a, []) for a in anchors]
+            idx, score = self._native.search_matrix(rows, actual_limit)
+            return [(a, self._map(i, s)) for a, i, s in zip(anchors, idx, score)]
+        except Exception as e:
+            logger.error("Error in distance matrix of HIP index: %s", e)
+            if self.swallow_errors:
+                return []
+            raise
 
     # ---- the same with one list PER QUERY (wdbx_index_search_row_lists: one call for the whole batch) ----
     supports_row_lists = True

@@ -24,6 +24,7 @@ import json
 import logging
 import os
 import pickle
+import random
 import threading
 import time
 import uuid
@@ -1387,6 +1388,71 @@ class VectorStore:
         loop = asyncio.get_running_loop()
         return await loop.run_in_executor(self.thread_pool, lambda: self.discover(
             target, context, limit=limit, filter_metadata=filter_metadata, with_wins=with_wins))
+
+    # ---- distance matrix (extension: each sampled vector's nearest among the sample) ----
+    def _matrix_sample(self, sample: int, filter_metadata, vector_ids, seed) -> List[str]:
+        """The sampled ids, sorted: the explicit ``vector_ids`` (known ones, once each), else ``sample`` of the ids the filter
+        matches -- the evaluation ``_row_masks`` caches -- or of every id, drawn by ``random.Random(seed)`` from the sorted ids."""
+        if vector_ids is not None:
+            chosen = sorted({vid for vid in vector_ids if self._known(vid)})
+        else:
+            if isinstance(sample, bool) or not isinstance(sample, int) or sample < 0:
+                raise ValueError("sample must be a non-negative integer")
+            masks = self._row_masks(filter_metadata) if filter_metadata else [None] * len(self.indices)
+            pool = sorted(vid for ix, mask in zip(self.indices, masks) for vid in ix.mapped_ids(mask))
+            chosen = sorted(random.Random(seed).sample(pool, min(sample, len(pool))))
+        cap = int(self.config.get("MATRIX_MAX_SAMPLE", 10000))
+        if len(chosen) > cap:
+            raise ValueError(f"a distance matrix over {len(chosen)} vectors: MATRIX_MAX_SAMPLE allows {cap}")
+        return chosen
+
+    def search_matrix(self, sample: int = 10, limit: int = 3, filter_metadata: Optional[Dict[str, Any]] = None,
+                      vector_ids=None, seed=None) -> List[Tuple[str, List[Tuple[str, float]]]]:
+        """Distance matrix: for every sampled vector its ``limit`` nearest among the OTHER sampled vectors, the stored vector
+        being the query -- ``[(id, [(neighbour id, score), ...]), ...]`` in sorted id order, what clustering, a 2-D layout or
+        a near-duplicate report reads.  The sample is ``vector_ids`` when given (unknown and deleted ids are ignored), else
+        ``sample`` of the vectors ``filter_metadata`` matches (of all vectors without one), drawn by
+        ``random.Random(seed)``: with a seed the same store gives the same sample.  More than ``MATRIX_MAX_SAMPLE``
+        sampled vectors is a ``ValueError``.  A vector is never its own neighbour; another vector equal to it is one.
+        One shard: one library call (``wdbx_index_search_matrix``), no vector leaves the device.  Several shards: every shard
+        answers its own sampled rows that way; its anchors' stored vectors are read once and go, as they are (nothing is
+        normalised again), to every other shard holding sampled rows, which ranks them among ITS part of the sample
+        (``wdbx_index_search_rows``); per anchor the parts are merged in ``_merge``'s order and cut to ``limit``.  Both
+        calls return the same score bits, so the merged lines are what one shard holding everything would return (up to
+        the order of exactly tied scores).  On the shard pool; never through the shard group."""
+        chosen = self._matrix_sample(sample, filter_metadata, vector_ids, seed)
+        self.last_search_path = "threads"
+        if not chosen:
+            return []
+        if limit <= 0:
+            return [(vid, []) for vid in chosen]
+        per = self._ids_by_shard(chosen)
+        work = [s for s, ids in enumerate(per) if ids]
+        own = list(self._shard_pool.map(lambda s: self.indices[s].search_matrix(per[s], limit), work)) if len(work) > 1 \
+            else [self.indices[work[0]].search_matrix(per[work[0]], limit)]
+        parts: Dict[str, List[List[Tuple[str, float]]]] = {}  # anchor -> its lists, in shard order
+        if len(work) == 1:
+            parts = {anchor: [res] for anchor, res in own[0]}
+        else:
+            stored = list(self._shard_pool.map(lambda s: self.indices[s].stored_vectors(per[s]), work))
+            cross = [(a, b) for a in range(len(work)) for b in range(len(work)) if a != b and len(stored[a][0])]
+
+            def one(ab):  # shard work[a]'s anchors among shard work[b]'s part of the sample
+                a, b = ab
+                return self.indices[work[b]].search_batch_among(stored[a][1], per[work[b]], limit=limit, normalize=False)
+            answers = dict(zip(cross, self._shard_pool.map(one, cross)))
+            for a in range(len(work)):
+                mine = dict(own[a])
+                for at, anchor in enumerate(stored[a][0]):
+                    parts[anchor] = [mine.get(anchor, []) if b == a else answers[(a, b)][at] for b in range(len(work))]
+        return [(anchor, [(vid, score) for vid, score, _ in self._merge(parts[anchor], limit, 0.0, None)])
+                for anchor in chosen if anchor in parts]
+
+    async def search_matrix_async(self, sample: int = 10, limit: int = 3, filter_metadata: Optional[Dict[str, Any]] = None,
+                                  vector_ids=None, seed=None) -> List[Tuple[str, List[Tuple[str, float]]]]:
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(self.thread_pool, lambda: self.search_matrix(
+            sample, limit, filter_metadata=filter_metadata, vector_ids=vector_ids, seed=seed))
 
     # ---- range search (extension: every vector within a similarity, no limit) ----
     def search_range(self, query_vector: List[float], threshold: float,

@@ -12,6 +12,7 @@ import uuid
 from pathlib import Path
 from typing import Any, Dict, List, Optional, Tuple
 
+from . import _native
 from .config import WDBXConfig
 from .vector_store import VectorStore
 
@@ -254,6 +255,54 @@ class WDBX:
                                     filter_metadata: Optional[Dict[str, Any]] = None, with_wins: bool = False) -> List[tuple]:
         return await self.vector_store.discover_async(target, context, limit=limit, filter_metadata=filter_metadata,
                                                       with_wins=with_wins)
+
+    def _matrix_lines(self, lines):
+        """a distance matrix's lines with the scores as reported: cosine similarity, for L2 the positive squared distance"""
+        if self.vector_store.indices[0].metric == _native.METRIC_COSINE:
+            return lines
+        return [(anchor, [(vid, -score) for vid, score in res]) for anchor, res in lines]
+
+    @staticmethod
+    def _matrix_pairs(lines) -> List[Dict[str, Any]]:
+        return [{"a": anchor, "b": vid, "score": score} for anchor, res in lines for vid, score in res]
+
+    @staticmethod
+    def _matrix_offsets(lines) -> Dict[str, List[Any]]:
+        ids = [anchor for anchor, _ in lines]
+        at = {vid: i for i, vid in enumerate(ids)}
+        cells = [(at[anchor], at[vid], score) for anchor, res in lines for vid, score in res]
+        return {"offsets_row": [c[0] for c in cells], "offsets_col": [c[1] for c in cells], "scores": [c[2] for c in cells],
+                "ids": ids}
+
+    def vector_search_matrix_pairs(self, sample: int = 10, limit: int = 3, filter_metadata: Optional[Dict[str, Any]] = None,
+                                   vector_ids=None, seed=None) -> List[Dict[str, Any]]:
+        """Extension: distance matrix.  A sample of the stored vectors -- ``vector_ids``, else ``sample`` of those
+        ``filter_metadata`` matches, drawn with ``seed`` -- and for each its ``limit`` nearest among the OTHER sampled
+        vectors: ``[{"a": id, "b": id, "score": s}, ...]``, anchor-major (anchors in sorted id order), each anchor's
+        neighbours nearest first.  Scores are cosine similarities, for L2 the positive squared distances.  Any number of
+        shards (``VectorStore.search_matrix`` states how)."""
+        return self._matrix_pairs(self._matrix_lines(self.vector_store.search_matrix(
+            sample, limit, filter_metadata=filter_metadata, vector_ids=vector_ids, seed=seed)))
+
+    async def vector_search_matrix_pairs_async(self, sample: int = 10, limit: int = 3,
+                                               filter_metadata: Optional[Dict[str, Any]] = None, vector_ids=None,
+                                               seed=None) -> List[Dict[str, Any]]:
+        return self._matrix_pairs(self._matrix_lines(await self.vector_store.search_matrix_async(
+            sample, limit, filter_metadata=filter_metadata, vector_ids=vector_ids, seed=seed)))
+
+    def vector_search_matrix_offsets(self, sample: int = 10, limit: int = 3, filter_metadata: Optional[Dict[str, Any]] = None,
+                                     vector_ids=None, seed=None) -> Dict[str, List[Any]]:
+        """``vector_search_matrix_pairs`` as a sparse matrix: ``{"offsets_row": [...], "offsets_col": [...], "scores": [...],
+        "ids": [...]}`` -- cell i says that ``ids[offsets_col[i]]`` is a neighbour of ``ids[offsets_row[i]]`` with
+        ``scores[i]``; the cells are in the order of the pairs."""
+        return self._matrix_offsets(self._matrix_lines(self.vector_store.search_matrix(
+            sample, limit, filter_metadata=filter_metadata, vector_ids=vector_ids, seed=seed)))
+
+    async def vector_search_matrix_offsets_async(self, sample: int = 10, limit: int = 3,
+                                                 filter_metadata: Optional[Dict[str, Any]] = None, vector_ids=None,
+                                                 seed=None) -> Dict[str, List[Any]]:
+        return self._matrix_offsets(self._matrix_lines(await self.vector_store.search_matrix_async(
+            sample, limit, filter_metadata=filter_metadata, vector_ids=vector_ids, seed=seed)))
 
     def vector_search_range(self, query_vector: List[float], threshold: float,
                             filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,
