@@ -1645,6 +1645,42 @@ def test_i8_second_stage_drops_rows_but_never_an_answer(native, metric, k):
         assert np.all(s1[9] == 0.0)
 
 
+@pytest.mark.parametrize("metric,k", [("cosine", 500), ("cosine", 2048), ("l2", 2048)])
+def test_i8_second_stage_at_large_k(native, metric, k):
+    """The second stage's launch at the k where its dynamic LDS request used to pass what a launch may ask for (64 KiB from
+    k = 482 without the function's limit raised, a CU's 160 KiB from k = 1205): refine_launch_for keeps it within 128 KiB by
+    running fewer waves (host_refine.h).  On the smallest corpus the batched path accepts at that k -- the sample's bounds
+    reach k from ceil(k / 8) tiles on, but the entry point asks for max(65 536, 1024 k) rows first -- the answers with and
+    without the stage are bit-identical and agree with the fp32 scan."""
+    n, d, nq = max(65_536, 1024 * k), 64, 20   # (d = 64: the shortest rows the int8 tiles take)
+    rng = np.random.default_rng(482 + k)
+    rows = rng.random((n, d), dtype=np.float32) - np.float32(0.5)
+    queries = rng.random((nq, d), dtype=np.float32) - np.float32(0.5)
+    if metric == "cosine":
+        rows, queries = O.normalize_rows_fast(rows), O.normalize_rows_fast(queries)
+    rows[1_000:1_040] = np.nan   # removed rows
+    with native.NativeIndex(d, metric=native.METRIC_L2 if metric == "l2" else native.METRIC_COSINE, capacity_rows=n) as ix:
+        ix.add(rows)
+        dq = ix.device_queries(queries)
+        d_idx, d_score = ix.alloc(nq * k * 8), ix.alloc(nq * k * 4)
+        out = {}
+        for refine in (0, 1):
+            ix.set_option("gemm8_refine", refine)
+            ix.search_batch_device(dq, nq, k, d_idx, d_score)
+            st = ix.batch_status(nq)
+            assert ix.get_option("last_gemm_family") == 3
+            out[refine] = (st["counts"].astype(np.int64), d_idx.download(np.int64, (nq, k)), d_score.download(np.float32, (nq, k)))
+        ix.set_option("gemm_min_queries", 1 << 30)   # the exact fp32 scan, query by query
+        ix.set_option("scan_shadow", 0)
+        s_idx, s_score = ix.search(queries[:3], k)
+    (c0, i0, s0), (c1, i1, s1) = out[0], out[1]
+    assert np.array_equal(i0, i1) and np.array_equal(s0.view(np.uint32), s1.view(np.uint32))
+    assert np.all(c1 <= c0) and np.all(c1 >= k)
+    for qi in range(3):
+        np.testing.assert_allclose(s1[qi], s_score[qi], rtol=1e-5, atol=2e-5)
+        _ids_match(i1[qi], s1[qi], s_idx[qi], s_score[qi], tie=1e-6)
+
+
 @pytest.mark.parametrize("metric,d,k", [("cosine", 384, 10), ("l2", 768, 100), ("cosine", 256, 10), ("l2", 100, 40)])
 def test_u8_sample_pass_for_several_queries_per_workgroup(native, metric, d, k):
     """scan8_sample4_kernel: on a shard whose sample does not stay cached the round's sample pass loads every sampled row

@@ -60,8 +60,9 @@ def tile_keeps(D, s_g, a_g, b_g, cn, s_q, E, M, tau, l2):
     """range_batch_bound_kernel, then gemm_i8_kernel<PHASE 1>'s fp32 chain (the exact epilogue; the prefilter in front of it is
     never stricter: tests/test_selection_bounds.py).  True = the pair is appended."""
     G = f32(GAMMA * f32(M) * f32(1.000001))
-    E = f32(f32(E) + f32(G * f32(1.000001)))
-    M = f32(f32(M) + f32(G * f32(1.000001)))
+    up = f32(1.0) + f32(1.1920929e-7)  # (the kernel takes both sums one ulp up)
+    E = f32(f32(f32(E) + f32(G * f32(1.000001))) * up)
+    M = f32(f32(f32(M) + f32(G * f32(1.000001))) * up)
     with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
         tau = f32(min(f32(tau), f32(1e38) * (f32(s_q) if s_q > 0 else f32(1.0))))
         if l2:

@@ -1933,11 +1933,10 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
       r.cn = ix->d_cn;
       r.qpar = ix->d_qpar;
       r.k = k;
-      const bool reg = k <= 128 && !ix->opt_lds_lists;
-      void (*fn)(RefineArgs) = l2 ? (reg ? refine_pairs_kernel<WDBX_METRIC_L2, true> : refine_pairs_kernel<WDBX_METRIC_L2, false>)
-                                  : (reg ? refine_pairs_kernel<WDBX_METRIC_COSINE, true> : refine_pairs_kernel<WDBX_METRIC_COSINE, false>);
-      r.n_lds = std::min<uint32_t>(cap, REFINE_R * 1024);
-      const size_t lds = std::max((size_t)r.n_lds * 4, (size_t)17 * k * sizeof(u64));
+      // (instance, waves, n_lds and LDS bytes: refine_launch_for -- within 128 KiB of LDS whatever k is, host_refine.h)
+      RefineLaunch rl;
+      HIP_TRY(refine_launch_for(l2 ? WDBX_METRIC_L2 : WDBX_METRIC_COSINE, k, cap, ix->opt_lds_lists != 0, &rl));
+      r.n_lds = rl.shape.n_lds;
       if (multi) {  // (one workgroup per query, one bad-row table per launch: a launch per class run, its class's table)
         for (const ClassRun& cr : runs) {
           RefineArgs rr = r;
@@ -1945,12 +1944,11 @@ static int enqueue_search_gemm8(wdbx_index* ix, const float* d_queries, int nq, 
           rr.count = r.count + cr.s0;
           rr.qpar = r.qpar + cr.s0;
           rr.gbad = gbad + (size_t)cr.row * ngroups;
-          hipLaunchKernelGGL(fn, dim3(cr.n), dim3(1024), lds, ix->stream, rr);
+          HIP_TRY(enqueue_refine(ix->stream, rl, rr, cr.n));
         }
       } else {
-        hipLaunchKernelGGL(fn, dim3(nv), dim3(1024), lds, ix->stream, r);
+        HIP_TRY(enqueue_refine(ix->stream, rl, r, nv));
       }
-      HIP_TRY(hipGetLastError());
     }
     // exact fp32 scores of the kept rows (L2: the direct form sum (c - q)^2)
     hipLaunchKernelGGL(l2 ? rescore_kernel<WDBX_METRIC_L2> : rescore_kernel<WDBX_METRIC_COSINE>, dim3(64, nv), dim3(256), 0, ix->stream,

@@ -17,7 +17,7 @@
 //   max|c| of the group times max|q| is at least 1e-36; below that the guarantee is not claimed, as above 2^127.)  Two facts turn that into the tile test's own terms:
 //       |q|_2 = s_q |m + eps|_2 <= s_q (|m|_2 + |eps|_2) = M_q          (M_q is rounded up by the quantiser, whatever the query's scale)
 //       |c_r|_2 = s_g |n_r + delta_r|_2 <= a_r + b_r <= a_g + b_g
-//   so adding G = RANGE_BATCH_GAMMA M_q (rounded up) to BOTH E_q and M_q widens the test by G (a_g + b_g) >= gamma |q|_2 |c_r|_2:
+//   so adding G = RANGE_BATCH_GAMMA M_q (rounded up, and the sums as well) to BOTH E_q and M_q widens the test by G (a_g + b_g) >= gamma |q|_2 |c_r|_2:
 //   every row whose fp32 score reaches t has  real c.q >= t - gamma |c||q|  and passes.  Nothing here assumes unit rows or
 //   unit queries.  L2 decides on the fp32 sum of (c - q)^2, whose rounding the caller's tau already covers
 //   (range_selection_tau_l2); the widened E, M are kept for L2 too (a wider test is never wrong).
@@ -40,8 +40,11 @@ __global__ __launch_bounds__(256) void range_batch_bound_kernel(uint32_t nv, uin
   }
   f4 par = qpar[r];  // {s_q, E_q, M_q, 1 / s_q}
   const float G = RANGE_BATCH_GAMMA * par.z * 1.000001f;
-  par.y += G * 1.000001f;  // (a non-finite query has E = +inf already and stays there)
-  par.z += G * 1.000001f;
+  // (the sums are taken one ulp UP: rounded to nearest, E + G loses up to half an ulp of E -- far more than G's own margins,
+  // G = 2e-6 M being a few ulps of M and of a typical E -- and the widening would fall short of RANGE_BATCH_GAMMA M)
+  constexpr float ULP_UP = 1.0f + 1.1920929e-7f;  // 1 + 2^-23: x * ULP_UP >= x + ulp(x)
+  par.y = (par.y + G * 1.000001f) * ULP_UP;  // (a non-finite query has E = +inf already and stays there)
+  par.z = (par.z + G * 1.000001f) * ULP_UP;
   qpar[r] = par;
   tau[r] = fminf(tau_in[r], 1e38f * (par.x > 0.f ? par.x : 1.0f));
 }

@@ -1,5 +1,6 @@
 // kernels_tiles8.h -- batched queries on the int8 matrix cores over a group-scaled i8 shadow copy (inner product / cosine).
 // Part of the single translation unit wdbx_hip.hip (included there, in order); not a standalone header.
+#include "host_refine.h"  // (device-free: the launch shape of refine_pairs_kernel)
 
 // ------------------------------------------------------------------------------------------------
 // int8 SELECTION tiles (default batched path for inner product / cosine, rows up to 1536 bytes of i8 shadow).
@@ -890,7 +891,7 @@ struct RefineArgs {
   const float* cn;    // L2: squared norms
   const f4* qpar;     // {s_q, E_q, M_q, 1 / s_q} per query of the block
   int k;
-  uint32_t n_lds;     // candidates per query the launch's dynamic LDS holds (4 bytes each; <= REFINE_R * 1024)
+  uint32_t n_lds;     // candidates per query the launch's dynamic LDS holds (4 bytes each; <= REFINE_R * blockDim.x)
 };
 
 // an entry's row and dot product, and what its bounds need from memory (all loads issued together)
@@ -930,15 +931,17 @@ __device__ __forceinline__ bool refine_bounds(const RefineEntry& r, const f4 p, 
     lb = w - err * 1.000001f - 4e-7f * fabsf(w);
     ub = w + err * 1.00001f + 4e-6f * (fabsf(w) + err) + gt.x * p.x;  // (+ one unit of D, as the tile kernel's threshold)
   }
+  // (a group that does not vouch: no bound of its rows is believed, whatever its a_g, b_g say -- the library's own tables
+  // give such a group a_g = +inf, which says the same)
   if (!(gt.w == 1.0f) || !(lb == lb)) lb = -INFINITY;
-  if (!(ub == ub)) ub = INFINITY;
+  if (!(gt.w == 1.0f) || !(ub == ub)) ub = INFINITY;
   return true;
 }
 
 // n_lds: entries whose upper bounds the dynamic LDS holds (4 bytes each; at most REFINE_R per thread) -- the usual case
 // (about 1 200 candidates per query): tau2 by block_kth_threshold over lower bounds kept in registers.  Beyond it (large k,
-// huge sample strides): the wave lists of the merge kernels.
-constexpr int REFINE_R = 8;
+// huge sample strides): the wave lists of the merge kernels.  The workgroup's waves, n_lds and the LDS bytes: refine_shape
+// (host_refine.h: REFINE_R and the LDS rule), through refine_launch_for below; every loop strides by blockDim.x.
 template <int METRIC, bool REG>
 __global__ __launch_bounds__(1024) void refine_pairs_kernel(RefineArgs a) {
   extern __shared__ u64 lds_lists[];
@@ -1034,6 +1037,29 @@ __global__ __launch_bounds__(1024) void refine_pairs_kernel(RefineArgs a) {
     __syncthreads();
   }
   if (threadIdx.x == 0) a.count[q] = kept;
+}
+
+// Host side of a refine launch, free of any index state (host_index.h and the tests' kernel harness both go through it):
+// the shape from refine_shape (host_refine.h), the instance, and the function's dynamic LDS limit raised where the request
+// passes 64 KiB.  Fill RefineArgs::n_lds from shape.n_lds.
+struct RefineLaunch {
+  void (*fn)(RefineArgs);
+  RefineShape shape;
+};
+static hipError_t refine_launch_for(int metric, int k, uint32_t cap, bool lds_lists, RefineLaunch* out) {
+  RefineLaunch rl;
+  rl.shape = refine_shape(k, cap, lds_lists);
+  const bool l2 = metric == WDBX_METRIC_L2, reg = rl.shape.reg;
+  rl.fn = l2 ? (reg ? refine_pairs_kernel<WDBX_METRIC_L2, true> : refine_pairs_kernel<WDBX_METRIC_L2, false>)
+             : (reg ? refine_pairs_kernel<WDBX_METRIC_COSINE, true> : refine_pairs_kernel<WDBX_METRIC_COSINE, false>);
+  *out = rl;
+  if (rl.shape.raise) return hipFuncSetAttribute((const void*)rl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rl.shape.lds);
+  return hipSuccess;
+}
+// one workgroup per query of r.count[0 .. nq)
+static hipError_t enqueue_refine(hipStream_t stream, const RefineLaunch& rl, const RefineArgs& r, int nq) {
+  hipLaunchKernelGGL(rl.fn, dim3(nq), dim3(rl.shape.waves * 64), rl.shape.lds, stream, r);
+  return hipGetLastError();
 }
 
 // a_ref, b_ref for the prefilter epilogue: the largest a_g, b_g among the ORDINARY groups -- finite bounds no larger than

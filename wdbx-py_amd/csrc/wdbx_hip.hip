@@ -28,6 +28,8 @@
 //                           bits, the low two bits only of the rows the four-bit bound cannot rule out; its quantiser
 //   kernels_range.h         range search: range_scan_kernel (fp32, every row scored exactly), range_filter_kernel (exact
 //                           scores of the u8 selection's candidates); wave-aggregated appends, no k
+//   host_refine.h           the device-free launch shape of refine_pairs_kernel (included by kernels_tiles8.h): instance, waves,
+//                           n_lds and dynamic LDS bytes within 128 KiB for every k
 //   kernels_range_batch.h   range_batch_bound_kernel: the selection thresholds and the widened bound of a block of range queries in
 //                           front of the int8 tiles' full pass (wdbx_index_range_search_batch)
 //   host_range_batch.h      that call's route, its blocks of up to 256 queries, buffer sizes and per-query fallback bookkeeping
