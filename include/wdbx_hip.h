@@ -89,6 +89,27 @@ int wdbx_index_clear(wdbx_index* idx);
 int wdbx_index_add(wdbx_index* idx, const float* rows, uint64_t n, int normalize, uint64_t* first_row_out);
 /* overwrite stored rows [first_row, first_row+n) (replace_vector / zero-on-remove) */
 int wdbx_index_set_rows(wdbx_index* idx, uint64_t first_row, const float* rows, uint64_t n, int normalize);
+/* Batch upsert and delete of LISTED rows (the write side of batch_store / delete): overwrite the stored rows row_ids[0 .. n)
+ * with rows[n, dim] (in the order of row_ids), or turn them into removed rows, in one call.
+ *   row_ids is strictly increasing and every row lies below the index size; a list that is not strictly increasing, a row at
+ *   or past the size, or a null pointer with n > 0 is WDBX_E_INVALID (wdbx_index_search_rows' rule for its list) and nothing
+ *   is written.  n == 0 is a no-op that returns WDBX_OK.
+ *   wdbx_index_remove_rows writes the NaN tombstone a removed row holds (quiet NaN in every element: never a result on any
+ *   path); it uploads no row data, the kernel writes the NaN.
+ * Contract.  After the call the fp32 rows are exactly what wdbx_index_set_rows called once per listed row with the same
+ * normalize (for a removal: with a row of NaN) would have left, and every derived copy that exists -- cached norms, bf16, the
+ * int8 groups with their scales and bad-row words, u8 and its scales, u6, the two u42 planes and their records -- is the same
+ * bit for bit: both forms run the same per-row device functions.  (One exception below a copy's horizon only: an int8 group
+ * that the copy's coverage cuts is quantised from the group's rows as they are at the end of the call, not as they were when
+ * its last covered row was written; the rows behind the coverage are re-quantised by the lazy pick-up in both cases.)  Rows
+ * past a copy's coverage stay for the lazy pick-up of the next search, as with wdbx_index_set_rows, and the same validity flags
+ * fall (group maxima, norm statistics, group reference bounds).  Labels are left alone.  No other entry point changes.
+ * Cost.  One upload of the list and one of the rows (in rounds of at most 256 MiB), then per round one scatter launch, one
+ * launch that refreshes every per-row copy of the listed rows and one for the int8 groups the list touches: the number of
+ * launches does not depend on n beyond the rounds (get_option "last_update_launches").  Both calls hold the handle's mutex
+ * and return when the device is done, as wdbx_index_set_rows does. */
+int wdbx_index_set_rows_at(wdbx_index* idx, const uint64_t* row_ids, uint64_t n, const float* rows, int normalize);
+int wdbx_index_remove_rows(wdbx_index* idx, const uint64_t* row_ids, uint64_t n);
 /* keep exactly the stored rows src_rows[0 .. n_keep) (strictly increasing row numbers), moved down to rows
  * 0 .. n_keep - 1 in that order; everything else is dropped.  The compaction behind the backend's optimize()
  * (the reference rebuilds its index there, indexing.py:1124-1149): removed rows are NaN tombstones that every scan

@@ -218,6 +218,11 @@ struct wdbx_index {
   DevBuf<char> d_grp{&bufs};
   int last_groups_path = 0;  // 0 nothing launched, 1 ran
   int64_t last_groups_tasks = 0, last_groups_rounds = 0;
+  // writes of listed rows (wdbx_index_set_rows_at / wdbx_index_remove_rows, host_update.h): the call's row list followed by its
+  // distinct int8 groups, and the block of caller rows one scatter round carries; kernel launches of the last such call
+  DevBuf<uint32_t> d_upd_list{&bufs};
+  DevBuf<float> d_upd_rows{&bufs};
+  int64_t last_update_launches = 0;
   // profiling
   bool profile = false;
   EventPool scan_ev, merge_ev, gemm_ev, sample_ev;
@@ -2071,6 +2076,86 @@ static int upload_rows(wdbx_index* ix, uint64_t first, const float* rows, uint64
   }
   if (first < ix->shadow42_rows && ix->d_rows42) HIP_TRY(launch_rows_to_u42(ix, first, std::min(end, ix->shadow42_rows)));
   HIP_TRY(hipStreamSynchronize(ix->stream));
+  return WDBX_OK;
+}
+
+// ---- writes of listed rows (kernels_update.h, host_update.h) ------------------------------------------------------------
+// ids: the call's validated list (strictly increasing, below ix->n), narrowed.  rows: [n, dim] in list order, or null for a
+// removal (the scatter writes the NaN tombstone and nothing is uploaded).  What upload_rows does for a range, for the listed
+// rows: the rows to their places (in rounds of UPDATE_ROUND_BYTES of caller rows), then every derived copy for exactly the
+// listed rows it covers -- one refresh launch for the per-row copies, one for the int8 groups the list touches.  The number of
+// launches does not depend on n beyond the rounds (read-only option "last_update_launches").  Returns when the device is done.
+constexpr size_t UPDATE_KEEP_BYTES = 16u << 20;  // a larger block of caller rows is released at the end of its call
+static int update_rows_at(wdbx_index* ix, const uint32_t* ids, uint64_t n, const float* rows, int normalize) {
+  UpdateCoverage cov;
+  cov.cn = ix->d_cn ? ix->cn_rows : 0;
+  cov.bf16 = ix->d_rows16 ? ix->shadow_rows : 0;
+  cov.i8g = ix->d_rows8g ? ix->shadowg_rows : 0;
+  cov.u8 = ix->d_rows8 ? ix->shadow8_rows : 0;
+  cov.u6 = ix->d_rows6 ? ix->shadow6_rows : 0;
+  cov.u42 = ix->d_rows42 ? ix->shadow42_rows : 0;
+  const UpdatePlan p = update_plan(ids, n, (uint32_t)ix->dim, cov, rows != nullptr);
+  ix->last_update_launches = p.launches;
+  if (!n) return WDBX_OK;
+  int rc = ix->d_upd_list.grow((size_t)(n + p.groups.size()) * sizeof(uint32_t));
+  if (rc) return rc;
+  const uint32_t* d_list = ix->d_upd_list;
+  const uint32_t* d_groups = d_list + n;
+  HIP_TRY(hipMemcpyAsync(ix->d_upd_list, ids, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+  if (!p.groups.empty())
+    HIP_TRY(hipMemcpyAsync(ix->d_upd_list + n, p.groups.data(), p.groups.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+  if (rows && (rc = ix->d_upd_rows.grow((size_t)std::min<uint64_t>(n, p.round_rows) * ix->dim * sizeof(float)))) return rc;
+  for (uint64_t round = 0; round < p.rounds; ++round) {
+    const uint64_t i0 = update_round_first(p, round), c = update_round_count(p, round);
+    if (rows)  // (stream order keeps this copy behind the scatter that read the block's previous contents)
+      HIP_TRY(hipMemcpyAsync(ix->d_upd_rows, rows + (size_t)i0 * ix->dim, (size_t)c * ix->dim * sizeof(float), hipMemcpyHostToDevice, ix->stream));
+    hipLaunchKernelGGL(update_scatter_kernel, dim3(update_rows_grid(c)), dim3(256), 0, ix->stream,
+                       rows ? (const float*)ix->d_upd_rows : (const float*)nullptr, d_list, (u64)i0, (u64)c, (uint32_t)ix->dim, (uint32_t)ix->pitch,
+                       (float*)ix->d_rows, normalize);
+    HIP_TRY(hipGetLastError());
+  }
+  // the validity flags upload_rows drops for an overwritten row of the same copies
+  if (p.n_cn) {
+    ix->gmax_valid = false;
+    ix->cn_stats_dirty = true;
+  }
+  if (p.n_refresh) {
+    UpdateArgs a = {};
+    a.rows = ix->d_rows;
+    a.list = d_list;
+    a.dim = (uint32_t)ix->dim;
+    a.pitch = (uint32_t)ix->pitch;
+    a.n_cn = p.n_cn, a.n_16 = p.n_16, a.n_8 = p.n_8, a.n_6 = p.n_6, a.n_42 = p.n_42;
+    a.cn = ix->d_cn;
+    a.rows16 = (__bf16*)ix->d_rows16.p;
+    a.pitch16 = ix->pitch16;
+    a.rows8 = ix->d_rows8;
+    a.pitch8 = ix->pitch8;
+    a.scale8 = ix->d_scale8;
+    if (p.n_6) {
+      a.units6 = ix->units6;
+      a.codes6 = ix->d_rows6;
+      a.sa6 = (f2v*)(ix->d_rows6 + (size_t)ix->rows6_tiles * ix->units6 * 192);
+    }
+    if (p.n_42) {
+      a.units42 = ix->units42;
+      a.lpitch42 = u42_lpitch(ix->units42);
+      a.h42 = ix->d_rows42;
+      a.sa42 = u42_sa4(ix);
+      a.lrec42 = u42_lrec(ix);
+    }
+    hipLaunchKernelGGL(update_refresh_kernel, dim3(update_rows_grid(p.n_refresh)), dim3(256), 0, ix->stream, a);
+    HIP_TRY(hipGetLastError());
+  }
+  if (!p.groups.empty()) {  // whole groups: a group's scale depends on all of its rows
+    hipLaunchKernelGGL(rows_to_i8g_list_kernel, dim3(rows_to_i8g_list_grid(p.groups.size())), dim3(256), 0, ix->stream,
+                       (const float*)ix->d_rows, d_groups, (u64)p.groups.size(), (u64)ix->n, (uint32_t)ix->dim, (uint32_t)ix->pitch,
+                       ix->d_rows8g, ix->pitch8g, ix->d_groups8, ix->d_gbad8);
+    HIP_TRY(hipGetLastError());
+    ix->gref_valid = false;
+  }
+  HIP_TRY(hipStreamSynchronize(ix->stream));  // (ids, the plan's groups and the caller's rows are free again)
+  if (ix->d_upd_rows.bytes > UPDATE_KEEP_BYTES) return ix->d_upd_rows.release();
   return WDBX_OK;
 }
 

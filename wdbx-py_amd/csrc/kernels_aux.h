@@ -6,6 +6,20 @@
 // ------------------------------------------------------------------------------------------------
 // cn[r] = sum c^2 (one wave per row) and the running maximum of cn (float bits of non-negative values
 // order like unsigned integers)
+// (one row's sum, by the whole wave: every lane returns it.  Shared with the list form of kernels_update.h)
+__device__ __forceinline__ float row_sqnorm(const f4* p, uint32_t pitch4, int lane) {
+  float s = 0.f;
+  for (uint32_t c = lane; c < pitch4; c += 64) {
+    const f4 v = __builtin_nontemporal_load(p + c);
+    s = fmaf(v.x, v.x, s);
+    s = fmaf(v.y, v.y, s);
+    s = fmaf(v.z, v.z, s);
+    s = fmaf(v.w, v.w, s);
+  }
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  return s;
+}
+
 __global__ __launch_bounds__(256) void row_sqnorm_kernel(const float* rows, u64 r0, u64 n, uint32_t pitch, float* cn,
                                                          uint32_t* cn_max_bits) {
   const int lane = threadIdx.x & 63;
@@ -14,16 +28,7 @@ __global__ __launch_bounds__(256) void row_sqnorm_kernel(const float* rows, u64 
   uint32_t wmax = 0, wcnt = 0;  // this wave's running maximum: ONE atomic per wave at the end, not one per row
   float wsum = 0.f;
   for (u64 r = r0 + wave; r < n; r += nw) {
-    const f4* p = (const f4*)(rows + r * pitch);
-    float s = 0.f;
-    for (uint32_t c = lane; c < pitch4; c += 64) {
-      const f4 v = __builtin_nontemporal_load(p + c);
-      s = fmaf(v.x, v.x, s);
-      s = fmaf(v.y, v.y, s);
-      s = fmaf(v.z, v.z, s);
-      s = fmaf(v.w, v.w, s);
-    }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const float s = row_sqnorm((const f4*)(rows + r * pitch), pitch4, lane);
     if (lane == 0) {
       cn[r] = s;
       if (s == s) wmax = max(wmax, __float_as_uint(s));
@@ -255,16 +260,18 @@ __global__ __launch_bounds__(256) void probe_read_kernel(const f4* p, u64 n_quad
 }
 
 // one wave per row: x / sqrt(sum x^2) when the norm is > 0 (indexing.py:851-856)
+// (one row in place, by the whole wave; a lane reads and writes its own elements only.  Shared with kernels_update.h)
+__device__ __forceinline__ void normalize_row(float* p, uint32_t pitch, int lane) {
+  float s = 0.f;
+  for (uint32_t c = lane; c < pitch; c += 64) s = fmaf(p[c], p[c], s);
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  const float nrm = sqrtf(s);
+  if (nrm > 0.f)
+    for (uint32_t c = lane; c < pitch; c += 64) p[c] = p[c] / nrm;
+}
+
 __global__ __launch_bounds__(256) void normalize_rows_kernel(float* rows, u64 n, uint32_t pitch) {
   const int lane = threadIdx.x & 63;
   const u64 wave = (u64)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (u64)gridDim.x * 4;
-  for (u64 r = wave; r < n; r += nw) {
-    float* p = rows + r * pitch;
-    float s = 0.f;
-    for (uint32_t c = lane; c < pitch; c += 64) s = fmaf(p[c], p[c], s);
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    const float nrm = sqrtf(s);
-    if (nrm > 0.f)
-      for (uint32_t c = lane; c < pitch; c += 64) p[c] = p[c] / nrm;
-  }
+  for (u64 r = wave; r < n; r += nw) normalize_row(rows + r * pitch, pitch, lane);
 }

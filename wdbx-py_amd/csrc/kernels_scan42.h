@@ -652,13 +652,10 @@ static scan42_mfma_fn pick_scan42_mfma(uint32_t units) { return u42_mfma_has_ins
 
 // rows [r0, n) fp32 -> h plane, {s, a4} and l records, one wave per row, one lane per 16 elements (half a unit): the walk of
 // rows_to_u6_kernel, so that a6 is its a bit for bit.  units = 32-element units (the pitch is a multiple of 32).
-__global__ __launch_bounds__(256) void rows_to_u42_kernel(const float* rows, u64 r0, u64 n, uint32_t dim, uint32_t pitch,
-                                                          uint32_t units, uint32_t* hcodes, f2v* sa4, uint32_t* lrec,
-                                                          uint32_t lpitch) {
-  const int lane = threadIdx.x & 63;
-  const u64 wave = (u64)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (u64)gridDim.x * 4;
-  for (u64 r = r0 + wave; r < n; r += nw) {
-    const float* p = rows + r * pitch;
+// (row r, its fp32 elements at p, by the whole wave.  Shared with the list form of kernels_update.h)
+__device__ __forceinline__ void row_to_u42(const float* p, u64 r, uint32_t dim, uint32_t units, uint32_t* hcodes, f2v* sa4, uint32_t* lrec,
+                                           uint32_t lpitch, int lane) {
+  {
     const U6RowScale rs = u6_row_scale(p, dim, lane);
     float rr = 0.f, rr4 = 0.f;  // sums of squared residuals in units of s: against the six-bit code, against 4 h + 1.5
     uint32_t* hout = hcodes + ((size_t)(r >> 6) * units * 64 + (size_t)(r & 63)) * 4;
@@ -692,6 +689,14 @@ __global__ __launch_bounds__(256) void rows_to_u42_kernel(const float* rows, u64
       lout[units * 2] = __float_as_uint(sa.y);
     }
   }
+}
+
+__global__ __launch_bounds__(256) void rows_to_u42_kernel(const float* rows, u64 r0, u64 n, uint32_t dim, uint32_t pitch,
+                                                          uint32_t units, uint32_t* hcodes, f2v* sa4, uint32_t* lrec,
+                                                          uint32_t lpitch) {
+  const int lane = threadIdx.x & 63;
+  const u64 wave = (u64)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (u64)gridDim.x * 4;
+  for (u64 r = r0 + wave; r < n; r += nw) row_to_u42(rows + r * pitch, r, dim, units, hcodes, sa4, lrec, lpitch, lane);
 }
 
 // ---- host side ---------------------------------------------------------------------------------

@@ -262,13 +262,10 @@ __device__ __forceinline__ f2v u6_row_pair(const U6RowScale& rs, float rr, uint3
   return rs.has_nan ? f2v{-1.0f, 0.f} : !rs.finite ? f2v{NAN, 0.f} : f2v{rs.s, a};
 }
 
-// rows [r0, n) fp32 -> u6 shadow + {s, a} per row, one wave per row, one lane per unit of 16 elements
-__global__ __launch_bounds__(256) void rows_to_u6_kernel(const float* rows, u64 r0, u64 n, uint32_t dim, uint32_t pitch,
-                                                         uint32_t units, uint32_t* codes, f2v* sa) {
-  const int lane = threadIdx.x & 63;
-  const u64 wave = (u64)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (u64)gridDim.x * 4;
-  for (u64 r = r0 + wave; r < n; r += nw) {
-    const float* p = rows + r * pitch;
+// row r (its fp32 elements at p) -> its codes of the u6 shadow and its {s, a}, by the whole wave, one lane per unit of 16
+// elements.  Shared with the list form of kernels_update.h
+__device__ __forceinline__ void row_to_u6(const float* p, u64 r, uint32_t dim, uint32_t units, uint32_t* codes, f2v* sa, int lane) {
+  {
     const U6RowScale rs = u6_row_scale(p, dim, lane);
     float rr = 0.f;  // sum of squared residuals in units of s
     uint32_t* out = codes + ((size_t)(r >> 6) * units * 64 + (size_t)(r & 63)) * 3;
@@ -287,6 +284,14 @@ __global__ __launch_bounds__(256) void rows_to_u6_kernel(const float* rows, u64 
     const f2v pair = u6_row_pair(rs, rr, dim);
     if (lane == 0) sa[r] = pair;
   }
+}
+
+// rows [r0, n) fp32 -> u6 shadow + {s, a} per row, one wave per row
+__global__ __launch_bounds__(256) void rows_to_u6_kernel(const float* rows, u64 r0, u64 n, uint32_t dim, uint32_t pitch,
+                                                         uint32_t units, uint32_t* codes, f2v* sa) {
+  const int lane = threadIdx.x & 63;
+  const u64 wave = (u64)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (u64)gridDim.x * 4;
+  for (u64 r = r0 + wave; r < n; r += nw) row_to_u6(rows + r * pitch, r, dim, units, codes, sa, lane);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -330,13 +330,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 }
 
-// rows [r0, n) fp32 -> u8 shadow + per-row scale, one wave per row
-__global__ __launch_bounds__(256) void rows_to_u8_kernel(const float* rows, u64 r0, u64 n, uint32_t dim, uint32_t pitch,
-                                                         uint8_t* out, uint32_t pitch8, float* scale) {
-  const int lane = threadIdx.x & 63;
-  const u64 wave = (u64)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (u64)gridDim.x * 4;
-  for (u64 r = r0 + wave; r < n; r += nw) {
-    const float* p = rows + r * pitch;
+// row r (its fp32 elements at p) -> its bytes of the u8 shadow and its scale, by the whole wave.  Shared with the list form of
+// kernels_update.h
+__device__ __forceinline__ void row_to_u8(const float* p, u64 r, uint32_t dim, uint8_t* out, uint32_t pitch8, float* scale, int lane) {
+  {
     float mx = 0.f;
     bool finite = true, has_nan = false;
     for (uint32_t c = lane; c < dim; c += 64) {
@@ -360,6 +357,14 @@ __global__ __launch_bounds__(256) void rows_to_u8_kernel(const float* rows, u64 
     }
     if (lane == 0) scale[r] = sc;
   }
+}
+
+// rows [r0, n) fp32 -> u8 shadow + per-row scale, one wave per row
+__global__ __launch_bounds__(256) void rows_to_u8_kernel(const float* rows, u64 r0, u64 n, uint32_t dim, uint32_t pitch,
+                                                         uint8_t* out, uint32_t pitch8, float* scale) {
+  const int lane = threadIdx.x & 63;
+  const u64 wave = (u64)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (u64)gridDim.x * 4;
+  for (u64 r = r0 + wave; r < n; r += nw) row_to_u8(rows + r * pitch, r, dim, out, pitch8, scale, lane);
 }
 
 // workgroups of a rows_to_u8_kernel launch over `rows` rows: four waves = four rows per workgroup at a time

@@ -587,6 +587,14 @@ __global__ __launch_bounds__(512) void gemm_bf16w8_kernel(GemmArgs a) {
   }
 }
 
+// elements [c, c + 8) of row r of the bf16 shadow copy.  Shared with the list form of kernels_update.h
+__device__ __forceinline__ void row_piece_to_bf16(const float* rows, u64 r, uint32_t c, uint32_t pitch, __bf16* out, uint32_t pitch16) {
+  bh8 h;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) h[i] = to_bf16_sel((c + i < pitch) ? rows[r * pitch + c + i] : 0.0f);
+  *(bh8*)(out + r * pitch16 + c) = h;
+}
+
 // rows [r0, n) fp32 -> the bf16 shadow copy (round to nearest even), zero padded to its own pitch
 __global__ __launch_bounds__(256) void rows_to_bf16_kernel(const float* rows, u64 r0, u64 n, uint32_t pitch, __bf16* out,
                                                            uint32_t pitch16) {
@@ -594,10 +602,7 @@ __global__ __launch_bounds__(256) void rows_to_bf16_kernel(const float* rows, u6
   for (u64 e = (u64)blockIdx.x * 256 + threadIdx.x; e < total; e += (u64)gridDim.x * 256) {
     const u64 r = r0 + e / (pitch16 / 8);
     const uint32_t c = (uint32_t)(e % (pitch16 / 8)) * 8;
-    bh8 h;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) h[i] = to_bf16_sel((c + i < pitch) ? rows[r * pitch + c + i] : 0.0f);
-    *(bh8*)(out + r * pitch16 + c) = h;
+    row_piece_to_bf16(rows, r, c, pitch, out, pitch16);
   }
 }
 

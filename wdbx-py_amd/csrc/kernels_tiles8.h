@@ -613,12 +613,12 @@ static inline hipError_t enqueue_gemm8(hipStream_t stream, const Gemm8Launch& l,
 // residual |delta|_2, and the group's maxima a_g = s_g max |n|_2, b_g = s_g max |delta|_2 (rounded up).
 //   rows past n_rows inside the last group are written as zero rows.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void rows_to_i8g_kernel(const float* rows, u64 g0, u64 g1, u64 n_rows, uint32_t dim, uint32_t pitch,
-                                                          int8_t* out, uint32_t pitch8, f4* groups, u64* gbad) {
-  __shared__ float red[4][4];
-  __shared__ uint32_t redbad[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (u64 grp = g0 + blockIdx.x; grp < g1; grp += gridDim.x) {
+// (group grp by one workgroup of four waves; red and redbad are the workgroup's LDS words.  Shared with the group-list form of
+// kernels_update.h)
+__device__ __forceinline__ void group_to_i8g(const float* rows, u64 grp, u64 n_rows, uint32_t dim, uint32_t pitch, int8_t* out,
+                                             uint32_t pitch8, f4* groups, u64* gbad, float (&red)[4][4], uint32_t (&redbad)[4], int lane,
+                                             int wave) {
+  {
     // pass 1: wave w takes rows 16 w .. 16 w + 15 of the group
     float mx = 0.f;
     bool any_inf = false, any_bad = false;
@@ -712,6 +712,15 @@ __global__ __launch_bounds__(256) void rows_to_i8g_kernel(const float* rows, u64
       gbad[grp] = (u64)redbad[0] | ((u64)redbad[1] << 16) | ((u64)redbad[2] << 32) | ((u64)redbad[3] << 48);
     }
   }
+}
+
+__global__ __launch_bounds__(256) void rows_to_i8g_kernel(const float* rows, u64 g0, u64 g1, u64 n_rows, uint32_t dim, uint32_t pitch,
+                                                          int8_t* out, uint32_t pitch8, f4* groups, u64* gbad) {
+  __shared__ float red[4][4];
+  __shared__ uint32_t redbad[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (u64 grp = g0 + blockIdx.x; grp < g1; grp += gridDim.x)
+    group_to_i8g(rows, grp, n_rows, dim, pitch, out, pitch8, groups, gbad, red, redbad, lane, wave);
 }
 
 // workgroups of a rows_to_i8g_kernel launch over `groups` 64-row groups: one each

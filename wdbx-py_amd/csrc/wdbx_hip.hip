@@ -62,6 +62,10 @@
 //   kernels_groups.h        group_members_kernel, group_merge_kernel: stage 2 of wdbx_index_search_groups -- the best group_size rows of
 //                           each chosen label, scored along the label's run of the label order, and the merge of a run's segments
 //   host_groups.h           the runs of the label order, the dense label of a label value, that call's tasks, slot table and rounds
+//   kernels_update.h        update_scatter_kernel, update_refresh_kernel, rows_to_i8g_list_kernel: wdbx_index_set_rows_at /
+//                           wdbx_index_remove_rows -- a call's rows to their listed places (or the NaN tombstone), then every derived
+//                           copy of exactly those rows through the per-row functions the range quantisers call
+//   host_update.h           that call's coverage counts, distinct int8 groups, upload rounds and launch count
 //   host_multimask.h        a call with one row mask per query: the placement of its queries in the int8 tiles' query blocks
 //   host_selection.h        the plan of the selection rounds: sampled tiles, stride, candidate and pair capacities of the tile paths and
 //                           the u8 / u6 rounds, the masked sample's growth, the 1 GiB shadow rule
@@ -119,6 +123,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_recommend.h"  // (device-free as well: offsets, exclusion list, plan, short queries and splice of a recommend search)
 #include "host_discover.h"  // (device-free as well: pair offsets, plans, staged vectors, zones and splice of a discovery search)
 #include "host_groups.h"  // (device-free as well: label runs, dense label lookup, tasks, slot table and rounds of a groups search)
+#include "host_update.h"  // (device-free as well: coverage counts, distinct int8 groups, rounds and launch count of a write of listed rows)
 
 #define HIP_TRY(expr)                                                                        \
   do {                                                                                       \
@@ -167,6 +172,7 @@ static_assert(DISCOVER_MAX_PAIRS == WDBX_MAX_CONTEXT_PAIRS && DISCOVER_ZONES == 
 #include "kernels_groups.h"
 static_assert(GROUPS_MAX_SIZE_DEV == GROUPS_MAX_SIZE && GROUPS_MAX_SIZE == WDBX_MAX_GROUP_SIZE, "a wave's register list holds a group");
 static_assert(sizeof(GroupTaskDev) == sizeof(GroupTask) && sizeof(GroupTask) == 16, "the device reads the host's tasks");
+#include "kernels_update.h"
 #include "host_index.h"
 #include "host_group.h"
 
@@ -329,6 +335,28 @@ int wdbx_index_set_rows(wdbx_index* ix, uint64_t first_row, const float* rows, u
   if (!n) return WDBX_OK;
   DeviceGuard g(ix->device);
   return upload_rows(ix, first_row, rows, n, normalize);
+} WDBX_CATCH
+
+// the two writes of listed rows: rows == nullptr is the removal
+static int update_listed(wdbx_index* ix, const uint64_t* row_ids, uint64_t n, const float* rows, int normalize) {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  if (n && !row_ids) return fail(WDBX_E_INVALID, "row_ids is null");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  std::vector<uint32_t> ids32((size_t)n);
+  const uint64_t bad = subset_validate(row_ids, n, ix->n, ids32.data());
+  if (bad != n)
+    return fail(WDBX_E_INVALID, "row_ids must be strictly increasing row numbers below %llu (entry %llu)", (u64)ix->n, (u64)bad);
+  DeviceGuard g(ix->device);
+  return update_rows_at(ix, ids32.data(), n, rows, normalize);
+}
+
+int wdbx_index_set_rows_at(wdbx_index* ix, const uint64_t* row_ids, uint64_t n, const float* rows, int normalize) try {
+  if (n && !rows) return fail(WDBX_E_INVALID, "rows is null");
+  return update_listed(ix, row_ids, n, rows, normalize);
+} WDBX_CATCH
+
+int wdbx_index_remove_rows(wdbx_index* ix, const uint64_t* row_ids, uint64_t n) try {
+  return update_listed(ix, row_ids, n, nullptr, 0);
 } WDBX_CATCH
 
 int wdbx_index_get_rows(wdbx_index* ix, uint64_t first_row, uint64_t n, float* out_rows) try {
@@ -2826,6 +2854,7 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "last_rows_path")) return *value = ix->last_rows_path, WDBX_OK;
   if (name && !strcmp(name, "last_matrix_path")) return *value = ix->last_matrix_path, WDBX_OK;
   if (name && !strcmp(name, "last_matrix_rounds")) return *value = ix->last_matrix_rounds, WDBX_OK;
+  if (name && !strcmp(name, "last_update_launches")) return *value = ix->last_update_launches, WDBX_OK;
   if (name && !strcmp(name, "last_lists_path")) return *value = ix->last_lists_path, WDBX_OK;
   if (name && !strcmp(name, "last_lists_items")) return *value = ix->last_lists_items, WDBX_OK;
   if (name && !strcmp(name, "last_lists_rounds")) return *value = ix->last_lists_rounds, WDBX_OK;

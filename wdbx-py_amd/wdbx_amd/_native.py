@@ -59,6 +59,8 @@ SIGNATURES = {
     "wdbx_index_clear": (C.c_int, [C.c_void_p]),
     "wdbx_index_add": (C.c_int, [C.c_void_p, _f32p, C.c_uint64, C.c_int, _u64p]),
     "wdbx_index_set_rows": (C.c_int, [C.c_void_p, C.c_uint64, _f32p, C.c_uint64, C.c_int]),
+    "wdbx_index_set_rows_at": (C.c_int, [C.c_void_p, _u64p, C.c_uint64, _f32p, C.c_int]),
+    "wdbx_index_remove_rows": (C.c_int, [C.c_void_p, _u64p, C.c_uint64]),
     "wdbx_index_get_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, _f32p]),
     "wdbx_index_fill_synthetic": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _u64p]),
     "wdbx_index_compact": (C.c_int, [C.c_void_p, _u64p, C.c_uint64]),
@@ -304,6 +306,21 @@ class NativeIndex:
         arr = _as_f32(rows, self.dim)
         _check(self._lib.wdbx_index_set_rows(self._h, int(first_row), arr.ctypes.data_as(_f32p), arr.shape[0],
                                              int(normalize)))
+
+    def set_rows_at(self, rows_idx, rows, normalize: bool = False) -> None:
+        """Overwrite the stored rows ``rows_idx`` (strictly increasing row numbers) with ``rows[len(rows_idx), dim]`` in one
+        call: every derived copy is refreshed for exactly those rows, as ``set_rows`` once per row would leave it."""
+        ids = np.ascontiguousarray(rows_idx, dtype=np.uint64).reshape(-1)
+        arr = _as_f32(rows, self.dim) if ids.size else np.empty((0, self.dim), np.float32)
+        if arr.shape[0] != ids.size:
+            raise ValueError(f"{ids.size} row numbers for {arr.shape[0]} rows")
+        _check(self._lib.wdbx_index_set_rows_at(self._h, ids.ctypes.data_as(_u64p), ids.size, arr.ctypes.data_as(_f32p),
+                                                int(normalize)))
+
+    def remove_rows(self, rows_idx) -> None:
+        """Turn the stored rows ``rows_idx`` (strictly increasing) into removed rows (NaN: never a result) in one call."""
+        ids = np.ascontiguousarray(rows_idx, dtype=np.uint64).reshape(-1)
+        _check(self._lib.wdbx_index_remove_rows(self._h, ids.ctypes.data_as(_u64p), ids.size))
 
     def get_rows(self, first_row: int, n: int) -> np.ndarray:
         out = np.empty((int(n), self.dim), np.float32)

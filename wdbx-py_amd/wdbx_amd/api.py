@@ -264,6 +264,25 @@ async def search_matrix_offsets_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[
     return await wdbx.vector_search_matrix_offsets_async(**_matrix_arguments(payload))
 
 
+async def delete_vectors_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
+    """Batch delete (extension): body ``{"vector_ids": ["a", "b"]}`` or ``{"filter_metadata": {...}}`` -- exactly one of the
+    two -- -> ``{"deleted": n}``, the number of ids that were stored (``wdbx.delete_vectors_async`` /
+    ``wdbx.delete_by_filter_async``): one removal per shard, whatever the number of ids.  An empty filter is refused: it
+    would match everything."""
+    if not isinstance(payload, dict):
+        raise ValueError("request body must be an object")
+    vector_ids, flt = payload.get("vector_ids"), payload.get("filter_metadata")
+    if (vector_ids is None) == (flt is None):
+        raise ValueError("exactly one of vector_ids and filter_metadata must be given")
+    if vector_ids is not None:
+        if not isinstance(vector_ids, (list, tuple)) or not all(isinstance(v, str) for v in vector_ids):
+            raise ValueError("vector_ids must be a list of vector ids")
+        return {"deleted": await wdbx.delete_vectors_async(list(vector_ids))}
+    if not isinstance(flt, dict) or not flt:
+        raise ValueError("filter_metadata must be a non-empty object")
+    return {"deleted": await wdbx.delete_by_filter_async(flt)}
+
+
 async def range_search_endpoint(wdbx, payload: Dict[str, Any]) -> Dict[str, Any]:
     """Range form (extension): body ``{"query_vector": [...], "threshold": 0.8, "filter_metadata": null,
     "max_results": null}`` -> the ``search_endpoint`` response shape with EVERY vector whose similarity reaches

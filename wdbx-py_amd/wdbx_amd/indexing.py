@@ -454,22 +454,29 @@ class HipFlatIndex(VectorIndex):
         return await loop.run_in_executor(self.thread_pool, self.add, vector_id, vector)
 
     def _batch_add_unlocked(self, vectors: Dict[str, np.ndarray]) -> bool:
-        """Append many rows with one upload (indexing.py:921-968)."""
+        """Append many rows with one upload (indexing.py:921-968); ids that are already stored are overwritten in place with
+        ONE native call for all of them (``wdbx_index_set_rows_at``: the listed rows and every derived copy of them)."""
         if not vectors:
             return True
         try:
+            fresh_pos: Dict[str, int] = {}  # id -> position in fresh_rows
             fresh_ids, fresh_rows = [], []
+            stored: Dict[int, np.ndarray] = {}  # row -> its new contents (a dict cannot repeat a key: no row twice)
             for vector_id, vector in vectors.items():
                 row = self._prepare(vector)
                 existing = self._row_of(vector_id)
                 if existing is not None:
-                    self._native.set_rows(existing, row)
-                    self._dirty_rows.add(existing)
-                elif vector_id in fresh_ids:
-                    fresh_rows[fresh_ids.index(vector_id)] = row
+                    stored[existing] = row
+                elif vector_id in fresh_pos:
+                    fresh_rows[fresh_pos[vector_id]] = row
                 else:
+                    fresh_pos[vector_id] = len(fresh_ids)
                     fresh_ids.append(vector_id)
                     fresh_rows.append(row)
+            if stored:
+                order = sorted(stored)
+                self._native.set_rows_at(order, np.stack([stored[r] for r in order]))
+                self._dirty_rows.update(order)
             if fresh_rows:
                 first = self._native.add(np.stack(fresh_rows))
                 assert first == self.next_index
@@ -549,6 +556,12 @@ class HipFlatIndex(VectorIndex):
     def remove(self, vector_id: str) -> bool:
         with self._ingest_lock:
             return self._remove_unlocked(vector_id)
+
+    def remove_many(self, vector_ids) -> int:
+        """Remove every id of ``vector_ids`` that is stored, with one native call (``wdbx_index_remove_rows``); returns how
+        many were present.  What ``remove`` does per id, once per call."""
+        with self._ingest_lock:
+            return self._remove_many_unlocked(vector_ids)
 
     def clear(self) -> bool:
         with self._ingest_lock:
@@ -1094,9 +1107,46 @@ class HipFlatIndex(VectorIndex):
                 raise
             return False
 
+    def _remove_many_unlocked(self, vector_ids) -> int:
+        """``_remove_unlocked`` for many ids: unmap them all, then ONE ``remove_rows`` over their rows (sorted; the kernel
+        writes the NaN tombstones).  A native failure maps every id again, as the single removal does."""
+        explicit: Dict[str, int] = {}
+        implicit: Dict[str, int] = {}
+        for vector_id in vector_ids:
+            if vector_id in explicit or vector_id in implicit:
+                continue
+            row = self._row_of(vector_id)
+            if row is None:
+                continue
+            (explicit if vector_id in self.id_to_index else implicit)[vector_id] = row
+        if not explicit and not implicit:
+            return 0
+        for vector_id, row in explicit.items():
+            self.id_to_index.pop(vector_id)
+            self.index_to_id.pop(row, None)
+        self._implicit_removed.update(implicit.values())
+        rows = sorted(set(explicit.values()) | set(implicit.values()))
+        try:
+            self._native.remove_rows(rows)
+            self._dirty_rows.update(rows)
+            return len(explicit) + len(implicit)
+        except Exception as e:
+            logger.error("Error removing vectors from HIP index: %s", e)
+            for vector_id, row in explicit.items():
+                self.id_to_index[vector_id] = row
+                self.index_to_id[row] = vector_id
+            self._implicit_removed.difference_update(implicit.values())
+            if not self.swallow_errors:
+                raise
+            return 0
+
     async def remove_async(self, vector_id: str) -> bool:
         loop = asyncio.get_event_loop()
         return await loop.run_in_executor(self.thread_pool, self.remove, vector_id)
+
+    async def remove_many_async(self, vector_ids) -> int:
+        loop = asyncio.get_event_loop()
+        return await loop.run_in_executor(self.thread_pool, self.remove_many, list(vector_ids))
 
     def _clear_unlocked(self) -> bool:
         try:

@@ -1549,6 +1549,43 @@ class VectorStore:
             await asyncio.get_event_loop().run_in_executor(self.thread_pool, self._save_now)
         return True
 
+    def delete_many(self, vector_ids) -> int:
+        """``delete`` for many ids: the ids split by shard, ONE native removal per shard (``HipFlatIndex.remove_many``), the
+        bookkeeping of ``delete`` once per call.  Unknown ids are skipped; returns how many were present."""
+        by_shard: Dict[int, List[str]] = {}
+        seen = set()
+        for vector_id in vector_ids:
+            if vector_id in seen or not self._known(vector_id):
+                continue
+            seen.add(vector_id)
+            by_shard.setdefault(self._get_shard_for_id(vector_id), []).append(vector_id)
+        if not seen:
+            return 0
+        for shard, ids in by_shard.items():
+            self.indices[shard].remove_many(ids)
+        for vector_id in seen:
+            self.vectors.pop(vector_id, None)
+            self.metadata.pop(vector_id, None)
+            self._bulk_id_shard.pop(vector_id, None)
+        self._meta_version += 1  # cached push-down masks name rows by position: rebuild them
+        if self.config.get("VECTOR_STORE_SAVE_IMMEDIATELY", False):
+            self._save_now()
+        return len(seen)
+
+    async def delete_many_async(self, vector_ids) -> int:
+        ids = list(vector_ids)
+        return await asyncio.get_event_loop().run_in_executor(self.thread_pool, self.delete_many, ids)
+
+    def delete_by_filter(self, filter_metadata: Dict[str, Any]) -> int:
+        """Delete every stored id whose metadata matches ``filter_metadata`` (the matcher of the filtered searches, evaluated
+        on the host); an empty filter deletes nothing.  Returns how many ids were deleted."""
+        if not filter_metadata:
+            return 0
+        return self.delete_many([vid for vid in list(self.metadata) if self._matches_filter(vid, filter_metadata)])
+
+    async def delete_by_filter_async(self, filter_metadata: Dict[str, Any]) -> int:
+        return await asyncio.get_event_loop().run_in_executor(self.thread_pool, self.delete_by_filter, filter_metadata)
+
     def _set_metadata(self, vector_id: str, metadata: Dict[str, Any]) -> bool:
         if not self._known(vector_id):
             return False

@@ -347,6 +347,20 @@ class WDBX:
     async def delete_vector_async(self, vector_id: str) -> bool:
         return await self.vector_store.delete_async(vector_id)
 
+    def delete_vectors(self, vector_ids: List[str]) -> int:
+        """Extension: delete many ids in one call (one native removal per shard); returns how many were stored."""
+        return self.vector_store.delete_many(vector_ids)
+
+    async def delete_vectors_async(self, vector_ids: List[str]) -> int:
+        return await self.vector_store.delete_many_async(vector_ids)
+
+    def delete_by_filter(self, filter_metadata: Dict[str, Any]) -> int:
+        """Extension: delete every id whose metadata matches the filter; returns how many were deleted."""
+        return self.vector_store.delete_by_filter(filter_metadata)
+
+    async def delete_by_filter_async(self, filter_metadata: Dict[str, Any]) -> int:
+        return await self.vector_store.delete_by_filter_async(filter_metadata)
+
     def update_metadata(self, vector_id: str, metadata: Dict[str, Any]) -> bool:
         return self.vector_store.update_metadata(vector_id, metadata)
 
