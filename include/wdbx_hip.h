@@ -225,6 +225,42 @@ int wdbx_index_search_rows(wdbx_index* idx, const float* queries, int nq, int k,
 int wdbx_index_search_matrix(wdbx_index* idx, const uint64_t* row_ids, uint64_t n_ids, int k,
                              int64_t* out_idx /* [n_ids, k] */, float* out_score /* [n_ids, k] */);
 
+/* ---- nearest-centre assignment: the transposed search ---- */
+/* For EVERY stored row (or those a mask allows), which of a few given vectors is nearest: cluster assignment, prototype /
+ * zero-shot classification, the inner step of k-means.  centers is host memory [n_centers, dim].  Blocking, host buffers; each
+ * of the four outputs may be null, not all of them.
+ *   out_center[r] = the centre with the best score for stored row r -- the handle's metric: largest inner product, or smallest
+ *   squared distance for L2 -- judged on exact_score's own fp32 arithmetic: the value wdbx_index_search_rows returns for
+ *   query = that centre and row r.  Equal score bits go to the lowest centre index.  out_score[r] is that value, bit for bit,
+ *   in the caller's convention (a positive squared distance for L2).
+ *   out_center[r] = -1 and out_score[r] = 0 when row r was removed, when the mask excludes it, or when every one of its scores
+ *   is NaN (a row with a NaN element).  A centre with a NaN element is never chosen.
+ *   normalize_centers acts as normalize_queries does (cosine only; a zero centre stays zero).
+ *   mask_words / mask_word_count as wdbx_index_search_masked_n (NULL / 0 = every row).
+ *   out_sums[c] = the fp32 sum of the stored rows assigned to c, as stored; out_counts[c] = their number.  No floating-point
+ *   atomics: the rows are cut into P consecutive ranges (get_option "last_assign_partials"), a range's rows are added to its
+ *   own partial sums in row order, and the partials are added in range order -- bit-identical from run to run.  The pass reads
+ *   every assigned row once.
+ *   How: a tile pass on the fp32 matrix cores (v_mfma_f32_32x32x2_f32) with the centres as the M operand and the stored rows as
+ *   the N operand, in blocks of up to 128 centres (get_option "last_assign_center_blocks"), keeps each row's best, its centre
+ *   and its second best in registers.  A row whose best beats its second best by more than twice the sum of the rigorous error
+ *   bounds of the tile arithmetic and of exact_score's is CERTAIN: its tile-pass winner is provably exact_score's.  Every other
+ *   row (get_option "last_assign_ambiguous") is decided by an exact pass over all centres.  A returned score is always
+ *   exact_score's; the launch that computes the certain rows' scores is skipped when out_score is null.  get_option
+ *   "last_assign_launches": kernel launches of the last call.
+ *   WDBX_E_INVALID: n_centers outside [1, WDBX_MAX_CENTERS], centers null, all four outputs null, a mask shorter than
+ *   ceil(rows / 32) words (checked under the handle's lock).  An empty index is WDBX_OK and launches nothing (sums and counts
+ *   are zero).  A refused call leaves the handle usable.
+ *   out_center / out_score must hold one entry per row the index holds WHEN THE CALL RUNS (the count is read under the handle's
+ *   lock and is not passed in): a caller sizes them from wdbx_index_size and keeps every wdbx_index_add / wdbx_index_fill_synthetic
+ *   on this handle out until the call has returned.  out_sums / out_counts are sized by n_centers alone.
+ *   The call holds the handle's mutex to its end.  Nothing of the call stays valid in the handle. */
+#define WDBX_MAX_CENTERS 4096
+int wdbx_index_assign(wdbx_index* idx, const float* centers /* host [n_centers, dim] */, int n_centers,
+                      int normalize_centers, const uint32_t* mask_words, uint64_t mask_word_count,
+                      int32_t* out_center /* [rows] or NULL */, float* out_score /* [rows] or NULL */,
+                      float* out_sums /* [n_centers, dim] or NULL */, uint64_t* out_counts /* [n_centers] or NULL */);
+
 /* ---- search among listed rows, one row list PER QUERY in one batched call ------ */
 /* What wdbx_index_search_rows answers for one list, for a batch whose queries each name their own list (a rerank stage's
  * candidates, a selective filter per tenant): query i is ranked among the rows of list query_list[i].  The lists come back to

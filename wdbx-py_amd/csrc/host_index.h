@@ -223,6 +223,17 @@ struct wdbx_index {
   DevBuf<uint32_t> d_upd_list{&bufs};
   DevBuf<float> d_upd_rows{&bufs};
   int64_t last_update_launches = 0;
+  // nearest-centre assignment (wdbx_index_assign, host_assign.h): the call's prepared centres; their norms followed by the words
+  // {largest centre norm, listed rows}; every row's centre and score; the ambiguous rows; the sums pass's partials; the sums and
+  // counts before their download.  What the last call did.
+  DevBuf<float> d_asg_centres{&bufs};
+  DevBuf<float> d_asg_aux{&bufs};
+  DevBuf<int32_t> d_asg_center{&bufs};
+  DevBuf<float> d_asg_score{&bufs};
+  DevBuf<u64> d_asg_list{&bufs};
+  DevBuf<char> d_asg_part{&bufs};
+  DevBuf<char> d_asg_out{&bufs};
+  int64_t last_assign_ambiguous = 0, last_assign_launches = 0, last_assign_center_blocks = 0, last_assign_partials = 0;
   // profiling
   bool profile = false;
   EventPool scan_ev, merge_ev, gemm_ev, sample_ev;

@@ -40,6 +40,10 @@
 //   kernels_matrix.h        matrix_kernel: the distance matrix among listed rows (wdbx_index_search_matrix): subset_kernel with the
 //                           listed rows themselves as the queries, read where they lie, each one's own list position left out
 //   host_matrix.h           that call's plan: subset_plan's route, anchor block and grid, the instance and the rounds
+//   kernels_assign.h        assign_tile_kernel: nearest-centre assignment (wdbx_index_assign), the transposed search -- every stored
+//                           row against a few given vectors on the fp32 matrix cores, a top-1 per row folded in registers; the exact
+//                           pass over the rows the tile pass cannot vouch for, the winner's exact score, per-centre sums
+//   host_assign.h           that call's argument checks, centre blocks, LDS, grids, partial sums and the certainty bound's coefficients
 //   kernels_rowlists.h      rowlists_kernel: the same scores for a call with one row list PER QUERY (wdbx_index_search_row_lists),
 //                           one workgroup per (chunk of a list, block of its queries) work item of host_rowlists.h
 //   kernels_labels.h        label_keys_kernel, label_rank_kernel: the full pass of wdbx_index_search_distinct (at most one row per
@@ -113,6 +117,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_calls.h"  // (device-free as well: mask popcount, padded query copies, host ranking of keys, class-by-class loop)
 #include "host_subset.h"  // (device-free as well: row-list validation, route and grid sizing of a search among listed rows)
 #include "host_matrix.h"  // (device-free as well: route, anchor block, instance and rounds of a distance matrix among listed rows)
+#include "host_assign.h"  // (device-free as well: argument checks, centre blocks, LDS, grids, partials and bound of an assignment)
 #include "host_multimask.h"  // (device-free as well: where the queries of a call with a mask per query sit in the tile blocks)
 #include "host_selection.h"  // (device-free as well: the sample, stride and capacities of the selection rounds)
 #include "host_scan_plan.h"  // (device-free as well: the fp32 scan and range forms of a pitch, grid / list / chunk / LDS numbers of a scan)
@@ -158,6 +163,8 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "kernels_rowblock.h"
 #include "kernels_subset.h"
 #include "kernels_matrix.h"
+#include "kernels_assign.h"
+static_assert(ASSIGN_MAX_CENTERS == WDBX_MAX_CENTERS, "the plan's limit is the header's");
 #include "kernels_rowlists.h"
 #include "kernels_labels.h"
 static_assert(LABEL_SPAN_DEV == LABEL_SPAN, "the kernels walk the spans the host built");
@@ -923,6 +930,135 @@ int wdbx_index_search_matrix(wdbx_index* ix, const uint64_t* row_ids, uint64_t n
     if ((rc = enqueue_rank_tail(ix, src, (int)first, b, k, ix->metric))) return rc;
   }
   return download_results(ix, elems, out_idx, out_score);
+} WDBX_CATCH
+
+// ---- nearest-centre assignment (kernels_assign.h, host_assign.h) ----------------------------
+// The whole call holds the handle's mutex.  Under it: the mask's length is checked, the row norms are brought up to date, the
+// centres go to the device once and are prepared in place (assign_prep_kernel, a sample launch in the profile), the tile pass
+// decides every certain row and lists the others (a gemm launch), the listed count comes back, the exact pass scores the
+// certain rows' winners when scores are asked for and decides the listed rows (scan launches), the sums pass and its
+// combination follow when sums or counts are asked for (merge launches); one download of what was asked for.
+int wdbx_index_assign(wdbx_index* ix, const float* centers, int n_centers, int normalize_centers, const uint32_t* mask_words,
+                      uint64_t mask_word_count, int32_t* out_center, float* out_score, float* out_sums, uint64_t* out_counts) try {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  switch (assign_validate(n_centers, centers != nullptr, out_center || out_score || out_sums || out_counts)) {
+    case ASSIGN_OK: break;
+    case ASSIGN_BAD_COUNT: return fail(WDBX_E_INVALID, "n_centers=%d outside [1, %d]", n_centers, WDBX_MAX_CENTERS);
+    case ASSIGN_NULL_CENTERS: return fail(WDBX_E_INVALID, "centers is null");
+    default: return fail(WDBX_E_INVALID, "every output is null");
+  }
+  std::unique_lock<std::mutex> lk(ix->mu);
+  const size_t sum_elems = (size_t)n_centers * ix->dim;
+  ix->last_assign_ambiguous = ix->last_assign_launches = ix->last_assign_center_blocks = ix->last_assign_partials = 0;
+  if (!ix->n) {  // (nothing stored: nothing assigned, nothing launched)
+    if (out_sums) std::fill(out_sums, out_sums + sum_elems, 0.f);
+    if (out_counts) std::fill(out_counts, out_counts + n_centers, (uint64_t)0);
+    return WDBX_OK;
+  }
+  int rc;
+  if (mask_words && (rc = check_mask_words(ix->n, mask_word_count))) return rc;
+  DeviceGuard g(ix->device);
+  MaskScope scope(ix);
+  if (mask_words && (rc = scope.set(mask_words))) return rc;
+  const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
+  const AssignPlan ap = assign_plan(ix->n, n_centers, (uint32_t)ix->pitch, ix->cu_count, ix->metric == WDBX_METRIC_L2);
+  const AssignBound ab = assign_bound((uint32_t)ix->pitch);
+  const bool want_sums = out_sums || out_counts;
+  const size_t counts_off = (sum_elems * sizeof(float) + 7) / 8 * 8;
+  if ((rc = ensure_row_norms(ix)) || (rc = ix->d_asg_centres.grow(ap.centre_bytes)) || (rc = ix->d_asg_aux.grow(ap.aux_bytes)) ||
+      (rc = ix->d_asg_center.grow((size_t)ix->n * sizeof(int32_t))) || (rc = ix->d_asg_list.grow((size_t)ix->n * sizeof(u64))) ||
+      (out_score && (rc = ix->d_asg_score.grow((size_t)ix->n * sizeof(float)))) ||
+      (want_sums && ((rc = ix->d_asg_part.grow(ap.partial_bytes)) || (rc = ix->d_asg_out.grow(counts_off + (size_t)n_centers * sizeof(u64))))))
+    return rc;
+  uint32_t* const d_words = (uint32_t*)(ix->d_asg_aux + ap.slots);  // {largest centre norm, listed rows}
+  HIP_TRY(hipMemsetAsync(d_words, 0, 2 * sizeof(uint32_t), ix->stream));
+  HIP_TRY(hipMemcpy2DAsync(ix->d_asg_centres, (size_t)ix->pitch * sizeof(float), centers, (size_t)ix->dim * sizeof(float),
+                           (size_t)ix->dim * sizeof(float), (size_t)n_centers, hipMemcpyHostToDevice, ix->stream));
+  AssignPrepArgs pa = {};
+  pa.centres = ix->d_asg_centres;
+  pa.cnorm = ix->d_asg_aux;
+  pa.cmax_bits = d_words;
+  pa.pitch = (uint32_t)ix->pitch;
+  pa.dim = (uint32_t)ix->dim;
+  pa.n_centers = (uint32_t)n_centers;
+  pa.slots = (uint32_t)ap.slots;
+  pa.normalize = normalize_centers && ix->metric == WDBX_METRIC_COSINE;
+  if ((rc = launch_bracketed(ix, ix->sample_ev, assign_prep_kernel, dim3(ap.prep_grid), 0, pa))) return rc;
+  AssignArgs ta = {};
+  ta.rows = (const f4*)ix->d_rows.p;
+  ta.centres = (const f4*)ix->d_asg_centres.p;
+  ta.cnorm = ix->d_asg_aux;
+  ta.cmax_bits = d_words;
+  ta.cn = ix->d_cn;
+  ta.mask = ix->active_mask;
+  ta.out_center = ix->d_asg_center;
+  ta.list = ix->d_asg_list;
+  ta.list_count = d_words + 1;
+  ta.n_rows = (uint32_t)ix->n;
+  ta.pitch4 = pitch4;
+  ta.n_centers = (uint32_t)n_centers;
+  ta.n_blocks = (uint32_t)ap.n_blocks;
+  ta.num_tiles = ap.tiles;
+  ta.gamma = ab.gamma;
+  ta.under = ab.under;
+  const assign_tile_fn tile = pick_assign_tile(ix->metric, ap.mt);
+  if (!tile) return fail(WDBX_E_STATE, "no assignment tile instance for blocks of %d centres", ap.block);
+  if ((rc = launch_bracketed(ix, ix->gemm_ev, tile, dim3(ap.grid), ap.lds, ta))) return rc;
+  uint32_t listed = 0;
+  HIP_TRY(hipMemcpyAsync(&listed, d_words + 1, sizeof listed, hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  int64_t launches = 2;
+  AssignExactArgs ea = {};
+  ea.rows = ta.rows;
+  ea.centres = ta.centres;
+  ea.list = ix->d_asg_list;
+  ea.list_count = d_words + 1;
+  ea.out_center = ix->d_asg_center;
+  ea.out_score = out_score ? (float*)ix->d_asg_score.p : nullptr;
+  ea.n_rows = ta.n_rows;
+  ea.pitch4 = pitch4;
+  ea.n_centers = ta.n_centers;
+  if (out_score) {  // the certain rows' scores: exact_score against the winner (the listed rows' are written by their own pass)
+    if ((rc = launch_bracketed(ix, ix->scan_ev, pick_assign_exact(ix->metric, true, pitch4), dim3(ap.exact_grid), 0, ea))) return rc;
+    ++launches;
+  }
+  if (listed) {
+    const uint32_t grid = assign_wave_grid(listed, 8u * (uint32_t)ix->cu_count);
+    if ((rc = launch_bracketed(ix, ix->scan_ev, pick_assign_exact(ix->metric, false, pitch4), dim3(grid), 0, ea))) return rc;
+    ++launches;
+  }
+  if (want_sums) {
+    AssignSumsArgs sa = {};
+    sa.rows = ta.rows;
+    sa.center = ix->d_asg_center;
+    sa.partial = (f4*)ix->d_asg_part.p;
+    sa.partial_count = (uint32_t*)(ix->d_asg_part + (size_t)ap.partials * n_centers * ix->pitch * sizeof(float));
+    sa.out_sums = out_sums ? (float*)ix->d_asg_out.p : nullptr;
+    sa.out_counts = out_counts ? (u64*)(ix->d_asg_out + counts_off) : nullptr;
+    sa.n_rows = ta.n_rows;
+    sa.pitch4 = pitch4;
+    sa.dim = (uint32_t)ix->dim;
+    sa.n_centers = ta.n_centers;
+    sa.partials = ap.partials;
+    sa.rows_per_partial = ap.rows_per_partial;
+    if ((rc = launch_bracketed(ix, ix->merge_ev, assign_sums_kernel, dim3(ap.sums_grid), 0, sa))) return rc;
+    const uint32_t cgrid = (uint32_t)std::min<size_t>((sum_elems + 255) / 256, 4096);
+    if ((rc = launch_bracketed(ix, ix->merge_ev, assign_combine_kernel, dim3(cgrid), 0, sa))) return rc;
+    launches += 2;
+  }
+  ix->last_assign_ambiguous = listed;
+  ix->last_assign_launches = launches;
+  ix->last_assign_center_blocks = ap.n_blocks;
+  ix->last_assign_partials = want_sums ? ap.partials : 0;
+  if (out_center) HIP_TRY(hipMemcpyAsync(out_center, ix->d_asg_center, (size_t)ix->n * sizeof(int32_t), hipMemcpyDeviceToHost, ix->stream));
+  if (out_score) HIP_TRY(hipMemcpyAsync(out_score, ix->d_asg_score, (size_t)ix->n * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+  if (out_sums) HIP_TRY(hipMemcpyAsync(out_sums, ix->d_asg_out.p, sum_elems * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+  if (out_counts)
+    HIP_TRY(hipMemcpyAsync(out_counts, ix->d_asg_out + counts_off, (size_t)n_centers * sizeof(u64), hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  // (partials of a call with many centres -- up to ASSIGN_PARTIALS_BUDGET -- do not stay on the handle; small ones are kept for the next iteration)
+  if (ix->d_asg_part.bytes > ASSIGN_PARTIALS_KEEP) return ix->d_asg_part.release();
+  return WDBX_OK;
 } WDBX_CATCH
 
 // ---- one row list PER QUERY in one batched call (host_rowlists.h, kernels_rowlists.h) --------
@@ -2854,6 +2990,10 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "last_rows_path")) return *value = ix->last_rows_path, WDBX_OK;
   if (name && !strcmp(name, "last_matrix_path")) return *value = ix->last_matrix_path, WDBX_OK;
   if (name && !strcmp(name, "last_matrix_rounds")) return *value = ix->last_matrix_rounds, WDBX_OK;
+  if (name && !strcmp(name, "last_assign_ambiguous")) return *value = ix->last_assign_ambiguous, WDBX_OK;
+  if (name && !strcmp(name, "last_assign_launches")) return *value = ix->last_assign_launches, WDBX_OK;
+  if (name && !strcmp(name, "last_assign_center_blocks")) return *value = ix->last_assign_center_blocks, WDBX_OK;
+  if (name && !strcmp(name, "last_assign_partials")) return *value = ix->last_assign_partials, WDBX_OK;
   if (name && !strcmp(name, "last_update_launches")) return *value = ix->last_update_launches, WDBX_OK;
   if (name && !strcmp(name, "last_lists_path")) return *value = ix->last_lists_path, WDBX_OK;
   if (name && !strcmp(name, "last_lists_items")) return *value = ix->last_lists_items, WDBX_OK;

@@ -21,6 +21,7 @@ MAX_EXAMPLES = 64        # WDBX_MAX_EXAMPLES: positives + negatives of one recom
 MAX_EXCLUDE_ROWS = 1024  # WDBX_MAX_EXCLUDE_ROWS
 MAX_CONTEXT_PAIRS = 32   # WDBX_MAX_CONTEXT_PAIRS: (positive, negative) pairs of one discovery query
 MAX_GROUP_SIZE = 64      # WDBX_MAX_GROUP_SIZE: members one group of wdbx_index_search_groups holds
+MAX_CENTERS = 4096       # WDBX_MAX_CENTERS: centres of one wdbx_index_assign call
 UNIQUE_ID_BYTES = 128
 
 _LIB_NAME = "libwdbx_hip.so"
@@ -73,6 +74,8 @@ SIGNATURES = {
                                               _u64p, C.c_int, C.POINTER(C.c_int32), _i64p, _f32p]),
     "wdbx_index_search_rows": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _u64p, C.c_uint64, _i64p, _f32p]),
     "wdbx_index_search_matrix": (C.c_int, [C.c_void_p, _u64p, C.c_uint64, C.c_int, _i64p, _f32p]),
+    "wdbx_index_assign": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
+                                    C.POINTER(C.c_int32), _f32p, _f32p, _u64p]),
     "wdbx_index_search_row_lists": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _u64p, _u64p, C.c_int,
                                               C.POINTER(C.c_int32), _i64p, _f32p]),
     "wdbx_index_set_labels": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]),
@@ -407,6 +410,39 @@ class NativeIndex:
         _check(self._lib.wdbx_index_search_matrix(self._h, ids.ctypes.data_as(_u64p), ids.size, int(k), idx.ctypes.data_as(_i64p),
                                                   score.ctypes.data_as(_f32p)))
         return idx, score
+
+    def assign(self, centers, normalize: bool = False, mask=None, want=("center", "score", "sums")) -> dict:
+        """Nearest-centre assignment of EVERY stored row (``wdbx_index_assign``): ``centers`` is ``[K, dim]``, ``mask`` uint32
+        words as in :meth:`search` (``mask_words``).  ``want`` names the outputs to compute, any of ``"center"`` (int32 per
+        row, -1 = none), ``"score"`` (f32 per row, :meth:`search_rows`' bits for that centre and row), ``"sums"`` (f32
+        ``[K, dim]``, the sum of each centre's rows as stored) and ``"counts"`` (uint64 ``[K]``); returns them by name.
+        The per-row outputs are sized here from :meth:`size` and the library writes one entry per row it holds WHEN IT RUNS:
+        the caller must keep rows from being added between the two (``HipFlatIndex.assign`` holds its ingest lock around
+        this call); sums and counts alone need no such care."""
+        c = _as_f32(centers, self.dim) if np.size(centers) else np.empty((0, self.dim), np.float32)
+        unknown = set(want) - {"center", "score", "sums", "counts"}
+        if unknown:
+            raise ValueError(f"unknown assignment outputs {sorted(unknown)}")
+        n = self.size()
+        out = {}
+        if "center" in want:
+            out["center"] = np.full(n, -1, np.int32)
+        if "score" in want:
+            out["score"] = np.zeros(n, np.float32)
+        if "sums" in want:
+            out["sums"] = np.zeros((c.shape[0], self.dim), np.float32)
+        if "counts" in want:
+            out["counts"] = np.zeros(c.shape[0], np.uint64)
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint32)
+
+        def ptr(name, ctype):
+            return out[name].ctypes.data_as(C.POINTER(ctype)) if name in out else None
+        # (the centre count, the outputs and the mask's length are checked by the library, the length under the handle's lock)
+        _check(self._lib.wdbx_index_assign(self._h, c.ctypes.data_as(_f32p), c.shape[0], int(normalize),
+                                           None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                           0 if m is None else m.size, ptr("center", C.c_int32), ptr("score", C.c_float),
+                                           ptr("sums", C.c_float), ptr("counts", C.c_uint64)))
+        return out
 
     def search_row_lists(self, queries, k: int, lists, query_list,
                          normalize_queries: bool = False) -> Tuple[np.ndarray, np.ndarray]:

@@ -823,6 +823,45 @@ class HipFlatIndex(VectorIndex):
                 return []
             raise
 
+    # ---- nearest-centre assignment (extension: the transposed search, every stored row against a few given vectors) ----
+    def assign(self, centers: np.ndarray, mask: Optional[np.ndarray] = None, want=("center", "score"),
+               normalize: bool = True) -> Optional[dict]:
+        """For every row that still has an id (and that ``mask``, as ``row_mask_for`` returns it, allows) the nearest of
+        ``centers`` ``[K, dim]``: one library call (``wdbx_index_assign``), no stored vector leaves the device.  Returns the
+        outputs named by ``want`` (``_native.NativeIndex.assign``) plus ``"ids"``: the id of every row with a centre, in
+        row order, and ``"rows"``, their row numbers -- ``center`` and ``score`` are cut to those rows, scores as ``search``
+        returns them.  With neither ``"center"`` nor ``"score"`` in ``want`` (a k-means iteration: sums and counts) nothing per
+        row comes back from the device and no id is mapped.  ``normalize=False``: the centres go to the library as they are.
+        None for an empty index; errors are swallowed (None) or raised as in ``search``.
+        The per-row outputs are sized by the row count, which the library reads again under its own lock: the call holds
+        ``_ingest_lock`` from sizing them to its return, so no ``add`` / ``batch_add`` / ``add_rows`` can grow the index in
+        between."""
+        try:
+            c = np.asarray(centers, dtype=np.float32)
+            if c.ndim != 2 or c.shape[1] != self.vector_dim:
+                raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {c.shape}")
+            if self.next_index == 0:
+                return None
+            c = np.stack([self._prepare(r) for r in c]) if normalize and c.shape[0] else np.ascontiguousarray(c)
+            per_row = "center" in want or "score" in want
+            # (a removed row is NaN on the device: the library gives it no centre, so it needs no mask)
+            with self._ingest_lock:
+                out = self._native.assign(c, normalize=False, mask=mask, want=tuple(set(want) | {"center"}) if per_row else want)
+                if not per_row:
+                    return out
+                rows = np.flatnonzero(out["center"] >= 0)
+                out["ids"] = [self._id_of(int(r)) for r in rows]
+            out["rows"] = rows
+            out["center"] = out["center"][rows]
+            if "score" in out:
+                out["score"] = out["score"][rows] if self.metric == _native.METRIC_COSINE else -out["score"][rows]
+            return out
+        except Exception as e:
+            logger.error("Error assigning rows of HIP index: %s", e)
+            if self.swallow_errors:
+                return None
+            raise
+
     # ---- the same with one list PER QUERY (wdbx_index_search_row_lists: one call for the whole batch) ----
     supports_row_lists = True
 

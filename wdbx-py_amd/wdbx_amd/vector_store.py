@@ -1454,6 +1454,96 @@ class VectorStore:
         return await loop.run_in_executor(self.thread_pool, lambda: self.search_matrix(
             sample, limit, filter_metadata=filter_metadata, vector_ids=vector_ids, seed=seed))
 
+    # ---- nearest-centre assignment and k-means (extension: every stored vector against a few given vectors) ----
+    def _assign_shards(self, centers: np.ndarray, masks, want) -> List[Optional[dict]]:
+        """One ``HipFlatIndex.assign`` per shard, on the shard pool, answers in shard order."""
+        work = list(zip(self.indices, masks))
+        one = lambda a: a[0].assign(centers, mask=a[1], want=want)  # noqa: E731
+        return list(self._shard_pool.map(one, work)) if len(work) > 1 else [one(work[0])]
+
+    def _centers_checked(self, centers) -> np.ndarray:
+        c = np.asarray(centers, dtype=np.float32)
+        if c.ndim != 2 or c.shape[1] != self.vector_dim:
+            raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {c.shape}")
+        if not 1 <= c.shape[0] <= _native.MAX_CENTERS:
+            raise ValueError(f"{c.shape[0]} centres: between 1 and {_native.MAX_CENTERS} are served")
+        return c
+
+    def assign(self, centers, filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Tuple[int, float]]:
+        """For every stored vector (with ``filter_metadata``: every vector it matches) the nearest of ``centers`` ``[K, dim]``:
+        ``{id: (centre index, score)}``, scores as ``search`` returns them, equal scores to the lowest centre index --
+        cluster assignment, prototype classification.  Every shard answers its own rows with one library call
+        (``wdbx_index_assign``: no stored vector leaves its device); the answer is per row, so the shards' parts are simply
+        put together.  A filter always travels as the row masks."""
+        c = self._centers_checked(centers)
+        masks = self._row_masks(filter_metadata) if filter_metadata else [None] * len(self.indices)
+        self.last_search_path = "threads"
+        out: Dict[str, Tuple[int, float]] = {}
+        for res in self._assign_shards(c, masks, ("center", "score")):
+            if res:
+                out.update(zip(res["ids"], zip(res["center"].tolist(), res["score"].tolist())))
+        return out
+
+    async def assign_async(self, centers, filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Tuple[int, float]]:
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(self.thread_pool, lambda: self.assign(centers, filter_metadata=filter_metadata))
+
+    def cluster(self, k: int, max_iter: int = 25, tol: float = 1e-4, seed=None,
+                filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        """k-means (Lloyd) over the stored vectors (with ``filter_metadata``: over those it matches).  The initial centres are
+        ``k`` distinct stored vectors drawn by ``random.Random(seed)`` from the sorted ids.  Every iteration is one ``assign``
+        per shard with per-centre sums and counts computed on the device; the shards' sums are added in shard order in
+        float64 and the new centre is the mean -- re-normalised for cosine (spherical k-means); a centre without rows keeps
+        its place.  It stops when no count changed and no centre moved by ``tol`` or more, or after ``max_iter`` iterations;
+        a last ``assign`` gives the assignments.  Returns ``{"centers": f32[k, dim], "counts": [k], "inertia": the sum of the
+        assignments' scores (as ``search`` returns them: larger is tighter), "iterations", "assignments": {id: centre}}`` --
+        the same bits from run to run for a given ``seed``."""
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _native.MAX_CENTERS:
+            raise ValueError(f"k must be an integer between 1 and {_native.MAX_CENTERS}")
+        masks = self._row_masks(filter_metadata) if filter_metadata else [None] * len(self.indices)
+        pool = sorted(vid for ix, mask in zip(self.indices, masks) for vid in ix.mapped_ids(mask))
+        if len(pool) < k:
+            raise ValueError(f"{k} clusters of {len(pool)} vectors")
+        cosine = self.indices[0].metric == _native.METRIC_COSINE
+
+        def unit(c64: np.ndarray) -> np.ndarray:
+            if cosine:
+                norms = np.linalg.norm(c64, axis=1)
+                c64 = np.where(norms[:, None] > 0, c64 / np.where(norms > 0, norms, 1.0)[:, None], c64)
+            return c64.astype(np.float32)
+        centers = unit(np.array([self.get(vid)[0] for vid in random.Random(seed).sample(pool, k)], dtype=np.float64))
+        self.last_search_path = "threads"
+        previous, iterations = None, 0
+        for iterations in range(1, max(int(max_iter), 0) + 1):
+            sums, counts = np.zeros((k, self.vector_dim), np.float64), np.zeros(k, np.int64)
+            for res in self._assign_shards(centers, masks, ("sums", "counts")):
+                if res:
+                    sums += res["sums"].astype(np.float64)
+                    counts += res["counts"].astype(np.int64)
+            moved = centers.astype(np.float64)
+            moved[counts > 0] = sums[counts > 0] / counts[counts > 0, None]
+            moved = unit(moved)
+            shift = float(np.max(np.linalg.norm(moved.astype(np.float64) - centers.astype(np.float64), axis=1)))
+            settled = previous is not None and np.array_equal(counts, previous) and shift < tol
+            centers, previous = moved, counts
+            if settled:
+                break
+        assignments: Dict[str, int] = {}
+        inertia, counts = 0.0, np.zeros(k, np.int64)
+        for res in self._assign_shards(centers, masks, ("center", "score")):
+            if res:
+                assignments.update(zip(res["ids"], res["center"].tolist()))
+                inertia += float(np.sum(res["score"].astype(np.float64)))
+                counts += np.bincount(res["center"], minlength=k)
+        return {"centers": centers, "counts": counts.tolist(), "inertia": inertia, "iterations": iterations,
+                "assignments": assignments}
+
+    async def cluster_async(self, k: int, max_iter: int = 25, tol: float = 1e-4, seed=None,
+                            filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(self.thread_pool, lambda: self.cluster(
+            k, max_iter=max_iter, tol=tol, seed=seed, filter_metadata=filter_metadata))
+
     # ---- range search (extension: every vector within a similarity, no limit) ----
     def search_range(self, query_vector: List[float], threshold: float,
                      filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,

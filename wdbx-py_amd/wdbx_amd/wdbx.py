@@ -304,6 +304,28 @@ class WDBX:
         return self._matrix_offsets(self._matrix_lines(await self.vector_store.search_matrix_async(
             sample, limit, filter_metadata=filter_metadata, vector_ids=vector_ids, seed=seed)))
 
+    def vector_assign(self, centers, filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Tuple[int, float]]:
+        """Extension: nearest-centre assignment.  For every stored vector (with ``filter_metadata``: every vector it matches)
+        the nearest of ``centers`` ``[K, dim]``: ``{id: (centre index, score)}`` -- cluster assignment, prototype / zero-shot
+        classification.  Scores are cosine similarities, for L2 the negated squared distances; equal scores go to the lowest
+        centre index.  Any number of shards (``VectorStore.assign``)."""
+        return self.vector_store.assign(centers, filter_metadata=filter_metadata)
+
+    async def vector_assign_async(self, centers,
+                                  filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Tuple[int, float]]:
+        return await self.vector_store.assign_async(centers, filter_metadata=filter_metadata)
+
+    def vector_cluster(self, k: int, max_iter: int = 25, tol: float = 1e-4, seed=None,
+                       filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        """Extension: k-means over the stored vectors (spherical k-means for cosine), every iteration's assignment and
+        per-centre sums computed on the device: ``{"centers", "counts", "inertia", "iterations", "assignments"}``
+        (``VectorStore.cluster`` states the steps).  The same result from run to run for a given ``seed``."""
+        return self.vector_store.cluster(k, max_iter=max_iter, tol=tol, seed=seed, filter_metadata=filter_metadata)
+
+    async def vector_cluster_async(self, k: int, max_iter: int = 25, tol: float = 1e-4, seed=None,
+                                   filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        return await self.vector_store.cluster_async(k, max_iter=max_iter, tol=tol, seed=seed, filter_metadata=filter_metadata)
+
     def vector_search_range(self, query_vector: List[float], threshold: float,
                             filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,
                             max_results: Optional[int] = None) -> List[Result]:
