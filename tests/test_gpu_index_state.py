@@ -19,7 +19,7 @@ five coverages the library reports (``shadow_rows``, ``shadowg_rows``, ``shadow8
 ``shadow42_rows``) must not pass the reach that ``index_model.Trace`` keeps for the sequence (the row count at the last warm
 op, cut by ``compact`` and ``clear``), which lies below the row count after an add that no search followed; after a warm
 checkpoint they equal the row count (cosine: all five; L2: the u8 copy, the one whose route reports that it ran there).
-The sixth coverage, ``cn_rows`` of the squared norms, has no option that reports it and is not observed here."""
+The sixth coverage, that of the squared norms, has no option that reports it and is not observed here."""
 import time
 
 import numpy as np

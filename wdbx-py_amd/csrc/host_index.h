@@ -80,13 +80,15 @@ struct wdbx_index {
   uint32_t last_batch_nq = 0, last_batch_cap = 0;
   bool last_batch_repaired = false;  // the last batch's overflowed queries were repaired on the device (conditional launches)
   DevBuf<void> d_qb16{&bufs};  // bf16 tiles: the query block as bf16
-  DevBuf<float> d_cn{&bufs};  // L2 / bf16 batched path: squared row norms for rows [0, cn_rows), and their maximum
-  uint64_t cn_rows = 0;
-  DevBuf<void> d_rows16{&bufs};  // bf16 shadow copy of rows [0, shadow_rows), row pitch pitch16 elements (zero padded)
-  uint64_t shadow_rows = 0;
+  // The derived copies of the rows: each one's coverage (host_copies.h) next to its buffers; what a mutation owes every one of
+  // them is described once, in DERIVED_COPIES below
+  DevBuf<float> d_cn{&bufs};  // L2 / bf16 batched path: squared row norms for the rows cov_cn covers, and their maximum
+  CopyCoverage cov_cn;
+  DevBuf<void> d_rows16{&bufs};  // bf16 shadow copy of the rows cov_bf16 covers, row pitch pitch16 elements (zero padded)
+  CopyCoverage cov_bf16{0, ~0ull, 1, false};  // (a refusal is never remembered: the next batch tries again)
   uint32_t pitch16 = 0;
   int last_gemm_mode = 0;  // tile kernel family the last batch ran on (GEMM_FP32 / GEMM_BF16 / GEMM_BF16_SHADOW)
-  DevBuf<uint8_t> d_rows8{&bufs};  // u8 shadow copy of rows [0, shadow8_rows) for the single-query selection scan, pitch8 bytes
+  DevBuf<uint8_t> d_rows8{&bufs};  // u8 shadow copy of the rows cov_u8 covers for the single-query selection scan, pitch8 bytes
   DevBuf<float> d_scale8{&bufs};   // its per-row scales
   DevBuf<float> d_gmax{&bufs};     // largest squared row norm per 64-row group (selection bounds of the tile kernels)
   DevBuf<float> d_qn{&bufs};       // |q| per query of a block
@@ -94,23 +96,22 @@ struct wdbx_index {
   bool cn_stats_dirty = false; // cached norms were refreshed in place: recompute their statistics before deciding
   bool group_bounds = false;   // per-group bounds (norms vary a lot) or one global bound (they do not: cheaper epilogue)
   DevBuf<void> d_selsrc{&bufs};    // device-side SelectSrc of the large-k selection epilogue
-  uint64_t shadow8_rows = 0;
+  CopyCoverage cov_u8;
   uint32_t pitch8 = 0;
-  uint64_t u8_no_room_cap = ~0ull;  // capacity at which the u8 shadow last failed to allocate
-  // u6 shadow copy of rows [0, shadow6_rows) for rounds of single queries (kernels_scan6.h): ONE allocation, the six-bit codes
+  // u6 shadow copy of the rows cov_u6 covers for rounds of single queries (kernels_scan6.h): ONE allocation, the six-bit codes
   // in 64-row tiles of units6 units followed by the per-row {s, a} pairs
   DevBuf<uint32_t> d_rows6{&bufs};
-  uint64_t shadow6_rows = 0, rows6_tiles = 0;
+  CopyCoverage cov_u6;
+  uint64_t rows6_tiles = 0;
   uint32_t units6 = 0;
-  uint64_t u6_no_room_cap = ~0ull;
   DevBuf<uint32_t> d_count6{&bufs};  // its candidate counters (d_count holds the cut's: what the repair launches look at)
   int last_single_u6 = 0;      // 1: the last single-query search selected on the u6 shadow (last_single_path stays 2)
   // the u6 codes once more in two planes (kernels_scan42.h): ONE allocation, the h plane in 64-row tiles of units42 units,
   // the per-row {s, a4} pairs, the l records of lpitch42 dwords per row
   DevBuf<uint32_t> d_rows42{&bufs};
-  uint64_t shadow42_rows = 0, rows42_tiles = 0;
+  CopyCoverage cov_u42;
+  uint64_t rows42_tiles = 0;
   uint32_t units42 = 0;
-  uint64_t u42_no_room_cap = ~0ull;
   DevBuf<uint32_t> d_count42{&bufs};  // rows that passed the four-bit bound, per query of the last round
   int last_single_u42 = 0;     // 1: the last u6 round's full passes ran over the split planes
   int last_u42_share = 0;      // ... the widest group of queries that shared one read of the four-bit plane in the last call (0: none ran)
@@ -133,17 +134,16 @@ struct wdbx_index {
   int last_single_path = 0;    // 0 fp32 scan, 1 bf16 tiles, 2 u8 scan (what the last single-query search ran on)
   int last_sample_qn = 1;      // queries per workgroup of the last u8 sample launch (1, 3 or 4: scan8_sample4_kernel)
   DevBuf<uint32_t> d_cnmax{&bufs};
-  // group-scaled i8 shadow copy of the rows for the int8 tiles (kernels_tiles8.h): rows [0, shadowg_rows) quantised
+  // group-scaled i8 shadow copy of the rows for the int8 tiles (kernels_tiles8.h): the rows cov_i8g covers quantised
   DevBuf<int8_t> d_rows8g{&bufs};
   DevBuf<f4> d_groups8{&bufs};       // per 64-row group {s_g, a_g, b_g, vouch}
   DevBuf<uint32_t> d_over_list{&bufs};  // {n, q_0 ..}: the overflowed queries of a batch block, for its repair scan (mark_lost_kernel)
   DevBuf<float> d_gref8{&bufs};      // {a_ref, b_ref, sum a, sum b} + a counter: the prefilter epilogue's ordinary-group bounds
   bool gref_valid = false;       // (recomputed when the group table changed)
   DevBuf<u64> d_gbad8{&bufs};        // per 64-row group: bits of the rows that hold a NaN (removed rows) or lie past the end
-  uint64_t shadowg_rows = 0;
+  CopyCoverage cov_i8g{0, ~0ull, 64, true};  // (whole 64-row groups: a group's scale depends on all of its rows)
   uint64_t shadowg_tail_n = ~0ull;  // the row count for which the groups behind the last row (to the end of its 256-row tile) were last written
   uint32_t pitch8g = 0;
-  uint64_t i8g_no_room_cap = ~0ull;
   DevBuf<int8_t> d_qb8{&bufs};       // the query block as i8
   DevBuf<f4> d_qpar{&bufs};          // its per-query parameters
   DevBuf<u64> d_pairs{&bufs};        // the tile waves' candidate (query, row) pairs and how many each wave produced
@@ -563,30 +563,125 @@ static void final_topk_output(const wdbx_index* ix, MergeArgs* f, u64* keys_out,
   }
 }
 
-// The life cycle of a shadow copy's allocations (u8: codes and scales; i8 groups: rows, table and bad-row bits; bf16, u6, u42: one
-// each).  SHADOW_KEPT: the shape is the same and every part is large enough, nothing was done.  Else the parts are released,
-// *shadow_rows restarts at 0 and they are allocated anew: SHADOW_FRESH, or SHADOW_NO_ROOM (= 0) with every part released and
-// the capacity remembered in *no_room_cap so that the next calls at this capacity do not try again.
-enum { SHADOW_NO_ROOM = 0, SHADOW_KEPT = 1, SHADOW_FRESH = 2 };
+// ---- the derived copies of the rows ------------------------------------------------------------------------------------------
+// The life cycle of a copy's allocations (u8: codes and scales; i8 groups: rows, table and bad-row bits; bf16, u6, u42: one
+// each), decided by copy_room_decision (host_copies.h).  SHADOW_KEPT: nothing was done.  Else the parts are released, the
+// coverage restarts at 0 and they are allocated anew: SHADOW_FRESH, or SHADOW_NO_ROOM with every part released and the refusal
+// remembered in the coverage so that the next calls at this capacity do not try again.
 struct ShadowPart {
   BufBase<HipMem>* buf;
   size_t need;
 };
-static int shadow_room(wdbx_index* ix, bool shape_changed, std::initializer_list<ShadowPart> parts, uint64_t* shadow_rows,
-                       uint64_t* no_room_cap) {
-  bool stale = shape_changed;
-  for (const ShadowPart& s : parts) stale = stale || s.buf->bytes < s.need;
-  if (!stale) return SHADOW_KEPT;
-  if (*no_room_cap == ix->cap) return SHADOW_NO_ROOM;
+static int shadow_room(wdbx_index* ix, bool shape_changed, std::initializer_list<ShadowPart> parts, CopyCoverage* cov) {
+  bool too_small = false;
+  for (const ShadowPart& s : parts) too_small = too_small || s.buf->bytes < s.need;
+  const int room = copy_room_decision(shape_changed, too_small, cov->refused_at(ix->cap));
+  if (room != SHADOW_FRESH) return room;
   for (const ShadowPart& s : parts) (void)s.buf->release();
-  *shadow_rows = 0;
+  cov->reset();
   for (const ShadowPart& s : parts) {
     if (s.buf->try_grow(s.need)) continue;
     for (const ShadowPart& r : parts) (void)r.buf->release();
-    *no_room_cap = ix->cap;
+    cov->refuse_at(ix->cap);
     return SHADOW_NO_ROOM;
   }
   return SHADOW_FRESH;
+}
+
+// Each copy's quantiser over rows [first, end), in the ONE launch both of its writers share.  extend: the lazy pick-up of rows
+// behind the coverage (the prepare functions); else the refresh in place of overwritten rows the copy covers (upload_rows).
+static hipError_t launch_rows_to_cn(wdbx_index* ix, uint64_t first, uint64_t end, bool extend) {
+  // (new rows join the running maximum / sum / count; a refreshed row is in them with its old norm: cn_stats_dirty)
+  hipLaunchKernelGGL(row_sqnorm_kernel, dim3(row_sqnorm_grid(end - first)), dim3(256), 0, ix->stream, (const float*)ix->d_rows,
+                     (u64)first, (u64)end, (uint32_t)ix->pitch, ix->d_cn, extend ? (uint32_t*)ix->d_cnmax : (uint32_t*)nullptr);
+  return hipGetLastError();
+}
+static hipError_t launch_rows_to_bf16(wdbx_index* ix, uint64_t first, uint64_t end, bool) {
+  const u64 pieces = (end - first) * (ix->pitch16 / 8);
+  hipLaunchKernelGGL(rows_to_bf16_kernel, dim3((uint32_t)std::min<u64>((pieces + 255) / 256, 1u << 20)), dim3(256), 0, ix->stream,
+                     (const float*)ix->d_rows, (u64)first, (u64)end, (uint32_t)ix->pitch, (__bf16*)ix->d_rows16.p, ix->pitch16);
+  return hipGetLastError();
+}
+// whole groups (a group's scale depends on all of its rows); rows at and behind the row count get their bad-row bits
+static hipError_t launch_rows_to_i8g(wdbx_index* ix, uint64_t first, uint64_t end, bool extend) {
+  const u64 g0 = first / 64, g1 = (end + 63) / 64;
+  if (g1 <= g0) return hipSuccess;
+  hipLaunchKernelGGL(rows_to_i8g_kernel, dim3(rows_to_i8g_grid(g1 - g0)), dim3(256), 0, ix->stream, (const float*)ix->d_rows, g0, g1,
+                     (u64)(extend ? ix->n : std::max<uint64_t>(ix->n, end)), (uint32_t)ix->dim, (uint32_t)ix->pitch, ix->d_rows8g,
+                     ix->pitch8g, ix->d_groups8, ix->d_gbad8);
+  return hipGetLastError();
+}
+static hipError_t launch_rows_to_u8(wdbx_index* ix, uint64_t first, uint64_t end, bool) {
+  hipLaunchKernelGGL(rows_to_u8_kernel, dim3(rows_to_u8_grid(end - first)), dim3(256), 0, ix->stream, (const float*)ix->d_rows,
+                     (u64)first, (u64)end, (uint32_t)ix->dim, (uint32_t)ix->pitch, ix->d_rows8, ix->pitch8, ix->d_scale8);
+  return hipGetLastError();
+}
+// the u6 allocation's second part (the per-row {s, a} pairs behind the code tiles) and the three parts of the split planes'
+static inline f2v* u6_sa(const wdbx_index* ix) { return (f2v*)(ix->d_rows6 + (size_t)ix->rows6_tiles * ix->units6 * 192); }
+static inline f2v* u42_sa4(const wdbx_index* ix) { return (f2v*)(ix->d_rows42 + (size_t)ix->rows42_tiles * ix->units42 * 256); }
+static inline uint32_t* u42_lrec(const wdbx_index* ix) { return (uint32_t*)(u42_sa4(ix) + (size_t)ix->rows42_tiles * 64); }
+static hipError_t launch_rows_to_u6(wdbx_index* ix, uint64_t first, uint64_t end, bool) {
+  hipLaunchKernelGGL(rows_to_u6_kernel, dim3(rows_to_u6_grid(end - first)), dim3(256), 0, ix->stream, (const float*)ix->d_rows,
+                     (u64)first, (u64)end, (uint32_t)ix->dim, (uint32_t)ix->pitch, ix->units6, ix->d_rows6, u6_sa(ix));
+  return hipGetLastError();
+}
+static hipError_t launch_rows_to_u42(wdbx_index* ix, uint64_t first, uint64_t end, bool) {
+  hipLaunchKernelGGL(rows_to_u42_kernel, dim3(rows_to_u42_grid(end - first)), dim3(256), 0, ix->stream, (const float*)ix->d_rows, (u64)first,
+                     (u64)end, (uint32_t)ix->dim, (uint32_t)ix->pitch, ix->units42, ix->d_rows42, u42_sa4(ix), u42_lrec(ix),
+                     u42_lpitch(ix->units42));
+  return hipGetLastError();
+}
+
+// One line per copy: everything a mutation has to know about it.  A new copy joins HERE (and gets its coverage member, its
+// launcher and its prepare function); clear, compact, upload_rows, update_rows_at and the coverage options walk the table.
+struct DerivedCopy {
+  CopyCoverage wdbx_index::*cov;
+  uint64_t UpdateCoverage::*listed;    // its field in the plan of a write of listed rows (host_update.h)
+  const char* rows_option;             // the read-only option that reports its coverage (null: none)
+  bool (*present)(const wdbx_index*);  // its buffer exists
+  hipError_t (*launch)(wdbx_index*, uint64_t first, uint64_t end, bool extend);
+  void (*drops)(wdbx_index*, bool extend);  // the validity flags a write of it drops (null: none)
+  void (*listed_args)(const wdbx_index*, const UpdatePlan&, UpdateArgs*);  // its part of the fused refresh of listed rows (null: a launch of its own)
+};
+enum { COPY_CN, COPY_BF16, COPY_I8G, COPY_U8, COPY_U6, COPY_U42 };  // (the order upload_rows refreshes them in)
+static const DerivedCopy DERIVED_COPIES[] = {
+    {&wdbx_index::cov_cn, &UpdateCoverage::cn, nullptr, [](const wdbx_index* ix) { return ix->d_cn.p != nullptr; }, launch_rows_to_cn,
+     [](wdbx_index* ix, bool extend) {
+       ix->gmax_valid = false;
+       if (!extend) ix->cn_stats_dirty = true;  // the running maximum / sum would keep the overwritten rows' old norms
+     },
+     [](const wdbx_index* ix, const UpdatePlan& p, UpdateArgs* a) { a->n_cn = p.n_cn, a->cn = ix->d_cn; }},
+    {&wdbx_index::cov_bf16, &UpdateCoverage::bf16, "shadow_rows", [](const wdbx_index* ix) { return ix->d_rows16.p != nullptr; },
+     launch_rows_to_bf16, nullptr,
+     [](const wdbx_index* ix, const UpdatePlan& p, UpdateArgs* a) { a->n_16 = p.n_16, a->rows16 = (__bf16*)ix->d_rows16.p, a->pitch16 = ix->pitch16; }},
+    {&wdbx_index::cov_i8g, &UpdateCoverage::i8g, "shadowg_rows", [](const wdbx_index* ix) { return ix->d_rows8g.p != nullptr; },
+     launch_rows_to_i8g, [](wdbx_index* ix, bool) { ix->gref_valid = false; }, nullptr},
+    {&wdbx_index::cov_u8, &UpdateCoverage::u8, "shadow8_rows", [](const wdbx_index* ix) { return ix->d_rows8.p != nullptr; },
+     launch_rows_to_u8, nullptr,
+     [](const wdbx_index* ix, const UpdatePlan& p, UpdateArgs* a) { a->n_8 = p.n_8, a->rows8 = ix->d_rows8, a->pitch8 = ix->pitch8, a->scale8 = ix->d_scale8; }},
+    {&wdbx_index::cov_u6, &UpdateCoverage::u6, "shadow6_rows", [](const wdbx_index* ix) { return ix->d_rows6.p != nullptr; },
+     launch_rows_to_u6, nullptr,
+     [](const wdbx_index* ix, const UpdatePlan& p, UpdateArgs* a) { a->n_6 = p.n_6, a->units6 = ix->units6, a->codes6 = ix->d_rows6, a->sa6 = u6_sa(ix); }},
+    {&wdbx_index::cov_u42, &UpdateCoverage::u42, "shadow42_rows", [](const wdbx_index* ix) { return ix->d_rows42.p != nullptr; },
+     launch_rows_to_u42, nullptr,
+     [](const wdbx_index* ix, const UpdatePlan& p, UpdateArgs* a) {
+       a->n_42 = p.n_42, a->units42 = ix->units42, a->lpitch42 = u42_lpitch(ix->units42);
+       a->h42 = ix->d_rows42, a->sa42 = u42_sa4(ix), a->lrec42 = u42_lrec(ix);
+     }},
+};
+
+// the lazy pick-up: rows [first, end) through the copy's launcher, after which it covers the n stored rows
+static hipError_t extend_copy(wdbx_index* ix, const DerivedCopy& c, uint64_t first, uint64_t end) {
+  const hipError_t e = c.launch(ix, first, end, true);
+  if (e != hipSuccess) return e;
+  (ix->*c.cov).extended_to(ix->n);
+  if (c.drops) c.drops(ix, true);
+  return hipSuccess;
+}
+// ... of the rows behind its coverage, if any
+static hipError_t extend_copy(wdbx_index* ix, const DerivedCopy& c) {
+  const CopyCoverage& cov = ix->*c.cov;
+  return cov.covers(ix->n) ? hipSuccess : extend_copy(ix, c, cov.rows, ix->n);
 }
 
 // all-gather this rank's key lists [b, k] (global rows) and merge the nranks lists per query
@@ -914,7 +1009,7 @@ static bool gemm_eligible(const wdbx_index* ix, int nq, int k) {
   // than one scan (10 M x 384: 0.71 ms for up to 16 queries against 0.60 ms per single query), so on large shards two
   // coalesced callers already share a pass -- unless the option was raised to keep batching off.
   int64_t min_nq = ix->opt_gemm_min_nq;
-  if (min_nq > 2 && min_nq <= 4 && ix->n >= 3000000 && ix->i8g_no_room_cap != ix->cap && i8_tiles_eligible(ix)) min_nq = 2;
+  if (min_nq > 2 && min_nq <= 4 && ix->n >= 3000000 && !ix->cov_i8g.refused_at(ix->cap) && i8_tiles_eligible(ix)) min_nq = 2;
   if (nq < min_nq || (uint64_t)k * 8 * GB_M > ix->n) return false;
   if ((int64_t)ix->n >= 2 * ix->opt_gemm_min_rows) return true;
   // Below 2 x gemm_min_rows the alternative is the fp32 scan with a round's queries as one grid, whose cost grows with
@@ -961,18 +1056,9 @@ static bool prepare_u8_shadow(wdbx_index* ix) {
   if (!sh) return false;
   const uint32_t pitch8 = sh->pieces * 16;
   const size_t need = ((size_t)ix->cap + TILE_PAD_ROWS) * pitch8, need_s = ((size_t)ix->cap + TILE_PAD_ROWS) * sizeof(float);
-  if (!shadow_room(ix, ix->pitch8 != pitch8, {{&ix->d_rows8, need}, {&ix->d_scale8, need_s}},
-                   &ix->shadow8_rows, &ix->u8_no_room_cap))
-    return false;
+  if (!shadow_room(ix, ix->pitch8 != pitch8, {{&ix->d_rows8, need}, {&ix->d_scale8, need_s}}, &ix->cov_u8)) return false;
   ix->pitch8 = pitch8;
-  if (ix->shadow8_rows < ix->n) {
-    const uint32_t blocks = rows_to_u8_grid(ix->n - ix->shadow8_rows);
-    hipLaunchKernelGGL(rows_to_u8_kernel, dim3(blocks), dim3(256), 0, ix->stream, (const float*)ix->d_rows, (u64)ix->shadow8_rows,
-                       (u64)ix->n, (uint32_t)ix->dim, (uint32_t)ix->pitch, ix->d_rows8, pitch8, ix->d_scale8);
-    if (hipGetLastError() != hipSuccess) return false;
-    ix->shadow8_rows = ix->n;
-  }
-  return true;
+  return extend_copy(ix, DERIVED_COPIES[COPY_U8]) == hipSuccess;
 }
 
 // ---- range search (wdbx_index_range_search) -------------------------------------------------------
@@ -991,17 +1077,45 @@ static int ensure_row_norms(wdbx_index* ix) {
   if ((rc = ix->d_cnmax.grow(4 * sizeof(uint32_t)))) return rc;
   if (ix->d_cn.bytes < (size_t)ix->n * sizeof(float)) {
     if ((rc = ix->d_cn.grow((size_t)ix->cap * sizeof(float)))) return rc;
-    ix->cn_rows = 0;
+    ix->cov_cn.reset();
   }
-  if (ix->cn_rows == 0) HIP_TRY(hipMemsetAsync(ix->d_cnmax, 0, 4 * sizeof(uint32_t), ix->stream));
-  if (ix->cn_rows < ix->n) {
-    const uint32_t blocks = row_sqnorm_grid(ix->n - ix->cn_rows);
-    hipLaunchKernelGGL(row_sqnorm_kernel, dim3(blocks), dim3(256), 0, ix->stream, (const float*)ix->d_rows, (u64)ix->cn_rows,
-                       (u64)ix->n, (uint32_t)ix->pitch, ix->d_cn, ix->d_cnmax);
+  if (ix->cov_cn.rows == 0) HIP_TRY(hipMemsetAsync(ix->d_cnmax, 0, 4 * sizeof(uint32_t), ix->stream));
+  HIP_TRY(extend_copy(ix, DERIVED_COPIES[COPY_CN]));
+  return WDBX_OK;
+}
+
+// How the selection error of a batch on the legacy tiles is bounded.  Norms all alike (the reference normalises its rows):
+// ONE bound from the largest norm, subtracted from the thresholds (tau_margin_kernel) -- nothing in the tile epilogue.
+// Norms that vary a lot (largest > 1.5 x mean: unnormalised data, outlier rows): a bound per 64-row group from that group's
+// largest norm, applied in the epilogue (+10 % kernel time), so an outlier only loosens its own group and the batch does not
+// degenerate into per-query repairs.  Decided when the norms change (one 8-byte read-back); the norms are in place.
+static int decide_group_bounds(wdbx_index* ix) {
+  if (ix->gmax_valid) return WDBX_OK;
+  if (ix->cn_stats_dirty) {  // rows were overwritten in place: rebuild maximum / sum / count from the cached norms
+    HIP_TRY(hipMemsetAsync(ix->d_cnmax, 0, 4 * sizeof(uint32_t), ix->stream));
+    hipLaunchKernelGGL(cn_stats_kernel, dim3((uint32_t)std::min<uint64_t>((ix->n + 255) / 256, 2048)), dim3(256), 0, ix->stream,
+                       (const float*)ix->d_cn, (u64)ix->n, ix->d_cnmax);
     HIP_TRY(hipGetLastError());
-    ix->cn_rows = ix->n;
-    ix->gmax_valid = false;
+    ix->cn_stats_dirty = false;
   }
+  uint32_t words[3] = {0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(words, ix->d_cnmax, sizeof words, hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  float cmax, csum;
+  memcpy(&cmax, &words[0], 4);
+  memcpy(&csum, &words[1], 4);
+  const float mean = words[2] ? csum / (float)words[2] : 0.f;  // over the rows with a finite norm (removed rows are NaN)
+  // an infinite norm (a row with an infinite or huge element) always takes the per-group instances: their epilogue
+  // sends such a group's rows to the exact pass whatever the selection scores say (kernels_tiles.h)
+  ix->group_bounds = ix->opt_group_bounds == 1 || !(cmax < INFINITY) || (ix->opt_group_bounds != 0 && !(cmax <= 1.5f * mean));
+  if (ix->group_bounds) {
+    int rc = ix->d_gmax.grow(((size_t)ix->cap + 63) / 64 * sizeof(float));
+    if (rc) return rc;
+    const uint32_t gblocks = (uint32_t)std::min<uint64_t>(((ix->n + 63) / 64 + 255) / 256, 4096);
+    hipLaunchKernelGGL(group_max_kernel, dim3(gblocks), dim3(256), 0, ix->stream, (const float*)ix->d_cn, (u64)ix->n, ix->d_gmax);
+    HIP_TRY(hipGetLastError());
+  }
+  ix->gmax_valid = true;
   return WDBX_OK;
 }
 
@@ -1016,7 +1130,7 @@ static int enqueue_singles_u8(wdbx_index* ix, const float* d_queries, int nq, in
   const bool l2 = ix->metric == WDBX_METRIC_L2;
   const uint32_t pitch8 = sh->pieces * 16;
   int rc;
-  if (ix->d_rows8.bytes < ((size_t)ix->cap + TILE_PAD_ROWS) * pitch8 || ix->pitch8 != pitch8 || ix->shadow8_rows < ix->n)
+  if (ix->d_rows8.bytes < ((size_t)ix->cap + TILE_PAD_ROWS) * pitch8 || ix->pitch8 != pitch8 || !ix->cov_u8.covers(ix->n))
     return fail(WDBX_E_STATE, "u8 shadow not prepared");
   if (l2 && (rc = ensure_row_norms(ix))) return rc;  // squared fp32 norms of the rows (the 2 w - |c|^2 form)
   // the plan (host_selection.h): sampled 256-row tiles of 4 groups of 64 rows each, as on the tile path; a larger sample for
@@ -1167,36 +1281,16 @@ static bool u6_single_eligible(const wdbx_index* ix, int k, int nq_call) {
   return true;
 }
 
-// the three parts of the split planes' allocation, and their quantiser over rows [first, end)
-static inline f2v* u42_sa4(const wdbx_index* ix) { return (f2v*)(ix->d_rows42 + (size_t)ix->rows42_tiles * ix->units42 * 256); }
-static inline uint32_t* u42_lrec(const wdbx_index* ix) { return (uint32_t*)(u42_sa4(ix) + (size_t)ix->rows42_tiles * 64); }
-static hipError_t launch_rows_to_u42(wdbx_index* ix, uint64_t first, uint64_t end) {
-  hipLaunchKernelGGL(rows_to_u42_kernel, dim3(rows_to_u42_grid(end - first)), dim3(256), 0, ix->stream, (const float*)ix->d_rows, (u64)first,
-                     (u64)end, (uint32_t)ix->dim, (uint32_t)ix->pitch, ix->units42, ix->d_rows42, u42_sa4(ix), u42_lrec(ix),
-                     u42_lpitch(ix->units42));
-  return hipGetLastError();
-}
-
 // Allocates / refreshes the u6 shadow for the rows added since the last search that took this path (the life cycle of
 // prepare_u8_shadow).  false = no room on the device (remembered per capacity): the caller stays on the u8 scan.
 static bool prepare_u6_shadow(wdbx_index* ix) {
   const uint32_t units = (uint32_t)ix->pitch / 16;
   const uint64_t tiles = ((uint64_t)ix->cap + 63) / 64;
   const size_t need = (size_t)tiles * units * 768 + (size_t)tiles * 64 * sizeof(f2v);
-  if (!shadow_room(ix, ix->units6 != units || ix->rows6_tiles != tiles, {{&ix->d_rows6, need}}, &ix->shadow6_rows,
-                   &ix->u6_no_room_cap))
-    return false;
+  if (!shadow_room(ix, ix->units6 != units || ix->rows6_tiles != tiles, {{&ix->d_rows6, need}}, &ix->cov_u6)) return false;
   ix->units6 = units;
   ix->rows6_tiles = tiles;
-  if (ix->shadow6_rows < ix->n) {
-    const uint32_t blocks = rows_to_u6_grid(ix->n - ix->shadow6_rows);
-    hipLaunchKernelGGL(rows_to_u6_kernel, dim3(blocks), dim3(256), 0, ix->stream, (const float*)ix->d_rows, (u64)ix->shadow6_rows,
-                       (u64)ix->n, (uint32_t)ix->dim, (uint32_t)ix->pitch, units, ix->d_rows6,
-                       (f2v*)(ix->d_rows6 + (size_t)ix->rows6_tiles * units * 192));
-    if (hipGetLastError() != hipSuccess) return false;
-    ix->shadow6_rows = ix->n;
-  }
-  return true;
+  return extend_copy(ix, DERIVED_COPIES[COPY_U6]) == hipSuccess;
 }
 
 // The split planes behind a u6 round (kernels_scan42.h): rows of whole 32-element units.  Option scan_u42: -1 = where the u6
@@ -1214,16 +1308,10 @@ static bool prepare_u42_shadow(wdbx_index* ix) {
   const uint32_t units = (uint32_t)ix->pitch / 32, lpitch = u42_lpitch(units);
   const uint64_t tiles = ((uint64_t)ix->cap + 63) / 64;
   const size_t need = (size_t)tiles * units * 1024 + (size_t)tiles * 64 * sizeof(f2v) + (size_t)tiles * 64 * lpitch * sizeof(uint32_t);
-  if (!shadow_room(ix, ix->units42 != units || ix->rows42_tiles != tiles, {{&ix->d_rows42, need}},
-                   &ix->shadow42_rows, &ix->u42_no_room_cap))
-    return false;
+  if (!shadow_room(ix, ix->units42 != units || ix->rows42_tiles != tiles, {{&ix->d_rows42, need}}, &ix->cov_u42)) return false;
   ix->units42 = units;
   ix->rows42_tiles = tiles;
-  if (ix->shadow42_rows < ix->n) {
-    if (launch_rows_to_u42(ix, ix->shadow42_rows, ix->n) != hipSuccess) return false;
-    ix->shadow42_rows = ix->n;
-  }
-  return true;
+  return extend_copy(ix, DERIVED_COPIES[COPY_U42]) == hipSuccess;
 }
 
 // queries per read of the four-bit plane where option scan_u42_share leaves it to the library.  10 M x 384, 2000 steps, whole
@@ -1254,13 +1342,13 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
   const int uc = u6_unit_chunk(units);
   scan6_fn f0 = pick_scan6(uc, true), f1 = pick_scan6(uc, false);
   if (!f0 || !f1) return fail(WDBX_E_STATE, "no u6 scan instance for %u units", units);
-  if (!ix->d_rows6 || ix->units6 != units || ix->shadow6_rows < ix->n) return fail(WDBX_E_STATE, "u6 shadow not prepared");
+  if (!ix->d_rows6 || ix->units6 != units || !ix->cov_u6.covers(ix->n)) return fail(WDBX_E_STATE, "u6 shadow not prepared");
   // option scan_u42_share: how many queries of a round share one read of the four-bit plane (-1: U42_SHARE_DEFAULT; 1: none)
   const uint32_t share = ix->opt_scan_u42_share == 1 || ix->opt_scan_u42_share == 2 || ix->opt_scan_u42_share == 4
                              ? (uint32_t)ix->opt_scan_u42_share : U42_SHARE_DEFAULT;
   scan42_fn f42[5] = {};  // by group width: 1, 2, 4
   for (int w = 1; u42 && w <= 4; w *= 2) f42[w] = pick_scan42(u42_unit_chunk(units / 2), w);
-  if (u42 && (!f42[1] || !f42[2] || !f42[4] || !ix->d_rows42 || ix->units42 != units / 2 || ix->shadow42_rows < ix->n))
+  if (u42 && (!f42[1] || !f42[2] || !f42[4] || !ix->d_rows42 || ix->units42 != units / 2 || !ix->cov_u42.covers(ix->n)))
     return fail(WDBX_E_STATE, "split planes not prepared");
   // option scan_u42_mfma: full groups of 16 (and a remainder of U42_MFMA_MIN_SHORT or more) on scan_u42_mfma_kernel.  -1: where
   // the unit count has an instance and scan_u42_share is left at -1; 1: wherever an instance exists; 0: never.  An explicit
@@ -1318,7 +1406,7 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
     const float* qsrc = d_queries + (size_t)q0 * ix->pitch;
     Scan6Args a = {};
     a.codes = ix->d_rows6;
-    a.sa = (const f2v*)(ix->d_rows6 + (size_t)ix->rows6_tiles * units * 192);
+    a.sa = u6_sa(ix);
     a.query = qsrc;
     a.n_rows = (uint32_t)ix->n;
     a.units = units;
@@ -1461,7 +1549,7 @@ static bool prepare_i8g_shadow(wdbx_index* ix) {
   const size_t need = (((size_t)ix->cap + G8_ROWS - 1) / G8_ROWS + 1) * G8_ROWS * pitch8;  // whole tiles (fragment order) + one of slack
   const size_t need_g = (((size_t)ix->cap + TILE_PAD_ROWS + 63) / 64 + 1) * sizeof(f4);
   const int room = shadow_room(ix, ix->pitch8g != pitch8, {{&ix->d_rows8g, need}, {&ix->d_groups8, need_g}, {&ix->d_gbad8, need_g / 2}},
-                               &ix->shadowg_rows, &ix->i8g_no_room_cap);
+                               &ix->cov_i8g);
   if (room != SHADOW_KEPT) ix->shadowg_tail_n = ~0ull;
   if (room == SHADOW_NO_ROOM) return false;
   if (room == SHADOW_FRESH) {
@@ -1478,18 +1566,10 @@ static bool prepare_i8g_shadow(wdbx_index* ix) {
   // threshold sample.  After wdbx_index_clear() + fewer rows, or a compaction that dropped live tail rows, the groups between
   // ceil(n / 64) and the tile's end would otherwise keep the OLD corpus's bytes, table entries and "good" bits, their lower
   // bounds could enter the k-th largest, and a threshold above the true k-th score silently drops true neighbours.
-  if (ix->shadowg_rows < ix->n || ix->shadowg_tail_n != ix->n) {
-    const u64 g0 = std::min<u64>(ix->shadowg_rows, ix->n) / 64;
-    const u64 g1 = (ix->n + G8_ROWS - 1) / G8_ROWS * (G8_ROWS / 64);
-    if (g1 > g0) {
-      hipLaunchKernelGGL(rows_to_i8g_kernel, dim3(rows_to_i8g_grid(g1 - g0)), dim3(256), 0, ix->stream,
-                         (const float*)ix->d_rows, g0, g1, (u64)ix->n, (uint32_t)ix->dim, (uint32_t)ix->pitch, ix->d_rows8g, pitch8,
-                         ix->d_groups8, ix->d_gbad8);
-      if (hipGetLastError() != hipSuccess) return false;
-    }
-    ix->shadowg_rows = ix->n;
+  if (!ix->cov_i8g.covers(ix->n) || ix->shadowg_tail_n != ix->n) {
+    const uint64_t tile_end = (ix->n + G8_ROWS - 1) / G8_ROWS * G8_ROWS;
+    if (extend_copy(ix, DERIVED_COPIES[COPY_I8G], std::min<uint64_t>(ix->cov_i8g.rows, ix->n), tile_end) != hipSuccess) return false;
     ix->shadowg_tail_n = ix->n;
-    ix->gref_valid = false;
   }
   return true;
 }
@@ -1499,6 +1579,16 @@ static bool prepare_i8g_shadow(wdbx_index* ix) {
 static bool masked_tiles_ready(wdbx_index* ix, int k) {
   if (ix->opt_gemm_masked <= 0 || ix->opt_gemm8_variant != 0 || use_select(ix, k) || !ix->n) return false;
   return i8_tiles_shape_ok(ix) && prepare_i8g_shadow(ix);
+}
+// Allocates / refreshes the bf16 shadow for the rows added since the last batch on its tiles.  *use = false: no room on the
+// device, the same tiles read the fp32 rows (nothing is remembered: the next batch tries again).
+static hipError_t prepare_bf16_shadow(wdbx_index* ix, bool* use) {
+  const uint32_t pitch16 = (uint32_t)((ix->pitch + 127) / 128 * 128);  // whole pairs of 64-element chunks
+  const size_t need = ((size_t)ix->cap + TILE_PAD_ROWS) * pitch16 * 2;
+  const int room = shadow_room(ix, ix->pitch16 != pitch16, {{&ix->d_rows16, need}}, &ix->cov_bf16);
+  if (room == SHADOW_FRESH) ix->pitch16 = pitch16;
+  *use = room != SHADOW_NO_ROOM;
+  return *use ? extend_copy(ix, DERIVED_COPIES[COPY_BF16]) : hipSuccess;
 }
 // (the instances, their pickers and the launch helpers: kernels_tiles.h, behind the kernels)
 template <int PHASE, int CT>
@@ -1548,20 +1638,9 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
   // short rows: the padded shadow would be no smaller than the fp32 rows, so the tiles read those
   if (family == GEMM_BF16_SHADOW && ((uint64_t)ix->pitch + 127) / 128 * 128 >= 2 * (uint64_t)ix->pitch) family = GEMM_BF16;
   if (family == GEMM_BF16_SHADOW) {  // the bf16 shadow copy of the rows added since the last batch
-    const uint32_t pitch16 = (uint32_t)((ix->pitch + 127) / 128 * 128);  // whole pairs of 64-element chunks
-    const size_t need = ((size_t)ix->cap + TILE_PAD_ROWS) * pitch16 * 2;
-    uint64_t every_call = ~0ull;  // (a shadow that found no room is tried again by the next batch: nothing is remembered)
-    const int room = shadow_room(ix, ix->pitch16 != pitch16, {{&ix->d_rows16, need}}, &ix->shadow_rows, &every_call);
-    if (room == SHADOW_FRESH) ix->pitch16 = pitch16;
-    if (room == SHADOW_NO_ROOM) family = GEMM_BF16;  // the same tiles on the fp32 rows
-    if (family == GEMM_BF16_SHADOW && ix->shadow_rows < ix->n) {
-      const u64 pieces = (ix->n - ix->shadow_rows) * (pitch16 / 8);
-      hipLaunchKernelGGL(rows_to_bf16_kernel, dim3((uint32_t)std::min<u64>((pieces + 255) / 256, 1u << 20)), dim3(256), 0,
-                         ix->stream, (const float*)ix->d_rows, (u64)ix->shadow_rows, (u64)ix->n, (uint32_t)ix->pitch,
-                         (__bf16*)ix->d_rows16.p, pitch16);
-      HIP_TRY(hipGetLastError());
-      ix->shadow_rows = ix->n;
-    }
+    bool shadow = false;
+    HIP_TRY(prepare_bf16_shadow(ix, &shadow));
+    if (!shadow) family = GEMM_BF16;  // no room: the same tiles on the fp32 rows
   }
   ix->last_gemm_mode = family;
   const bool l2 = ix->metric == WDBX_METRIC_L2, bf16 = family != GEMM_FP32;
@@ -1593,37 +1672,7 @@ static int enqueue_search_gemm(wdbx_index* ix, const float* d_queries, int nq, i
   if (bf16 && (rc = ix->d_qb16.grow((size_t)GB_N * kpad * 2))) return rc;
   if (inexact) {  // squared norms of the rows added since the last such batch (L2 term, and the error margin)
     if ((rc = ensure_row_norms(ix))) return rc;
-    // How the selection error is bounded.  Norms all alike (the reference normalises its rows): ONE bound from the
-    // largest norm, subtracted from the thresholds (tau_margin_kernel) -- nothing in the tile epilogue.  Norms that
-    // vary a lot (largest > 1.5 x mean: unnormalised data, outlier rows): a bound per 64-row group from that group's
-    // largest norm, applied in the epilogue (+10 % kernel time), so an outlier only loosens its own group and the
-    // batch does not degenerate into per-query repairs.  Decided when the norms change (one 8-byte read-back).
-    if (!ix->gmax_valid) {
-      if (ix->cn_stats_dirty) {  // rows were overwritten in place: rebuild maximum / sum / count from the cached norms
-        HIP_TRY(hipMemsetAsync(ix->d_cnmax, 0, 4 * sizeof(uint32_t), ix->stream));
-        hipLaunchKernelGGL(cn_stats_kernel, dim3((uint32_t)std::min<uint64_t>((ix->n + 255) / 256, 2048)), dim3(256), 0, ix->stream,
-                           (const float*)ix->d_cn, (u64)ix->n, ix->d_cnmax);
-        HIP_TRY(hipGetLastError());
-        ix->cn_stats_dirty = false;
-      }
-      uint32_t words[3] = {0, 0, 0};
-      HIP_TRY(hipMemcpyAsync(words, ix->d_cnmax, sizeof words, hipMemcpyDeviceToHost, ix->stream));
-      HIP_TRY(hipStreamSynchronize(ix->stream));
-      float cmax, csum;
-      memcpy(&cmax, &words[0], 4);
-      memcpy(&csum, &words[1], 4);
-      const float mean = words[2] ? csum / (float)words[2] : 0.f;  // over the rows with a finite norm (removed rows are NaN)
-      // an infinite norm (a row with an infinite or huge element) always takes the per-group instances: their epilogue
-      // sends such a group's rows to the exact pass whatever the selection scores say (kernels_tiles.h)
-      ix->group_bounds = ix->opt_group_bounds == 1 || !(cmax < INFINITY) || (ix->opt_group_bounds != 0 && !(cmax <= 1.5f * mean));
-      if (ix->group_bounds) {
-        if ((rc = ix->d_gmax.grow(((size_t)ix->cap + 63) / 64 * sizeof(float)))) return rc;
-        const uint32_t gblocks = (uint32_t)std::min<uint64_t>(((ix->n + 63) / 64 + 255) / 256, 4096);
-        hipLaunchKernelGGL(group_max_kernel, dim3(gblocks), dim3(256), 0, ix->stream, (const float*)ix->d_cn, (u64)ix->n, ix->d_gmax);
-        HIP_TRY(hipGetLastError());
-      }
-      ix->gmax_valid = true;
-    }
+    if ((rc = decide_group_bounds(ix))) return rc;
     if ((rc = ix->d_qn.grow((size_t)2 * GB_N * sizeof(float)))) return rc;
   }
   const bool group_bounds = inexact && ix->group_bounds;
@@ -2043,49 +2092,15 @@ static int upload_rows(wdbx_index* ix, uint64_t first, const float* rows, uint64
   int rc = copy_padded(ix, dst, rows, n, ix->dim);
   if (rc) return rc;
   if (normalize && (rc = launch_normalize(ix, dst, n))) return rc;
-  // Derived copies (cached norms, bf16 and u8 shadows) of OVERWRITTEN rows are refreshed right here, for exactly
+  // Derived copies (DERIVED_COPIES: norms and every shadow) of OVERWRITTEN rows are refreshed right here, for exactly
   // those rows: an update in the middle of a large corpus must not invalidate everything behind it.  Rows appended
   // past what a copy covers are picked up lazily by the next search, as before.
-  const uint64_t end = first + n;
-  if (first < ix->cn_rows && ix->d_cn) {
-    const uint64_t e = std::min(end, ix->cn_rows);
-    hipLaunchKernelGGL(row_sqnorm_kernel, dim3(row_sqnorm_grid(e - first)), dim3(256), 0, ix->stream,
-                       (const float*)ix->d_rows, (u64)first, (u64)e, (uint32_t)ix->pitch, ix->d_cn, (uint32_t*)nullptr);
-    HIP_TRY(hipGetLastError());
-    ix->gmax_valid = false;
-    ix->cn_stats_dirty = true;  // the running maximum / sum would keep the overwritten rows' old norms
+  for (const DerivedCopy& c : DERIVED_COPIES) {
+    const RowRange r = (ix->*c.cov).overlap(first, first + n);
+    if (r.empty() || !c.present(ix)) continue;
+    HIP_TRY(c.launch(ix, r.first, r.end, false));
+    if (c.drops) c.drops(ix, false);
   }
-  if (first < ix->shadow_rows && ix->d_rows16) {
-    const uint64_t e = std::min(end, ix->shadow_rows);
-    const u64 pieces = (e - first) * (ix->pitch16 / 8);
-    hipLaunchKernelGGL(rows_to_bf16_kernel, dim3((uint32_t)std::min<u64>((pieces + 255) / 256, 1u << 20)), dim3(256), 0, ix->stream,
-                       (const float*)ix->d_rows, (u64)first, (u64)e, (uint32_t)ix->pitch, (__bf16*)ix->d_rows16.p, ix->pitch16);
-    HIP_TRY(hipGetLastError());
-  }
-  if (first < ix->shadowg_rows && ix->d_rows8g) {  // whole groups: a group's scale depends on all of its rows
-    const uint64_t e = std::min(end, ix->shadowg_rows);
-    const u64 g0 = first / 64, g1 = (e + 63) / 64;
-    hipLaunchKernelGGL(rows_to_i8g_kernel, dim3(rows_to_i8g_grid(g1 - g0)), dim3(256), 0, ix->stream,
-                       (const float*)ix->d_rows, g0, g1, (u64)std::max<uint64_t>(ix->n, end), (uint32_t)ix->dim, (uint32_t)ix->pitch,
-                       ix->d_rows8g, ix->pitch8g, ix->d_groups8, ix->d_gbad8);
-    HIP_TRY(hipGetLastError());
-    ix->gref_valid = false;
-  }
-  if (first < ix->shadow8_rows && ix->d_rows8) {
-    const uint64_t e = std::min(end, ix->shadow8_rows);
-    hipLaunchKernelGGL(rows_to_u8_kernel, dim3(rows_to_u8_grid(e - first)), dim3(256), 0, ix->stream,
-                       (const float*)ix->d_rows, (u64)first, (u64)e, (uint32_t)ix->dim, (uint32_t)ix->pitch, ix->d_rows8, ix->pitch8,
-                       ix->d_scale8);
-    HIP_TRY(hipGetLastError());
-  }
-  if (first < ix->shadow6_rows && ix->d_rows6) {
-    const uint64_t e = std::min(end, ix->shadow6_rows);
-    hipLaunchKernelGGL(rows_to_u6_kernel, dim3(rows_to_u6_grid(e - first)), dim3(256), 0, ix->stream,
-                       (const float*)ix->d_rows, (u64)first, (u64)e, (uint32_t)ix->dim, (uint32_t)ix->pitch, ix->units6, ix->d_rows6,
-                       (f2v*)(ix->d_rows6 + (size_t)ix->rows6_tiles * ix->units6 * 192));
-    HIP_TRY(hipGetLastError());
-  }
-  if (first < ix->shadow42_rows && ix->d_rows42) HIP_TRY(launch_rows_to_u42(ix, first, std::min(end, ix->shadow42_rows)));
   HIP_TRY(hipStreamSynchronize(ix->stream));
   return WDBX_OK;
 }
@@ -2099,12 +2114,7 @@ static int upload_rows(wdbx_index* ix, uint64_t first, const float* rows, uint64
 constexpr size_t UPDATE_KEEP_BYTES = 16u << 20;  // a larger block of caller rows is released at the end of its call
 static int update_rows_at(wdbx_index* ix, const uint32_t* ids, uint64_t n, const float* rows, int normalize) {
   UpdateCoverage cov;
-  cov.cn = ix->d_cn ? ix->cn_rows : 0;
-  cov.bf16 = ix->d_rows16 ? ix->shadow_rows : 0;
-  cov.i8g = ix->d_rows8g ? ix->shadowg_rows : 0;
-  cov.u8 = ix->d_rows8 ? ix->shadow8_rows : 0;
-  cov.u6 = ix->d_rows6 ? ix->shadow6_rows : 0;
-  cov.u42 = ix->d_rows42 ? ix->shadow42_rows : 0;
+  for (const DerivedCopy& c : DERIVED_COPIES) update_cover(&cov, c.listed, ix->*c.cov, c.present(ix));
   const UpdatePlan p = update_plan(ids, n, (uint32_t)ix->dim, cov, rows != nullptr);
   ix->last_update_launches = p.launches;
   if (!n) return WDBX_OK;
@@ -2125,36 +2135,19 @@ static int update_rows_at(wdbx_index* ix, const uint32_t* ids, uint64_t n, const
                        (float*)ix->d_rows, normalize);
     HIP_TRY(hipGetLastError());
   }
-  // the validity flags upload_rows drops for an overwritten row of the same copies
-  if (p.n_cn) {
-    ix->gmax_valid = false;
-    ix->cn_stats_dirty = true;
+  // every copy that covers a listed row (the list is increasing): the validity flags upload_rows drops for an overwritten row
+  // of it, and its part of the fused refresh
+  UpdateArgs a = {};
+  a.rows = ix->d_rows;
+  a.list = d_list;
+  a.dim = (uint32_t)ix->dim;
+  a.pitch = (uint32_t)ix->pitch;
+  for (const DerivedCopy& c : DERIVED_COPIES) {
+    if (ids[0] >= cov.*c.listed) continue;
+    if (c.drops) c.drops(ix, false);
+    if (c.listed_args) c.listed_args(ix, p, &a);
   }
   if (p.n_refresh) {
-    UpdateArgs a = {};
-    a.rows = ix->d_rows;
-    a.list = d_list;
-    a.dim = (uint32_t)ix->dim;
-    a.pitch = (uint32_t)ix->pitch;
-    a.n_cn = p.n_cn, a.n_16 = p.n_16, a.n_8 = p.n_8, a.n_6 = p.n_6, a.n_42 = p.n_42;
-    a.cn = ix->d_cn;
-    a.rows16 = (__bf16*)ix->d_rows16.p;
-    a.pitch16 = ix->pitch16;
-    a.rows8 = ix->d_rows8;
-    a.pitch8 = ix->pitch8;
-    a.scale8 = ix->d_scale8;
-    if (p.n_6) {
-      a.units6 = ix->units6;
-      a.codes6 = ix->d_rows6;
-      a.sa6 = (f2v*)(ix->d_rows6 + (size_t)ix->rows6_tiles * ix->units6 * 192);
-    }
-    if (p.n_42) {
-      a.units42 = ix->units42;
-      a.lpitch42 = u42_lpitch(ix->units42);
-      a.h42 = ix->d_rows42;
-      a.sa42 = u42_sa4(ix);
-      a.lrec42 = u42_lrec(ix);
-    }
     hipLaunchKernelGGL(update_refresh_kernel, dim3(update_rows_grid(p.n_refresh)), dim3(256), 0, ix->stream, a);
     HIP_TRY(hipGetLastError());
   }
@@ -2163,7 +2156,6 @@ static int update_rows_at(wdbx_index* ix, const uint32_t* ids, uint64_t n, const
                        (const float*)ix->d_rows, d_groups, (u64)p.groups.size(), (u64)ix->n, (uint32_t)ix->dim, (uint32_t)ix->pitch,
                        ix->d_rows8g, ix->pitch8g, ix->d_groups8, ix->d_gbad8);
     HIP_TRY(hipGetLastError());
-    ix->gref_valid = false;
   }
   HIP_TRY(hipStreamSynchronize(ix->stream));  // (ids, the plan's groups and the caller's rows are free again)
   if (ix->d_upd_rows.bytes > UPDATE_KEEP_BYTES) return ix->d_upd_rows.release();

@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "host_copies.h"
 #include "host_subset.h"
 
 // bytes of caller rows one upload round carries at most (the scratch block never grows past it)
@@ -19,6 +20,10 @@ constexpr uint64_t UPDATE_ROUND_BYTES = 256ull << 20;
 struct UpdateCoverage {
   uint64_t cn = 0, bf16 = 0, i8g = 0, u8 = 0, u6 = 0, u42 = 0;
 };
+// one copy's entry: its coverage (host_copies.h) where its buffer exists
+static inline void update_cover(UpdateCoverage* c, uint64_t UpdateCoverage::*field, const CopyCoverage& cov, bool present) {
+  c->*field = present ? cov.rows : 0;
+}
 
 struct UpdatePlan {
   uint64_t n = 0;                                  // listed rows

@@ -69,6 +69,7 @@
 //   kernels_update.h        update_scatter_kernel, update_refresh_kernel, rows_to_i8g_list_kernel: wdbx_index_set_rows_at /
 //                           wdbx_index_remove_rows -- a call's rows to their listed places (or the NaN tombstone), then every derived
 //                           copy of exactly those rows through the per-row functions the range quantisers call
+//   host_copies.h           the coverage of one derived copy of the rows and its transitions; whether its allocations may stay
 //   host_update.h           that call's coverage counts, distinct int8 groups, upload rounds and launch count
 //   host_multimask.h        a call with one row mask per query: the placement of its queries in the int8 tiles' query blocks
 //   host_selection.h        the plan of the selection rounds: sampled tiles, stride, candidate and pair capacities of the tile paths and
@@ -299,13 +300,8 @@ int wdbx_index_clear(wdbx_index* ix) try {
   DeviceGuard g(ix->device);
   HIP_TRY(hipStreamSynchronize(ix->stream));
   ix->n = 0;
-  ix->cn_rows = 0;
+  for (const DerivedCopy& c : DERIVED_COPIES) (ix->*c.cov).reset();
   ix->cn_stats_dirty = false;
-  ix->shadow_rows = 0;
-  ix->shadow8_rows = 0;
-  ix->shadow6_rows = 0;
-  ix->shadow42_rows = 0;
-  ix->shadowg_rows = 0;
   ix->shadowg_tail_n = ~0ull;
   ix->labels.clear();  // (back to "no label was ever set")
   ix->lab_valid = false;
@@ -447,12 +443,7 @@ int wdbx_index_compact(wdbx_index* ix, const uint64_t* src_rows, uint64_t n_keep
   }
   ix->lab_valid = false;
   ix->n = n_keep;
-  ix->cn_rows = std::min(ix->cn_rows, first_moved);
-  ix->shadow_rows = std::min(ix->shadow_rows, first_moved);
-  ix->shadow8_rows = std::min(ix->shadow8_rows, first_moved);
-  ix->shadow6_rows = std::min(ix->shadow6_rows, first_moved);
-  ix->shadow42_rows = std::min(ix->shadow42_rows, first_moved);
-  ix->shadowg_rows = std::min(ix->shadowg_rows, first_moved / 64 * 64);  // (whole 64-row groups: a group's scale depends on all its rows)
+  for (const DerivedCopy& c : DERIVED_COPIES) (ix->*c.cov).cut(first_moved);
   ix->shadowg_tail_n = ~0ull;  // the groups behind the new last row still describe dropped rows: rewritten by the next batch
   ix->cn_stats_dirty = true;  // the running maximum / sum still hold the dropped rows' norms
   ix->gmax_valid = false;
@@ -2945,11 +2936,10 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   std::lock_guard<std::mutex> lk(ix->mu);
   // read-only state of the batched path
   if (name && !strcmp(name, "last_gemm_family")) return *value = ix->last_gemm_mode, WDBX_OK;
-  if (name && !strcmp(name, "shadow_rows")) return *value = (int64_t)ix->shadow_rows, WDBX_OK;
+  for (const DerivedCopy& c : DERIVED_COPIES)  // shadow_rows, shadowg_rows, shadow8_rows, shadow6_rows, shadow42_rows
+    if (name && c.rows_option && !strcmp(name, c.rows_option)) return *value = (int64_t)(ix->*c.cov).rows, WDBX_OK;
   if (name && !strcmp(name, "shadow_bytes")) return *value = (int64_t)ix->d_rows16.bytes, WDBX_OK;
-  if (name && !strcmp(name, "shadow8_rows")) return *value = (int64_t)ix->shadow8_rows, WDBX_OK;
   if (name && !strcmp(name, "shadow8_bytes")) return *value = (int64_t)(ix->d_rows8.bytes + ix->d_scale8.bytes), WDBX_OK;
-  if (name && !strcmp(name, "shadowg_rows")) return *value = (int64_t)ix->shadowg_rows, WDBX_OK;
   if (name && !strcmp(name, "shadowg_bytes")) return *value = (int64_t)(ix->d_rows8g.bytes + ix->d_groups8.bytes), WDBX_OK;
   if (name && !strcmp(name, "last_single_path")) return *value = ix->last_single_path, WDBX_OK;
   if (name && !strcmp(name, "last_single_u6")) return *value = ix->last_single_u6, WDBX_OK;
@@ -2978,9 +2968,7 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
     for (uint32_t v : c) sum += v;
     return *value = sum, WDBX_OK;
   }
-  if (name && !strcmp(name, "shadow42_rows")) return *value = (int64_t)ix->shadow42_rows, WDBX_OK;
   if (name && !strcmp(name, "shadow42_bytes")) return *value = (int64_t)ix->d_rows42.bytes, WDBX_OK;
-  if (name && !strcmp(name, "shadow6_rows")) return *value = (int64_t)ix->shadow6_rows, WDBX_OK;
   if (name && !strcmp(name, "shadow6_bytes")) return *value = (int64_t)ix->d_rows6.bytes, WDBX_OK;
   if (name && !strcmp(name, "last_range_path")) return *value = ix->last_range_path, WDBX_OK;
   if (name && !strcmp(name, "last_range_batch_path")) return *value = ix->last_range_batch_path, WDBX_OK;
