@@ -415,8 +415,20 @@ int wdbx_index_search_group_members(wdbx_index* idx, const float* queries, int n
  *   row scored once per block of 8 vectors; counted as scan launches in wdbx_index_profile_read), then one reduce-and-rank
  *   kernel (per-workgroup top-k lists and the merge kernel below option "select_min_k", a key per label and the radix-select
  *   chain from it).  The answer does not depend on the rounds.
+ *   Scoring route of a round (inner product / cosine handles only; an L2 handle always takes the kernel above): option
+ *   "multivector_tiles" = 0 never, 1 every round, -1 (the default) a round of at least option
+ *   "multivector_tiles_min_vectors" vectors (default 24, 1 .. 256); any other value is WDBX_E_INVALID.  On that route a wave
+ *   reads a span of 64 gathered rows ONCE for a block of up to 128 vectors: a fp32 pass on the matrix cores
+ *   (v_mfma_f32_32x32x2_f32) finds, per vector and item (a run of one label inside a span), the best and second-best row.
+ *   With u = 2^-24, n = row pitch + 18, gamma = n u / (1 - n u), under = n 2^-149, R the largest norm among the span's
+ *   eligible rows and |c| the vector's norm (both rounded up), the pair is CERTAIN when everything is finite and
+ *       best - second > 4 (gamma R |c| + under):
+ *   the exact arithmetic's maximum over the item is then that row's, uniquely, and only that row is scored with it; any other
+ *   pair is AMBIGUOUS and every eligible row of the item is scored, as on the other route.  Either way the score that enters
+ *   the key is the exact arithmetic's, so the keys -- and every property above -- are the same bits at every setting.
  *   get_option, read-only: "last_multivector_rounds", "last_multivector_vectors", "last_multivector_labels" (0 after a call
- *   on an empty index). */
+ *   on an empty index); "last_multivector_tile_rounds" (rounds of the last call scored on the matrix cores),
+ *   "last_multivector_pairs" (their (vector, item) pairs) and "last_multivector_ambiguous" (of these, the ambiguous ones). */
 #define WDBX_MAX_QUERY_VECTORS 1024
 int wdbx_index_search_multivector(wdbx_index* idx,
                                   const float* vectors,           /* [vector_offsets[nq], dim]: the queries' vectors back to back */
@@ -788,8 +800,9 @@ int wdbx_index_probe_read(wdbx_index* idx, int nontemporal, int blocks, int reps
  * scan_shadow (2 u8 selection scan / 1 bf16 tiles / 0 fp32 scan; range search: 2 u8 selection, below 2 the fp32 range scan), scan8_wgs, single_min_rows,
  * range_min_rows (rows from which a range search takes the u8 selection scan, default 131 072), gemm_bf16 (tile family
  * 3/2/1/0 as above), gemm_ct, gemm_l2, gemm_l2_i8, gemm8_variant (the i8 tiles' full-pass epilogue, for A/B: 0 = 14 the product form, 12, 13; any other value returns WDBX_E_INVALID), gemm8_refine (1: second selection stage of the i8 tiles, default), batch_repair, scan8_per_query, scan8_sample4 (1: a round's sample pass serves 3-4 queries per workgroup when the sample is too large for the L2s; 2: always; 0: never), gemm_min_queries, gemm_min_rows, gemm_min_work (below gemm_min_rows: the tiles from queries x rows >= this, default 800000; 0: never), gemm_sample_div, gemm_masked (1: a masked call with enough queries is one masked pass over the int8 tiles, default; 0: masked per-query scans), group_bounds, rows_keys_max (wdbx_index_search_rows: lists of at most this many rows are ranked from one key per listed row, default 8192; 0: never),
- * scan_u42_mfma (the split planes' full passes of a round on the matrix cores, 16 queries per read of the four-bit plane: -1 where the row's unit count has an instance (d from 257 to 384) and scan_u42_share is -1, default; 0: never; 1: wherever an instance exists; any other value returns WDBX_E_INVALID.  Answers are bit-identical at every setting).
- * get_option also answers the read-only names: last_u42_mfma_groups (the groups of 16 queries whose full pass ran on the matrix cores in the last call), last_gemm_family (0/1/2/3: what the last batch ran on),
+ * scan_u42_mfma (the split planes' full passes of a round on the matrix cores, 16 queries per read of the four-bit plane: -1 where the row's unit count has an instance (d from 257 to 384) and scan_u42_share is -1, default; 0: never; 1: wherever an instance exists; any other value returns WDBX_E_INVALID.  Answers are bit-identical at every setting),
+ * multivector_tiles (the scoring of a round of wdbx_index_search_multivector on the matrix cores, up to 128 vectors per row read, inner product / cosine only: -1 a round of at least multivector_tiles_min_vectors vectors, default; 0: never; 1: every round; any other value returns WDBX_E_INVALID.  Answers are bit-identical at every setting), multivector_tiles_min_vectors (default 24, 1 .. 256).
+ * get_option also answers the read-only names: last_multivector_tile_rounds, last_multivector_pairs, last_multivector_ambiguous (the last multi-vector call's rounds on the matrix cores, their (vector, item) pairs and those of them the certainty margin left to the exact arithmetic), last_u42_mfma_groups (the groups of 16 queries whose full pass ran on the matrix cores in the last call), last_gemm_family (0/1/2/3: what the last batch ran on),
  * last_single_path (0 fp32 scan / 1 bf16 tiles / 2 u8 selection scan), last_range_path (0 fp32 range scan / 2 u8 selection + exact filter), last_rows_path (the route of the last wdbx_index_search_rows: 0 nothing launched / 1 keys + merge / 2 lists + merge / 3 keys + radix select), last_sample_qn (queries per workgroup of the last u8 sample launch: 1, 3 or 4), last_batch_repaired, last_batch_masked (1: the last batch ran the masked tile pass), last_batch_allowed_rows (the rows its mask allowed), shadow_rows + shadow_bytes (bf16 copy),
  * shadow8_rows + shadow8_bytes (u8 copy), shadowg_rows + shadowg_bytes (group-scaled i8 copy), group_bounds_active,
  * exchanges (all-gather + merge steps this handle's per-rank communicator has enqueued), device_bytes_resident (every device

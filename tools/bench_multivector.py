@@ -7,8 +7,10 @@
   * the rounds the call took, and the scoring time per block of 8 vectors (the yardstick: the distinct search's full pass on
     the same corpus, profiles/distinct/).
 
-    python tools/bench_multivector.py [rows] [dim] [k] [reps] [--out FILE]
+    python tools/bench_multivector.py [rows] [dim] [k] [reps] [--out FILE] [--tiles {0,1}] [--rows-per-label N] [--vectors 8,32]
 
+--tiles sets option multivector_tiles for every call (0 = the vector-ALU scoring pass, 1 = the matrix-core pass; without the
+switch the library's default route); each record then carries the call's tile rounds and its ambiguous share.
 One JSON line per case on stdout; --out appends them to FILE (default profiles/multivector/results.jsonl)."""
 import json
 import sys
@@ -34,7 +36,9 @@ out_path.parent.mkdir(parents=True, exist_ok=True)
 ix = _native.NativeIndex(dim, capacity_rows=rows)
 ix.fill_synthetic(0xC0FFEE, 0, rows, True)
 rng = np.random.default_rng(1)
-vectors = rng.standard_normal((32, dim)).astype(np.float32)
+counts = [int(v) for v in flags.get("--vectors", "8,32").split(",")]
+per_label = int(flags.get("--rows-per-label", 10))
+vectors = rng.standard_normal((max(32, *counts), dim)).astype(np.float32)
 vectors /= np.linalg.norm(vectors, axis=1, keepdims=True)
 
 
@@ -49,12 +53,14 @@ def median(v):
     return float(np.median(v))
 
 
-ix.set_labels(0, (np.arange(rows, dtype=np.uint64) // 10).astype(np.uint32))
+ix.set_labels(0, (np.arange(rows, dtype=np.uint64) // per_label).astype(np.uint32))
+if "--tiles" in flags:
+    ix.set_option("multivector_tiles", int(flags["--tiles"]))
 ix.profile(True)
 t0 = time.perf_counter()
 ix.search_multivector(vectors[:1], [0, 1], k)  # (builds and uploads the label order)
 first_ms = (time.perf_counter() - t0) * 1e3
-for nv in (8, 32):
+for nv in counts:
     ix.search_multivector(vectors[:nv], [0, nv], k)
     ix.profile_read()
     wall, dev_scan, dev_rank = [], [], []
@@ -71,6 +77,9 @@ for nv in (8, 32):
           "wall_ms_per_query": median(wall), "scoring_dev_ms": s_ms, "reduce_rank_merge_dev_ms": r_ms,
           "reduce_rank_merge_share": r_ms / (s_ms + r_ms) if s_ms + r_ms > 0 else None,
           "scoring_dev_ms_per_block_of_8": s_ms / (nv / 8),
+          "rows_per_label": per_label, "tiles": flags.get("--tiles"), "tile_rounds": ix.get_option("last_multivector_tile_rounds"),
+          "ambiguous_share": ix.get_option("last_multivector_ambiguous") / max(1, ix.get_option("last_multivector_pairs")),
+          "scoring_tflops": 2e-9 * nv * rows * dim / s_ms if s_ms > 0 else None,
           "first_call_with_label_order_build_ms": first_ms,
           "device_bytes_resident": ix.get_option("device_bytes_resident")})
 ix.close()

@@ -53,6 +53,9 @@
 //   kernels_multivector.h   multivector_rank_kernel: the reduction and ranking of wdbx_index_search_multivector (late interaction): per
 //                           label the sum over a query's vectors of the vector's best key score, the labels ranked by that sum
 //   host_multivector.h      the rounds and segments of that call's vectors, its route, grids and scratch
+//   kernels_multivector_tiles.h  label_keys_tile_kernel: that call's scoring on the fp32 matrix cores (metric 0) -- a span's gathered rows
+//                           against up to 128 vectors per row read, a certainty margin, the exact resolve in the same launch
+//   host_multivector_tiles.h  which rounds take it, the vector blocks, the instance, its LDS and grid
 //   kernels_mmr.h           mmr_pairs_kernel, mmr_select_kernel: wdbx_index_search_mmr (maximal marginal relevance) behind its pool -- the
 //                           similarity square of a query's gathered candidates and the greedy selection over it
 //   host_mmr.h              that call's argument checks, pools, rounds and grids
@@ -124,6 +127,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_scan_plan.h"  // (device-free as well: the fp32 scan and range forms of a pitch, grid / list / chunk / LDS numbers of a scan)
 #include "host_labels.h"  // (device-free as well: label order, items, over-fetch walk, rounds and scratch of a distinct search)
 #include "host_multivector.h"  // (device-free as well: rounds, segments, route and scratch of a multi-vector search)
+#include "host_multivector_tiles.h"  // (device-free as well: route, vector blocks, instance, LDS and grid of its matrix-core scoring)
 #include "host_rowlists.h"  // (device-free as well: slots, rounds, query blocks and work items of a call with a row list per query)
 #include "host_mmr.h"  // (device-free as well: argument checks, pools, rounds and grids of an MMR search)
 #include "host_recommend.h"  // (device-free as well: offsets, exclusion list, plan, short queries and splice of a recommend search)
@@ -171,6 +175,8 @@ static_assert(ASSIGN_MAX_CENTERS == WDBX_MAX_CENTERS, "the plan's limit is the h
 static_assert(LABEL_SPAN_DEV == LABEL_SPAN, "the kernels walk the spans the host built");
 #include "kernels_multivector.h"
 static_assert(MULTIVECTOR_MAX_VECTORS == WDBX_MAX_QUERY_VECTORS, "the plan's limit is the header's");
+#include "kernels_multivector_tiles.h"
+static_assert(MVT_SPAN == LABEL_SPAN, "a wave of the tile route owns one span of the label order");
 #include "kernels_mmr.h"
 static_assert(MMR_MAX_POOL == WDBX_MAX_K, "a pool is a top-k answer");
 #include "kernels_recommend.h"
@@ -1508,7 +1514,8 @@ int wdbx_index_search_group_members(wdbx_index* ix, const float* queries, int nq
 // ---- multi-vector search: labels ranked by the sum of per-vector best scores (host_multivector.h, kernels_multivector.h,
 // DESIGN.md section 4.12) ----
 // Under the handle's mutex to its end.  Per round of vectors (multivector_plan): label_keys_kernel with the round's vectors as
-// its queries (bracketed as a scan launch), multivector_rank_kernel over the round's segments and, for the segments that end a
+// its queries or, where options multivector_tiles / multivector_tiles_min_vectors send the round there (metric 0 only),
+// label_keys_tile_kernel, which fills the same keys bit for bit (either one bracketed as a scan launch), multivector_rank_kernel over the round's segments and, for the segments that end a
 // query, merge_kernel over their partial lists or per query the radix-select chain over its label keys (bracketed as merge
 // launches).  No memset: every item key, accumulator entry, list entry and label key that is read has been written.
 int wdbx_index_search_multivector(wdbx_index* ix, const float* vectors, const uint64_t* vector_offsets, int nq, int k,
@@ -1529,6 +1536,7 @@ int wdbx_index_search_multivector(wdbx_index* ix, const float* vectors, const ui
   int rc;
   const size_t elems = (size_t)nq * k;
   ix->last_multivector_rounds = ix->last_multivector_vectors = ix->last_multivector_labels = 0;
+  ix->last_multivector_tile_rounds = ix->last_multivector_ambiguous = ix->last_multivector_pairs = 0;
   if (ix->n == 0) {  // every slot empty, nothing launched
     for (size_t i = 0; i < elems; ++i) {
       out_idx[i] = -1;
@@ -1559,11 +1567,54 @@ int wdbx_index_search_multivector(wdbx_index* ix, const float* vectors, const ui
   const bool reg = k <= 128 && !ix->opt_lds_lists;
   const multivector_rank_fn rfn = pick_multivector_rank(mp.select ? 2 : (reg ? 1 : 0));
   if (mp.lds >= 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)rfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mp.lds));
+  // the matrix-core scoring route (host_multivector_tiles.h), chosen round by round; what it needs once per call: the rows'
+  // cached norms, the vectors' norms and the zeroed counter of ambiguous pairs behind them
+  auto tile_plan = [&](const MultivectorRound& r) {
+    return multivector_tile_plan(ix->metric, r.vectors, (uint32_t)ix->pitch, ix->lab_spans, ix->cu_count);
+  };
+  auto tile_round = [&](const MultivectorRound& r) {
+    return multivector_tile_route(ix->opt_multivector_tiles, ix->opt_multivector_tiles_min_vectors, r.vectors, tile_plan(r));
+  };
+  const size_t amb_off = ((size_t)total * sizeof(float) + 7) / 8 * 8;
+  u64 ambiguous = 0;
+  int64_t tile_rounds = 0, tile_pairs = 0;
+  bool raised[5] = {false, false, false, false, false};  // (by vt: the LDS limit of an instance is raised once, not per round)
+  if (std::any_of(mp.rounds.begin(), mp.rounds.end(), tile_round)) {
+    if ((rc = ensure_row_norms(ix)) || (rc = ix->d_mv_norm.grow(amb_off + sizeof(u64)))) return rc;
+    HIP_TRY(hipMemsetAsync(ix->d_mv_norm + amb_off, 0, sizeof(u64), ix->stream));
+    hipLaunchKernelGGL(multivector_norms_kernel, dim3((uint32_t)((total + 3) / 4)), dim3(256), 0, ix->stream, (const float*)ix->d_q,
+                       (float*)ix->d_mv_norm.p, (uint32_t)ix->pitch, (uint32_t)total);
+    HIP_TRY(hipGetLastError());
+  }
   for (const MultivectorRound& r : mp.rounds) {
-    const uint32_t vblocks = (r.vectors + (uint32_t)mp.qb - 1) / (uint32_t)mp.qb;
-    const uint32_t sblocks = r.vectors == (uint32_t)mp.round_max ? mp.score_blocks
-                                                                 : multivector_score_blocks(r.vectors, mp.qb, ix->lab_spans, ix->cu_count);
-    if ((rc = launch_bracketed(ix, ix->scan_ev, kfn, dim3(sblocks, vblocks), 0, label_keys_args(ix, r.first, r.vectors, pitch4)))) return rc;
+    if (tile_round(r)) {
+      const MultivectorTilePlan tp = tile_plan(r);
+      const label_keys_tile_fn tfn = pick_label_keys_tile(tp.vt, pitch4);
+      if (!tfn) return fail(WDBX_E_STATE, "no label-keys tile instance with blocks of %u vectors", tp.block);
+      if (tp.lds >= 64 * 1024 && !raised[tp.vt]) {
+        HIP_TRY(hipFuncSetAttribute((const void*)tfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tp.lds));
+        raised[tp.vt] = true;
+      }
+      const AssignBound ab = assign_bound((uint32_t)ix->pitch);
+      LabelKeysTileArgs ta = {};
+      ta.k = label_keys_args(ix, r.first, r.vectors, pitch4);
+      ta.cn = ix->d_cn;
+      ta.vnorm = (const float*)ix->d_mv_norm.p + r.first;
+      ta.ambiguous = (u64*)(ix->d_mv_norm + amb_off);
+      ta.gamma = ab.gamma;
+      ta.under = ab.under;
+      if ((rc = record(ix->scan_ev, ix->profile, ix->stream, true))) return rc;
+      hipLaunchKernelGGL(tfn, dim3(tp.grid, tp.vblocks), dim3(256), tp.lds, ix->stream, ta);
+      HIP_TRY(hipGetLastError());
+      if ((rc = record(ix->scan_ev, ix->profile, ix->stream, false))) return rc;
+      ++tile_rounds;
+      tile_pairs += (int64_t)r.vectors * ix->lab_items;
+    } else {
+      const uint32_t vblocks = (r.vectors + (uint32_t)mp.qb - 1) / (uint32_t)mp.qb;
+      const uint32_t sblocks = r.vectors == (uint32_t)mp.round_max ? mp.score_blocks
+                                                                   : multivector_score_blocks(r.vectors, mp.qb, ix->lab_spans, ix->cu_count);
+      if ((rc = launch_bracketed(ix, ix->scan_ev, kfn, dim3(sblocks, vblocks), 0, label_keys_args(ix, r.first, r.vectors, pitch4)))) return rc;
+    }
     MultivectorRankArgs m = {};
     m.keys = ix->d_sub_keys;
     m.key_stride = ix->lab_items;
@@ -1590,7 +1641,11 @@ int wdbx_index_search_multivector(wdbx_index* ix, const float* vectors, const ui
     const RankSource src = label_rank_source(ix, mp.select, mp.keys_u64, mp.rank_blocks);
     if ((rc = enqueue_rank_tail(ix, src, (int)r.ranked_query0, (int)r.ranked, k, ix->metric))) return rc;
   }
+  if (tile_rounds) HIP_TRY(hipMemcpyAsync(&ambiguous, ix->d_mv_norm + amb_off, sizeof ambiguous, hipMemcpyDeviceToHost, ix->stream));
   if ((rc = download_results(ix, elems, out_idx, out_score))) return rc;
+  ix->last_multivector_tile_rounds = tile_rounds;
+  ix->last_multivector_ambiguous = (int64_t)ambiguous;
+  ix->last_multivector_pairs = tile_pairs;
   // label positions -> (smallest row of the label, its stored label)
   const uint64_t n_set = std::min<uint64_t>(ix->labels.size(), ix->n);
   for (size_t i = 0; i < elems; ++i) {
@@ -2897,6 +2952,8 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"rows_keys_max", &wdbx_index::opt_rows_keys_max},
     {"distinct_overfetch", &wdbx_index::opt_distinct_overfetch},
     {"multivector_round_vectors", &wdbx_index::opt_multivector_round_vectors},
+    {"multivector_tiles", &wdbx_index::opt_multivector_tiles},
+    {"multivector_tiles_min_vectors", &wdbx_index::opt_multivector_tiles_min_vectors},
     {"range_batch_min_queries", &wdbx_index::opt_range_batch_min_queries},
     {"range_pair_cap", &wdbx_index::opt_range_pair_cap},
     {"mmr_scratch_mib", &wdbx_index::opt_mmr_scratch_mib},
@@ -2914,6 +2971,10 @@ int wdbx_index_set_option(wdbx_index* ix, const char* name, int64_t value) try {
     return fail(WDBX_E_INVALID, "gemm8_variant %lld: 0 (= 14), 12 and 13 are the forms the library has", (long long)value);
   if (slot == &ix->opt_multivector_round_vectors && (value < 1 || value > MULTIVECTOR_MAX_ROUND))
     return fail(WDBX_E_INVALID, "multivector_round_vectors %lld outside [1, %d]", (long long)value, MULTIVECTOR_MAX_ROUND);
+  if (slot == &ix->opt_multivector_tiles && value != -1 && value != 0 && value != 1)
+    return fail(WDBX_E_INVALID, "multivector_tiles %lld: -1 (by the round's size), 0 or 1", (long long)value);
+  if (slot == &ix->opt_multivector_tiles_min_vectors && (value < 1 || value > MULTIVECTOR_MAX_ROUND))
+    return fail(WDBX_E_INVALID, "multivector_tiles_min_vectors %lld outside [1, %d]", (long long)value, MULTIVECTOR_MAX_ROUND);
   if (slot == &ix->opt_range_pair_cap && value != 0 && (value < (int64_t)RANGE_PAIR_CAP_MIN || value > (int64_t)RANGE_PAIR_CAP_MAX))
     return fail(WDBX_E_INVALID, "range_pair_cap %lld: 0 (the default sizing) or [%u, %u] pairs per wave", (long long)value,
                 RANGE_PAIR_CAP_MIN, RANGE_PAIR_CAP_MAX);
@@ -2993,6 +3054,9 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "last_multivector_rounds")) return *value = ix->last_multivector_rounds, WDBX_OK;
   if (name && !strcmp(name, "last_multivector_vectors")) return *value = ix->last_multivector_vectors, WDBX_OK;
   if (name && !strcmp(name, "last_multivector_labels")) return *value = ix->last_multivector_labels, WDBX_OK;
+  if (name && !strcmp(name, "last_multivector_tile_rounds")) return *value = ix->last_multivector_tile_rounds, WDBX_OK;
+  if (name && !strcmp(name, "last_multivector_ambiguous")) return *value = ix->last_multivector_ambiguous, WDBX_OK;
+  if (name && !strcmp(name, "last_multivector_pairs")) return *value = ix->last_multivector_pairs, WDBX_OK;
   if (name && !strcmp(name, "last_mmr_path")) return *value = ix->last_mmr_path, WDBX_OK;
   if (name && !strcmp(name, "last_recommend_path")) return *value = ix->last_recommend_path, WDBX_OK;
   if (name && !strcmp(name, "last_recommend_short")) return *value = ix->last_recommend_short, WDBX_OK;

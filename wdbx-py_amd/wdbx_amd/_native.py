@@ -554,7 +554,9 @@ class NativeIndex:
         labels are ranked by the sum over the query's vectors of each vector's best score among the label's rows (fp32,
         folded in vector order).  Returns ``(rows int64, scores f32, labels uint32)``, each ``[nq, k]``: a label's smallest
         row, its sum and its stored label; unused slots hold -1 / 0 / :data:`LABEL_NONE`.  ``mask_words`` as in
-        :meth:`search`."""
+        :meth:`search`.  Options ``multivector_tiles`` (-1 / 0 / 1) and ``multivector_tiles_min_vectors`` choose the scoring
+        route of a round (the same bits either way); ``last_multivector_tile_rounds``, ``last_multivector_pairs`` and
+        ``last_multivector_ambiguous`` say what the last call did."""
         v = _as_f32(vectors, self.dim)
         off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
         nq = off.size - 1

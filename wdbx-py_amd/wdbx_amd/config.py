@@ -10,7 +10,8 @@ fan-out + exchange + merge in ONE library call, a host thread per shard; "auto" 
 copies), True = also one shard per GPU (RCCL all-gather), "always" = also a single shard, False = off), ``HIP_AUTOSAVE_ROWS``
 (index files follow ingest every N adds, reference: 1000), ``HIP_PERSIST_INDEX``, ``HIP_COMPACT_MIN_FRACTION`` (``optimize()`` compacts removed rows away once they are this share of a shard; 0 = any), ``HIP_BF16_SHADOW`` / ``HIP_U8_SHADOW`` (keep a bf16 / u8 copy of the
 rows for the batched / single-query selection passes: +50 % / +25 % device memory,
-several times the query rate; results are the exact fp32 ranking either way), ``FILTER_PUSHDOWN`` (metadata filter before the scan),
+several times the query rate; results are the exact fp32 ranking either way), ``HIP_MULTIVECTOR_TILES`` (multi-vector search:
+None = the library's default route per round of query vectors, 0 / 1 / -1 = library option ``multivector_tiles``), ``FILTER_PUSHDOWN`` (metadata filter before the scan),
 ``ASYNC_COALESCE`` (concurrent ``search_async`` callers share one batched pass)."""
 
 from __future__ import annotations
@@ -71,6 +72,10 @@ class WDBXConfig:
         "HIP_SWALLOW_ERRORS": True,
         "HIP_BF16_SHADOW": True,
         "HIP_U8_SHADOW": True,
+        # multi-vector search: the scoring route of a round of query vectors (library option multivector_tiles): None = the
+        # library's default, 0 = the vector-ALU pass (8 vectors per row read), 1 = the matrix-core pass wherever it exists (up to
+        # 128 vectors per row read, inner product / cosine only), -1 = by the round's size.  The answers are the same bits.
+        "HIP_MULTIVECTOR_TILES": None,
         "HIP_GROUP_SEARCH": "auto",
         "HIP_AUTOSAVE_ROWS": 1000,
         "HIP_PERSIST_INDEX": True,

@@ -173,6 +173,9 @@ class HipFlatIndex(VectorIndex):
             self._native.set_option("gemm_bf16", 1)  # bf16 selection tiles on the fp32 rows
         if not bool(self.config.get("HIP_U8_SHADOW", True)):
             self._native.set_option("scan_shadow", 1)  # single queries on the bf16 tile path (or fp32 scans without it)
+        tiles = self.config.get("HIP_MULTIVECTOR_TILES")
+        if tiles is not None:  # (None: the library's default route per round of a multi-vector search)
+            self._native.set_option("multivector_tiles", int(tiles))
 
         self.id_to_index: Dict[str, int] = {}
         self.index_to_id: Dict[int, str] = {}
