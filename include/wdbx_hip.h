@@ -261,6 +261,53 @@ int wdbx_index_assign(wdbx_index* idx, const float* centers /* host [n_centers, 
                       int32_t* out_center /* [rows] or NULL */, float* out_score /* [rows] or NULL */,
                       float* out_sums /* [n_centers, dim] or NULL */, uint64_t* out_counts /* [n_centers] or NULL */);
 
+/* ---- device PCA: moments of the stored rows, and their projection ---- */
+/* The two corpus-sized passes of a principal component analysis (the reference's VectorVisualizer.reduce_dimensions(method="pca"),
+ * wdbx/utils/visualization.py:35-66, fed there by at most 1 000 vectors fetched one by one, visualization.py:487-505) with no
+ * stored vector leaving the device; the d x d eigenproblem between them is the caller's (numpy.linalg.eigh in the facade).
+ * Both calls are blocking, take host buffers, serve both metrics without looking at the metric (the arithmetic is on the rows
+ * as stored: cosine rows are the normalised rows) and hold the handle's mutex to their end.
+ *   COUNTED rows, the same for both calls: the rows the mask allows (mask_words / mask_word_count as
+ *   wdbx_index_search_masked_n, NULL / 0 = every row) whose cached squared norm is finite.  Removed rows are NaN rows and
+ *   drop out; so do rows with a NaN or infinite element (and rows whose squared norm overflows fp32).
+ * wdbx_index_moments: each of the three outputs may be null, not all of them.
+ *   out_count = the number of counted rows.
+ *   out_mean[i] = the fp32 mean of column i over the counted rows.  No floating-point atomics: the rows are cut into
+ *   consecutive ranges (get_option "last_moments_sum_partials" of them, "last_moments_sum_rows" rows each), a range's counted
+ *   rows are added in fp32 in row order, the ranges' sums are added in fp32 in range order, and one fp32 division by the count
+ *   (converted to fp32) follows.
+ *   out_scatter [dim, dim], float64: with center = 1 the sum over the counted rows of (x (-) mu)(x (-) mu)^T, where mu is
+ *   exactly the returned fp32 mean and (-) the fp32 subtraction done while a row is staged; with center = 0 the sum of
+ *   x x^T.  The rows are cut into P consecutive ranges of L rows ("last_moments_partials", "last_moments_range_rows", L a
+ *   multiple of 32); a range's partial is, per element, one fp32 fma chain over its rows in row order on
+ *   v_mfma_f32_32x32x2_f32 (uncounted rows enter as zeros); the P partials are folded in FLOAT64 in range order by one thread
+ *   per element of the upper triangle, which writes [i][j] and [j][i]: the matrix is symmetric bit for bit and identical from
+ *   run to run, its bits depend on P only, and P on (rows, dim, CU count) only.  The upper triangle of 32 x 32 tiles is cut
+ *   into tile groups ("last_moments_tile_groups"), one workgroup per (range, group).  "last_moments_launches": kernel
+ *   launches of the last call.
+ *   set_option, for tests and measurements: "moments_tiles_per_group" = blocks per side of a tile group (0 = the plan's
+ *   choice: the whole triangle up to 12 blocks a side, else 8; larger values are cut to that), "moments_partials" = the
+ *   number of ranges of both passes (0 = the plan's choice; cut to what the rows and 256 MiB of partials allow).
+ *   An empty index or nothing counted: WDBX_OK, count 0, zeros, no scatter launch.
+ *   WDBX_E_INVALID: center not 0 or 1, all three outputs null, out_scatter with dim > 4096, a mask shorter than
+ *   ceil(rows / 32) words (checked under the handle's lock).  A refused call leaves the handle usable.
+ * wdbx_index_project: out[r][c] = sum_i (x_r[i] (-) offset[i]) * basis[c][i], one fp32 fma chain in ascending i on
+ *   v_mfma_f32_32x32x2_f32 (columns past dim, up to the next multiple of 32, enter as zeros); a row that is not counted
+ *   gets zeros in its m slots.  offset NULL = zeros.
+ *   WDBX_E_INVALID: m outside [1, WDBX_MAX_COMPONENTS] (more components, in blocks of 32 as assign's centre blocks, are left
+ *   for later), basis null, out null, a mask shorter than ceil(rows / 32) words.  An empty index is WDBX_OK and writes nothing.
+ *   out must hold m entries per row the index holds WHEN THE CALL RUNS (the count is read under the handle's lock and is not
+ *   passed in): a caller sizes it from wdbx_index_size and keeps every wdbx_index_add / wdbx_index_fill_synthetic on this
+ *   handle out until the call has returned.
+ * Nothing of either call stays valid in the handle. */
+int wdbx_index_moments(wdbx_index* idx, int center, const uint32_t* mask_words, uint64_t mask_word_count,
+                       float* out_mean /* [dim] or NULL */, double* out_scatter /* [dim, dim] or NULL */,
+                       uint64_t* out_count /* or NULL */);
+#define WDBX_MAX_COMPONENTS 32
+int wdbx_index_project(wdbx_index* idx, const float* basis /* host [m, dim] */, int m,
+                       const float* offset /* host [dim] or NULL = zeros */, const uint32_t* mask_words,
+                       uint64_t mask_word_count, float* out /* [rows, m] */);
+
 /* ---- search among listed rows, one row list PER QUERY in one batched call ------ */
 /* What wdbx_index_search_rows answers for one list, for a batch whose queries each name their own list (a rerank stage's
  * candidates, a selective filter per tenant): query i is ranked among the rows of list query_list[i].  The lists come back to

@@ -238,6 +238,17 @@ struct wdbx_index {
   DevBuf<char> d_asg_part{&bufs};
   DevBuf<char> d_asg_out{&bufs};
   int64_t last_assign_ambiguous = 0, last_assign_launches = 0, last_assign_center_blocks = 0, last_assign_partials = 0;
+  // device PCA (wdbx_index_moments / wdbx_index_project, host_pca.h): the mean (padded dimension) followed by the count; the
+  // column sums' partials; the scatter pass's partials; the scatter matrix before its download; the call's basis followed by
+  // its offset; every row's coordinates.  What the last moments call did.
+  DevBuf<char> d_pca_mean{&bufs};
+  DevBuf<char> d_pca_sums{&bufs};
+  DevBuf<char> d_pca_part{&bufs};
+  DevBuf<double> d_pca_out{&bufs};
+  DevBuf<float> d_pca_basis{&bufs};
+  DevBuf<float> d_pca_proj{&bufs};
+  int64_t last_moments_partials = 0, last_moments_tile_groups = 0, last_moments_launches = 0, last_moments_range_rows = 0,
+          last_moments_sum_partials = 0, last_moments_sum_rows = 0;
   // profiling
   bool profile = false;
   EventPool scan_ev, merge_ev, gemm_ev, sample_ev;
@@ -250,7 +261,8 @@ struct wdbx_index {
           opt_merge_fast = 1, opt_poll_done = 1, opt_scan_one_grid = 1, opt_select_min_k = 200, opt_gemm_min_nq = 4, opt_gemm_min_rows = 65536, opt_gemm_min_work = 800000,
           opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0, opt_scan_u42 = -1, opt_scan_u42_share = -1, opt_scan_u42_mfma = -1, opt_gemm_masked = 1, opt_rows_keys_max = 8192, opt_distinct_overfetch = 4,
           opt_multivector_round_vectors = 256, opt_multivector_tiles = -1, opt_multivector_tiles_min_vectors = 24, opt_range_batch_min_queries = 4, opt_range_pair_cap = 0,
-          opt_mmr_scratch_mib = MMR_SCRATCH_MIB_MAX, opt_groups_segment_rows = GROUPS_SEGMENT_DEFAULT;
+          opt_mmr_scratch_mib = MMR_SCRATCH_MIB_MAX, opt_groups_segment_rows = GROUPS_SEGMENT_DEFAULT,
+          opt_moments_tiles_per_group = 0, opt_moments_partials = 0;
 };
 
 struct DeviceGuard {

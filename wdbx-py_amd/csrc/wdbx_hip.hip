@@ -44,6 +44,10 @@
 //                           row against a few given vectors on the fp32 matrix cores, a top-1 per row folded in registers; the exact
 //                           pass over the rows the tile pass cannot vouch for, the winner's exact score, per-centre sums
 //   host_assign.h           that call's argument checks, centre blocks, LDS, grids, partial sums and the certainty bound's coefficients
+//   kernels_pca.h           scatter_tile_kernel, project_tile_kernel: device PCA (wdbx_index_moments / wdbx_index_project) -- the
+//                           centred scatter matrix as a split-K SYRK over the stored rows on the fp32 matrix cores, column sums
+//                           and the float64 combination around it, every row's coordinates on up to 32 directions
+//   host_pca.h              those calls' argument checks, tile groups, LDS, row ranges, partials and grids
 //   kernels_rowlists.h      rowlists_kernel: the same scores for a call with one row list PER QUERY (wdbx_index_search_row_lists),
 //                           one workgroup per (chunk of a list, block of its queries) work item of host_rowlists.h
 //   kernels_labels.h        label_keys_kernel, label_rank_kernel: the full pass of wdbx_index_search_distinct (at most one row per
@@ -122,6 +126,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_subset.h"  // (device-free as well: row-list validation, route and grid sizing of a search among listed rows)
 #include "host_matrix.h"  // (device-free as well: route, anchor block, instance and rounds of a distance matrix among listed rows)
 #include "host_assign.h"  // (device-free as well: argument checks, centre blocks, LDS, grids, partials and bound of an assignment)
+#include "host_pca.h"  // (device-free as well: argument checks, tile groups, LDS, ranges, partials and grids of the moments and the projection)
 #include "host_multimask.h"  // (device-free as well: where the queries of a call with a mask per query sit in the tile blocks)
 #include "host_selection.h"  // (device-free as well: the sample, stride and capacities of the selection rounds)
 #include "host_scan_plan.h"  // (device-free as well: the fp32 scan and range forms of a pitch, grid / list / chunk / LDS numbers of a scan)
@@ -170,6 +175,8 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "kernels_matrix.h"
 #include "kernels_assign.h"
 static_assert(ASSIGN_MAX_CENTERS == WDBX_MAX_CENTERS, "the plan's limit is the header's");
+#include "kernels_pca.h"
+static_assert(PCA_MAX_COMPONENTS == WDBX_MAX_COMPONENTS, "the plan's limit is the header's");
 #include "kernels_rowlists.h"
 #include "kernels_labels.h"
 static_assert(LABEL_SPAN_DEV == LABEL_SPAN, "the kernels walk the spans the host built");
@@ -1055,6 +1062,154 @@ int wdbx_index_assign(wdbx_index* ix, const float* centers, int n_centers, int n
   HIP_TRY(hipStreamSynchronize(ix->stream));
   // (partials of a call with many centres -- up to ASSIGN_PARTIALS_BUDGET -- do not stay on the handle; small ones are kept for the next iteration)
   if (ix->d_asg_part.bytes > ASSIGN_PARTIALS_KEEP) return ix->d_asg_part.release();
+  return WDBX_OK;
+} WDBX_CATCH
+
+// ---- device PCA: moments of the stored rows and their projection (kernels_pca.h, host_pca.h) ---
+// The whole call holds the handle's mutex.  Under it: the mask's length is checked, the row norms are brought up to date, the
+// column sums go range by range and are folded into the mean and the count (two merge launches), the count comes back; with
+// rows counted and a scatter matrix asked for, the tile pass writes one partial per range (a gemm launch of 512-thread
+// workgroups, its bracket written out) and the combination folds them in float64 (a merge launch); one download.
+int wdbx_index_moments(wdbx_index* ix, int center, const uint32_t* mask_words, uint64_t mask_word_count, float* out_mean,
+                       double* out_scatter, uint64_t* out_count) try {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  switch (moments_validate(center, out_mean || out_scatter || out_count, out_scatter != nullptr, ix->dim)) {
+    case PCA_OK: break;
+    case PCA_BAD_CENTER: return fail(WDBX_E_INVALID, "center=%d: 0 or 1", center);
+    case PCA_DIM_TOO_LARGE: return fail(WDBX_E_INVALID, "a scatter matrix of dimension %d: at most %d is served", ix->dim, PCA_MAX_DIM);
+    default: return fail(WDBX_E_INVALID, "every output is null");
+  }
+  std::unique_lock<std::mutex> lk(ix->mu);
+  const size_t dim = (size_t)ix->dim;
+  ix->last_moments_partials = ix->last_moments_tile_groups = ix->last_moments_launches = ix->last_moments_range_rows = 0;
+  ix->last_moments_sum_partials = ix->last_moments_sum_rows = 0;
+  auto zeros = [&]() {
+    if (out_mean) std::fill(out_mean, out_mean + dim, 0.f);
+    if (out_scatter) std::fill(out_scatter, out_scatter + dim * dim, 0.0);
+    if (out_count) *out_count = 0;
+  };
+  if (!ix->n) return zeros(), WDBX_OK;  // (nothing stored: nothing counted, nothing launched)
+  int rc;
+  if (mask_words && (rc = check_mask_words(ix->n, mask_word_count))) return rc;
+  DeviceGuard g(ix->device);
+  MaskScope scope(ix);
+  if (mask_words && (rc = scope.set(mask_words))) return rc;
+  const PcaPlan pp = pca_plan(ix->n, ix->dim, (uint32_t)ix->pitch, ix->cu_count, (int)ix->opt_moments_tiles_per_group,
+                              ix->opt_moments_partials, out_scatter != nullptr);
+  const size_t mean_bytes = (size_t)pp.dp * sizeof(float);
+  if ((rc = ensure_row_norms(ix)) || (rc = ix->d_pca_mean.grow(mean_bytes + sizeof(u64))) || (rc = ix->d_pca_sums.grow(pp.sum_bytes)))
+    return rc;
+  const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
+  MomentsSumArgs sa = {};
+  sa.rows = (const f4*)ix->d_rows.p;
+  sa.cn = ix->d_cn;
+  sa.mask = ix->active_mask;
+  sa.partial = (f4*)ix->d_pca_sums.p;
+  sa.partial_count = (uint32_t*)(ix->d_pca_sums + (size_t)pp.sum_ranges * ix->pitch * sizeof(float));
+  sa.mean = (float*)ix->d_pca_mean.p;
+  sa.count = (u64*)(ix->d_pca_mean + mean_bytes);
+  sa.n_rows = (uint32_t)ix->n;
+  sa.pitch4 = pitch4;
+  sa.dim = (uint32_t)ix->dim;
+  sa.mean_len = (uint32_t)pp.dp;
+  sa.ranges = pp.sum_ranges;
+  sa.rows_per_range = pp.sum_rows;
+  if ((rc = launch_bracketed(ix, ix->merge_ev, moments_sum_kernel, dim3(pp.sum_grid), 0, sa)) ||
+      (rc = launch_bracketed(ix, ix->merge_ev, moments_mean_kernel, dim3((uint32_t)(pp.dp + 255) / 256), 0, sa)))
+    return rc;
+  u64 count = 0;
+  HIP_TRY(hipMemcpyAsync(&count, sa.count, sizeof count, hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  ix->last_moments_launches = 2;
+  ix->last_moments_sum_partials = pp.sum_ranges;
+  ix->last_moments_sum_rows = (int64_t)pp.sum_rows;
+  if (!count) return zeros(), WDBX_OK;  // (nothing counted: no scatter launch)
+  // (the mean leaves before a center = 0 call clears the device copy the staging subtracts)
+  if (out_mean) HIP_TRY(hipMemcpyAsync(out_mean, ix->d_pca_mean, dim * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+  if (out_scatter) {
+    const scatter_tile_fn tile = pick_scatter_tile(pp.instance);
+    if (!tile || pp.lds > PCA_LDS_LIMIT || pp.wave_tiles > pp.instance || pp.staged > (pp.instance <= 8 ? 16 : 12))
+      return fail(WDBX_E_STATE, "no scatter tile instance for %d tiles a wave and %d staged blocks", pp.wave_tiles, pp.staged);
+    if ((rc = ix->d_pca_part.grow(pp.partial_bytes)) || (rc = ix->d_pca_out.grow(dim * dim * sizeof(double)))) return rc;
+    if (!center) HIP_TRY(hipMemsetAsync(ix->d_pca_mean, 0, mean_bytes, ix->stream));  // (what the staging subtracts: nothing)
+    ScatterArgs ta = {};
+    ta.rows = sa.rows;
+    ta.cn = sa.cn;
+    ta.mask = sa.mask;
+    ta.mean = (const f4*)ix->d_pca_mean.p;
+    ta.partial = (float*)ix->d_pca_part.p;
+    ta.out = ix->d_pca_out;
+    ta.n_rows = sa.n_rows;
+    ta.pitch4 = pitch4;
+    ta.dim = sa.dim;
+    ta.dp = (uint32_t)pp.dp;
+    ta.nb = (uint32_t)pp.nb;
+    ta.side = (uint32_t)pp.side;
+    ta.ranges = pp.ranges;
+    ta.rows_per_range = pp.range_rows;
+    if (pp.lds >= 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)tile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp.lds));
+    if ((rc = record(ix->gemm_ev, ix->profile, ix->stream, true))) return rc;
+    hipLaunchKernelGGL(tile, dim3(pp.ranges, (uint32_t)pp.groups), dim3(64 * PCA_WAVES), pp.lds, ix->stream, ta);
+    HIP_TRY(hipGetLastError());
+    if ((rc = record(ix->gemm_ev, ix->profile, ix->stream, false))) return rc;
+    const uint32_t cgrid = (uint32_t)std::min<size_t>((dim * dim + 255) / 256, 4096);
+    if ((rc = launch_bracketed(ix, ix->merge_ev, scatter_combine_kernel, dim3(cgrid), 0, ta))) return rc;
+    ix->last_moments_launches = 4;
+    ix->last_moments_partials = pp.ranges;
+    ix->last_moments_tile_groups = pp.groups;
+    ix->last_moments_range_rows = (int64_t)pp.range_rows;
+    HIP_TRY(hipMemcpyAsync(out_scatter, ix->d_pca_out, dim * dim * sizeof(double), hipMemcpyDeviceToHost, ix->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  if (out_count) *out_count = count;
+  if (ix->d_pca_part.bytes > PCA_PARTIALS_KEEP) return ix->d_pca_part.release();
+  return WDBX_OK;
+} WDBX_CATCH
+
+// The whole call holds the handle's mutex.  Under it: the mask's length is checked, the row norms are brought up to date, the
+// basis (zero-filled to 32 vectors of the padded dimension) and the offset go to the device once, one tile pass (a gemm
+// launch) writes every row's coordinates, one download.
+int wdbx_index_project(wdbx_index* ix, const float* basis, int m, const float* offset, const uint32_t* mask_words,
+                       uint64_t mask_word_count, float* out) try {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  switch (project_validate(m, basis != nullptr, out != nullptr)) {
+    case PCA_OK: break;
+    case PCA_BAD_COMPONENTS: return fail(WDBX_E_INVALID, "m=%d outside [1, %d]", m, WDBX_MAX_COMPONENTS);
+    case PCA_NULL_BASIS: return fail(WDBX_E_INVALID, "basis is null");
+    default: return fail(WDBX_E_INVALID, "out is null");
+  }
+  std::unique_lock<std::mutex> lk(ix->mu);
+  if (!ix->n) return WDBX_OK;
+  int rc;
+  if (mask_words && (rc = check_mask_words(ix->n, mask_word_count))) return rc;
+  DeviceGuard g(ix->device);
+  MaskScope scope(ix);
+  if (mask_words && (rc = scope.set(mask_words))) return rc;
+  const size_t dp = (size_t)32 * pca_blocks(ix->dim), dim = (size_t)ix->dim;
+  const size_t basis_floats = 33 * dp, out_floats = (size_t)ix->n * m;  // 32 basis slots, then the offset
+  if ((rc = ensure_row_norms(ix)) || (rc = ix->d_pca_basis.grow(basis_floats * sizeof(float))) ||
+      (rc = ix->d_pca_proj.grow(out_floats * sizeof(float))))
+    return rc;
+  HIP_TRY(hipMemsetAsync(ix->d_pca_basis, 0, basis_floats * sizeof(float), ix->stream));
+  HIP_TRY(hipMemcpy2DAsync(ix->d_pca_basis, dp * sizeof(float), basis, dim * sizeof(float), dim * sizeof(float), (size_t)m,
+                           hipMemcpyHostToDevice, ix->stream));
+  if (offset) HIP_TRY(hipMemcpyAsync(ix->d_pca_basis + 32 * dp, offset, dim * sizeof(float), hipMemcpyHostToDevice, ix->stream));
+  ProjectArgs pa = {};
+  pa.rows = (const f4*)ix->d_rows.p;
+  pa.cn = ix->d_cn;
+  pa.mask = ix->active_mask;
+  pa.basis = (const f4*)ix->d_pca_basis.p;
+  pa.offset = (const f4*)(ix->d_pca_basis + 32 * dp);
+  pa.out = ix->d_pca_proj;
+  pa.n_rows = (uint32_t)ix->n;
+  pa.pitch4 = (uint32_t)ix->pitch / 4;
+  pa.kq = (uint32_t)(dp / 4);
+  pa.m = (uint32_t)m;
+  pa.num_tiles = (uint32_t)((ix->n + PCA_PROJECT_TILE_ROWS - 1) / PCA_PROJECT_TILE_ROWS);
+  if ((rc = launch_bracketed(ix, ix->gemm_ev, project_tile_kernel, dim3(project_grid(ix->n, ix->cu_count)), project_lds_bytes(), pa)))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(out, ix->d_pca_proj, out_floats * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
   return WDBX_OK;
 } WDBX_CATCH
 
@@ -2958,6 +3113,8 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"range_pair_cap", &wdbx_index::opt_range_pair_cap},
     {"mmr_scratch_mib", &wdbx_index::opt_mmr_scratch_mib},
     {"groups_segment_rows", &wdbx_index::opt_groups_segment_rows},
+    {"moments_tiles_per_group", &wdbx_index::opt_moments_tiles_per_group},
+    {"moments_partials", &wdbx_index::opt_moments_partials},
 };
 
 static int64_t* option_slot(wdbx_index* ix, const char* name) { return find_option(ix, kOptions, name); }
@@ -2983,6 +3140,8 @@ int wdbx_index_set_option(wdbx_index* ix, const char* name, int64_t value) try {
   if (slot == &ix->opt_groups_segment_rows && (value < GROUPS_SEGMENT_MIN || value > GROUPS_SEGMENT_MAX))
     return fail(WDBX_E_INVALID, "groups_segment_rows %lld outside [%lld, %lld]", (long long)value, (long long)GROUPS_SEGMENT_MIN,
                 (long long)GROUPS_SEGMENT_MAX);
+  if ((slot == &ix->opt_moments_tiles_per_group || slot == &ix->opt_moments_partials) && (value < 0 || value > (1 << 20)))
+    return fail(WDBX_E_INVALID, "%s %lld: 0 (the plan's choice) or a positive count", name, (long long)value);
   if (slot == &ix->opt_scan_u42_share && value != -1 && value != 1 && value != 2 && value != 4)
     return fail(WDBX_E_INVALID, "scan_u42_share %lld: -1 (the default), 1, 2 or 4 queries per read", (long long)value);
   if (slot == &ix->opt_scan_u42_mfma && value != -1 && value != 0 && value != 1)
@@ -3043,6 +3202,12 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "last_assign_launches")) return *value = ix->last_assign_launches, WDBX_OK;
   if (name && !strcmp(name, "last_assign_center_blocks")) return *value = ix->last_assign_center_blocks, WDBX_OK;
   if (name && !strcmp(name, "last_assign_partials")) return *value = ix->last_assign_partials, WDBX_OK;
+  if (name && !strcmp(name, "last_moments_partials")) return *value = ix->last_moments_partials, WDBX_OK;
+  if (name && !strcmp(name, "last_moments_tile_groups")) return *value = ix->last_moments_tile_groups, WDBX_OK;
+  if (name && !strcmp(name, "last_moments_launches")) return *value = ix->last_moments_launches, WDBX_OK;
+  if (name && !strcmp(name, "last_moments_range_rows")) return *value = ix->last_moments_range_rows, WDBX_OK;
+  if (name && !strcmp(name, "last_moments_sum_partials")) return *value = ix->last_moments_sum_partials, WDBX_OK;
+  if (name && !strcmp(name, "last_moments_sum_rows")) return *value = ix->last_moments_sum_rows, WDBX_OK;
   if (name && !strcmp(name, "last_update_launches")) return *value = ix->last_update_launches, WDBX_OK;
   if (name && !strcmp(name, "last_lists_path")) return *value = ix->last_lists_path, WDBX_OK;
   if (name && !strcmp(name, "last_lists_items")) return *value = ix->last_lists_items, WDBX_OK;

@@ -22,6 +22,7 @@ MAX_EXCLUDE_ROWS = 1024  # WDBX_MAX_EXCLUDE_ROWS
 MAX_CONTEXT_PAIRS = 32   # WDBX_MAX_CONTEXT_PAIRS: (positive, negative) pairs of one discovery query
 MAX_GROUP_SIZE = 64      # WDBX_MAX_GROUP_SIZE: members one group of wdbx_index_search_groups holds
 MAX_CENTERS = 4096       # WDBX_MAX_CENTERS: centres of one wdbx_index_assign call
+MAX_COMPONENTS = 32      # WDBX_MAX_COMPONENTS: basis vectors of one wdbx_index_project call
 UNIQUE_ID_BYTES = 128
 
 _LIB_NAME = "libwdbx_hip.so"
@@ -76,6 +77,8 @@ SIGNATURES = {
     "wdbx_index_search_matrix": (C.c_int, [C.c_void_p, _u64p, C.c_uint64, C.c_int, _i64p, _f32p]),
     "wdbx_index_assign": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
                                     C.POINTER(C.c_int32), _f32p, _f32p, _u64p]),
+    "wdbx_index_moments": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64, _f32p, _dblp, _u64p]),
+    "wdbx_index_project": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.POINTER(C.c_uint32), C.c_uint64, _f32p]),
     "wdbx_index_search_row_lists": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _u64p, _u64p, C.c_int,
                                               C.POINTER(C.c_int32), _i64p, _f32p]),
     "wdbx_index_set_labels": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]),
@@ -442,6 +445,48 @@ class NativeIndex:
                                            None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint32)),
                                            0 if m is None else m.size, ptr("center", C.c_int32), ptr("score", C.c_float),
                                            ptr("sums", C.c_float), ptr("counts", C.c_uint64)))
+        return out
+
+    def moments(self, center: bool = True, mask=None, want=("mean", "scatter")) -> dict:
+        """Moments of the COUNTED rows (``wdbx_index_moments``: the rows ``mask`` allows whose norm is finite): ``"count"``
+        always, ``"mean"`` (f32 ``[dim]``) and ``"scatter"`` (f64 ``[dim, dim]``: the sum of ``(x - mean)(x - mean)^T`` with
+        ``center``, of ``x x^T`` without; symmetric bit for bit) as ``want`` names them.  No stored vector leaves the device."""
+        unknown = set(want) - {"mean", "scatter", "count"}
+        if unknown:
+            raise ValueError(f"unknown moments outputs {sorted(unknown)}")
+        mean = np.zeros(self.dim, np.float32) if "mean" in want else None
+        scatter = np.zeros((self.dim, self.dim), np.float64) if "scatter" in want else None
+        count = C.c_uint64(0)
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint32)
+        # (the outputs and the mask's length are checked by the library, the length under the handle's lock)
+        _check(self._lib.wdbx_index_moments(self._h, int(center),
+                                            None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                            0 if m is None else m.size,
+                                            None if mean is None else mean.ctypes.data_as(_f32p),
+                                            None if scatter is None else scatter.ctypes.data_as(_dblp), C.byref(count)))
+        out = {"count": int(count.value)}
+        if mean is not None:
+            out["mean"] = mean
+        if scatter is not None:
+            out["scatter"] = scatter
+        return out
+
+    def project(self, basis, offset=None, mask=None) -> np.ndarray:
+        """Every stored row's coordinates ``(x - offset) . basis[c]`` (``wdbx_index_project``): ``basis`` is ``[m, dim]``,
+        ``m <= MAX_COMPONENTS``; a row that is not counted (:meth:`moments`) gets zeros.  Returns f32 ``[rows, m]``, sized here
+        from :meth:`size` while the library writes ``m`` entries per row it holds WHEN IT RUNS: the caller keeps rows from
+        being added between the two (``HipFlatIndex.project`` holds its ingest lock around this call)."""
+        b = _as_f32(basis, self.dim) if np.size(basis) else np.empty((0, self.dim), np.float32)
+        o = None if offset is None else np.ascontiguousarray(offset, dtype=np.float32).reshape(-1)
+        if o is not None and o.size != self.dim:
+            raise ValueError(f"offset has {o.size} entries for dimension {self.dim}")
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint32)
+        out = np.zeros((self.size(), b.shape[0]), np.float32)
+        # (the component count and the mask's length are checked by the library, the length under the handle's lock)
+        _check(self._lib.wdbx_index_project(self._h, b.ctypes.data_as(_f32p), b.shape[0],
+                                            None if o is None else o.ctypes.data_as(_f32p),
+                                            None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                            0 if m is None else m.size, out.ctypes.data_as(_f32p)))
         return out
 
     def search_row_lists(self, queries, k: int, lists, query_list,

@@ -865,6 +865,50 @@ class HipFlatIndex(VectorIndex):
                 return None
             raise
 
+    # ---- device PCA (extension: moments of the stored rows and their projection, no stored vector leaves the device) ----
+    def moments(self, mask: Optional[np.ndarray] = None, center: bool = True) -> Optional[dict]:
+        """``{"count", "mean", "scatter"}`` of the rows that ``mask`` (as ``row_mask_for`` returns it) allows and that are
+        neither removed nor hold a NaN or infinite element: one library call (``wdbx_index_moments``).  ``scatter`` is the
+        float64 sum of ``(x - mean)(x - mean)^T`` (``center=False``: of ``x x^T``) over the rows as stored.  None for an
+        empty index; errors are swallowed (None) or raised as in ``search``."""
+        try:
+            if self.next_index == 0:
+                return None
+            with self._ingest_lock:
+                return self._native.moments(center=center, mask=mask)
+        except Exception as e:
+            logger.error("Error computing moments of HIP index: %s", e)
+            if self.swallow_errors:
+                return None
+            raise
+
+    def project(self, basis: np.ndarray, offset: Optional[np.ndarray] = None,
+                mask: Optional[np.ndarray] = None) -> Optional[dict]:
+        """For every row that still has an id (and that ``mask`` allows) its coordinates ``(x - offset) . basis[c]`` on the
+        ``m <= 32`` directions ``basis`` ``[m, dim]``: one library call (``wdbx_index_project``).  Returns ``{"ids", "rows",
+        "coords": f32[len(ids), m]}`` in row order.  The output is sized by the row count, which the library reads again under
+        its own lock: the call holds ``_ingest_lock`` around sizing, the call and the id mapping, as ``assign`` does.  None for
+        an empty index; errors are swallowed (None) or raised as in ``search``."""
+        try:
+            b = np.asarray(basis, dtype=np.float32)
+            if b.ndim != 2 or b.shape[1] != self.vector_dim:
+                raise ValueError(f"Vector dimension mismatch: expected {self.vector_dim}, got {b.shape}")
+            if self.next_index == 0:
+                return None
+            with self._ingest_lock:
+                coords = self._native.project(np.ascontiguousarray(b), offset=offset, mask=mask)
+                # (a removed row has no id; a masked-out row is not asked for: both hold zeros and are left out)
+                words = None if mask is None else np.asarray(mask, dtype=np.uint32)
+                pairs = sorted((row, vid) for row, vid in self.mapped_rows() if row < coords.shape[0] and (
+                    words is None or (row < 32 * words.size and (int(words[row >> 5]) >> (row & 31)) & 1)))
+            rows = np.array([r for r, _ in pairs], dtype=np.int64)
+            return {"ids": [vid for _, vid in pairs], "rows": rows, "coords": coords[rows]}
+        except Exception as e:
+            logger.error("Error projecting rows of HIP index: %s", e)
+            if self.swallow_errors:
+                return None
+            raise
+
     # ---- the same with one list PER QUERY (wdbx_index_search_row_lists: one call for the whole batch) ----
     supports_row_lists = True
 

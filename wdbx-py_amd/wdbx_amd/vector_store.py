@@ -1544,6 +1544,91 @@ class VectorStore:
         return await loop.run_in_executor(self.thread_pool, lambda: self.cluster(
             k, max_iter=max_iter, tol=tol, seed=seed, filter_metadata=filter_metadata))
 
+    # ---- PCA (extension: principal components of the stored vectors and their coordinates, computed on the device) ----
+    @staticmethod
+    def merge_moments(parts) -> Tuple[int, np.ndarray, np.ndarray]:
+        """Per-shard ``(count, mean, centred scatter)`` to the whole set's, in float64 in shard order, by the pairwise update
+        ``S = S_a + S_b + (n_a n_b / n) dd^T``, ``d = mean_b - mean_a``; a shard that counted nothing is skipped."""
+        n, mean, scatter = 0, None, None
+        for nb, mb, sb in parts:
+            if not nb:
+                continue
+            mb, sb = np.asarray(mb, np.float64), np.asarray(sb, np.float64)
+            if not n:
+                n, mean, scatter = int(nb), mb.copy(), sb.copy()
+                continue
+            delta, total = mb - mean, n + int(nb)
+            scatter = scatter + sb + (n * int(nb) / total) * np.outer(delta, delta)
+            mean = mean + delta * (int(nb) / total)
+            n = total
+        return n, mean, scatter
+
+    def _shard_map(self, one, masks) -> list:
+        work = list(zip(self.indices, masks))
+        return list(self._shard_pool.map(one, work)) if len(work) > 1 else [one(work[0])]
+
+    def pca(self, n_components: int, filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        """Principal components of the stored vectors (with ``filter_metadata``: of those it matches), as stored.  Every
+        shard returns its count, fp32 mean and float64 centred scatter matrix from one library call (``wdbx_index_moments``:
+        the scatter on the matrix cores, no stored vector leaves its device); the shards' moments are merged in float64 in
+        shard order (``merge_moments``), ``numpy.linalg.eigh`` decomposes ``S / (n - 1)``, the components come in descending
+        variance, each signed so that its largest-magnitude entry is positive.  Returns ``{"mean" f64[d], "components"
+        f64[m, d], "explained_variance", "explained_variance_ratio", "count"}``; with fewer than two vectors counted, count
+        and empty arrays."""
+        d = self.vector_dim
+        if isinstance(n_components, bool) or not isinstance(n_components, int) or not 1 <= n_components <= d:
+            raise ValueError(f"n_components must be an integer between 1 and {d}")
+        masks = self._row_masks(filter_metadata) if filter_metadata else [None] * len(self.indices)
+        self.last_search_path = "threads"
+        got = self._shard_map(lambda a: a[0].moments(mask=a[1], center=True), masks)
+        n, mean, scatter = self.merge_moments([(r["count"], r["mean"], r["scatter"]) for r in got if r])
+        if n < 2:
+            return {"mean": np.zeros(d) if mean is None else mean, "components": np.zeros((0, d)),
+                    "explained_variance": np.zeros(0), "explained_variance_ratio": np.zeros(0), "count": n}
+        values, vectors = np.linalg.eigh(scatter / (n - 1))
+        order = np.argsort(values)[::-1][:n_components]
+        components = vectors[:, order].T.copy()
+        lead = components[np.arange(len(order)), np.argmax(np.abs(components), axis=1)]
+        components[lead < 0] *= -1.0
+        variance = values[order]
+        total = float(np.sum(values))
+        return {"mean": mean, "components": components, "explained_variance": variance,
+                "explained_variance_ratio": variance / total if total > 0 else np.zeros_like(variance), "count": n}
+
+    async def pca_async(self, n_components: int, filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(self.thread_pool, lambda: self.pca(n_components, filter_metadata=filter_metadata))
+
+    def reduce(self, n_components: int = 2, filter_metadata: Optional[Dict[str, Any]] = None, components=None,
+               mean=None) -> Dict[str, List[float]]:
+        """``{id: [m floats]}``: the coordinates of every stored vector (with ``filter_metadata``: of every vector it matches)
+        on ``components`` ``[m, dim]`` after subtracting ``mean`` -- fitted first by ``pca(n_components)`` over the same
+        vectors when no basis is given.  One ``wdbx_index_project`` per shard with the GLOBAL mean as the offset; at most 32
+        components.  A layout of the whole (filtered) corpus, not of a sample."""
+        if components is None:
+            fit = self.pca(n_components, filter_metadata=filter_metadata)
+            if not len(fit["components"]):
+                return {}
+            components, mean = fit["components"], fit["mean"]
+        basis = np.ascontiguousarray(components, dtype=np.float32)
+        if basis.ndim != 2 or basis.shape[1] != self.vector_dim or not 1 <= basis.shape[0] <= _native.MAX_COMPONENTS:
+            raise ValueError(f"components {basis.shape}: between 1 and {_native.MAX_COMPONENTS} vectors of dimension "
+                             f"{self.vector_dim} are served")
+        offset = None if mean is None else np.ascontiguousarray(mean, dtype=np.float32)
+        masks = self._row_masks(filter_metadata) if filter_metadata else [None] * len(self.indices)
+        self.last_search_path = "threads"
+        out: Dict[str, List[float]] = {}
+        for res in self._shard_map(lambda a: a[0].project(basis, offset=offset, mask=a[1]), masks):
+            if res:
+                out.update(zip(res["ids"], res["coords"].tolist()))
+        return out
+
+    async def reduce_async(self, n_components: int = 2, filter_metadata: Optional[Dict[str, Any]] = None, components=None,
+                           mean=None) -> Dict[str, List[float]]:
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(self.thread_pool, lambda: self.reduce(
+            n_components, filter_metadata=filter_metadata, components=components, mean=mean))
+
     # ---- range search (extension: every vector within a similarity, no limit) ----
     def search_range(self, query_vector: List[float], threshold: float,
                      filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,

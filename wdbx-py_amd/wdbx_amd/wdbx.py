@@ -326,6 +326,28 @@ class WDBX:
                                    filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
         return await self.vector_store.cluster_async(k, max_iter=max_iter, tol=tol, seed=seed, filter_metadata=filter_metadata)
 
+    def vector_pca(self, n_components: int, filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        """Extension: principal components of the stored vectors (with ``filter_metadata``: of those it matches), mean and
+        scatter matrix computed on the device: ``{"mean", "components", "explained_variance", "explained_variance_ratio",
+        "count"}`` (``VectorStore.pca`` states the steps) -- what the reference's ``reduce_dimensions(method="pca")`` fits on a
+        1 000-vector sample on the host (wdbx/utils/visualization.py:35-66).  Any number of shards."""
+        return self.vector_store.pca(n_components, filter_metadata=filter_metadata)
+
+    async def vector_pca_async(self, n_components: int, filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        return await self.vector_store.pca_async(n_components, filter_metadata=filter_metadata)
+
+    def vector_reduce(self, n_components: int = 2, filter_metadata: Optional[Dict[str, Any]] = None, components=None,
+                      mean=None) -> Dict[str, List[float]]:
+        """Extension: ``{id: [m floats]}``, the coordinates of every stored vector (with ``filter_metadata``: of every vector it
+        matches) on its principal components -- or on ``components`` / ``mean`` given by the caller -- projected on the
+        device (``VectorStore.reduce``): a 2-D layout of the whole corpus."""
+        return self.vector_store.reduce(n_components, filter_metadata=filter_metadata, components=components, mean=mean)
+
+    async def vector_reduce_async(self, n_components: int = 2, filter_metadata: Optional[Dict[str, Any]] = None,
+                                  components=None, mean=None) -> Dict[str, List[float]]:
+        return await self.vector_store.reduce_async(n_components, filter_metadata=filter_metadata, components=components,
+                                                    mean=mean)
+
     def vector_search_range(self, query_vector: List[float], threshold: float,
                             filter_metadata: Optional[Dict[str, Any]] = None, prefilter: Optional[bool] = None,
                             max_results: Optional[int] = None) -> List[Result]:
