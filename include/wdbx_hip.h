@@ -261,6 +261,42 @@ int wdbx_index_assign(wdbx_index* idx, const float* centers /* host [n_centers, 
                       int32_t* out_center /* [rows] or NULL */, float* out_score /* [rows] or NULL */,
                       float* out_sums /* [n_centers, dim] or NULL */, uint64_t* out_counts /* [n_centers] or NULL */);
 
+/* ---- k-NN graph: every stored row's k nearest stored rows ---- */
+/* The k-nearest-neighbour graph of the corpus where it lies (UMAP, t-SNE, HDBSCAN, label propagation, near-duplicate reports).
+ * Blocking, host buffers.  rows is the handle's row count when the call runs.
+ *   Line r is the exact fp32 top-k of all rows that are unmasked, not removed and not r.  The STORED row r is the query;
+ *   nothing is normalised again.  Self is left out by row number, not by score: a vector with more than k exact duplicates gets
+ *   k of them and never itself.  A masked-out, removed or NaN-holding row has a line of -1 / 0 as anchor and is never returned
+ *   as a candidate.  A line with fewer than k eligible neighbours is padded with -1 / 0, exactly as wdbx_index_search_matrix
+ *   pads.  Order within a line: score descending, row ascending.
+ *   Line r is bit-identical, ids and score bits, to line r of wdbx_index_search_matrix over the list of all eligible rows --
+ *   hence to wdbx_index_search_rows too -- and the same bits from run to run.
+ *   mask_words / mask_word_count as wdbx_index_search_masked_n (NULL / 0 = every row).
+ *   How: a sweep on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16) with both operands read from the bf16 shadow copy --
+ *   candidates as the M operand, anchors as the N operand -- appends to each anchor's bounded list every candidate whose
+ *   approximate score reaches the anchor's threshold less twice the rigorous error bound of the two arithmetics; a list about to
+ *   fill up is compacted around its own k-th largest entry, which becomes the threshold.  The surviving lists are re-scored with
+ *   exact_score's arithmetic and ranked by the ranking tail of the listed-row calls.  An anchor whose list overflowed or whose
+ *   bound is not finite (get_option "last_knn_repaired") is answered by wdbx_index_search_matrix' own rounds, and so is the
+ *   whole call (get_option "last_knn_path" = 2, else 1) below 512 eligible rows, when an eligible row has an infinite norm or
+ *   when the shadow copy finds no room.  get_option "last_knn_launches" / "last_knn_passes" / "last_knn_appends": kernel
+ *   launches, sweep launches and appended list entries of the last call.  A sweep launch covers as many anchor tiles of 128
+ *   rows as are resident at once (two per compute unit) and as the 256 MiB of lists hold; set_option "knn_max_grid" lowers
+ *   that (0 = the plan's choice): more passes, the same bits.
+ *   Cost cliff: a list holds about k + 128 rows within twice the bound of the k-th neighbour; an anchor with more of them
+ *   there -- dense clusters, or (L2) one eligible row of a huge norm, which widens every anchor's bound -- takes the repair
+ *   route, a full row scan on the vector ALUs per anchor.  "last_knn_repaired" is the only report of it.
+ *   WDBX_E_INVALID: k outside [1, WDBX_MAX_GRAPH_K], a null output, a mask shorter than ceil(rows / 32) words (checked under
+ *   the handle's lock).  An empty index is WDBX_OK and launches nothing.  A refused call leaves the handle usable.
+ *   out_idx / out_score must hold k entries per row the index holds WHEN THE CALL RUNS (the count is read under the handle's
+ *   lock and is not passed in): a caller sizes them from wdbx_index_size and keeps every wdbx_index_add / wdbx_index_fill_synthetic
+ *   on this handle out until the call has returned.
+ *   The call holds the handle's mutex to its end.  Nothing of the call stays valid in the handle. */
+#define WDBX_MAX_GRAPH_K 64
+int wdbx_index_knn_graph(wdbx_index* idx, int k,
+                         const uint32_t* mask_words, uint64_t mask_word_count,   /* NULL / 0: every row */
+                         int64_t* out_idx /* [rows, k] */, float* out_score /* [rows, k] */);
+
 /* ---- device PCA: moments of the stored rows, and their projection ---- */
 /* The two corpus-sized passes of a principal component analysis (the reference's VectorVisualizer.reduce_dimensions(method="pca"),
  * wdbx/utils/visualization.py:35-66, fed there by at most 1 000 vectors fetched one by one, visualization.py:487-505) with no

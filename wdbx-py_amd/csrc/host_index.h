@@ -238,6 +238,13 @@ struct wdbx_index {
   DevBuf<char> d_asg_part{&bufs};
   DevBuf<char> d_asg_out{&bufs};
   int64_t last_assign_ambiguous = 0, last_assign_launches = 0, last_assign_center_blocks = 0, last_assign_partials = 0;
+  // k-NN graph (wdbx_index_knn_graph, host_knn.h): one pass's candidate lists; their fill counters followed by the call's
+  // {appended entries, largest eligible norm} words; every row's repair flag.  What the last call did.
+  DevBuf<u64> d_knn_lists{&bufs};
+  DevBuf<uint32_t> d_knn_counts{&bufs};
+  DevBuf<uint32_t> d_knn_flags{&bufs};
+  int last_knn_path = 0;
+  int64_t last_knn_repaired = 0, last_knn_launches = 0, last_knn_appends = 0, last_knn_passes = 0;
   // device PCA (wdbx_index_moments / wdbx_index_project, host_pca.h): the mean (padded dimension) followed by the count; the
   // column sums' partials; the scatter pass's partials; the scatter matrix before its download; the call's basis followed by
   // its offset; every row's coordinates.  What the last moments call did.
@@ -262,7 +269,8 @@ struct wdbx_index {
           opt_gemm_sample_div = 0, opt_range_min_rows = 131072, opt_scan_u6 = -1, opt_scan_u6_cap = 0, opt_scan_u42 = -1, opt_scan_u42_share = -1, opt_scan_u42_mfma = -1, opt_gemm_masked = 1, opt_rows_keys_max = 8192, opt_distinct_overfetch = 4,
           opt_multivector_round_vectors = 256, opt_multivector_tiles = -1, opt_multivector_tiles_min_vectors = 24, opt_range_batch_min_queries = 4, opt_range_pair_cap = 0,
           opt_mmr_scratch_mib = MMR_SCRATCH_MIB_MAX, opt_groups_segment_rows = GROUPS_SEGMENT_DEFAULT,
-          opt_moments_tiles_per_group = 0, opt_moments_partials = 0;
+          opt_moments_tiles_per_group = 0, opt_moments_partials = 0,
+          opt_knn_max_grid = 0;  // workgroups of one k-NN sweep launch at most (0: what is resident and fits the scratch)
 };
 
 struct DeviceGuard {
@@ -456,7 +464,8 @@ static int launch_merge(wdbx_index* ix, const MergeArgs& m_in, int nq) {
 // One launch of 256-thread workgroups between the two records of `pool`; a kernel whose dynamic LDS passes 64 KiB gets its limit
 // raised first -- a runtime call on EVERY such launch, so a site that launches in a loop of rounds with lists in LDS raises the
 // limit once before the loop and keeps its bracket written out (wdbx_index_search_matrix passes its lists' LDS and reaches the raise
-// only with k = WDBX_MAX_K lists in LDS, once per round of 256 anchors; every other caller passes lds = 0);
+// only with k = WDBX_MAX_K lists in LDS, once per round of 256 anchors; wdbx_index_knn_graph's sweep raises its limit before its
+// loop of passes and writes the bracket out; every other caller passes lds = 0);
 // so does a site that launches twice inside one bracket or counts more than one launch per bracket.
 template <typename Fn, typename Args>
 static int launch_bracketed(wdbx_index* ix, EventPool& pool, Fn fn, dim3 grid, size_t lds, const Args& a) {

@@ -44,6 +44,10 @@
 //                           row against a few given vectors on the fp32 matrix cores, a top-1 per row folded in registers; the exact
 //                           pass over the rows the tile pass cannot vouch for, the winner's exact score, per-centre sums
 //   host_assign.h           that call's argument checks, centre blocks, LDS, grids, partial sums and the certainty bound's coefficients
+//   kernels_knn.h           knn_tile_kernel: the k-nearest-neighbour graph of the stored rows (wdbx_index_knn_graph) -- both operands
+//                           the bf16 shadow copy on the bf16 matrix cores, an anchor per accumulator column, a bounded candidate
+//                           list per anchor that tightens its own threshold; knn_exact_kernel: the lists' exact scores
+//   host_knn.h              that call's argument checks, tiles, list capacity, LDS, scratch, passes, route cut and the margin
 //   kernels_pca.h           scatter_tile_kernel, project_tile_kernel: device PCA (wdbx_index_moments / wdbx_index_project) -- the
 //                           centred scatter matrix as a split-K SYRK over the stored rows on the fp32 matrix cores, column sums
 //                           and the float64 combination around it, every row's coordinates on up to 32 directions
@@ -126,6 +130,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_subset.h"  // (device-free as well: row-list validation, route and grid sizing of a search among listed rows)
 #include "host_matrix.h"  // (device-free as well: route, anchor block, instance and rounds of a distance matrix among listed rows)
 #include "host_assign.h"  // (device-free as well: argument checks, centre blocks, LDS, grids, partials and bound of an assignment)
+#include "host_knn.h"  // (device-free as well: argument checks, tiles, list capacity, scratch, passes, route cut and margin of a k-NN graph)
 #include "host_pca.h"  // (device-free as well: argument checks, tile groups, LDS, ranges, partials and grids of the moments and the projection)
 #include "host_multimask.h"  // (device-free as well: where the queries of a call with a mask per query sit in the tile blocks)
 #include "host_selection.h"  // (device-free as well: the sample, stride and capacities of the selection rounds)
@@ -175,6 +180,8 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "kernels_matrix.h"
 #include "kernels_assign.h"
 static_assert(ASSIGN_MAX_CENTERS == WDBX_MAX_CENTERS, "the plan's limit is the header's");
+#include "kernels_knn.h"
+static_assert(KNN_MAX_K == WDBX_MAX_GRAPH_K, "the plan's limit is the header's");
 #include "kernels_pca.h"
 static_assert(PCA_MAX_COMPONENTS == WDBX_MAX_COMPONENTS, "the plan's limit is the header's");
 #include "kernels_rowlists.h"
@@ -1062,6 +1069,178 @@ int wdbx_index_assign(wdbx_index* ix, const float* centers, int n_centers, int n
   HIP_TRY(hipStreamSynchronize(ix->stream));
   // (partials of a call with many centres -- up to ASSIGN_PARTIALS_BUDGET -- do not stay on the handle; small ones are kept for the next iteration)
   if (ix->d_asg_part.bytes > ASSIGN_PARTIALS_KEEP) return ix->d_asg_part.release();
+  return WDBX_OK;
+} WDBX_CATCH
+
+// ---- k-NN graph of the stored rows (kernels_knn.h, host_knn.h) --------------------------------
+// The repair route: the listed anchors -- positions in the eligible list, ascending -- answered by matrix_kernel over the whole
+// eligible list, in rounds of consecutive positions whose rows are consecutive too, so that a round's ranking tail writes its
+// lines where they belong: slot = row.  The eligible list is in d_sub_ids.
+static int knn_repair(wdbx_index* ix, const std::vector<uint32_t>& ids32, const std::vector<uint32_t>& positions, int k, int64_t* launches) {
+  const uint64_t n_ids = ids32.size();
+  const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
+  const MatrixPlan mp = matrix_plan(n_ids, k, pitch4, ix->cu_count, ix->opt_rows_keys_max, ix->opt_select_min_k, ix->opt_lds_lists != 0);
+  const bool lists = mp.sp.route == SUBSET_LISTS;
+  const RankSource::Form form = lists ? RankSource::LISTS : mp.sp.route == SUBSET_SELECT ? RankSource::SELECT : RankSource::KEYS;
+  int rc;
+  if ((rc = grow_rank_scratch(ix, form, mp.sp.scratch_u64))) return rc;
+  const matrix_fn fn = pick_matrix(ix->metric, mp.mode, mp.sp.qb, pitch4);
+  if (!fn) return fail(WDBX_E_STATE, "no distance-matrix instance for mode %d with %d anchors per block", mp.mode, mp.sp.qb);
+  const size_t lds = lists ? mp.sp.lds : 0;
+  for (size_t i = 0; i < positions.size();) {
+    const uint32_t first = positions[i];
+    int b = 1;
+    while (i + b < positions.size() && b < mp.sp.round && positions[i + b] == first + (uint32_t)b && ids32[first + b] == ids32[first] + (uint32_t)b) ++b;
+    MatrixArgs a = {};
+    a.rows = (const f4*)ix->d_rows.p;
+    a.ids = ix->d_sub_ids;
+    a.out = lists ? ix->d_partials : ix->d_sub_keys;
+    a.key_stride = n_ids;
+    a.n_ids = (uint32_t)n_ids;
+    a.pitch4 = pitch4;
+    a.first = first;
+    a.na = (uint32_t)b;
+    a.k = k;
+    if ((rc = launch_bracketed(ix, ix->scan_ev, fn, dim3(mp.sp.blocks, matrix_anchor_blocks(mp, b)), lds, a))) return rc;
+    const RankSource src = lists ? RankSource{form, ix->d_partials, mp.sp.P, nullptr} : RankSource{form, ix->d_sub_keys, n_ids, nullptr};
+    if ((rc = enqueue_rank_tail(ix, src, (int)ids32[first], b, k, ix->metric))) return rc;
+    *launches += 2;
+    i += (size_t)b;
+  }
+  return WDBX_OK;
+}
+
+// The whole call holds the handle's mutex.  Under it: the mask's length is checked, the row norms are brought up to date and
+// come back once -- the eligible rows, their largest norm and whether one is infinite are found on the host -- and the bf16
+// shadow copy is extended.  Every pass of the plan is a sweep launch (a gemm launch in the profile), the exact pass over its
+// lists (a scan launch) and the ranking tail writing from the pass's first row on (a merge launch); then the flags come back
+// and the flagged anchors take the repair route; one download, and the lines of the rows without a result are filled in.
+int wdbx_index_knn_graph(wdbx_index* ix, int k, const uint32_t* mask_words, uint64_t mask_word_count, int64_t* out_idx,
+                         float* out_score) try {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  switch (knn_validate(k, out_idx != nullptr, out_score != nullptr)) {
+    case KNN_OK: break;
+    case KNN_BAD_K: return fail(WDBX_E_INVALID, "k=%d outside [1, %d]", k, WDBX_MAX_GRAPH_K);
+    default: return fail(WDBX_E_INVALID, "null output");
+  }
+  std::unique_lock<std::mutex> lk(ix->mu);
+  ix->last_knn_path = KNN_PATH_NONE;
+  ix->last_knn_repaired = ix->last_knn_launches = ix->last_knn_appends = ix->last_knn_passes = 0;
+  if (!ix->n) return WDBX_OK;  // (nothing stored: nothing to write, nothing launched)
+  if (ix->n > MATRIX_MAX_IDS) return fail(WDBX_E_INVALID, "%llu rows in one call: at most 2^31 - 1", (u64)ix->n);
+  int rc;
+  if (mask_words && (rc = check_mask_words(ix->n, mask_word_count))) return rc;
+  DeviceGuard g(ix->device);
+  MaskScope scope(ix);
+  if (mask_words && (rc = scope.set(mask_words))) return rc;
+  if ((rc = ensure_row_norms(ix))) return rc;
+  const size_t n = (size_t)ix->n, elems = n * (size_t)k;
+  std::vector<float> cn(n);
+  HIP_TRY(hipMemcpyAsync(cn.data(), ix->d_cn, n * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  std::vector<uint32_t> ids32;
+  ids32.reserve(n);
+  float cmax = 0.f;
+  bool finite = true;
+  for (size_t r = 0; r < n; ++r) {
+    if ((mask_words && !((mask_words[r >> 5] >> (r & 31)) & 1u)) || cn[r] != cn[r]) continue;
+    ids32.push_back((uint32_t)r);
+    if (cn[r] < INFINITY) cmax = std::max(cmax, cn[r]);
+    else finite = false;
+  }
+  bool shadow = false;
+  if (finite && ids32.size() >= KNN_TILE_MIN_ROWS) {
+    HIP_TRY(prepare_bf16_shadow(ix, &shadow));
+    shadow = shadow && ix->cov_bf16.covers(ix->n);
+  }
+  const KnnPlan kp = knn_plan(ix->n, ids32.size(), k, ix->cu_count, shadow, finite, (uint64_t)ix->opt_knn_max_grid);
+  ix->last_knn_path = kp.path;
+  auto fill_empty = [&](size_t r) {
+    std::fill(out_idx + r * k, out_idx + (r + 1) * k, (int64_t)-1);
+    std::fill(out_score + r * k, out_score + (r + 1) * k, 0.0f);
+  };
+  if (kp.path == KNN_PATH_NONE) {
+    for (size_t r = 0; r < n; ++r) fill_empty(r);
+    return WDBX_OK;
+  }
+  if ((rc = ensure_out(ix, elems))) return rc;
+  int64_t launches = 0;
+  std::vector<uint32_t> positions;  // of the anchors the repair route answers, in the eligible list
+  if (kp.path == KNN_PATH_TILES) {
+    if ((rc = ix->d_knn_lists.grow(kp.list_bytes)) || (rc = ix->d_knn_counts.grow(kp.count_bytes)) || (rc = ix->d_knn_flags.grow(kp.flag_bytes)))
+      return rc;
+    uint32_t* const d_words = ix->d_knn_counts + (size_t)kp.grid * KNN_ANCHOR_TILE;  // {appends (two words), largest norm}
+    uint32_t h_words[4] = {0, 0, 0, 0};
+    memcpy(&h_words[2], &cmax, sizeof cmax);
+    HIP_TRY(hipMemcpyAsync(d_words, h_words, sizeof h_words, hipMemcpyHostToDevice, ix->stream));
+    const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
+    const knn_tile_fn tile = pick_knn_tile(ix->metric);
+    const knn_exact_fn exact = pick_knn_exact(ix->metric, pitch4);
+    KnnArgs ta = {};
+    ta.rows16 = (const char*)ix->d_rows16.p;
+    ta.cn = ix->d_cn;
+    ta.mask = ix->active_mask;
+    ta.cmax_bits = d_words + 2;
+    ta.lists = ix->d_knn_lists;
+    ta.counts = ix->d_knn_counts;
+    ta.flags = ix->d_knn_flags;
+    ta.appends = (unsigned long long*)d_words;
+    ta.n_rows = (uint32_t)ix->n;
+    ta.pitch16 = ix->pitch16;
+    ta.cap = kp.cap;
+    ta.cand_tiles = kp.cand_tiles;
+    ta.k = k;
+    ta.bound = knn_bound((uint32_t)ix->pitch);
+    // (the sweep's LDS passes 64 KiB: its limit is raised once, and the passes' brackets are written out)
+    HIP_TRY(hipFuncSetAttribute((const void*)tile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kp.lds));
+    for (uint32_t p = 0; p < kp.passes; ++p) {
+      const uint64_t first = knn_pass_first(kp, p);
+      const uint32_t b = knn_pass_anchors(kp, ix->n, p);
+      ta.tile0 = p * kp.grid;
+      const uint32_t wgs = (b + KNN_ANCHOR_TILE - 1) / KNN_ANCHOR_TILE;
+      if ((rc = record(ix->gemm_ev, ix->profile, ix->stream, true))) return rc;
+      hipLaunchKernelGGL(tile, dim3(wgs), dim3(256), kp.lds, ix->stream, ta);
+      HIP_TRY(hipGetLastError());
+      if ((rc = record(ix->gemm_ev, ix->profile, ix->stream, false))) return rc;
+      KnnExactArgs ea = {};
+      ea.rows = (const f4*)ix->d_rows.p;
+      ea.lists = ix->d_knn_lists;
+      ea.counts = ix->d_knn_counts;
+      ea.first = (uint32_t)first;
+      ea.anchors = b;
+      ea.cap = kp.cap;
+      ea.pitch4 = pitch4;
+      if ((rc = launch_bracketed(ix, ix->scan_ev, exact, dim3(kp.exact_grid), 0, ea))) return rc;
+      const RankSource src = {RankSource::KEYS, ix->d_knn_lists, kp.cap, ix->d_knn_counts};
+      if ((rc = enqueue_rank_tail(ix, src, (int)first, (int)b, k, ix->metric))) return rc;
+      launches += 3;
+    }
+    std::vector<uint32_t> flags(n);
+    HIP_TRY(hipMemcpyAsync(flags.data(), ix->d_knn_flags, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipMemcpyAsync(h_words, d_words, sizeof h_words, hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    for (size_t i = 0; i < ids32.size(); ++i)
+      if (flags[ids32[i]]) positions.push_back((uint32_t)i);
+    ix->last_knn_appends = (int64_t)(((u64)h_words[1] << 32) | h_words[0]);
+    ix->last_knn_passes = kp.passes;
+  } else {
+    positions.resize(ids32.size());
+    for (size_t i = 0; i < positions.size(); ++i) positions[i] = (uint32_t)i;
+  }
+  if (!positions.empty()) {
+    if ((rc = ix->d_sub_ids.grow(ids32.size() * sizeof(uint32_t)))) return rc;
+    HIP_TRY(hipMemcpyAsync(ix->d_sub_ids, ids32.data(), ids32.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ix->stream));
+    if ((rc = knn_repair(ix, ids32, positions, k, &launches))) return rc;
+  }
+  ix->last_knn_repaired = (int64_t)positions.size();
+  ix->last_knn_launches = launches;
+  if ((rc = download_results(ix, elems, out_idx, out_score))) return rc;
+  // the rows without a line of their own (the repair route writes none for them)
+  size_t e = 0;
+  for (size_t r = 0; r < n; ++r) {
+    if (e < ids32.size() && ids32[e] == r) ++e;
+    else fill_empty(r);
+  }
   return WDBX_OK;
 } WDBX_CATCH
 
@@ -3115,6 +3294,7 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"groups_segment_rows", &wdbx_index::opt_groups_segment_rows},
     {"moments_tiles_per_group", &wdbx_index::opt_moments_tiles_per_group},
     {"moments_partials", &wdbx_index::opt_moments_partials},
+    {"knn_max_grid", &wdbx_index::opt_knn_max_grid},
 };
 
 static int64_t* option_slot(wdbx_index* ix, const char* name) { return find_option(ix, kOptions, name); }
@@ -3146,6 +3326,8 @@ int wdbx_index_set_option(wdbx_index* ix, const char* name, int64_t value) try {
     return fail(WDBX_E_INVALID, "scan_u42_share %lld: -1 (the default), 1, 2 or 4 queries per read", (long long)value);
   if (slot == &ix->opt_scan_u42_mfma && value != -1 && value != 0 && value != 1)
     return fail(WDBX_E_INVALID, "scan_u42_mfma %lld: -1 (the default), 0 or 1", (long long)value);
+  if (slot == &ix->opt_knn_max_grid && (value < 0 || value > (1 << 20)))
+    return fail(WDBX_E_INVALID, "knn_max_grid %lld: 0 (the plan's choice) or a positive count", (long long)value);
   *slot = value;
   if (!strcmp(name, "group_bounds")) ix->gmax_valid = false;  // re-decide (and rebuild the group maxima) at the next batch
   return WDBX_OK;
@@ -3202,6 +3384,11 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "last_assign_launches")) return *value = ix->last_assign_launches, WDBX_OK;
   if (name && !strcmp(name, "last_assign_center_blocks")) return *value = ix->last_assign_center_blocks, WDBX_OK;
   if (name && !strcmp(name, "last_assign_partials")) return *value = ix->last_assign_partials, WDBX_OK;
+  if (name && !strcmp(name, "last_knn_path")) return *value = ix->last_knn_path, WDBX_OK;
+  if (name && !strcmp(name, "last_knn_repaired")) return *value = ix->last_knn_repaired, WDBX_OK;
+  if (name && !strcmp(name, "last_knn_launches")) return *value = ix->last_knn_launches, WDBX_OK;
+  if (name && !strcmp(name, "last_knn_appends")) return *value = ix->last_knn_appends, WDBX_OK;
+  if (name && !strcmp(name, "last_knn_passes")) return *value = ix->last_knn_passes, WDBX_OK;
   if (name && !strcmp(name, "last_moments_partials")) return *value = ix->last_moments_partials, WDBX_OK;
   if (name && !strcmp(name, "last_moments_tile_groups")) return *value = ix->last_moments_tile_groups, WDBX_OK;
   if (name && !strcmp(name, "last_moments_launches")) return *value = ix->last_moments_launches, WDBX_OK;

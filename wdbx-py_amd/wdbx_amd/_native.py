@@ -22,6 +22,7 @@ MAX_EXCLUDE_ROWS = 1024  # WDBX_MAX_EXCLUDE_ROWS
 MAX_CONTEXT_PAIRS = 32   # WDBX_MAX_CONTEXT_PAIRS: (positive, negative) pairs of one discovery query
 MAX_GROUP_SIZE = 64      # WDBX_MAX_GROUP_SIZE: members one group of wdbx_index_search_groups holds
 MAX_CENTERS = 4096       # WDBX_MAX_CENTERS: centres of one wdbx_index_assign call
+MAX_GRAPH_K = 64         # WDBX_MAX_GRAPH_K: neighbours per row of one wdbx_index_knn_graph call
 MAX_COMPONENTS = 32      # WDBX_MAX_COMPONENTS: basis vectors of one wdbx_index_project call
 UNIQUE_ID_BYTES = 128
 
@@ -77,6 +78,7 @@ SIGNATURES = {
     "wdbx_index_search_matrix": (C.c_int, [C.c_void_p, _u64p, C.c_uint64, C.c_int, _i64p, _f32p]),
     "wdbx_index_assign": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
                                     C.POINTER(C.c_int32), _f32p, _f32p, _u64p]),
+    "wdbx_index_knn_graph": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64, _i64p, _f32p]),
     "wdbx_index_moments": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64, _f32p, _dblp, _u64p]),
     "wdbx_index_project": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.POINTER(C.c_uint32), C.c_uint64, _f32p]),
     "wdbx_index_search_row_lists": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _u64p, _u64p, C.c_int,
@@ -446,6 +448,21 @@ class NativeIndex:
                                            0 if m is None else m.size, ptr("center", C.c_int32), ptr("score", C.c_float),
                                            ptr("sums", C.c_float), ptr("counts", C.c_uint64)))
         return out
+
+    def knn_graph(self, k: int, mask=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The k-nearest-neighbour graph of the stored rows (``wdbx_index_knn_graph``): line ``r`` is the exact top-``k`` of
+        the rows ``mask`` allows (uint32 words as in :meth:`search`) other than ``r`` itself, with the stored row ``r`` as the
+        query -- :meth:`search_matrix`' ids and score bits over all those rows.  A masked, removed or NaN-holding row has a
+        line of -1 / 0.  Returns ``(idx[n, k], score[n, k])``, sized here from :meth:`size`: the caller keeps rows from being
+        added between that and the call (``HipFlatIndex.knn_graph`` holds its ingest lock around it)."""
+        n = self.size()
+        idx = np.full((n, int(k)), -1, np.int64)
+        score = np.zeros((n, int(k)), np.float32)
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint32)
+        # (k, the outputs and the mask's length are checked by the library, the length under the handle's lock)
+        _check(self._lib.wdbx_index_knn_graph(self._h, int(k), None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                              0 if m is None else m.size, idx.ctypes.data_as(_i64p), score.ctypes.data_as(_f32p)))
+        return idx, score
 
     def moments(self, center: bool = True, mask=None, want=("mean", "scatter")) -> dict:
         """Moments of the COUNTED rows (``wdbx_index_moments``: the rows ``mask`` allows whose norm is finite): ``"count"``

@@ -98,6 +98,9 @@ class WDBXConfig:
         # distance matrix (``vector_search_matrix_pairs`` / ``_offsets``): the largest sample one call accepts -- the work grows
         # with its square, so an accidental "every vector" is refused instead of served
         "MATRIX_MAX_SAMPLE": 10000,
+        # k-NN graph (``vector_knn_graph``): the most stored rows one call accepts -- every row is scored against every other,
+        # so the default admits the corpus sizes the sweep serves in seconds and refuses an accidental n^2 beyond them
+        "GRAPH_MAX_ROWS": 2000000,
     }
 
     def __init__(self, config_dict: Optional[Dict[str, Any]] = None, config_path: Optional[str] = None):

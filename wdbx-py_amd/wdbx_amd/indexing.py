@@ -865,6 +865,40 @@ class HipFlatIndex(VectorIndex):
                 return None
             raise
 
+    # ---- k-NN graph (extension: every stored row's nearest stored rows, no stored vector leaves the device) ----
+    def knn_graph(self, k: int, row_mask: Optional[np.ndarray] = None) -> Optional[dict]:
+        """Every row's ``k`` nearest rows among those that still have an id (and that ``row_mask``, as ``row_mask_for`` returns
+        it, allows), itself left out by row number: one library call (``wdbx_index_knn_graph``).  Returns ``{"rows", "ids",
+        "idx", "score", "neighbor_ids"}``: the rows with a line and their ids, ``idx`` / ``score`` ``[len(rows), k]`` cut to
+        those rows (-1 / 0 where a line has fewer than ``k`` neighbours; scores as ``search`` returns them) and the id of every
+        row that occurs as a neighbour.  None for an empty index; errors are swallowed (None) or raised as in ``search``.
+        The outputs are sized by the row count, which the library reads again under its own lock: the call holds
+        ``_ingest_lock`` from sizing them to the id mapping, as ``assign`` does."""
+        try:
+            if self.next_index == 0:
+                return None
+            # (a removed row is NaN on the device: the library gives it no line and never returns it, so it needs no mask)
+            with self._ingest_lock:
+                idx, score = self._native.knn_graph(int(k), mask=row_mask)
+                repaired = self._native.get_option("last_knn_repaired")
+                swept = self._native.get_option("last_knn_path") == 1
+                rows = np.flatnonzero((idx >= 0).any(axis=1)) if idx.shape[0] else np.empty(0, np.int64)
+                ids = [self._id_of(int(r)) for r in rows]
+                seen = np.unique(idx[rows])
+                names = {int(r): self._id_of(int(r)) for r in seen if r >= 0}
+            # (a swept anchor with more rows within the margin of its k-th neighbour than its list holds -- dense clusters, or an
+            # L2 row of a huge norm -- is answered by a full row scan instead: the same lines, but quadratic time when many are)
+            if swept and repaired:
+                log = logger.warning if repaired * 10 > len(rows) else logger.info
+                log("k-NN graph: %d of %d rows overflowed their candidate list and were answered by full row scans", repaired, len(rows))
+            score = score[rows] if self.metric == _native.METRIC_COSINE else -score[rows]
+            return {"rows": rows, "ids": ids, "idx": idx[rows], "score": score, "neighbor_ids": names}
+        except Exception as e:
+            logger.error("Error building the k-NN graph of HIP index: %s", e)
+            if self.swallow_errors:
+                return None
+            raise
+
     # ---- device PCA (extension: moments of the stored rows and their projection, no stored vector leaves the device) ----
     def moments(self, mask: Optional[np.ndarray] = None, center: bool = True) -> Optional[dict]:
         """``{"count", "mean", "scatter"}`` of the rows that ``mask`` (as ``row_mask_for`` returns it) allows and that are

@@ -1488,6 +1488,38 @@ class VectorStore:
         loop = asyncio.get_running_loop()
         return await loop.run_in_executor(self.thread_pool, lambda: self.assign(centers, filter_metadata=filter_metadata))
 
+    # ---- k-NN graph (extension: every stored vector's nearest stored vectors) ----
+    def knn_graph(self, k: int = 15, filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, List[Tuple[str, float]]]:
+        """For every stored vector (with ``filter_metadata``: every vector it matches, among those it matches) its ``k``
+        nearest other vectors: ``{id: [(neighbour id, score), ...]}``, best first, scores as ``search`` returns them -- what
+        UMAP, t-SNE, HDBSCAN, label propagation and a near-duplicate report start from.  A vector is never its own neighbour;
+        another vector equal to it is one.  One library call (``wdbx_index_knn_graph``), no vector leaves the device; a
+        filter always travels as the row mask.  More than ``GRAPH_MAX_ROWS`` stored rows is a ``ValueError``: the work grows
+        with the square of the rows.  A vector without any neighbour (the only match of a filter) has no entry."""
+        if len(self.indices) != 1:
+            raise ValueError(
+                f"knn_graph needs a store of one shard, this one has {len(self.indices)}: a cross-shard graph needs anchors "
+                "from another device, which is a later variant")
+        if not 1 <= int(k) <= _native.MAX_GRAPH_K:
+            raise ValueError(f"k={k}: between 1 and {_native.MAX_GRAPH_K} neighbours are served")
+        index = self.indices[0]
+        cap = int(self.config.get("GRAPH_MAX_ROWS", 2000000))
+        if index.next_index > cap:
+            raise ValueError(f"a k-NN graph over {index.next_index} rows: GRAPH_MAX_ROWS allows {cap}")
+        mask = self._row_masks(filter_metadata)[0] if filter_metadata else None
+        self.last_search_path = "threads"
+        res = index.knn_graph(int(k), row_mask=mask)
+        out: Dict[str, List[Tuple[str, float]]] = {}
+        if res:
+            names = res["neighbor_ids"]
+            for vid, line, scores in zip(res["ids"], res["idx"].tolist(), res["score"].tolist()):
+                out[vid] = [(names[r], s) for r, s in zip(line, scores) if r >= 0]
+        return out
+
+    async def knn_graph_async(self, k: int = 15, filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, List[Tuple[str, float]]]:
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(self.thread_pool, lambda: self.knn_graph(k, filter_metadata=filter_metadata))
+
     def cluster(self, k: int, max_iter: int = 25, tol: float = 1e-4, seed=None,
                 filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
         """k-means (Lloyd) over the stored vectors (with ``filter_metadata``: over those it matches).  The initial centres are

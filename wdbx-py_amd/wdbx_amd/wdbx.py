@@ -326,6 +326,17 @@ class WDBX:
                                    filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
         return await self.vector_store.cluster_async(k, max_iter=max_iter, tol=tol, seed=seed, filter_metadata=filter_metadata)
 
+    def vector_knn_graph(self, k: int = 15, filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, List[Tuple[str, float]]]:
+        """Extension: the k-nearest-neighbour graph of the stored vectors.  For every stored vector (with ``filter_metadata``:
+        every vector it matches, among those it matches) its ``k`` nearest other vectors, ``{id: [(neighbour_id, score), ...]}``
+        best first -- the input of UMAP, t-SNE, HDBSCAN, label propagation and near-duplicate reports.  Exact fp32 ranking; a
+        vector is never its own neighbour, an equal one is.  A store of one shard only (``VectorStore.knn_graph`` says why)."""
+        return self.vector_store.knn_graph(k, filter_metadata=filter_metadata)
+
+    async def vector_knn_graph_async(self, k: int = 15,
+                                     filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, List[Tuple[str, float]]]:
+        return await self.vector_store.knn_graph_async(k, filter_metadata=filter_metadata)
+
     def vector_pca(self, n_components: int, filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
         """Extension: principal components of the stored vectors (with ``filter_metadata``: of those it matches), mean and
         scatter matrix computed on the device: ``{"mean", "components", "explained_variance", "explained_variance_ratio",
