@@ -297,6 +297,45 @@ int wdbx_index_knn_graph(wdbx_index* idx, int k,
                          const uint32_t* mask_words, uint64_t mask_word_count,   /* NULL / 0: every row */
                          int64_t* out_idx /* [rows, k] */, float* out_score /* [rows, k] */);
 
+/* ---- similarity self-join: every pair of stored rows above a threshold ---- */
+/* Which stored vectors are near-duplicates of each other (deduplication before indexing, a near-duplicate report, the edges of a
+ * threshold graph), answered where the corpus lies.  Blocking, host buffers.  rows is the handle's row count when the call runs.
+ *   The result is every unordered pair of distinct ELIGIBLE rows -- unmasked, not removed, without a NaN element -- whose exact
+ *   fp32 score reaches threshold, each pair ONCE.  The comparison is wdbx_index_range_search's: cosine / inner product
+ *   score >= threshold, L2 squared distance <= threshold.  CSR by the LOWER row: segment a = [out_offsets[a], out_offsets[a + 1])
+ *   holds the rows b > a.  The score of (a, b) is the exact score with the STORED row a as the query (nothing is normalised
+ *   again) and row b.  Segment a is bit-identical -- rows, order, score bits -- to wdbx_index_range_search with the same
+ *   threshold and mask, wdbx_index_get_rows(a) as the query and normalize_queries = 0, with the rows <= a removed.  A row is never
+ *   paired with itself (by row number); exact duplicates are pairs like any other.  An ineligible row has an empty segment and
+ *   appears in none.  The same bits from run to run.
+ *   mask_words / mask_word_count as wdbx_index_search_masked_n (NULL / 0 = every row).
+ *   capacity: wdbx_index_range_search's rule.  out_offsets (rows + 1 entries) is always true; out_rows / out_scores are written
+ *   only when out_offsets[rows] <= capacity; capacity = 0 is count only (out_rows / out_scores may be NULL).
+ *   How (get_option "last_join_path": 0 nothing launched, 1 the sweep, 2 the exact route): the sweep reads BOTH operands from
+ *   the group-scaled int8 shadow copy on v_mfma_i32_16x16x64_i8 -- an anchor block of 128 / 64 rows resident in LDS as it
+ *   lies in HBM, candidate rows streamed over the triangle of tiles at or behind it -- and keeps a pair when its integer dot
+ *   product reaches ONE integer threshold per pair of 64-row groups, which bounds the exact score from the quantiser's residual
+ *   norms and exact_score's own rounding; the kept pairs (get_option "last_join_candidates") are scored exactly, thresholded,
+ *   grouped by anchor and sorted as a range search's.  A candidate buffer that was too small is grown to the exact count and
+ *   the sweep runs once more ("last_join_reruns"; set_option "join_pair_cap" sets the first size); a buffer past 2 GiB is
+ *   WDBX_E_NOMEM and the message names the candidate count.  The sweep serves rows of at most 1536 dimensions when the shadow
+ *   copy finds room and at least "join_min_rows" (default 1024, arithmetic) rows are eligible.  Everything else takes the exact
+ *   route -- the anchors' stored rows staged device to device as the queries of the fp32 range scan -- which is refused with
+ *   WDBX_E_INVALID above "join_exact_max_rows" (default 65536) rows; the message says which condition sent the call there.
+ *   "last_join_launches" / "last_join_blocks" / "last_join_pairs": kernel launches, anchor blocks and result pairs of the last
+ *   call.  set_option "join_max_grid" lowers the sweep's workgroups (0 = one per compute unit): the same bits.
+ *   WDBX_E_INVALID: a NaN threshold, a null out_offsets, capacity without result buffers, a mask shorter than ceil(rows / 32)
+ *   words (checked under the handle's lock).  An empty index is WDBX_OK and launches nothing.  A refused call leaves the handle
+ *   usable.
+ *   out_offsets must hold rows + 1 entries for the rows the index holds WHEN THE CALL RUNS (the count is read under the handle's
+ *   lock and is not passed in): a caller sizes it from wdbx_index_size and keeps every wdbx_index_add / wdbx_index_fill_synthetic
+ *   on this handle out until the call has returned.
+ *   The call holds the handle's mutex to its end.  Nothing of the call stays valid in the handle. */
+int wdbx_index_self_join(wdbx_index* idx, float threshold,
+                         const uint32_t* mask_words, uint64_t mask_word_count,   /* NULL / 0: every row */
+                         uint64_t capacity, uint64_t* out_offsets /* [rows + 1] */,
+                         int64_t* out_rows, float* out_scores);
+
 /* ---- device PCA: moments of the stored rows, and their projection ---- */
 /* The two corpus-sized passes of a principal component analysis (the reference's VectorVisualizer.reduce_dimensions(method="pca"),
  * wdbx/utils/visualization.py:35-66, fed there by at most 1 000 vectors fetched one by one, visualization.py:487-505) with no

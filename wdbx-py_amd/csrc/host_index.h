@@ -245,6 +245,14 @@ struct wdbx_index {
   DevBuf<uint32_t> d_knn_flags{&bufs};
   int last_knn_path = 0;
   int64_t last_knn_repaired = 0, last_knn_launches = 0, last_knn_appends = 0, last_knn_passes = 0;
+  // similarity self-join (wdbx_index_self_join, host_join.h): the sweep's candidate pairs; the exact pass's keys and their
+  // anchors; the call's words {candidate count (two words), block ticket, result count}.  What the last call did.
+  DevBuf<u64> d_join_pairs{&bufs};
+  DevBuf<u64> d_join_keys{&bufs};
+  DevBuf<uint32_t> d_join_anchor{&bufs};
+  DevBuf<uint32_t> d_join_words{&bufs};
+  int last_join_path = 0;
+  int64_t last_join_launches = 0, last_join_blocks = 0, last_join_candidates = 0, last_join_pairs = 0, last_join_reruns = 0;
   // device PCA (wdbx_index_moments / wdbx_index_project, host_pca.h): the mean (padded dimension) followed by the count; the
   // column sums' partials; the scatter pass's partials; the scatter matrix before its download; the call's basis followed by
   // its offset; every row's coordinates.  What the last moments call did.
@@ -270,7 +278,11 @@ struct wdbx_index {
           opt_multivector_round_vectors = 256, opt_multivector_tiles = -1, opt_multivector_tiles_min_vectors = 24, opt_range_batch_min_queries = 4, opt_range_pair_cap = 0,
           opt_mmr_scratch_mib = MMR_SCRATCH_MIB_MAX, opt_groups_segment_rows = GROUPS_SEGMENT_DEFAULT,
           opt_moments_tiles_per_group = 0, opt_moments_partials = 0,
-          opt_knn_max_grid = 0;  // workgroups of one k-NN sweep launch at most (0: what is resident and fits the scratch)
+          opt_knn_max_grid = 0,  // workgroups of one k-NN sweep launch at most (0: what is resident and fits the scratch)
+          // self-join: workgroups of the sweep at most (0: one per CU); first size of the candidate buffer (0: the plan's);
+          // eligible rows below which the exact route answers; rows above which the exact route is refused
+          opt_join_max_grid = 0, opt_join_pair_cap = 0, opt_join_min_rows = JOIN_MIN_ROWS_DEFAULT,
+          opt_join_exact_max_rows = JOIN_EXACT_MAX_ROWS_DEFAULT;
 };
 
 struct DeviceGuard {

@@ -48,6 +48,10 @@
 //                           the bf16 shadow copy on the bf16 matrix cores, an anchor per accumulator column, a bounded candidate
 //                           list per anchor that tightens its own threshold; knn_exact_kernel: the lists' exact scores
 //   host_knn.h              that call's argument checks, tiles, list capacity, LDS, scratch, passes, route cut and the margin
+//   kernels_join.h          join_tile_kernel: the similarity self-join of the stored rows (wdbx_index_self_join) -- both operands the
+//                           group-scaled i8 shadow copy on the int8 matrix cores, an anchor block resident in LDS as it lies in
+//                           HBM, the triangle of tiles, an integer compare per group pair; join_filter_kernel: the exact pass
+//   host_join.h             that call's argument checks, anchor block, triangle, LDS, grid, buffer size, route cut and tile test
 //   kernels_pca.h           scatter_tile_kernel, project_tile_kernel: device PCA (wdbx_index_moments / wdbx_index_project) -- the
 //                           centred scatter matrix as a split-K SYRK over the stored rows on the fp32 matrix cores, column sums
 //                           and the float64 combination around it, every row's coordinates on up to 32 directions
@@ -131,6 +135,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_matrix.h"  // (device-free as well: route, anchor block, instance and rounds of a distance matrix among listed rows)
 #include "host_assign.h"  // (device-free as well: argument checks, centre blocks, LDS, grids, partials and bound of an assignment)
 #include "host_knn.h"  // (device-free as well: argument checks, tiles, list capacity, scratch, passes, route cut and margin of a k-NN graph)
+#include "host_join.h"  // (device-free as well: argument checks, anchor block, triangle, LDS, grid, route cut and tile test of a self-join)
 #include "host_pca.h"  // (device-free as well: argument checks, tile groups, LDS, ranges, partials and grids of the moments and the projection)
 #include "host_multimask.h"  // (device-free as well: where the queries of a call with a mask per query sit in the tile blocks)
 #include "host_selection.h"  // (device-free as well: the sample, stride and capacities of the selection rounds)
@@ -182,6 +187,9 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 static_assert(ASSIGN_MAX_CENTERS == WDBX_MAX_CENTERS, "the plan's limit is the header's");
 #include "kernels_knn.h"
 static_assert(KNN_MAX_K == WDBX_MAX_GRAPH_K, "the plan's limit is the header's");
+#include "kernels_join.h"
+static_assert(JOIN_TILE_ROWS == G8_ROWS && JOIN_LDS_BLOCK_MAX == (size_t)G8_LDS_B_MAX && JOIN_GAMMA == RANGE_BATCH_GAMMA,
+              "the join streams the int8 tiles' rows and charges the exact pass's rounding as the range block does");
 #include "kernels_pca.h"
 static_assert(PCA_MAX_COMPONENTS == WDBX_MAX_COMPONENTS, "the plan's limit is the header's");
 #include "kernels_rowlists.h"
@@ -1241,6 +1249,272 @@ int wdbx_index_knn_graph(wdbx_index* ix, int k, const uint32_t* mask_words, uint
     if (e < ids32.size() && ids32[e] == r) ++e;
     else fill_empty(r);
   }
+  return WDBX_OK;
+} WDBX_CATCH
+
+// ---- similarity self-join of the stored rows (kernels_join.h, host_join.h) --------------------
+// Both routes leave the result pairs as two host arrays in no particular order: the lower row (the anchor) and the key
+// (score, higher row) of each.  join_emit groups them by anchor -- the CSR offsets are always written; with room the keys go to
+// the caller's row array at their segments and range_sort_decode (host_range.h) sorts and decodes them there, as a range
+// search's do.
+static void join_emit(bool l2, uint64_t n, const std::vector<uint32_t>& anchors, const std::vector<u64>& keys, uint64_t capacity,
+                      uint64_t* out_offsets, int64_t* out_rows, float* out_scores) {
+  std::vector<uint64_t> cnt((size_t)n, 0);
+  for (const uint32_t a : anchors) ++cnt[a];
+  out_offsets[0] = 0;
+  const uint64_t total = range_csr_offsets(cnt.data(), (int)n, out_offsets);
+  if (!total || total > capacity) return;
+  for (size_t r = 0; r < (size_t)n; ++r) cnt[r] = out_offsets[r];  // (now each segment's cursor)
+  for (size_t i = 0; i < anchors.size(); ++i) out_rows[cnt[anchors[i]]++] = (int64_t)keys[i];
+  range_sort_decode(l2 ? 1 : 0, (int)n, out_offsets, out_rows, out_scores);
+}
+
+// The sweep: [the call's bad-row table] -> join_tile_kernel over the triangle (a gemm launch in the profile) -> the candidate
+// count comes back; past the buffer it grows to the exact count and the sweep runs once more -> join_filter_kernel (a merge
+// launch) -> the result count, the anchors and, with room, the keys come back.
+static int join_sweep(wdbx_index* ix, const JoinPlan& jp, float threshold, uint64_t capacity, std::vector<uint32_t>& h_anchor,
+                      std::vector<u64>& h_keys) {
+  int rc;
+  const bool l2 = ix->metric == WDBX_METRIC_L2;
+  const uint32_t pitch8 = ix->pitch8g;
+  const join_tile_fn fn = pick_join_tile(ix->metric, jp.ct8, pitch8);
+  if (!fn) return fail(WDBX_E_STATE, "no self-join instance for anchor blocks of %u rows", jp.block_rows);
+  if ((rc = ix->d_join_words.grow(4 * sizeof(uint32_t)))) return rc;
+  const u64* gbad = ix->d_gbad8;
+  if (ix->active_mask) {  // this call's bad-row table: removed rows, rows past the end, rows the mask leaves out
+    const u64 ngroups = ix->d_groups8.bytes / sizeof(f4);
+    if ((rc = ix->d_call_bad.grow((size_t)ngroups * sizeof(u64)))) return rc;
+    hipLaunchKernelGGL(gbad_with_mask_kernel, dim3(gbad_with_mask_grid(ngroups), 1), dim3(256), 0, ix->stream, (const u64*)ix->d_gbad8,
+                       (const uint32_t*)ix->active_mask, (u64)((ix->n + 31) / 32), ngroups, ix->d_call_bad, (u64)0, (const int32_t*)nullptr);
+    HIP_TRY(hipGetLastError());
+    gbad = ix->d_call_bad;
+    ++ix->last_join_launches;
+  }
+  HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)jp.lds));
+  uint32_t h_words[4];
+  u64 cap = jp.pair_cap, count = 0;
+  auto sweep = [&]() -> int {
+    int rc2 = ix->d_join_pairs.grow((size_t)cap * sizeof(u64));
+    if (rc2) return rc2;
+    const uint32_t zero[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(ix->d_join_words, zero, sizeof zero, hipMemcpyHostToDevice, ix->stream));
+    JoinArgs a = {};
+    a.rows8 = ix->d_rows8g;
+    a.groups = ix->d_groups8;
+    a.gbad = gbad;
+    a.cn = ix->d_cn;
+    a.n_rows = (uint32_t)ix->n;
+    a.pitch8 = pitch8;
+    a.num_tiles = jp.tiles;
+    a.num_blocks = jp.blocks;
+    a.thr = threshold;
+    a.pairs = ix->d_join_pairs;
+    a.pair_count = (unsigned long long*)ix->d_join_words.p;
+    a.ticket = ix->d_join_words + 2;
+    a.pair_cap = cap;
+    if ((rc2 = record(ix->gemm_ev, ix->profile, ix->stream, true))) return rc2;
+    hipLaunchKernelGGL(fn, dim3(jp.grid), dim3(512), jp.lds, ix->stream, a);
+    HIP_TRY(hipGetLastError());
+    if ((rc2 = record(ix->gemm_ev, ix->profile, ix->stream, false))) return rc2;
+    HIP_TRY(hipMemcpyAsync(h_words, ix->d_join_words, sizeof h_words, hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    count = ((u64)h_words[1] << 32) | h_words[0];
+    ++ix->last_join_launches;
+    return WDBX_OK;
+  };
+  if ((rc = sweep())) return rc;
+  if (count > cap) {  // candidates past the buffer: grow to the exact count, the sweep again
+    if (!join_pairs_fit(count))
+      return fail(WDBX_E_NOMEM, "self-join: the threshold admits %llu candidate pairs, whose buffer would pass 2 GiB", count);
+    const u64 first = count;
+    cap = count;
+    ix->last_join_reruns = 1;
+    if ((rc = sweep())) return rc;
+    if (count != first) return fail(WDBX_E_STATE, "self-join: candidate count changed between two sweeps");
+  }
+  ix->last_join_candidates = (int64_t)count;
+  if (!count) return WDBX_OK;
+  if ((rc = ix->d_join_keys.grow((size_t)count * sizeof(u64))) || (rc = ix->d_join_anchor.grow((size_t)count * sizeof(uint32_t)))) return rc;
+  JoinFilterArgs f = {};
+  f.rows = (const f4*)ix->d_rows.p;
+  f.pairs = ix->d_join_pairs;
+  f.n_pairs = count;
+  f.mask = ix->active_mask;
+  f.thr = threshold;
+  f.pitch4 = (uint32_t)ix->pitch / 4;
+  f.out_keys = ix->d_join_keys;
+  f.out_anchor = ix->d_join_anchor;
+  f.count = ix->d_join_words + 3;  // (zero since the sweep's words went up)
+  f.cap = (uint32_t)count;         // (results <= candidates: never past the buffer)
+  const uint32_t fgrid = (uint32_t)std::max<u64>(1, std::min<u64>((u64)ix->cu_count * 8, (count + 3) / 4));
+  const auto ffn = l2 ? join_filter_kernel<WDBX_METRIC_L2> : join_filter_kernel<WDBX_METRIC_COSINE>;
+  if ((rc = launch_bracketed(ix, ix->merge_ev, ffn, dim3(fgrid), 0, f))) return rc;
+  ++ix->last_join_launches;
+  HIP_TRY(hipMemcpyAsync(h_words, ix->d_join_words, sizeof h_words, hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  const size_t res = h_words[3];
+  h_anchor.resize(res);
+  if (res) HIP_TRY(hipMemcpyAsync(h_anchor.data(), ix->d_join_anchor, res * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
+  if (res && res <= capacity) {
+    h_keys.resize(res);
+    HIP_TRY(hipMemcpyAsync(h_keys.data(), ix->d_join_keys, res * sizeof(u64), hipMemcpyDeviceToHost, ix->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  return WDBX_OK;
+}
+
+// The exact route: rounds of up to 64 consecutive anchors whose stored rows are staged device to device as the queries of
+// the fp32 range scan (range_scan_kernel, unchanged), with range search's grow-and-rerun rule for the key buffer; the keys with
+// row <= anchor and the lines of ineligible anchors are dropped as they are decoded.
+static int join_exact(wdbx_index* ix, float threshold, const std::vector<uint8_t>& eligible, std::vector<uint32_t>& h_anchor,
+                      std::vector<u64>& h_keys) {
+  int rc;
+  constexpr int ROUND = 64;
+  const bool l2 = ix->metric == WDBX_METRIC_L2;
+  const uint32_t pitch4 = (uint32_t)ix->pitch / 4;
+  const range_fn fscan = l2 ? pick_range_scan<WDBX_METRIC_L2>(pitch4) : pick_range_scan<WDBX_METRIC_COSINE>(pitch4);
+  if (!fscan) return fail(WDBX_E_STATE, "no range scan instance for rows of %u quads", pitch4);
+  if ((rc = ix->d_rcnt.grow(2 * ROUND * sizeof(uint32_t))) || (rc = ix->d_rthr.grow(2 * ROUND * sizeof(float))) ||
+      (rc = ix->d_q.grow((size_t)ROUND * ix->pitch * sizeof(float))))
+    return rc;
+  const std::vector<float> hthr(ROUND, threshold);
+  HIP_TRY(hipMemcpyAsync(ix->d_rthr, hthr.data(), ROUND * sizeof(float), hipMemcpyHostToDevice, ix->stream));
+  uint32_t P = 1;  // (lanes per row, as pick_range_scan chose them)
+  while (P < pitch4 && P < 64) P <<= 1;
+  const uint64_t groups = (ix->n + (64 / P) - 1) / (64 / P);
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((groups + 3) / 4, (uint64_t)ix->cu_count * 8);
+  std::vector<uint32_t> hcnt(ROUND);
+  std::vector<u64> round_keys;
+  for (uint64_t a0 = 0; a0 < ix->n; a0 += ROUND) {
+    const int nv = (int)std::min<uint64_t>(ROUND, ix->n - a0);
+    if (!std::any_of(eligible.begin() + (size_t)a0, eligible.begin() + (size_t)a0 + nv, [](uint8_t e) { return e != 0; })) continue;
+    HIP_TRY(hipMemcpyAsync(ix->d_q, ix->d_rows + (size_t)a0 * ix->pitch, (size_t)nv * ix->pitch * sizeof(float),
+                           hipMemcpyDeviceToDevice, ix->stream));
+    auto scan = [&]() -> int {
+      int rc2 = ix->d_rkeys.grow((size_t)nv * ix->range_out_cap * sizeof(u64));
+      if (rc2) return rc2;
+      HIP_TRY(hipMemsetAsync(ix->d_rcnt, 0, (size_t)nv * sizeof(uint32_t), ix->stream));
+      RangeArgs r = {};
+      r.rows = (const f4*)ix->d_rows.p;
+      r.queries = (const f4*)ix->d_q.p;
+      r.thr = ix->d_rthr;
+      r.mask = ix->active_mask;
+      r.n_rows = (uint32_t)ix->n;
+      r.pitch4 = pitch4;
+      r.out = ix->d_rkeys;
+      r.count = ix->d_rcnt;
+      r.cap = ix->range_out_cap;
+      if ((rc2 = record(ix->scan_ev, ix->profile, ix->stream, true))) return rc2;
+      hipLaunchKernelGGL(fscan, dim3(grid, nv), dim3(256), 0, ix->stream, r);
+      HIP_TRY(hipGetLastError());
+      if ((rc2 = record(ix->scan_ev, ix->profile, ix->stream, false, (uint32_t)nv))) return rc2;
+      HIP_TRY(hipMemcpyAsync(hcnt.data(), ix->d_rcnt, (size_t)nv * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
+      HIP_TRY(hipStreamSynchronize(ix->stream));
+      ++ix->last_join_launches;
+      return WDBX_OK;
+    };
+    if ((rc = scan())) return rc;
+    const uint32_t most = *std::max_element(hcnt.begin(), hcnt.begin() + nv);
+    if (most > ix->range_out_cap) {  // results past their buffer: grow, the scan again
+      ix->range_out_cap = most;
+      if ((rc = scan())) return rc;
+      if (*std::max_element(hcnt.begin(), hcnt.begin() + nv) > ix->range_out_cap)
+        return fail(WDBX_E_STATE, "self-join: result count changed between two passes");
+    }
+    size_t have = 0;
+    for (int i = 0; i < nv; ++i) have += eligible[(size_t)a0 + i] ? hcnt[i] : 0;
+    round_keys.resize(have);
+    size_t at = 0;
+    for (int i = 0; i < nv; ++i) {
+      if (!eligible[(size_t)a0 + i] || !hcnt[i]) continue;
+      HIP_TRY(hipMemcpyAsync(round_keys.data() + at, ix->d_rkeys + (size_t)i * ix->range_out_cap, hcnt[i] * sizeof(u64),
+                             hipMemcpyDeviceToHost, ix->stream));
+      at += hcnt[i];
+    }
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    at = 0;
+    for (int i = 0; i < nv; ++i) {
+      if (!eligible[(size_t)a0 + i]) continue;
+      for (uint32_t e = 0; e < hcnt[i]; ++e) {
+        const u64 key = round_keys[at + e];
+        if ((uint64_t)range_key_row(key) <= a0 + (uint64_t)i) continue;
+        h_anchor.push_back((uint32_t)(a0 + i));
+        h_keys.push_back(key);
+      }
+      at += hcnt[i];
+    }
+  }
+  return WDBX_OK;
+}
+
+// The whole call holds the handle's mutex.  Under it: the mask's length is checked, the row norms are brought up to date and
+// come back once (the eligible rows -- unmasked, no NaN -- are found on the host), shadow copy G is asked for as the batched
+// path asks for it, and the plan (host_join.h) picks the route.
+int wdbx_index_self_join(wdbx_index* ix, float threshold, const uint32_t* mask_words, uint64_t mask_word_count, uint64_t capacity,
+                         uint64_t* out_offsets, int64_t* out_rows, float* out_scores) try {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  switch (join_validate(threshold, out_offsets != nullptr, capacity, out_rows != nullptr, out_scores != nullptr)) {
+    case JOIN_OK: break;
+    case JOIN_NAN_THRESHOLD: return fail(WDBX_E_INVALID, "threshold is NaN");
+    case JOIN_NULL_OFFSETS: return fail(WDBX_E_INVALID, "null out_offsets");
+    default: return fail(WDBX_E_INVALID, "capacity %llu without result buffers", (u64)capacity);
+  }
+  std::unique_lock<std::mutex> lk(ix->mu);
+  ix->last_join_path = JOIN_PATH_NONE;
+  ix->last_join_launches = ix->last_join_blocks = ix->last_join_candidates = ix->last_join_pairs = ix->last_join_reruns = 0;
+  out_offsets[0] = 0;
+  if (!ix->n) return WDBX_OK;  // (nothing stored: nothing launched)
+  if (ix->n > MATRIX_MAX_IDS) return fail(WDBX_E_INVALID, "%llu rows in one call: at most 2^31 - 1", (u64)ix->n);
+  int rc;
+  if (mask_words && (rc = check_mask_words(ix->n, mask_word_count))) return rc;
+  DeviceGuard g(ix->device);
+  MaskScope scope(ix);
+  if (mask_words && (rc = scope.set(mask_words))) return rc;
+  if ((rc = ensure_row_norms(ix))) return rc;
+  const size_t n = (size_t)ix->n;
+  std::vector<uint8_t> eligible(n);
+  uint64_t n_eligible = 0;
+  {
+    std::vector<float> cn(n);
+    HIP_TRY(hipMemcpyAsync(cn.data(), ix->d_cn, n * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    for (size_t r = 0; r < n; ++r) {
+      eligible[r] = (!mask_words || ((mask_words[r >> 5] >> (r & 31)) & 1u)) && cn[r] == cn[r];
+      n_eligible += eligible[r];
+    }
+  }
+  // (the shadow copy is built only when everything else says sweep: a call on the exact route must not allocate it)
+  const uint32_t pitch8 = i8_tiles_shape_ok(ix) ? i8g_pitch(ix) : 0u;
+  const bool l2 = ix->metric == WDBX_METRIC_L2;
+  const bool shadow = join_ct8(pitch8) && n_eligible >= 2 && n_eligible >= (uint64_t)ix->opt_join_min_rows && prepare_i8g_shadow(ix);
+  const JoinPlan jp = join_plan(ix->n, n_eligible, pitch8, shadow, ix->cu_count, (uint64_t)ix->opt_join_max_grid,
+                                (uint64_t)ix->opt_join_pair_cap, (uint64_t)ix->opt_join_min_rows, (uint64_t)ix->opt_join_exact_max_rows);
+  if (jp.refused) {
+    const char* why = jp.why == JOIN_WHY_PITCH    ? "no int8 tiles for rows of this length on this handle"
+                      : jp.why == JOIN_WHY_SHADOW ? "no room for the int8 shadow copy"
+                                                  : "fewer eligible rows than join_min_rows";
+    return fail(WDBX_E_INVALID, "self-join of %llu rows takes the exact route (%s), which join_exact_max_rows allows up to %lld rows",
+                (u64)ix->n, why, (long long)ix->opt_join_exact_max_rows);
+  }
+  ix->last_join_path = jp.path;
+  std::vector<uint32_t> h_anchor;
+  std::vector<u64> h_keys;
+  if (jp.path == JOIN_PATH_SWEEP) {
+    ix->last_join_blocks = jp.blocks;
+    rc = join_sweep(ix, jp, threshold, capacity, h_anchor, h_keys);
+    // a threshold that admitted very many pairs must not pin gigabytes for the handle's life
+    if (ix->d_join_pairs.bytes > ((size_t)256 << 20)) {
+      (void)hipStreamSynchronize(ix->stream);
+      (void)ix->d_join_pairs.release();
+      (void)ix->d_join_keys.release();
+      (void)ix->d_join_anchor.release();
+    }
+    if (rc) return rc;
+  } else if (jp.path == JOIN_PATH_EXACT) {
+    if ((rc = join_exact(ix, threshold, eligible, h_anchor, h_keys))) return rc;
+  }
+  ix->last_join_pairs = (int64_t)h_anchor.size();
+  join_emit(l2, ix->n, h_anchor, h_keys, capacity, out_offsets, out_rows, out_scores);
   return WDBX_OK;
 } WDBX_CATCH
 
@@ -3295,6 +3569,10 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"moments_tiles_per_group", &wdbx_index::opt_moments_tiles_per_group},
     {"moments_partials", &wdbx_index::opt_moments_partials},
     {"knn_max_grid", &wdbx_index::opt_knn_max_grid},
+    {"join_max_grid", &wdbx_index::opt_join_max_grid},
+    {"join_pair_cap", &wdbx_index::opt_join_pair_cap},
+    {"join_min_rows", &wdbx_index::opt_join_min_rows},
+    {"join_exact_max_rows", &wdbx_index::opt_join_exact_max_rows},
 };
 
 static int64_t* option_slot(wdbx_index* ix, const char* name) { return find_option(ix, kOptions, name); }
@@ -3328,6 +3606,13 @@ int wdbx_index_set_option(wdbx_index* ix, const char* name, int64_t value) try {
     return fail(WDBX_E_INVALID, "scan_u42_mfma %lld: -1 (the default), 0 or 1", (long long)value);
   if (slot == &ix->opt_knn_max_grid && (value < 0 || value > (1 << 20)))
     return fail(WDBX_E_INVALID, "knn_max_grid %lld: 0 (the plan's choice) or a positive count", (long long)value);
+  if (slot == &ix->opt_join_max_grid && (value < 0 || value > (1 << 20)))
+    return fail(WDBX_E_INVALID, "join_max_grid %lld: 0 (the plan's choice) or a positive count", (long long)value);
+  if (slot == &ix->opt_join_pair_cap && value != 0 && (value < (int64_t)JOIN_PAIR_CAP_MIN || value > (int64_t)(JOIN_PAIR_BYTES_MAX / 8)))
+    return fail(WDBX_E_INVALID, "join_pair_cap %lld: 0 (the plan's sizing) or [%llu, %llu] candidate pairs", (long long)value,
+                (u64)JOIN_PAIR_CAP_MIN, (u64)(JOIN_PAIR_BYTES_MAX / 8));
+  if ((slot == &ix->opt_join_min_rows || slot == &ix->opt_join_exact_max_rows) && value < 0)
+    return fail(WDBX_E_INVALID, "%s %lld: a row count", name, (long long)value);
   *slot = value;
   if (!strcmp(name, "group_bounds")) ix->gmax_valid = false;  // re-decide (and rebuild the group maxima) at the next batch
   return WDBX_OK;
@@ -3389,6 +3674,12 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "last_knn_launches")) return *value = ix->last_knn_launches, WDBX_OK;
   if (name && !strcmp(name, "last_knn_appends")) return *value = ix->last_knn_appends, WDBX_OK;
   if (name && !strcmp(name, "last_knn_passes")) return *value = ix->last_knn_passes, WDBX_OK;
+  if (name && !strcmp(name, "last_join_path")) return *value = ix->last_join_path, WDBX_OK;
+  if (name && !strcmp(name, "last_join_launches")) return *value = ix->last_join_launches, WDBX_OK;
+  if (name && !strcmp(name, "last_join_blocks")) return *value = ix->last_join_blocks, WDBX_OK;
+  if (name && !strcmp(name, "last_join_candidates")) return *value = ix->last_join_candidates, WDBX_OK;
+  if (name && !strcmp(name, "last_join_pairs")) return *value = ix->last_join_pairs, WDBX_OK;
+  if (name && !strcmp(name, "last_join_reruns")) return *value = ix->last_join_reruns, WDBX_OK;
   if (name && !strcmp(name, "last_moments_partials")) return *value = ix->last_moments_partials, WDBX_OK;
   if (name && !strcmp(name, "last_moments_tile_groups")) return *value = ix->last_moments_tile_groups, WDBX_OK;
   if (name && !strcmp(name, "last_moments_launches")) return *value = ix->last_moments_launches, WDBX_OK;

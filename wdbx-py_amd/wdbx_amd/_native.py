@@ -79,6 +79,7 @@ SIGNATURES = {
     "wdbx_index_assign": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
                                     C.POINTER(C.c_int32), _f32p, _f32p, _u64p]),
     "wdbx_index_knn_graph": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64, _i64p, _f32p]),
+    "wdbx_index_self_join": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint64, _u64p, _i64p, _f32p]),
     "wdbx_index_moments": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64, _f32p, _dblp, _u64p]),
     "wdbx_index_project": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.POINTER(C.c_uint32), C.c_uint64, _f32p]),
     "wdbx_index_search_row_lists": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _u64p, _u64p, C.c_int,
@@ -463,6 +464,33 @@ class NativeIndex:
         _check(self._lib.wdbx_index_knn_graph(self._h, int(k), None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint32)),
                                               0 if m is None else m.size, idx.ctypes.data_as(_i64p), score.ctypes.data_as(_f32p)))
         return idx, score
+
+    def self_join(self, threshold: float, mask=None, capacity: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Similarity self-join of the stored rows (``wdbx_index_self_join``): every pair of distinct rows ``mask`` allows
+        (uint32 words as in :meth:`search`) whose exact score reaches ``threshold`` (cosine / inner product: score >= t; L2:
+        squared distance <= t), each pair once, CSR by the lower row: ``(offsets int64[n + 1], rows int64[total], scores
+        f32[total])``, segment ``a`` holding the rows ``b > a`` as :meth:`range_search` orders them.  ``capacity=0`` counts
+        only (empty ``rows`` / ``scores``); None guesses and retries as :meth:`range_search` does.  ``offsets`` is sized here
+        from :meth:`size`: the caller keeps rows from being added between that and the call."""
+        n = self.size()
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint32)
+        offsets = np.zeros(n + 1, np.uint64)
+        cap = max(4096, getattr(self, "_join_hint", 0)) if capacity is None else int(capacity)
+        for _ in range(3):
+            rows = np.empty(cap, np.int64)
+            scores = np.empty(cap, np.float32)
+            _check(self._lib.wdbx_index_self_join(
+                self._h, float(threshold), None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint32)), 0 if m is None else m.size,
+                cap, offsets.ctypes.data_as(_u64p), rows.ctypes.data_as(_i64p) if cap else None,
+                scores.ctypes.data_as(_f32p) if cap else None))
+            total = int(offsets[n])
+            if capacity is not None:
+                return (offsets.astype(np.int64),) + ((rows[:total], scores[:total]) if total <= cap else (rows[:0], scores[:0]))
+            self._join_hint = total
+            if total <= cap:
+                return offsets.astype(np.int64), rows[:total], scores[:total]
+            cap = total
+        raise HipBackendError(-6, "self-join: the result kept growing between calls (concurrent adds)")
 
     def moments(self, center: bool = True, mask=None, want=("mean", "scatter")) -> dict:
         """Moments of the COUNTED rows (``wdbx_index_moments``: the rows ``mask`` allows whose norm is finite): ``"count"``

@@ -101,6 +101,9 @@ class WDBXConfig:
         # k-NN graph (``vector_knn_graph``): the most stored rows one call accepts -- every row is scored against every other,
         # so the default admits the corpus sizes the sweep serves in seconds and refuses an accidental n^2 beyond them
         "GRAPH_MAX_ROWS": 2000000,
+        # similarity self-join (``vector_similar_pairs``): the most stored rows one call accepts -- a guard against an
+        # accidental n^2, not a measurement
+        "JOIN_MAX_ROWS": 2000000,
     }
 
     def __init__(self, config_dict: Optional[Dict[str, Any]] = None, config_path: Optional[str] = None):

@@ -899,6 +899,38 @@ class HipFlatIndex(VectorIndex):
                 return None
             raise
 
+    # ---- similarity self-join (extension: every pair of stored rows above a threshold, no stored vector leaves the device) ----
+    def self_join(self, threshold: float, row_mask: Optional[np.ndarray] = None) -> Optional[List[Tuple[str, str, float]]]:
+        """Every pair of distinct stored vectors that still have an id (and that ``row_mask``, as ``row_mask_for`` returns it,
+        allows) whose score reaches ``threshold`` -- in the convention ``search`` returns scores in, as ``range_search`` --
+        each pair once: ``[(id_a, id_b, score), ...]`` ordered by the lower row, within a row best first.  One library call
+        (``wdbx_index_self_join``; its capacity retry as ``range_search``'s).  None for an empty index; errors are swallowed
+        (None) or raised as in ``search``.  The offsets are sized by the row count, which the library reads again under its
+        own lock: the call holds ``_ingest_lock`` from sizing them to the id mapping, as ``knn_graph`` does."""
+        try:
+            if self.next_index == 0:
+                return None
+            threshold = float(threshold)
+            if threshold != threshold:
+                raise ValueError("threshold is NaN")
+            cosine = self.metric == _native.METRIC_COSINE
+            words = None
+            if row_mask is not None:
+                words = row_mask if row_mask.dtype == np.uint32 else _native.pack_row_mask(row_mask)
+            with self._ingest_lock:
+                # (a removed row is NaN on the device: the library never pairs it, so it needs no mask)
+                offsets, rows, scores = self._native.self_join(threshold if cosine else -threshold, mask=words)
+                anchors = np.repeat(np.arange(len(offsets) - 1), np.diff(offsets))
+                names = {int(r): self._id_of(int(r)) for r in np.union1d(anchors, rows)}
+            if not cosine:
+                scores = -scores
+            return [(names[a], names[b], s) for a, b, s in zip(anchors.tolist(), rows.tolist(), scores.tolist())]
+        except Exception as e:
+            logger.error("Error in the self-join of HIP index: %s", e)
+            if self.swallow_errors:
+                return None
+            raise
+
     # ---- device PCA (extension: moments of the stored rows and their projection, no stored vector leaves the device) ----
     def moments(self, mask: Optional[np.ndarray] = None, center: bool = True) -> Optional[dict]:
         """``{"count", "mean", "scatter"}`` of the rows that ``mask`` (as ``row_mask_for`` returns it) allows and that are

@@ -1520,6 +1520,39 @@ class VectorStore:
         loop = asyncio.get_running_loop()
         return await loop.run_in_executor(self.thread_pool, lambda: self.knn_graph(k, filter_metadata=filter_metadata))
 
+    # ---- similarity self-join (extension: which stored vectors are near-duplicates of each other) ----
+    def similar_pairs(self, threshold: float, filter_metadata: Optional[Dict[str, Any]] = None,
+                      max_pairs: Optional[int] = None) -> List[Tuple[str, str, float]]:
+        """Every pair of distinct stored vectors (with ``filter_metadata``: of those it matches) whose similarity reaches
+        ``threshold`` (the convention ``search`` returns scores in), each pair once: ``[(id_a, id_b, score), ...]`` ordered by
+        the first vector's row, within it best first; ``max_pairs`` (None = all) cuts the list as ``search_range``'s
+        ``max_results`` does.  Deduplication before indexing, near-duplicate reports, the edges of a threshold graph.  One
+        library call (``wdbx_index_self_join``), no vector leaves the device; a filter always travels as the row mask.  More
+        than ``JOIN_MAX_ROWS`` stored rows is a ``ValueError``: the work grows with the square of the rows."""
+        if len(self.indices) != 1:
+            raise ValueError(
+                f"similar_pairs needs a store of one shard, this one has {len(self.indices)}: a cross-shard join needs anchors "
+                "from another device, which is a later variant")
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError("threshold is NaN")
+        index = self.indices[0]
+        cap = int(self.config.get("JOIN_MAX_ROWS", 2000000))
+        if index.next_index > cap:
+            raise ValueError(f"a self-join over {index.next_index} rows: JOIN_MAX_ROWS allows {cap}")
+        mask = self._row_masks(filter_metadata)[0] if filter_metadata else None
+        self.last_search_path = "threads"
+        pairs = index.self_join(threshold, row_mask=mask) or []
+        if max_pairs is not None:
+            pairs = pairs[: max(0, int(max_pairs))]
+        return pairs
+
+    async def similar_pairs_async(self, threshold: float, filter_metadata: Optional[Dict[str, Any]] = None,
+                                  max_pairs: Optional[int] = None) -> List[Tuple[str, str, float]]:
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(self.thread_pool, lambda: self.similar_pairs(
+            threshold, filter_metadata=filter_metadata, max_pairs=max_pairs))
+
     def cluster(self, k: int, max_iter: int = 25, tol: float = 1e-4, seed=None,
                 filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
         """k-means (Lloyd) over the stored vectors (with ``filter_metadata``: over those it matches).  The initial centres are

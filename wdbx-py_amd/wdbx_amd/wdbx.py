@@ -337,6 +337,18 @@ class WDBX:
                                      filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, List[Tuple[str, float]]]:
         return await self.vector_store.knn_graph_async(k, filter_metadata=filter_metadata)
 
+    def vector_similar_pairs(self, threshold: float, filter_metadata: Optional[Dict[str, Any]] = None,
+                             max_pairs: Optional[int] = None) -> List[Tuple[str, str, float]]:
+        """Extension: the similarity self-join of the stored vectors.  Every pair of distinct stored vectors (with
+        ``filter_metadata``: of those it matches) whose similarity reaches ``threshold``, each pair once:
+        ``[(id_a, id_b, score), ...]`` -- deduplication, near-duplicate reports, threshold graphs.  Exact fp32 scores; exact
+        duplicates are pairs like any other.  A store of one shard only (``VectorStore.similar_pairs`` says why)."""
+        return self.vector_store.similar_pairs(threshold, filter_metadata=filter_metadata, max_pairs=max_pairs)
+
+    async def vector_similar_pairs_async(self, threshold: float, filter_metadata: Optional[Dict[str, Any]] = None,
+                                         max_pairs: Optional[int] = None) -> List[Tuple[str, str, float]]:
+        return await self.vector_store.similar_pairs_async(threshold, filter_metadata=filter_metadata, max_pairs=max_pairs)
+
     def vector_pca(self, n_components: int, filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
         """Extension: principal components of the stored vectors (with ``filter_metadata``: of those it matches), mean and
         scatter matrix computed on the device: ``{"mean", "components", "explained_variance", "explained_variance_ratio",
