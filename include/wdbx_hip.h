@@ -248,6 +248,17 @@ int wdbx_index_search_matrix(wdbx_index* idx, const uint64_t* row_ids, uint64_t 
  *   row (get_option "last_assign_ambiguous") is decided by an exact pass over all centres.  A returned score is always
  *   exact_score's; the launch that computes the certain rows' scores is skipped when out_score is null.  get_option
  *   "last_assign_launches": kernel launches of the last call.
+ *   A second route with the same answers, bit for bit (set_option "assign_i8": -1 the library's choice, which is the fp32 tiles
+ *   until the int8 route has been found faster; 0 never; 1 wherever the handle has an i8 image of at most 1024 bytes per row;
+ *   any other value is WDBX_E_INVALID): the centres are quantised to signed bytes, a sweep over the group-scaled i8 shadow copy
+ *   on the int8 matrix cores (v_mfma_i32_16x16x64_i8) appends, per row, every centre within a rigorous quantisation margin of
+ *   the row's running best, and only those candidates are scored with exact_score (get_option "last_assign_pairs"; the candidate
+ *   buffer starts at "assign_pair_cap" pairs, 0 = four per row, and a sweep that passes it runs once more: "last_assign_sweeps";
+ *   more candidates than fit 2 GiB fail the call with WDBX_E_NOMEM).  "assign_i8_min_rows" (default 65536, at least 32768): rows
+ *   from which the library's choice may take this route; "assign_max_grid": workgroups of the sweep (0 = one per CU).  get_option
+ *   "last_assign_path": 1 the fp32 tiles, 2 the int8 sweep; "last_assign_why": why the int8 route was left (0 it ran, 1 off,
+ *   2 row length, 3 too few rows, 4 no room for the shadow copy).  "last_assign_ambiguous" is then the rows of groups the shadow
+ *   copy does not vouch for (an infinite element) or whose margin is not finite.
  *   WDBX_E_INVALID: n_centers outside [1, WDBX_MAX_CENTERS], centers null, all four outputs null, a mask shorter than
  *   ceil(rows / 32) words (checked under the handle's lock).  An empty index is WDBX_OK and launches nothing (sums and counts
  *   are zero).  A refused call leaves the handle usable.

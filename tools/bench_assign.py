@@ -9,7 +9,12 @@
     of 256 queries: config 4) -- 2 * rows * pitch * 256 over the device ms of its two launches, sample pass included, so the
     yardstick is understated by the sample pass's share.  The existing kernel is the yardstick, not the new one.
 
-    python tools/bench_assign.py [rows] [dim] [rounds] [--out FILE]
+    python tools/bench_assign.py [rows] [dim] [rounds] [--out FILE] [--route 0|1|both] [--metric 0|1]
+
+--route sets option assign_i8 for every call (0 = the fp32 tiles, 1 = the int8 candidate sweep; both = the two alternating per K
+in this one process; without it the library's choice).  A line's "route" is what ran (last_assign_path: 1 fp32 tiles, 2 int8
+sweep); on the int8 route tile_ms is the sweep (every sweep of the call), sums_ms also holds the exact pass over the candidates
+(merge launches), "pairs_per_row" the candidates scored per row and tile_tflops counts integer operations.
 
 One JSON line per K on stdout, appended to FILE (default profiles/assign/results.jsonl).  Nothing is a threshold."""
 import json
@@ -32,7 +37,9 @@ out_path = Path(flags.get("--out", ROOT / "profiles" / "assign" / "results.jsonl
 out_path.parent.mkdir(parents=True, exist_ok=True)
 PEAK = 157.3
 
-ix = _native.NativeIndex(dim, capacity_rows=rows)
+routes = {"0": (0,), "1": (1,), "both": (0, 1)}.get(flags.get("--route"), (None,))
+
+ix = _native.NativeIndex(dim, metric=int(flags.get("--metric", 0)), capacity_rows=rows)
 ix.fill_synthetic(0xC0FFEE, 0, rows, True)
 ix.profile(True)
 rng = np.random.default_rng(1)
@@ -55,12 +62,22 @@ yard = []
 for _ in range(rounds):
     ix.search(queries, 10, normalize_queries=True)
     yard.append(drain()["gemm_ms"])
+ix.set_option("gemm_bf16", 3)  # (the default again: the int8 route exists only where the batched path's i8 image does)
 yard_tflops = 2.0 * rows * ix.pitch * 256 / (median(yard) * 1e-3) / 1e12 if median(yard) > 0 else 0.0
 
-for k in (16, 256, 1024, 4096):
-    centers = rng.standard_normal((k, dim)).astype(np.float32)
+for k, route in ((k, r) for k in (16, 256, 1024, 4096) for r in routes):
+    centers = np.random.default_rng(k).standard_normal((k, dim)).astype(np.float32)
     want = ("center", "score", "sums", "counts")
-    ix.assign(centers, normalize=True, want=want)
+    if route is not None:
+        ix.set_option("assign_i8", route)
+    try:
+        ix.assign(centers, normalize=True, want=want)
+    except _native.HipBackendError as e:  # (an int8 sweep whose candidates would pass the buffer limit: recorded, not timed)
+        line = json.dumps({"rows": rows, "dim": dim, "centers": k, "assign_i8": route, "error": str(e)})
+        print(line, flush=True)
+        with open(out_path, "a") as f:
+            f.write(line + "\n")
+        continue
     drain()
     runs = []
     for _ in range(rounds):
@@ -69,10 +86,12 @@ for k in (16, 256, 1024, 4096):
         wall = (time.perf_counter() - t0) * 1e3
         runs.append({**drain(), "wall_ms": wall})
     blocks = ix.get_option("last_assign_center_blocks")
-    slots = blocks * (32 if k <= 32 else 64 if k <= 64 else 128)
+    path = ix.get_option("last_assign_path")
+    slots = blocks * ((128 if ix.dim <= 512 else 64) if path == 2 else 32 if k <= 32 else 64 if k <= 64 else 128)
     tile_ms = median([r["gemm_ms"] for r in runs])
-    tflops = 2.0 * rows * ix.pitch * slots / (tile_ms * 1e-3) / 1e12 if tile_ms > 0 else 0.0
-    rec = {"rows": rows, "dim": dim, "centers": k, "rounds": rounds, "center_blocks": blocks,
+    tflops = 2.0 * rows * (-(-dim // 128) * 128 if path == 2 else ix.pitch) * slots / (tile_ms * 1e-3) / 1e12 if tile_ms > 0 else 0.0
+    rec = {"rows": rows, "dim": dim, "centers": k, "rounds": rounds, "center_blocks": blocks, "route": path, "why": ix.get_option("last_assign_why"),
+           "pairs_per_row": ix.get_option("last_assign_pairs") / rows, "sweeps": ix.get_option("last_assign_sweeps"),
            "prep_ms": median([r["sample_ms"] for r in runs]), "tile_ms": tile_ms,
            "exact_ms": median([r["scan_ms"] for r in runs]), "sums_ms": median([r["merge_ms"] for r in runs]),
            "wall_ms": median([r["wall_ms"] for r in runs]), "launches": ix.get_option("last_assign_launches"),

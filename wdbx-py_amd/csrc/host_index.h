@@ -238,6 +238,15 @@ struct wdbx_index {
   DevBuf<char> d_asg_part{&bufs};
   DevBuf<char> d_asg_out{&bufs};
   int64_t last_assign_ambiguous = 0, last_assign_launches = 0, last_assign_center_blocks = 0, last_assign_partials = 0;
+  // ... its int8 route (host_assign8.h): the centres as signed bytes in fragment order; per centre {scale, squared norm} followed by
+  // the words {a_max, b_max}; the sweep's candidate pairs; the call's words {candidate count (two words), listed rows}; a key per row
+  DevBuf<int8_t> d_asg8_centres{&bufs};
+  DevBuf<float> d_asg8_par{&bufs};
+  DevBuf<u64> d_asg8_pairs{&bufs};
+  DevBuf<uint32_t> d_asg8_words{&bufs};
+  DevBuf<u64> d_asg8_keys{&bufs};
+  int last_assign_path = 0, last_assign_why = 0;
+  int64_t last_assign_pairs = 0, last_assign_sweeps = 0;
   // k-NN graph (wdbx_index_knn_graph, host_knn.h): one pass's candidate lists; their fill counters followed by the call's
   // {appended entries, largest eligible norm} words; every row's repair flag.  What the last call did.
   DevBuf<u64> d_knn_lists{&bufs};
@@ -282,7 +291,10 @@ struct wdbx_index {
           // self-join: workgroups of the sweep at most (0: one per CU); first size of the candidate buffer (0: the plan's);
           // eligible rows below which the exact route answers; rows above which the exact route is refused
           opt_join_max_grid = 0, opt_join_pair_cap = 0, opt_join_min_rows = JOIN_MIN_ROWS_DEFAULT,
-          opt_join_exact_max_rows = JOIN_EXACT_MAX_ROWS_DEFAULT;
+          opt_join_exact_max_rows = JOIN_EXACT_MAX_ROWS_DEFAULT,
+          // assignment's int8 route (host_assign8.h): -1 the library's choice, 0 never, 1 whenever the shape allows; rows from which
+          // the choice may take it; first size of the candidate buffer (0: the plan's); workgroups of the sweep at most (0: one per CU)
+          opt_assign_i8 = -1, opt_assign_i8_min_rows = ASSIGN8_MIN_ROWS_DEFAULT, opt_assign_pair_cap = 0, opt_assign_max_grid = 0;
 };
 
 struct DeviceGuard {

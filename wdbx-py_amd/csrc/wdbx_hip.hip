@@ -44,6 +44,10 @@
 //                           row against a few given vectors on the fp32 matrix cores, a top-1 per row folded in registers; the exact
 //                           pass over the rows the tile pass cannot vouch for, the winner's exact score, per-centre sums
 //   host_assign.h           that call's argument checks, centre blocks, LDS, grids, partial sums and the certainty bound's coefficients
+//   kernels_assign8.h       assign_i8_kernel: that call's int8 route (option assign_i8) -- the centres quantised per centre in shadow
+//                           copy G's fragment order, a candidate sweep on the int8 matrix cores with a running best per row in
+//                           registers, assign_pairs_kernel: the candidates' exact scores folded into one 64-bit key per row
+//   host_assign8.h          that route's cut and reason, centre blocks, LDS, grid, candidate capacity and the candidate inequality
 //   kernels_knn.h           knn_tile_kernel: the k-nearest-neighbour graph of the stored rows (wdbx_index_knn_graph) -- both operands
 //                           the bf16 shadow copy on the bf16 matrix cores, an anchor per accumulator column, a bounded candidate
 //                           list per anchor that tightens its own threshold; knn_exact_kernel: the lists' exact scores
@@ -136,6 +140,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_assign.h"  // (device-free as well: argument checks, centre blocks, LDS, grids, partials and bound of an assignment)
 #include "host_knn.h"  // (device-free as well: argument checks, tiles, list capacity, scratch, passes, route cut and margin of a k-NN graph)
 #include "host_join.h"  // (device-free as well: argument checks, anchor block, triangle, LDS, grid, route cut and tile test of a self-join)
+#include "host_assign8.h"  // (device-free as well: route, centre blocks, LDS, grid, capacity and inequality of an assignment's int8 sweep)
 #include "host_pca.h"  // (device-free as well: argument checks, tile groups, LDS, ranges, partials and grids of the moments and the projection)
 #include "host_multimask.h"  // (device-free as well: where the queries of a call with a mask per query sit in the tile blocks)
 #include "host_selection.h"  // (device-free as well: the sample, stride and capacities of the selection rounds)
@@ -190,6 +195,8 @@ static_assert(KNN_MAX_K == WDBX_MAX_GRAPH_K, "the plan's limit is the header's")
 #include "kernels_join.h"
 static_assert(JOIN_TILE_ROWS == G8_ROWS && JOIN_LDS_BLOCK_MAX == (size_t)G8_LDS_B_MAX && JOIN_GAMMA == RANGE_BATCH_GAMMA,
               "the join streams the int8 tiles' rows and charges the exact pass's rounding as the range block does");
+#include "kernels_assign8.h"
+static_assert(ASSIGN8_TILE_ROWS == G8_ROWS, "the sweep streams the int8 tiles' rows");
 #include "kernels_pca.h"
 static_assert(PCA_MAX_COMPONENTS == WDBX_MAX_COMPONENTS, "the plan's limit is the header's");
 #include "kernels_rowlists.h"
@@ -957,6 +964,120 @@ int wdbx_index_search_matrix(wdbx_index* ix, const uint64_t* row_ids, uint64_t n
 // decides every certain row and lists the others (a gemm launch), the listed count comes back, the exact pass scores the
 // certain rows' winners when scores are asked for and decides the listed rows (scan launches), the sums pass and its
 // combination follow when sums or counts are asked for (merge launches); one download of what was asked for.
+// The int8 route's first pass (kernels_assign8.h, host_assign8.h), behind assign_prep_kernel:
+// assign_quant_kernel (a sample launch) -> [the call's bad-row table] -> assign_i8_kernel (a gemm launch); the candidate and
+// listed counts come back; candidates past the buffer grow it to that count and the sweep runs once more -> the rows' keys
+// are cleared, assign_pairs_kernel folds the candidates' exact scores into them, assign_decode_kernel writes every row's
+// centre (merge launches).  The listed rows are left to the caller's exact pass, as on the fp32 route.
+static int assign_sweep8(wdbx_index* ix, const Assign8Plan& a8, const AssignBound& ab, int n_centers, uint32_t* listed, int64_t* launches) {
+  int rc;
+  const bool l2 = ix->metric == WDBX_METRIC_L2;
+  const uint32_t pitch8 = ix->pitch8g;
+  const assign_i8_fn fn = pick_assign_i8(ix->metric, a8.ct8);
+  if (!fn) return fail(WDBX_E_STATE, "no int8 assignment instance for blocks of %d centres", a8.block);
+  if ((rc = ix->d_asg8_centres.grow(a8.centre_bytes)) || (rc = ix->d_asg8_par.grow(a8.par_bytes)) ||
+      (rc = ix->d_asg8_words.grow(4 * sizeof(uint32_t))) || (rc = ix->d_asg8_keys.grow((size_t)ix->n * sizeof(u64))))
+    return rc;
+  uint32_t* const d_max = (uint32_t*)(ix->d_asg8_par + (size_t)2 * a8.slots);
+  HIP_TRY(hipMemsetAsync(d_max, 0, 2 * sizeof(uint32_t), ix->stream));
+  AssignQuantArgs qa = {};
+  qa.centres = ix->d_asg_centres;
+  qa.cnorm = ix->d_asg_aux;
+  qa.out8 = ix->d_asg8_centres;
+  qa.par = ix->d_asg8_par;
+  qa.max_bits = d_max;
+  qa.pitch = (uint32_t)ix->pitch;
+  qa.dim = (uint32_t)ix->dim;
+  qa.pitch8 = pitch8;
+  qa.n_centers = (uint32_t)n_centers;
+  qa.slots8 = (uint32_t)a8.slots;
+  if ((rc = launch_bracketed(ix, ix->sample_ev, assign_quant_kernel, dim3(a8.quant_grid), 0, qa))) return rc;
+  ++*launches;
+  const u64* gbad = ix->d_gbad8;
+  if (ix->active_mask) {  // this call's bad-row table: removed rows, rows past the end, rows the mask leaves out
+    const u64 ngroups = ix->d_groups8.bytes / sizeof(f4);
+    if ((rc = ix->d_call_bad.grow((size_t)ngroups * sizeof(u64)))) return rc;
+    hipLaunchKernelGGL(gbad_with_mask_kernel, dim3(gbad_with_mask_grid(ngroups), 1), dim3(256), 0, ix->stream, (const u64*)ix->d_gbad8,
+                       (const uint32_t*)ix->active_mask, (u64)((ix->n + 31) / 32), ngroups, ix->d_call_bad, (u64)0, (const int32_t*)nullptr);
+    HIP_TRY(hipGetLastError());
+    gbad = ix->d_call_bad;
+    ++*launches;
+  }
+  HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a8.lds));
+  uint32_t h_words[4];
+  u64 cap = a8.pair_cap, count = 0;
+  auto sweep = [&]() -> int {
+    int rc2 = ix->d_asg8_pairs.grow((size_t)cap * sizeof(u64));
+    if (rc2) return rc2;
+    HIP_TRY(hipMemsetAsync(ix->d_asg8_words, 0, 4 * sizeof(uint32_t), ix->stream));
+    Assign8Args a = {};
+    a.rows8 = ix->d_rows8g;
+    a.groups = ix->d_groups8;
+    a.gbad = gbad;
+    a.centres8 = ix->d_asg8_centres;
+    a.par = ix->d_asg8_par;
+    a.max_bits = d_max;
+    a.n_rows = (uint32_t)ix->n;
+    a.pitch8 = pitch8;
+    a.num_tiles = a8.tiles;
+    a.n_blocks = (uint32_t)a8.n_blocks;
+    a.gamma = ab.gamma;
+    a.under = ab.under;
+    a.pairs = ix->d_asg8_pairs;
+    a.pair_count = (unsigned long long*)ix->d_asg8_words.p;
+    a.pair_cap = cap;
+    a.list = ix->d_asg_list;
+    a.list_count = ix->d_asg8_words + 2;
+    if ((rc2 = record(ix->gemm_ev, ix->profile, ix->stream, true))) return rc2;
+    hipLaunchKernelGGL(fn, dim3(a8.grid), dim3(512), a8.lds, ix->stream, a);
+    HIP_TRY(hipGetLastError());
+    if ((rc2 = record(ix->gemm_ev, ix->profile, ix->stream, false))) return rc2;
+    HIP_TRY(hipMemcpyAsync(h_words, ix->d_asg8_words, sizeof h_words, hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    count = ((u64)h_words[1] << 32) | h_words[0];
+    ++*launches;
+    ++ix->last_assign_sweeps;
+    return WDBX_OK;
+  };
+  if ((rc = sweep())) return rc;
+  if (count > cap) {  // candidates past the buffer: grow to the exact count, the sweep again (it appends the same candidates)
+    if (!join_pairs_fit(count))
+      return fail(WDBX_E_NOMEM, "assign: %llu candidate pairs, whose buffer would pass 2 GiB (option assign_i8 = 0 takes the fp32 route)", count);
+    const u64 first = count;
+    cap = count;
+    if ((rc = sweep())) return rc;
+    if (count != first) return fail(WDBX_E_STATE, "assign: candidate count changed between two sweeps");
+  }
+  *listed = h_words[2];
+  ix->last_assign_pairs = (int64_t)count;
+  AssignPairsArgs pa = {};
+  pa.rows = (const f4*)ix->d_rows.p;
+  pa.centres = (const f4*)ix->d_asg_centres.p;
+  pa.pairs = ix->d_asg8_pairs;
+  pa.n_pairs = count;
+  pa.keys = ix->d_asg8_keys;
+  pa.out_center = ix->d_asg_center;
+  pa.n_rows = (uint32_t)ix->n;
+  pa.pitch4 = (uint32_t)ix->pitch / 4;
+  const uint32_t rgrid = (uint32_t)std::max<u64>(1, std::min<u64>((u64)ix->cu_count * 8, (ix->n + 255) / 256));
+  if ((rc = launch_bracketed(ix, ix->merge_ev, assign_clear_kernel, dim3(rgrid), 0, pa))) return rc;
+  ++*launches;
+  if (count) {
+    const uint32_t pgrid = (uint32_t)std::max<u64>(1, std::min<u64>((u64)ix->cu_count * 8, (count + 3) / 4));
+    const auto pfn = l2 ? assign_pairs_kernel<WDBX_METRIC_L2> : assign_pairs_kernel<WDBX_METRIC_COSINE>;
+    if ((rc = launch_bracketed(ix, ix->merge_ev, pfn, dim3(pgrid), 0, pa))) return rc;
+    ++*launches;
+  }
+  if ((rc = launch_bracketed(ix, ix->merge_ev, assign_decode_kernel, dim3(rgrid), 0, pa))) return rc;
+  ++*launches;
+  // a call that admitted very many candidates must not pin gigabytes for the handle's life
+  if (ix->d_asg8_pairs.bytes > ((size_t)256 << 20)) {
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    return ix->d_asg8_pairs.release();
+  }
+  return WDBX_OK;
+}
+
 int wdbx_index_assign(wdbx_index* ix, const float* centers, int n_centers, int normalize_centers, const uint32_t* mask_words,
                       uint64_t mask_word_count, int32_t* out_center, float* out_score, float* out_sums, uint64_t* out_counts) try {
   if (!ix) return fail(WDBX_E_INVALID, "null handle");
@@ -969,6 +1090,9 @@ int wdbx_index_assign(wdbx_index* ix, const float* centers, int n_centers, int n
   std::unique_lock<std::mutex> lk(ix->mu);
   const size_t sum_elems = (size_t)n_centers * ix->dim;
   ix->last_assign_ambiguous = ix->last_assign_launches = ix->last_assign_center_blocks = ix->last_assign_partials = 0;
+  ix->last_assign_path = ASSIGN_PATH_NONE;
+  ix->last_assign_why = ASSIGN8_WHY_NONE;
+  ix->last_assign_pairs = ix->last_assign_sweeps = 0;
   if (!ix->n) {  // (nothing stored: nothing assigned, nothing launched)
     if (out_sums) std::fill(out_sums, out_sums + sum_elems, 0.f);
     if (out_counts) std::fill(out_counts, out_counts + n_centers, (uint64_t)0);
@@ -1020,18 +1144,31 @@ int wdbx_index_assign(wdbx_index* ix, const float* centers, int n_centers, int n
   ta.num_tiles = ap.tiles;
   ta.gamma = ab.gamma;
   ta.under = ab.under;
-  const assign_tile_fn tile = pick_assign_tile(ix->metric, ap.mt);
-  if (!tile) return fail(WDBX_E_STATE, "no assignment tile instance for blocks of %d centres", ap.block);
-  if ((rc = launch_bracketed(ix, ix->gemm_ev, tile, dim3(ap.grid), ap.lds, ta))) return rc;
+  // the first pass: the int8 sweep with its exact pass over the candidates, or the fp32 tiles (host_assign8.h has the cut; shadow
+  // copy G is asked for only when everything else says sweep)
+  const uint32_t pitch8 = i8_tiles_shape_ok(ix) ? i8g_pitch(ix) : 0u;
+  const Assign8Why why8 = assign8_why(ix->opt_assign_i8, ix->n, (uint64_t)ix->opt_assign_i8_min_rows, pitch8);
+  const Assign8Plan a8 = assign8_plan(why8, why8 == ASSIGN8_WHY_NONE && prepare_i8g_shadow(ix), ix->n, n_centers, pitch8, ix->cu_count,
+                                      (uint64_t)ix->opt_assign_max_grid, (uint64_t)ix->opt_assign_pair_cap);
+  ix->last_assign_path = a8.path;
+  ix->last_assign_why = a8.why;
   uint32_t listed = 0;
-  HIP_TRY(hipMemcpyAsync(&listed, d_words + 1, sizeof listed, hipMemcpyDeviceToHost, ix->stream));
-  HIP_TRY(hipStreamSynchronize(ix->stream));
-  int64_t launches = 2;
+  int64_t launches = 1;
+  if (a8.path == ASSIGN_PATH_I8) {
+    if ((rc = assign_sweep8(ix, a8, ab, n_centers, &listed, &launches))) return rc;
+  } else {
+    const assign_tile_fn tile = pick_assign_tile(ix->metric, ap.mt);
+    if (!tile) return fail(WDBX_E_STATE, "no assignment tile instance for blocks of %d centres", ap.block);
+    if ((rc = launch_bracketed(ix, ix->gemm_ev, tile, dim3(ap.grid), ap.lds, ta))) return rc;
+    HIP_TRY(hipMemcpyAsync(&listed, d_words + 1, sizeof listed, hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+    ++launches;
+  }
   AssignExactArgs ea = {};
   ea.rows = ta.rows;
   ea.centres = ta.centres;
   ea.list = ix->d_asg_list;
-  ea.list_count = d_words + 1;
+  ea.list_count = a8.path == ASSIGN_PATH_I8 ? ix->d_asg8_words + 2 : d_words + 1;
   ea.out_center = ix->d_asg_center;
   ea.out_score = out_score ? (float*)ix->d_asg_score.p : nullptr;
   ea.n_rows = ta.n_rows;
@@ -1067,7 +1204,7 @@ int wdbx_index_assign(wdbx_index* ix, const float* centers, int n_centers, int n
   }
   ix->last_assign_ambiguous = listed;
   ix->last_assign_launches = launches;
-  ix->last_assign_center_blocks = ap.n_blocks;
+  ix->last_assign_center_blocks = a8.path == ASSIGN_PATH_I8 ? a8.n_blocks : ap.n_blocks;
   ix->last_assign_partials = want_sums ? ap.partials : 0;
   if (out_center) HIP_TRY(hipMemcpyAsync(out_center, ix->d_asg_center, (size_t)ix->n * sizeof(int32_t), hipMemcpyDeviceToHost, ix->stream));
   if (out_score) HIP_TRY(hipMemcpyAsync(out_score, ix->d_asg_score, (size_t)ix->n * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
@@ -3573,6 +3710,10 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"join_pair_cap", &wdbx_index::opt_join_pair_cap},
     {"join_min_rows", &wdbx_index::opt_join_min_rows},
     {"join_exact_max_rows", &wdbx_index::opt_join_exact_max_rows},
+    {"assign_i8", &wdbx_index::opt_assign_i8},
+    {"assign_i8_min_rows", &wdbx_index::opt_assign_i8_min_rows},
+    {"assign_pair_cap", &wdbx_index::opt_assign_pair_cap},
+    {"assign_max_grid", &wdbx_index::opt_assign_max_grid},
 };
 
 static int64_t* option_slot(wdbx_index* ix, const char* name) { return find_option(ix, kOptions, name); }
@@ -3613,6 +3754,15 @@ int wdbx_index_set_option(wdbx_index* ix, const char* name, int64_t value) try {
                 (u64)JOIN_PAIR_CAP_MIN, (u64)(JOIN_PAIR_BYTES_MAX / 8));
   if ((slot == &ix->opt_join_min_rows || slot == &ix->opt_join_exact_max_rows) && value < 0)
     return fail(WDBX_E_INVALID, "%s %lld: a row count", name, (long long)value);
+  if (slot == &ix->opt_assign_i8 && value != -1 && value != 0 && value != 1)
+    return fail(WDBX_E_INVALID, "assign_i8 %lld: -1 (the library's choice), 0 or 1", (long long)value);
+  if (slot == &ix->opt_assign_i8_min_rows && value < ASSIGN8_MIN_ROWS_FLOOR)
+    return fail(WDBX_E_INVALID, "assign_i8_min_rows %lld: at least %lld rows", (long long)value, (long long)ASSIGN8_MIN_ROWS_FLOOR);
+  if (slot == &ix->opt_assign_pair_cap && value != 0 && (value < (int64_t)JOIN_PAIR_CAP_MIN || value > (int64_t)(JOIN_PAIR_BYTES_MAX / 8)))
+    return fail(WDBX_E_INVALID, "assign_pair_cap %lld: 0 (the plan's sizing) or [%llu, %llu] candidate pairs", (long long)value,
+                (u64)JOIN_PAIR_CAP_MIN, (u64)(JOIN_PAIR_BYTES_MAX / 8));
+  if (slot == &ix->opt_assign_max_grid && (value < 0 || value > (1 << 20)))
+    return fail(WDBX_E_INVALID, "assign_max_grid %lld: 0 (the plan's choice) or a positive count", (long long)value);
   *slot = value;
   if (!strcmp(name, "group_bounds")) ix->gmax_valid = false;  // re-decide (and rebuild the group maxima) at the next batch
   return WDBX_OK;
@@ -3669,6 +3819,10 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "last_assign_launches")) return *value = ix->last_assign_launches, WDBX_OK;
   if (name && !strcmp(name, "last_assign_center_blocks")) return *value = ix->last_assign_center_blocks, WDBX_OK;
   if (name && !strcmp(name, "last_assign_partials")) return *value = ix->last_assign_partials, WDBX_OK;
+  if (name && !strcmp(name, "last_assign_path")) return *value = ix->last_assign_path, WDBX_OK;
+  if (name && !strcmp(name, "last_assign_why")) return *value = ix->last_assign_why, WDBX_OK;
+  if (name && !strcmp(name, "last_assign_pairs")) return *value = ix->last_assign_pairs, WDBX_OK;
+  if (name && !strcmp(name, "last_assign_sweeps")) return *value = ix->last_assign_sweeps, WDBX_OK;
   if (name && !strcmp(name, "last_knn_path")) return *value = ix->last_knn_path, WDBX_OK;
   if (name && !strcmp(name, "last_knn_repaired")) return *value = ix->last_knn_repaired, WDBX_OK;
   if (name && !strcmp(name, "last_knn_launches")) return *value = ix->last_knn_launches, WDBX_OK;

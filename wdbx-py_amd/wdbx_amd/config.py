@@ -76,6 +76,9 @@ class WDBXConfig:
         # library's default, 0 = the vector-ALU pass (8 vectors per row read), 1 = the matrix-core pass wherever it exists (up to
         # 128 vectors per row read, inner product / cosine only), -1 = by the round's size.  The answers are the same bits.
         "HIP_MULTIVECTOR_TILES": None,
+        # nearest-centre assignment: the route of its first pass (library option assign_i8): None / -1 = the library's choice,
+        # 0 = the fp32 tiles, 1 = the int8 candidate sweep wherever the handle has an i8 image.  The answers are the same bits.
+        "HIP_ASSIGN_I8": None,
         "HIP_GROUP_SEARCH": "auto",
         "HIP_AUTOSAVE_ROWS": 1000,
         "HIP_PERSIST_INDEX": True,

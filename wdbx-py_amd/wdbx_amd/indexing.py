@@ -176,6 +176,9 @@ class HipFlatIndex(VectorIndex):
         tiles = self.config.get("HIP_MULTIVECTOR_TILES")
         if tiles is not None:  # (None: the library's default route per round of a multi-vector search)
             self._native.set_option("multivector_tiles", int(tiles))
+        assign_i8 = self.config.get("HIP_ASSIGN_I8")
+        if assign_i8 is not None:  # (None: the library's choice between the fp32 tiles and the int8 sweep of an assignment)
+            self._native.set_option("assign_i8", int(assign_i8))
 
         self.id_to_index: Dict[str, int] = {}
         self.index_to_id: Dict[int, str] = {}
@@ -850,6 +853,9 @@ class HipFlatIndex(VectorIndex):
             # (a removed row is NaN on the device: the library gives it no centre, so it needs no mask)
             with self._ingest_lock:
                 out = self._native.assign(c, normalize=False, mask=mask, want=tuple(set(want) | {"center"}) if per_row else want)
+                if logger.isEnabledFor(10):  # (DEBUG: the two reads take the handle's lock, not worth it otherwise)
+                    logger.debug("assign: %d centres, path %d (1 fp32 tiles, 2 int8 sweep), %d candidate pairs", c.shape[0],
+                                 self._native.get_option("last_assign_path"), self._native.get_option("last_assign_pairs"))
                 if not per_row:
                     return out
                 rows = np.flatnonzero(out["center"] >= 0)
