@@ -308,6 +308,46 @@ int wdbx_index_knn_graph(wdbx_index* idx, int k,
                          const uint32_t* mask_words, uint64_t mask_word_count,   /* NULL / 0: every row */
                          int64_t* out_idx /* [rows, k] */, float* out_score /* [rows, k] */);
 
+/* ---- k-means++ seeding: D^2 sampling of initial centres among the stored rows ---- */
+/* Greedy k-means++ (scikit-learn's default initialisation) where the corpus lies: n_centers stored rows, each drawn with
+ * probability proportional to its distance from the nearest row chosen so far, the best of n_trials draws kept.  Blocking, host
+ * buffers.  Weights are INTEGERS and the random words are the caller's, so the result is a pure function of the stored rows and
+ * the draws: independent of summation order, the same from run to run, checkable by a plain loop.
+ *   Eligible: a row that is unmasked, not removed and whose squared norm, as the library computes it in fp32, is finite (no NaN
+ *   or infinite element, and no overflow).  Every other row weighs 0 for the whole call and is never picked.
+ *   The weight of row r against a centre row c: s = the exact score wdbx_index_search_rows returns for the STORED row c as the
+ *   query (normalize_queries = 0) and row r, bit for bit.  Cosine handle: t = min(max(1.0f - s, 0), 2), w = (uint32_t)(t * 2^30).
+ *   L2 handle: d = -s, w = (uint32_t)min(ldexpf(d, shift), 2^31 - 1); shift is fixed once per call as the largest one with
+ *   4 M 2^shift < 2^31 for M the largest eligible squared norm (within +-100; get_option "last_seed_shift").  Row c itself
+ *   weighs 0 against c by its row number, not by its score, and a chosen row weighs 0 from then on.
+ *   A draw picks a row over weights w[]: target = the high 64 bits of draw * W, W the sum of the weights; the pick is the lowest
+ *   row whose inclusive prefix sum exceeds the target.
+ *   Step 0: every eligible row weighs 1, draws[0] picks out_rows[0], and w(r) becomes the weight against that row;
+ *   out_potential[0] is their sum.  Step c >= 1: trial j < n_trials picks its candidate with draws[c * n_trials + j] over the
+ *   current w; the candidate's potential is P_j = sum over r of min(w(r), w_j(r)) as an exact 64-bit integer; the smallest P_j
+ *   wins, ties to the lowest j; w <- min(w, w_win), the winner weighs 0; out_rows[c] = the winner, out_potential[c] = P_win,
+ *   which is the next step's W.  When W is 0 (every eligible row coincides with a chosen one) the trials pick as if every
+ *   eligible unchosen row weighed 1; the potentials are still those of the true weights (0).
+ *   mask_words / mask_word_count as wdbx_index_search_masked_n (NULL / 0 = every row).
+ *   How: seed_eval_kernel reads the stored fp32 rows ONCE per step against the step's candidate rows, which each workgroup
+ *   fetches by row number from the corpus into LDS; exact_score's arithmetic per candidate, integer weights to a scratch of
+ *   n_trials words per row, potentials by integer shuffles, LDS and one integer atomic per workgroup and candidate.  The
+ *   candidates are resident in chunks of 64 KiB of LDS -- all 16 up to 1024 floats per row, fewer for longer rows, which costs more
+ *   reads of the rows per step (get_option "last_seed_passes"; set_option "seed_max_resident", 0 = the plan's choice, lowers the
+ *   chunk: more passes, the same answer).  seed_apply_kernel takes the winner and the minimum and sums the weights per block of
+ *   1024 rows; seed_pick_kernel (one workgroup) turns the draws into rows by prefix scans of those sums.  The whole loop of steps
+ *   is enqueued without a host synchronisation (get_option "last_seed_launches": 3 launches per step, more when chunked); the
+ *   draws go up once and the results come down once.
+ *   WDBX_E_INVALID: n_centers outside [1, WDBX_MAX_CENTERS], n_trials outside [1, WDBX_MAX_SEED_TRIALS], draws or out_rows null,
+ *   a mask shorter than ceil(rows / 32) words, fewer eligible rows than n_centers (an empty index therefore), a row longer than
+ *   a workgroup's LDS (40960 floats).  A refused call leaves the handle usable.
+ *   The call holds the handle's mutex to its end.  Nothing of the call stays valid in the handle. */
+#define WDBX_MAX_SEED_TRIALS 16
+int wdbx_index_seed_centers(wdbx_index* idx, int n_centers, int n_trials,
+                            const uint64_t* draws /* host [n_centers * n_trials], raw 64-bit random words */,
+                            const uint32_t* mask_words, uint64_t mask_word_count,   /* NULL / 0: every row */
+                            uint64_t* out_rows /* [n_centers] */, uint64_t* out_potential /* [n_centers] or NULL */);
+
 /* ---- similarity self-join: every pair of stored rows above a threshold ---- */
 /* Which stored vectors are near-duplicates of each other (deduplication before indexing, a near-duplicate report, the edges of a
  * threshold graph), answered where the corpus lies.  Blocking, host buffers.  rows is the handle's row count when the call runs.

@@ -254,6 +254,11 @@ struct wdbx_index {
   DevBuf<uint32_t> d_knn_flags{&bufs};
   int last_knn_path = 0;
   int64_t last_knn_repaired = 0, last_knn_launches = 0, last_knn_appends = 0, last_knn_passes = 0;
+  // k-means++ seeding (wdbx_index_seed_centers, host_seed.h): the call's state in one allocation (weights | dead bits | block sums |
+  // potentials | candidates | chosen rows | their potentials | draws) and every candidate's weights of a step.  What the last call did.
+  DevBuf<char> d_seed_state{&bufs};
+  DevBuf<uint32_t> d_seed_scratch{&bufs};
+  int64_t last_seed_launches = 0, last_seed_passes = 0, last_seed_shift = 0;
   // similarity self-join (wdbx_index_self_join, host_join.h): the sweep's candidate pairs; the exact pass's keys and their
   // anchors; the call's words {candidate count (two words), block ticket, result count}.  What the last call did.
   DevBuf<u64> d_join_pairs{&bufs};
@@ -288,6 +293,7 @@ struct wdbx_index {
           opt_mmr_scratch_mib = MMR_SCRATCH_MIB_MAX, opt_groups_segment_rows = GROUPS_SEGMENT_DEFAULT,
           opt_moments_tiles_per_group = 0, opt_moments_partials = 0,
           opt_knn_max_grid = 0,  // workgroups of one k-NN sweep launch at most (0: what is resident and fits the scratch)
+          opt_seed_max_resident = 0,  // candidates of one seeding eval launch at most (0: what fits 64 KiB of LDS)
           // self-join: workgroups of the sweep at most (0: one per CU); first size of the candidate buffer (0: the plan's);
           // eligible rows below which the exact route answers; rows above which the exact route is refused
           opt_join_max_grid = 0, opt_join_pair_cap = 0, opt_join_min_rows = JOIN_MIN_ROWS_DEFAULT,

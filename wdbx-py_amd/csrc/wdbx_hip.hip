@@ -52,6 +52,10 @@
 //                           the bf16 shadow copy on the bf16 matrix cores, an anchor per accumulator column, a bounded candidate
 //                           list per anchor that tightens its own threshold; knn_exact_kernel: the lists' exact scores
 //   host_knn.h              that call's argument checks, tiles, list capacity, LDS, scratch, passes, route cut and the margin
+//   kernels_seed.h          seed_eval_kernel: k-means++ seeding of the stored rows (wdbx_index_seed_centers) -- one read of the rows
+//                           against a step's candidate rows resident in LDS, exact_score's bits turned into integer weights and
+//                           64-bit potentials; seed_pick_kernel (the draws' rows by prefix scans), seed_apply_kernel (the winner)
+//   host_seed.h             that call's argument checks, shift, resident candidates, LDS, grids, scratch, the weight and the target
 //   kernels_join.h          join_tile_kernel: the similarity self-join of the stored rows (wdbx_index_self_join) -- both operands the
 //                           group-scaled i8 shadow copy on the int8 matrix cores, an anchor block resident in LDS as it lies in
 //                           HBM, the triangle of tiles, an integer compare per group pair; join_filter_kernel: the exact pass
@@ -139,6 +143,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #include "host_matrix.h"  // (device-free as well: route, anchor block, instance and rounds of a distance matrix among listed rows)
 #include "host_assign.h"  // (device-free as well: argument checks, centre blocks, LDS, grids, partials and bound of an assignment)
 #include "host_knn.h"  // (device-free as well: argument checks, tiles, list capacity, scratch, passes, route cut and margin of a k-NN graph)
+#include "host_seed.h"  // (device-free as well: argument checks, shift, resident candidates, LDS, grids, scratch, weight and target of a seeding)
 #include "host_join.h"  // (device-free as well: argument checks, anchor block, triangle, LDS, grid, route cut and tile test of a self-join)
 #include "host_assign8.h"  // (device-free as well: route, centre blocks, LDS, grid, capacity and inequality of an assignment's int8 sweep)
 #include "host_pca.h"  // (device-free as well: argument checks, tile groups, LDS, ranges, partials and grids of the moments and the projection)
@@ -192,6 +197,8 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 static_assert(ASSIGN_MAX_CENTERS == WDBX_MAX_CENTERS, "the plan's limit is the header's");
 #include "kernels_knn.h"
 static_assert(KNN_MAX_K == WDBX_MAX_GRAPH_K, "the plan's limit is the header's");
+#include "kernels_seed.h"
+static_assert(SEED_MAX_CENTERS == WDBX_MAX_CENTERS && SEED_MAX_TRIALS == WDBX_MAX_SEED_TRIALS, "the plan's limits are the header's");
 #include "kernels_join.h"
 static_assert(JOIN_TILE_ROWS == G8_ROWS && JOIN_LDS_BLOCK_MAX == (size_t)G8_LDS_B_MAX && JOIN_GAMMA == RANGE_BATCH_GAMMA,
               "the join streams the int8 tiles' rows and charges the exact pass's rounding as the range block does");
@@ -1386,6 +1393,98 @@ int wdbx_index_knn_graph(wdbx_index* ix, int k, const uint32_t* mask_words, uint
     if (e < ids32.size() && ids32[e] == r) ++e;
     else fill_empty(r);
   }
+  return WDBX_OK;
+} WDBX_CATCH
+
+// ---- k-means++ seeding of the stored rows (kernels_seed.h, host_seed.h) -----------------------
+// The whole call holds the handle's mutex.  Under it: the mask's length is checked, the row norms are brought up to date and
+// come back once -- the eligible rows are counted and their largest norm fixes the L2 shift on the host.  Then the draws go up
+// and every step is enqueued without a wait: the pick (a merge launch in the profile), the eval launches over the chunks of
+// resident candidates (scan launches), the apply (a merge launch).  One download of the chosen rows and their potentials.
+int wdbx_index_seed_centers(wdbx_index* ix, int n_centers, int n_trials, const uint64_t* draws, const uint32_t* mask_words,
+                            uint64_t mask_word_count, uint64_t* out_rows, uint64_t* out_potential) try {
+  if (!ix) return fail(WDBX_E_INVALID, "null handle");
+  switch (seed_validate(n_centers, n_trials, draws != nullptr, out_rows != nullptr)) {
+    case SEED_OK: break;
+    case SEED_BAD_CENTERS: return fail(WDBX_E_INVALID, "n_centers=%d outside [1, %d]", n_centers, WDBX_MAX_CENTERS);
+    case SEED_BAD_TRIALS: return fail(WDBX_E_INVALID, "n_trials=%d outside [1, %d]", n_trials, WDBX_MAX_SEED_TRIALS);
+    case SEED_NULL_DRAWS: return fail(WDBX_E_INVALID, "draws is null");
+    default: return fail(WDBX_E_INVALID, "out_rows is null");
+  }
+  std::unique_lock<std::mutex> lk(ix->mu);
+  ix->last_seed_launches = ix->last_seed_passes = ix->last_seed_shift = 0;
+  if (ix->n < (uint64_t)n_centers) return fail(WDBX_E_INVALID, "%d centres of %llu stored rows", n_centers, (u64)ix->n);
+  if (ix->n > MATRIX_MAX_IDS) return fail(WDBX_E_INVALID, "%llu rows in one call: at most 2^31 - 1", (u64)ix->n);
+  int rc;
+  if (mask_words && (rc = check_mask_words(ix->n, mask_word_count))) return rc;
+  DeviceGuard g(ix->device);
+  MaskScope scope(ix);
+  if (mask_words && (rc = scope.set(mask_words))) return rc;
+  if ((rc = ensure_row_norms(ix))) return rc;
+  const size_t n = (size_t)ix->n;
+  std::vector<float> cn(n);
+  HIP_TRY(hipMemcpyAsync(cn.data(), ix->d_cn, n * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  uint64_t eligible = 0;
+  float cmax = 0.f;
+  for (size_t r = 0; r < n; ++r) {
+    if ((mask_words && !((mask_words[r >> 5] >> (r & 31)) & 1u)) || !(std::fabs(cn[r]) < INFINITY)) continue;
+    ++eligible;
+    cmax = std::max(cmax, cn[r]);
+  }
+  if (eligible < (uint64_t)n_centers) return fail(WDBX_E_INVALID, "%d centres of %llu eligible rows", n_centers, (u64)eligible);
+  const SeedPlan sp = seed_plan(ix->n, n_centers, n_trials, (uint32_t)ix->pitch, ix->cu_count, (uint64_t)ix->opt_seed_max_resident);
+  if (!sp.fits) return fail(WDBX_E_INVALID, "a row of %d floats does not fit a workgroup's LDS", ix->pitch);
+  if ((rc = ix->d_seed_state.grow(sp.state_bytes)) || (rc = ix->d_seed_scratch.grow(sp.scratch_bytes))) return rc;
+  char* const st = ix->d_seed_state;
+  const size_t n_draws = (size_t)n_centers * n_trials;
+  HIP_TRY(hipMemcpyAsync(st + sp.off_draws, draws, n_draws * sizeof(uint64_t), hipMemcpyHostToDevice, ix->stream));
+  SeedArgs a = {};
+  a.rows = (const f4*)ix->d_rows.p;
+  a.cn = ix->d_cn;
+  a.mask = ix->active_mask;
+  a.w = (uint32_t*)st;
+  a.dead = (uint32_t*)(st + sp.off_dead);
+  a.sums = (u64*)(st + sp.off_sums);
+  a.pot = (u64*)(st + sp.off_pot);
+  a.cand = (uint32_t*)(st + sp.off_cand);
+  a.out_rows = (u64*)(st + sp.off_rows);
+  a.out_pot = (u64*)(st + sp.off_outpot);
+  a.draws = (const u64*)(st + sp.off_draws);
+  a.scratch = ix->d_seed_scratch;
+  a.n_rows = (uint32_t)ix->n;
+  a.pitch4 = (uint32_t)ix->pitch / 4;
+  a.blocks = sp.blocks;
+  a.span = sp.span;
+  a.n_trials = n_trials;
+  a.shift = seed_shift(cmax);
+  const int metric = ix->metric == WDBX_METRIC_L2 ? WDBX_METRIC_L2 : WDBX_METRIC_COSINE;
+  int64_t launches = 1;
+  if ((rc = launch_bracketed(ix, ix->merge_ev, seed_init_kernel, dim3(sp.apply_grid), 0, a))) return rc;
+  for (int c = 0; c < n_centers; ++c) {
+    a.step = c;
+    a.trials = c ? n_trials : 1;
+    if ((rc = launch_bracketed(ix, ix->merge_ev, seed_pick_kernel, dim3(1), 0, a))) return rc;
+    for (int j0 = 0; j0 < a.trials; j0 += (int)sp.resident) {
+      a.j0 = j0;
+      a.n_res = std::min((int)sp.resident, a.trials - j0);
+      const seed_eval_fn fn = pick_seed_eval(metric, seed_block((uint32_t)a.n_res));
+      if (!fn) return fail(WDBX_E_STATE, "no seeding instance for %d resident candidates", a.n_res);
+      if ((rc = launch_bracketed(ix, ix->scan_ev, fn, dim3(sp.eval_grid), seed_lds_bytes((uint32_t)a.n_res, (uint32_t)ix->pitch), a))) return rc;
+      ++launches;
+    }
+    if ((rc = launch_bracketed(ix, ix->merge_ev, seed_apply_kernel, dim3(sp.apply_grid), 0, a))) return rc;
+    launches += 2;
+  }
+  HIP_TRY(hipMemcpyAsync(out_rows, st + sp.off_rows, (size_t)n_centers * sizeof(uint64_t), hipMemcpyDeviceToHost, ix->stream));
+  if (out_potential)
+    HIP_TRY(hipMemcpyAsync(out_potential, st + sp.off_outpot, (size_t)n_centers * sizeof(uint64_t), hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  ix->last_seed_launches = launches;
+  ix->last_seed_passes = sp.passes;
+  ix->last_seed_shift = a.shift;
+  // (every candidate's weights of a large corpus do not stay on the handle: 16 trials of 100 M rows are 6.4 GB)
+  if (ix->d_seed_scratch.bytes > ((size_t)256 << 20)) return ix->d_seed_scratch.release();
   return WDBX_OK;
 } WDBX_CATCH
 
@@ -3706,6 +3805,7 @@ static const OptionDesc<wdbx_index> kOptions[] = {
     {"moments_tiles_per_group", &wdbx_index::opt_moments_tiles_per_group},
     {"moments_partials", &wdbx_index::opt_moments_partials},
     {"knn_max_grid", &wdbx_index::opt_knn_max_grid},
+    {"seed_max_resident", &wdbx_index::opt_seed_max_resident},
     {"join_max_grid", &wdbx_index::opt_join_max_grid},
     {"join_pair_cap", &wdbx_index::opt_join_pair_cap},
     {"join_min_rows", &wdbx_index::opt_join_min_rows},
@@ -3745,6 +3845,8 @@ int wdbx_index_set_option(wdbx_index* ix, const char* name, int64_t value) try {
     return fail(WDBX_E_INVALID, "scan_u42_share %lld: -1 (the default), 1, 2 or 4 queries per read", (long long)value);
   if (slot == &ix->opt_scan_u42_mfma && value != -1 && value != 0 && value != 1)
     return fail(WDBX_E_INVALID, "scan_u42_mfma %lld: -1 (the default), 0 or 1", (long long)value);
+  if (slot == &ix->opt_seed_max_resident && (value < 0 || value > SEED_MAX_TRIALS))
+    return fail(WDBX_E_INVALID, "seed_max_resident %lld: 0 (the plan's choice) or 1 .. %d candidates", (long long)value, SEED_MAX_TRIALS);
   if (slot == &ix->opt_knn_max_grid && (value < 0 || value > (1 << 20)))
     return fail(WDBX_E_INVALID, "knn_max_grid %lld: 0 (the plan's choice) or a positive count", (long long)value);
   if (slot == &ix->opt_join_max_grid && (value < 0 || value > (1 << 20)))
@@ -3828,6 +3930,9 @@ int wdbx_index_get_option(wdbx_index* ix, const char* name, int64_t* value) try 
   if (name && !strcmp(name, "last_knn_launches")) return *value = ix->last_knn_launches, WDBX_OK;
   if (name && !strcmp(name, "last_knn_appends")) return *value = ix->last_knn_appends, WDBX_OK;
   if (name && !strcmp(name, "last_knn_passes")) return *value = ix->last_knn_passes, WDBX_OK;
+  if (name && !strcmp(name, "last_seed_launches")) return *value = ix->last_seed_launches, WDBX_OK;
+  if (name && !strcmp(name, "last_seed_passes")) return *value = ix->last_seed_passes, WDBX_OK;
+  if (name && !strcmp(name, "last_seed_shift")) return *value = ix->last_seed_shift, WDBX_OK;
   if (name && !strcmp(name, "last_join_path")) return *value = ix->last_join_path, WDBX_OK;
   if (name && !strcmp(name, "last_join_launches")) return *value = ix->last_join_launches, WDBX_OK;
   if (name && !strcmp(name, "last_join_blocks")) return *value = ix->last_join_blocks, WDBX_OK;

@@ -23,6 +23,7 @@ MAX_CONTEXT_PAIRS = 32   # WDBX_MAX_CONTEXT_PAIRS: (positive, negative) pairs of
 MAX_GROUP_SIZE = 64      # WDBX_MAX_GROUP_SIZE: members one group of wdbx_index_search_groups holds
 MAX_CENTERS = 4096       # WDBX_MAX_CENTERS: centres of one wdbx_index_assign call
 MAX_GRAPH_K = 64         # WDBX_MAX_GRAPH_K: neighbours per row of one wdbx_index_knn_graph call
+MAX_SEED_TRIALS = 16     # WDBX_MAX_SEED_TRIALS: candidates per step of one wdbx_index_seed_centers call
 MAX_COMPONENTS = 32      # WDBX_MAX_COMPONENTS: basis vectors of one wdbx_index_project call
 UNIQUE_ID_BYTES = 128
 
@@ -79,6 +80,7 @@ SIGNATURES = {
     "wdbx_index_assign": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_uint64,
                                     C.POINTER(C.c_int32), _f32p, _f32p, _u64p]),
     "wdbx_index_knn_graph": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64, _i64p, _f32p]),
+    "wdbx_index_seed_centers": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _u64p, C.POINTER(C.c_uint32), C.c_uint64, _u64p, _u64p]),
     "wdbx_index_self_join": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint64, _u64p, _i64p, _f32p]),
     "wdbx_index_moments": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.c_uint64, _f32p, _dblp, _u64p]),
     "wdbx_index_project": (C.c_int, [C.c_void_p, _f32p, C.c_int, _f32p, C.POINTER(C.c_uint32), C.c_uint64, _f32p]),
@@ -464,6 +466,23 @@ class NativeIndex:
         _check(self._lib.wdbx_index_knn_graph(self._h, int(k), None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint32)),
                                               0 if m is None else m.size, idx.ctypes.data_as(_i64p), score.ctypes.data_as(_f32p)))
         return idx, score
+
+    def seed_centers(self, n_centers: int, draws, n_trials: int, mask=None) -> Tuple[np.ndarray, np.ndarray]:
+        """k-means++ seeding among the stored rows (``wdbx_index_seed_centers``): ``draws`` are ``n_centers * n_trials`` raw
+        64-bit random words (step ``c``, trial ``j`` at ``c * n_trials + j``), ``mask`` uint32 words as in :meth:`search`.
+        Returns ``(rows uint64[n_centers], potentials uint64[n_centers])``: the chosen rows in the order they were chosen and
+        the integer potential behind each -- a pure function of the stored rows and the draws."""
+        d = np.ascontiguousarray(draws, dtype=np.uint64).reshape(-1)
+        if d.size != max(int(n_centers), 0) * max(int(n_trials), 0):
+            raise ValueError(f"{d.size} draws for {n_centers} centres of {n_trials} trials")
+        rows = np.zeros(max(int(n_centers), 0), np.uint64)
+        potential = np.zeros_like(rows)
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint32)
+        # (the counts, the eligible rows and the mask's length are checked by the library, the last two under the handle's lock)
+        _check(self._lib.wdbx_index_seed_centers(self._h, int(n_centers), int(n_trials), d.ctypes.data_as(_u64p) if d.size else None,
+                                                 None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                 0 if m is None else m.size, rows.ctypes.data_as(_u64p), potential.ctypes.data_as(_u64p)))
+        return rows, potential
 
     def self_join(self, threshold: float, mask=None, capacity: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Similarity self-join of the stored rows (``wdbx_index_self_join``): every pair of distinct rows ``mask`` allows

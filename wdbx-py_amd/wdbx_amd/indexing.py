@@ -905,6 +905,26 @@ class HipFlatIndex(VectorIndex):
                 return None
             raise
 
+    # ---- k-means++ seeding (extension: D^2 sampling of initial centres, no stored vector leaves the device) ----
+    def seed_centers(self, n_centers: int, draws, n_trials: int, row_mask: Optional[np.ndarray] = None) -> Optional[dict]:
+        """``n_centers`` stored vectors that still have an id (and that ``row_mask``, as ``row_mask_for`` returns it, allows)
+        chosen by greedy k-means++ from the caller's ``n_centers * n_trials`` raw 64-bit ``draws``: one library call
+        (``wdbx_index_seed_centers``).  Returns ``{"rows", "ids", "potential"}`` in the order the rows were chosen.  None for
+        an empty index; errors are swallowed (None) or raised as in ``search``."""
+        try:
+            if self.next_index == 0:
+                return None
+            # (a removed row is NaN on the device: the library never picks it, so it needs no mask)
+            with self._ingest_lock:
+                rows, potential = self._native.seed_centers(int(n_centers), draws, int(n_trials), mask=row_mask)
+                ids = [self._id_of(int(r)) for r in rows]
+            return {"rows": rows, "ids": ids, "potential": potential}
+        except Exception as e:
+            logger.error("Error seeding centres on HIP index: %s", e)
+            if self.swallow_errors:
+                return None
+            raise
+
     # ---- similarity self-join (extension: every pair of stored rows above a threshold, no stored vector leaves the device) ----
     def self_join(self, threshold: float, row_mask: Optional[np.ndarray] = None) -> Optional[List[Tuple[str, str, float]]]:
         """Every pair of distinct stored vectors that still have an id (and that ``row_mask``, as ``row_mask_for`` returns it,

@@ -22,6 +22,7 @@ import array
 import asyncio
 import json
 import logging
+import math
 import os
 import pickle
 import random
@@ -1554,9 +1555,14 @@ class VectorStore:
             threshold, filter_metadata=filter_metadata, max_pairs=max_pairs))
 
     def cluster(self, k: int, max_iter: int = 25, tol: float = 1e-4, seed=None,
-                filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+                filter_metadata: Optional[Dict[str, Any]] = None, init: str = "random",
+                n_trials: Optional[int] = None) -> Dict[str, Any]:
         """k-means (Lloyd) over the stored vectors (with ``filter_metadata``: over those it matches).  The initial centres are
-        ``k`` distinct stored vectors drawn by ``random.Random(seed)`` from the sorted ids.  Every iteration is one ``assign``
+        ``k`` distinct stored vectors: with ``init="random"`` drawn by ``random.Random(seed)`` from the sorted ids; with
+        ``init="k-means++"`` chosen on the device by greedy D^2 sampling (``wdbx_index_seed_centers``) from ``k * n_trials``
+        words of ``random.Random(seed).getrandbits(64)``, ``n_trials`` candidates per centre (default ``2 + int(ln k)``, at
+        most 16) -- a store of one shard only: D^2 sampling across shards needs candidate vectors from another device, which
+        is a later variant.  Every iteration is one ``assign``
         per shard with per-centre sums and counts computed on the device; the shards' sums are added in shard order in
         float64 and the new centre is the mean -- re-normalised for cosine (spherical k-means); a centre without rows keeps
         its place.  It stops when no count changed and no centre moved by ``tol`` or more, or after ``max_iter`` iterations;
@@ -1576,7 +1582,25 @@ class VectorStore:
                 norms = np.linalg.norm(c64, axis=1)
                 c64 = np.where(norms[:, None] > 0, c64 / np.where(norms > 0, norms, 1.0)[:, None], c64)
             return c64.astype(np.float32)
-        centers = unit(np.array([self.get(vid)[0] for vid in random.Random(seed).sample(pool, k)], dtype=np.float64))
+        if init == "random":
+            chosen = random.Random(seed).sample(pool, k)
+        elif init == "k-means++":
+            if len(self.indices) != 1:
+                raise ValueError(
+                    f"init='k-means++' needs a store of one shard, this one has {len(self.indices)}: D^2 sampling across shards "
+                    "needs candidates from another device, which is a later variant")
+            trials = min(_native.MAX_SEED_TRIALS, 2 + int(math.log(k))) if n_trials is None else int(n_trials)
+            if not 1 <= trials <= _native.MAX_SEED_TRIALS:
+                raise ValueError(f"n_trials={n_trials}: between 1 and {_native.MAX_SEED_TRIALS} candidates per centre are served")
+            rng = random.Random(seed)
+            draws = np.array([rng.getrandbits(64) for _ in range(k * trials)], dtype=np.uint64)
+            picked = self.indices[0].seed_centers(k, draws, trials, row_mask=masks[0])
+            if not picked:
+                raise ValueError("k-means++ seeding returned nothing")
+            chosen = picked["ids"]
+        else:
+            raise ValueError(f"init={init!r}: 'random' or 'k-means++'")
+        centers = unit(np.array([self.get(vid)[0] for vid in chosen], dtype=np.float64))
         self.last_search_path = "threads"
         previous, iterations = None, 0
         for iterations in range(1, max(int(max_iter), 0) + 1):
@@ -1604,10 +1628,11 @@ class VectorStore:
                 "assignments": assignments}
 
     async def cluster_async(self, k: int, max_iter: int = 25, tol: float = 1e-4, seed=None,
-                            filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+                            filter_metadata: Optional[Dict[str, Any]] = None, init: str = "random",
+                            n_trials: Optional[int] = None) -> Dict[str, Any]:
         loop = asyncio.get_running_loop()
         return await loop.run_in_executor(self.thread_pool, lambda: self.cluster(
-            k, max_iter=max_iter, tol=tol, seed=seed, filter_metadata=filter_metadata))
+            k, max_iter=max_iter, tol=tol, seed=seed, filter_metadata=filter_metadata, init=init, n_trials=n_trials))
 
     # ---- PCA (extension: principal components of the stored vectors and their coordinates, computed on the device) ----
     @staticmethod

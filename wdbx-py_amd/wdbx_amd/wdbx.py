@@ -316,15 +316,21 @@ class WDBX:
         return await self.vector_store.assign_async(centers, filter_metadata=filter_metadata)
 
     def vector_cluster(self, k: int, max_iter: int = 25, tol: float = 1e-4, seed=None,
-                       filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+                       filter_metadata: Optional[Dict[str, Any]] = None, init: str = "random",
+                       n_trials: Optional[int] = None) -> Dict[str, Any]:
         """Extension: k-means over the stored vectors (spherical k-means for cosine), every iteration's assignment and
         per-centre sums computed on the device: ``{"centers", "counts", "inertia", "iterations", "assignments"}``
-        (``VectorStore.cluster`` states the steps).  The same result from run to run for a given ``seed``."""
-        return self.vector_store.cluster(k, max_iter=max_iter, tol=tol, seed=seed, filter_metadata=filter_metadata)
+        (``VectorStore.cluster`` states the steps).  ``init="random"`` starts from ``k`` stored vectors drawn uniformly,
+        ``init="k-means++"`` from greedy D^2 sampling on the device with ``n_trials`` candidates per centre (a store of one
+        shard).  The same result from run to run for a given ``seed``."""
+        return self.vector_store.cluster(k, max_iter=max_iter, tol=tol, seed=seed, filter_metadata=filter_metadata, init=init,
+                                         n_trials=n_trials)
 
     async def vector_cluster_async(self, k: int, max_iter: int = 25, tol: float = 1e-4, seed=None,
-                                   filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
-        return await self.vector_store.cluster_async(k, max_iter=max_iter, tol=tol, seed=seed, filter_metadata=filter_metadata)
+                                   filter_metadata: Optional[Dict[str, Any]] = None, init: str = "random",
+                                   n_trials: Optional[int] = None) -> Dict[str, Any]:
+        return await self.vector_store.cluster_async(k, max_iter=max_iter, tol=tol, seed=seed, filter_metadata=filter_metadata,
+                                                     init=init, n_trials=n_trials)
 
     def vector_knn_graph(self, k: int = 15, filter_metadata: Optional[Dict[str, Any]] = None) -> Dict[str, List[Tuple[str, float]]]:
         """Extension: the k-nearest-neighbour graph of the stored vectors.  For every stored vector (with ``filter_metadata``:
