@@ -5,10 +5,15 @@
 // unit query is about normal with mean -0.5 sum q and deviation 18.4, so tau = 61.7 and a4 = 17.3 let about 0.8 % of the (row,
 // query) pairs survive and 0.04 % become candidates, the shares of the headline corpus (profiles/u42_mfma/README.md).
 // The kernels are the library's own: this file includes the headers wdbx_hip.hip includes and owns no device code.
-// Prints one JSON line: ms per launch (mean and minimum of `launches` timed one by one with an event pair), survivors and
-// candidates per query of one launch.
+// A ROUND is `groups per round` groups of 16 queries over the same planes, issued as launches of `groups per launch` groups each
+// (grid.y), every launch with `grid.x` workgroups per group (0: the library's rule for one group, workgroups per CU x CUs).  The
+// defaults are one group, one launch.  `nt`: 1 takes the plane and {s, a4} with non-temporal loads, 0 with plain ones, -1 as the
+// library does (non-temporal for a launch of one group, plain for more).
+// Prints one JSON line: ms per round (mean, minimum and maximum of `launches` rounds timed one by one with an event pair),
+// survivors and candidates per query of one round.
 //   build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I wdbx-py_amd/csrc tools/probes/u42_mfma_floor.hip -o tools/probes/bin/u42_mfma_floor
 //   usage: u42_mfma_floor [rows = 10000000] [workgroups per CU = 2] [tau = inf] [a4 = 0] [launches = 20]
+//                         [groups per launch = 1] [grid.x = 0] [groups per round = groups per launch] [nt = -1]
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -53,13 +58,18 @@ int main(int argc, char** argv) {
   const float tau = argc > 3 ? (float)atof(argv[3]) : INFINITY;
   const float a4 = argc > 4 ? (float)atof(argv[4]) : 0.f;
   const int launches = argc > 5 ? atoi(argv[5]) : 20;
-  const uint32_t units = U42_MFMA_MAX_UNITS, nq = U42_MFMA_QUERIES, cap = 65536, qpitch = units * 32;
-  if (n_rows < 1 || n_rows > (1u << 24) || wgs < 1 || wgs > 8 || launches < 1 || launches > 1000) {
+  const uint32_t gpl = argc > 6 ? (uint32_t)atoi(argv[6]) : 1u;
+  const uint32_t grid_x = argc > 7 ? (uint32_t)atoi(argv[7]) : 0u;
+  const uint32_t gpr = argc > 8 ? (uint32_t)atoi(argv[8]) : gpl;
+  const int nt = argc > 9 ? atoi(argv[9]) : -1;
+  const uint32_t units = U42_MFMA_MAX_UNITS, nq = U42_MFMA_QUERIES * gpr, cap = 65536, qpitch = units * 32;
+  if (n_rows < 1 || n_rows > (1u << 24) || wgs < 1 || wgs > 8 || launches < 1 || launches > 1000 || gpl < 1 || gpl > 4 || gpr < gpl ||
+      gpr > 4 || gpr % gpl || grid_x > 65535 || nt < -1 || nt > 1) {
     fprintf(stderr, "arguments out of range\n");
     return 2;
   }
-  const scan42_mfma_fn fn = pick_scan42_mfma(units);
-  if (!fn) return 2;
+  if (!pick_scan42_mfma(units)) return 2;
+  const scan42_mfma_fn fn = (nt < 0 ? gpl == 1 : nt == 1) ? pick_scan42_mfma(units) : pick_scan42_mfma_round(units);
   const uint32_t tiles64 = (n_rows + 63) / 64, lpitch = u42_lpitch(units);
   const size_t h_dwords = (size_t)tiles64 * units * 256, l_dwords = (size_t)n_rows * lpitch;
 
@@ -96,7 +106,7 @@ int main(int argc, char** argv) {
   CK(hipMalloc(&d_cand, (size_t)nq * cap * sizeof(u64)));
   CK(hipMalloc(&d_count, nq * 4));
   CK(hipMalloc(&d_surv, nq * 4));
-  CK(hipMalloc(&d_qb, (size_t)u42_mfma_group_dwords(units) * 4));
+  CK(hipMalloc(&d_qb, (size_t)gpr * u42_mfma_group_dwords(units) * 4));
   CK(hipMalloc(&d_qc, nq * sizeof(U42QConst)));
   CK(hipMemcpy(d_h, h.data(), h_dwords * 4, hipMemcpyHostToDevice));
   CK(hipMemcpy(d_sa, sa.data(), (size_t)n_rows * sizeof(f2v), hipMemcpyHostToDevice));
@@ -116,39 +126,49 @@ int main(int argc, char** argv) {
   a.count = (uint32_t*)d_count;
   a.survivors = (uint32_t*)d_surv;
   a.cap = cap;
-  m.qb = (const uint32_t*)d_qb;
-  m.qc = (const U42QConst*)d_qc;
-  m.nq = nq;
   m.surv_p = nullptr;
   hipLaunchKernelGGL(u42_query_i16_kernel, dim3(nq), dim3(64), 0, nullptr, a.query, qpitch, units, nq, (uint32_t*)d_qb, (U42QConst*)d_qc);
   CK(hipGetLastError());
-  const uint32_t grid = scan_full_grid(tiles64, (uint32_t)prop.multiProcessorCount, wgs);
+  const uint32_t grid = grid_x ? grid_x : scan_full_grid(tiles64, (uint32_t)prop.multiProcessorCount, wgs);
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
-  double sum = 0, best = 1e30;
+  double sum = 0, best = 1e30, worst = 0;
   std::vector<uint32_t> count(nq), surv(nq);
   for (int it = -3; it < launches; ++it) {  // (three launches to warm up)
     CK(hipMemset(d_count, 0, nq * 4));
     CK(hipMemset(d_surv, 0, nq * 4));
     CK(hipEventRecord(e0, nullptr));
-    hipLaunchKernelGGL(fn, dim3(grid, 1), dim3(256), 0, nullptr, m);
-    CK(hipGetLastError());
+    for (uint32_t g = 0; g < gpr; g += gpl) {  // (launch g: groups g .. g + gpl - 1, addressed from its first query)
+      const uint32_t i = g * U42_MFMA_QUERIES;
+      Scan42MfmaArgs mm = m;
+      mm.a.query = (const float*)d_q + (size_t)i * qpitch;
+      mm.a.tau = (const float*)d_tau + i;
+      mm.a.cand = (u64*)d_cand + (size_t)i * cap;
+      mm.a.count = (uint32_t*)d_count + i;
+      mm.a.survivors = (uint32_t*)d_surv + i;
+      mm.qb = (const uint32_t*)d_qb + (size_t)g * u42_mfma_group_dwords(units);
+      mm.qc = (const U42QConst*)d_qc + i;
+      mm.nq = gpl * U42_MFMA_QUERIES;
+      hipLaunchKernelGGL(fn, dim3(grid, gpl), dim3(256), 0, nullptr, mm);
+      CK(hipGetLastError());
+    }
     CK(hipEventRecord(e1, nullptr));
     CK(hipEventSynchronize(e1));
     float ms = 0;
     CK(hipEventElapsedTime(&ms, e0, e1));
-    if (it >= 0) sum += ms, best = std::min(best, (double)ms);
+    if (it >= 0) sum += ms, best = std::min(best, (double)ms), worst = std::max(worst, (double)ms);
   }
   CK(hipMemcpy(count.data(), d_count, nq * 4, hipMemcpyDeviceToHost));
   CK(hipMemcpy(surv.data(), d_surv, nq * 4, hipMemcpyDeviceToHost));
   double cs = 0, ss = 0;
   for (uint32_t j = 0; j < nq; ++j) cs += count[j], ss += surv[j];
-  const double bytes = (double)h_dwords * 4 + (double)n_rows * 8;
-  printf("{\"probe\": \"u42_mfma_floor\", \"rows\": %u, \"units\": %u, \"wgs_per_cu\": %u, \"grid\": %u, \"tau\": %g, \"a4\": %g, "
-         "\"launches\": %d, \"ms_mean\": %.4f, \"ms_min\": %.4f, \"plane_bytes\": %.0f, \"plane_TBps_at_mean\": %.3f, "
+  const double bytes = (double)h_dwords * 4 + (double)n_rows * 8;  // (one read of the plane and {s, a4}; a round of A reads it gpr / gpl times)
+  printf("{\"probe\": \"u42_mfma_floor\", \"rows\": %u, \"units\": %u, \"wgs_per_cu\": %u, \"grid\": %u, \"groups_per_launch\": %u, "
+         "\"groups_per_round\": %u, \"nt\": %d, \"tau\": %g, \"a4\": %g, "
+         "\"launches\": %d, \"ms_mean\": %.4f, \"ms_min\": %.4f, \"ms_max\": %.4f, \"plane_bytes\": %.0f, \"plane_TBps_at_mean\": %.3f, "
          "\"survivors_per_query\": %.1f, \"candidates_per_query\": %.1f}\n",
-         n_rows, units, wgs, grid, (double)tau, (double)a4, launches, sum / launches, best, bytes, bytes / (sum / launches * 1e-3) / 1e12,
-         ss / nq, cs / nq);
+         n_rows, units, wgs, grid, gpl, gpr, nt, (double)tau, (double)a4, launches, sum / launches, best, worst, bytes,
+         bytes / (sum / launches * 1e-3) / 1e12, ss / nq, cs / nq);
   return 0;
 }

@@ -1410,6 +1410,7 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
   // scan_u42_share of 1, 2 or 4 keeps the VALU kernels for the whole round unless scan_u42_mfma = 1 asks for both.
   const scan42_mfma_fn fm = u42 && ix->opt_scan_u42_mfma != 0 && (ix->opt_scan_u42_mfma == 1 || ix->opt_scan_u42_share == -1)
                                 ? pick_scan42_mfma(units / 2) : nullptr;
+  const scan42_mfma_fn fm_round = fm ? pick_scan42_mfma_round(units / 2) : nullptr;  // (several groups in one launch: plain loads)
   int rc;
   // the plan (host_selection.h): sampled 256-row tiles of 4 groups of 64 rows each and the divisor of the u8 scan
   const SelectionSample s = selection_sample(ix->n, 256, 4, k, selection_div(ix->opt_gemm_sample_div, k, true));
@@ -1448,13 +1449,22 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
   const uint32_t grid_shared = scan_full_grid(tiles64, (uint32_t)ix->cu_count, wgs_of(2));
   // the matrix-core pass, 2000 steps, means of three: 1 -> 22579 q/s, 2 -> 30096, 3 -> 22514 (spreads 73 / 352 / 66;
   // profiles/u42_mfma_pipe/README.md).  Its 70.8 KiB of LDS let a CU hold two workgroups: a grid of three per CU runs them in two
-  // uneven rounds.  No load is in flight while a wave computes its tile, so the second wave of a SIMD is what overlaps
-  const uint32_t grid_mfma = scan_full_grid(tiles64, (uint32_t)ix->cu_count,
-                                            (uint32_t)std::max<int64_t>(1, std::min<int64_t>(ix->opt_scan8_wgs > 0 ? ix->opt_scan8_wgs : 2, 8)));
+  // uneven rounds.  No load is in flight while a wave computes its tile, so the second wave of a SIMD is what overlaps.
+  // grid_mfma is the grid of ONE group: a round's lone group, and every group under scan8_per_query = 1
+  const uint32_t wgs_mfma = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(ix->opt_scan8_wgs > 0 ? ix->opt_scan8_wgs : 2, 8));
+  const uint32_t grid_mfma = scan_full_grid(tiles64, (uint32_t)ix->cu_count, wgs_mfma);
   const uint32_t grid0 = scan_sample_grid(ngroups, (uint32_t)ix->cu_count);
   const size_t pitch4 = ix->pitch / 4;
   const Scan8Shape* sh = scan8_shape((uint32_t)ix->dim);
+  // one_grid: the VALU passes of a round (the u6 scan, the split planes' remainder) as one grid on small shards, as the u8 scan
   const bool one_grid = ix->opt_scan8_per_query == 0 || (ix->opt_scan8_per_query < 0 && sh && !shadow_over_1gib(ix->n, sh->pieces * 16));
+  // mfma_round: a round's matrix-core groups as ONE launch (grid.y = the groups) whose grid.x is cut so that all of them are
+  // resident at once (u42_mfma_round_grid, host_selection.h), on shards of every size: the groups walk the tiles together, the
+  // plane a group has read serves the others from cache, and the refine tail behind the last tile is paid once per round.
+  // 10 M x 12 units alone (profiles/u42_round/step0.md): four launches of (512, 1) 1.63 ms, one of (512, 4) -- four times the
+  // resident slots, so the groups still run one after another -- 1.62 ms, one of (128, 4) 1.43 ms, with plain loads 1.29 ms.
+  // scan8_per_query = 1 keeps a launch per group
+  const bool mfma_round = ix->opt_scan8_per_query != 1;
 
   for (int q0 = 0; q0 < nq; q0 += ROUND) {
     const int nv = std::min(ROUND, nq - q0);
@@ -1494,8 +1504,8 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
       b.cap = cap;
       // (the survivors are counted for the probes only: an atomic per 64 of them)
       HIP_TRY(hipMemsetAsync(ix->d_count42, 0, (size_t)nv * sizeof(uint32_t), ix->stream));
-      // the groups of 16 on the matrix cores (host_selection.h): the round's queries as 16-bit operands once, then one grid
-      // for all groups or a launch per group
+      // the groups of 16 on the matrix cores (host_selection.h): the round's queries as 16-bit operands once, then one launch
+      // that holds all groups (mfma_round) or a launch per group
       uint32_t taken = 0;
       if (fm) {
         const uint32_t ngm = u42_mfma_groups((uint32_t)nv, U42_MFMA_MIN_SHORT, &taken);
@@ -1506,7 +1516,7 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
           HIP_TRY(hipGetLastError());
           Scan42MfmaArgs mm = {};
           for (uint32_t g = 0; g < ngm;) {
-            const uint32_t run = one_grid ? ngm : 1, i = g * U42_MFMA_GROUP;
+            const uint32_t run = mfma_round ? ngm : 1, i = g * U42_MFMA_GROUP;
             mm.a = b;
             mm.a.query = qsrc + (size_t)i * ix->pitch;
             mm.a.tau = ix->d_tau + i;
@@ -1515,8 +1525,9 @@ static int enqueue_singles_u6(wdbx_index* ix, const float* d_queries, int nq, in
             mm.a.survivors = ix->d_count42 + i;
             mm.qb = ix->d_q16 + (size_t)g * u42_mfma_group_dwords(b.units);
             mm.qc = qc + i;
-            mm.nq = one_grid ? taken : std::min(taken - i, U42_MFMA_GROUP);
-            hipLaunchKernelGGL(fm, dim3(grid_mfma, run), dim3(256), 0, ix->stream, mm);
+            mm.nq = mfma_round ? taken : std::min(taken - i, U42_MFMA_GROUP);
+            const uint32_t gx = run > 1 ? u42_mfma_round_grid(tiles64, (uint32_t)ix->cu_count, wgs_mfma, run) : grid_mfma;
+            hipLaunchKernelGGL(run > 1 ? fm_round : fm, dim3(gx, run), dim3(256), 0, ix->stream, mm);
             HIP_TRY(hipGetLastError());
             g += run;
           }

@@ -107,6 +107,26 @@ static inline uint32_t u42_mfma_groups(uint32_t nv, uint32_t min_short, uint32_t
   return full + (tail ? 1u : 0u);
 }
 
+// grid.x of a full selection pass, four waves per workgroup: one wave-pass of rows (u8: 64 / L rows, u6 and u42: a 64-row tile)
+// per wave at a time and `wgs` workgroups per CU
+static inline uint32_t scan_full_grid(uint32_t wave_passes, uint32_t cus, uint32_t wgs) {
+  return std::min<uint32_t>((wave_passes + 3) / 4, cus * wgs);
+}
+
+// grid.x of ONE launch that holds all `groups` matrix-core groups of a round (grid.y) at the same time, so that they walk the
+// tiles together and the second to last reader of a tile finds it in a cache: groups * grid.x <= cus * wgs_per_cu keeps every
+// workgroup of every group resident at once (wgs_per_cu: what the kernel's LDS lets a CU hold).  The largest multiple of the XCD
+// count inside that, 8 at least (a device too small for it runs the groups' workgroups in turns, which is slower and nothing
+// else), never more than the tiles give work to.  With grid.x a multiple of 8 the workgroups (x, 0 .. groups - 1) have linear
+// ids that differ by multiples of 8 and the dispatcher's round-robin hands them to one XCD and its L2: a locality property of
+// that dispatcher, nothing a result depends on.  One group: the grid of a lone pass.
+constexpr uint32_t U42_XCDS = 8;
+static inline uint32_t u42_mfma_round_grid(uint32_t tiles64, uint32_t cus, uint32_t wgs_per_cu, uint32_t groups) {
+  if (groups <= 1) return scan_full_grid(tiles64, cus, wgs_per_cu);
+  const uint32_t fit = cus * wgs_per_cu / groups / U42_XCDS * U42_XCDS;
+  return std::min<uint32_t>((tiles64 + 3) / 4, std::max<uint32_t>(fit, U42_XCDS));
+}
+
 // "the u8 shadow exceeds 1 GiB": the size from which a pass per launch is the rule (u8_pitch bytes per row).  The u6 and u42
 // scans are taken by size above it, a round's passes go out as one grid up to it.
 static inline bool shadow_over_1gib(uint64_t n_rows, uint32_t u8_pitch) { return n_rows * u8_pitch > (1ull << 30); }

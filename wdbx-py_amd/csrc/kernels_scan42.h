@@ -315,6 +315,14 @@ __global__ __launch_bounds__(256) void scan_u42_kernel(Scan42Args a) {
 // column in one instruction of sixteen lanes at the wave's end.
 // LDS: 4 waves x (16 KiB lists + 1 KiB + 128 B stage + 512 B of {s, a4} + 64 B of counters) = 70.6 KiB per workgroup: two fit a CU and
 // two run, one wave of each per SIMD (the sweep in host_index.h).
+// A ROUND'S GROUPS IN ONE LAUNCH.  blockIdx.y is the group, and the host cuts grid.x so that all groups of a round are resident
+// at the same time (u42_mfma_round_grid, host_selection.h: groups * grid.x <= 2 * CUs, grid.x a multiple of the XCD count).  The
+// workgroups (x, 0 .. groups - 1) then start together and walk the same tiles, and that launch runs the instance that takes the
+// plane and {s, a4} with PLAIN loads so that what one group has fetched stays in L2 / the Infinity Cache for the others; a lone
+// group keeps the non-temporal loads (it streams, nothing is read twice).  No workgroup waits for another: the groups drift apart as their
+// refines differ, and how much of the plane the followers still find in a cache is a measurement (profiles/u42_round/README.md),
+// not a premise -- every workgroup reads what it needs from wherever it is.  Besides the reads, one launch pays the tail behind
+// the last tile (every wave gathers its sixteen lists, no plane load in flight) once per round instead of once per group.
 // ------------------------------------------------------------------------------------------------
 typedef int i4v __attribute__((ext_vector_type(4)));
 
@@ -530,8 +538,25 @@ __device__ __forceinline__ void u42_mfma_finish(const Scan42MfmaArgs& m, uint32_
   st.push(keep, make_key((w == w) ? w + 0.0f : INFINITY, g.row), c, a.cand + (size_t)q0 * a.cap, a.count + q0, a.cap, lane);
 }
 
-// NCH chunks of four units: units in (4 NCH - 4, 4 NCH]
-template <int NCH>
+// a tile's loads of one lane, all with one policy: the row's {s, a4} and, per 16-row block and chunk, 16 bytes of the plane
+template <int NCH, bool NT>
+__device__ __forceinline__ void u42_mfma_tile_loads(const uint32_t* p, const f2v* sap, uint32_t kg, uint32_t units, f2v& sa, u4v (&v)[4][NCH]) {
+  sa = NT ? __builtin_nontemporal_load(sap) : *sap;
+#pragma unroll
+  for (int rb = 0; rb < 4; ++rb)
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      if (c < NCH - 1 || 4 * c + kg < units) v[rb][c] = u42_load<NT>(p + (size_t)c * 1024 + rb * 64);
+      else v[rb][c] = u4v{0u, 0u, 0u, 0u};  // (a short last chunk: this lane group's unit is past the row)
+    }
+}
+
+// NCH chunks of four units: units in (4 NCH - 4, 4 NCH].  NT: how the plane and {s, a4} are loaded -- non-temporal for a lone
+// group (pick_scan42_mfma), plain for the launch that holds all groups of a round (pick_scan42_mfma_round: the groups are
+// resident together and walk the same tiles, so the line a group has read is what the next one should find in L2 or the Infinity
+// Cache).  Two instances, not a branch on gridDim.y around the loads: with the branch in the tile loop the lone pass measured
+// 3.7 % slower through the library (profiles/u42_round/README.md)
+template <int NCH, bool NT = true>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_u42_mfma_kernel(Scan42MfmaArgs m) {
   static_assert(4 * NCH <= (int)U42_MFMA_MAX_UNITS, "the refine gathers six 16-byte loads per record");
   static_assert(U42_MFMA_TRIGGER == 64 && U42_MFMA_LIST_CAP >= U42_MFMA_TRIGGER - 1 + 64, "a refine takes 64 entries, a tile adds up to 64");
@@ -565,15 +590,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const size_t tile_dw = (size_t)a.units * 256;
   for (uint32_t tile = blockIdx.x * 4 + wave; tile < tiles; tile += gridDim.x * 4) {
     const uint32_t* p = a.hcodes + tile * tile_dw + kg * 256 + col * 4;
-    const f2v sa = __builtin_nontemporal_load(a.sa4 + min(tile * 64 + (uint32_t)lane, a.n_rows - 1));
+    const f2v* sap = a.sa4 + min(tile * 64 + (uint32_t)lane, a.n_rows - 1);
+    f2v sa;
     u4v v[4][NCH];
-#pragma unroll
-    for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        if (c < NCH - 1 || 4 * c + kg < a.units) v[rb][c] = u42_load<true>(p + (size_t)c * 1024 + rb * 64);
-        else v[rb][c] = u4v{0u, 0u, 0u, 0u};  // (a short last chunk: this lane group's unit is past the row)
-      }
+    u42_mfma_tile_loads<NCH, NT>(p, sap, kg, a.units, sa, v);
     u42_wave_sync();  // (the last tile's reads of sas are done)
     sas[wave][lane] = sa;
     u42_wave_sync();
@@ -648,7 +668,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 typedef void (*scan42_mfma_fn)(Scan42MfmaArgs);
-static scan42_mfma_fn pick_scan42_mfma(uint32_t units) { return u42_mfma_has_instance(units) ? scan_u42_mfma_kernel<3> : nullptr; }
+static scan42_mfma_fn pick_scan42_mfma(uint32_t units) { return u42_mfma_has_instance(units) ? scan_u42_mfma_kernel<3, true> : nullptr; }
+// ... and the instance for a launch of several groups that are resident together (plain loads)
+static scan42_mfma_fn pick_scan42_mfma_round(uint32_t units) { return u42_mfma_has_instance(units) ? scan_u42_mfma_kernel<3, false> : nullptr; }
 
 // rows [r0, n) fp32 -> h plane, {s, a4} and l records, one wave per row, one lane per 16 elements (half a unit): the walk of
 // rows_to_u6_kernel, so that a6 is its a bit for bit.  units = 32-element units (the pitch is a multiple of 32).

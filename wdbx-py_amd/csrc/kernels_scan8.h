@@ -384,11 +384,9 @@ static const Scan8Shape* scan8_shape(uint32_t dim) {
 
 // grid.x of a selection pass (u8 and u6 alike), four waves per workgroup: the sample pass takes one sampled 64-row group per
 // wave at a time and at most 4 workgroups per CU; the full pass one wave-pass of rows (u8: 64 / L rows, u6: a 64-row tile)
-// per wave at a time and `wgs` workgroups per CU
+// per wave at a time and `wgs` workgroups per CU (scan_full_grid: host_selection.h, device-free, next to the round's grid rule)
+#include "host_selection.h"
 static inline uint32_t scan_sample_grid(uint32_t ngroups, uint32_t cus) { return std::min<uint32_t>((ngroups + 3) / 4, cus * 4); }
-static inline uint32_t scan_full_grid(uint32_t wave_passes, uint32_t cus, uint32_t wgs) {
-  return std::min<uint32_t>((wave_passes + 3) / 4, cus * wgs);
-}
 
 typedef void (*scan8_fn)(Scan8Args);
 template <int PHASE, int METRIC>
